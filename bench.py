@@ -39,6 +39,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6.3 TB/s is the measured copy ceiling
+DUMP_BYTES = 32 * 2**20  # --dump-outputs writes at most this much, all ranks together
 
 
 def parse():
@@ -65,7 +66,13 @@ def parse():
     ap.add_argument("--extra-seconds", type=float, default=90.0,
                     help="N=1 only: time budget of the secondary measurements appended as \"extra\" (tools/secondary.py: "
                          "joiner TFLOP/s, loss-block step, CTC, greedy, beam, hot-word); 0 skips them")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32): the "
+                         "per-utterance costs and the gradient, whole if it fits 32 MiB, else a fixed seeded sample of it")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch(args) -> int:
@@ -239,6 +246,8 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs:                            # before anything below touches the gradient buffer
+        dump_outputs(args.dump_outputs, costs, grads, rank, world)
 
     # same-process calibration outside the timed region: the runtime's own device-to-device copy of the
     # logits-sized buffer (one read + one write per byte, like the gradient pass).  MI355X parts differ
@@ -336,6 +345,23 @@ def main():
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, costs, grads, rank, world):
+    """Write the last timed step's costs [B] and gradient [B,T,U+1,V] as float32 .npy files (suffix _rank<r> when
+    world > 1).  A gradient larger than this rank's share of DUMP_BYTES is written as grads_sample: the elements at
+    sorted flat indices drawn from a generator seeded by the rank, so the same arguments always pick the same ones."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(out_dir, f"costs{sfx}.npy"), costs.cpu().numpy())
+    fit = (DUMP_BYTES // world - 4 * costs.numel() - 2 * 128) // 4          # elements left after costs and two headers
+    flat = grads.view(-1)
+    if flat.numel() <= fit:
+        np.save(os.path.join(out_dir, f"grads{sfx}.npy"), grads.cpu().numpy())
+        return
+    idx = torch.randint(flat.numel(), (fit,), generator=torch.Generator().manual_seed(20260 + rank)).sort().values
+    np.save(os.path.join(out_dir, f"grads_sample{sfx}.npy"), flat[idx.to(flat.device)].cpu().numpy())
 
 
 def host_cores() -> int:

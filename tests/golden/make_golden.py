@@ -31,6 +31,7 @@ for modules that are absent from the image -- `typeguard`, used only for
                                       the reference Transducer class  -> asr_surface.npz
   wenet/transformer/context_bias.py   ContextBias (the real module) driven by
   wenet/transducer/search/greedy_search.py  basic_greedy_search_both -> greedy_both_real_*.npz
+  wenet/bin/recognize.py              the --mode branches and the model methods they call -> recognize_modes.npz
 torchaudio.functional.rnnt_loss cannot be imported (torchaudio is absent), so no
 RNN-T-loss fixture comes from the reference; rnnt_kat.npz holds the public
 known-answer vector instead.
@@ -960,6 +961,19 @@ def gen_common():
          log_add_all_inf=np.array(log_add([-float("inf"), -float("inf")])))
 
 
+def gen_recognize_modes():
+    """wenet/bin/recognize.py:259-362 as data: each `args.mode` branch and the model method it calls, plus every
+    method called on the model anywhere in the script (only names are stored, no source text)."""
+    import re
+    with open(os.path.join(REF, "wenet/bin/recognize.py")) as f:
+        text = f.read()
+    branches = re.split(r"args\.mode == '([a-z_]+)'", text)[1:]
+    modes = branches[0::2]
+    methods = [re.search(r"model\.([a-z_]+)\(", body).group(1) for body in branches[1::2]]
+    called = sorted(set(re.findall(r"model\.([a-z_]+)\(", text)) - {"eval", "to", "load_state_dict"})
+    save("recognize_modes", modes=np.array(modes), methods=np.array(methods), called=np.array(called))
+
+
 def gen_rnnt_kat():
     # Public warp-transducer / torchaudio unit-test vector (SURVEY.md App. A.5); not produced by the reference.
     sys.path.insert(0, os.path.dirname(HERE))
@@ -993,3 +1007,4 @@ if __name__ == "__main__":
     gen_greedy_both_real()
     gen_transducer_wrappers()
     gen_asr_surface()
+    gen_recognize_modes()

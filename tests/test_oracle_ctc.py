@@ -1,6 +1,6 @@
 """Pins the CPU oracle for the fused log-softmax + CTC loss (oracle/ctc_oracle.c)
 against torch.nn.CTCLoss run live, exactly as the reference calls it
-(/root/reference/wenet/transformer/ctc.py:57-63: log_softmax(2) on (T,B,V),
+(wenet/transformer/ctc.py:57-63: log_softmax(2) on (T,B,V),
 CTCLoss(reduction='sum'), blank=0, zero_infinity=False)."""
 import numpy as np
 import pytest

@@ -1,7 +1,7 @@
 """Pins the CPU oracle for the RNN-T loss (oracle/rnnt_oracle.c).
 
 The reference holds no fixture for torchaudio.functional.rnnt_loss
-(/root/reference/wenet/transducer/transducer.py:142-147), so the oracle is
+(wenet/transducer/transducer.py:142-147), so the oracle is
 pinned by: the public warp-transducer/torchaudio known-answer vector
 (SURVEY.md App. A.5), brute-force enumeration of all alignments, and an
 independent float64 autograd of the alpha recursion.

@@ -340,3 +340,45 @@ def test_full_baseline_shape_properties():
         np.testing.assert_allclose(got, g32[0], rtol=2e-2, atol=3e-5)
         del g32
     print("full-shape gradient vs f64 oracle, worst |err| / (1e-5 + 1e-4 |ref|):", worst)
+
+
+def _bench_dump(tmp_path, name, *shape_args):
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    out = tmp_path / name
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--cpu-sample", "0", "--extra-seconds", "0", "--dump-outputs", str(out), *shape_args],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    files = {p.name: np.load(p) for p in out.iterdir()}
+    assert all(a.dtype == np.float32 for a in files.values())
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 * 10**6
+    return files
+
+
+def test_bench_dump_outputs_are_the_last_step_and_repeat(tmp_path):
+    """bench.py --dump-outputs: a small shape is written whole and equals the float64 oracle on bench.py's own seeded
+    inputs; a gradient above the size cap is written as a seeded sample that is identical from run to run."""
+    B, T, U, V = 3, 12, 5, 20
+    d = _bench_dump(tmp_path, "small", "--B", str(B), "--T", str(T), "--U", str(U), "--V", str(V))
+    assert sorted(d) == ["costs.npy", "grads.npy"] and d["grads.npy"].shape == (B, T, U + 1, V)
+    gen = torch.Generator(device=DEV)                   # bench.py's inputs: same seed, same draws, same order
+    gen.manual_seed(20260)
+    x = torch.empty(B, T, U + 1, V, dtype=torch.float32, device=DEV)
+    for b in range(B):
+        x[b].normal_(generator=gen)
+    y = torch.randint(1, V, (B, U), dtype=torch.int32, device=DEV, generator=gen)
+    c64, g64 = oracle.rnnt_loss_f64(x.cpu().numpy(), y.cpu().numpy(), np.full(B, T, np.int32), np.full(B, U, np.int32))
+    np.testing.assert_allclose(d["costs.npy"], c64, rtol=1e-5)
+    np.testing.assert_allclose(d["grads.npy"], g64 / B, rtol=1e-4, atol=1e-6)
+    big = ("--B", "4", "--T", "200", "--U", "50", "--V", "500")       # 82 MB of gradient
+    d1, d2 = _bench_dump(tmp_path, "big1", *big), _bench_dump(tmp_path, "big2", *big)
+    assert sorted(d1) == ["costs.npy", "grads_sample.npy"] and d1["grads_sample.npy"].size > 10**6
+    assert all(np.array_equal(d1[k], d2[k]) for k in d1)
+    assert np.abs(d1["grads_sample.npy"]).max() > 0
