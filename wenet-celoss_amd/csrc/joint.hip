@@ -553,7 +553,8 @@ __global__ __launch_bounds__(512) void joint_bwd_dw_kernel(
     auto mfma_set = [&](const float (&a)[2][kDwPF], const float (&bb)[4][kDwPF], const float (&sc)[kDwPF]) {
 #pragma unroll
         for (int q = 0; q < kDwPF; ++q) {
-            const float a0 = a[0][q] * sc[q], a1 = a[1][q] * sc[q];
+            // selected, not scaled: 0 * NaN would carry a non-finite padded gradient into every column
+            const float a0 = sc[q] != 0.f ? a[0][q] : 0.f, a1 = sc[q] != 0.f ? a[1][q] : 0.f;
             bsum[0] += a0;
             bsum[1] += a1;
 #pragma unroll

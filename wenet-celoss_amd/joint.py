@@ -144,8 +144,16 @@ def _amp_backward_library(lib, gout, ep, pp, w, llens, tlens, need_w, need_b, go
     d_ep = dz.sum(dim=2)
     d_pp = dz.sum(dim=1)
     d_w = d_b = None
-    if need_w:                                      # H is zero in padded cells: they contribute nothing
-        d_w = torch.mm(g2.t(), hb, out_dtype=torch.float32)
+    if need_w:                                      # H is zero in padded cells: they contribute nothing ...
+        gw = g2
+        if not gout_zero_in_padding and llens is not None:
+            # ... unless the gradient there is not finite (0 * NaN = NaN would poison every column of d_w): padded rows
+            # are selected to zero, as the kernels' cell mask does -- one pass over the gradient, only when the caller
+            # does not guarantee zeros there (the RNN-T loss does: no pass on the training path)
+            tt = torch.arange(T, device=dev)[None, :, None] < llens[:, None, None]
+            uu = torch.arange(U1, device=dev)[None, None, :] <= tlens[:, None, None]
+            gw = torch.where((tt & uu).view(M, 1), g2, torch.zeros((), dtype=dt, device=dev))
+        d_w = torch.mm(gw.t(), hb, out_dtype=torch.float32)
     if need_b:                                      # (as one more column of that GEMM, N = J + 8, the library padded to
         d_b = torch.empty(V, dtype=torch.float32, device=dev)       # its next tile: 23.3 ms against 15.8 + 3)
         wsb = lib.wr_joint_db_workspace_bytes(B, T, U1, V)
