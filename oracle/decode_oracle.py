@@ -470,3 +470,239 @@ def forced_align(ctc_probs, y, blank_id=0):
     for t in range(T - 2, -1, -1):
         seq[t] = path[t + 1, seq[t + 1]]
     return [ext[s] for s in seq]
+
+
+# ------------------------------------------- float64 single steps (the guided walk of tests/decode_follow.py) --
+# The state of both transducer searches at a frame boundary is a function of what they export: a prefix-beam survivor
+# is (hyp, score) and its predictor state follows from the hyp (prefix_beam_search.py:73-146: `cache` is always the
+# state of the LSTM that consumed hyp[:-1], and the step at the next frame feeds hyp[-1]); a greedy stream's state is
+# its token list ('greedy_search copy.py':14-63).  The functions below recompute ONE frame in float64 from such a
+# state, together with a first-order bound on how far an fp32 evaluation of the same step may land from it:
+#   * every contraction y = W x + b of K terms in fp32 (any summation order, FMA or not) is within
+#     gamma(K) * (|W| |x| + |b|) of the exact result, gamma(K) = K u / (1 - K u), u = 2^-24;
+#   * the terms of the contractions that feed a row are added along the path as each one's largest element (an
+#     elementwise function passes an error on times |f'|: sigmoid' <= 1/4, tanh' <= 1), NOT re-multiplied by the |W|
+#     of every later contraction: that worst case (all roundings aligned with the signs of W) grows ~8x per 256-wide
+#     layer and bounds nothing an implementation does;
+#   * every fp32 transcendental (exp, log, tanh, sigmoid) adds TU relative to its result, every fp32 + or * adds u;
+#   * log-softmax: the log-sum-exp is 1-Lipschitz in the max norm, so an error dz in the logits reaches a log-prob as
+#     at most dz_v + max(dz) (2x the row's largest error) plus the roundings of the exp / sum / log chain;
+#   * the mixture log(tw e^a + cw e^c) weighs the errors of a and c by their shares of the sum (each <= 1).
+# The analysis covers ONE step: the contractions and activations of the predictor step that produces the row (from
+# the parent's state), the joiner and the mixture.  The error a search carries in its fp32 LSTM state from earlier
+# steps is not added: propagated with absolute values through the recurrence (|W_hh| times the gate slopes, ~8 per
+# step for a 256-wide layer) such a bound grows geometrically with the hypothesis length and says nothing, while the
+# actual recurrence damps it (forget gates < 1).  The guided walk reports its worst |error| / bound so that a history
+# term that mattered would show up as a ratio near 1, not be absorbed.
+U32 = 2.0 ** -24
+TU = 4 * 2.0 ** -23                 # fp32 transcendental (exp, log, tanh, expf-based sigmoid): within 4 ulp
+
+
+def gamma(k):
+    return k * U32 / (1.0 - k * U32)
+
+
+def _f64(w):
+    return {k: np.asarray(v, np.float64) for k, v in w.items()}
+
+
+class PredictorTrie64:
+    """RNNPredictor (predictor.py:160-200) in float64, memoised on the token tuple it has consumed.
+    node(hyp) -> (out (P,), out_err (P,)): the projection output after feeding every token of `hyp` (seed blank
+    included) from the zero state -- what the step at the next frame feeds the joiner for a hypothesis `hyp` -- and
+    the fp32 bound of that last step (see above).  A new
+    node is one step from its parent node (hyp[:-1]); survivors are always a parent's hyp or a parent's hyp plus one
+    token, so a walk adds at most one node per survivor and frame."""
+
+    def __init__(self, w, n_layers):
+        self.w = _f64(w)
+        self.L = int(n_layers)
+        self.H = self.w["rnn.weight_hh_l0"].shape[1]
+        self.a = {k: np.abs(v) for k, v in self.w.items()}
+        z = np.zeros((self.L, self.H))
+        self.nodes = {(): (None, None, z, z)}      # hyp -> (out, out_err of its own step, h, c)
+
+    def _step(self, parent, tok):
+        _, _, h0, c0 = parent
+        w, a, H = self.w, self.a, self.H
+        x = w["embed.weight"][tok]
+        xe = 0.0
+        hs, cs = [], []
+        for l in range(self.L):
+            wi, wh = w[f"rnn.weight_ih_l{l}"], w[f"rnn.weight_hh_l{l}"]
+            b = w[f"rnn.bias_ih_l{l}"] + w[f"rnn.bias_hh_l{l}"]
+            g = wi @ x + wh @ h0[l] + b
+            K = x.size + H + 2
+            ge = (gamma(K) * (a[f"rnn.weight_ih_l{l}"] @ np.abs(x) + a[f"rnn.weight_hh_l{l}"] @ np.abs(h0[l])
+                              + a[f"rnn.bias_ih_l{l}"] + a[f"rnn.bias_hh_l{l}"])
+                  + xe)
+            sg = lambda v: 1.0 / (1.0 + np.exp(-v))
+            i, f, gg, o = sg(g[:H]), sg(g[H:2 * H]), np.tanh(g[2 * H:3 * H]), sg(g[3 * H:])
+            ie, fe, oe = (0.25 * ge[:H] + TU * i, 0.25 * ge[H:2 * H] + TU * f, 0.25 * ge[3 * H:] + TU * o)
+            gge = ge[2 * H:3 * H] + TU * np.abs(gg)
+            c = f * c0[l] + i * gg
+            ce = (np.abs(c0[l]) * fe + i * gge + np.abs(gg) * ie
+                  + 2 * U32 * (np.abs(f * c0[l]) + np.abs(i * gg)))
+            tc = np.tanh(c)
+            h = o * tc
+            he = o * (ce + TU * np.abs(tc)) + np.abs(tc) * oe + U32 * np.abs(h)
+            hs.append(h); cs.append(c)
+            x, xe = h, he.max()
+        out = w["projection.weight"] @ x + w["projection.bias"]
+        oe = gamma(H + 1) * (a["projection.weight"] @ np.abs(x) + a["projection.bias"]) + xe.max()
+        return out, oe, np.stack(hs), np.stack(cs)
+
+    def node(self, hyp):
+        hyp = tuple(int(t) for t in hyp)
+        k = len(hyp)
+        while hyp[:k] not in self.nodes:
+            k -= 1
+        for q in range(k + 1, len(hyp) + 1):
+            self.nodes[hyp[:q]] = self._step(self.nodes[hyp[:q - 1]], hyp[q - 1])
+        return self.nodes[hyp][:2]
+
+
+class Joint64:
+    """TransducerJoint (joint.py:45-70, tanh) in float64 with the fp32 bound of its logits."""
+
+    def __init__(self, w):
+        self.w = _f64(w)
+        self.a = {k: np.abs(v) for k, v in self.w.items()}
+
+    def enc(self, enc_row):
+        """enc_ffn of one encoder frame: (value, bound)."""
+        e = np.asarray(enc_row, np.float64)
+        return (self.w["enc_ffn.weight"] @ e + self.w["enc_ffn.bias"],
+                gamma(e.size + 1) * (self.a["enc_ffn.weight"] @ np.abs(e) + self.a["enc_ffn.bias"]))
+
+    def logits(self, ep, outs, out_errs):
+        """ep = enc(...), outs / out_errs (N, P) predictor outputs -> logits (N, V) and their bound (N, V).
+        The pred_ffn term also covers a device that composes pred_ffn with the projection (|W_f W_p| <= |W_f||W_p|)."""
+        w, a = self.w, self.a
+        e, ee = ep
+        P = outs.shape[1]
+        p = outs @ w["pred_ffn.weight"].T + w["pred_ffn.bias"]
+        pe = gamma(P + 1) * (np.abs(outs) @ a["pred_ffn.weight"].T + a["pred_ffn.bias"]) + out_errs.max(1, keepdims=True)
+        s_in = e + p
+        s = np.tanh(s_in)
+        se = ee.max() + pe + U32 * np.abs(s_in) + TU * np.abs(s)
+        J = s.shape[1]
+        z = s @ w["ffn_out.weight"].T + w["ffn_out.bias"]
+        ze = gamma(J + 1) * (np.abs(s) @ a["ffn_out.weight"].T + a["ffn_out.bias"]) + se.max(1, keepdims=True)
+        return z, ze
+
+
+def log_softmax_f64(z, ze):
+    """Float64 log-softmax of the last axis and the bound of an fp32 evaluation (max, exp, sum, log, subtract)
+    whose input logits are within `ze` of z."""
+    m = z.max(-1, keepdims=True)
+    lse = np.log(np.exp(z - m).sum(-1, keepdims=True))
+    lp = z - m - lse
+    V = z.shape[-1]
+    err = (ze + ze.max(-1, keepdims=True)
+           + U32 * np.abs(z - m) + gamma(V) + 2 * TU + TU * np.abs(lse) + U32 * np.abs(lp))
+    return lp, err
+
+
+def ctc_log_softmax_f64(w, enc):
+    """ctc.py:66-75 in float64: log_softmax(ctc_lo(enc)), enc (T, E) -> (log-probs (T, V), bound (T, V))."""
+    W = np.asarray(w["ctc_lo.weight"], np.float64)
+    b = np.asarray(w["ctc_lo.bias"], np.float64)
+    e = np.asarray(enc, np.float64)
+    z = e @ W.T + b
+    ze = gamma(e.shape[1] + 1) * (np.abs(e) @ np.abs(W).T + np.abs(b))
+    return log_softmax_f64(z, ze)
+
+
+def mixture_f64(lp, lp_err, ctc, ctc_err, tw, cw):
+    """prefix_beam_search.py:99-101, log(tw * exp(logp) + cw * exp(ctc)) in float64 with the weights as the fp32
+    scalars the tensors are multiplied by; returns (value, bound)."""
+    tw, cw = float(F(tw)), float(F(cw))
+    with np.errstate(divide="ignore"):
+        a = np.log(tw) + lp if tw > 0 else np.full_like(lp, -np.inf)
+        c = np.log(cw) + ctc if cw > 0 else np.full_like(ctc, -np.inf)
+    mx = np.maximum(a, c)
+    ea, ec = np.exp(a - mx), np.exp(c - mx)
+    mix = mx + np.log(ea + ec)
+    sa, sc = ea / (ea + ec), ec / (ea + ec)
+    err = (sa * (lp_err + U32 * np.abs(lp)) + sc * (ctc_err + U32 * np.abs(ctc))
+           + 2 * TU + 3 * U32 + TU * np.abs(mix))
+    return mix, err
+
+
+def prefix_beam_rows_f64(trie: PredictorTrie64, joint: Joint64, enc_row, ctc_row, ctc_err, hyps, tw, cw):
+    """The per-hypothesis rows of one frame (prefix_beam_search.py:77-101): mixture log-probs (N, V) and bounds."""
+    outs = [trie.node(h) for h in hyps]
+    z, ze = joint.logits(joint.enc(enc_row), np.stack([o for o, _ in outs]), np.stack([e for _, e in outs]))
+    lp, lpe = log_softmax_f64(z, ze)
+    return mixture_f64(lp, lpe, ctc_row[None, :], ctc_err[None, :], tw, cw)
+
+
+def topk_order(row, k):
+    """torch.topk order of the k largest (larger first, lower index on ties)."""
+    k = min(k, row.size)
+    part = np.argpartition(-row, k - 1)[:k] if k < row.size else np.arange(row.size)
+    return part[np.lexsort((part, -row[part]))]
+
+
+def prefix_beam_step_f64(beam, mix, mix_err, beam_size, blank=0, maybe=None):
+    """prefix_beam_search.py:103-146 from the float64 rows of prefix_beam_rows_f64: `beam` = [(hyp tuple, score)] in
+    the order of the previous frame.  Candidates are fp32(fp32(score) + fp32(mix)) -- the reference's own rounding
+    (the fp32 scores tensor of :86 plus the fp32 top-k values, :105), kept on purpose -- and fused with float64
+    log_add in the reference's visiting order (parent-major, then rank).
+    maybe: optional per-parent sets of tokens whose top-`beam_size` membership an fp32 evaluation may decide either
+    way (those within their bounds of the parent's rank-`beam_size` boundary); the ones outside the float64 top-k are
+    visited after the parent's top-k.
+    Returns (fused, gaps): fused = [dict(hyp, score, lo, hi, err, first)] sorted like list.sort(reverse=True) (stable):
+    `score` fuses the float64 top-k members, `lo` only the members outside `maybe`, `hi` every possible member (-inf
+    for none), `err` is the largest candidate bound of the class (log_add is 1-Lipschitz in the max norm) and `first`
+    the visiting index of the class's first float64 top-k candidate (None for a class of possible members only);
+    gaps[j] = rank-beam minus rank-(beam+1) float64 value of parent j's row (inf when it has no rank beam+1)."""
+    ninf = -float("inf")
+    fused, index = [], {}
+    gaps = np.full(len(beam), np.inf)
+    n = 0
+    for j, (hyp, score) in enumerate(beam):
+        row, rerr = mix[j], mix_err[j]
+        order = topk_order(row, beam_size + 1)
+        if order.size > beam_size:
+            gaps[j] = row[order[beam_size - 1]] - row[order[beam_size]]
+        mj = set() if maybe is None else set(maybe[j])
+        top = [int(k) for k in order[:beam_size]]
+        extra = sorted((k for k in mj if k not in top), key=lambda v: (-row[v], v))
+        s32 = F(score)
+        for k in top + extra:
+            in_top, sure = k in top, k not in mj
+            m32 = F(row[k])
+            cand = float(F(s32 + m32))
+            err = float(rerr[k] + U32 * abs(row[k]) + 2 * U32 * abs(cand))
+            h = tuple(hyp) if k == blank else tuple(hyp) + (k,)
+            if h not in index:
+                index[h] = len(fused)
+                fused.append(dict(hyp=h, score=ninf, lo=ninf, hi=ninf, err=0.0, first=None))
+            c = fused[index[h]]
+            c["hi"] = log_add([c["hi"], cand])
+            c["err"] = max(c["err"], err)
+            if in_top:
+                c["score"] = log_add([c["score"], cand])
+                if c["first"] is None:
+                    c["first"] = n
+                n += 1
+            if sure:
+                c["lo"] = log_add([c["lo"], cand])
+    top_classes = sorted((c for c in fused if c["first"] is not None), key=lambda c: c["first"])
+    top_classes.sort(key=lambda c: c["score"], reverse=True)
+    return top_classes + [c for c in fused if c["first"] is None], gaps
+
+
+def greedy_frame_f64(trie: PredictorTrie64, joint: Joint64, enc_row, hyp, tokens, blank=0):
+    """'greedy_search copy.py':27-58 at one encoder frame, from the stream's token list `hyp` (seed blank excluded).
+    The predictor output of every decision is that of the tokens so far (the cache after an emission is the new one,
+    a blank keeps the last output), so decision i of the frame sees hyp + tokens[:i].  Returns one (log-probs (V,),
+    bound (V,)) pair for each of the len(tokens) + 1 decisions -- the caller follows whichever sequence it checks."""
+    ep = joint.enc(enc_row)
+    seqs = [(blank,) + tuple(hyp) + tuple(tokens[:i]) for i in range(len(tokens) + 1)]
+    outs = [trie.node(s) for s in seqs]
+    z, ze = joint.logits(ep, np.stack([o for o, _ in outs]), np.stack([e for _, e in outs]))
+    lp, err = log_softmax_f64(z, ze)
+    return list(zip(lp, err))
