@@ -224,6 +224,16 @@ int wr_joint_fwd_split(const float *ep_d, const float *pp_d, const float *w_out_
                        void *out_d /* [B,T,U1,V] */, int out_dtype,
                        void *workspace_d, size_t workspace_bytes, void *stream);
 
+/* The single-term mode on the f16 matrix cores (v_mfma_f32_32x32x16_f16): ep + pp, the activation and w_out rounded to
+ * float16 (nearest even; subnormals kept, beyond +-65504 -> +-inf as torch's .half()), fp32 accumulation -- the
+ * operand format of the reference's ffn_out under fp16 autocast (executor.py:91, --use_amp with the default dtype).
+ * Arguments, out_dtype and workspace (wr_joint_split_workspace_bytes) as wr_joint_fwd_split with terms = 1. */
+int wr_joint_fwd_f16(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
+                     const int32_t *logit_lengths_d /* nullable */, const int32_t *target_lengths_d /* nullable */,
+                     int B, int T, int U1, int J, int V, int activation,
+                     void *out_d /* [B,T,U1,V] */, int out_dtype,
+                     void *workspace_d, size_t workspace_bytes, void *stream);
+
 /* wr_joint_fwd_split with the RNN-T loss's row statistics fused into the epilogue (see wr_joint_fwd_lse); fp32 logits. */
 int wr_joint_fwd_split_lse(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
                            const int32_t *logit_lengths_d, const int32_t *target_lengths_d, const int32_t *targets_d,
@@ -254,6 +264,16 @@ int wr_joint_bwd_dz_split_bf16(const void *gout_bf16_d /* [B,T,U1,V] bf16 */, co
                                int B, int T, int U1, int J, int V, int activation, int terms,
                                float *dz_d /* [B,T,U1,J] */, float *h_d /* [B,T,U1,J] or NULL */,
                                void *workspace_d, size_t workspace_bytes, void *stream);
+
+/* wr_joint_bwd_dz_split (terms = 1) on the f16 matrix cores: dY and W rounded to float16, fp32 accumulation.  gout_dtype
+ * WR_F32 (rounded to f16 in the kernel; V a multiple of 4) or WR_F16 (taken as it is; V a multiple of 8); V at least 32.
+ * Workspace: wr_joint_dz_split_workspace_bytes. */
+int wr_joint_bwd_dz_f16(const void *gout_d /* [B,T,U1,V] */, int gout_dtype, const float *ep_d, const float *pp_d,
+                        const float *w_out_d,
+                        const int32_t *logit_lengths_d /* nullable */, const int32_t *target_lengths_d /* nullable */,
+                        int B, int T, int U1, int J, int V, int activation,
+                        float *dz_d /* [B,T,U1,J] */, float *h_d /* [B,T,U1,J] or NULL */,
+                        void *workspace_d, size_t workspace_bytes, void *stream);
 
 /* Second half of the activation gradient for callers that form dH = gout . W themselves (the AMP step hands that plain
  * bf16 contraction to the vendor GEMM library): dz[cell, j] = dH[cell, j] * act'(ep + pp) in place (zero in padded cells
@@ -307,6 +327,15 @@ int wr_joint_bwd_dw_split_bf16(const void *gout_bf16_d /* [B,T,U1,V] bf16 */, co
                                int B, int T, int U1, int J, int V, int terms,
                                float *dw_d /* [V,J] */, float *db_d /* [V] or NULL */,
                                void *workspace_d, size_t workspace_bytes, void *stream);
+
+/* wr_joint_bwd_dw_split (terms = 1) on the f16 matrix cores: dY and h rounded to float16, fp32 accumulation; db summed in
+ * fp32 from the gradient as given.  gout_dtype WR_F32 or WR_F16; V and J multiples of 4.  Workspace:
+ * wr_joint_dw_split_workspace_bytes. */
+int wr_joint_bwd_dw_f16(const void *gout_d /* [B,T,U1,V] */, int gout_dtype, const float *h_d /* [B,T,U1,J] */,
+                        const int32_t *logit_lengths_d /* nullable */, const int32_t *target_lengths_d /* nullable */,
+                        int B, int T, int U1, int J, int V,
+                        float *dw_d /* [V,J] */, float *db_d /* [V] or NULL */,
+                        void *workspace_d, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------
  * Transducer decoding: batched greedy search, batched prefix beam search and

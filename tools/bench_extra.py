@@ -60,6 +60,22 @@ def bench_joint(args):
                           "max_abs_err_vs_fp32": err, "logit_std": scale, "rel_to_scale": err / scale}), flush=True)
         del out_s
     lib.wr_tune_set(7, 0)
+    # the single-term forward with bf16 operands (wr_joint_fwd_split, terms=1) and with f16 operands (wr_joint_fwd_f16) on
+    # the same shape, bf16 / f16 logits (the fp16-autocast configuration), alternating in one process; default launch form
+    out16 = torch.empty(B, T, U1, V, dtype=torch.bfloat16, device=dev)
+    outh = torch.empty(B, T, U1, V, dtype=torch.float16, device=dev)
+    fb = lambda: _lib.check(lib.wr_joint_fwd_split(P(ep), P(pp), P(w), P(b), None, None, B, T, U1, J, V, 0, 1, P(out16),
+                                                   _lib.WR_BF16, P(ws_s), wsb_s, st))
+    fh = lambda: _lib.check(lib.wr_joint_fwd_f16(P(ep), P(pp), P(w), P(b), None, None, B, T, U1, J, V, 0, P(outh),
+                                                 _lib.WR_F16, P(ws_s), wsb_s, st))
+    for rep_ in range(2):
+        for name, fn, o in (("bf16", fb, out16), ("f16", fh, outh)):
+            ms = timeit(fn, args.steps)
+            err = float((o[:1].float() - out[:1]).abs().max())
+            print(json.dumps({"what": "joint_fwd_single_term", "operands": name, "logits": str(o.dtype).split(".")[-1],
+                              "rep": rep_, "shape": [B, T, U1, J, V], "ms": round(ms, 3), "TFLOPs": round(flops / ms / 1e9, 1),
+                              "max_abs_err_vs_fp32": err, "rel_to_scale": err / scale}), flush=True)
+    del out16, outh
     dz = torch.empty(B, T, U1, J, device=dev); h = torch.empty_like(dz)
     g = lambda: _lib.check(lib.wr_joint_bwd_dz(P(out), P(ep), P(pp), P(w), None, None, B, T, U1, J, V, 0, P(dz), P(h), st))
     dz_blocks = None
@@ -361,13 +377,14 @@ def bench_step(args):
         tl = torch.randint(U // 3, U + 1, (B,), generator=gcpu).to(torch.int32).to(dev)
         ll[0], tl[-1] = T, U
     base = None
-    precs = ("fp32", "fp32-fused", "bf16x3", "bf16x3-fused", "bf16-autocast")
+    precs = ("fp32", "fp32-fused", "bf16x3", "bf16x3-fused", "bf16-autocast", "bf16-autocast-f16", "f16-autocast-f16")
     if args.only:
         precs = tuple(x for x in precs if x in args.only.split(","))
     for prec in precs:
-        amp = prec == "bf16-autocast"                  # the --use_amp configuration (executor.py:91)
+        amp = "-autocast" in prec                      # the --use_amp configuration (executor.py:91)
+        adt = torch.float16 if prec.endswith("-f16") else torch.bfloat16      # "-f16": fp16 autocast, the reference's default
         fused = prec.endswith("-fused")                # joiner + loss as one node (fused.py): no pass 1, gradient in place
-        jprec = "bf16" if amp else prec.replace("-fused", "")
+        jprec = prec.split("-")[0] if amp else prec.replace("-fused", "")
         joint = w.TransducerJoint(V, E, P, J, precision=jprec).to(dev)
         torch.manual_seed(4)
         with torch.no_grad():
@@ -376,7 +393,7 @@ def bench_step(args):
 
         def step():
             joint.zero_grad(set_to_none=True); enc.grad = None; pred.grad = None
-            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+            with torch.autocast("cuda", dtype=adt, enabled=amp):
                 if fused:
                     loss = w.joint_rnnt_loss(joint.enc_ffn(enc), joint.pred_ffn(pred), joint.ffn_out.weight,
                                              joint.ffn_out.bias, y, ll, tl, blank=0, reduction="mean", precision=jprec,

@@ -9,7 +9,10 @@
 //                 fp32 accumulation; |error| of a logit ~ 1e-5 of its scale -- inside the 1e-4 parity bar
 //                 of the fp32 path (tests/test_joint_gpu.py states the tolerance);
 //     terms = 1:  a_hi*b_hi only -- the AMP path: the reference under --use_amp (executor.py:91 autocast)
-//                 runs this Linear in fp16 with fp32 accumulation; bf16 operands, fp32 accumulate here.
+//                 runs this Linear in fp16 with fp32 accumulation; bf16 operands, fp32 accumulate here --
+//                 or, the f16 arm (OpT = _Float16: wr_joint_fwd_f16 / wr_joint_bwd_dz_f16 / wr_joint_bwd_dw_f16), f16
+//                 operands on v_mfma_f32_32x32x16_f16 (same shape and rate): the reference's own fp16 operand format,
+//                 rounded to nearest even, subnormals kept, beyond +-65504 -> +-inf as torch's .half().
 // The exact-fp32 kernels of joint.hip stay the default; this file is opt-in (precision argument of
 // wenet_celoss_amd.TransducerJoint / joint_logits, or WR_JOINT_PRECISION).
 //
@@ -34,6 +37,8 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kSM = 64;          // lattice cells per workgroup
@@ -81,6 +86,20 @@ __device__ __forceinline__ void split_pair(float x0, float x1, unsigned &hi, uns
     lo = __builtin_bit_cast(unsigned, l);
 }
 
+// two floats -> packed f16 pair (v_cvt_pk_f16_f32: round to nearest even, subnormals kept, beyond +-65504 -> +-inf)
+__device__ __forceinline__ unsigned f16_pair(float x0, float x1)
+{
+    return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){x0, x1}, f16x2));
+}
+__device__ __forceinline__ u32x4 f16_pack8(const f32x4 &a, const f32x4 &b)
+{
+    return (u32x4){f16_pair(a[0], a[1]), f16_pair(a[2], a[3]), f16_pair(b[0], b[1]), f16_pair(b[2], b[3])};
+}
+__device__ __forceinline__ f32x16 mfma_f16(u32x4 a, u32x4 b, f32x16 c)
+{
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+
 // tanh through the hardware exp2 / rcp (|error| ~ 1e-7 absolute: below the split's own 2^-17 operand error)
 __device__ __forceinline__ float tanh_fast(float x)
 {
@@ -112,6 +131,22 @@ __global__ void split_w_kernel(const float *__restrict__ w, int V, int J, int Vp
     }
 }
 
+// f16 arm of the single-term mode: the same fragment order, ONE image (no lo part), W rounded to nearest even --
+// subnormals kept, beyond +-65504 -> +-inf, as W.half()
+__global__ void split_w_f16_kernel(const float *__restrict__ w, int V, int J, int Vp, int Jp, _Float16 *__restrict__ wh)
+{
+    const int S = Jp / 16;
+    const long total = (long)(Vp / 32) * S * 64;
+    for (long f = (long)blockIdx.x * blockDim.x + threadIdx.x; f < total; f += (long)gridDim.x * blockDim.x) {
+        const int l = (int)(f & 63);
+        const long cs = f >> 6;
+        const int s = (int)(cs % S), ct = (int)(cs / S);
+        const int v = ct * 32 + (l & 31), k0 = s * 16 + 8 * (l >> 5);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) wh[f * 8 + j] = (_Float16)((v < V && k0 + j < J) ? w[(size_t)v * J + k0 + j] : 0.f);
+    }
+}
+
 #ifdef WR_SPLIT_PLAIN_STORE
 #define WR_SPLIT_STORE(v, p) (*(p) = (v))
 #else
@@ -132,6 +167,9 @@ template <> __device__ __forceinline__ __bf16 to_out<__bf16>(float x) { return (
 // stage takes 16 or 8 rows at a time) -- with one wave per SIMD nothing overlaps a workgroup's tile build, the issue of
 // its W loads (the CU's 64 B/clk vector-memory path is busy for as long as the MFMAs of the set) and its epilogues;
 // a second workgroup's MFMAs do (stamps: profiles/r03_amp_stamps_*.json).
+// OpT (single-term mode): the operand format, __bf16 (v_mfma_f32_32x32x16_bf16) or _Float16 (v_mfma_f32_32x32x16_f16, same
+// shape and rate: what the reference's fp16 autocast multiplies).  The f16 arm changes only the operands -- the activation
+// tile is packed with v_cvt_pk_f16_f32 and W comes from split_w_f16_kernel's image -- every tiling and store form is shared.
 // TRN (single-term mode): the MFMAs take the W fragment as the A operand and the activation fragment as the B operand
 // (both have the same register layout), so a tile comes out transposed -- a lane holds ONE lattice cell and 4 x 4
 // consecutive vocabulary entries of it, which it adds the bias to, packs and stores itself (8 or 16 bytes per lane and
@@ -140,7 +178,8 @@ template <> __device__ __forceinline__ __bf16 to_out<__bf16>(float x) { return (
 // waves per CU (two per SIMD, 256 registers each; a 4 x 2 register tile needs half the W bytes per MFMA): measured 9.1-10.2 ms
 // against 7.8 for two 64-cell workgroups -- eight accumulator tiles in 256 registers spill in the staged epilogue
 // (26 k cycles per round), the transposed epilogue does not but stores 16-byte pieces -- so it is not instantiated.
-template <int TERMS, typename OutT, bool LSE = false, int RT = 2, int OCC = 1, bool TRN = false, int NW = kSWaves>
+template <int TERMS, typename OutT, bool LSE = false, int RT = 2, int OCC = 1, bool TRN = false, int NW = kSWaves,
+          typename OpT = __bf16>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : OCC) void joint_fwd_split_kernel(
     const float *__restrict__ ep, const float *__restrict__ pp, const u32x4 *__restrict__ wh, const u32x4 *__restrict__ wl,
     const float *__restrict__ bias, const int32_t *__restrict__ llens, const int32_t *__restrict__ tlens, int B, int T,
@@ -155,6 +194,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : OCC) void joint_fwd_split_ke
                   "two waves per SIMD: single-term mode; 64 cells x two workgroups or 128 cells x eight waves");
     static_assert(NW == 4 || NW == 8, "waves per workgroup");
     static_assert(!TRN || (TERMS == 1 && !LSE), "transposed tiles: single-term mode without row statistics");
+    constexpr bool F16 = std::is_same<OpT, _Float16>::value;
+    static_assert(F16 ? (TERMS == 1 && !LSE) : std::is_same<OpT, __bf16>::value, "f16 operands: single-term mode only");
     const int JS = Jp + 8;                                 // padded row stride (bf16 elements): 16-byte pad
     unsigned short *Ahi = lds_s;                            // [SM][JS]
     unsigned short *Alo = lds_s + (size_t)SM * JS;          // [SM][JS]   (TERMS == 3)
@@ -330,7 +371,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : OCC) void joint_fwd_split_ke
                         const float z0 = ec[i][j] + pv[q][i][j], z1 = ec[i][j + 1] + pv[q][i][j + 1];
                         const float a0 = act == WR_ACT_TANH ? tanh_fast(z0) : act_value(act, z0);
                         const float a1 = act == WR_ACT_TANH ? tanh_fast(z1) : act_value(act, z1);
-                        split_pair(kin ? a0 : 0.f, kin ? a1 : 0.f, hp[j / 2], lp[j / 2]);
+                        if constexpr (F16) hp[j / 2] = f16_pair(kin ? a0 : 0.f, kin ? a1 : 0.f);
+                        else split_pair(kin ? a0 : 0.f, kin ? a1 : 0.f, hp[j / 2], lp[j / 2]);
                     }
                     if constexpr (VW == 4) {
                         typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -398,14 +440,20 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : OCC) void joint_fwd_split_ke
             for (int r = 0; r < RT; ++r)
 #pragma unroll
                 for (int c = 0; c < kSCT; ++c) {
-                    const bf16x8 bhv = __builtin_bit_cast(bf16x8, bh[i][c]);
-                    if (TERMS == 3) {
-                        const bf16x8 blv = __builtin_bit_cast(bf16x8, bl[i][c]);
-                        acc[r][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[buf][r], bhv, acc[r][c], 0, 0, 0);   // small terms first
-                        acc[r][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[buf][r], blv, acc[r][c], 0, 0, 0);
+                    if constexpr (F16) {
+                        const u32x4 av = __builtin_bit_cast(u32x4, ah[buf][r]);
+                        if (TRN) acc[r][c] = mfma_f16(bh[i][c], av, acc[r][c]);
+                        else acc[r][c] = mfma_f16(av, bh[i][c], acc[r][c]);
+                    } else {
+                        const bf16x8 bhv = __builtin_bit_cast(bf16x8, bh[i][c]);
+                        if (TERMS == 3) {
+                            const bf16x8 blv = __builtin_bit_cast(bf16x8, bl[i][c]);
+                            acc[r][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[buf][r], bhv, acc[r][c], 0, 0, 0);   // small terms first
+                            acc[r][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[buf][r], blv, acc[r][c], 0, 0, 0);
+                        }
+                        if (TRN) acc[r][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bhv, ah[buf][r], acc[r][c], 0, 0, 0);
+                        else acc[r][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[buf][r], bhv, acc[r][c], 0, 0, 0);
                     }
-                    if (TRN) acc[r][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bhv, ah[buf][r], acc[r][c], 0, 0, 0);
-                    else acc[r][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[buf][r], bhv, acc[r][c], 0, 0, 0);
                 }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -672,6 +720,22 @@ __global__ void split_w_dz_kernel(const float *__restrict__ w, int V, int J, int
     }
 }
 
+// f16 arm of the single-term mode: the same fragment order, one image, W rounded to nearest even (as split_w_f16_kernel)
+__global__ void split_w_dz_f16_kernel(const float *__restrict__ w, int V, int J, int D, int n_jt, _Float16 *__restrict__ wh)
+{
+    const long total = (long)n_jt * D * 2 * 64;
+    for (long f = (long)blockIdx.x * blockDim.x + threadIdx.x; f < total; f += (long)gridDim.x * blockDim.x) {
+        const int l = (int)(f & 63);
+        const long r = f >> 6;
+        const int t = (int)(r & 1);
+        const long jd = r >> 1;
+        const int d = (int)(jd % D), jt = (int)(jd / D);
+        const int j = jt * 32 + (l & 31), v0 = 32 * d + 16 * (l >> 5) + 8 * t;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) wh[f * 8 + e] = (_Float16)((j < J && v0 + e < V) ? w[(size_t)(v0 + e) * J + j] : 0.f);
+    }
+}
+
 // eight floats -> bf16x8 hi (and lo) fragments
 __device__ __forceinline__ void split8(const f32x4 &a, const f32x4 &b, bf16x8 &hi, bf16x8 &lo, bool want_lo)
 {
@@ -695,8 +759,10 @@ constexpr int kZStages = 3;
 // FULL: all 16 column tiles are in use (J = 512, the shipped join_dim): no per-tile guards in the k-loop
 // GT: dtype of the logits gradient -- float, or __bf16 (the AMP step: the loss hands back a bf16 gradient; its values ARE
 // their own hi parts, so a lane's 16 values of a double step are two ready-made MFMA operands: half the bytes, no
-// conversion pass, no split arithmetic, and the lo term vanishes)
-template <int TERMS, bool FULL, typename GT = float>
+// conversion pass, no split arithmetic, and the lo term vanishes), or _Float16 with OpT = _Float16
+// OpT: operand format of the single-term mode, __bf16 or _Float16 (v_mfma_f32_32x32x16_f16; an fp32 gradient is rounded to
+// f16 in registers, an f16 gradient is taken as it is, W comes from split_w_dz_f16_kernel's image)
+template <int TERMS, bool FULL, typename GT = float, typename OpT = __bf16>
 __global__ __launch_bounds__(256) void joint_bwd_dz_split128_kernel(
     const GT *__restrict__ gout /* [M, V] */, const float *__restrict__ ep, const float *__restrict__ pp,
     const u32x4 *__restrict__ wh, const u32x4 *__restrict__ wl, const int32_t *__restrict__ llens,
@@ -741,6 +807,9 @@ __global__ __launch_bounds__(256) void joint_bwd_dz_split128_kernel(
         return;
     }
 
+    constexpr bool F16 = std::is_same<OpT, _Float16>::value;
+    static_assert(F16 ? TERMS == 1 : (std::is_same<OpT, __bf16>::value && !std::is_same<GT, _Float16>::value),
+                  "f16 operands: single-term mode; an f16 gradient needs f16 operands");
     f32x16 acc[16];
 #pragma unroll
     for (int c = 0; c < 16; ++c) acc[c] = (f32x16){0};
@@ -831,6 +900,7 @@ __global__ __launch_bounds__(256) void joint_bwd_dz_split128_kernel(
         }
         bf16x8 ah, al;
         if constexpr (G16) ah = __builtin_bit_cast(bf16x8, z.a[t]);
+        else if constexpr (F16) ah = __builtin_bit_cast(bf16x8, f16_pack8(z.a[2 * t], z.a[2 * t + 1]));
         else split8(z.a[2 * t], z.a[2 * t + 1], ah, al, TERMS == 3);
         const u32x4 *st = stage + (size_t)(s % kZStages) * 2 * 16 * 64 + lane;
         // the fragments of column tile c + 2 are requested before the MFMAs of tile c (the compiler issued each tile's two
@@ -851,13 +921,17 @@ __global__ __launch_bounds__(256) void joint_bwd_dz_split128_kernel(
                 else if (c >= 8 && c < 8 + NQ) wload_fast(s + 4, zw, c - 8);
             }
             if (FULL || c < n_jt) {
-                const bf16x8 bhv = __builtin_bit_cast(bf16x8, rh[c % 3]);
-                if (TERMS == 3) {
-                    const bf16x8 blv = __builtin_bit_cast(bf16x8, rl[c % 3]);
-                    if (!G16) acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bhv, acc[c], 0, 0, 0);
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, blv, acc[c], 0, 0, 0);
+                if constexpr (F16) {
+                    acc[c] = mfma_f16(__builtin_bit_cast(u32x4, ah), rh[c % 3], acc[c]);
+                } else {
+                    const bf16x8 bhv = __builtin_bit_cast(bf16x8, rh[c % 3]);
+                    if (TERMS == 3) {
+                        const bf16x8 blv = __builtin_bit_cast(bf16x8, rl[c % 3]);
+                        if (!G16) acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bhv, acc[c], 0, 0, 0);
+                        acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, blv, acc[c], 0, 0, 0);
+                    }
+                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bhv, acc[c], 0, 0, 0);
                 }
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bhv, acc[c], 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -954,8 +1028,10 @@ __global__ void cell_mask_kernel(const int32_t *__restrict__ llens, const int32_
     }
 }
 
-// GT: dtype of the logits gradient (float, or __bf16 in the AMP step: a dY patch is then 4 x 2 bytes per cell)
-template <int TERMS, typename GT = float>
+// GT: dtype of the logits gradient (float, or __bf16 in the AMP step: a dY patch is then 4 x 2 bytes per cell; _Float16 with
+// OpT = _Float16).  OpT: operand format of the single-term mode, __bf16 or _Float16 (dY and H rounded to f16 where they are
+// staged, v_mfma_f32_32x32x16_f16)
+template <int TERMS, typename GT = float, typename OpT = __bf16>
 __global__ __launch_bounds__(512) void joint_bwd_dw_split_kernel(
     const GT *__restrict__ gout /* [M, V] */, const float *__restrict__ h /* [M, J] */,
     const unsigned char *__restrict__ mask /* [M] or null */, long M, int V, int J, int n_vs, int n_js, long rows_per_part,
@@ -986,6 +1062,9 @@ __global__ __launch_bounds__(512) void joint_bwd_dw_split_kernel(
     const bool col_in = op == 0 ? (v0 + 4 * c4 < V) : (j0 + 4 * c4 < J);   // V, J multiples of 4: wholly in or out
     const int ld = op == 0 ? V : J;
     constexpr bool G16 = !std::is_same<GT, float>::value;
+    constexpr bool F16 = std::is_same<OpT, _Float16>::value;
+    static_assert(F16 ? TERMS == 1 : (std::is_same<OpT, __bf16>::value && !std::is_same<GT, _Float16>::value),
+                  "f16 operands: single-term mode; an f16 gradient needs f16 operands");
     const float *__restrict__ gsrc = (op == 0 ? (G16 ? h : reinterpret_cast<const float *>(gout) + v0) : h + j0) + (col_in ? 4 * c4 : 0);
     const GT *__restrict__ gsrc16 = gout + v0 + (col_in ? 4 * c4 : 0);          // G16: the dY patches
     struct Regs { f32x4 x[8]; };                            // G16 dY patches: four bf16 as loaded in x[e][0..1] (widening them
@@ -1016,7 +1095,13 @@ __global__ __launch_bounds__(512) void joint_bwd_dw_split_kernel(
         const f32x4 zero = (f32x4){0, 0, 0, 0};
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            if (G16 && op == 0) {                                    // four bf16 -> four floats (exact: a shift)
+            if constexpr (std::is_same<GT, _Float16>::value) {
+                if (op == 0) {                                       // four f16 -> four floats (exact)
+                    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+                    const f32x4 raw = z.x[e];
+                    z.x[e] = __builtin_convertvector(__builtin_bit_cast(f16x4, __builtin_shufflevector(raw, raw, 0, 1)), f32x4);
+                }
+            } else if (G16 && op == 0) {                             // four bf16 -> four floats (exact: a shift)
                 const u32x4 raw = __builtin_bit_cast(u32x4, z.x[e]);
                 const unsigned rx = raw[0], ry = raw[1];
                 z.x[e] = (f32x4){__builtin_bit_cast(float, rx << 16), __builtin_bit_cast(float, rx & 0xffff0000u),
@@ -1034,6 +1119,10 @@ __global__ __launch_bounds__(512) void joint_bwd_dw_split_kernel(
             bf16x8 hi, lo;
             const f32x4 lo4 = (f32x4){z.x[0][t], z.x[1][t], z.x[2][t], z.x[3][t]};
             const f32x4 hi4 = (f32x4){z.x[4][t], z.x[5][t], z.x[6][t], z.x[7][t]};
+            if constexpr (F16) {
+                st[t * 64] = f16_pack8(lo4, hi4);
+                continue;
+            }
             split8(lo4, hi4, hi, lo, TERMS == 3);
             st[t * 64] = __builtin_bit_cast(u32x4, hi);
             if (TERMS == 3) st[2 * 4 * 64 + t * 64] = __builtin_bit_cast(u32x4, lo);
@@ -1065,6 +1154,10 @@ __global__ __launch_bounds__(512) void joint_bwd_dw_split_kernel(
             if (TERMS == 3) bl = __builtin_bit_cast(bf16x8, sb[2 * 4 * 64 + (2 * u + bsub) * 64]);
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
+                if constexpr (F16) {
+                    acc[t][u] = mfma_f16(__builtin_bit_cast(u32x4, ah[t]), __builtin_bit_cast(u32x4, bh), acc[t][u]);
+                    continue;
+                }
                 if (TERMS == 3) {
                     acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[t], bh, acc[t][u], 0, 0, 0);
                     acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t], bl, acc[t][u], 0, 0, 0);
@@ -1737,15 +1830,20 @@ namespace {
 int joint_fwd_split_launch(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
                            const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1, int J,
                            int V, int act, int terms, void *out_d, int out_dtype, void *workspace_d, size_t workspace_bytes,
-                           const JointLse *lse, hipStream_t st)
+                           const JointLse *lse, hipStream_t st, bool f16 = false)
 {
     const int Vp = split_vpad(V), Jp = split_jpad(J);
     const size_t img = align_up((size_t)Jp * Vp * sizeof(unsigned short), 256);
     WR_REQUIRE(workspace_bytes >= 2 * img, WR_EWORKSPACE, "joint_fwd_split: workspace too small");
     unsigned short *wh = static_cast<unsigned short *>(workspace_d);
     unsigned short *wl = reinterpret_cast<unsigned short *>(static_cast<char *>(workspace_d) + img);
-    hipLaunchKernelGGL(split_w_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, Vp, Jp, wh, wl);
-    WR_CHECK_LAUNCH("split_w_kernel");
+    if (f16) {                                              // f16 operands (terms == 1): one image, the lo half stays unused
+        hipLaunchKernelGGL(split_w_f16_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, Vp, Jp, reinterpret_cast<_Float16 *>(wh));
+        WR_CHECK_LAUNCH("split_w_f16_kernel");
+    } else {
+        hipLaunchKernelGGL(split_w_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, Vp, Jp, wh, wl);
+        WR_CHECK_LAUNCH("split_w_kernel");
+    }
     const long M = (long)B * T * U1;
     // Column slabs per XCD (part = blockIdx % npart) would keep W in each XCD's L2; measured (B=8: 20.8 / 21.5 / 23.0 ms
     // for 1 / 2 / 4 parts) the Infinity Cache already feeds the fragments fast enough and the extra activation tiles
@@ -1796,30 +1894,30 @@ int joint_fwd_split_launch(const float *ep_d, const float *pp_d, const float *w_
     const int kb_bias = two ? 0 : (int)bias_al, kb_stage = (two || stage_fits) ? 1 : 0;
     WR_REQUIRE(lds <= 160 * 1024, WR_EUNSUPPORTED, "joint_fwd_split: V=%d needs %zu bytes of LDS", V, lds);
     const dim3 grid((unsigned)((M + cells - 1) / cells * npart));
-#define WR_LAUNCH_SPLIT_WIDE(OutT, TRN)                                                                                  \
+#define WR_LAUNCH_SPLIT_WIDE(OutT, TRN, OpT)                                                                             \
     do {                                                                                                              \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<1, OutT, false, 4, 1, TRN>),    \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<1, OutT, false, 4, 1, TRN, kSWaves, OpT>), \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-        hipLaunchKernelGGL((joint_fwd_split_kernel<1, OutT, false, 4, 1, TRN>), grid, dim3(64 * kSWaves), lds, st, ep_d, pp_d, \
-                           reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl), b_out_d,          \
+        hipLaunchKernelGGL((joint_fwd_split_kernel<1, OutT, false, 4, 1, TRN, kSWaves, OpT>), grid, dim3(64 * kSWaves), lds, st, \
+                           ep_d, pp_d, reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl), b_out_d, \
                            logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, npart, act, static_cast<OutT *>(out_d), \
                            JointLse{}, kb_bias, kb_stage);                                                            \
     } while (0)
-#define WR_LAUNCH_SPLIT_TWO(OutT, TRN)                                                                                   \
+#define WR_LAUNCH_SPLIT_TWO(OutT, TRN, OpT)                                                                              \
     do {                                                                                                              \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<1, OutT, false, 2, 2, TRN>),    \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<1, OutT, false, 2, 2, TRN, kSWaves, OpT>), \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-        hipLaunchKernelGGL((joint_fwd_split_kernel<1, OutT, false, 2, 2, TRN>), grid, dim3(64 * kSWaves), lds, st, ep_d, \
-                           pp_d, reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl), b_out_d,    \
+        hipLaunchKernelGGL((joint_fwd_split_kernel<1, OutT, false, 2, 2, TRN, kSWaves, OpT>), grid, dim3(64 * kSWaves), lds, st, \
+                           ep_d, pp_d, reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl), b_out_d, \
                            logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, npart, act, static_cast<OutT *>(out_d), \
                            JointLse{}, kb_bias, kb_stage);                                                            \
     } while (0)
-#define WR_LAUNCH_SPLIT(TERMS, OutT, TRN)                                                                             \
+#define WR_LAUNCH_SPLIT(TERMS, OutT, TRN, OpT)                                                                        \
     do {                                                                                                              \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<TERMS, OutT, false, 2, 1, TRN>), \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<TERMS, OutT, false, 2, 1, TRN, kSWaves, OpT>), \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-        hipLaunchKernelGGL((joint_fwd_split_kernel<TERMS, OutT, false, 2, 1, TRN>), grid, dim3(64 * kSWaves), lds, st, ep_d, pp_d, \
-                           reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl), b_out_d,          \
+        hipLaunchKernelGGL((joint_fwd_split_kernel<TERMS, OutT, false, 2, 1, TRN, kSWaves, OpT>), grid, dim3(64 * kSWaves), lds, \
+                           st, ep_d, pp_d, reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl), b_out_d, \
                            logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, npart, act, static_cast<OutT *>(out_d), \
                            JointLse{}, kb_bias, kb_stage);                                                            \
     } while (0)
@@ -1832,37 +1930,36 @@ int joint_fwd_split_launch(const float *ep_d, const float *pp_d, const float *w_
                            logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, npart, act, static_cast<float *>(out_d), \
                            *lse);                                                                                     \
     } while (0)
+#define WR_BY_OUT(LAUNCH, ...)                                                                                        \
+    do {                                                                                                              \
+        if (out_dtype == 0) LAUNCH(float, __VA_ARGS__);                                                               \
+        else if (out_dtype == 1) LAUNCH(_Float16, __VA_ARGS__);                                                       \
+        else LAUNCH(__bf16, __VA_ARGS__);                                                                             \
+    } while (0)
+#define WR_LAUNCH_SPLIT1(OutT, TRN, OpT) WR_LAUNCH_SPLIT(1, OutT, TRN, OpT)
+#define WR_SINGLE_TERM(OpT)                                                                                           \
+    do {                                                                                                              \
+        if (two && trn) WR_BY_OUT(WR_LAUNCH_SPLIT_TWO, true, OpT);                                                    \
+        else if (two) WR_BY_OUT(WR_LAUNCH_SPLIT_TWO, false, OpT);                                                     \
+        else if (wide && trn) WR_BY_OUT(WR_LAUNCH_SPLIT_WIDE, true, OpT);                                             \
+        else if (wide) WR_BY_OUT(WR_LAUNCH_SPLIT_WIDE, false, OpT);                                                   \
+        else if (trn) WR_BY_OUT(WR_LAUNCH_SPLIT1, true, OpT);                                                         \
+        else WR_BY_OUT(WR_LAUNCH_SPLIT1, false, OpT);                                                                 \
+    } while (0)
     if (lse) {
         if (terms == 3) WR_LAUNCH_SPLIT_LSE(3); else WR_LAUNCH_SPLIT_LSE(1);
     } else if (terms == 3) {
-        if (out_dtype == 0) WR_LAUNCH_SPLIT(3, float, false);
-        else if (out_dtype == 1) WR_LAUNCH_SPLIT(3, _Float16, false);
-        else WR_LAUNCH_SPLIT(3, __bf16, false);
-    } else if (two && trn) {
-        if (out_dtype == 0) WR_LAUNCH_SPLIT_TWO(float, true);
-        else if (out_dtype == 1) WR_LAUNCH_SPLIT_TWO(_Float16, true);
-        else WR_LAUNCH_SPLIT_TWO(__bf16, true);
-    } else if (two) {
-        if (out_dtype == 0) WR_LAUNCH_SPLIT_TWO(float, false);
-        else if (out_dtype == 1) WR_LAUNCH_SPLIT_TWO(_Float16, false);
-        else WR_LAUNCH_SPLIT_TWO(__bf16, false);
-    } else if (wide && trn) {
-        if (out_dtype == 0) WR_LAUNCH_SPLIT_WIDE(float, true);
-        else if (out_dtype == 1) WR_LAUNCH_SPLIT_WIDE(_Float16, true);
-        else WR_LAUNCH_SPLIT_WIDE(__bf16, true);
-    } else if (wide) {
-        if (out_dtype == 0) WR_LAUNCH_SPLIT_WIDE(float, false);
-        else if (out_dtype == 1) WR_LAUNCH_SPLIT_WIDE(_Float16, false);
-        else WR_LAUNCH_SPLIT_WIDE(__bf16, false);
-    } else if (trn) {
-        if (out_dtype == 0) WR_LAUNCH_SPLIT(1, float, true);
-        else if (out_dtype == 1) WR_LAUNCH_SPLIT(1, _Float16, true);
-        else WR_LAUNCH_SPLIT(1, __bf16, true);
+        if (out_dtype == 0) WR_LAUNCH_SPLIT(3, float, false, __bf16);
+        else if (out_dtype == 1) WR_LAUNCH_SPLIT(3, _Float16, false, __bf16);
+        else WR_LAUNCH_SPLIT(3, __bf16, false, __bf16);
+    } else if (f16) {
+        WR_SINGLE_TERM(_Float16);
     } else {
-        if (out_dtype == 0) WR_LAUNCH_SPLIT(1, float, false);
-        else if (out_dtype == 1) WR_LAUNCH_SPLIT(1, _Float16, false);
-        else WR_LAUNCH_SPLIT(1, __bf16, false);
+        WR_SINGLE_TERM(__bf16);
     }
+#undef WR_SINGLE_TERM
+#undef WR_LAUNCH_SPLIT1
+#undef WR_BY_OUT
 #undef WR_LAUNCH_SPLIT_WIDE
 #undef WR_LAUNCH_SPLIT_TWO
 #undef WR_LAUNCH_SPLIT
@@ -1884,6 +1981,19 @@ extern "C" int wr_joint_fwd_split(const float *ep_d, const float *pp_d, const fl
                "joint_fwd_split: pass both length arrays or neither");
     return joint_fwd_split_launch(ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation,
                                   terms, out_d, out_dtype, workspace_d, workspace_bytes, nullptr, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int wr_joint_fwd_f16(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
+                                const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1, int J,
+                                int V, int activation, void *out_d, int out_dtype, void *workspace_d, size_t workspace_bytes,
+                                void *stream)
+{
+    if (int rc = split_check(B, T, U1, J, V, 1, out_dtype, activation)) return rc;
+    WR_REQUIRE(ep_d && pp_d && w_out_d && b_out_d && out_d && workspace_d, WR_EINVAL, "joint_fwd_f16: null pointer argument");
+    WR_REQUIRE((logit_lengths_d == nullptr) == (target_lengths_d == nullptr), WR_EINVAL,
+               "joint_fwd_f16: pass both length arrays or neither");
+    return joint_fwd_split_launch(ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation,
+                                  1, out_d, out_dtype, workspace_d, workspace_bytes, nullptr, static_cast<hipStream_t>(stream), true);
 }
 
 extern "C" int wr_joint_fwd_split_lse(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
@@ -1920,7 +2030,7 @@ namespace {
 int joint_bwd_dz_split_launch(const void *gout_d, bool g16, const float *ep_d, const float *pp_d, const float *w_out_d,
                               const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1,
                               int J, int V, int activation, int terms, float *dz_d, float *h_d, void *workspace_d,
-                              size_t workspace_bytes, void *stream)
+                              size_t workspace_bytes, void *stream, bool f16 = false)
 {
     if (int rc = split_check(B, T, U1, J, V, terms, 0, activation)) return rc;
     WR_REQUIRE(V % (g16 ? 8 : 4) == 0 && V >= 32, WR_EUNSUPPORTED,
@@ -1935,25 +2045,33 @@ int joint_bwd_dz_split_launch(const void *gout_d, bool g16, const float *ep_d, c
     hipStream_t st = static_cast<hipStream_t>(stream);
     unsigned short *wh = static_cast<unsigned short *>(workspace_d);
     unsigned short *wl = reinterpret_cast<unsigned short *>(static_cast<char *>(workspace_d) + img);
-    hipLaunchKernelGGL(split_w_dz_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, D, n_jt, wh, wl);
-    WR_CHECK_LAUNCH("split_w_dz_kernel");
+    if (f16) {                                              // f16 operands (terms == 1): one image
+        hipLaunchKernelGGL(split_w_dz_f16_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, D, n_jt, reinterpret_cast<_Float16 *>(wh));
+        WR_CHECK_LAUNCH("split_w_dz_f16_kernel");
+    } else {
+        hipLaunchKernelGGL(split_w_dz_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, D, n_jt, wh, wl);
+        WR_CHECK_LAUNCH("split_w_dz_kernel");
+    }
     const long M = (long)B * T * U1;
     const dim3 grid((unsigned)((M + kSM - 1) / kSM));
     {                                                       // 128-cell tiling, W fragments staged in LDS
         const size_t lds = (size_t)kZStages * 2 * 16 * 64 * 16 + (size_t)kZM2 * (2 * sizeof(long) + sizeof(int));
         const dim3 grid2((unsigned)((M + kZM2 - 1) / kZM2));
-#define WR_LAUNCH_DZ2(TERMS, FULL_, GT)                                                                                \
+#define WR_LAUNCH_DZ2(TERMS, FULL_, GT, OpT)                                                                           \
         do {                                                                                                          \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_bwd_dz_split128_kernel<TERMS, FULL_, GT>),   \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_bwd_dz_split128_kernel<TERMS, FULL_, GT, OpT>), \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
-            hipLaunchKernelGGL((joint_bwd_dz_split128_kernel<TERMS, FULL_, GT>), grid2, dim3(256), lds, st,             \
+            hipLaunchKernelGGL((joint_bwd_dz_split128_kernel<TERMS, FULL_, GT, OpT>), grid2, dim3(256), lds, st,        \
                                static_cast<const GT *>(gout_d), ep_d, pp_d,                                            \
                                reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl),               \
                                logit_lengths_d, target_lengths_d, B, T, U1, J, V, D, n_jt, activation, dz_d, h_d);     \
         } while (0)
-#define WR_LAUNCH_DZ2_T(TERMS, FULL_) do { if (g16) WR_LAUNCH_DZ2(TERMS, FULL_, __bf16); else WR_LAUNCH_DZ2(TERMS, FULL_, float); } while (0)
-        if (n_jt == 16) { if (terms == 3) WR_LAUNCH_DZ2_T(3, true); else WR_LAUNCH_DZ2_T(1, true); }
+#define WR_LAUNCH_DZ2_T(TERMS, FULL_) do { if (g16) WR_LAUNCH_DZ2(TERMS, FULL_, __bf16, __bf16); else WR_LAUNCH_DZ2(TERMS, FULL_, float, __bf16); } while (0)
+#define WR_LAUNCH_DZ2_H(FULL_) do { if (g16) WR_LAUNCH_DZ2(1, FULL_, _Float16, _Float16); else WR_LAUNCH_DZ2(1, FULL_, float, _Float16); } while (0)
+        if (f16) { if (n_jt == 16) WR_LAUNCH_DZ2_H(true); else WR_LAUNCH_DZ2_H(false); }
+        else if (n_jt == 16) { if (terms == 3) WR_LAUNCH_DZ2_T(3, true); else WR_LAUNCH_DZ2_T(1, true); }
         else { if (terms == 3) WR_LAUNCH_DZ2_T(3, false); else WR_LAUNCH_DZ2_T(1, false); }
+#undef WR_LAUNCH_DZ2_H
 #undef WR_LAUNCH_DZ2_T
 #undef WR_LAUNCH_DZ2
         WR_CHECK_LAUNCH("joint_bwd_dz_split128_kernel");
@@ -1969,6 +2087,16 @@ extern "C" int wr_joint_bwd_dz_split(const float *gout_d, const float *ep_d, con
 {
     return joint_bwd_dz_split_launch(gout_d, false, ep_d, pp_d, w_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V,
                                      activation, terms, dz_d, h_d, workspace_d, workspace_bytes, stream);
+}
+
+extern "C" int wr_joint_bwd_dz_f16(const void *gout_d, int gout_dtype, const float *ep_d, const float *pp_d, const float *w_out_d,
+                                   const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1,
+                                   int J, int V, int activation, float *dz_d, float *h_d, void *workspace_d,
+                                   size_t workspace_bytes, void *stream)
+{
+    WR_REQUIRE(gout_dtype == WR_F32 || gout_dtype == WR_F16, WR_EINVAL, "joint_bwd_dz_f16: gradient dtype must be WR_F32 or WR_F16");
+    return joint_bwd_dz_split_launch(gout_d, gout_dtype == WR_F16, ep_d, pp_d, w_out_d, logit_lengths_d, target_lengths_d, B, T,
+                                     U1, J, V, activation, 1, dz_d, h_d, workspace_d, workspace_bytes, stream, true);
 }
 
 extern "C" int wr_joint_bwd_dz_split_bf16(const void *gout_bf16_d, const float *ep_d, const float *pp_d, const float *w_out_d,
@@ -2131,7 +2259,8 @@ extern "C" size_t wr_joint_dw_split_workspace_bytes(int B, int T, int U1, int J,
 namespace {
 int joint_bwd_dw_split_launch(const void *gout_d, bool g16, const float *h_d, const int32_t *logit_lengths_d,
                               const int32_t *target_lengths_d, int B, int T, int U1, int J, int V, int terms,
-                              float *dw_d, float *db_d, void *workspace_d, size_t workspace_bytes, void *stream)
+                              float *dw_d, float *db_d, void *workspace_d, size_t workspace_bytes, void *stream,
+                              bool f16 = false)
 {
     if (int rc = split_check(B, T, U1, J, V, terms, 0)) return rc;
     WR_REQUIRE(V % 4 == 0 && J % 4 == 0, WR_EUNSUPPORTED,
@@ -2157,15 +2286,16 @@ int joint_bwd_dw_split_launch(const void *gout_d, bool g16, const float *h_d, co
     long rows_per_part = (M + parts - 1) / parts;
     rows_per_part = (rows_per_part + 15) / 16 * 16;
     const size_t lds = (size_t)kWStages * 2 * 2 * 2 * 4 * 64 * 16;   // three stages of ready-made fragments
-#define WR_LAUNCH_DW(TERMS, GT)                                                                                        \
+#define WR_LAUNCH_DW(TERMS, GT, OpT)                                                                                   \
     do {                                                                                                              \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_bwd_dw_split_kernel<TERMS, GT>),                 \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_bwd_dw_split_kernel<TERMS, GT, OpT>),            \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-        hipLaunchKernelGGL((joint_bwd_dw_split_kernel<TERMS, GT>), dim3(n_vs * n_js * parts), dim3(512), lds, st,       \
+        hipLaunchKernelGGL((joint_bwd_dw_split_kernel<TERMS, GT, OpT>), dim3(n_vs * n_js * parts), dim3(512), lds, st,  \
                            static_cast<const GT *>(gout_d), h_d, mask, M, V, J, n_vs, n_js, rows_per_part, part_dw, part_db); \
     } while (0)
-    if (g16) { if (terms == 3) WR_LAUNCH_DW(3, __bf16); else WR_LAUNCH_DW(1, __bf16); }
-    else { if (terms == 3) WR_LAUNCH_DW(3, float); else WR_LAUNCH_DW(1, float); }
+    if (f16) { if (g16) WR_LAUNCH_DW(1, _Float16, _Float16); else WR_LAUNCH_DW(1, float, _Float16); }
+    else if (g16) { if (terms == 3) WR_LAUNCH_DW(3, __bf16, __bf16); else WR_LAUNCH_DW(1, __bf16, __bf16); }
+    else { if (terms == 3) WR_LAUNCH_DW(3, float, __bf16); else WR_LAUNCH_DW(1, float, __bf16); }
 #undef WR_LAUNCH_DW
     WR_CHECK_LAUNCH("joint_bwd_dw_split_kernel");
     hipLaunchKernelGGL(split_dw_reduce_kernel, dim3(1024), dim3(256), 0, st, part_dw, part_db, parts, (long)V * J, V, dw_d,
@@ -2189,4 +2319,13 @@ extern "C" int wr_joint_bwd_dw_split_bf16(const void *gout_bf16_d, const float *
 {
     return joint_bwd_dw_split_launch(gout_bf16_d, true, h_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, terms, dw_d,
                                      db_d, workspace_d, workspace_bytes, stream);
+}
+
+extern "C" int wr_joint_bwd_dw_f16(const void *gout_d, int gout_dtype, const float *h_d, const int32_t *logit_lengths_d,
+                                   const int32_t *target_lengths_d, int B, int T, int U1, int J, int V, float *dw_d, float *db_d,
+                                   void *workspace_d, size_t workspace_bytes, void *stream)
+{
+    WR_REQUIRE(gout_dtype == WR_F32 || gout_dtype == WR_F16, WR_EINVAL, "joint_bwd_dw_f16: gradient dtype must be WR_F32 or WR_F16");
+    return joint_bwd_dw_split_launch(gout_d, gout_dtype == WR_F16, h_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, 1, dw_d,
+                                     db_d, workspace_d, workspace_bytes, stream, true);
 }

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .joint import _PRECISIONS, _resolve_precision, activation_code, joint_backward
+from .joint import _PRECISIONS, _call_precision, activation_code, joint_backward
 
 
 class _JointRnntFn(torch.autograd.Function):
@@ -202,13 +202,14 @@ def joint_rnnt_loss(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Tensor, b_o
     logits ever leaving the node.  ep (B, T, J) = enc_ffn(encoder_out), pp (B, U+1, J) = pred_ffn(predictor_out);
     targets (B, U) int32 with padding already mapped to a valid class; lengths (B,) int32; requires
     max(logit_lengths) == T and max(target_lengths) + 1 == U+1 like torchaudio's rnnt_loss.
-    ``precision``: "fp32" (exact MFMA, default) or "bf16x3" (split precision, joint.py); reduction as rnnt_loss.
+    ``precision``: "fp32" (exact MFMA, default), "bf16x3" (split precision, joint.py) or "autocast" outside autocast (= "fp32");
+    the 16-bit modes are refused; reduction as rnnt_loss.
     ``buckets``: at most this many groups by label length, each padded to its own maxima (`plan_buckets`; default from
     WR_FUSED_BUCKETS, 4; 1 = one call for the whole batch).  Costs come back in the caller's utterance order."""
     if reduction not in ("none", "mean", "sum"):
         raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
-    precision = _resolve_precision(precision)
-    if precision == "bf16":
+    precision = _call_precision(precision)             # "autocast": "fp32" outside autocast, a 16-bit mode under it
+    if precision in ("bf16", "f16"):
         raise ValueError("joint_rnnt_loss: the AMP single-term mode keeps 16-bit logits; use TransducerJoint + rnnt_loss")
     V = w_out.shape[0]
     if blank < 0:

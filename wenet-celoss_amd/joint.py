@@ -17,6 +17,14 @@ accumulation): logits within 1e-4 of the fp32 result relative to their scale, 2.
 under autocast the logits come out in the autocast dtype.  In both modes the activation gradient ``dZ = dY W``
 and the weight gradient ``dW = dY^T H`` use the same split (``wr_joint_bwd_dz_split``, ``wr_joint_bwd_dw_split``,
 when V is a multiple of 4; otherwise the exact kernels); the bias gradient is summed in fp32.
+``precision="f16"`` is the same single-term mode with float16 operands (``wr_joint_fwd_f16``: the operand format of the
+reference's ``ffn_out`` under its default fp16 autocast, 11 significand bits against bf16's 8); its logits follow the
+``"bf16"`` rule.  With a float32 logits gradient, or a float16 one under ``WR_AMP_BACKWARD=kernels``, its backward runs
+``wr_joint_bwd_dz_f16`` / ``wr_joint_bwd_dw_f16``; a float16 gradient otherwise takes the library GEMMs (already fp16), a
+bfloat16 one (bf16 autocast) the ``"bf16"`` backward.
+``precision="autocast"`` is resolved at every call (``effective_precision``): ``"fp32"`` outside autocast (the reference's
+``cv`` pass and runs without ``--use_amp``), ``"bf16"`` under bf16 autocast, ``"f16"`` under fp16 autocast -- the
+recommended ``WR_JOINT_PRECISION`` for ``--use_amp``.
 
 Supported configurations: ``joint_mode='add'`` (the only mode the reference accepts, joint.py:22); every
 ``activation`` of ``get_activation`` (common.py:228-242: tanh -- shipped --, relu, hardtanh, selu, swish, gelu; value
@@ -35,7 +43,9 @@ from torch import nn
 
 from . import _lib
 
-_PRECISIONS = {"fp32": 0, "bf16x3": 3, "bf16": 1}
+# name -> `terms` code of the kernels; TERMS_F16 selects the f16 single-term entry points; "autocast" is resolved per call
+TERMS_F16 = 16
+_PRECISIONS = {"fp32": 0, "bf16x3": 3, "bf16": 1, "f16": TERMS_F16, "autocast": None}
 
 
 def activation_code(activation: str) -> int:
@@ -55,6 +65,27 @@ def _resolve_precision(precision: Optional[str]) -> str:
     if precision not in _PRECISIONS:
         raise ValueError(f"joint precision must be one of {sorted(_PRECISIONS)}, got {precision!r}")
     return precision
+
+
+def effective_precision(precision: str, autocast_enabled: bool, autocast_dtype) -> str:
+    """The mode a call runs in: "autocast" becomes "fp32" outside autocast, "bf16" under bf16 autocast and "f16" under fp16
+    autocast; every other name stands for itself."""
+    if precision != "autocast":
+        return precision
+    if not autocast_enabled:
+        return "fp32"
+    if autocast_dtype == torch.float16:
+        return "f16"
+    if autocast_dtype == torch.bfloat16:
+        return "bf16"
+    return "fp32"
+
+
+def _call_precision(precision: Optional[str]) -> str:
+    """_resolve_precision, then effective_precision under the current CUDA autocast state."""
+    precision = _resolve_precision(precision)
+    on = torch.is_autocast_enabled("cuda")
+    return effective_precision(precision, on, torch.get_autocast_dtype("cuda") if on else None)
 
 
 class _JointFn(torch.autograd.Function):
@@ -81,6 +112,15 @@ class _JointFn(torch.autograd.Function):
                                       _lib.ptr(tlens), B, T, U1, J, V, act, _lib.ptr(out), _lib.ptr(ws), ws_bytes,
                                       _lib.current_stream(dev))
             _lib.check(rc, "wr_joint_fwd")
+        elif terms == TERMS_F16:
+            out = torch.empty(B, T, U1, V, dtype=out_dtype, device=dev)
+            ws_bytes = lib.wr_joint_split_workspace_bytes(J, V)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                rc = lib.wr_joint_fwd_f16(_lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(b), _lib.ptr(llens),
+                                          _lib.ptr(tlens), B, T, U1, J, V, act, _lib.ptr(out), _lib.dtype_code(out_dtype),
+                                          _lib.ptr(ws), ws_bytes, _lib.current_stream(dev))
+            _lib.check(rc, "wr_joint_fwd_f16")
         else:
             out = torch.empty(B, T, U1, V, dtype=out_dtype, device=dev)
             ws_bytes = lib.wr_joint_split_workspace_bytes(J, V)
@@ -168,6 +208,59 @@ def _amp_backward_library(lib, gout, ep, pp, w, llens, tlens, need_w, need_b, go
     return d_ep, d_pp, d_w, d_b
 
 
+def _f16_backward(lib, gout, ep, pp, w, llens, tlens, need_w, need_b, gout_zero_in_padding, act):
+    """Backward of precision "f16" from a float16 or float32 logits gradient.  A float16 gradient (fp16 autocast) goes to the
+    library GEMMs, already fp16, unless WR_AMP_BACKWARD=kernels or torch.mm has no out_dtype; otherwise the f16 kernels
+    take it as it is (V % 8 == 0) or widened to fp32 (rounded back to f16 in the kernel: the same values).  V % 4 != 0 or
+    V < 32: the exact-fp32 kernels, as every split mode."""
+    B, T, J = ep.shape
+    U1 = pp.shape[1]
+    V = w.shape[0]
+    dev = ep.device
+    ok16 = V % 8 == 0 and V >= 32 and J % 4 == 0
+    if (ok16 and gout.dtype == torch.float16 and os.environ.get("WR_AMP_BACKWARD", "library") != "kernels"
+            and _mm_takes_out_dtype()):
+        return _amp_backward_library(lib, gout.contiguous(), ep, pp, w, llens, tlens, need_w, need_b, gout_zero_in_padding, act)
+    if V % 4 != 0 or V < 32:
+        return joint_backward(gout, ep, pp, w, llens, tlens, 0, need_w, need_b, gout_zero_in_padding, act)
+    g16 = gout.dtype == torch.float16 and ok16
+    gout = gout.contiguous() if g16 else gout.float().contiguous()
+    gcode = _lib.WR_F16 if g16 else _lib.WR_F32
+    dz = torch.empty(B, T, U1, J, dtype=torch.float32, device=dev)
+    h = torch.empty_like(dz) if need_w else None
+    wsb = lib.wr_joint_dz_split_workspace_bytes(J, V)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.wr_joint_bwd_dz_f16(_lib.ptr(gout), gcode, _lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(llens),
+                                     _lib.ptr(tlens), B, T, U1, J, V, act, _lib.ptr(dz), _lib.ptr(h), _lib.ptr(ws), wsb,
+                                     _lib.current_stream(dev))
+    _lib.check(rc, "wr_joint_bwd_dz_f16")
+    d_ep = dz.sum(dim=2)
+    d_pp = dz.sum(dim=1)
+    d_w = d_b = None
+    if gout_zero_in_padding:
+        llens = tlens = None
+    if need_w:
+        d_w = torch.empty(V, J, dtype=torch.float32, device=dev)
+        d_b = torch.empty(V, dtype=torch.float32, device=dev)
+        wsb = lib.wr_joint_dw_split_workspace_bytes(B, T, U1, J, V)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.wr_joint_bwd_dw_f16(_lib.ptr(gout), gcode, _lib.ptr(h), _lib.ptr(llens), _lib.ptr(tlens), B, T, U1, J, V,
+                                         _lib.ptr(d_w), _lib.ptr(d_b), _lib.ptr(ws), wsb, _lib.current_stream(dev))
+        _lib.check(rc, "wr_joint_bwd_dw_f16")
+    elif need_b:
+        g2 = gout.float().view(-1, V)
+        if llens is not None:
+            tt = torch.arange(T, device=dev)[None, :, None] < llens[:, None, None]
+            uu = torch.arange(U1, device=dev)[None, None, :] <= tlens[:, None, None]
+            g2 = torch.where((tt & uu).view(-1, 1), g2, torch.zeros((), device=dev))
+        d_b = g2.sum(0)
+    if not need_b:
+        d_b = None
+    return d_ep, d_pp, d_w, d_b
+
+
 def joint_backward(gout, ep, pp, w, llens, tlens, terms: int, need_w: bool, need_b: bool,
                    gout_zero_in_padding: bool = False, act: int = 0):
     """Backward of the joiner from the logits gradient `gout` (B,T,U1,V): returns (d_ep, d_pp, d_w, d_b).
@@ -180,6 +273,10 @@ def joint_backward(gout, ep, pp, w, llens, tlens, terms: int, need_w: bool, need
     U1 = pp.shape[1]
     V = w.shape[0]
     dev = ep.device
+    if terms == TERMS_F16 and gout.dtype == torch.bfloat16:
+        terms = 1                                   # "f16" under bf16 autocast: the "bf16" backward, as it stands
+    if terms == TERMS_F16:
+        return _f16_backward(lib, gout, ep, pp, w, llens, tlens, need_w, need_b, gout_zero_in_padding, act)
     # AMP step: the loss hands back a bf16 gradient for bf16 logits; the split kernels take it as it is (bf16 values are
     # their own hi parts) -- no widening pass over the logits-sized tensor, half the gradient bytes in dZ and dW
     ok16 = terms != 0 and V % 8 == 0 and V >= 32 and J % 4 == 0
@@ -247,11 +344,11 @@ def joint_logits(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Tensor, b_out:
                  activation: str = "tanh") -> torch.Tensor:
     """ffn_out(act(ep[:, :, None] + pp[:, None])) -> (B, T, U1, V); `activation` one of _lib.ACTIVATIONS (default tanh).  With lengths, cells in the
     padded region are left unwritten (they are never read by the RNN-T loss).  ``precision``: see the
-    module docstring ("fp32" exact, "bf16x3" split, "bf16" AMP)."""
-    precision = _resolve_precision(precision)
+    module docstring ("fp32" exact, "bf16x3" split, "bf16" / "f16" AMP, "autocast" resolved per call)."""
+    precision = _call_precision(precision)
     terms = _PRECISIONS[precision]
     out_dtype = torch.float32
-    if precision == "bf16" and torch.is_autocast_enabled("cuda"):
+    if precision in ("bf16", "f16") and torch.is_autocast_enabled("cuda"):
         out_dtype = torch.get_autocast_dtype("cuda")
     if (logit_lengths is None) != (target_lengths is None):
         raise RuntimeError("joint_logits: pass both length tensors or neither")

@@ -31,7 +31,7 @@ from torch.nn.utils.rnn import pad_sequence
 from .common import IGNORE_ID, LabelSmoothingLoss, add_blank, add_sos_eos, end_blank, reverse_pad_list
 from .decoder import DecoderCache
 from .fused import joint_rnnt_loss, plan_buckets
-from .joint import TransducerJoint, _resolve_precision
+from .joint import TransducerJoint, _call_precision
 from .rnnt_loss import rnnt_loss
 from .search.greedy_search import basic_greedy_search, basic_greedy_search_both, basic_greedy_search_hw
 from .search.prefix_beam_search import PrefixBeamSearch
@@ -142,8 +142,9 @@ class Transducer(nn.Module):
 
     def _can_fuse_loss(self) -> bool:
         jt = self.joint
+        # the AMP single-term modes keep 16-bit logits ("autocast" is one of them under autocast only)
         return (self.fused_loss and isinstance(jt, TransducerJoint)
-                and _resolve_precision(jt.precision) != "bf16")        # the AMP single-term mode keeps 16-bit logits
+                and _call_precision(jt.precision) not in ("bf16", "f16"))
 
     @torch.jit.unused      # wenet/bin/train.py:203-205 scripts the model as an export smoke test; the HIP-backed forward
     def forward(self, speech: torch.Tensor, speech_lengths: torch.Tensor, text: torch.Tensor,  # is opaque to TorchScript
