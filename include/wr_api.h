@@ -71,7 +71,10 @@ const char *wr_last_error(void);
  * cells -- measured slower), key 13: its logit stores (0: cell-major tiles through a per-wave LDS stage as whole lines, the
  * default; 1: transposed tiles stored from registers in 8/16-byte pieces -- measured slower).  Keys 6-13 pick between kernels that compute the
  * same sums; the two dZ tilings are bit-identical, the dW tilings differ in the order of fp32 additions, the folded
- * projection in the rounding of one composed weight matrix (formed in float64). */
+ * projection in the rounding of one composed weight matrix (formed in float64).  key 14: dead-cell skip of the RNN-T
+ * gradient pass (1, the default: a cell whose every exponential is provably +0 -- its log-occupancy and the bounds of
+ * its blank and label terms below -110 nats, a finite row log-sum-exp -- is written as grad_costs[b] * 0 without
+ * reading its logits; 0: every valid cell reads its logits) -- bit-identical results either way. */
 int wr_tune_set(int key, int value);
 
 /* ------------------------------------------------------------------------

@@ -42,11 +42,15 @@ if os.environ.get("SWEEP") == "grid2":         # gradient-pass grid with the row
     variants = [dict(lse=0, grad=g, nt=7, un=16, lun=16) for g in (16, 64, 128, 256, 512, 768, 1024, 1400, 0)]
 if os.environ.get("SWEEP") == "auto":          # automatic grids: non-temporal bits and vectors in flight once more
     variants = [dict(lse=0, grad=0, nt=nt, un=u, lun=lu) for nt in (7, 3, 5, 6) for u, lu in ((16, 16), (8, 8), (16, 8), (8, 16))]
+if os.environ.get("SWEEP") == "skip":          # gradient-pass grid with the dead-cell skip (key 14) on; the automatic grid is
+    # about 340 workgroups per CU here (68 KB of logits per wave at B=8); the last variant streams every valid cell
+    variants = [dict(lse=0, grad=g, nt=7, un=16, lun=16, skip=1) for g in (0, 170, 250, 340, 500, 700, 1000)]
+    variants.append(dict(lse=0, grad=0, nt=7, un=16, lun=16, skip=0))
 STEPS = int(os.environ.get("STEPS", 1))
 res = {i: ([], []) for i in range(len(variants))}
 for rnd in range(int(os.environ.get("ROUNDS", 5))):
     for i, v in enumerate(variants):
-        lib.wr_tune_set(0, v["lse"]); lib.wr_tune_set(1, v["grad"]); lib.wr_tune_set(2, v["nt"]); lib.wr_tune_set(3, v["un"]); lib.wr_tune_set(4, v["lun"])
+        lib.wr_tune_set(0, v["lse"]); lib.wr_tune_set(1, v["grad"]); lib.wr_tune_set(2, v["nt"]); lib.wr_tune_set(3, v["un"]); lib.wr_tune_set(4, v["lun"]); lib.wr_tune_set(14, v.get("skip", 1))
         fwd(); bwd(); torch.cuda.synchronize()
         ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(STEPS)]
         for e in ev:

@@ -20,10 +20,14 @@
 //           (T + U dependent steps, ~0.26 us each: 0.30 ms at the BASELINE shape).
 //   pass 3  rnnt_grad_kernel   one wave per cell again: re-reads the V logits,
 //           writes grad = g_b * (exp(logit + alpha + beta + cost - denom) with
-//           the blank / label corrections), zero in the padded region.
-//           HBM-bound: 4*V read + 4*V written per cell.
+//           the blank / label corrections), zero in the padded region.  A dead
+//           cell (every exponential provably +0, kDeadThr) is written as
+//           g_b * 0 without reading its logits.
+//           HBM-bound: 4*V read (live cells only) + 4*V written per cell.
 //
-// Algorithmic traffic: 3 * 4 * V bytes per valid cell (+ 4*V per padded cell).
+// Algorithmic traffic: 3 * 4 * V bytes per live valid cell, 2 * 4 * V per dead
+// cell (+ 4*V per padded cell).  Dead cells are about 30 % of the BASELINE
+// batch (iid N(0,1) logits); the share depends on the data.
 #include "row_stream.hpp"
 #include "wr_common.hpp"
 
@@ -215,6 +219,30 @@ __global__ __launch_bounds__(kRnntMaxCols) void rnnt_sweep_kernel(
 }
 
 // ------------------------------------------------------------------ pass 3 --
+// Dead cells.  Every exponential of a cell's gradient is bounded without its logits: x <= denom for every logit x of
+// the row, so the main term's exponent x + alpha + beta + cost - denom is at most lo = alpha + beta + cost (the
+// cell's log-occupancy), the blank term's at most alpha + cost + beta(t+1,u) (alpha + cost at the final cell) and the
+// label term's at most alpha + cost + beta(t,u+1).  When every bound that applies is below kDeadThr, each
+// fast_exp2 of the row returns +0, the case-chain subtraction gives 0 - 0 = +0, and the gradient is finish(0) in
+// every element whatever the logits hold: such a row is written without being read.
+//
+// Bound on what the kernel itself evaluates (log2 units; u = 2^-24 is the fp32 unit roundoff):
+//   - denom >= max x up to its own rounding: pass 1 takes M = fl(max x * log2e) (fmaxf of rounded products is the
+//     rounded maximum), adds fast_log2(s) >= 0 (s >= 1: the maximum's own term is 2^0) and rounds (M + l) * ln2;
+//     the joiner epilogue (joint_lse.hpp) bounds a lane's ref + log2(s) the same way.  So x - denom <= 4u |denom|.
+//   - main term: c2 = fl(fl(cmd + be) * log2e) rounds a quantity of magnitude |lo - denom| twice and fmaf rounds
+//     once more.  Blank / label terms: blank_sub (lab_sub) = fl(cmd + beta') once, then the sum with x and the
+//     product with log2e once each.  For a negative bound every argument is therefore at most
+//     log2e * ((1 - 4u) * bound + 12u * |denom|).
+//   - |denom| < kDeadDenomMax = 2^16 caps the last term at 0.05 nats.  It is also the test that denom is finite: a
+//     +inf or NaN logit makes denom +inf or NaN, and such rows keep the streaming path and their NaN pattern.
+// With bound < -110 nats every argument is below -158.6 (log2): a margin of 8.6 to the -150 at which a correctly
+// rounded exp2 that keeps fp32 denormals first returns +0 (-126 if it flushes them; the margin is then 32.6).
+// tests/test_rnnt_dead_rows_gpu.py checks that __builtin_amdgcn_exp2f gives +0 for every float <= -151.  Every
+// comparison is written so that a NaN operand makes the row live.
+constexpr double kDeadThr = -110.0;
+constexpr float kDeadDenomMax = 65536.f;
+
 template <typename T, bool NT /* loads */, bool NTS /* stores */, int UN>
 __global__ __launch_bounds__(256) void rnnt_grad_kernel(
     const T *logits, const int32_t *__restrict__ targets,
@@ -222,7 +250,7 @@ __global__ __launch_bounds__(256) void rnnt_grad_kernel(
     int B, int Tmax, int U1max, int V, int blank, float clamp, int K, int S,
     const double *__restrict__ alpha_skew, const double *__restrict__ beta_skew,
     const float *__restrict__ denom, const double *__restrict__ cost_ws,
-    const float *__restrict__ grad_costs, T *grads)
+    const float *__restrict__ grad_costs, T *grads, int skip_dead)
 {
     typedef typename VecOf<T>::type vec_t;
     constexpr int N = VecOf<T>::N;
@@ -246,42 +274,60 @@ __global__ __launch_bounds__(256) void rnnt_grad_kernel(
         const vec_t *body = reinterpret_cast<const vec_t *>(row + h);
         vec_t *gbody = reinterpret_cast<vec_t *>(grow + h);
 
-        if (t >= T_ || u > U) {          // padded cell: gradient is exactly zero
+        // Lattice state is fp64; the combinations below are small in magnitude
+        // (log-occupancies), so they are formed in fp64 and only then rounded.
+        // Special entries (SURVEY.md App. A.1 case chain; first match wins): the blank term at the final cell and
+        // wherever t < T-1 (with beta(t+1,u): b1), the label term (with beta(t,u+1): b2) unless it is the blank.
+        const size_t dbase = (size_t)b * S * U1max;
+        const int s = t + u;
+        const bool valid = t < T_ && u <= U;
+        const bool final_cell = t == T_ - 1 && u == U;
+        const bool has_b1 = t < T_ - 1;
+        const bool blank_special = final_cell || has_b1;
+        double al = 0.0, be = 0.0, cost = 0.0, b1 = 0.0, b2 = 0.0;
+        float go = 1.f, d = 0.f;
+        int lab = -1;
+        bool has_lab = false;
+        if (valid) {
+            al = alpha_skew[dbase + (size_t)s * U1max + u];
+            be = beta_skew[dbase + (size_t)s * U1max + u];
+            cost = cost_ws[b];
+            if (grad_costs) go = grad_costs[b];
+            d = denom[r];
+            if (has_b1) b1 = beta_skew[dbase + (size_t)(s + 1) * U1max + u];
+            if (u < U) {
+                lab = targets[(size_t)b * (U1max - 1) + u];
+                if (lab == blank && blank_special) lab = -1;
+                else has_lab = true;
+            }
+            if (has_lab) b2 = beta_skew[dbase + (size_t)(s + 1) * U1max + (u + 1)];
+        }
+        const double ac = al + cost;
+        auto finish = [&](float val) -> float {
+            if (clamp > 0.f) val = fminf(fmaxf(val, -clamp), clamp);
+            return val * go;
+        };
+
+        // A padded cell's gradient is exactly zero; a dead cell's (kDeadThr: every bound that applies is below the
+        // threshold, a NaN anywhere makes the cell live) is finish(0).  Either row is written without being read.
+        const bool dead = skip_dead != 0 && fabsf(d) < kDeadDenomMax && ac + be < kDeadThr &&
+                          (!blank_special || (has_b1 ? ac + b1 : ac) < kDeadThr) && (!has_lab || ac + b2 < kDeadThr);
+        if (__builtin_amdgcn_readfirstlane((!valid || dead) ? 1 : 0)) {
+            const T val = valid ? (T)finish(0.f) : (T)0.f;
             vec_t z;
 #pragma unroll
-            for (int q = 0; q < N; ++q) z[q] = (T)0.f;
-            if (lane < h) grow[lane] = (T)0.f;
-            if (lane < tail) grow[h + N * nv + lane] = (T)0.f;
+            for (int q = 0; q < N; ++q) z[q] = val;
+            if (lane < h) grow[lane] = val;
+            if (lane < tail) grow[h + N * nv + lane] = val;
             for (int i = lane; i < nv; i += kWave) stv<NTS>(z, gbody + i);
             continue;
         }
 
-        const size_t dbase = (size_t)b * S * U1max;
-        const int s = t + u;
-        // Lattice state is fp64; the combinations below are small in magnitude
-        // (log-occupancies), so they are formed in fp64 and only then rounded.
-        const double al = alpha_skew[dbase + (size_t)s * U1max + u];
-        const double be = beta_skew[dbase + (size_t)s * U1max + u];
-        const double cost = cost_ws[b];
-        const float go = grad_costs ? grad_costs[b] : 1.f;
-        const double cmd = al + cost - (double)denom[r];      // g = logit + cm
+        const double cmd = ac - (double)d;          // g = logit + cm
         const float c2 = (float)(cmd + be) * kLog2e;
-
-        // special entries (SURVEY.md App. A.1 case chain; first match wins)
-        bool blank_special = false;
-        float blank_sub = 0.f;                      // exponent (natural log) of the subtracted term, minus logit
-        if (t == T_ - 1 && u == U) { blank_special = true; blank_sub = (float)cmd; }
-        else if (t < T_ - 1) {
-            blank_special = true;
-            blank_sub = (float)(cmd + beta_skew[dbase + (size_t)(s + 1) * U1max + u]);
-        }
-        int lab = -1;
-        float lab_sub = 0.f;
-        if (u < U) {
-            lab = targets[(size_t)b * (U1max - 1) + u];
-            if (lab == blank && blank_special) lab = -1;
-            else lab_sub = (float)(cmd + beta_skew[dbase + (size_t)(s + 1) * U1max + (u + 1)]);
-        }
+        // exponents (natural log) of the subtracted terms, minus the logit
+        const float blank_sub = final_cell ? (float)cmd : (has_b1 ? (float)(cmd + b1) : 0.f);
+        const float lab_sub = has_lab ? (float)(cmd + b2) : 0.f;
         const int blk = blank_special ? blank : -1;
 
         auto fix = [&](float val, float x, int v) -> float {
@@ -289,10 +335,6 @@ __global__ __launch_bounds__(256) void rnnt_grad_kernel(
             if (v == blk) val -= fast_exp2((x + blank_sub) * kLog2e);
             else if (v == lab) val -= fast_exp2((x + lab_sub) * kLog2e);
             return val;
-        };
-        auto finish = [&](float val) -> float {
-            if (clamp > 0.f) val = fminf(fmaxf(val, -clamp), clamp);
-            return val * go;
         };
 
         if (lane < h) {
@@ -516,7 +558,7 @@ extern "C" int wr_rnnt_loss_bwd(const void *logits_d, int dtype, const int32_t *
                        reinterpret_cast<const double *>(ws + w.alpha_off),                                           \
                        reinterpret_cast<const double *>(ws + w.beta_off),                                            \
                        reinterpret_cast<const float *>(ws + w.denom_off),                                            \
-                       reinterpret_cast<const double *>(ws + w.cost_off), grad_costs_d, static_cast<T *>(grads_d))
+                       reinterpret_cast<const double *>(ws + w.cost_off), grad_costs_d, static_cast<T *>(grads_d), skip)
 #define WR_LAUNCH_GRAD(T, NT)                                             \
     do {                                                                   \
         if (tune_get(kTuneGradUnroll) >= 16) { WR_LAUNCH_GRAD_U(T, NT, 16); } \
@@ -525,6 +567,7 @@ extern "C" int wr_rnnt_loss_bwd(const void *logits_d, int dtype, const int32_t *
     } while (0)
     const bool nt = (tune_get(kTuneNonTemporal) & 1) != 0;
     const bool nts = (tune_get(kTuneNonTemporal) & 2) != 0;
+    const int skip = tune_get(kTuneGradSkip) != 0 ? 1 : 0;
     if (dtype == WR_F32) { if (nt) WR_LAUNCH_GRAD(float, true); else WR_LAUNCH_GRAD(float, false); }
     else if (dtype == WR_F16) { if (nt) WR_LAUNCH_GRAD(_Float16, true); else WR_LAUNCH_GRAD(_Float16, false); }
     else { if (nt) WR_LAUNCH_GRAD(__bf16, true); else WR_LAUNCH_GRAD(__bf16, false); }
