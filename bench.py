@@ -20,10 +20,16 @@ value = utterances of the whole job per step / max-over-ranks time.
 Prints ONE JSON line on rank 0 (contract in the task statement), including
   roofline     -- for the dominant kernel (rnnt_grad_kernel: 2/3 of the bytes),
                   algorithmic bytes per launch / its mean duration measured with
-                  HIP events on the launch stream inside the timed region;
+                  HIP events on the launch stream inside the timed region.
+A plain run does only that: set-up, warm-up, the timed steps, --dump-outputs, the
+line.  --full adds the measurements that take runs of their own, after the timed
+region:
+  roofline.device_copy_GBps -- the runtime's device-to-device copy of the
+                  logits-sized buffer (what this part gives a plain copy);
   cpu_baseline -- the threaded fp32 CPU port (oracle/rnnt_baseline.c, "port")
-                  timed on this box's host cores on a bounded sample of the same
-                  (T,U,V) utterances (N=1 only).
+                  timed on the host cores on a bounded sample of the same
+                  (T,U,V) utterances (N=1 only);
+  extra        -- the secondary measurements of tools/secondary.py (N=1 only).
 """
 from __future__ import annotations
 
@@ -61,17 +67,29 @@ def parse():
                          "backend for the barrier -- exercises the N>1 code path on a 1-GPU box; the line is marked")
     ap.add_argument("--launch-timeout", type=float, default=3000.0,
                     help="self-launch only: seconds after which ranks that are still running are stopped (exit code 3)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="utterances timed on the CPU (-1: auto, 0: skip)")
-    ap.add_argument("--cpu-seconds", type=float, default=25.0, help="target CPU time budget for the baseline")
-    ap.add_argument("--extra-seconds", type=float, default=90.0,
-                    help="N=1 only: time budget of the secondary measurements appended as \"extra\" (tools/secondary.py: "
-                         "joiner TFLOP/s, loss-block step, CTC, greedy, beam, hot-word); 0 skips them")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the device-copy "
+                         "calibration (roofline.device_copy_GBps), and at N=1 the CPU baseline and the secondary "
+                         "measurements (\"extra\")")
+    ap.add_argument("--cpu-sample", type=int, help="--full: utterances timed on the CPU (-1: auto, the default; 0: skip)")
+    ap.add_argument("--cpu-seconds", type=float, help="--full: target CPU time budget for the baseline (default 25)")
+    ap.add_argument("--extra-seconds", type=float,
+                    help="--full, N=1 only: time budget of the secondary measurements appended as \"extra\" "
+                         "(tools/secondary.py: joiner TFLOP/s, loss-block step, CTC, greedy, beam, hot-word; default 90); "
+                         "0 skips them")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32): the "
                          "per-utterance costs and the gradient, whole if it fits 32 MiB, else a fixed seeded sample of it")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:                                  # 0 (skip) is what a plain run does anyway
+        given = [f"--{k.replace('_', '-')}" for k in ("cpu_sample", "cpu_seconds", "extra_seconds") if getattr(args, k)]
+        if given:
+            ap.error(f"{', '.join(given)}: only with --full")
+    for k, default in (("cpu_sample", -1), ("cpu_seconds", 25.0), ("extra_seconds", 90.0)):
+        if getattr(args, k) is None:
+            setattr(args, k, default)
     return args
 
 
@@ -253,7 +271,7 @@ def main():
     # logits-sized buffer (one read + one write per byte, like the gradient pass).  MI355X parts differ
     # by several per cent in sustained HBM rate; this says what this device gives a plain copy.
     copy_gbs = None
-    if not inplace:
+    if args.full and not inplace:
         cms = []
         for _ in range(3):
             c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -327,9 +345,9 @@ def main():
 
     if args.rehearse_on_one_gpu:
         out["rehearsal"] = "ranks share one device (development run, not a scaling measurement)"
-    if rank == 0 and world == 1 and args.cpu_sample != 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample != 0:
         out["cpu_baseline"] = cpu_baseline(args, logits if not inplace else None, targets, llens, tlens, costs, gen, dev)
-    if rank == 0 and world == 1 and args.extra_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.extra_seconds > 0:
         # secondary metrics (SURVEY.md 8d "Secondary"), after the timed region and the CPU baseline, every leg guarded
         # on its own; the 193 GB of headline buffers are released first
         fwd = bwd = None

@@ -251,6 +251,20 @@ def test_bench_self_launch_names_the_missing_devices():
     assert r.returncode != 0 and "WORLD_SIZE=4" in r.stderr
 
 
+def test_bench_side_measurement_options_need_full():
+    """The CPU baseline and secondary-measurement budgets belong to `bench.py --full`: asking a plain run for them is
+    refused before anything touches a GPU; 0 (skip them) is what a plain run does and is accepted."""
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    bench = [sys.executable, os.path.join(ROOT, "bench.py")]
+    for extra in (["--cpu-sample", "4"], ["--extra-seconds", "30"], ["--cpu-seconds", "5", "--cpu-sample", "-1"]):
+        r = subprocess.run(bench + extra, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and "only with --full" in r.stderr and r.stdout == "", (extra, r.stderr)
+    r = subprocess.run(bench + ["--full", "--cpu-sample", "4", "--extra-seconds", "30", "--help"], env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout
+
+
 def test_plan_buckets_properties():
     """fused.plan_buckets: a partition of the batch in ascending label length that saves at least the stated share of
     lattice cells, or None (uniform batches, tiny batches, savings below the bar)."""

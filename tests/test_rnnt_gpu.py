@@ -382,3 +382,32 @@ def test_bench_dump_outputs_are_the_last_step_and_repeat(tmp_path):
     assert sorted(d1) == ["costs.npy", "grads_sample.npy"] and d1["grads_sample.npy"].size > 10**6
     assert all(np.array_equal(d1[k], d2[k]) for k in d1)
     assert np.abs(d1["grads_sample.npy"]).max() > 0
+
+
+def test_bench_plain_run_leaves_side_measurements_to_full(tmp_path):
+    """A plain bench.py run carries the headline and the timed steps' own roofline figures only; --full adds the
+    device-copy calibration, the CPU baseline and the secondary measurements, after the same timed steps with the same
+    results."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    shape = ["--B", "3", "--T", "12", "--U", "5", "--V", "20", "--steps", "2", "--warmup", "1"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--extra-seconds", "1"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *shape, *extra,
+                            "--dump-outputs", str(tmp_path / mode)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[mode] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert plain[k] == full[k], k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["roofline"]["avg_ms"] > 0
+    assert "cpu_baseline" not in plain and "extra" not in plain and plain["roofline"]["device_copy_GBps"] is None
+    assert full["roofline"]["device_copy_GBps"] > 0
+    assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["max_rel_cost_diff_vs_gpu"] < 1e-4
+    assert "joiner" in full["extra"] and "error" not in full["extra"]
+    for name in ("costs.npy", "grads.npy"):
+        assert np.array_equal(np.load(tmp_path / "plain" / name), np.load(tmp_path / "full" / name)), name

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Secondary measurements for bench.py's `"extra"` object (SURVEY.md section 8d "Secondary": CTC loss+grad utt/s, joiner
 TFLOP/s, greedy steps/s and utt/s, beam frames/s) -- the numbers `tools/bench_extra.py` prints in development, in a
-bounded form (about 20-40 s on one MI355X) so that the driver-run bench line carries them.
+bounded form (about 20-40 s on one MI355X) so that the `bench.py --full` line carries them.
 
 Every leg is guarded on its own: a failure is recorded as {"error": ...} and the other legs still run; the headline
 fields of bench.py never depend on anything here.  All legs go through the product's public entry points (the C-ABI via
