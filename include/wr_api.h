@@ -128,6 +128,12 @@ int wr_rnnt_loss_fwd_from_lse(const float *logits_d, const int32_t *targets_d,
                               int B, int Tmax, int U1max, int V, int blank, float *costs_d /* [B] out */,
                               void *workspace_d, size_t workspace_bytes, void *stream);
 
+/* The lattice sweeps alone, with no logits at all: for a workspace whose row statistics were written by
+ * wr_joint_rnnt_stats (below), which repairs an overflowed row itself -- there is no pass-1 fallback here.  costs as
+ * wr_rnnt_loss_fwd. */
+int wr_rnnt_loss_sweeps(const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax, int U1max,
+                        float *costs_d /* [B] out */, void *workspace_d, size_t workspace_bytes, void *stream);
+
 /* Diagnostic view of the lattice state left in the workspace by wr_rnnt_loss_fwd
  * (tests compare alpha/beta with the oracle): copies alpha and beta into plain
  * [B, Tmax, U1max] float arrays (entries outside the valid region are 0). */
@@ -205,6 +211,35 @@ int wr_joint_fwd_lse(const float *ep_d, const float *pp_d, const float *w_out_d,
                      float *out_d /* [B,T,U1,V] */,
                      void *workspace_d, size_t workspace_bytes,
                      void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream);
+
+/* Joiner + RNN-T loss without a logits tensor (the memory-bounded fused node, fused.py `logits_budget`).
+ *
+ * wr_joint_rnnt_stats: the joiner forward with the row statistics of wr_joint_fwd_lse as its only output -- denom and the
+ * blank / label log-probabilities go into the RNN-T workspace, no logit is stored.  A row whose partial sums overflow
+ * (more than 88 nats of spread) is repaired by a second launch of the same kernel with a running maximum, whose
+ * workgroups leave at once unless the first launch raised the flag.  Then wr_rnnt_loss_sweeps.
+ * terms: 0 = exact fp32 (workspace wr_joint_workspace_bytes), 3 = split precision (wr_joint_split_workspace_bytes).
+ *
+ * wr_joint_rnnt_grad: the loss gradient grad_costs[b] * d cost_b / d logits of the cells [cell_begin, cell_end) of the
+ * flattened (B, T, U1) lattice into g_out [(cell_end - cell_begin), V]: every 64-cell logits tile is recomputed by the
+ * same forward kernel (bit-identical to the logits the statistics were taken from) and turned into the gradient in its
+ * epilogue with the formula of wr_rnnt_loss_bwd (same clamp, same zero outside [0,T_b) x [0,U_b]).  Needs the workspace
+ * after wr_joint_rnnt_stats + wr_rnnt_loss_sweeps; it only reads it.  w_ready != 0: `workspace_d` already holds the
+ * re-laid W of an earlier wr_joint_rnnt_grad call with the same W, terms and kernel selection (the slices of one backward
+ * share it); 0 = lay it out first.  Other arguments as wr_joint_rnnt_stats. */
+int wr_joint_rnnt_stats(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
+                        const int32_t *logit_lengths_d, const int32_t *target_lengths_d, const int32_t *targets_d,
+                        int B, int T, int U1, int J, int V, int activation, int blank, int terms,
+                        void *workspace_d, size_t workspace_bytes,
+                        void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream);
+
+int wr_joint_rnnt_grad(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
+                       const int32_t *logit_lengths_d, const int32_t *target_lengths_d, const int32_t *targets_d,
+                       int B, int T, int U1, int J, int V, int activation, int blank, float clamp, int terms,
+                       const float *grad_costs_d /* [B] or NULL */,
+                       const void *rnnt_workspace_d, size_t rnnt_workspace_bytes,
+                       long long cell_begin, long long cell_end, float *g_out_d /* [cell_end - cell_begin, V] */,
+                       void *workspace_d, size_t workspace_bytes, int w_ready, void *stream);
 
 int wr_joint_bwd_dz(const float *gout_d /* [B,T,U1,V] */, const float *ep_d, const float *pp_d,
                     const float *w_out_d,

@@ -378,13 +378,17 @@ def bench_step(args):
         ll[0], tl[-1] = T, U
     base = None
     precs = ("fp32", "fp32-fused", "bf16x3", "bf16x3-fused", "bf16-autocast", "bf16-autocast-f16", "f16-autocast-f16")
+    if args.budget_mb:                                 # the memory-bounded node beside the one that keeps the logits
+        precs = ("fp32-fused", "fp32-bounded", "bf16x3-fused", "bf16x3-bounded")
     if args.only:
         precs = tuple(x for x in precs if x in args.only.split(","))
     for prec in precs:
         amp = "-autocast" in prec                      # the --use_amp configuration (executor.py:91)
         adt = torch.float16 if prec.endswith("-f16") else torch.bfloat16      # "-f16": fp16 autocast, the reference's default
-        fused = prec.endswith("-fused")                # joiner + loss as one node (fused.py): no pass 1, gradient in place
-        jprec = prec.split("-")[0] if amp else prec.replace("-fused", "")
+        bounded = prec.endswith("-bounded")            # the same node without a logits tensor (logits_budget)
+        fused = prec.endswith("-fused") or bounded     # joiner + loss as one node (fused.py): no pass 1, gradient in place
+        jprec = prec.split("-")[0] if amp else prec.replace("-fused", "").replace("-bounded", "")
+        budget = int(args.budget_mb * (1 << 20)) if bounded else None
         joint = w.TransducerJoint(V, E, P, J, precision=jprec).to(dev)
         torch.manual_seed(4)
         with torch.no_grad():
@@ -397,17 +401,22 @@ def bench_step(args):
                 if fused:
                     loss = w.joint_rnnt_loss(joint.enc_ffn(enc), joint.pred_ffn(pred), joint.ffn_out.weight,
                                              joint.ffn_out.bias, y, ll, tl, blank=0, reduction="mean", precision=jprec,
-                                             buckets=args.buckets)
+                                             buckets=args.buckets, logits_budget=budget)
                 else:
                     logits = joint(enc, pred, ll, tl) if args.ragged else joint(enc, pred)
                     loss = w.rnnt_loss(logits, y, ll, tl, blank=0, reduction="mean", inplace_grad=True)
             loss.backward()
             return loss
         loss = step()
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
         ms = timeit(step, args.steps)
         rec = {"what": "joint+rnnt_loss fwd+bwd (autograd)", "precision": prec, "shape": [B, T, U + 1, J, V],
                "ragged": bool(args.ragged), "buckets": args.buckets if fused else None,
-               "ms": round(ms, 2), "utt_per_s": round(B / ms * 1e3, 1), "loss": float(loss)}
+               "ms": round(ms, 2), "utt_per_s": round(B / ms * 1e3, 1), "loss": float(loss),
+               "peak_gb": round(torch.cuda.max_memory_allocated() / 1e9, 2)}
+        if bounded:
+            rec["budget_mb"] = args.budget_mb
         if base is None:
             base = (float(loss), enc.grad.clone(), joint.ffn_out.weight.grad.clone())
         else:
@@ -435,6 +444,9 @@ if __name__ == "__main__":
     ap.add_argument("--ragged", action="store_true", help="step: frames in [0.8 T, T] sorted, labels in [U/3, U]")
     ap.add_argument("--buckets", type=int, default=4, help="step: label-length groups of the fused node (1 = off)")
     ap.add_argument("--only", default="", help="step: comma-separated subset of the configurations")
+    ap.add_argument("--budget-mb", type=float, default=0.0,
+                    help="step: time the memory-bounded fused node (logits_budget = this many MiB) beside the plain one, "
+                         "fp32 and bf16x3, with max_memory_allocated of each")
     ap.add_argument("--streams", type=int, default=64, help="greedy: independent streams decoded together")
     ap.add_argument("--tile", type=int, default=0, help="lane-GEMM tile policy of the decoders (wr_tune_set key 6)")
     a = ap.parse_args()

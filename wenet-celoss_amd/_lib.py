@@ -114,6 +114,10 @@ SIGNATURES = {
     "wr_joint_fwd_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp]),
     "wr_joint_fwd_split_lse": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
     "wr_rnnt_loss_fwd_from_lse": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "wr_rnnt_loss_sweeps": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "wr_joint_rnnt_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp]),
+    "wr_joint_rnnt_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _sz,
+                                ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _sz, _i, _vp]),
     "wr_joint_bwd_dz": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "wr_joint_split_workspace_bytes": (_sz, [_i, _i]),
     "wr_joint_fwd_split": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp]),

@@ -85,16 +85,19 @@ __device__ __forceinline__ void fill_h_tile(float *__restrict__ Ht, const float 
 // and no LDS write at all -- only the read-only activation tile lives in LDS.
 // LSE = true: the epilogue also produces the RNN-T loss's row statistics (joint_lse.hpp) -- the workgroup owns
 // every column of its 64 cells, so pass 1 of the loss never has to read the logits back.
-template <int PFK, int CT /* 32-column tiles per wave */, bool LSE, int NW = (CT == 2 ? 4 : 8) /* waves */>
+template <int PFK, int CT /* 32-column tiles per wave */, int EPI /* JointEpi */, int NW = (CT == 2 ? 4 : 8) /* waves */>
 __global__ __launch_bounds__(64 * NW) void joint_fwd_direct_kernel(
     const float *__restrict__ ep, const float *__restrict__ pp, const float *__restrict__ wt /* [Jp, Vp] */,
     const float *__restrict__ bias, const int32_t *__restrict__ llens, const int32_t *__restrict__ tlens,
     int B, int T, int U1, int J, int Jp, int V, int Vp, int act, float *__restrict__ out, JointLse lse)
 {
+    constexpr bool LSE = EPI == kEpiStoreLse || EPI == kEpiStats, STORE = EPI <= kEpiStoreLse, GRAD = EPI == kEpiGrad;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *Ht = lds;                                  // [Jp][65]
-    const long M = (long)B * T * U1;
-    const long m0 = (long)blockIdx.x * kBM;
+    if (EPI == kEpiStats && lse.run_if != nullptr && *lse.run_if == 0) return;
+    const long M = GRAD ? lse.m_end : (long)B * T * U1;
+    const long mb = GRAD ? lse.m_begin : 0;           // first cell of the launch (out row 0)
+    const long m0 = mb + (long)blockIdx.x * kBM;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float rm[32], rs[32];                             // LSE: this lane's (reference, partial sum) of its 32 rows
     if (LSE) {
@@ -111,7 +114,16 @@ __global__ __launch_bounds__(64 * NW) void joint_fwd_direct_kernel(
             const int b = (int)(bt / T), t = (int)(bt - (long)b * T);
             valid = (t < llens[b]) && (u <= tlens[b]);
         }
-        if (!__syncthreads_or(valid)) return;
+        if (!__syncthreads_or(valid)) {
+            if (GRAD) joint_epi_zero_rows(out, m0, M, mb, V);
+            return;
+        }
+    }
+    EpiRows er{};
+    if (!STORE) {
+        const size_t tile = (size_t)Jp * kHPad * sizeof(float);
+        er = joint_epi_rows(reinterpret_cast<char *>(lds) + (tile > joint_lse_exchange_bytes(NW) ? tile : joint_lse_exchange_bytes(NW)));
+        joint_epi_rows_init<EPI>(lse, er, llens, tlens, m0, M, T, U1);
     }
     fill_h_tile(Ht, ep, pp, m0, M, T, U1, J, Jp, act);
     __syncthreads();
@@ -174,14 +186,17 @@ __global__ __launch_bounds__(64 * NW) void joint_fwd_direct_kernel(
                     const int row = 32 * rt + (r & 3) + 8 * (r >> 2) + 4 * half;   // C/D layout of the 32x32 MFMA
                     const long m = m0 + row;
                     const float x = acc[rt][c][r] + bv;
-                    if (m < M && col < V) out[(size_t)m * V + col] = x;
-                    if (LSE) joint_lse_add(rm[rt * 16 + r], rs[rt * 16 + r], x, col < V, nc == 0 && c == 0);
+                    if (STORE && m < M && col < V) out[(size_t)m * V + col] = x;
+                    if (LSE) joint_lse_add_mode<EPI>(lse, rm[rt * 16 + r], rs[rt * 16 + r], x, col < V, nc == 0 && c == 0);
+                    if (EPI == kEpiStats) joint_epi_park(er, lse.blank, row, col, x);
+                    if (GRAD && m < M && col < V) out[(size_t)(m - mb) * V + col] = joint_epi_grad(er, lse.clamp, row, col, x);
                 }
         }
     }
     if (LSE) {
         __syncthreads();                               // every wave is done with the activation tile: reuse its storage
-        joint_lse_finish<NW>(lse, lds, rm, rs, llens, tlens, out, m0, M, T, U1, V);
+        joint_lse_finish<NW>(lse, lds, rm, rs, llens, tlens, out, m0, M, T, U1, V, EPI == kEpiStats ? er.xb : nullptr,
+                            EPI == kEpiStats ? er.xl : nullptr);
     }
 }
 
@@ -215,17 +230,20 @@ __global__ void joint_frag_w_kernel(const float *__restrict__ w, int V, int J, i
     }
 }
 
-template <bool LSE, int CT>
+template <int EPI /* JointEpi */, int CT>
 __global__ __launch_bounds__(512) void joint_fwd_frag_kernel(
     const float *__restrict__ ep, const float *__restrict__ pp, const float4 *__restrict__ wf, const float *__restrict__ bias,
     const int32_t *__restrict__ llens, const int32_t *__restrict__ tlens, int B, int T, int U1, int J, int Jp, int V, int Vp,
     int act, float *__restrict__ out, JointLse lse)
 {
+    constexpr bool LSE = EPI == kEpiStoreLse || EPI == kEpiStats, STORE = EPI <= kEpiStoreLse, GRAD = EPI == kEpiGrad;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int AS = Jp + 4;                            // row stride of the activation tile (floats)
     float *Ht = lds;                                  // [64][AS]
-    const long M = (long)B * T * U1;
-    const long m0 = (long)blockIdx.x * kBM;
+    if (EPI == kEpiStats && lse.run_if != nullptr && *lse.run_if == 0) return;
+    const long M = GRAD ? lse.m_end : (long)B * T * U1;
+    const long mb = GRAD ? lse.m_begin : 0;           // first cell of the launch (out row 0)
+    const long m0 = mb + (long)blockIdx.x * kBM;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
     float rm[32], rs[32];
@@ -242,7 +260,16 @@ __global__ __launch_bounds__(512) void joint_fwd_frag_kernel(
             const int b = (int)(bt / T), t = (int)(bt - (long)b * T);
             valid = (t < llens[b]) && (u <= tlens[b]);
         }
-        if (!__syncthreads_or(valid)) return;
+        if (!__syncthreads_or(valid)) {
+            if (GRAD) joint_epi_zero_rows(out, m0, M, mb, V);
+            return;
+        }
+    }
+    EpiRows er{};
+    if (!STORE) {
+        const size_t tile = (size_t)kBM * AS * sizeof(float);
+        er = joint_epi_rows(reinterpret_cast<char *>(lds) + (tile > joint_lse_exchange_bytes(8) ? tile : joint_lse_exchange_bytes(8)));
+        joint_epi_rows_init<EPI>(lse, er, llens, tlens, m0, M, T, U1);
     }
     // activation tile: Ht[row][k & 1][k >> 1]
     for (int row = wave; row < kBM; row += 8) {
@@ -322,15 +349,18 @@ __global__ __launch_bounds__(512) void joint_fwd_frag_kernel(
                     const int row = 32 * rt + (r & 3) + 8 * (r >> 2) + 4 * half;
                     const long m = m0 + row;
                     const float x = acc[rt][c][r] + bv;
-                    if (m < M && col < V) out[(size_t)m * V + col] = x;
-                    if (LSE) joint_lse_add(rm[rt * 16 + r], rs[rt * 16 + r], x, col < V, nc == 0 && c == 0);
+                    if (STORE && m < M && col < V) out[(size_t)m * V + col] = x;
+                    if (LSE) joint_lse_add_mode<EPI>(lse, rm[rt * 16 + r], rs[rt * 16 + r], x, col < V, nc == 0 && c == 0);
+                    if (EPI == kEpiStats) joint_epi_park(er, lse.blank, row, col, x);
+                    if (GRAD && m < M && col < V) out[(size_t)(m - mb) * V + col] = joint_epi_grad(er, lse.clamp, row, col, x);
                 }
         }
     }
 #undef WR_LOADF
     if (LSE) {
         __syncthreads();
-        joint_lse_finish<8>(lse, lds, rm, rs, llens, tlens, out, m0, M, T, U1, V);
+        joint_lse_finish<8>(lse, lds, rm, rs, llens, tlens, out, m0, M, T, U1, V, EPI == kEpiStats ? er.xb : nullptr,
+                            EPI == kEpiStats ? er.xl : nullptr);
     }
 }
 
@@ -650,10 +680,57 @@ extern "C" size_t wr_joint_workspace_bytes(int J, int V)
 }
 
 namespace {
-// shared body of wr_joint_fwd / wr_joint_fwd_lse
+// the statistics-only (kEpiStats, one launch plus the repair launch) and gradient (kEpiGrad) modes of either exact
+// forward kernel; W is already re-laid in `wsw` (Wt for the direct kernel, fragments for the frag kernel)
+int joint_fwd_epi_launch(bool frag, int epi, const float *ep_d, const float *pp_d, const void *wsw, const float *b_out_d,
+                         const int32_t *llens, const int32_t *tlens, int B, int T, int U1, int J, int Jp, int V, int Vp,
+                         int act, float *out_d, const JointLse &lse, hipStream_t st)
+{
+    const long cells = epi == kEpiGrad ? lse.m_end - lse.m_begin : (long)B * T * U1;
+    const dim3 grid((unsigned)((cells + kBM - 1) / kBM));
+    const size_t tile = frag ? (size_t)kBM * (Jp + 4) * sizeof(float) : (size_t)Jp * kHPad * sizeof(float);
+    const size_t lds = (tile > joint_lse_exchange_bytes(8) ? tile : joint_lse_exchange_bytes(8)) + joint_epi_rows_bytes();
+    WR_REQUIRE(lds <= 160 * 1024, WR_EUNSUPPORTED, "joint_fwd: J=%d needs %zu bytes of LDS", J, lds);
+#define WR_LAUNCH_EPI(EPI_, lse_)                                                                                      \
+    do {                                                                                                              \
+        if (frag) {                                                                                                   \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_frag_kernel<EPI_, 1>),                  \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
+            hipLaunchKernelGGL((joint_fwd_frag_kernel<EPI_, 1>), grid, dim3(512), lds, st, ep_d, pp_d,                 \
+                               static_cast<const float4 *>(wsw), b_out_d, llens, tlens, B, T, U1, J, Jp, V, Vp, act,   \
+                               out_d, lse_);                                                                          \
+        } else {                                                                                                      \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_direct_kernel<8, 1, EPI_>),             \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
+            hipLaunchKernelGGL((joint_fwd_direct_kernel<8, 1, EPI_>), grid, dim3(512), lds, st, ep_d, pp_d,            \
+                               static_cast<const float *>(wsw), b_out_d, llens, tlens, B, T, U1, J, Jp, V, Vp, act,    \
+                               out_d, lse_);                                                                          \
+        }                                                                                                             \
+    } while (0)
+    if (epi == kEpiGrad) {
+        WR_LAUNCH_EPI(kEpiGrad, lse);
+        WR_CHECK_LAUNCH("joint_fwd (gradient epilogue)");
+        return WR_OK;
+    }
+    (void)hipMemsetAsync(lse.repair, 0, sizeof(int32_t), st);
+    WR_LAUNCH_EPI(kEpiStats, lse);
+    WR_CHECK_LAUNCH("joint_fwd (statistics epilogue)");
+    // repair: the same launch with a running maximum, whose workgroups leave at once unless a partial sum overflowed
+    JointLse rep = lse;
+    rep.run_if = lse.repair;
+    rep.online = 1;
+    WR_LAUNCH_EPI(kEpiStats, rep);
+#undef WR_LAUNCH_EPI
+    WR_CHECK_LAUNCH("joint_fwd (statistics epilogue, repair)");
+    return WR_OK;
+}
+
+// shared body of wr_joint_fwd / wr_joint_fwd_lse / wr_joint_rnnt_stats / wr_joint_rnnt_grad (epi: JointEpi; -1 = kEpiStore
+// without `lse`, kEpiStoreLse with it)
 int joint_fwd_launch(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
                      const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1, int J, int V,
-                     int act, float *out_d, void *workspace_d, size_t workspace_bytes, const JointLse *lse, hipStream_t st)
+                     int act, float *out_d, void *workspace_d, size_t workspace_bytes, const JointLse *lse, hipStream_t st,
+                     int epi = -1, bool w_ready = false)
 {
     const int Vp = joint_vpad(V), Jp = joint_jpad(J);
     WR_REQUIRE(workspace_bytes >= (size_t)Jp * Vp * sizeof(float), WR_EWORKSPACE, "joint_fwd: workspace too small");
@@ -664,9 +741,12 @@ int joint_fwd_launch(const float *ep_d, const float *pp_d, const float *w_out_d,
     // default: the fragment-layout kernel; wr_tune_set(5, 1) selects the first forward kernel (kept for the equivalence test)
     if (tune_get(kTuneJointFwdVariant) != 1) {
         float4 *wf = static_cast<float4 *>(workspace_d);
-        hipLaunchKernelGGL(joint_frag_w_kernel, dim3(1024), dim3(256), 0, st, w_out_d, V, J, Jp, Vp, wf);
+        if (!w_ready) hipLaunchKernelGGL(joint_frag_w_kernel, dim3(1024), dim3(256), 0, st, w_out_d, V, J, Jp, Vp, wf);
         const size_t tile2 = (size_t)kBM * (Jp + 4) * sizeof(float);
-        if (lse == nullptr) {
+        if (epi == kEpiStats || epi == kEpiGrad) {
+            return joint_fwd_epi_launch(true, epi, ep_d, pp_d, wf, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, Jp,
+                                        V, Vp, act, out_d, *lse, st);
+        } else if (lse == nullptr) {
 #define WR_LAUNCH_FRAG(LSE_, CT_, lds_, lse_)                                                                          \
             do {                                                                                                      \
                 (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_frag_kernel<LSE_, CT_>),             \
@@ -674,31 +754,36 @@ int joint_fwd_launch(const float *ep_d, const float *pp_d, const float *w_out_d,
                 hipLaunchKernelGGL((joint_fwd_frag_kernel<LSE_, CT_>), grid, dim3(512), lds_, st, ep_d, pp_d, wf, b_out_d, \
                                    logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, act, out_d, lse_);       \
             } while (0)
-            WR_LAUNCH_FRAG(false, 1, tile2, JointLse{});
+            WR_LAUNCH_FRAG(kEpiStore, 1, tile2, JointLse{});
         } else {
             const size_t lds2 = tile2 > joint_lse_exchange_bytes(8) ? tile2 : joint_lse_exchange_bytes(8);
             (void)hipMemsetAsync(lse->repair, 0, sizeof(int32_t), st);
-            WR_LAUNCH_FRAG(true, 1, lds2, *lse);
+            WR_LAUNCH_FRAG(kEpiStoreLse, 1, lds2, *lse);
 #undef WR_LAUNCH_FRAG
         }
         WR_CHECK_LAUNCH("joint_fwd_frag_kernel");
         return WR_OK;
     }
-    hipLaunchKernelGGL(joint_transpose_w_kernel, dim3(Vp / 32, (Jp + 31) / 32), dim3(256), 0, st, w_out_d, V, J, Jp, Vp,
-                       wt);
-    WR_CHECK_LAUNCH("joint_transpose_w_kernel");
-    if (lse == nullptr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_direct_kernel<8, 1, false>),
+    if (!w_ready) {
+        hipLaunchKernelGGL(joint_transpose_w_kernel, dim3(Vp / 32, (Jp + 31) / 32), dim3(256), 0, st, w_out_d, V, J, Jp,
+                           Vp, wt);
+        WR_CHECK_LAUNCH("joint_transpose_w_kernel");
+    }
+    if (epi == kEpiStats || epi == kEpiGrad) {
+        return joint_fwd_epi_launch(false, epi, ep_d, pp_d, wt, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V,
+                                    Vp, act, out_d, *lse, st);
+    } else if (lse == nullptr) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_direct_kernel<8, 1, kEpiStore>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile);
-        hipLaunchKernelGGL((joint_fwd_direct_kernel<8, 1, false>), grid, dim3(512), tile, st, ep_d, pp_d, wt, b_out_d,
+        hipLaunchKernelGGL((joint_fwd_direct_kernel<8, 1, kEpiStore>), grid, dim3(512), tile, st, ep_d, pp_d, wt, b_out_d,
                            logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, act, out_d, JointLse{});
     } else {
         // the statistics exchange reuses the activation tile's storage
         const size_t lds = tile > joint_lse_exchange_bytes(8) ? tile : joint_lse_exchange_bytes(8);
         (void)hipMemsetAsync(lse->repair, 0, sizeof(int32_t), st);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_direct_kernel<8, 1, true>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_direct_kernel<8, 1, kEpiStoreLse>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((joint_fwd_direct_kernel<8, 1, true>), grid, dim3(512), lds, st, ep_d, pp_d, wt, b_out_d,
+        hipLaunchKernelGGL((joint_fwd_direct_kernel<8, 1, kEpiStoreLse>), grid, dim3(512), lds, st, ep_d, pp_d, wt, b_out_d,
                            logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, act, out_d, *lse);
     }
     WR_CHECK_LAUNCH("joint_fwd_direct_kernel");
@@ -740,6 +825,85 @@ extern "C" int wr_joint_fwd_lse(const float *ep_d, const float *pp_d, const floa
                  reinterpret_cast<int32_t *>(rws + w.flag_off)};
     return joint_fwd_launch(ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation,
                             out_d, workspace_d, workspace_bytes, &lse, static_cast<hipStream_t>(stream));
+}
+
+namespace {
+// what wr_joint_rnnt_stats and wr_joint_rnnt_grad check and share
+int joint_rnnt_check(const char *what, const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
+                     const int32_t *llens, const int32_t *tlens, const int32_t *targets_d, int B, int T, int U1, int J,
+                     int V, int activation, int blank, int terms, const void *workspace_d, const void *rws,
+                     size_t rws_bytes)
+{
+    if (int rc = joint_check(B, T, U1, J, V, activation)) return rc;
+    WR_REQUIRE(ep_d && pp_d && w_out_d && b_out_d && workspace_d && rws && llens && tlens, WR_EINVAL,
+               "%s: null pointer argument", what);
+    WR_REQUIRE(targets_d || U1 == 1, WR_EINVAL, "%s: targets is null", what);
+    WR_REQUIRE(terms == 0 || terms == 3, WR_EUNSUPPORTED, "%s: terms must be 0 (exact fp32) or 3 (split), got %d", what, terms);
+    WR_REQUIRE(blank >= 0 && blank < V, WR_EINVAL, "%s: blank %d out of range [0,%d)", what, blank, V);
+    WR_REQUIRE(U1 <= kRnntMaxCols, WR_EUNSUPPORTED, "%s: U1=%d exceeds the loss's limit of %d", what, U1, kRnntMaxCols);
+    WR_REQUIRE((long)B * T * U1 < (1L << 31), WR_EUNSUPPORTED, "%s: more than 2^31 lattice cells", what);
+    const size_t need = rnnt_ws_layout(B, T, U1).total;
+    WR_REQUIRE(rws_bytes >= need, WR_EWORKSPACE, "%s: RNN-T workspace %zu < required %zu", what, rws_bytes, need);
+    return WR_OK;
+}
+
+JointLse joint_rnnt_lse(const int32_t *targets_d, int B, int T, int U1, int blank, void *rnnt_workspace_d)
+{
+    const RnntWs w = rnnt_ws_layout(B, T, U1);
+    char *rws = static_cast<char *>(rnnt_workspace_d);
+    JointLse lse{targets_d, blank, w.S, reinterpret_cast<float2 *>(rws + w.lp_off), reinterpret_cast<float *>(rws + w.denom_off),
+                 reinterpret_cast<int32_t *>(rws + w.flag_off)};
+    lse.alpha_skew = reinterpret_cast<const double *>(rws + w.alpha_off);
+    lse.beta_skew = reinterpret_cast<const double *>(rws + w.beta_off);
+    lse.cost = reinterpret_cast<const double *>(rws + w.cost_off);
+    return lse;
+}
+}  // namespace
+
+extern "C" int wr_joint_rnnt_stats(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
+                                   const int32_t *logit_lengths_d, const int32_t *target_lengths_d, const int32_t *targets_d,
+                                   int B, int T, int U1, int J, int V, int activation, int blank, int terms,
+                                   void *workspace_d, size_t workspace_bytes, void *rnnt_workspace_d,
+                                   size_t rnnt_workspace_bytes, void *stream)
+{
+    if (int rc = joint_rnnt_check("joint_rnnt_stats", ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d,
+                                  targets_d, B, T, U1, J, V, activation, blank, terms, workspace_d, rnnt_workspace_d,
+                                  rnnt_workspace_bytes))
+        return rc;
+    const JointLse lse = joint_rnnt_lse(targets_d, B, T, U1, blank, rnnt_workspace_d);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (terms == 3)
+        return joint_fwd_split_epi(ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation,
+                                   kEpiStats, lse, nullptr, workspace_d, workspace_bytes, st);
+    return joint_fwd_launch(ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation,
+                            nullptr, workspace_d, workspace_bytes, &lse, st, kEpiStats);
+}
+
+extern "C" int wr_joint_rnnt_grad(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
+                                  const int32_t *logit_lengths_d, const int32_t *target_lengths_d, const int32_t *targets_d,
+                                  int B, int T, int U1, int J, int V, int activation, int blank, float clamp, int terms,
+                                  const float *grad_costs_d, const void *rnnt_workspace_d, size_t rnnt_workspace_bytes,
+                                  long long cell_begin, long long cell_end, float *g_out_d, void *workspace_d,
+                                  size_t workspace_bytes, int w_ready, void *stream)
+{
+    if (int rc = joint_rnnt_check("joint_rnnt_grad", ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d,
+                                  targets_d, B, T, U1, J, V, activation, blank, terms, workspace_d, rnnt_workspace_d,
+                                  rnnt_workspace_bytes))
+        return rc;
+    WR_REQUIRE(g_out_d, WR_EINVAL, "joint_rnnt_grad: null pointer argument");
+    WR_REQUIRE(0 <= cell_begin && cell_begin < cell_end && cell_end <= (long long)B * T * U1, WR_EINVAL,
+               "joint_rnnt_grad: cell range [%lld, %lld) outside [0, %lld)", cell_begin, cell_end, (long long)B * T * U1);
+    JointLse lse = joint_rnnt_lse(targets_d, B, T, U1, blank, const_cast<void *>(rnnt_workspace_d));
+    lse.grad_costs = grad_costs_d;
+    lse.clamp = clamp;
+    lse.m_begin = (long)cell_begin;
+    lse.m_end = (long)cell_end;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (terms == 3)
+        return joint_fwd_split_epi(ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation,
+                                   kEpiGrad, lse, g_out_d, workspace_d, workspace_bytes, st, w_ready != 0);
+    return joint_fwd_launch(ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation,
+                            g_out_d, workspace_d, workspace_bytes, &lse, st, kEpiGrad, w_ready != 0);
 }
 
 extern "C" int wr_joint_bwd_dz(const float *gout_d, const float *ep_d, const float *pp_d, const float *w_out_d,

@@ -23,6 +23,17 @@
 
 namespace wr {
 
+// Epilogue modes of the forward kernels (template argument EPI):
+//   kEpiStore     the logits leave for HBM (the joiner);
+//   kEpiStoreLse  the logits leave and the row statistics are written (wr_joint_fwd_lse / wr_joint_fwd_split_lse);
+//   kEpiStats     the row statistics only, no logit is stored (wr_joint_rnnt_stats): the blank / label logit of a row is
+//                 parked in LDS by the lane that holds its column; `online` = the repair launch (below);
+//   kEpiGrad      the RNN-T loss gradient of the cells [m_begin, m_end) instead of their logits (wr_joint_rnnt_grad):
+//                 the formula and case chain of rnnt_grad_kernel (rnnt_loss.hip) with per-row constants from LDS, out row
+//                 m - m_begin.  The logits are recomputed with the same k order, so they are bit-identical to the ones the
+//                 statistics were taken from.
+enum JointEpi : int { kEpiStore = 0, kEpiStoreLse = 1, kEpiStats = 2, kEpiGrad = 3 };
+
 struct JointLse {
     const int32_t *targets;   // [B, U1-1]
     int blank;
@@ -30,13 +41,135 @@ struct JointLse {
     float2 *lp_skew;          // [B, S, U1]   {skip, emit}
     float *denom;             // [B, T, U1]
     int32_t *repair;          // set to 1 when a partial sum overflowed (RnntWs::flag_off)
+    // kEpiStats: the repair launch runs only if *run_if != 0 and keeps a running maximum (no overflow possible)
+    const int32_t *run_if = nullptr;
+    int online = 0;
+    // kEpiGrad: the lattice of the sweeps and the gradient's scalars; cells [m_begin, m_end) of the flattened lattice
+    const double *alpha_skew = nullptr, *beta_skew = nullptr, *cost = nullptr;
+    const float *grad_costs = nullptr;   // [B] or null (= 1)
+    float clamp = -1.f;
+    long m_begin = 0, m_end = 0;
 };
 
 constexpr int kLseRows = 64;  // cells per workgroup (= kBM = kSM)
 
+// Per-row constants of the kEpiStats / kEpiGrad epilogues, in LDS behind everything else the kernel keeps there
+// (joint_epi_rows_bytes).  Stats: lab = the row's label column (-1: none), xb / xl = the parked blank / label logit.
+// Grad (rnnt_grad_kernel's names): c2 = (cmd + beta) log2e, bsub / lsub = the exponents of the blank / label terms minus
+// the logit, blk / lab = their columns (-1: no such term), go = grad_costs[b]; a padded row has c2 = -inf and go = 0.
+struct EpiRows {
+    int *lab, *blk;
+    float *xb, *xl, *c2, *bsub, *lsub, *go;
+};
+__host__ __device__ inline size_t joint_epi_rows_bytes() { return (size_t)8 * kLseRows * sizeof(float); }
+
+__device__ __forceinline__ EpiRows joint_epi_rows(void *base)
+{
+    float *f = static_cast<float *>(base);
+    EpiRows r;
+    r.lab = reinterpret_cast<int *>(f);
+    r.blk = reinterpret_cast<int *>(f + kLseRows);
+    r.xb = f + 2 * kLseRows;
+    r.xl = f + 3 * kLseRows;
+    r.c2 = f + 4 * kLseRows;
+    r.bsub = f + 5 * kLseRows;
+    r.lsub = f + 6 * kLseRows;
+    r.go = f + 7 * kLseRows;
+    return r;
+}
+
+// Fill the per-row constants of the 64 cells m0.. (threads 0..63; the caller synchronises before the epilogues read them).
+template <int EPI>
+__device__ __forceinline__ void joint_epi_rows_init(const JointLse &a, const EpiRows &er, const int32_t *llens,
+                                                    const int32_t *tlens, long m0, long M, int T, int U1)
+{
+    const int row = threadIdx.x;
+    if (row >= kLseRows) return;
+    const long m = m0 + row;
+    int b = 0, t = 0, u = 0, T_ = 0, U = -1;
+    if (m < M) {
+        const long bt = m / U1;
+        u = (int)(m - bt * U1);
+        b = (int)(bt / T);
+        t = (int)(bt - (long)b * T);
+        T_ = llens[b];
+        U = tlens[b];
+    }
+    const bool valid = m < M && t < T_ && u <= U;
+    if (EPI == kEpiStats) {
+        er.lab[row] = (valid && u < U) ? a.targets[(size_t)b * (U1 - 1) + u] : -1;
+        er.xb[row] = 0.f;
+        er.xl[row] = 0.f;
+        return;
+    }
+    if (!valid) {
+        er.c2[row] = kNegInf;
+        er.bsub[row] = 0.f;
+        er.lsub[row] = 0.f;
+        er.blk[row] = -1;
+        er.lab[row] = -1;
+        er.go[row] = 0.f;
+        return;
+    }
+    // rnnt_grad_kernel, term by term (fp64 where it is)
+    const size_t dbase = (size_t)b * a.S * U1;
+    const int s = t + u;
+    const bool final_cell = t == T_ - 1 && u == U;
+    const bool has_b1 = t < T_ - 1;
+    const bool blank_special = final_cell || has_b1;
+    const double al = a.alpha_skew[dbase + (size_t)s * U1 + u];
+    const double be = a.beta_skew[dbase + (size_t)s * U1 + u];
+    const double cost = a.cost[b];
+    const float d = a.denom[m];
+    double b1 = 0.0, b2 = 0.0;
+    if (has_b1) b1 = a.beta_skew[dbase + (size_t)(s + 1) * U1 + u];
+    int lab = -1;
+    bool has_lab = false;
+    if (u < U) {
+        lab = a.targets[(size_t)b * (U1 - 1) + u];
+        if (lab == a.blank && blank_special) lab = -1;
+        else has_lab = true;
+    }
+    if (has_lab) b2 = a.beta_skew[dbase + (size_t)(s + 1) * U1 + (u + 1)];
+    const double ac = al + cost;
+    const double cmd = ac - (double)d;
+    er.c2[row] = (float)(cmd + be) * kLog2e;
+    er.bsub[row] = final_cell ? (float)cmd : (has_b1 ? (float)(cmd + b1) : 0.f);
+    er.lsub[row] = has_lab ? (float)(cmd + b2) : 0.f;
+    er.blk[row] = blank_special ? a.blank : -1;
+    er.lab[row] = has_lab ? lab : -1;
+    er.go[row] = a.grad_costs ? a.grad_costs[b] : 1.f;
+}
+
+// kEpiStats: park the blank / label logit of `row` if this lane holds its column
+__device__ __forceinline__ void joint_epi_park(const EpiRows &er, int blank, int row, int col, float x)
+{
+    if (col == blank) er.xb[row] = x;
+    if (col == er.lab[row]) er.xl[row] = x;
+}
+
+// kEpiGrad: the gradient of logit x of `row`, column `col` (rnnt_grad_kernel's fix + finish)
+__device__ __forceinline__ float joint_epi_grad(const EpiRows &er, float clamp, int row, int col, float x)
+{
+    float val = fast_exp2(fmaf(x, kLog2e, er.c2[row]));
+    if (col == er.blk[row]) val -= fast_exp2((x + er.bsub[row]) * kLog2e);
+    else if (col == er.lab[row]) val -= fast_exp2((x + er.lsub[row]) * kLog2e);
+    if (clamp > 0.f) val = fminf(fmaxf(val, -clamp), clamp);
+    return val * er.go[row];
+}
+
+// kEpiGrad, a tile whose 64 cells are all padded: no matrix work, its rows of the gradient are 0
+__device__ __forceinline__ void joint_epi_zero_rows(float *out, long m0, long M, long m_begin, int V)
+{
+    const long m1 = m0 + kLseRows < M ? m0 + kLseRows : M;
+    float *o = out + (size_t)(m0 - m_begin) * V;
+    const long n = (m1 - m0) * (long)V;
+    for (long i = threadIdx.x; i < n; i += blockDim.x) o[i] = 0.f;
+}
+
 // statistics exchange: [64 rows][waves * 32 entries] floats (one log-sum-exp per lane and row), overlaid on the
 // activation tile after the k-loops
-inline size_t joint_lse_exchange_bytes(int waves) { return (size_t)kLseRows * waves * 32 * sizeof(float); }
+__host__ __device__ inline size_t joint_lse_exchange_bytes(int waves) { return (size_t)kLseRows * waves * 32 * sizeof(float); }
 
 // one logit of column `col` (col >= V: padding, contributes nothing); first = this is the lane's first column
 __device__ __forceinline__ void joint_lse_add(float &ref, float &s, float x, bool in, bool first)
@@ -50,13 +183,40 @@ __device__ __forceinline__ void joint_lse_add(float &ref, float &s, float x, boo
     }
 }
 
+// the same with a running maximum (the repair launch of kEpiStats: two exponentials per logit, no overflow)
+__device__ __forceinline__ void joint_lse_add_online(float &ref, float &s, float x, bool in, bool first)
+{
+    const float y = x * kLog2e;
+    if (first) {
+        ref = in ? y : -3.0e38f;
+        s = in ? 1.f : 0.f;
+    } else if (in) {
+        if (y > ref) {
+            s = s * fast_exp2(ref - y) + 1.f;
+            ref = y;
+        } else {
+            s += fast_exp2(y - ref);
+        }
+    }
+}
+
+template <int EPI>
+__device__ __forceinline__ void joint_lse_add_mode(const JointLse &a, float &ref, float &s, float x, bool in, bool first)
+{
+    if (EPI == kEpiStats && a.online) joint_lse_add_online(ref, s, x, in, first);
+    else joint_lse_add(ref, s, x, in, first);
+}
+
 // Merge and write.  ref/s: this lane's statistics, index rt * 16 + r <-> row 32 rt + (r&3) + 8 (r>>2) + 4 half.
 // `xch` must be free for joint_lse_exchange_bytes(WAVES) bytes and every wave must have finished with whatever
-// lived there (the caller synchronises before the call); `out` = the logits this workgroup has stored.
+// lived there (the caller synchronises before the call); `out` = the logits this workgroup has stored, or null with
+// `parked_xb` / `parked_xl` = the blank / label logits parked in LDS (kEpiStats; EpiRows::xb / xl, passed by value so that
+// they stay LDS addresses).
 template <int WAVES>
 __device__ __forceinline__ void joint_lse_finish(const JointLse &a, float *xch, const float (&ref)[32], const float (&s)[32],
                                                  const int32_t *llens, const int32_t *tlens, const float *out, long m0,
-                                                 long M, int T, int U1, int V)
+                                                 long M, int T, int U1, int V, const float *parked_xb = nullptr,
+                                                 const float *parked_xl = nullptr)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
@@ -99,15 +259,27 @@ __device__ __forceinline__ void joint_lse_finish(const JointLse &a, float *xch, 
             const int U = tlens[b];
             if (t < llens[b] && u <= U) {                 // same rows as rnnt_lse_kernel writes
                 const float d = (mx + fast_log2(sum)) * kLn2;
-                const float *orow = out + (size_t)m * V;
-                const float xb = __builtin_nontemporal_load(orow + a.blank);
-                float em = 0.f;
-                if (u < U) em = __builtin_nontemporal_load(orow + a.targets[(size_t)b * (U1 - 1) + u]) - d;
+                float xb, em = 0.f;
+                if (parked_xb != nullptr) {
+                    xb = parked_xb[row];
+                    if (u < U) em = parked_xl[row] - d;
+                } else {
+                    const float *orow = out + (size_t)m * V;
+                    xb = __builtin_nontemporal_load(orow + a.blank);
+                    if (u < U) em = __builtin_nontemporal_load(orow + a.targets[(size_t)b * (U1 - 1) + u]) - d;
+                }
                 a.denom[m] = d;
                 a.lp_skew[((size_t)b * a.S + (t + u)) * U1 + u] = make_float2(xb - d, em);
             }
         }
     }
 }
+
+// joint_split.hip: the kEpiStats / kEpiGrad modes of the split-precision forward (terms = 3); `workspace` as
+// wr_joint_split_workspace_bytes; w_ready: it already holds W's bf16 images from an earlier call with the same W
+int joint_fwd_split_epi(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
+                        const int32_t *llens, const int32_t *tlens, int B, int T, int U1, int J, int V, int act, int epi,
+                        const JointLse &lse, float *out_d, void *workspace_d, size_t workspace_bytes, hipStream_t st,
+                        bool w_ready = false);
 
 }  // namespace wr

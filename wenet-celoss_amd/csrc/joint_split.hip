@@ -178,8 +178,8 @@ template <> __device__ __forceinline__ __bf16 to_out<__bf16>(float x) { return (
 // waves per CU (two per SIMD, 256 registers each; a 4 x 2 register tile needs half the W bytes per MFMA): measured 9.1-10.2 ms
 // against 7.8 for two 64-cell workgroups -- eight accumulator tiles in 256 registers spill in the staged epilogue
 // (26 k cycles per round), the transposed epilogue does not but stores 16-byte pieces -- so it is not instantiated.
-template <int TERMS, typename OutT, bool LSE = false, int RT = 2, int OCC = 1, bool TRN = false, int NW = kSWaves,
-          typename OpT = __bf16>
+template <int TERMS, typename OutT, int EPI = kEpiStore /* JointEpi */, int RT = 2, int OCC = 1, bool TRN = false,
+          int NW = kSWaves, typename OpT = __bf16>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : OCC) void joint_fwd_split_kernel(
     const float *__restrict__ ep, const float *__restrict__ pp, const u32x4 *__restrict__ wh, const u32x4 *__restrict__ wl,
     const float *__restrict__ bias, const int32_t *__restrict__ llens, const int32_t *__restrict__ tlens, int B, int T,
@@ -187,15 +187,19 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : OCC) void joint_fwd_split_ke
     int lds_bias_bytes = 0, int lds_stage = 0)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned short lds_s[];
+    constexpr bool LSE = EPI == kEpiStoreLse || EPI == kEpiStats, STORE = EPI <= kEpiStoreLse, GRAD = EPI == kEpiGrad;
+    constexpr bool PLAIN = EPI == kEpiStore;               // logits only: the forms below that store nothing else
+    static_assert(STORE || (RT == 2 && OCC == 1 && !TRN && NW == kSWaves && std::is_same<OutT, float>::value),
+                  "statistics / gradient epilogues: the 64-cell, one-per-CU form with fp32 values");
     constexpr int SM = 32 * RT;                            // lattice cells of this workgroup
     constexpr int PF = RT == 4 ? 2 : kSPF;                 // k-steps per register set (eight accumulator tiles leave room for less)
-    static_assert(RT == 2 || (RT == 4 && TERMS == 1 && !LSE), "128-cell tiles: single-term mode without row statistics");
-    static_assert(OCC == 1 || (OCC == 2 && TERMS == 1 && !LSE && ((RT == 2 && NW == 4) || (RT == 4 && NW == 8))),
+    static_assert(RT == 2 || (RT == 4 && TERMS == 1 && PLAIN), "128-cell tiles: single-term mode without row statistics");
+    static_assert(OCC == 1 || (OCC == 2 && TERMS == 1 && PLAIN && ((RT == 2 && NW == 4) || (RT == 4 && NW == 8))),
                   "two waves per SIMD: single-term mode; 64 cells x two workgroups or 128 cells x eight waves");
     static_assert(NW == 4 || NW == 8, "waves per workgroup");
-    static_assert(!TRN || (TERMS == 1 && !LSE), "transposed tiles: single-term mode without row statistics");
+    static_assert(!TRN || (TERMS == 1 && PLAIN), "transposed tiles: single-term mode without row statistics");
     constexpr bool F16 = std::is_same<OpT, _Float16>::value;
-    static_assert(F16 ? (TERMS == 1 && !LSE) : std::is_same<OpT, __bf16>::value, "f16 operands: single-term mode only");
+    static_assert(F16 ? (TERMS == 1 && PLAIN) : std::is_same<OpT, __bf16>::value, "f16 operands: single-term mode only");
     const int JS = Jp + 8;                                 // padded row stride (bf16 elements): 16-byte pad
     unsigned short *Ahi = lds_s;                            // [SM][JS]
     unsigned short *Alo = lds_s + (size_t)SM * JS;          // [SM][JS]   (TERMS == 3)
@@ -203,13 +207,15 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : OCC) void joint_fwd_split_ke
     // per-wave store stage of the single-term mode (see finish_round): behind the bias slab; rows of V elements must keep
     // 16-byte alignment for the vector stores
     char *stage = reinterpret_cast<char *>(bias_s) + lds_bias_bytes;
-    const bool stage_ok = TERMS == 1 && !LSE && lds_stage && ((size_t)V * sizeof(OutT)) % 16 == 0 &&
+    const bool stage_ok = TERMS == 1 && PLAIN && lds_stage && ((size_t)V * sizeof(OutT)) % 16 == 0 &&
                           (reinterpret_cast<size_t>(out) & 15) == 0;
-    const long M = (long)B * T * U1;
+    if (EPI == kEpiStats && lse.run_if != nullptr && *lse.run_if == 0) return;
+    const long M = GRAD ? lse.m_end : (long)B * T * U1;
+    const long mb = GRAD ? lse.m_begin : 0;                 // first cell of the launch (out row 0)
     // consecutive workgroups land on consecutive XCDs: part = blockIdx % npart keeps each XCD on one column slab of W
     // (<= ~2.5 MB of fragments, resident in its 4 MB L2) for the whole launch
     const int part = blockIdx.x % npart;
-    const long m0 = (long)(blockIdx.x / npart) * SM;
+    const long m0 = mb + (long)(blockIdx.x / npart) * SM;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
 #ifdef WR_JS_STAMPS
@@ -233,8 +239,17 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : OCC) void joint_fwd_split_ke
             const int b = (int)(bt / T), t = (int)(bt - (long)b * T);
             valid = (t < llens[b]) && (u <= tlens[b]);
         }
-        if (!__syncthreads_or(valid)) return;
+        if (!__syncthreads_or(valid)) {
+            if (GRAD) joint_epi_zero_rows(reinterpret_cast<float *>(out), m0, M, mb, V);
+            return;
+        }
     }
+    // per-row constants of the statistics / gradient epilogues: behind the activation images and the bias slab, and behind
+    // the statistics exchange of joint_lse_finish.  Every user derives its EpiRows from lds_s and this offset itself: an
+    // EpiRows captured by the lambdas below would live in scratch and reach LDS through flat loads.
+    const size_t epi_used = (size_t)(TERMS == 3 ? 2 : 1) * SM * JS * sizeof(unsigned short) + lds_bias_bytes;
+    const int epi_off = (int)(epi_used > joint_lse_exchange_bytes(NW) ? epi_used : joint_lse_exchange_bytes(NW));
+    if (!STORE) joint_epi_rows_init<EPI>(lse, joint_epi_rows(reinterpret_cast<char *>(lds_s) + epi_off), llens, tlens, m0, M, T, U1);
     const int S = Jp / 16;                                  // k-steps per column tile; Jp is a multiple of 16 * PF
     const int cpr = S / PF;                               // register sets ("chunks") per round
     const int n_ct = Vp / 32;                               // column tiles
@@ -529,7 +544,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : OCC) void joint_fwd_split_ke
             next_bias(r + 1);
             return;
         }
-        if constexpr (TERMS == 1 && !LSE && !TRN) {
+        if constexpr (TERMS == 1 && PLAIN && !TRN) {
             // Interior tiles of the single-term mode leave through a per-wave LDS stage as whole 128-byte lines: in the
             // C/D layout a lane holds ONE column, so a direct store moves 2 or 4 bytes per lane (64 store instructions per
             // round and wave, 64-byte pieces of lines); staged, a lane stores 16 bytes of 8 (bf16 / f16) or 4 (fp32)
@@ -616,15 +631,29 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : OCC) void joint_fwd_split_ke
             const int col = (ct0 + c) * 32 + l31;
             const bool colin = pr < npairs && col < V;
             const float bv = colin ? (OCC == 2 ? bvr[c] : bias_s[(pr * kSCT + c) * 32 + l31]) : 0.f;
-            OutT *__restrict__ ocol = out + (size_t)m0 * V + (colin ? col : 0);
+            OutT *__restrict__ ocol = out + (size_t)(m0 - mb) * V + (colin ? col : 0);
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
                 if (LSE) {
 #pragma unroll
                     for (int q = 0; q < 16; ++q)
-                        joint_lse_add(rm[rt * 16 + q], rs[rt * 16 + q], acc[rt][c][q] + bv, colin, r == 0 && c == 0);
+                        joint_lse_add_mode<EPI>(lse, rm[rt * 16 + q], rs[rt * 16 + q], acc[rt][c][q] + bv, colin, r == 0 && c == 0);
                 }
-                if (full) {
+                if constexpr (EPI == kEpiStats) {
+                    const EpiRows er = joint_epi_rows(reinterpret_cast<char *>(lds_s) + epi_off);
+#pragma unroll
+                    for (int q = 0; q < 16; ++q)
+                        joint_epi_park(er, lse.blank, 32 * rt + (q & 3) + 8 * (q >> 2) + 4 * half, colin ? col : -1,
+                                       acc[rt][c][q] + bv);
+                } else if constexpr (GRAD) {
+                    const EpiRows er = joint_epi_rows(reinterpret_cast<char *>(lds_s) + epi_off);
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        const int row = 32 * rt + (q & 3) + 8 * (q >> 2) + 4 * half;
+                        if (m0 + row < M && colin)
+                            ocol[(size_t)row * V] = to_out<OutT>(joint_epi_grad(er, lse.clamp, row, col, acc[rt][c][q] + bv));
+                    }
+                } else if (full) {
 #pragma unroll
                     for (int q = 0; q < 16; ++q) {
                         const int row = 32 * rt + (q & 3) + 8 * (q >> 2) + 4 * half;   // C/D layout of the 32x32 MFMA
@@ -681,8 +710,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : OCC) void joint_fwd_split_ke
 #endif
     if (LSE) {
         __syncthreads();                                    // every wave is done with the activation images: reuse them
+        const EpiRows er = joint_epi_rows(reinterpret_cast<char *>(lds_s) + epi_off);
         joint_lse_finish<NW>(lse, reinterpret_cast<float *>(lds_s), rm, rs, llens, tlens,
-                                  reinterpret_cast<const float *>(out), m0, M, T, U1, V);
+                                  reinterpret_cast<const float *>(out), m0, M, T, U1, V, EPI == kEpiStats ? er.xb : nullptr,
+                                  EPI == kEpiStats ? er.xl : nullptr);
     }
 }
 
@@ -1896,36 +1927,36 @@ int joint_fwd_split_launch(const float *ep_d, const float *pp_d, const float *w_
     const dim3 grid((unsigned)((M + cells - 1) / cells * npart));
 #define WR_LAUNCH_SPLIT_WIDE(OutT, TRN, OpT)                                                                             \
     do {                                                                                                              \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<1, OutT, false, 4, 1, TRN, kSWaves, OpT>), \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<1, OutT, kEpiStore, 4, 1, TRN, kSWaves, OpT>), \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-        hipLaunchKernelGGL((joint_fwd_split_kernel<1, OutT, false, 4, 1, TRN, kSWaves, OpT>), grid, dim3(64 * kSWaves), lds, st, \
+        hipLaunchKernelGGL((joint_fwd_split_kernel<1, OutT, kEpiStore, 4, 1, TRN, kSWaves, OpT>), grid, dim3(64 * kSWaves), lds, st, \
                            ep_d, pp_d, reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl), b_out_d, \
                            logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, npart, act, static_cast<OutT *>(out_d), \
                            JointLse{}, kb_bias, kb_stage);                                                            \
     } while (0)
 #define WR_LAUNCH_SPLIT_TWO(OutT, TRN, OpT)                                                                              \
     do {                                                                                                              \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<1, OutT, false, 2, 2, TRN, kSWaves, OpT>), \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<1, OutT, kEpiStore, 2, 2, TRN, kSWaves, OpT>), \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-        hipLaunchKernelGGL((joint_fwd_split_kernel<1, OutT, false, 2, 2, TRN, kSWaves, OpT>), grid, dim3(64 * kSWaves), lds, st, \
+        hipLaunchKernelGGL((joint_fwd_split_kernel<1, OutT, kEpiStore, 2, 2, TRN, kSWaves, OpT>), grid, dim3(64 * kSWaves), lds, st, \
                            ep_d, pp_d, reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl), b_out_d, \
                            logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, npart, act, static_cast<OutT *>(out_d), \
                            JointLse{}, kb_bias, kb_stage);                                                            \
     } while (0)
 #define WR_LAUNCH_SPLIT(TERMS, OutT, TRN, OpT)                                                                        \
     do {                                                                                                              \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<TERMS, OutT, false, 2, 1, TRN, kSWaves, OpT>), \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<TERMS, OutT, kEpiStore, 2, 1, TRN, kSWaves, OpT>), \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-        hipLaunchKernelGGL((joint_fwd_split_kernel<TERMS, OutT, false, 2, 1, TRN, kSWaves, OpT>), grid, dim3(64 * kSWaves), lds, \
+        hipLaunchKernelGGL((joint_fwd_split_kernel<TERMS, OutT, kEpiStore, 2, 1, TRN, kSWaves, OpT>), grid, dim3(64 * kSWaves), lds, \
                            st, ep_d, pp_d, reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl), b_out_d, \
                            logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, npart, act, static_cast<OutT *>(out_d), \
                            JointLse{}, kb_bias, kb_stage);                                                            \
     } while (0)
 #define WR_LAUNCH_SPLIT_LSE(TERMS)                                                                                    \
     do {                                                                                                              \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<TERMS, float, true>),           \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<TERMS, float, kEpiStoreLse>),           \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-        hipLaunchKernelGGL((joint_fwd_split_kernel<TERMS, float, true>), grid, dim3(64 * kSWaves), lds, st, ep_d, pp_d, \
+        hipLaunchKernelGGL((joint_fwd_split_kernel<TERMS, float, kEpiStoreLse>), grid, dim3(64 * kSWaves), lds, st, ep_d, pp_d, \
                            reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl), b_out_d,          \
                            logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, npart, act, static_cast<float *>(out_d), \
                            *lse);                                                                                     \
@@ -1968,6 +1999,57 @@ int joint_fwd_split_launch(const float *ep_d, const float *pp_d, const float *w_
     return WR_OK;
 }
 }  // namespace
+
+namespace wr {
+// The statistics-only (kEpiStats: one launch plus the repair launch) and gradient (kEpiGrad) modes of
+// joint_fwd_split_kernel (terms = 3, fp32 values, one column part).  Declared in joint_lse.hpp.
+int joint_fwd_split_epi(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
+                        const int32_t *llens, const int32_t *tlens, int B, int T, int U1, int J, int V, int act, int epi,
+                        const JointLse &lse, float *out_d, void *workspace_d, size_t workspace_bytes, hipStream_t st,
+                        bool w_ready)
+{
+    const int Vp = split_vpad(V), Jp = split_jpad(J);
+    const size_t img = align_up((size_t)Jp * Vp * sizeof(unsigned short), 256);
+    WR_REQUIRE(workspace_bytes >= 2 * img, WR_EWORKSPACE, "joint_fwd_split: workspace too small");
+    unsigned short *wh = static_cast<unsigned short *>(workspace_d);
+    unsigned short *wl = reinterpret_cast<unsigned short *>(static_cast<char *>(workspace_d) + img);
+    if (!w_ready) {
+        hipLaunchKernelGGL(split_w_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, Vp, Jp, wh, wl);
+        WR_CHECK_LAUNCH("split_w_kernel");
+    }
+    const long cells = epi == kEpiGrad ? lse.m_end - lse.m_begin : (long)B * T * U1;
+    const size_t tile_lds = (size_t)2 * kSM * (Jp + 8) * sizeof(unsigned short);
+    const size_t bias_al = align_up((size_t)(Vp / (32 * kSCT)) * 32 * kSCT * sizeof(float), 16);
+    const size_t used = tile_lds + bias_al;
+    const size_t lds = (used > joint_lse_exchange_bytes(kSWaves) ? used : joint_lse_exchange_bytes(kSWaves)) + joint_epi_rows_bytes();
+    WR_REQUIRE(lds <= 160 * 1024, WR_EUNSUPPORTED, "joint_fwd_split: V=%d needs %zu bytes of LDS", V, lds);
+    const dim3 grid((unsigned)((cells + kSM - 1) / kSM));
+#define WR_LAUNCH_SPLIT_EPI(EPI_, lse_)                                                                                \
+    do {                                                                                                              \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<3, float, EPI_>),              \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
+        hipLaunchKernelGGL((joint_fwd_split_kernel<3, float, EPI_>), grid, dim3(64 * kSWaves), lds, st, ep_d, pp_d,    \
+                           reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl), b_out_d, llens,   \
+                           tlens, B, T, U1, J, Jp, V, Vp, 1, act, out_d, lse_, (int)bias_al, 0);                       \
+    } while (0)
+    if (epi == kEpiGrad) {
+        WR_LAUNCH_SPLIT_EPI(kEpiGrad, lse);
+        WR_CHECK_LAUNCH("joint_fwd_split_kernel (gradient epilogue)");
+        return WR_OK;
+    }
+    (void)hipMemsetAsync(lse.repair, 0, sizeof(int32_t), st);
+    WR_LAUNCH_SPLIT_EPI(kEpiStats, lse);
+    WR_CHECK_LAUNCH("joint_fwd_split_kernel (statistics epilogue)");
+    // repair: the same launch with a running maximum, whose workgroups leave at once unless a partial sum overflowed
+    JointLse rep = lse;
+    rep.run_if = lse.repair;
+    rep.online = 1;
+    WR_LAUNCH_SPLIT_EPI(kEpiStats, rep);
+#undef WR_LAUNCH_SPLIT_EPI
+    WR_CHECK_LAUNCH("joint_fwd_split_kernel (statistics epilogue, repair)");
+    return WR_OK;
+}
+}  // namespace wr
 
 extern "C" int wr_joint_fwd_split(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
                                   const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1,

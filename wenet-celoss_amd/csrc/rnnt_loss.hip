@@ -532,6 +532,21 @@ extern "C" int wr_rnnt_loss_fwd_from_lse(const float *logits_d, const int32_t *t
     return WR_OK;
 }
 
+extern "C" int wr_rnnt_loss_sweeps(const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax,
+                                   int U1max, float *costs_d, void *workspace_d, size_t workspace_bytes, void *stream)
+{
+    if (int rc = check_shape(B, Tmax, U1max, 1, 0)) return rc;
+    WR_REQUIRE(logit_lengths_d && target_lengths_d && costs_d && workspace_d, WR_EINVAL,
+               "rnnt_loss_sweeps: null pointer argument");
+    const RnntWs w = rnnt_ws_layout(B, Tmax, U1max);
+    WR_REQUIRE(workspace_bytes >= w.total, WR_EWORKSPACE, "rnnt_loss_sweeps: workspace %zu < required %zu",
+               workspace_bytes, w.total);
+    rnnt_launch_sweep(w, static_cast<char *>(workspace_d), logit_lengths_d, target_lengths_d, B, Tmax, U1max, costs_d,
+                      static_cast<hipStream_t>(stream));
+    WR_CHECK_LAUNCH("rnnt_sweep_kernel");
+    return WR_OK;
+}
+
 extern "C" int wr_rnnt_loss_bwd(const void *logits_d, int dtype, const int32_t *targets_d,
                                 const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax,
                                 int U1max, int V, int blank, float clamp, const float *grad_costs_d, void *grads_d,

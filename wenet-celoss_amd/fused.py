@@ -12,11 +12,18 @@ the logits are internal to the node, the gradient pass writes over them: one log
 
 Results: costs and every gradient agree with the unfused path to fp32 rounding of the row log-sum-exp (the
 statistics are merged in a different order); tests/test_fused_gpu.py states the tolerance (1e-6 relative on costs).
+
+Memory-bounded mode (`logits_budget`, `_JointRnntBoundedFn`): no logits tensor at all.  The forward keeps only the row
+statistics (`wr_joint_rnnt_stats`: the joiner forward with a statistics-only epilogue) and runs the lattice sweeps
+(`wr_rnnt_loss_sweeps`); the backward walks the lattice in slices (`plan_slices`) and, per slice, recomputes the logits
+tile by tile and turns them into the loss gradient in the same kernel's epilogue (`wr_joint_rnnt_grad`), then runs the
+joiner backward on that slice.  One extra joiner forward's matrix work buys a footprint that does not grow with the batch
+(DESIGN.md, "The memory-bounded loss block").
 """
 from __future__ import annotations
 
 import os
-from typing import Optional
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -146,6 +153,153 @@ class _JointRnntFn(torch.autograd.Function):
         return d_ep, d_pp, d_w, d_b, None, None, None, None, None, None, None
 
 
+class Slice(NamedTuple):
+    """Part of the (B, T, U1) lattice the memory-bounded backward handles at once: utterances [b0, b1), frames [t0, t1)
+    of each.  Either a run of whole utterances (t0 = 0, t1 = T: the view ep[b0:b1] is contiguous, so the buffer also
+    holds their padded frames, which get a zero gradient and count against the budget) or one utterance's frames
+    [t0, t1) with t1 <= its length (b1 = b0 + 1)."""
+    b0: int
+    b1: int
+    t0: int
+    t1: int
+
+    def cells(self, U1: int) -> int:
+        return (self.b1 - self.b0) * (self.t1 - self.t0) * U1
+
+
+def plan_slices(t_lens, u_lens, T: int, U1: int, V: int, budget_bytes: int) -> List[Slice]:
+    """Cut the lattice of a batch into slices whose fp32 logits gradient, (cells x V) floats, fits `budget_bytes`.
+
+    Utterances are taken in order.  An utterance whose T x U1 cells fit the budget joins the current run of whole
+    utterances while the run still fits (else it starts a new one); one that does not fit is cut into frame ranges of
+    budget // (4 V U1) frames over [0, T_b).  Frames at or past T_b belong to no frame range, and an utterance with
+    T_b = 0 has no cell and no slice.  `u_lens` is accepted for symmetry with plan_buckets: the label axis is never cut.
+    Raises ValueError when the budget holds less than one frame row (U1 x V x 4 bytes)."""
+    del u_lens
+    cap = int(budget_bytes) // (4 * V)
+    row = U1 * V * 4
+    if cap < U1:
+        raise ValueError(f"logits_budget={budget_bytes} bytes is below one frame row of the lattice: at least "
+                         f"U1 * V * 4 = {U1} * {V} * 4 = {row} bytes are needed")
+    whole = T * U1
+    slices: List[Slice] = []
+    run0 = None                                   # first utterance of the open run
+    for b, tb in enumerate(int(x) for x in t_lens):
+        if run0 is not None and (tb == 0 or whole > cap or (b + 1 - run0) * whole > cap):
+            slices.append(Slice(run0, b, 0, T))
+            run0 = None
+        if tb == 0:
+            continue
+        if whole <= cap:
+            if run0 is None:
+                run0 = b
+            continue
+        step = cap // U1
+        for t0 in range(0, tb, step):
+            slices.append(Slice(b, b + 1, t0, min(t0 + step, tb)))
+    if run0 is not None:
+        slices.append(Slice(run0, len(t_lens), 0, T))
+    return slices
+
+
+class _JointRnntBoundedFn(torch.autograd.Function):
+    """Joiner + RNN-T loss with no logits tensor (joint_rnnt_loss(..., logits_budget=n)).  Saves ep, pp, w, b, the lengths
+    and the RNN-T workspace; `slices` (plan_slices) and the host lengths come from the caller's one length sync."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, ep, pp, w, b, targets, llens, tlens, blank, clamp, terms, act, slices, host_t, host_u):
+        if not ep.is_cuda:
+            raise RuntimeError("wenet_celoss_amd.joint_rnnt_loss: tensors must live on a HIP device "
+                               "(this package has no CPU path)")
+        lib = _lib.load()
+        B, T, J = ep.shape
+        U1 = pp.shape[1]
+        V = w.shape[0]
+        dev = ep.device
+        ep, pp, w, b = ep.contiguous(), pp.contiguous(), w.contiguous(), b.contiguous()
+        rws_bytes = lib.wr_rnnt_workspace_bytes(B, T, U1)
+        rws = torch.empty(rws_bytes, dtype=torch.uint8, device=dev)
+        costs = torch.empty(B, dtype=torch.float32, device=dev)
+        ws_bytes = lib.wr_joint_workspace_bytes(J, V) if terms == 0 else lib.wr_joint_split_workspace_bytes(J, V)
+        with torch.cuda.device(dev):
+            st = _lib.current_stream(dev)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            rc = lib.wr_joint_rnnt_stats(_lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(b), _lib.ptr(llens), _lib.ptr(tlens),
+                                         _lib.ptr(targets), B, T, U1, J, V, act, blank, terms, _lib.ptr(ws), ws_bytes,
+                                         _lib.ptr(rws), rws_bytes, st)
+            _lib.check(rc, "wr_joint_rnnt_stats")
+            rc = lib.wr_rnnt_loss_sweeps(_lib.ptr(llens), _lib.ptr(tlens), B, T, U1, _lib.ptr(costs), _lib.ptr(rws), rws_bytes, st)
+            _lib.check(rc, "wr_rnnt_loss_sweeps")
+            # per-slice length arrays, built once on the host from the caller's length sync: [ll of every slice | tl ...]
+            ll_s, tl_s = [], []
+            for s in slices:
+                for u in range(s.b0, s.b1):
+                    ll_s.append(min(host_t[u], s.t1) - s.t0)
+                    tl_s.append(host_u[u])
+            lens = torch.tensor(ll_s + tl_s, dtype=torch.int32)
+            lens = lens.pin_memory().to(dev, non_blocking=True) if lens.numel() else lens.to(dev)
+        ctx.save_for_backward(ep, pp, w, b, targets, llens, tlens, rws)
+        ctx.slice_lens = lens
+        ctx.slices = slices
+        ctx.blank, ctx.clamp, ctx.terms, ctx.act = blank, clamp, terms, act
+        return costs
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_costs):
+        ep, pp, w, b, targets, llens, tlens, rws = ctx.saved_tensors
+        lib = _lib.load()
+        B, T, J = ep.shape
+        U1 = pp.shape[1]
+        V = w.shape[0]
+        dev = ep.device
+        need_w, need_b = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        gc = grad_costs.to(torch.float32).contiguous()
+        d_ep = torch.zeros_like(ep)                 # utterances without a slice (no frame) keep zero gradients
+        d_pp = torch.zeros_like(pp)
+        d_w = torch.zeros(V, J, dtype=torch.float32, device=dev) if need_w else None
+        d_b = torch.zeros(V, dtype=torch.float32, device=dev) if need_b else None
+        slices = ctx.slices
+        if not slices:
+            return d_ep, d_pp, d_w, d_b, None, None, None, None, None, None, None, None, None, None
+        nmax = max(s.cells(U1) for s in slices)
+        # buffers sized to the largest slice, allocated once per backward
+        g = torch.empty(nmax * V, dtype=torch.float32, device=dev)
+        dz = torch.empty(nmax * J, dtype=torch.float32, device=dev)
+        h = torch.empty(nmax * J, dtype=torch.float32, device=dev) if need_w else None
+        ws_bytes = lib.wr_joint_workspace_bytes(J, V) if ctx.terms == 0 else lib.wr_joint_split_workspace_bytes(J, V)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        nl = ctx.slice_lens.numel() // 2
+        k = 0
+        with torch.cuda.device(dev):
+            st = _lib.current_stream(dev)
+            for i, s in enumerate(slices):
+                nb, nt = s.b1 - s.b0, s.t1 - s.t0
+                cells = nb * nt * U1
+                begin = (s.b0 * T + s.t0) * U1
+                rc = lib.wr_joint_rnnt_grad(_lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(b), _lib.ptr(llens),
+                                            _lib.ptr(tlens), _lib.ptr(targets), B, T, U1, J, V, ctx.act, ctx.blank,
+                                            float(ctx.clamp), ctx.terms, _lib.ptr(gc), _lib.ptr(rws), rws.numel(), begin,
+                                            begin + cells, _lib.ptr(g), _lib.ptr(ws), ws_bytes, int(i > 0), st)
+                _lib.check(rc, "wr_joint_rnnt_grad")
+                ll = ctx.slice_lens[k:k + nb]
+                tl = ctx.slice_lens[nl + k:nl + k + nb]
+                k += nb
+                de, dp, dw, db = joint_backward(g[:cells * V].view(nb, nt, U1, V), ep[s.b0:s.b1, s.t0:s.t1],
+                                                pp[s.b0:s.b1], w, ll, tl, ctx.terms, need_w, need_b,
+                                                gout_zero_in_padding=True, act=ctx.act,
+                                                dz_out=dz[:cells * J].view(nb, nt, U1, J),
+                                                h_out=h[:cells * J].view(nb, nt, U1, J) if need_w else None)
+                d_ep[s.b0:s.b1, s.t0:s.t1] = de
+                d_pp[s.b0:s.b1] += dp
+                if need_w:
+                    d_w += dw
+                if need_b:
+                    d_b += db
+        return d_ep, d_pp, d_w, d_b, None, None, None, None, None, None, None, None, None, None
+
+
 def plan_buckets(t_lens, u_lens, max_buckets: int = 4, min_gain: float = 0.08, min_cells: int = 20000):
     """Group utterances by label length so that each group is padded to its own maxima.
 
@@ -197,7 +351,8 @@ def plan_buckets(t_lens, u_lens, max_buckets: int = 4, min_gain: float = 0.08, m
 def joint_rnnt_loss(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tensor,
                     targets: torch.Tensor, logit_lengths: torch.Tensor, target_lengths: torch.Tensor, blank: int = 0,
                     clamp: float = -1.0, reduction: str = "mean", precision: Optional[str] = None,
-                    buckets: Optional[int] = None, activation: str = "tanh") -> torch.Tensor:
+                    buckets: Optional[int] = None, activation: str = "tanh",
+                    logits_budget: Optional[int] = None) -> torch.Tensor:
     """rnnt_loss(ffn_out(act(ep[:, :, None] + pp[:, None])), targets, logit_lengths, target_lengths) without the
     logits ever leaving the node.  ep (B, T, J) = enc_ffn(encoder_out), pp (B, U+1, J) = pred_ffn(predictor_out);
     targets (B, U) int32 with padding already mapped to a valid class; lengths (B,) int32; requires
@@ -205,7 +360,10 @@ def joint_rnnt_loss(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Tensor, b_o
     ``precision``: "fp32" (exact MFMA, default), "bf16x3" (split precision, joint.py) or "autocast" outside autocast (= "fp32");
     the 16-bit modes are refused; reduction as rnnt_loss.
     ``buckets``: at most this many groups by label length, each padded to its own maxima (`plan_buckets`; default from
-    WR_FUSED_BUCKETS, 4; 1 = one call for the whole batch).  Costs come back in the caller's utterance order."""
+    WR_FUSED_BUCKETS, 4; 1 = one call for the whole batch).  Costs come back in the caller's utterance order.
+    ``logits_budget``: None (default) = the node above; an int = the memory-bounded node (`_JointRnntBoundedFn`): no
+    logits tensor, the backward recomputes the logits in slices whose gradient buffer holds at most this many bytes
+    (`plan_slices`; ValueError below one frame row, U1 * V * 4 bytes).  "fp32" and "bf16x3" only, as the node above."""
     if reduction not in ("none", "mean", "sum"):
         raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
     precision = _call_precision(precision)             # "autocast": "fp32" outside autocast, a 16-bit mode under it
@@ -236,17 +394,26 @@ def joint_rnnt_loss(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Tensor, b_o
     groups = plan_buckets(lens[0].tolist(), lens[1].tolist(), max_buckets=buckets) if buckets > 1 else None
     terms = _PRECISIONS[precision]
     act = activation_code(activation)
+
+    def node(ep_, pp_, tg_, ll_, tl_, host_t, host_u):
+        if logits_budget is None:
+            return _JointRnntFn.apply(ep_, pp_, w_out, b_out, tg_, ll_, tl_, int(blank), float(clamp), terms, act)
+        slices = plan_slices(host_t, host_u, ep_.shape[1], pp_.shape[1], V, int(logits_budget))
+        return _JointRnntBoundedFn.apply(ep_, pp_, w_out, b_out, tg_, ll_, tl_, int(blank), float(clamp), terms, act,
+                                         slices, host_t, host_u)
+
+    if logits_budget is not None:
+        plan_slices(lens[0].tolist(), lens[1].tolist(), T, U1, V, int(logits_budget))   # a bad budget fails before any launch
     if groups is None:
-        costs = _JointRnntFn.apply(ep, pp, w_out, b_out, tg, ll, tl, int(blank), float(clamp), terms, act)
+        costs = node(ep, pp, tg, ll, tl, lens[0].tolist(), lens[1].tolist())
     else:
         costs = torch.empty(B, dtype=torch.float32, device=dev)
         parts, index = [], []
         for g in groups:
             idx = torch.tensor(g, device=dev)
             tg_max, ug_max = int(lens[0][g].max()), int(lens[1][g].max())
-            parts.append(_JointRnntFn.apply(ep[idx, :tg_max], pp[idx, :ug_max + 1], w_out, b_out,
-                                            tg[idx, :ug_max].contiguous(), ll[idx].contiguous(), tl[idx].contiguous(),
-                                            int(blank), float(clamp), terms, act))
+            parts.append(node(ep[idx, :tg_max], pp[idx, :ug_max + 1], tg[idx, :ug_max].contiguous(), ll[idx].contiguous(),
+                              tl[idx].contiguous(), lens[0][g].tolist(), lens[1][g].tolist()))
             index.append(idx)
         costs = torch.cat(parts)[torch.argsort(torch.cat(index))]      # back to the caller's order (differentiable)
     if reduction == "mean":

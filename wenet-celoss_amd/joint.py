@@ -262,12 +262,14 @@ def _f16_backward(lib, gout, ep, pp, w, llens, tlens, need_w, need_b, gout_zero_
 
 
 def joint_backward(gout, ep, pp, w, llens, tlens, terms: int, need_w: bool, need_b: bool,
-                   gout_zero_in_padding: bool = False, act: int = 0):
+                   gout_zero_in_padding: bool = False, act: int = 0, dz_out=None, h_out=None):
     """Backward of the joiner from the logits gradient `gout` (B,T,U1,V): returns (d_ep, d_pp, d_w, d_b).
     Shared by the joiner's autograd Function and by the fused joiner + RNN-T loss Function (fused.py).
     `gout_zero_in_padding`: the caller guarantees gout == 0 outside [0,T_b) x [0,U_b] (the RNN-T gradient pass
     zero-fills there).  The activation gradient still gets the lengths (it skips padded tiles and writes H = 0 in
-    padded cells), but the weight-gradient reduction then needs no per-row mask: padded rows contribute 0 * 0."""
+    padded cells), but the weight-gradient reduction then needs no per-row mask: padded rows contribute 0 * 0.
+    `dz_out` / `h_out`: fp32 (B,T,U1,J) buffers for dZ and H in the exact and split modes (the memory-bounded fused node
+    reuses one pair for all its slices); allocated here when None."""
     lib = _lib.load()
     B, T, J = ep.shape
     U1 = pp.shape[1]
@@ -285,8 +287,8 @@ def joint_backward(gout, ep, pp, w, llens, tlens, terms: int, need_w: bool, need
         return _amp_backward_library(lib, gout.contiguous(), ep, pp, w, llens, tlens, need_w, need_b, gout_zero_in_padding, act)
     g16 = gout.dtype == torch.bfloat16 and ok16
     gout = gout.contiguous() if g16 else gout.float().contiguous()
-    dz = torch.empty(B, T, U1, J, dtype=torch.float32, device=dev)
-    h = torch.empty_like(dz) if need_w else None
+    dz = dz_out if dz_out is not None else torch.empty(B, T, U1, J, dtype=torch.float32, device=dev)
+    h = (h_out if h_out is not None else torch.empty_like(dz)) if need_w else None
     if terms != 0 and V % 4 == 0 and V >= 32:       # same split as the forward (gradient rows 16-byte aligned)
         wsb = lib.wr_joint_dz_split_workspace_bytes(J, V)
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)

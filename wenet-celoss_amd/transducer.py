@@ -22,6 +22,7 @@ over the HIP step kernels).
 from __future__ import annotations
 
 import os
+import warnings
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -95,8 +96,18 @@ class Transducer(nn.Module):
         # joiner + RNN-T loss as one autograd node (fused.py): pass 1 of the loss rides on the joiner's epilogue and the
         # logits never leave the node (half the footprint).  WR_FUSED_LOSS=0 (or this attribute) selects the two separate ops.
         self.fused_loss = os.environ.get("WR_FUSED_LOSS", "1") != "0"
+        # memory-bounded fused node (fused.joint_rnnt_loss `logits_budget`, bytes): no logits tensor, the backward
+        # recomputes them in slices of at most this size.  None: WR_FUSED_LOGITS_BUDGET_MB if set, else the plain node.
+        self.logits_budget: Optional[int] = None
 
     # ------------------------------------------------------------- training --
+    def _logits_budget(self) -> Optional[int]:
+        budget = getattr(self, "logits_budget", None)     # absent on instances built without __init__
+        if budget is not None:
+            return int(budget)
+        mb = os.environ.get("WR_FUSED_LOGITS_BUDGET_MB")
+        return None if mb is None or mb == "" else int(float(mb) * (1 << 20))
+
     def compute_loss(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, predictor_out: torch.Tensor,
                      text: torch.Tensor, text_lengths: torch.Tensor, skip_padding: bool = False
                      ) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -113,8 +124,13 @@ class Transducer(nn.Module):
             ep, pp = jt.pre_activation(encoder_out, predictor_out)
             loss = joint_rnnt_loss(ep, pp, jt.ffn_out.weight, jt.ffn_out.bias,
                                    rnnt_text, encoder_out_lens, rnnt_text_lengths, blank=self.blank, reduction="mean",
-                                   precision=jt.precision, activation=jt.activation)
+                                   precision=jt.precision, activation=jt.activation, logits_budget=self._logits_budget())
             return None, loss
+        if self._logits_budget() is not None and not getattr(self, "_warned_budget", False):
+            # the 16-bit (AMP) joiner modes and the two-op path keep a logits tensor: the budget does not apply to them
+            warnings.warn("Transducer: logits_budget / WR_FUSED_LOGITS_BUDGET_MB applies to the fused joiner + loss node with "
+                          "the \"fp32\" or \"bf16x3\" joiner only; this step keeps its logits tensor", RuntimeWarning)
+            self._warned_budget = True
         if self.fused_loss and isinstance(self.joint, TransducerJoint):
             # the AMP single-term joiner keeps 16-bit logits (two ops), but a ragged batch is still cut into
             # label-length groups, each padded to its own maxima (fused.plan_buckets): same costs, fewer padded cells
