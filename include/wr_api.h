@@ -572,6 +572,31 @@ int wr_ctc_prefix_beam_search(const float *logits_d, const int32_t *lens_d, int 
                               int blank, int32_t *hyps_d, int32_t *hyp_lens_d, double *scores_d,
                               int32_t *n_hyps_d, void *workspace_d, size_t workspace_bytes, void *stream);
 
+/* RNN-T forced alignment: the single best path through the lattice of wr_rnnt_loss_fwd (a Viterbi pass: the forward
+ * sweep with max in place of log-add-exp, one decision bit per cell, and a backtrace).  No reference call site: the
+ * reference aligns with the CTC head only (wenet/bin/alignment.py); this is the transducer head's counterpart.
+ *   A(0,0) = 0, A(t,u) = max(A(t-1,u) + blank(t-1,u), A(t,u-1) + emit(t,u-1)), scores[b] = A(T_b-1,U_b) + blank(T_b-1,U_b)
+ * in fp64 over the fp32 log-probabilities of pass 1.  Tie rule: the emit predecessor wins only if its candidate is
+ * strictly greater; on equality or a NaN comparison the blank predecessor wins (a NaN candidate makes the value NaN), so
+ * the path is always a valid monotone one.  label_frames [B, U1max-1] int32: the frame at which label u+1 is emitted on
+ * the best path (non-decreasing in u), -1 for u >= U_b.  scores [B] double.
+ * Lengths: 1 <= logit_lengths[b] <= Tmax and 0 <= target_lengths[b] <= U1max-1 (the maxima need not equal the padded
+ * sizes, unlike the loss; the caller checks them); targets within [0, V) inside each length.
+ * wr_rnnt_align: pass 1 over the logits (fp32, fp16 or bf16, as wr_rnnt_loss_fwd), then the Viterbi kernel.  Workspace:
+ * wr_rnnt_workspace_bytes(B, Tmax, U1max).
+ * wr_rnnt_align_from_stats: the Viterbi kernel alone, on an RNN-T workspace whose row statistics wr_joint_rnnt_stats
+ * wrote (no logits tensor; that call repairs an overflowed row itself).  `targets_d` are the labels the statistics
+ * were taken with (they are not read again: the emit log-probabilities carry them). */
+int wr_rnnt_align(const void *logits_d, int dtype, const int32_t *targets_d, const int32_t *logit_lengths_d,
+                  const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V, int blank,
+                  int32_t *label_frames_d /* [B, U1max-1] out */, double *scores_d /* [B] out */,
+                  void *workspace_d, size_t workspace_bytes, void *stream);
+
+int wr_rnnt_align_from_stats(const int32_t *targets_d, const int32_t *logit_lengths_d, const int32_t *target_lengths_d,
+                             int B, int Tmax, int U1max, int32_t *label_frames_d /* [B, U1max-1] out */,
+                             double *scores_d /* [B] out */, void *rnnt_workspace_d, size_t rnnt_workspace_bytes,
+                             void *stream);
+
 /* CTC forced alignment: Viterbi over the T x (2S+1) lattice, replacing
  * forced_align, wenet/utils/ctc_util.py:27-83 (CLI wenet/bin/alignment.py:215).  logits [B, Tmax, V]: pre-softmax
  * ctc_lo output, or log-posteriors if normalized != 0 (the reference is handed ctc.log_softmax(...)).

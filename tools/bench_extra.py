@@ -429,9 +429,68 @@ def bench_step(args):
         del joint
 
 
+def bench_align(args):
+    """RNN-T forced alignment.  At B utterances (default 32) of the BASELINE lattice, fp32 logits: rnnt_forced_align
+    (pass 1 + Viterbi), wr_rnnt_align alone, the Viterbi kernel alone (wr_rnnt_align_from_stats on the workspace pass 1
+    filled) and wr_rnnt_loss_fwd (pass 1 + both sweeps) on the same logits.  At 8 utterances: joint_rnnt_forced_align
+    ("fp32", "bf16x3") beside wr_joint_rnnt_stats + wr_rnnt_loss_sweeps, J = 512."""
+    import wenet_celoss_amd as w
+    from wenet_celoss_amd import _lib
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    P = _lib.ptr
+    T, U1, V, J = args.T, args.U + 1, args.V, 512
+    for B in (args.B, 8):
+        tg = torch.randint(1, V, (B, U1 - 1), dtype=torch.int32, device=dev)
+        ll = torch.full((B,), T, dtype=torch.int32, device=dev)
+        tl = torch.full((B,), U1 - 1, dtype=torch.int32, device=dev)
+        rws_bytes = lib.wr_rnnt_workspace_bytes(B, T, U1)
+        rws = torch.empty(rws_bytes, dtype=torch.uint8, device=dev)
+        costs = torch.empty(B, device=dev)
+        frames = torch.empty(B, U1 - 1, dtype=torch.int32, device=dev)
+        scores = torch.empty(B, dtype=torch.float64, device=dev)
+        st = _lib.current_stream(dev)
+        viterbi = lambda: _lib.check(lib.wr_rnnt_align_from_stats(P(tg), P(ll), P(tl), B, T, U1, P(frames), P(scores),
+                                                                  P(rws), rws_bytes, st))
+        if B == args.B:
+            logits = torch.randn(B, T, U1, V, device=dev)
+            rec = {"what": "rnnt_align", "shape": [B, T, U1, V], "dtype": "fp32"}
+            rec["rnnt_forced_align_ms"] = timeit(lambda: w.rnnt_forced_align(logits, tg, ll, tl), args.steps)
+            rec["wr_rnnt_align_ms"] = timeit(lambda: _lib.check(lib.wr_rnnt_align(
+                P(logits), 0, P(tg), P(ll), P(tl), B, T, U1, V, 0, P(frames), P(scores), P(rws), rws_bytes, st)),
+                args.steps)
+            rec["viterbi_kernel_ms"] = timeit(viterbi, max(args.steps, 20))
+            rec["wr_rnnt_loss_fwd_ms"] = timeit(lambda: _lib.check(lib.wr_rnnt_loss_fwd(
+                P(logits), 0, P(tg), P(ll), P(tl), B, T, U1, V, 0, P(costs), P(rws), rws_bytes, st)), args.steps)
+            rec["loss_sweeps_ms"] = timeit(lambda: _lib.check(lib.wr_rnnt_loss_sweeps(
+                P(ll), P(tl), B, T, U1, P(costs), P(rws), rws_bytes, st)), max(args.steps, 20))
+            print(json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in rec.items()}), flush=True)
+            del logits
+            torch.cuda.empty_cache()
+            continue
+        g = torch.Generator(device=dev).manual_seed(0)
+        ep = torch.randn(B, T, J, device=dev, generator=g)
+        pp = torch.randn(B, U1, J, device=dev, generator=g)
+        wt = torch.randn(V, J, device=dev, generator=g) * (2.0 / J ** 0.5)
+        bt = torch.randn(V, device=dev, generator=g)
+        for precision, terms in (("fp32", 0), ("bf16x3", 3)):
+            ws_bytes = lib.wr_joint_workspace_bytes(J, V) if terms == 0 else lib.wr_joint_split_workspace_bytes(J, V)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+
+            def stats_sweeps():
+                _lib.check(lib.wr_joint_rnnt_stats(P(ep), P(pp), P(wt), P(bt), P(ll), P(tl), P(tg), B, T, U1, J, V, 0, 0,
+                                                   terms, P(ws), ws_bytes, P(rws), rws_bytes, st))
+                _lib.check(lib.wr_rnnt_loss_sweeps(P(ll), P(tl), B, T, U1, P(costs), P(rws), rws_bytes, st))
+            rec = {"what": "joint_rnnt_align", "shape": [B, T, U1, J, V], "precision": precision}
+            rec["joint_rnnt_forced_align_ms"] = timeit(
+                lambda: w.joint_rnnt_forced_align(ep, pp, wt, bt, tg, ll, tl, precision=precision), args.steps)
+            rec["stats_plus_loss_sweeps_ms"] = timeit(stats_sweeps, args.steps)
+            print(json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in rec.items()}), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword"])
+    ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align"])
     ap.add_argument("--n-steps", type=int, default=64)
     ap.add_argument("--chunks", type=int, default=4)
     ap.add_argument("--B", type=int, default=32)
@@ -453,4 +512,5 @@ if __name__ == "__main__":
     if a.tile:
         from wenet_celoss_amd import _lib
         _lib.load().wr_tune_set(6, a.tile)
-    {"joint": bench_joint, "ctc": bench_ctc, "greedy": bench_greedy, "beam": bench_beam, "step": bench_step, "ctcdec": bench_ctcdec, "hotword": bench_hotword}[a.what](a)
+    {"joint": bench_joint, "ctc": bench_ctc, "greedy": bench_greedy, "beam": bench_beam, "step": bench_step, "ctcdec": bench_ctcdec, "hotword": bench_hotword,
+     "align": bench_align}[a.what](a)

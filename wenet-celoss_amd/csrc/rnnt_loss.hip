@@ -88,22 +88,6 @@ __device__ __forceinline__ double log_add_exp_d(double a, double b)
     return (m == (double)kNegInf) ? (double)kNegInf : m + (double)r;
 }
 
-// Rotate a double by one lane: lane l receives lane l-1 (lane 0 receives lane 63).  gfx9 DPP wave_ror:1.
-__device__ __forceinline__ double lane_rotate_up_d(double v)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x13C, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x13C, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
-// Lane l receives lane l+1 (lane 63 receives lane 0).  DPP wave_rol:1.
-__device__ __forceinline__ double lane_rotate_down_d(double v)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x134, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x134, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
 // One workgroup per (utterance, direction), one lane per label column u (NW = ceil(U1max/64) waves).
 // At step s every lane works on the cell (t = s - u, u) of anti-diagonal s.  What a cell needs from
 // diagonal s -/+ 1 is the lane's own previous value and its neighbouring lane's previous value: inside a
@@ -460,6 +444,29 @@ void rnnt_launch_sweep(const RnntWs &w, char *ws, const int32_t *llens, const in
                        reinterpret_cast<double *>(ws + w.dump_off));
 }
 
+int rnnt_launch_lse(const RnntWs &w, char *ws, const void *logits_d, int dtype, const int32_t *targets_d,
+                    const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V,
+                    int blank, hipStream_t st)
+{
+    const long nrows = (long)B * Tmax * U1max;
+    const size_t row_bytes = (size_t)V * (dtype == WR_F32 ? 4 : 2);
+    const dim3 grid1(stream_grid(nrows, tune_get(kTuneLseBlocksPerCu), row_bytes, kLseBytesPerWave));
+#define WR_LAUNCH_LSE(T, NT)                                                                                        \
+    if (tune_get(kTuneLseUnroll) >= 16) WR_LAUNCH_LSE_U(T, NT, 16); else if (tune_get(kTuneLseUnroll) >= 8) WR_LAUNCH_LSE_U(T, NT, 8); else WR_LAUNCH_LSE_U(T, NT, 4)
+#define WR_LAUNCH_LSE_U(T, NT, UN)                                                                                  \
+    hipLaunchKernelGGL((rnnt_lse_kernel<T, NT, UN>), grid1, dim3(256), 0, st, static_cast<const T *>(logits_d), targets_d, \
+                       logit_lengths_d, target_lengths_d, B, Tmax, U1max, V, blank, w.K, w.S,                        \
+                       reinterpret_cast<float2 *>(ws + w.lp_off), reinterpret_cast<float *>(ws + w.denom_off), nullptr)
+    const bool nt = (tune_get(kTuneNonTemporal) & 4) != 0;
+    if (dtype == WR_F32) { if (nt) { WR_LAUNCH_LSE(float, true); } else { WR_LAUNCH_LSE(float, false); } }
+    else if (dtype == WR_F16) { if (nt) { WR_LAUNCH_LSE(_Float16, true); } else { WR_LAUNCH_LSE(_Float16, false); } }
+    else { if (nt) { WR_LAUNCH_LSE(__bf16, true); } else { WR_LAUNCH_LSE(__bf16, false); } }
+#undef WR_LAUNCH_LSE
+#undef WR_LAUNCH_LSE_U
+    WR_CHECK_LAUNCH("rnnt_lse_kernel");
+    return WR_OK;
+}
+
 }  // namespace wr
 
 using namespace wr;
@@ -485,22 +492,9 @@ extern "C" int wr_rnnt_loss_fwd(const void *logits_d, int dtype, const int32_t *
                workspace_bytes, w.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
     char *ws = static_cast<char *>(workspace_d);
-    const long nrows = (long)B * Tmax * U1max;
-    const size_t row_bytes = (size_t)V * (dtype == WR_F32 ? 4 : 2);
-    const dim3 grid1(stream_grid(nrows, tune_get(kTuneLseBlocksPerCu), row_bytes, kLseBytesPerWave));
-#define WR_LAUNCH_LSE(T, NT)                                                                                        \
-    if (tune_get(kTuneLseUnroll) >= 16) WR_LAUNCH_LSE_U(T, NT, 16); else if (tune_get(kTuneLseUnroll) >= 8) WR_LAUNCH_LSE_U(T, NT, 8); else WR_LAUNCH_LSE_U(T, NT, 4)
-#define WR_LAUNCH_LSE_U(T, NT, UN)                                                                                  \
-    hipLaunchKernelGGL((rnnt_lse_kernel<T, NT, UN>), grid1, dim3(256), 0, st, static_cast<const T *>(logits_d), targets_d, \
-                       logit_lengths_d, target_lengths_d, B, Tmax, U1max, V, blank, w.K, w.S,                        \
-                       reinterpret_cast<float2 *>(ws + w.lp_off), reinterpret_cast<float *>(ws + w.denom_off), nullptr)
-    const bool nt = (tune_get(kTuneNonTemporal) & 4) != 0;
-    if (dtype == WR_F32) { if (nt) { WR_LAUNCH_LSE(float, true); } else { WR_LAUNCH_LSE(float, false); } }
-    else if (dtype == WR_F16) { if (nt) { WR_LAUNCH_LSE(_Float16, true); } else { WR_LAUNCH_LSE(_Float16, false); } }
-    else { if (nt) { WR_LAUNCH_LSE(__bf16, true); } else { WR_LAUNCH_LSE(__bf16, false); } }
-#undef WR_LAUNCH_LSE
-#undef WR_LAUNCH_LSE_U
-    WR_CHECK_LAUNCH("rnnt_lse_kernel");
+    if (int rc = rnnt_launch_lse(w, ws, logits_d, dtype, targets_d, logit_lengths_d, target_lengths_d, B, Tmax, U1max, V,
+                                 blank, st))
+        return rc;
     rnnt_launch_sweep(w, ws, logit_lengths_d, target_lengths_d, B, Tmax, U1max, costs_d, st);
     WR_CHECK_LAUNCH("rnnt_sweep_kernel");
     return WR_OK;

@@ -86,10 +86,30 @@ inline RnntWs rnnt_ws_layout(int B, int Tmax, int U1max)
 // rnnt_loss.hip: lattice sweeps over a workspace whose row statistics (denom, skip/emit log-probs) are in place
 void rnnt_launch_sweep(const RnntWs &w, char *ws, const int32_t *llens, const int32_t *tlens, int B, int Tmax, int U1max,
                        float *costs, hipStream_t st);
+// rnnt_loss.hip: pass 1 (row log-sum-exp, skip / emit log-probs into the skewed array) over a logits tensor of `dtype`
+int rnnt_launch_lse(const RnntWs &w, char *ws, const void *logits_d, int dtype, const int32_t *targets_d,
+                    const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V,
+                    int blank, hipStream_t st);
 
 // ---- device helpers ---------------------------------------------------------
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ float fast_log2(float x) { return __builtin_amdgcn_logf(x); }
+
+// Rotate a double by one lane: lane l receives lane l-1 (lane 0 receives lane 63).  gfx9 DPP wave_ror:1.
+__device__ __forceinline__ double lane_rotate_up_d(double v)
+{
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x13C, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x13C, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+// Lane l receives lane l+1 (lane 63 receives lane 0).  DPP wave_rol:1.
+__device__ __forceinline__ double lane_rotate_down_d(double v)
+{
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x134, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x134, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
 
 // Joiner activations (wenet/utils/common.py:228-242 get_activation; codes WR_ACT_* of wr_api.h).  `act` is a kernel
 // argument (wave-uniform: the switch is scalar control flow).  Value and derivative w.r.t. the pre-activation z as

@@ -33,6 +33,7 @@ from .common import IGNORE_ID, LabelSmoothingLoss, add_blank, add_sos_eos, end_b
 from .decoder import DecoderCache
 from .fused import joint_rnnt_loss, plan_buckets
 from .joint import TransducerJoint, _call_precision
+from .rnnt_align import joint_rnnt_forced_align, rnnt_forced_align
 from .rnnt_loss import rnnt_loss
 from .search.greedy_search import basic_greedy_search, basic_greedy_search_both, basic_greedy_search_hw
 from .search.prefix_beam_search import PrefixBeamSearch
@@ -162,16 +163,11 @@ class Transducer(nn.Module):
         return (self.fused_loss and isinstance(jt, TransducerJoint)
                 and _call_precision(jt.precision) not in ("bf16", "f16"))
 
-    @torch.jit.unused      # wenet/bin/train.py:203-205 scripts the model as an export smoke test; the HIP-backed forward
-    def forward(self, speech: torch.Tensor, speech_lengths: torch.Tensor, text: torch.Tensor,  # is opaque to TorchScript
-                text_lengths: torch.Tensor, context_list: torch.Tensor = torch.IntTensor([0]),
-                context_lengths: torch.Tensor = torch.IntTensor([0]), hw_label=torch.IntTensor([0])
-                ) -> Dict[str, Optional[torch.Tensor]]:
-        """Frontend + Encoder + predictor + joint + loss (transducer.py:79-270)."""
-        assert text_lengths.dim() == 1, text_lengths.shape
-        assert (speech.shape[0] == speech_lengths.shape[0] == text.shape[0] == text_lengths.shape[0]), \
-            (speech.shape, speech_lengths.shape, text.shape, text_lengths.shape)
-        check_limits(text, text_lengths, with_ctc=self.ctc_weight != 0.0 and self.ctc is not None)
+    def _loss_inputs(self, speech: torch.Tensor, speech_lengths: torch.Tensor, text: torch.Tensor,
+                     context_list: torch.Tensor, context_lengths: torch.Tensor):
+        """The prelude of `forward` up to the loss block (transducer.py:90-120): encoder, ContextBias biasing when a
+        module is attached, the blank-prefixed predictor input.  Returns (bias_hidden, encoder_out, encoder_mask,
+        encoder_out_lens, encoder_out_bias, predictor_out, predictor_out_bias)."""
         cb = self.context_bias
         bias_hidden = cb.forward_bias_hidden(context_list, context_lengths) if cb is not None else None
 
@@ -185,6 +181,22 @@ class Transducer(nn.Module):
         predictor_out_bias = None
         if cb is not None:
             predictor_out, predictor_out_bias = cb.forward_predictor_bias(bias_hidden, predictor_out)
+        return (bias_hidden, encoder_out, encoder_mask, encoder_out_lens, encoder_out_bias, predictor_out,
+                predictor_out_bias)
+
+    @torch.jit.unused      # wenet/bin/train.py:203-205 scripts the model as an export smoke test; the HIP-backed forward
+    def forward(self, speech: torch.Tensor, speech_lengths: torch.Tensor, text: torch.Tensor,  # is opaque to TorchScript
+                text_lengths: torch.Tensor, context_list: torch.Tensor = torch.IntTensor([0]),
+                context_lengths: torch.Tensor = torch.IntTensor([0]), hw_label=torch.IntTensor([0])
+                ) -> Dict[str, Optional[torch.Tensor]]:
+        """Frontend + Encoder + predictor + joint + loss (transducer.py:79-270)."""
+        assert text_lengths.dim() == 1, text_lengths.shape
+        assert (speech.shape[0] == speech_lengths.shape[0] == text.shape[0] == text_lengths.shape[0]), \
+            (speech.shape, speech_lengths.shape, text.shape, text_lengths.shape)
+        check_limits(text, text_lengths, with_ctc=self.ctc_weight != 0.0 and self.ctc is not None)
+        cb = self.context_bias
+        (bias_hidden, encoder_out, encoder_mask, encoder_out_lens, encoder_out_bias, predictor_out,
+         predictor_out_bias) = self._loss_inputs(speech, speech_lengths, text, context_list, context_lengths)
         predictor_out_unbiased = predictor_out.clone()
 
         _, loss_rnnt = self.compute_loss(encoder_out, encoder_out_lens, predictor_out, text, text_lengths)
@@ -217,6 +229,37 @@ class Transducer(nn.Module):
                 hw_loss = self.hw_criterion(hw_output_dec.permute(0, 2, 1), hw_label_pad)
             loss = loss + self.hw_weight * hw_loss
         return {"loss": loss, "loss_att": loss_att, "loss_ctc": loss_ctc, "loss_rnnt": loss_rnnt, "hw_loss": hw_loss}
+
+    @torch.jit.unused      # HIP-backed, like forward
+    def forced_align(self, speech: torch.Tensor, speech_lengths: torch.Tensor, text: torch.Tensor,
+                     text_lengths: torch.Tensor, context_list: torch.Tensor = torch.IntTensor([0]),
+                     context_lengths: torch.Tensor = torch.IntTensor([0])) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Forced alignment with the transducer head (extension; the reference aligns with the CTC head only,
+        wenet/bin/alignment.py): the best path through the lattice whose negative log-sum `forward` reports as
+        `loss_rnnt` -- the same encoder, ContextBias biasing and blank / IGNORE_ID label mapping as the loss block.
+        With the joiner's precision resolving to "fp32" or "bf16x3" no logits tensor is formed (joint_rnnt_forced_align);
+        under a 16-bit (AMP) mode the joiner's logits go to rnnt_forced_align.  Frames are encoder frames (after
+        subsampling).  Returns (label_frames (B, U) int32, -1 past text_lengths; scores (B,) float64) on the device.
+        Call it in eval mode unless dropout is wanted."""
+        assert text_lengths.dim() == 1, text_lengths.shape
+        assert (speech.shape[0] == speech_lengths.shape[0] == text.shape[0] == text_lengths.shape[0]), \
+            (speech.shape, speech_lengths.shape, text.shape, text_lengths.shape)
+        check_limits(text, text_lengths, with_ctc=False)
+        with torch.no_grad():
+            _, encoder_out, _, encoder_out_lens, _, predictor_out, _ = self._loss_inputs(
+                speech, speech_lengths, text, context_list, context_lengths)
+            rnnt_text = text.to(torch.int64)
+            rnnt_text = torch.where(rnnt_text == self.ignore_id, 0, rnnt_text).to(torch.int32)
+            rnnt_text_lengths = text_lengths.to(torch.int32)
+            encoder_out_lens = encoder_out_lens.to(torch.int32)
+            jt = self.joint
+            if isinstance(jt, TransducerJoint) and _call_precision(jt.precision) not in ("bf16", "f16"):
+                ep, pp = jt.pre_activation(encoder_out, predictor_out)
+                return joint_rnnt_forced_align(ep, pp, jt.ffn_out.weight, jt.ffn_out.bias, rnnt_text, encoder_out_lens,
+                                               rnnt_text_lengths, blank=self.blank, precision=jt.precision,
+                                               activation=jt.activation)
+            logits = self.joint(encoder_out, predictor_out)
+            return rnnt_forced_align(logits, rnnt_text, encoder_out_lens, rnnt_text_lengths, blank=self.blank)
 
     def _calc_att_loss(self, encoder_out, encoder_mask, ys_pad, ys_pad_lens):
         """asr_model.py:115-148 (attention decoder is whatever module the caller attached)."""
