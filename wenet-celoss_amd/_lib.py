@@ -230,6 +230,25 @@ def current_stream(device=None):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def call(name: str, *args, device) -> None:
+    """Run entry point `name` on `device`'s current stream: tensors become their device pointers, None stays a null
+    pointer, every other argument passes through; the stream is appended as the last argument (where every entry point
+    that takes one has it, wr_decoder_create excepted).  The symbol is looked up on the loaded library at call time; a
+    non-zero return raises as `check` does, naming it."""
+    import torch
+    fn = getattr(load(), name)
+    argv = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+    with torch.cuda.device(device):
+        rc = fn(*argv, current_stream(device))
+    check(rc, name)
+
+
+def workspace(name: str, *dims, device):
+    """Fresh uint8 tensor on `device` of the size the `*_workspace_bytes` query `name` gives for `dims`."""
+    import torch
+    return torch.empty(getattr(load(), name)(*dims), dtype=torch.uint8, device=device)
+
+
 def dtype_code(dt) -> int:
     import torch
     if dt == torch.float32:

@@ -32,18 +32,13 @@ class _CTCLossFn(torch.autograd.Function):
         if not logits.is_cuda:
             raise RuntimeError("wenet_celoss_amd.ctc_loss: logits must live on a HIP device "
                                "(this package has no CPU path)")
-        lib = _lib.load()
         B, T, V = logits.shape
         S = targets.shape[1]
         dev = logits.device
-        ws_bytes = lib.wr_ctc_workspace_bytes(B, T, S)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _lib.workspace("wr_ctc_workspace_bytes", B, T, S, device=dev)
         nll = torch.empty(B, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.wr_ctc_loss_fwd(_lib.ptr(logits), _lib.dtype_code(logits.dtype), _lib.ptr(targets),
-                                     _lib.ptr(input_lengths), _lib.ptr(target_lengths), B, T, S, V, blank,
-                                     _lib.ptr(nll), _lib.ptr(ws), ws_bytes, _lib.current_stream(dev))
-        _lib.check(rc, "wr_ctc_loss_fwd")
+        _lib.call("wr_ctc_loss_fwd", logits, _lib.dtype_code(logits.dtype), targets, input_lengths, target_lengths, B, T, S, V,
+                  blank, nll, ws, ws.numel(), device=dev)
         ctx.save_for_backward(logits, targets, input_lengths, target_lengths, ws)
         ctx.blank = blank
         return nll
@@ -52,17 +47,13 @@ class _CTCLossFn(torch.autograd.Function):
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_nll):
         logits, targets, input_lengths, target_lengths, ws = ctx.saved_tensors
-        lib = _lib.load()
         B, T, V = logits.shape
         S = targets.shape[1]
         dev = logits.device
         grads = torch.empty_like(logits)
         g = grad_nll.to(torch.float32).contiguous()
-        with torch.cuda.device(dev):
-            rc = lib.wr_ctc_loss_bwd(_lib.ptr(logits), _lib.dtype_code(logits.dtype), _lib.ptr(targets),
-                                     _lib.ptr(input_lengths), _lib.ptr(target_lengths), B, T, S, V, ctx.blank,
-                                     _lib.ptr(g), _lib.ptr(grads), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev))
-        _lib.check(rc, "wr_ctc_loss_bwd")
+        _lib.call("wr_ctc_loss_bwd", logits, _lib.dtype_code(logits.dtype), targets, input_lengths, target_lengths, B, T, S, V,
+                  ctx.blank, g, grads, ws, ws.numel(), device=dev)
         return grads, None, None, None, None
 
 
@@ -107,20 +98,16 @@ def ctc_greedy_search(logits: torch.Tensor, lens: torch.Tensor, blank: int = 0, 
     returns (hyps: List[List[int]], scores (B,)).  eos defaults to V-1 (asr_model.py:52-53)."""
     if not logits.is_cuda:
         raise RuntimeError("wenet_celoss_amd.ctc_greedy_search: logits must live on a HIP device (no CPU path)")
-    lib = _lib.load()
     x = logits.detach().float().contiguous()
     B, T, V = x.shape
     dev = x.device
     ln = lens.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-    wsb = lib.wr_ctc_decode_workspace_bytes(B, T, 1)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace("wr_ctc_decode_workspace_bytes", B, T, 1, device=dev)
     hyps = torch.empty(B, T, dtype=torch.int32, device=dev)
     hl = torch.empty(B, dtype=torch.int32, device=dev)
     sc = torch.empty(B, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.wr_ctc_greedy_search(_lib.ptr(x), _lib.ptr(ln), B, T, V, int(blank), int(eos if eos >= 0 else V - 1),
-                                      _lib.ptr(hyps), _lib.ptr(hl), _lib.ptr(sc), _lib.ptr(ws), wsb, _lib.current_stream(dev))
-    _lib.check(rc, "wr_ctc_greedy_search")
+    _lib.call("wr_ctc_greedy_search", x, ln, B, T, V, int(blank), int(eos if eos >= 0 else V - 1), hyps, hl, sc, ws,
+              ws.numel(), device=dev)
     hc, lc = hyps.cpu(), hl.cpu().tolist()
     return [hc[b, :lc[b]].tolist() for b in range(B)], sc
 
@@ -130,22 +117,17 @@ def ctc_prefix_beam_search(logits: torch.Tensor, lens: torch.Tensor, beam_size: 
     Per utterance: [(prefix tuple, score)] best first (the reference's `hyps` for batch size 1)."""
     if not logits.is_cuda:
         raise RuntimeError("wenet_celoss_amd.ctc_prefix_beam_search: logits must live on a HIP device (no CPU path)")
-    lib = _lib.load()
     x = logits.detach().float().contiguous()
     B, T, V = x.shape
     dev = x.device
     ln = lens.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-    wsb = lib.wr_ctc_decode_workspace_bytes(B, T, beam_size)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace("wr_ctc_decode_workspace_bytes", B, T, beam_size, device=dev)
     hyps = torch.empty(B, beam_size, T, dtype=torch.int32, device=dev)
     hl = torch.empty(B, beam_size, dtype=torch.int32, device=dev)
     sc = torch.empty(B, beam_size, dtype=torch.float64, device=dev)
     nh = torch.empty(B, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.wr_ctc_prefix_beam_search(_lib.ptr(x), _lib.ptr(ln), B, T, V, int(beam_size), int(blank), _lib.ptr(hyps),
-                                           _lib.ptr(hl), _lib.ptr(sc), _lib.ptr(nh), _lib.ptr(ws), wsb,
-                                           _lib.current_stream(dev))
-    _lib.check(rc, "wr_ctc_prefix_beam_search")
+    _lib.call("wr_ctc_prefix_beam_search", x, ln, B, T, V, int(beam_size), int(blank), hyps, hl, sc, nh, ws, ws.numel(),
+              device=dev)
     hc, lc, scc, nc = hyps.cpu(), hl.cpu().tolist(), sc.cpu().tolist(), nh.cpu().tolist()
     return [[(tuple(hc[b, e, :lc[b][e]].tolist()), scc[b][e]) for e in range(nc[b])] for b in range(B)]
 
@@ -161,7 +143,6 @@ def forced_align_batch(logits: torch.Tensor, targets: torch.Tensor, input_length
     """Extension: B utterances at once.  logits (B, T, V) pre-softmax (or log-posteriors with normalized=True)."""
     if not logits.is_cuda:
         raise RuntimeError("wenet_celoss_amd.forced_align: tensors must live on a HIP device (no CPU path)")
-    lib = _lib.load()
     x = logits.detach().float().contiguous()
     B, T, V = x.shape
     dev = x.device
@@ -170,13 +151,10 @@ def forced_align_batch(logits: torch.Tensor, targets: torch.Tensor, input_length
     S = tg.shape[1]
     il = input_lengths.to(device=dev, dtype=torch.int32).contiguous()
     tl = target_lengths.to(device=dev, dtype=torch.int32).contiguous()
-    wsb = lib.wr_ctc_align_workspace_bytes(B, T, S)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace("wr_ctc_align_workspace_bytes", B, T, S, device=dev)
     ali = torch.empty(B, T, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.wr_ctc_forced_align(_lib.ptr(x), int(normalized), _lib.ptr(tg), _lib.ptr(il), _lib.ptr(tl), B, T, S, V,
-                                     int(blank_id), _lib.ptr(ali), _lib.ptr(ws), wsb, _lib.current_stream(dev))
-    _lib.check(rc, "wr_ctc_forced_align")
+    _lib.call("wr_ctc_forced_align", x, int(normalized), tg, il, tl, B, T, S, V, int(blank_id), ali, ws, ws.numel(),
+              device=dev)
     ac, ilc = ali.cpu(), il.cpu().tolist()
     return [ac[b, :ilc[b]].tolist() for b in range(B)]
 

@@ -145,11 +145,14 @@ class DeviceDecoder:
         if look is not None:
             self.set_lookahead(int(look))
 
-    def _check(self, rc: int, what: str) -> None:
-        """A failed search leaves the handle's lane state undefined: mark it so that DecoderCache rebuilds it."""
-        if rc != 0:
+    def _call(self, name: str, *args) -> None:
+        """`_lib.call` on this handle.  A failed search leaves the handle's lane state undefined: mark it so that
+        DecoderCache rebuilds it."""
+        try:
+            _lib.call(name, self._h, *args, device=self.device)
+        except RuntimeError:
             self.poisoned = True
-        _lib.check(rc, what)
+            raise
 
     poisoned = False
 
@@ -177,10 +180,7 @@ class DeviceDecoder:
         lens = encoder_out_lens.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
         hyps = torch.empty(N, max(self.max_hyp, 1), dtype=torch.int32, device=self.device)
         hl = torch.empty(N, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.wr_greedy_search(self._h, _lib.ptr(enc), _lib.ptr(lens), N, T, int(n_steps), int(blank),
-                                            _lib.ptr(hyps), _lib.ptr(hl), _lib.current_stream(self.device))
-        self._check(rc, "wr_greedy_search")
+        self._call("wr_greedy_search", enc, lens, N, T, int(n_steps), int(blank), hyps, hl)
         hl_c, hy_c = hl.cpu().tolist(), hyps.cpu()
         if max(hl_c, default=0) > self.max_hyp:
             raise RuntimeError(f"greedy search produced {max(hl_c)} tokens but the decoder was sized for {self.max_hyp}")
@@ -194,11 +194,8 @@ class DeviceDecoder:
         lens = chunk_lens.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
         hyps = torch.empty(N, max(self.max_hyp, 1), dtype=torch.int32, device=self.device)
         hl = torch.empty(N, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.wr_greedy_search_chunk(self._h, _lib.ptr(enc), _lib.ptr(lens), N, T, int(n_steps), int(blank),
-                                                  int(reset), int(reference_new_cache), _lib.ptr(hyps), _lib.ptr(hl),
-                                                  _lib.current_stream(self.device))
-        self._check(rc, "wr_greedy_search_chunk")
+        self._call("wr_greedy_search_chunk", enc, lens, N, T, int(n_steps), int(blank), int(reset), int(reference_new_cache),
+                   hyps, hl)
         hl_c, hy_c = hl.cpu().tolist(), hyps.cpu()
         if max(hl_c, default=0) > self.max_hyp:
             raise RuntimeError(f"greedy search produced {max(hl_c)} tokens but the decoder was sized for {self.max_hyp}")
@@ -217,11 +214,8 @@ class DeviceDecoder:
         hl = torch.empty(B, beam_size, dtype=torch.int32, device=self.device)
         sc = torch.empty(B, beam_size, dtype=torch.float64, device=self.device)
         nh = torch.empty(B, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.wr_prefix_beam_search(self._h, _lib.ptr(enc), _lib.ptr(lens), _lib.ptr(ctc), B, T, int(beam_size),
-                                                 float(ctc_weight), float(transducer_weight), int(blank), _lib.ptr(hyps),
-                                                 _lib.ptr(hl), _lib.ptr(sc), _lib.ptr(nh), _lib.current_stream(self.device))
-        self._check(rc, "wr_prefix_beam_search")
+        self._call("wr_prefix_beam_search", enc, lens, ctc, B, T, int(beam_size), float(ctc_weight), float(transducer_weight),
+                   int(blank), hyps, hl, sc, nh)
         hyps, hl, sc, nh = hyps.cpu(), hl.cpu().tolist(), sc.cpu().tolist(), nh.cpu().tolist()
         out = []
         for b in range(B):
@@ -235,10 +229,7 @@ class DeviceDecoder:
         ch, cc = _f32(cache_h), _f32(cache_c)
         out = torch.empty(N, self.dims["P"], dtype=torch.float32, device=self.device)
         nh, nc = torch.empty_like(ch), torch.empty_like(cc)
-        with torch.cuda.device(self.device):
-            rc = self._lib.wr_predictor_step(self._h, _lib.ptr(tok), _lib.ptr(ch), _lib.ptr(cc), N, _lib.ptr(out),
-                                             _lib.ptr(nh), _lib.ptr(nc), _lib.current_stream(self.device))
-        self._check(rc, "wr_predictor_step")
+        self._call("wr_predictor_step", tok, ch, cc, N, out, nh, nc)
         return out, nh, nc
 
 

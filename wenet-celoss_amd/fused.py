@@ -10,6 +10,9 @@ forward takes the epilogue, the exact-fp32 forward runs the loss's own row pass 
 shape since the round-2 launch-shape change).  And because
 the logits are internal to the node, the gradient pass writes over them: one logits-sized tensor instead of two.
 
+Both nodes launch the joiner forward through `joint.joint_forward` (the one place that picks its entry point) and hand their
+logits gradient to `joint.joint_backward`, whose dispatch is the table in `joint.backward_route`.
+
 Results: costs and every gradient agree with the unfused path to fp32 rounding of the row log-sum-exp (the
 statistics are merged in a different order); tests/test_fused_gpu.py states the tolerance (1e-6 relative on costs).
 
@@ -29,7 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .joint import _PRECISIONS, _call_precision, activation_code, joint_backward
+from .joint import _PRECISIONS, _call_precision, activation_code, joiner_workspace, joint_backward, joint_forward
 
 
 class _JointRnntFn(torch.autograd.Function):
@@ -39,102 +42,48 @@ class _JointRnntFn(torch.autograd.Function):
         if not ep.is_cuda:
             raise RuntimeError("wenet_celoss_amd.joint_rnnt_loss: tensors must live on a HIP device "
                                "(this package has no CPU path)")
-        lib = _lib.load()
         B, T, J = ep.shape
         U1 = pp.shape[1]
         V = w.shape[0]
         dev = ep.device
         ep, pp, w, b = ep.contiguous(), pp.contiguous(), w.contiguous(), b.contiguous()
         logits = torch.empty(B, T, U1, V, dtype=torch.float32, device=dev)
-        rws_bytes = lib.wr_rnnt_workspace_bytes(B, T, U1)
-        rws = torch.empty(rws_bytes, dtype=torch.uint8, device=dev)
+        rws = _lib.workspace("wr_rnnt_workspace_bytes", B, T, U1, device=dev)
         costs = torch.empty(B, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            st = _lib.current_stream(dev)
-            # Row statistics of the loss: as the joiner forward's epilogue (wr_joint_fwd*_lse) or as the loss's own row pass.
-            # Round 2 measured both ways per 8 utterances at the BASELINE shape: the split-precision forward pays 1.7 ms for
-            # the epilogue against 3.5 ms for the row pass (epilogue wins); the exact-fp32 forward, since its fragment-layout
-            # rewrite, pays 5.6 ms (54.8 against 49.2 ms: the epilogue's vector work does not hide behind the wave's own
-            # MFMAs) against the same 3.5 ms (the row pass wins).  WR_FUSED_LSE_EPILOGUE=1 / 0 forces either.
-            epi = os.environ.get("WR_FUSED_LSE_EPILOGUE")
-            epilogue = (terms != 0) if epi is None else (epi == "1")
-            if terms == 0 and not epilogue:
-                ws_bytes = lib.wr_joint_workspace_bytes(J, V)
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-                rc = lib.wr_joint_fwd(_lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(b), _lib.ptr(llens), _lib.ptr(tlens),
-                                      B, T, U1, J, V, act, _lib.ptr(logits), _lib.ptr(ws), ws_bytes, st)
-                _lib.check(rc, "wr_joint_fwd")
-            elif not epilogue:
-                ws_bytes = lib.wr_joint_split_workspace_bytes(J, V)
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-                rc = lib.wr_joint_fwd_split(_lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(b), _lib.ptr(llens),
-                                            _lib.ptr(tlens), B, T, U1, J, V, act, terms, _lib.ptr(logits), _lib.WR_F32,
-                                            _lib.ptr(ws), ws_bytes, st)
-                _lib.check(rc, "wr_joint_fwd_split")
-            elif terms == 0:
-                ws_bytes = lib.wr_joint_workspace_bytes(J, V)
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-                rc = lib.wr_joint_fwd_lse(_lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(b), _lib.ptr(llens),
-                                          _lib.ptr(tlens), _lib.ptr(targets), B, T, U1, J, V, act, blank, _lib.ptr(logits),
-                                          _lib.ptr(ws), ws_bytes, _lib.ptr(rws), rws_bytes, st)
-                _lib.check(rc, "wr_joint_fwd_lse")
-            else:
-                ws_bytes = lib.wr_joint_split_workspace_bytes(J, V)
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-                rc = lib.wr_joint_fwd_split_lse(_lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(b), _lib.ptr(llens),
-                                                _lib.ptr(tlens), _lib.ptr(targets), B, T, U1, J, V, act, blank, terms,
-                                                _lib.ptr(logits), _lib.ptr(ws), ws_bytes, _lib.ptr(rws), rws_bytes, st)
-                _lib.check(rc, "wr_joint_fwd_split_lse")
-            if epilogue:
-                rc = lib.wr_rnnt_loss_fwd_from_lse(_lib.ptr(logits), _lib.ptr(targets), _lib.ptr(llens), _lib.ptr(tlens), B, T,
-                                                   U1, V, blank, _lib.ptr(costs), _lib.ptr(rws), rws_bytes, st)
-                _lib.check(rc, "wr_rnnt_loss_fwd_from_lse")
-            else:
-                rc = lib.wr_rnnt_loss_fwd(_lib.ptr(logits), _lib.WR_F32, _lib.ptr(targets), _lib.ptr(llens), _lib.ptr(tlens), B,
-                                          T, U1, V, blank, _lib.ptr(costs), _lib.ptr(rws), rws_bytes, st)
-                _lib.check(rc, "wr_rnnt_loss_fwd")
+        # Row statistics of the loss: as the joiner forward's epilogue (wr_joint_fwd*_lse) or as the loss's own row pass.
+        # Round 2 measured both ways per 8 utterances at the BASELINE shape: the split-precision forward pays 1.7 ms for
+        # the epilogue against 3.5 ms for the row pass (epilogue wins); the exact-fp32 forward, since its fragment-layout
+        # rewrite, pays 5.6 ms (54.8 against 49.2 ms: the epilogue's vector work does not hide behind the wave's own
+        # MFMAs) against the same 3.5 ms (the row pass wins).  WR_FUSED_LSE_EPILOGUE=1 / 0 forces either.
+        epi = os.environ.get("WR_FUSED_LSE_EPILOGUE")
+        epilogue = (terms != 0) if epi is None else (epi == "1")
+        joint_forward(ep, pp, w, b, llens, tlens, terms, act, out=logits, stats=(targets, blank, rws) if epilogue else None)
+        if epilogue:
+            _lib.call("wr_rnnt_loss_fwd_from_lse", logits, targets, llens, tlens, B, T, U1, V, blank, costs, rws, rws.numel(),
+                      device=dev)
+        else:
+            _lib.call("wr_rnnt_loss_fwd", logits, _lib.WR_F32, targets, llens, tlens, B, T, U1, V, blank, costs, rws,
+                      rws.numel(), device=dev)
         ctx.save_for_backward(ep, pp, w, b, targets, llens, tlens, logits, rws)
         ctx.blank, ctx.clamp, ctx.terms, ctx.act = blank, clamp, terms, act
         ctx.logits_hold_gradient = False
         return costs
 
     @staticmethod
-    def _recompute_logits(ctx, lib, ep, pp, w, b, llens, tlens, logits):
-        """A second backward through a retained graph (retain_graph=True, per-loss torch.autograd.grad) finds the
-        gradient of the first one where the logits were: the write went through a raw pointer, which autograd's
-        version counter never sees.  The joiner forward is deterministic and its plain / epilogue variants give
-        bit-identical logits, so the node rebuilds them in the same buffer (one forward's time) instead of failing
-        or -- what it did before -- differentiating gradients-as-logits.  The lattice in `rws` is still the first
-        forward's (the gradient pass only reads it)."""
-        B, T, U1, V = logits.shape
-        J = ep.shape[2]
-        dev = logits.device
-        st = _lib.current_stream(dev)
-        if ctx.terms == 0:
-            ws_bytes = lib.wr_joint_workspace_bytes(J, V)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            rc = lib.wr_joint_fwd(_lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(b), _lib.ptr(llens), _lib.ptr(tlens),
-                                  B, T, U1, J, V, ctx.act, _lib.ptr(logits), _lib.ptr(ws), ws_bytes, st)
-            _lib.check(rc, "wr_joint_fwd")
-        else:
-            ws_bytes = lib.wr_joint_split_workspace_bytes(J, V)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            rc = lib.wr_joint_fwd_split(_lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(b), _lib.ptr(llens),
-                                        _lib.ptr(tlens), B, T, U1, J, V, ctx.act, ctx.terms, _lib.ptr(logits), _lib.WR_F32,
-                                        _lib.ptr(ws), ws_bytes, st)
-            _lib.check(rc, "wr_joint_fwd_split")
-
-    @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_costs):
         ep, pp, w, b, targets, llens, tlens, logits, rws = ctx.saved_tensors
-        lib = _lib.load()
         B, T, U1, V = logits.shape
         dev = logits.device
         gc = grad_costs.to(torch.float32).contiguous()
         if ctx.logits_hold_gradient:
-            with torch.cuda.device(dev):
-                _JointRnntFn._recompute_logits(ctx, lib, ep, pp, w, b, llens, tlens, logits)
+            # A second backward through a retained graph (retain_graph=True, per-loss torch.autograd.grad) finds the
+            # gradient of the first one where the logits were: the write went through a raw pointer, which autograd's
+            # version counter never sees.  The joiner forward is deterministic and its plain / epilogue variants give
+            # bit-identical logits, so the node rebuilds them in the same buffer (one forward's time) instead of failing
+            # or -- what it did before -- differentiating gradients-as-logits.  The lattice in `rws` is still the first
+            # forward's (the gradient pass only reads it).
+            joint_forward(ep, pp, w, b, llens, tlens, ctx.terms, ctx.act, out=logits)
             ctx.logits_hold_gradient = False
         # Nothing else holds the logits, so the gradient overwrites them (one logits-sized tensor instead of two).  With
         # round 1's plain loads that cost the gradient pass ~11 % (a line rewritten microseconds after it was read); with
@@ -142,11 +91,8 @@ class _JointRnntFn(torch.autograd.Function):
         # 32-utterance step).  WR_FUSED_INPLACE_BYTES=n keeps a separate buffer below n bytes.
         inplace = logits.numel() * logits.element_size() >= int(os.environ.get("WR_FUSED_INPLACE_BYTES", "0"))
         grads = logits if inplace else torch.empty_like(logits)
-        with torch.cuda.device(dev):
-            rc = lib.wr_rnnt_loss_bwd(_lib.ptr(logits), _lib.WR_F32, _lib.ptr(targets), _lib.ptr(llens), _lib.ptr(tlens),
-                                      B, T, U1, V, ctx.blank, float(ctx.clamp), _lib.ptr(gc), _lib.ptr(grads),
-                                      _lib.ptr(rws), rws.numel(), _lib.current_stream(dev))
-        _lib.check(rc, "wr_rnnt_loss_bwd")
+        _lib.call("wr_rnnt_loss_bwd", logits, _lib.WR_F32, targets, llens, tlens, B, T, U1, V, ctx.blank, float(ctx.clamp), gc,
+                  grads, rws, rws.numel(), device=dev)
         ctx.logits_hold_gradient = inplace
         d_ep, d_pp, d_w, d_b = joint_backward(grads, ep, pp, w, llens, tlens, ctx.terms, ctx.needs_input_grad[2],
                                               ctx.needs_input_grad[3], gout_zero_in_padding=True, act=ctx.act)
@@ -212,32 +158,25 @@ class _JointRnntBoundedFn(torch.autograd.Function):
         if not ep.is_cuda:
             raise RuntimeError("wenet_celoss_amd.joint_rnnt_loss: tensors must live on a HIP device "
                                "(this package has no CPU path)")
-        lib = _lib.load()
         B, T, J = ep.shape
         U1 = pp.shape[1]
         V = w.shape[0]
         dev = ep.device
         ep, pp, w, b = ep.contiguous(), pp.contiguous(), w.contiguous(), b.contiguous()
-        rws_bytes = lib.wr_rnnt_workspace_bytes(B, T, U1)
-        rws = torch.empty(rws_bytes, dtype=torch.uint8, device=dev)
+        rws = _lib.workspace("wr_rnnt_workspace_bytes", B, T, U1, device=dev)
         costs = torch.empty(B, dtype=torch.float32, device=dev)
-        ws_bytes = lib.wr_joint_workspace_bytes(J, V) if terms == 0 else lib.wr_joint_split_workspace_bytes(J, V)
+        ws = joiner_workspace(terms, J, V, dev)
+        _lib.call("wr_joint_rnnt_stats", ep, pp, w, b, llens, tlens, targets, B, T, U1, J, V, act, blank, terms, ws, ws.numel(),
+                  rws, rws.numel(), device=dev)
+        _lib.call("wr_rnnt_loss_sweeps", llens, tlens, B, T, U1, costs, rws, rws.numel(), device=dev)
+        # per-slice length arrays, built once on the host from the caller's length sync: [ll of every slice | tl ...]
+        ll_s, tl_s = [], []
+        for s in slices:
+            for u in range(s.b0, s.b1):
+                ll_s.append(min(host_t[u], s.t1) - s.t0)
+                tl_s.append(host_u[u])
+        lens = torch.tensor(ll_s + tl_s, dtype=torch.int32)
         with torch.cuda.device(dev):
-            st = _lib.current_stream(dev)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            rc = lib.wr_joint_rnnt_stats(_lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(b), _lib.ptr(llens), _lib.ptr(tlens),
-                                         _lib.ptr(targets), B, T, U1, J, V, act, blank, terms, _lib.ptr(ws), ws_bytes,
-                                         _lib.ptr(rws), rws_bytes, st)
-            _lib.check(rc, "wr_joint_rnnt_stats")
-            rc = lib.wr_rnnt_loss_sweeps(_lib.ptr(llens), _lib.ptr(tlens), B, T, U1, _lib.ptr(costs), _lib.ptr(rws), rws_bytes, st)
-            _lib.check(rc, "wr_rnnt_loss_sweeps")
-            # per-slice length arrays, built once on the host from the caller's length sync: [ll of every slice | tl ...]
-            ll_s, tl_s = [], []
-            for s in slices:
-                for u in range(s.b0, s.b1):
-                    ll_s.append(min(host_t[u], s.t1) - s.t0)
-                    tl_s.append(host_u[u])
-            lens = torch.tensor(ll_s + tl_s, dtype=torch.int32)
             lens = lens.pin_memory().to(dev, non_blocking=True) if lens.numel() else lens.to(dev)
         ctx.save_for_backward(ep, pp, w, b, targets, llens, tlens, rws)
         ctx.slice_lens = lens
@@ -249,7 +188,6 @@ class _JointRnntBoundedFn(torch.autograd.Function):
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_costs):
         ep, pp, w, b, targets, llens, tlens, rws = ctx.saved_tensors
-        lib = _lib.load()
         B, T, J = ep.shape
         U1 = pp.shape[1]
         V = w.shape[0]
@@ -268,35 +206,30 @@ class _JointRnntBoundedFn(torch.autograd.Function):
         g = torch.empty(nmax * V, dtype=torch.float32, device=dev)
         dz = torch.empty(nmax * J, dtype=torch.float32, device=dev)
         h = torch.empty(nmax * J, dtype=torch.float32, device=dev) if need_w else None
-        ws_bytes = lib.wr_joint_workspace_bytes(J, V) if ctx.terms == 0 else lib.wr_joint_split_workspace_bytes(J, V)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = joiner_workspace(ctx.terms, J, V, dev)
         nl = ctx.slice_lens.numel() // 2
         k = 0
-        with torch.cuda.device(dev):
-            st = _lib.current_stream(dev)
-            for i, s in enumerate(slices):
-                nb, nt = s.b1 - s.b0, s.t1 - s.t0
-                cells = nb * nt * U1
-                begin = (s.b0 * T + s.t0) * U1
-                rc = lib.wr_joint_rnnt_grad(_lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(b), _lib.ptr(llens),
-                                            _lib.ptr(tlens), _lib.ptr(targets), B, T, U1, J, V, ctx.act, ctx.blank,
-                                            float(ctx.clamp), ctx.terms, _lib.ptr(gc), _lib.ptr(rws), rws.numel(), begin,
-                                            begin + cells, _lib.ptr(g), _lib.ptr(ws), ws_bytes, int(i > 0), st)
-                _lib.check(rc, "wr_joint_rnnt_grad")
-                ll = ctx.slice_lens[k:k + nb]
-                tl = ctx.slice_lens[nl + k:nl + k + nb]
-                k += nb
-                de, dp, dw, db = joint_backward(g[:cells * V].view(nb, nt, U1, V), ep[s.b0:s.b1, s.t0:s.t1],
-                                                pp[s.b0:s.b1], w, ll, tl, ctx.terms, need_w, need_b,
-                                                gout_zero_in_padding=True, act=ctx.act,
-                                                dz_out=dz[:cells * J].view(nb, nt, U1, J),
-                                                h_out=h[:cells * J].view(nb, nt, U1, J) if need_w else None)
-                d_ep[s.b0:s.b1, s.t0:s.t1] = de
-                d_pp[s.b0:s.b1] += dp
-                if need_w:
-                    d_w += dw
-                if need_b:
-                    d_b += db
+        for i, s in enumerate(slices):
+            nb, nt = s.b1 - s.b0, s.t1 - s.t0
+            cells = nb * nt * U1
+            begin = (s.b0 * T + s.t0) * U1
+            _lib.call("wr_joint_rnnt_grad", ep, pp, w, b, llens, tlens, targets, B, T, U1, J, V, ctx.act, ctx.blank,
+                      float(ctx.clamp), ctx.terms, gc, rws, rws.numel(), begin, begin + cells, g, ws, ws.numel(), int(i > 0),
+                      device=dev)
+            ll = ctx.slice_lens[k:k + nb]
+            tl = ctx.slice_lens[nl + k:nl + k + nb]
+            k += nb
+            de, dp, dw, db = joint_backward(g[:cells * V].view(nb, nt, U1, V), ep[s.b0:s.b1, s.t0:s.t1],
+                                            pp[s.b0:s.b1], w, ll, tl, ctx.terms, need_w, need_b,
+                                            gout_zero_in_padding=True, act=ctx.act,
+                                            dz_out=dz[:cells * J].view(nb, nt, U1, J),
+                                            h_out=h[:cells * J].view(nb, nt, U1, J) if need_w else None)
+            d_ep[s.b0:s.b1, s.t0:s.t1] = de
+            d_pp[s.b0:s.b1] += dp
+            if need_w:
+                d_w += dw
+            if need_b:
+                d_b += db
         return d_ep, d_pp, d_w, d_b, None, None, None, None, None, None, None, None, None, None
 
 

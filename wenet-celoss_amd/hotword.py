@@ -89,10 +89,7 @@ class HotwordDecoder(DeviceDecoder):
         if nbytes == 0:
             raise RuntimeError("wr_hotword_workspace_bytes rejected the configuration")
         self._hw_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.wr_decoder_attach_hotword(self._h, ctypes.byref(w), max_ctx, _lib.ptr(self._hw_ws), nbytes,
-                                                     _lib.current_stream(self.device))
-        self._check(rc, "wr_decoder_attach_hotword")
+        self._call("wr_decoder_attach_hotword", ctypes.byref(w), max_ctx, self._hw_ws, nbytes)
 
     def greedy_hotword(self, enc_hot, enc_cold, enc_feat, enc_lens, hidden_hot, hidden_cold, n_steps: int = 64,
                        blank: int = 0, filter_on: bool = False) -> Tuple[List[List[int]], List[List[int]]]:
@@ -106,12 +103,8 @@ class HotwordDecoder(DeviceDecoder):
         hl = torch.empty(N, dtype=torch.int32, device=self.device)
         trace = torch.empty(N, cap, dtype=torch.int32, device=self.device)
         tl = torch.empty(N, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.wr_greedy_search_hotword(self._h, _lib.ptr(eh), _lib.ptr(ec), _lib.ptr(ef), _lib.ptr(lens),
-                                                    _lib.ptr(hh), hh.shape[0], _lib.ptr(hc), hc.shape[0], N, T, int(n_steps),
-                                                    int(blank), int(bool(filter_on)), _lib.ptr(hyps), _lib.ptr(hl),
-                                                    _lib.ptr(trace), cap, _lib.ptr(tl), _lib.current_stream(self.device))
-        self._check(rc, "wr_greedy_search_hotword")
+        self._call("wr_greedy_search_hotword", eh, ec, ef, lens, hh, hh.shape[0], hc, hc.shape[0], N, T, int(n_steps),
+                   int(blank), int(bool(filter_on)), hyps, hl, trace, cap, tl)
         hl_c, tl_c, hy_c, tr_c = hl.cpu().tolist(), tl.cpu().tolist(), hyps.cpu(), trace.cpu()
         if max(hl_c, default=0) > self.max_hyp:
             raise RuntimeError(f"greedy search produced {max(hl_c)} tokens but the decoder was sized for {self.max_hyp}")

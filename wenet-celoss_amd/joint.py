@@ -14,14 +14,14 @@ Precision (extension, default exact fp32): ``precision="bf16x3"`` (or env ``WR_J
 forward contraction on the bf16 matrix cores with every fp32 operand split in two (three MFMA terms, fp32
 accumulation): logits within 1e-4 of the fp32 result relative to their scale, 2.7x faster.
 ``precision="bf16"`` is the single-term AMP mode (the reference under ``--use_amp`` runs this Linear in fp16):
-under autocast the logits come out in the autocast dtype.  In both modes the activation gradient ``dZ = dY W``
-and the weight gradient ``dW = dY^T H`` use the same split (``wr_joint_bwd_dz_split``, ``wr_joint_bwd_dw_split``,
-when V is a multiple of 4; otherwise the exact kernels); the bias gradient is summed in fp32.
+under autocast the logits come out in the autocast dtype.
 ``precision="f16"`` is the same single-term mode with float16 operands (``wr_joint_fwd_f16``: the operand format of the
 reference's ``ffn_out`` under its default fp16 autocast, 11 significand bits against bf16's 8); its logits follow the
-``"bf16"`` rule.  With a float32 logits gradient, or a float16 one under ``WR_AMP_BACKWARD=kernels``, its backward runs
-``wr_joint_bwd_dz_f16`` / ``wr_joint_bwd_dw_f16``; a float16 gradient otherwise takes the library GEMMs (already fp16), a
-bfloat16 one (bf16 autocast) the ``"bf16"`` backward.
+``"bf16"`` rule.
+Every forward is launched by ``joint_forward``.  In the backward, which entry points compute the activation gradient
+``dZ = dY W`` and the weight gradient ``dW = dY^T H`` (the same split as the forward, the f16 kernels, the exact kernels,
+or the vendor GEMM library for a 16-bit gradient) and whether the gradient is widened first is the table in
+``backward_route``'s docstring, run by ``joint_backward``; the bias gradient is summed in fp32.
 ``precision="autocast"`` is resolved at every call (``effective_precision``): ``"fp32"`` outside autocast (the reference's
 ``cv`` pass and runs without ``--use_amp``), ``"bf16"`` under bf16 autocast, ``"f16"`` under fp16 autocast -- the
 recommended ``WR_JOINT_PRECISION`` for ``--use_amp``.
@@ -34,7 +34,7 @@ and derivative are evaluated inside the kernels from the pre-activation), ``prej
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import os
 
@@ -88,6 +88,40 @@ def _call_precision(precision: Optional[str]) -> str:
     return effective_precision(precision, on, torch.get_autocast_dtype("cuda") if on else None)
 
 
+def joiner_workspace(terms: int, J: int, V: int, dev):
+    """Workspace of a joiner forward (also of wr_joint_rnnt_stats / wr_joint_rnnt_grad, which run the same forward)."""
+    return _lib.workspace("wr_joint_workspace_bytes" if terms == 0 else "wr_joint_split_workspace_bytes", J, V, device=dev)
+
+
+def joint_forward(ep, pp, w, b, llens, tlens, terms: int, act: int, out=None, out_dtype=torch.float32, stats=None):
+    """Launch the joiner forward into `out` (B, T, U1, V; allocated in `out_dtype` when None) and return it.  The one
+    place that picks the entry point: exact fp32 (`terms` 0), f16 single term (TERMS_F16) or bf16 split (1 / 3 terms);
+    `stats` = (targets, blank, RNN-T workspace) asks for the variant whose epilogue also leaves the loss's row statistics
+    in that workspace (fp32 logits; the plain and the epilogue variant write bit-identical logits).  Inputs contiguous."""
+    B, T, J = ep.shape
+    U1 = pp.shape[1]
+    V = w.shape[0]
+    dev = ep.device
+    if out is None:
+        out = torch.empty(B, T, U1, V, dtype=out_dtype, device=dev)
+    ws = joiner_workspace(terms, J, V, dev)
+    head, dims = (ep, pp, w, b, llens, tlens), (B, T, U1, J, V, act)
+    if stats is not None:
+        targets, blank, rws = stats
+        if terms == 0:
+            _lib.call("wr_joint_fwd_lse", *head, targets, *dims, blank, out, ws, ws.numel(), rws, rws.numel(), device=dev)
+        else:
+            _lib.call("wr_joint_fwd_split_lse", *head, targets, *dims, blank, terms, out, ws, ws.numel(), rws, rws.numel(),
+                      device=dev)
+    elif terms == 0:
+        _lib.call("wr_joint_fwd", *head, *dims, out, ws, ws.numel(), device=dev)
+    elif terms == TERMS_F16:
+        _lib.call("wr_joint_fwd_f16", *head, *dims, out, _lib.dtype_code(out.dtype), ws, ws.numel(), device=dev)
+    else:
+        _lib.call("wr_joint_fwd_split", *head, *dims, terms, out, _lib.dtype_code(out.dtype), ws, ws.numel(), device=dev)
+    return out
+
+
 class _JointFn(torch.autograd.Function):
     # Under AMP (executor.py:91 wraps the forward in autocast) the pre-join Linear layers hand over fp16/bf16
     # activations; the MFMA kernels are exact-fp32, so inputs are cast up and the logits come out fp32.
@@ -97,40 +131,8 @@ class _JointFn(torch.autograd.Function):
         if not ep.is_cuda:
             raise RuntimeError("wenet_celoss_amd.TransducerJoint: tensors must live on a HIP device "
                                "(this package has no CPU path)")
-        lib = _lib.load()
-        B, T, J = ep.shape
-        U1 = pp.shape[1]
-        V = w.shape[0]
-        dev = ep.device
         ep, pp, w, b = ep.contiguous(), pp.contiguous(), w.contiguous(), b.contiguous()
-        if terms == 0:
-            out = torch.empty(B, T, U1, V, dtype=torch.float32, device=dev)
-            ws_bytes = lib.wr_joint_workspace_bytes(J, V)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                rc = lib.wr_joint_fwd(_lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(b), _lib.ptr(llens),
-                                      _lib.ptr(tlens), B, T, U1, J, V, act, _lib.ptr(out), _lib.ptr(ws), ws_bytes,
-                                      _lib.current_stream(dev))
-            _lib.check(rc, "wr_joint_fwd")
-        elif terms == TERMS_F16:
-            out = torch.empty(B, T, U1, V, dtype=out_dtype, device=dev)
-            ws_bytes = lib.wr_joint_split_workspace_bytes(J, V)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                rc = lib.wr_joint_fwd_f16(_lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(b), _lib.ptr(llens),
-                                          _lib.ptr(tlens), B, T, U1, J, V, act, _lib.ptr(out), _lib.dtype_code(out_dtype),
-                                          _lib.ptr(ws), ws_bytes, _lib.current_stream(dev))
-            _lib.check(rc, "wr_joint_fwd_f16")
-        else:
-            out = torch.empty(B, T, U1, V, dtype=out_dtype, device=dev)
-            ws_bytes = lib.wr_joint_split_workspace_bytes(J, V)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                rc = lib.wr_joint_fwd_split(_lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(b), _lib.ptr(llens),
-                                            _lib.ptr(tlens), B, T, U1, J, V, act, terms, _lib.ptr(out),
-                                            _lib.dtype_code(out_dtype), _lib.ptr(ws), ws_bytes,
-                                            _lib.current_stream(dev))
-            _lib.check(rc, "wr_joint_fwd_split")
+        out = joint_forward(ep, pp, w, b, llens, tlens, terms, act, out_dtype=out_dtype if terms else torch.float32)
         ctx.save_for_backward(ep, pp, w, llens, tlens)
         ctx.terms = terms
         ctx.act = act
@@ -161,13 +163,76 @@ def _mm_takes_out_dtype() -> bool:
     return _MM_OUT_DTYPE
 
 
+class Route(NamedTuple):
+    """What `backward_route` decides.  `library`: the vendor GEMMs (`_amp_backward_library`), `dz` / `dw` are then None.
+    Otherwise the two entry points, the dtype the gradient is handed to them in (its own, or widened to float32) and the
+    `terms` the split ones are given."""
+    library: bool
+    dz: Optional[str]
+    dw: Optional[str]
+    grad_dtype: torch.dtype
+    terms: int
+
+
+def backward_route(terms: int, gout_dtype, V: int, J: int, amp_backward: str, mm_out_dtype: bool) -> Route:
+    """Where a logits gradient of dtype `gout_dtype` goes in the backward of a joiner run with `terms`; `amp_backward` is
+    the value of WR_AMP_BACKWARD, `mm_out_dtype` that of `_mm_takes_out_dtype()`.  The single statement of the dispatch:
+
+    A bfloat16 gradient under TERMS_F16 ("f16" under bf16 autocast) is first read as terms = 1.  With
+    ok16 = V % 8 == 0 and V >= 32 and J % 4 == 0, rows are tried in order:
+
+      terms     gradient     condition                      dZ / dW entry points              gradient handed over
+      1         bf16, f16    ok16, not "kernels", mm        library GEMMs                     as it is
+      F16       f16          ok16, not "kernels", mm        library GEMMs                     as it is
+      0         any          --                             wr_joint_bwd_dz / _dw             float32
+      F16       any          V % 4 != 0 or V < 32           wr_joint_bwd_dz / _dw             float32
+      F16       f16          ok16                           wr_joint_bwd_dz_f16 / _dw_f16     as it is
+      F16       any          otherwise                      wr_joint_bwd_dz_f16 / _dw_f16     float32 (rounded to f16 in the kernel)
+      1, 3      bf16         ok16                           .._dz_split_bf16 / _dw_split_bf16 as it is
+      1, 3      any          otherwise                      dZ, dW chosen separately (below)  float32
+          dZ: wr_joint_bwd_dz_split when V % 4 == 0 and V >= 32, else wr_joint_bwd_dz
+          dW: wr_joint_bwd_dw_split when V % 4 == 0 and J % 4 == 0, else wr_joint_bwd_dw
+
+    Kept as they were, not repaired here:
+      * the dW rule has no V >= 32, so V % 4 == 0 and V < 32 pairs the exact dZ with the split dW (F16 goes exact for both);
+      * the dW rule tests J % 4 and the dZ rule does not: with V >= 32 the library refuses such a J in the dZ call already
+        (so does every F16 kernel row), and the test only decides for V < 32;
+      * a float16 gradient under terms 1 or 3 is only ever taken as it is by the library row; the kernels get it widened;
+      * V % 8 != 0 (with V % 4 == 0) widens a 16-bit gradient although the kernels round it back to the same values."""
+    bf16, f16 = torch.bfloat16, torch.float16
+    if terms == TERMS_F16 and gout_dtype == bf16:
+        terms = 1
+    half = f16 if terms == TERMS_F16 else bf16            # the 16-bit format this mode's kernels take as it is
+    ok16 = terms != 0 and V % 8 == 0 and V >= 32 and J % 4 == 0
+    if (ok16 and amp_backward != "kernels" and mm_out_dtype
+            and (terms == 1 and gout_dtype in (bf16, f16) or terms == TERMS_F16 and gout_dtype == f16)):
+        return Route(True, None, None, gout_dtype, terms)
+    grad = half if ok16 and gout_dtype == half else torch.float32
+    if terms == 0 or (terms == TERMS_F16 and (V % 4 != 0 or V < 32)):
+        return Route(False, "wr_joint_bwd_dz", "wr_joint_bwd_dw", grad, 0)
+    if terms == TERMS_F16:
+        return Route(False, "wr_joint_bwd_dz_f16", "wr_joint_bwd_dw_f16", grad, terms)
+    sfx = "_bf16" if grad == bf16 else ""
+    return Route(False, "wr_joint_bwd_dz_split" + sfx if V % 4 == 0 and V >= 32 else "wr_joint_bwd_dz",
+                 "wr_joint_bwd_dw_split" + sfx if V % 4 == 0 and J % 4 == 0 else "wr_joint_bwd_dw", grad, terms)
+
+
+def _valid_cells(llens, tlens, T: int, U1: int):
+    """(B, T, U1) bool: the cells inside [0, T_b) x [0, U_b]; the rest is padding."""
+    dev = llens.device
+    tt = torch.arange(T, device=dev)[None, :, None] < llens[:, None, None]
+    uu = torch.arange(U1, device=dev)[None, None, :] <= tlens[:, None, None]
+    return tt & uu
+
+
 def _amp_backward_library(lib, gout, ep, pp, w, llens, tlens, need_w, need_b, gout_zero_in_padding, act):
     """Single-term (AMP) backward with a 16-bit (bfloat16 or float16) logits gradient: the two contractions dH = dY W and [dW | db] = dY^T [H | 1]
     are plain 16-bit GEMMs with fp32 accumulation and fp32 results -- they go to the vendor GEMM library (measured at the
     B = 16 BASELINE slice: 11.9 + 15.8 ms against 23.0 + 34.5 ms for this package's single-term kernels, which stay
     reachable with WR_AMP_BACKWARD=kernels); what is fused around them stays here: ``wr_joint_dz_act`` applies the
-    activation's derivative to dH in place and writes H in bf16 (zero in padded cells), ``wr_joint_db_bf16`` sums the
-    gradient's columns for the bias; the gradient tensor is never widened."""
+    activation's derivative to dH in place and writes H in bf16 (zero in padded cells), ``wr_joint_db_bf16`` / ``_f16`` sums
+    the gradient's columns for the bias; the gradient tensor is never widened.  (`lib`, the loaded library, is not used:
+    the entry points are reached through `_lib.call`.)"""
     B, T, J = ep.shape
     U1 = pp.shape[1]
     V = w.shape[0]
@@ -177,10 +242,7 @@ def _amp_backward_library(lib, gout, ep, pp, w, llens, tlens, need_w, need_b, go
     dt = gout.dtype                                 # bfloat16, or float16 (autocast's default dtype: the reference's --use_amp)
     dz = torch.mm(g2, w.to(dt), out_dtype=torch.float32).view(B, T, U1, J)
     hb = torch.empty(M, J, dtype=dt, device=dev) if need_w else None
-    with torch.cuda.device(dev):
-        rc = lib.wr_joint_dz_act(_lib.ptr(dz), _lib.ptr(ep), _lib.ptr(pp), _lib.ptr(llens), _lib.ptr(tlens), B, T, U1, J, act,
-                                 _lib.ptr(hb), _lib.dtype_code(dt), J, _lib.current_stream(dev))
-    _lib.check(rc, "wr_joint_dz_act")
+    _lib.call("wr_joint_dz_act", dz, ep, pp, llens, tlens, B, T, U1, J, act, hb, _lib.dtype_code(dt), J, device=dev)
     d_ep = dz.sum(dim=2)
     d_pp = dz.sum(dim=1)
     d_w = d_b = None
@@ -190,120 +252,55 @@ def _amp_backward_library(lib, gout, ep, pp, w, llens, tlens, need_w, need_b, go
             # ... unless the gradient there is not finite (0 * NaN = NaN would poison every column of d_w): padded rows
             # are selected to zero, as the kernels' cell mask does -- one pass over the gradient, only when the caller
             # does not guarantee zeros there (the RNN-T loss does: no pass on the training path)
-            tt = torch.arange(T, device=dev)[None, :, None] < llens[:, None, None]
-            uu = torch.arange(U1, device=dev)[None, None, :] <= tlens[:, None, None]
-            gw = torch.where((tt & uu).view(M, 1), g2, torch.zeros((), dtype=dt, device=dev))
+            gw = torch.where(_valid_cells(llens, tlens, T, U1).view(M, 1), g2, torch.zeros((), dtype=dt, device=dev))
         d_w = torch.mm(gw.t(), hb, out_dtype=torch.float32)
     if need_b:                                      # (as one more column of that GEMM, N = J + 8, the library padded to
         d_b = torch.empty(V, dtype=torch.float32, device=dev)       # its next tile: 23.3 ms against 15.8 + 3)
-        wsb = lib.wr_joint_db_workspace_bytes(B, T, U1, V)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        ws = _lib.workspace("wr_joint_db_workspace_bytes", B, T, U1, V, device=dev)
         if gout_zero_in_padding:
             llens = tlens = None
-        with torch.cuda.device(dev):
-            fn = lib.wr_joint_db_bf16 if dt == torch.bfloat16 else lib.wr_joint_db_f16
-            rc = fn(_lib.ptr(g2), _lib.ptr(llens), _lib.ptr(tlens), B, T, U1, V, _lib.ptr(d_b), _lib.ptr(ws),
-                    wsb, _lib.current_stream(dev))
-        _lib.check(rc, "wr_joint_db_bf16")
-    return d_ep, d_pp, d_w, d_b
-
-
-def _f16_backward(lib, gout, ep, pp, w, llens, tlens, need_w, need_b, gout_zero_in_padding, act):
-    """Backward of precision "f16" from a float16 or float32 logits gradient.  A float16 gradient (fp16 autocast) goes to the
-    library GEMMs, already fp16, unless WR_AMP_BACKWARD=kernels or torch.mm has no out_dtype; otherwise the f16 kernels
-    take it as it is (V % 8 == 0) or widened to fp32 (rounded back to f16 in the kernel: the same values).  V % 4 != 0 or
-    V < 32: the exact-fp32 kernels, as every split mode."""
-    B, T, J = ep.shape
-    U1 = pp.shape[1]
-    V = w.shape[0]
-    dev = ep.device
-    ok16 = V % 8 == 0 and V >= 32 and J % 4 == 0
-    if (ok16 and gout.dtype == torch.float16 and os.environ.get("WR_AMP_BACKWARD", "library") != "kernels"
-            and _mm_takes_out_dtype()):
-        return _amp_backward_library(lib, gout.contiguous(), ep, pp, w, llens, tlens, need_w, need_b, gout_zero_in_padding, act)
-    if V % 4 != 0 or V < 32:
-        return joint_backward(gout, ep, pp, w, llens, tlens, 0, need_w, need_b, gout_zero_in_padding, act)
-    g16 = gout.dtype == torch.float16 and ok16
-    gout = gout.contiguous() if g16 else gout.float().contiguous()
-    gcode = _lib.WR_F16 if g16 else _lib.WR_F32
-    dz = torch.empty(B, T, U1, J, dtype=torch.float32, device=dev)
-    h = torch.empty_like(dz) if need_w else None
-    wsb = lib.wr_joint_dz_split_workspace_bytes(J, V)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.wr_joint_bwd_dz_f16(_lib.ptr(gout), gcode, _lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(llens),
-                                     _lib.ptr(tlens), B, T, U1, J, V, act, _lib.ptr(dz), _lib.ptr(h), _lib.ptr(ws), wsb,
-                                     _lib.current_stream(dev))
-    _lib.check(rc, "wr_joint_bwd_dz_f16")
-    d_ep = dz.sum(dim=2)
-    d_pp = dz.sum(dim=1)
-    d_w = d_b = None
-    if gout_zero_in_padding:
-        llens = tlens = None
-    if need_w:
-        d_w = torch.empty(V, J, dtype=torch.float32, device=dev)
-        d_b = torch.empty(V, dtype=torch.float32, device=dev)
-        wsb = lib.wr_joint_dw_split_workspace_bytes(B, T, U1, J, V)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.wr_joint_bwd_dw_f16(_lib.ptr(gout), gcode, _lib.ptr(h), _lib.ptr(llens), _lib.ptr(tlens), B, T, U1, J, V,
-                                         _lib.ptr(d_w), _lib.ptr(d_b), _lib.ptr(ws), wsb, _lib.current_stream(dev))
-        _lib.check(rc, "wr_joint_bwd_dw_f16")
-    elif need_b:
-        g2 = gout.float().view(-1, V)
-        if llens is not None:
-            tt = torch.arange(T, device=dev)[None, :, None] < llens[:, None, None]
-            uu = torch.arange(U1, device=dev)[None, None, :] <= tlens[:, None, None]
-            g2 = torch.where((tt & uu).view(-1, 1), g2, torch.zeros((), device=dev))
-        d_b = g2.sum(0)
-    if not need_b:
-        d_b = None
+        _lib.call("wr_joint_db_bf16" if dt == torch.bfloat16 else "wr_joint_db_f16", g2, llens, tlens, B, T, U1, V, d_b,
+                  ws, ws.numel(), device=dev)
     return d_ep, d_pp, d_w, d_b
 
 
 def joint_backward(gout, ep, pp, w, llens, tlens, terms: int, need_w: bool, need_b: bool,
                    gout_zero_in_padding: bool = False, act: int = 0, dz_out=None, h_out=None):
     """Backward of the joiner from the logits gradient `gout` (B,T,U1,V): returns (d_ep, d_pp, d_w, d_b).
-    Shared by the joiner's autograd Function and by the fused joiner + RNN-T loss Function (fused.py).
+    Shared by the joiner's autograd Function and by the fused joiner + RNN-T loss Function (fused.py); which entry points
+    it reaches is `backward_route`'s table.
     `gout_zero_in_padding`: the caller guarantees gout == 0 outside [0,T_b) x [0,U_b] (the RNN-T gradient pass
     zero-fills there).  The activation gradient still gets the lengths (it skips padded tiles and writes H = 0 in
     padded cells), but the weight-gradient reduction then needs no per-row mask: padded rows contribute 0 * 0.
-    `dz_out` / `h_out`: fp32 (B,T,U1,J) buffers for dZ and H in the exact and split modes (the memory-bounded fused node
-    reuses one pair for all its slices); allocated here when None."""
-    lib = _lib.load()
+    `dz_out` / `h_out`: fp32 (B,T,U1,J) buffers for dZ and H of the kernel routes (the memory-bounded fused node
+    reuses one pair for all its slices); allocated here when None.  (Before the dispatch became one table, the "f16"
+    mode's fall-back to the exact kernels allocated its own pair whatever was passed; no caller passes one there.)"""
     B, T, J = ep.shape
     U1 = pp.shape[1]
     V = w.shape[0]
     dev = ep.device
-    if terms == TERMS_F16 and gout.dtype == torch.bfloat16:
-        terms = 1                                   # "f16" under bf16 autocast: the "bf16" backward, as it stands
-    if terms == TERMS_F16:
-        return _f16_backward(lib, gout, ep, pp, w, llens, tlens, need_w, need_b, gout_zero_in_padding, act)
-    # AMP step: the loss hands back a bf16 gradient for bf16 logits; the split kernels take it as it is (bf16 values are
-    # their own hi parts) -- no widening pass over the logits-sized tensor, half the gradient bytes in dZ and dW
-    ok16 = terms != 0 and V % 8 == 0 and V >= 32 and J % 4 == 0
-    if (ok16 and terms == 1 and gout.dtype in (torch.bfloat16, torch.float16)
-            and os.environ.get("WR_AMP_BACKWARD", "library") != "kernels" and _mm_takes_out_dtype()):
-        return _amp_backward_library(lib, gout.contiguous(), ep, pp, w, llens, tlens, need_w, need_b, gout_zero_in_padding, act)
-    g16 = gout.dtype == torch.bfloat16 and ok16
-    gout = gout.contiguous() if g16 else gout.float().contiguous()
+    amp = os.environ.get("WR_AMP_BACKWARD", "library")
+    # (the probe behind _mm_takes_out_dtype launches a GEMM the first time: not asked where the answer cannot matter)
+    mm = gout.dtype != torch.float32 and amp != "kernels" and _mm_takes_out_dtype()
+    route = backward_route(terms, gout.dtype, V, J, amp, mm)
+    # AMP step: the loss hands back a 16-bit gradient for 16-bit logits; where the route takes it as it is (bf16 values are
+    # their own hi parts) there is no widening pass over the logits-sized tensor, half the gradient bytes in dZ and dW
+    gout = gout.to(route.grad_dtype).contiguous()
+    if route.library:
+        return _amp_backward_library(_lib.load(), gout, ep, pp, w, llens, tlens, need_w, need_b, gout_zero_in_padding, act)
+
+    def extra(name):
+        """The arguments only some entry points take: the f16 ones the gradient's dtype code, the split ones `terms`."""
+        return (_lib.dtype_code(gout.dtype),) if name.endswith("_f16") else (), (route.terms,) if "_split" in name else ()
+
     dz = dz_out if dz_out is not None else torch.empty(B, T, U1, J, dtype=torch.float32, device=dev)
     h = (h_out if h_out is not None else torch.empty_like(dz)) if need_w else None
-    if terms != 0 and V % 4 == 0 and V >= 32:       # same split as the forward (gradient rows 16-byte aligned)
-        wsb = lib.wr_joint_dz_split_workspace_bytes(J, V)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        fn = lib.wr_joint_bwd_dz_split_bf16 if g16 else lib.wr_joint_bwd_dz_split
-        with torch.cuda.device(dev):
-            rc = fn(_lib.ptr(gout), _lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(llens),
-                    _lib.ptr(tlens), B, T, U1, J, V, act, terms, _lib.ptr(dz), _lib.ptr(h),
-                    _lib.ptr(ws), wsb, _lib.current_stream(dev))
-        _lib.check(rc, "wr_joint_bwd_dz_split")
-    else:
-        with torch.cuda.device(dev):
-            rc = lib.wr_joint_bwd_dz(_lib.ptr(gout), _lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(llens),
-                                     _lib.ptr(tlens), B, T, U1, J, V, act, _lib.ptr(dz), _lib.ptr(h),
-                                     _lib.current_stream(dev))
-        _lib.check(rc, "wr_joint_bwd_dz")
+    code, tm = extra(route.dz)
+    ws = ()
+    if route.dz != "wr_joint_bwd_dz":
+        ws = _lib.workspace("wr_joint_dz_split_workspace_bytes", J, V, device=dev)
+        ws = (ws, ws.numel())
+    _lib.call(route.dz, gout, *code, ep, pp, w, llens, tlens, B, T, U1, J, V, act, *tm, dz, h, *ws, device=dev)
     d_ep = dz.sum(dim=2)
     d_pp = dz.sum(dim=1)
     d_w = d_b = None
@@ -312,28 +309,16 @@ def joint_backward(gout, ep, pp, w, llens, tlens, terms: int, need_w: bool, need
     if need_w:
         d_w = torch.empty(V, J, dtype=torch.float32, device=dev)
         d_b = torch.empty(V, dtype=torch.float32, device=dev)
-        if terms != 0 and V % 4 == 0 and J % 4 == 0:
-            wsb = lib.wr_joint_dw_split_workspace_bytes(B, T, U1, J, V)
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            fn = lib.wr_joint_bwd_dw_split_bf16 if g16 else lib.wr_joint_bwd_dw_split
-            with torch.cuda.device(dev):
-                rc = fn(_lib.ptr(gout), _lib.ptr(h), _lib.ptr(llens), _lib.ptr(tlens), B, T, U1,
-                        J, V, terms, _lib.ptr(d_w), _lib.ptr(d_b), _lib.ptr(ws), wsb,
-                        _lib.current_stream(dev))
-            _lib.check(rc, "wr_joint_bwd_dw_split")
+        code, tm = extra(route.dw)
+        if route.dw == "wr_joint_bwd_dw":
+            ws = _lib.workspace("wr_joint_dw_workspace_bytes", J, V, device=dev)
         else:
-            wsb = lib.wr_joint_dw_workspace_bytes(J, V)
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                rc = lib.wr_joint_bwd_dw(_lib.ptr(gout), _lib.ptr(h), _lib.ptr(llens), _lib.ptr(tlens), B, T, U1, J, V,
-                                         _lib.ptr(d_w), _lib.ptr(d_b), _lib.ptr(ws), wsb, _lib.current_stream(dev))
-            _lib.check(rc, "wr_joint_bwd_dw")
+            ws = _lib.workspace("wr_joint_dw_split_workspace_bytes", B, T, U1, J, V, device=dev)
+        _lib.call(route.dw, gout, *code, h, llens, tlens, B, T, U1, J, V, *tm, d_w, d_b, ws, ws.numel(), device=dev)
     elif need_b:
         g2 = gout.float().view(-1, V)
         if llens is not None:
-            tt = torch.arange(T, device=dev)[None, :, None] < llens[:, None, None]
-            uu = torch.arange(U1, device=dev)[None, None, :] <= tlens[:, None, None]
-            g2 = torch.where((tt & uu).view(-1, 1), g2, torch.zeros((), device=dev))
+            g2 = torch.where(_valid_cells(llens, tlens, T, U1).view(-1, 1), g2, torch.zeros((), device=dev))
         d_b = g2.sum(0)
     if not need_b:
         d_b = None

@@ -20,7 +20,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from . import _lib
-from .joint import _PRECISIONS, _call_precision, activation_code
+from .joint import _PRECISIONS, _call_precision, activation_code, joiner_workspace
 
 
 def _prepare(targets, logit_lengths, target_lengths, B: int, T: int, U1: int, V: int, dev, what: str):
@@ -74,15 +74,10 @@ def rnnt_forced_align(logits: torch.Tensor, targets: torch.Tensor, logit_lengths
     tg, ll, tl = _prepare(targets, logit_lengths, target_lengths, B, T, U1, V, dev, what)
     if not x.is_cuda:
         raise RuntimeError(f"wenet_celoss_amd.{what}: logits must live on a HIP device (this package has no CPU path)")
-    lib = _lib.load()
     frames = torch.empty(B, U1 - 1, dtype=torch.int32, device=dev)
     scores = torch.empty(B, dtype=torch.float64, device=dev)
-    ws_bytes = lib.wr_rnnt_workspace_bytes(B, T, U1)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.wr_rnnt_align(_lib.ptr(x), code, _lib.ptr(tg), _lib.ptr(ll), _lib.ptr(tl), B, T, U1, V, blank,
-                               _lib.ptr(frames), _lib.ptr(scores), _lib.ptr(ws), ws_bytes, _lib.current_stream(dev))
-    _lib.check(rc, "wr_rnnt_align")
+    ws = _lib.workspace("wr_rnnt_workspace_bytes", B, T, U1, device=dev)
+    _lib.call("wr_rnnt_align", x, code, tg, ll, tl, B, T, U1, V, blank, frames, scores, ws, ws.numel(), device=dev)
     return frames, scores
 
 
@@ -116,22 +111,13 @@ def joint_rnnt_forced_align(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Ten
     tg, ll, tl = _prepare(targets, logit_lengths, target_lengths, B, T, U1, V, dev, what)
     if not (ep.is_cuda and pp.is_cuda and w.is_cuda and b.is_cuda):
         raise RuntimeError(f"wenet_celoss_amd.{what}: tensors must live on a HIP device (this package has no CPU path)")
-    lib = _lib.load()
     frames = torch.empty(B, U1 - 1, dtype=torch.int32, device=dev)
     scores = torch.empty(B, dtype=torch.float64, device=dev)
-    rws_bytes = lib.wr_rnnt_workspace_bytes(B, T, U1)
-    rws = torch.empty(rws_bytes, dtype=torch.uint8, device=dev)
-    ws_bytes = lib.wr_joint_workspace_bytes(J, V) if terms == 0 else lib.wr_joint_split_workspace_bytes(J, V)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        st = _lib.current_stream(dev)
-        rc = lib.wr_joint_rnnt_stats(_lib.ptr(ep), _lib.ptr(pp), _lib.ptr(w), _lib.ptr(b), _lib.ptr(ll), _lib.ptr(tl),
-                                     _lib.ptr(tg), B, T, U1, J, V, act, blank, terms, _lib.ptr(ws), ws_bytes,
-                                     _lib.ptr(rws), rws_bytes, st)
-        _lib.check(rc, "wr_joint_rnnt_stats")
-        rc = lib.wr_rnnt_align_from_stats(_lib.ptr(tg), _lib.ptr(ll), _lib.ptr(tl), B, T, U1, _lib.ptr(frames),
-                                          _lib.ptr(scores), _lib.ptr(rws), rws_bytes, st)
-        _lib.check(rc, "wr_rnnt_align_from_stats")
+    rws = _lib.workspace("wr_rnnt_workspace_bytes", B, T, U1, device=dev)
+    ws = joiner_workspace(terms, J, V, dev)
+    _lib.call("wr_joint_rnnt_stats", ep, pp, w, b, ll, tl, tg, B, T, U1, J, V, act, blank, terms, ws, ws.numel(), rws,
+              rws.numel(), device=dev)
+    _lib.call("wr_rnnt_align_from_stats", tg, ll, tl, B, T, U1, frames, scores, rws, rws.numel(), device=dev)
     return frames, scores
 
 

@@ -64,17 +64,12 @@ class _RNNTLossFn(torch.autograd.Function):
         if not logits.is_cuda:
             raise RuntimeError("wenet_celoss_amd.rnnt_loss: logits must live on a HIP device "
                                "(this package has no CPU path)")
-        lib = _lib.load()
         B, T, U1, V = logits.shape
         dev = logits.device
-        ws_bytes = lib.wr_rnnt_workspace_bytes(B, T, U1)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _lib.workspace("wr_rnnt_workspace_bytes", B, T, U1, device=dev)
         costs = torch.empty(B, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.wr_rnnt_loss_fwd(_lib.ptr(logits), _lib.dtype_code(logits.dtype), _lib.ptr(targets),
-                                      _lib.ptr(logit_lengths), _lib.ptr(target_lengths), B, T, U1, V, blank,
-                                      _lib.ptr(costs), _lib.ptr(ws), ws_bytes, _lib.current_stream(dev))
-        _lib.check(rc, "wr_rnnt_loss_fwd")
+        _lib.call("wr_rnnt_loss_fwd", logits, _lib.dtype_code(logits.dtype), targets, logit_lengths, target_lengths, B, T, U1,
+                  V, blank, costs, ws, ws.numel(), device=dev)
         ctx.save_for_backward(logits, targets, logit_lengths, target_lengths, ws)
         ctx.blank, ctx.clamp, ctx.inplace_grad = blank, clamp, inplace_grad
         return costs.to(logits.dtype) if logits.dtype != torch.float32 else costs
@@ -83,17 +78,12 @@ class _RNNTLossFn(torch.autograd.Function):
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_costs):
         logits, targets, logit_lengths, target_lengths, ws = ctx.saved_tensors
-        lib = _lib.load()
         B, T, U1, V = logits.shape
         dev = logits.device
         grads = logits if ctx.inplace_grad else torch.empty_like(logits)
         gc = grad_costs.to(torch.float32).contiguous()
-        with torch.cuda.device(dev):
-            rc = lib.wr_rnnt_loss_bwd(_lib.ptr(logits), _lib.dtype_code(logits.dtype), _lib.ptr(targets),
-                                      _lib.ptr(logit_lengths), _lib.ptr(target_lengths), B, T, U1, V, ctx.blank,
-                                      float(ctx.clamp), _lib.ptr(gc), _lib.ptr(grads), _lib.ptr(ws), ws.numel(),
-                                      _lib.current_stream(dev))
-        _lib.check(rc, "wr_rnnt_loss_bwd")
+        _lib.call("wr_rnnt_loss_bwd", logits, _lib.dtype_code(logits.dtype), targets, logit_lengths, target_lengths, B, T, U1,
+                  V, ctx.blank, float(ctx.clamp), gc, grads, ws, ws.numel(), device=dev)
         return grads, None, None, None, None, None, None
 
 
@@ -137,20 +127,13 @@ class RNNTLoss(torch.nn.Module):
 
 def rnnt_lattice(logits, targets, logit_lengths, target_lengths, blank=0):
     """Diagnostics for tests: (costs, alpha, beta) with alpha/beta as plain (B,T,U+1) tensors."""
-    lib = _lib.load()
     B, T, U1, V = logits.shape
     dev = logits.device
-    ws_bytes = lib.wr_rnnt_workspace_bytes(B, T, U1)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace("wr_rnnt_workspace_bytes", B, T, U1, device=dev)
     costs = torch.empty(B, dtype=torch.float32, device=dev)
     alpha = torch.empty(B, T, U1, dtype=torch.float32, device=dev)
     beta = torch.empty_like(alpha)
-    with torch.cuda.device(dev):
-        st = _lib.current_stream(dev)
-        _lib.check(lib.wr_rnnt_loss_fwd(_lib.ptr(logits), _lib.dtype_code(logits.dtype), _lib.ptr(targets),
-                                        _lib.ptr(logit_lengths), _lib.ptr(target_lengths), B, T, U1, V, blank,
-                                        _lib.ptr(costs), _lib.ptr(ws), ws_bytes, st), "wr_rnnt_loss_fwd")
-        _lib.check(lib.wr_rnnt_export_lattice(_lib.ptr(ws), ws_bytes, _lib.ptr(logit_lengths),
-                                              _lib.ptr(target_lengths), B, T, U1, _lib.ptr(alpha), _lib.ptr(beta),
-                                              st), "wr_rnnt_export_lattice")
+    _lib.call("wr_rnnt_loss_fwd", logits, _lib.dtype_code(logits.dtype), targets, logit_lengths, target_lengths, B, T, U1, V,
+              blank, costs, ws, ws.numel(), device=dev)
+    _lib.call("wr_rnnt_export_lattice", ws, ws.numel(), logit_lengths, target_lengths, B, T, U1, alpha, beta, device=dev)
     return costs, alpha, beta
