@@ -597,6 +597,46 @@ int wr_rnnt_align_from_stats(const int32_t *targets_d, const int32_t *logit_leng
                              double *scores_d /* [B] out */, void *rnnt_workspace_d, size_t rnnt_workspace_bytes,
                              void *stream);
 
+/* The additive-joiner ("simple") RNN-T loss: the transducer loss of logits(b,t,u,v) = am[b,t,v] + lm[b,u,v], which is
+ * what k2's rnnt_loss_simple computes (wenet/transducer/transducer_k2_loss.py:140-157), without a (B,T,U1,V) tensor.
+ * am [B,T,V], lm [B,U1,V] fp32; symbols [B,U1-1]; lengths as wr_rnnt_loss_fwd (1 <= logit_lengths[b] <= T or 0 for an
+ * empty utterance, 0 <= target_lengths[b] <= U1-1); V >= 2, U1 <= 1024.  Two workspaces: the RNN-T one
+ * (wr_rnnt_workspace_bytes(B,T,U1)) and this loss's own scratch (wr_rnnt_simple_workspace_bytes: the row maxima of am and
+ * lm, and a few floats per lattice cell for the gradient -- never logits-sized).
+ *
+ * wr_rnnt_simple_stats: the row statistics of every valid cell into the RNN-T workspace, in the layout and with the
+ * conventions of pass 1 of wr_rnnt_loss_fwd: denom(t,u) = log sum_v exp(am[t,v] + lm[u,v]) as a [T x V].[V x U1]
+ * contraction of the exponentiated, max-shifted operands (exact-fp32 MFMA), and the skewed blank / label log-probabilities
+ * (emit = 0 at u == U_b).  wr_rnnt_loss_sweeps, wr_rnnt_export_lattice and wr_rnnt_align_from_stats follow unchanged.
+ * A valid cell whose factored sum is zero, not finite or below 1e-20 (the peaks of am[t] and lm[u] sit on different
+ * symbols and are both tall) raises the flag word of the RNN-T workspace; a second, direct kernel (one wave per cell,
+ * running maximum over am + lm) is always enqueued and redoes every cell then -- its workgroups leave at once
+ * otherwise.  No host synchronisation.
+ *
+ * wr_rnnt_simple_grad: d_am [B,T,V] and d_lm [B,U1,V] (fp32, every element written, zero for t >= T_b and u > U_b) of
+ * sum_b grad_costs[b] * cost_b (NULL = 1; no clamp, as k2), as two MFMA contractions over u and over t plus the scatter
+ * terms at the blank and the labels, summed in a fixed order: bit-identical run to run.  Needs both workspaces after
+ * wr_rnnt_simple_stats + wr_rnnt_loss_sweeps; it only reads the RNN-T one.  With the flag raised the contractions are
+ * replaced by direct sums of occupancy * softmax.  occ_emit_d / occ_blank_d [B,T,U1] (nullable): the arc occupancies
+ * exp(alpha(t,u) + emit(t,u) + beta(t,u+1) - ll) and exp(alpha(t,u) + blank(t,u) + beta(t+1,u) - ll) (beta := 0 past the
+ * final cell), zero outside the valid region, not scaled by grad_costs -- k2's px_grad / py_grad transposed. */
+size_t wr_rnnt_simple_workspace_bytes(int B, int T, int U1, int V);
+
+int wr_rnnt_simple_stats(const float *am_d, const float *lm_d, const int32_t *symbols_d,
+                         const int32_t *logit_lengths_d, const int32_t *target_lengths_d,
+                         int B, int T, int U1, int V, int blank,
+                         void *simple_workspace_d, size_t simple_workspace_bytes,
+                         void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream);
+
+int wr_rnnt_simple_grad(const float *am_d, const float *lm_d, const int32_t *symbols_d,
+                        const int32_t *logit_lengths_d, const int32_t *target_lengths_d,
+                        int B, int T, int U1, int V, int blank,
+                        const float *grad_costs_d /* [B] or NULL */,
+                        float *d_am_d /* [B,T,V] out */, float *d_lm_d /* [B,U1,V] out */,
+                        float *occ_emit_d /* [B,T,U1] out or NULL */, float *occ_blank_d /* [B,T,U1] out or NULL */,
+                        void *simple_workspace_d, size_t simple_workspace_bytes,
+                        const void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream);
+
 /* CTC forced alignment: Viterbi over the T x (2S+1) lattice, replacing
  * forced_align, wenet/utils/ctc_util.py:27-83 (CLI wenet/bin/alignment.py:215).  logits [B, Tmax, V]: pre-softmax
  * ctc_lo output, or log-posteriors if normalized != 0 (the reference is handed ctc.log_softmax(...)).

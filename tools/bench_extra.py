@@ -488,12 +488,72 @@ def bench_align(args):
             print(json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in rec.items()}), flush=True)
 
 
+def bench_simple(args):
+    """The additive-joiner loss step (rnnt_loss_simple forward + backward) beside the composite it replaces:
+    am.unsqueeze(2) + lm.unsqueeze(1) -> rnnt_loss, fp32, which writes and re-reads a (B,T,U+1,V) tensor.  N(0,1) inputs,
+    full lengths.  HIP events around each step after warm-up, the two alternating, median of --steps runs; peak memory of
+    each above what the inputs hold.  One JSON line.  --only simple: the new step alone (for a kernel trace)."""
+    import wenet_celoss_amd as w
+    dev = torch.device("cuda:0")
+    B, T, U, V = args.B, args.T, args.U, args.V
+    gen = torch.Generator(device=dev).manual_seed(0)
+    am = torch.randn(B, T, V, device=dev, generator=gen).requires_grad_(True)
+    lm = torch.randn(B, U + 1, V, device=dev, generator=gen).requires_grad_(True)
+    sy = torch.randint(1, V, (B, U), device=dev, generator=gen)
+    sy32 = sy.to(torch.int32)
+    ll = torch.full((B,), T, dtype=torch.int32, device=dev)
+    tl = torch.full((B,), U, dtype=torch.int32, device=dev)
+
+    def simple():
+        am.grad = lm.grad = None
+        loss = w.rnnt_loss_simple(lm, am, sy, 0, reduction="mean")
+        loss.backward()
+        return loss
+
+    def composite():
+        am.grad = lm.grad = None
+        loss = w.rnnt_loss(am.unsqueeze(2) + lm.unsqueeze(1), sy32, ll, tl, blank=0, reduction="mean")
+        loss.backward()
+        return loss
+
+    fns = {"simple": simple} if args.only == "simple" else {"simple": simple, "composite": composite}
+    peak, loss = {}, {}
+    for name, fn in fns.items():                       # warm-up, and the memory peak of one step
+        fn()
+        am.grad = lm.grad = None
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        loss[name] = float(fn())
+        torch.cuda.synchronize()
+        peak[name] = torch.cuda.max_memory_allocated() - base
+    times = {name: [] for name in fns}
+    for _ in range(max(args.steps, 1)):
+        for name, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); fn(); b.record()
+            torch.cuda.synchronize()
+            times[name].append(a.elapsed_time(b))
+    med = {name: sorted(ts)[len(ts) // 2] for name, ts in times.items()}
+    rec = {"what": "rnnt_loss_simple fwd+bwd", "shape": [B, T, U + 1, V], "runs": max(args.steps, 1),
+           "simple_ms": round(med["simple"], 3), "simple_ms_min_max": [round(min(times["simple"]), 3), round(max(times["simple"]), 3)],
+           "simple_peak_mib": round(peak["simple"] / 2**20, 1), "simple_loss": loss["simple"],
+           "contraction_gflop": round(3 * 2.0 * B * T * (U + 1) * V / 1e9, 1),
+           "logits_gib": round(B * T * (U + 1) * V * 4 / 2**30, 2)}
+    if "composite" in med:
+        rec.update({"composite_ms": round(med["composite"], 3),
+                    "composite_ms_min_max": [round(min(times["composite"]), 3), round(max(times["composite"]), 3)],
+                    "composite_peak_mib": round(peak["composite"] / 2**20, 1), "composite_loss": loss["composite"],
+                    "composite_over_simple": round(med["composite"] / med["simple"], 1)})
+    print(json.dumps(rec), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align"])
+    ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align", "simple"])
     ap.add_argument("--n-steps", type=int, default=64)
     ap.add_argument("--chunks", type=int, default=4)
-    ap.add_argument("--B", type=int, default=32)
+    ap.add_argument("--B", type=int, default=None, help="batch size (default 32; simple: 16)")
     ap.add_argument("--T", type=int, default=1000)
     ap.add_argument("--U", type=int, default=150)
     ap.add_argument("--V", type=int, default=5000)
@@ -502,15 +562,18 @@ if __name__ == "__main__":
     ap.add_argument("--fwd-only", action="store_true", help="joint: stop after the exact forward sweep")
     ap.add_argument("--ragged", action="store_true", help="step: frames in [0.8 T, T] sorted, labels in [U/3, U]")
     ap.add_argument("--buckets", type=int, default=4, help="step: label-length groups of the fused node (1 = off)")
-    ap.add_argument("--only", default="", help="step: comma-separated subset of the configurations")
+    ap.add_argument("--only", default="", help="step: comma-separated subset of the configurations; simple: \"simple\" "
+                                              "skips the composite")
     ap.add_argument("--budget-mb", type=float, default=0.0,
                     help="step: time the memory-bounded fused node (logits_budget = this many MiB) beside the plain one, "
                          "fp32 and bf16x3, with max_memory_allocated of each")
     ap.add_argument("--streams", type=int, default=64, help="greedy: independent streams decoded together")
     ap.add_argument("--tile", type=int, default=0, help="lane-GEMM tile policy of the decoders (wr_tune_set key 6)")
     a = ap.parse_args()
+    if a.B is None:
+        a.B = 16 if a.what == "simple" else 32
     if a.tile:
         from wenet_celoss_amd import _lib
         _lib.load().wr_tune_set(6, a.tile)
     {"joint": bench_joint, "ctc": bench_ctc, "greedy": bench_greedy, "beam": bench_beam, "step": bench_step, "ctcdec": bench_ctcdec, "hotword": bench_hotword,
-     "align": bench_align}[a.what](a)
+     "align": bench_align, "simple": bench_simple}[a.what](a)

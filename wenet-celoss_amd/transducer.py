@@ -35,8 +35,25 @@ from .fused import joint_rnnt_loss, plan_buckets
 from .joint import TransducerJoint, _call_precision
 from .rnnt_align import joint_rnnt_forced_align, rnnt_forced_align
 from .rnnt_loss import rnnt_loss
+from .rnnt_simple import rnnt_loss_simple, rnnt_simple_forced_align
 from .search.greedy_search import basic_greedy_search, basic_greedy_search_both, basic_greedy_search_hw
 from .search.prefix_beam_search import PrefixBeamSearch
+
+
+def _output_width(module: nn.Module, role: str, joint: nn.Module, joint_ffn: str) -> int:
+    """Feature width of an encoder's / predictor's output: `output_size` (a method on wenet encoders, an attribute on its
+    predictors), `_output_size`, the predictor's output projection, else the joiner's pre-join projection for it."""
+    for name in ("output_size", "_output_size"):
+        width = getattr(module, name, None)
+        width = width() if callable(width) else width
+        if isinstance(width, int):
+            return width
+    for owner, name in ((module, "projection"), (joint, joint_ffn)):
+        lin = getattr(owner, name, None)
+        if isinstance(lin, nn.Linear):
+            return lin.out_features if owner is module else lin.in_features
+    raise ValueError(f"Transducer: simple_loss_weight > 0 needs the {role}'s output width (no output_size, and the joiner "
+                     f"has no {joint_ffn})")
 
 
 def check_limits(text: torch.Tensor, text_lengths: torch.Tensor, with_ctc: bool) -> None:
@@ -61,7 +78,7 @@ class Transducer(nn.Module):
                  context_bias: Optional[nn.Module] = None, ctc_weight: float = 0, ignore_id: int = IGNORE_ID,
                  reverse_weight: float = 0.0, lsm_weight: float = 0.0, length_normalized_loss: bool = False,
                  transducer_weight: float = 1.0, attention_weight: float = 0.0, hw_weight: float = 0.4,
-                 loss_mode: str = "both") -> None:
+                 loss_mode: str = "both", simple_loss_weight: float = 0.0) -> None:
         assert attention_weight + ctc_weight + transducer_weight == 1.0          # transducer.py:46 (kept as is)
         super().__init__()
         # ASRModel part (asr_model.py:38-70): sos/eos are the last class
@@ -100,6 +117,14 @@ class Transducer(nn.Module):
         # memory-bounded fused node (fused.joint_rnnt_loss `logits_budget`, bytes): no logits tensor, the backward
         # recomputes them in slices of at most this size.  None: WR_FUSED_LOGITS_BUDGET_MB if set, else the plain node.
         self.logits_budget: Optional[int] = None
+        # the additive-joiner ("simple") loss of the reference's second transducer class (transducer_k2_loss.py:73-78,
+        # :147-157): two linear heads onto the vocabulary whose sum is the logits of a second RNN-T loss, added with this
+        # weight.  Each head is applied to the tensor its name says (the reference builds them with the two widths
+        # crossed, which only works when the widths are equal).  0.0: no parameters, no extra loss.
+        self.simple_loss_weight = float(simple_loss_weight)
+        if self.simple_loss_weight > 0.0:
+            self.simple_am_proj = nn.Linear(_output_width(encoder, "encoder", joint, "enc_ffn"), vocab_size)
+            self.simple_lm_proj = nn.Linear(_output_width(predictor, "predictor", joint, "pred_ffn"), vocab_size)
 
     # ------------------------------------------------------------- training --
     def _logits_budget(self) -> Optional[int]:
@@ -157,6 +182,23 @@ class Transducer(nn.Module):
                          rnnt_text_lengths.contiguous(), blank=self.blank, reduction="mean")
         return joint_out, loss
 
+    def _simple_inputs(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, predictor_out: torch.Tensor,
+                       text: torch.Tensor, text_lengths: torch.Tensor):
+        """(lm, am, symbols, boundary) of the additive-joiner loss (transducer_k2_loss.py:131-148): the two heads on the
+        encoder and predictor outputs the joiner sees, IGNORE_ID mapped to 0, boundary rows (0, 0, U_b, T_b)."""
+        symbols = text.to(torch.int64)
+        symbols = torch.where(symbols == self.ignore_id, 0, symbols)
+        boundary = torch.zeros((text.size(0), 4), dtype=torch.int64, device=encoder_out.device)
+        boundary[:, 2] = text_lengths
+        boundary[:, 3] = encoder_out_lens
+        return self.simple_lm_proj(predictor_out), self.simple_am_proj(encoder_out), symbols, boundary
+
+    def compute_simple_loss(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, predictor_out: torch.Tensor,
+                            text: torch.Tensor, text_lengths: torch.Tensor) -> torch.Tensor:
+        """rnnt_loss_simple on the two vocabulary heads, reduction "mean" (transducer_k2_loss.py:147-157)."""
+        lm, am, symbols, boundary = self._simple_inputs(encoder_out, encoder_out_lens, predictor_out, text, text_lengths)
+        return rnnt_loss_simple(lm, am, symbols, self.blank, boundary=boundary, reduction="mean")
+
     def _can_fuse_loss(self) -> bool:
         jt = self.joint
         # the AMP single-term modes keep 16-bit logits ("autocast" is one of them under autocast only)
@@ -201,6 +243,10 @@ class Transducer(nn.Module):
 
         _, loss_rnnt = self.compute_loss(encoder_out, encoder_out_lens, predictor_out, text, text_lengths)
         loss = self.transducer_weight * loss_rnnt
+        loss_simple: Optional[torch.Tensor] = None
+        if getattr(self, "simple_loss_weight", 0.0) > 0.0:
+            loss_simple = self.compute_simple_loss(encoder_out, encoder_out_lens, predictor_out, text, text_lengths)
+            loss = loss + self.simple_loss_weight * loss_simple
 
         loss_att: Optional[torch.Tensor] = None
         if self.attention_decoder_weight != 0.0 and self.decoder is not None:
@@ -228,19 +274,28 @@ class Transducer(nn.Module):
                 hw_label_pad = add_blank(hw_label, self.blank, self.ignore_id)
                 hw_loss = self.hw_criterion(hw_output_dec.permute(0, 2, 1), hw_label_pad)
             loss = loss + self.hw_weight * hw_loss
-        return {"loss": loss, "loss_att": loss_att, "loss_ctc": loss_ctc, "loss_rnnt": loss_rnnt, "hw_loss": hw_loss}
+        out = {"loss": loss, "loss_att": loss_att, "loss_ctc": loss_ctc, "loss_rnnt": loss_rnnt, "hw_loss": hw_loss}
+        if loss_simple is not None:
+            out["loss_simple"] = loss_simple
+        return out
 
     @torch.jit.unused      # HIP-backed, like forward
     def forced_align(self, speech: torch.Tensor, speech_lengths: torch.Tensor, text: torch.Tensor,
                      text_lengths: torch.Tensor, context_list: torch.Tensor = torch.IntTensor([0]),
-                     context_lengths: torch.Tensor = torch.IntTensor([0])) -> Tuple[torch.Tensor, torch.Tensor]:
+                     context_lengths: torch.Tensor = torch.IntTensor([0]), head: str = "joint"
+                     ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Forced alignment with the transducer head (extension; the reference aligns with the CTC head only,
         wenet/bin/alignment.py): the best path through the lattice whose negative log-sum `forward` reports as
         `loss_rnnt` -- the same encoder, ContextBias biasing and blank / IGNORE_ID label mapping as the loss block.
         With the joiner's precision resolving to "fp32" or "bf16x3" no logits tensor is formed (joint_rnnt_forced_align);
         under a 16-bit (AMP) mode the joiner's logits go to rnnt_forced_align.  Frames are encoder frames (after
-        subsampling).  Returns (label_frames (B, U) int32, -1 past text_lengths; scores (B,) float64) on the device.
-        Call it in eval mode unless dropout is wanted."""
+        subsampling).  ``head="simple"`` aligns on the lattice of the additive-joiner loss instead (`loss_simple`; the
+        model must have been built with `simple_loss_weight > 0`).  Returns (label_frames (B, U) int32, -1 past
+        text_lengths; scores (B,) float64) on the device.  Call it in eval mode unless dropout is wanted."""
+        if head not in ("joint", "simple"):
+            raise ValueError(f"forced_align: head must be \"joint\" or \"simple\", got {head!r}")
+        if head == "simple" and not hasattr(self, "simple_am_proj"):
+            raise ValueError("forced_align: head=\"simple\" needs a model built with simple_loss_weight > 0")
         assert text_lengths.dim() == 1, text_lengths.shape
         assert (speech.shape[0] == speech_lengths.shape[0] == text.shape[0] == text_lengths.shape[0]), \
             (speech.shape, speech_lengths.shape, text.shape, text_lengths.shape)
@@ -248,6 +303,10 @@ class Transducer(nn.Module):
         with torch.no_grad():
             _, encoder_out, _, encoder_out_lens, _, predictor_out, _ = self._loss_inputs(
                 speech, speech_lengths, text, context_list, context_lengths)
+            if head == "simple":
+                lm, am, symbols, boundary = self._simple_inputs(encoder_out, encoder_out_lens, predictor_out, text,
+                                                                text_lengths)
+                return rnnt_simple_forced_align(lm, am, symbols, self.blank, boundary=boundary)
             rnnt_text = text.to(torch.int64)
             rnnt_text = torch.where(rnnt_text == self.ignore_id, 0, rnnt_text).to(torch.int32)
             rnnt_text_lengths = text_lengths.to(torch.int32)
