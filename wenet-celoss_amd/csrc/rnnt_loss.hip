@@ -22,12 +22,15 @@
 //           writes grad = g_b * (exp(logit + alpha + beta + cost - denom) with
 //           the blank / label corrections), zero in the padded region.  A dead
 //           cell (every exponential provably +0, kDeadThr) is written as
-//           g_b * 0 without reading its logits.
+//           g_b * 0 without reading its logits; a faint cell (the main
+//           exponential provably +0, the blank or label term not) the same
+//           way except that element, for which that one logit is read.
 //           HBM-bound: 4*V read (live cells only) + 4*V written per cell.
 //
 // Algorithmic traffic: 3 * 4 * V bytes per live valid cell, 2 * 4 * V per dead
-// cell (+ 4*V per padded cell).  Dead cells are about 30 % of the BASELINE
-// batch (iid N(0,1) logits); the share depends on the data.
+// cell, 2 * 4 * V + two sectors read per faint cell (+ 4*V per padded cell).
+// Dead and faint cells are about 38 % of the BASELINE batch (iid N(0,1)
+// logits; 2 % faint); the share depends on the data.
 #include "row_stream.hpp"
 #include "wr_common.hpp"
 
@@ -203,12 +206,16 @@ __global__ __launch_bounds__(kRnntMaxCols) void rnnt_sweep_kernel(
 }
 
 // ------------------------------------------------------------------ pass 3 --
-// Dead cells.  Every exponential of a cell's gradient is bounded without its logits: x <= denom for every logit x of
-// the row, so the main term's exponent x + alpha + beta + cost - denom is at most lo = alpha + beta + cost (the
-// cell's log-occupancy), the blank term's at most alpha + cost + beta(t+1,u) (alpha + cost at the final cell) and the
-// label term's at most alpha + cost + beta(t,u+1).  When every bound that applies is below kDeadThr, each
-// fast_exp2 of the row returns +0, the case-chain subtraction gives 0 - 0 = +0, and the gradient is finish(0) in
-// every element whatever the logits hold: such a row is written without being read.
+// Dead and faint cells.  Every exponential of a cell's gradient is bounded without its logits: x <= denom for every
+// logit x of the row, so the main term's exponent x + alpha + beta + cost - denom is at most lo = alpha + beta + cost
+// (the cell's log-occupancy), the blank term's at most alpha + cost + beta(t+1,u) (alpha + cost at the final cell) and
+// the label term's at most alpha + cost + beta(t,u+1).  A term whose bound is below kDeadThr has a fast_exp2 that
+// returns +0 whatever the logits hold.  Main term below it: every element of the row is finish(+0 - its case-chain
+// term), and only the blank and the label element have such a term.  If those bounds are below the threshold too
+// (or do not apply) the subtraction gives 0 - 0 = +0 and the row is finish(0) everywhere: a dead row, written without
+// being read.  Otherwise it is a faint row: finish(0) everywhere except the blank and / or label element, for which
+// that one logit is read.  The side bounds exceed lo by about one step's log-probability, so faint rows are a rim
+// around the dead region.
 //
 // Bound on what the kernel itself evaluates (log2 units; u = 2^-24 is the fp32 unit roundoff):
 //   - denom >= max x up to its own rounding: pass 1 takes M = fl(max x * log2e) (fmaxf of rounded products is the
@@ -220,12 +227,22 @@ __global__ __launch_bounds__(kRnntMaxCols) void rnnt_sweep_kernel(
 //     log2e * ((1 - 4u) * bound + 12u * |denom|).
 //   - |denom| < kDeadDenomMax = 2^16 caps the last term at 0.05 nats.  It is also the test that denom is finite: a
 //     +inf or NaN logit makes denom +inf or NaN, and such rows keep the streaming path and their NaN pattern.
-// With bound < -110 nats every argument is below -158.6 (log2): a margin of 8.6 to the -150 at which a correctly
-// rounded exp2 that keeps fp32 denormals first returns +0 (-126 if it flushes them; the margin is then 32.6).
-// tests/test_rnnt_dead_rows_gpu.py checks that __builtin_amdgcn_exp2f gives +0 for every float <= -151.  Every
-// comparison is written so that a NaN operand makes the row live.
-constexpr double kDeadThr = -110.0;
+// The cut-off: __builtin_amdgcn_exp2f (v_exp_f32) flushes denormal results on gfx950.  Measured over every float in
+// [-152, -125] with the library's compile flags (tests/test_rnnt_faint_rows_gpu.py::test_exp2_cutoff): +0 for every
+// float <= x0 = -126.00000763 (0xC2FC0001, the float below -126), 2^-126 at -126.  kDeadThr = (x0 - 8.6) / log2e
+// rounded down to one decimal keeps the margin of 8.6 log2 units this threshold has always had (-110 nats against the
+// -150 of an exp2 that keeps denormals): bound < -93.3 nats gives log2e * bound < -134.60, and with the roundings
+// above every argument is below log2e * (-93.3 * (1 - 4u) + 0.047) = -134.53.  The same test checks +0 for every float
+// <= x0 down to -inf.  Every comparison is written so that a NaN operand makes the row live / the element read.
+constexpr double kDeadThr = -93.3;
 constexpr float kDeadDenomMax = 65536.f;
+
+// Element v of a row whose main term is +0: the blank / label element that was read, or the row's finish(0).
+template <typename T>
+__device__ __forceinline__ T faint_pick(int v, int sblk, T vblk, int slab, T vlab, T val)
+{
+    return v == sblk ? vblk : (v == slab ? vlab : val);
+}
 
 template <typename T, bool NT /* loads */, bool NTS /* stores */, int UN>
 __global__ __launch_bounds__(256) void rnnt_grad_kernel(
@@ -292,18 +309,58 @@ __global__ __launch_bounds__(256) void rnnt_grad_kernel(
             return val * go;
         };
 
-        // A padded cell's gradient is exactly zero; a dead cell's (kDeadThr: every bound that applies is below the
-        // threshold, a NaN anywhere makes the cell live) is finish(0).  Either row is written without being read.
-        const bool dead = skip_dead != 0 && fabsf(d) < kDeadDenomMax && ac + be < kDeadThr &&
-                          (!blank_special || (has_b1 ? ac + b1 : ac) < kDeadThr) && (!has_lab || ac + b2 < kDeadThr);
-        if (__builtin_amdgcn_readfirstlane((!valid || dead) ? 1 : 0)) {
+        // A padded cell's gradient is exactly zero.  A valid cell whose main bound is below kDeadThr (a NaN anywhere
+        // makes the cell live) has a main term of +0 in every element, so the row is finish(0) except where a blank /
+        // label term with a bound of its own at or above the threshold is subtracted: none in a dead row, one or two
+        // in a faint row.  Those logits are the only ones read, before anything is stored (grads may alias logits),
+        // and their elements are computed by the expressions of c2 / blank_sub / lab_sub / fix() below.
+        // A label outside [0, V) matches no element on either path.
+        const bool main_dead = skip_dead != 0 && fabsf(d) < kDeadDenomMax && ac + be < kDeadThr;
+        if (__builtin_amdgcn_readfirstlane((!valid || main_dead) ? 1 : 0)) {
             const T val = valid ? (T)finish(0.f) : (T)0.f;
+            const bool blank_dead = !blank_special || (has_b1 ? ac + b1 : ac) < kDeadThr;
+            const bool label_dead = !has_lab || ac + b2 < kDeadThr || lab >= V;
+            const int sblk = (valid && !blank_dead) ? blank : -1;
+            const int slab = (valid && !label_dead) ? lab : -1;
+            // The main term is evaluated for these elements as the streamed row evaluates it (it is +0): written as a
+            // literal 0 the compiler folds 0 - e into -e under the clamp, and -0 is not what the streamed row gives.
+            const double cmd = ac - (double)d;
+            const float c2 = (float)(cmd + be) * kLog2e;
+            T vblk = val, vlab = val;
+            if (sblk >= 0) {
+                const float x = (float)row[sblk];
+                const float sub = final_cell ? (float)cmd : (float)(cmd + b1);
+                float g = fast_exp2(fmaf(x, kLog2e, c2));
+                g -= fast_exp2((x + sub) * kLog2e);
+                vblk = (T)finish(g);
+            }
+            if (slab >= 0) {
+                const float x = (float)row[slab];
+                const float sub = (float)(cmd + b2);
+                float g = fast_exp2(fmaf(x, kLog2e, c2));
+                g -= fast_exp2((x + sub) * kLog2e);
+                vlab = (T)finish(g);
+            }
             vec_t z;
 #pragma unroll
             for (int q = 0; q < N; ++q) z[q] = val;
-            if (lane < h) grow[lane] = val;
-            if (lane < tail) grow[h + N * nv + lane] = val;
-            for (int i = lane; i < nv; i += kWave) stv<NTS>(z, gbody + i);
+            if (lane < h) grow[lane] = faint_pick(lane, sblk, vblk, slab, vlab, val);
+            if (lane < tail) grow[h + N * nv + lane] = faint_pick(h + N * nv + lane, sblk, vblk, slab, vlab, val);
+            const int iblk = (sblk >= h) ? ((sblk - h) / N) : -1;
+            const int ilab = (slab >= h) ? ((slab - h) / N) : -1;
+            // the one or two body vectors that hold a read element, made up front: the store loop only selects
+            vec_t oblk = z, olab = z;
+#pragma unroll
+            for (int q = 0; q < N; ++q) {
+                oblk[q] = faint_pick(h + N * iblk + q, sblk, vblk, slab, vlab, val);
+                olab[q] = faint_pick(h + N * ilab + q, sblk, vblk, slab, vlab, val);
+            }
+            for (int i = lane; i < nv; i += kWave) {
+                vec_t o = z;
+#pragma unroll
+                for (int q = 0; q < N; ++q) o[q] = i == iblk ? oblk[q] : (i == ilab ? olab[q] : z[q]);
+                stv<NTS>(o, gbody + i);
+            }
             continue;
         }
 
