@@ -637,6 +637,63 @@ int wr_rnnt_simple_grad(const float *am_d, const float *lm_d, const int32_t *sym
                         void *simple_workspace_d, size_t simple_workspace_bytes,
                         const void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream);
 
+/* Pruned RNN-T training: k2's get_rnnt_prune_ranges / do_rnnt_pruning / rnnt_loss_pruned for the regular lattice type
+ * (the second half of the recipe whose first half is the additive-joiner loss above: its arc occupancies choose, per
+ * frame, a band of R label positions on which the real joiner and the real loss are evaluated).  Lengths as
+ * wr_rnnt_simple_stats: logit_lengths[b] = T_b in [0, T], target_lengths[b] = U_b in [0, U1-1].  1 <= R <= U1
+ * everywhere.  ranges [B,T,R] int64 with ranges[b,t,r] = ranges[b,t,0] + r inside [0, U1-1]: the caller checks what it
+ * did not get from wr_rnnt_prune_ranges (the kernels clamp or skip an index outside that interval, they never read or
+ * write out of bounds).  No host synchronisation, no float atomics: every result is bit-identical run to run.
+ *
+ * wr_rnnt_prune_ranges: px_grad [B,U1-1,T+1] and py_grad [B,U1,T] fp32 are the emit / blank arc occupancies in k2's
+ * layout (frames minor; px_grad may be NULL when U1 == 1).  Per utterance, one workgroup:
+ *   1. for u0 in [0, U1-R]: score(u0,t) = ((py[u0,t] + py[u0+1,t]) + ... + py[u0+R-1,t]) - (u0 > 0 ? px[u0-1,t] : 0),
+ *      in fp64 in exactly that order; s_begin[t] = the u0 of the largest score, the lowest u0 on ties;
+ *   2. for t >= T_b - 1: s_begin[t] = max(U_b - R + 1, 0);
+ *   3. over all T frames: s = suffix_min(s); x = t - s; x = suffix_min(x); x = max(x, 0); s = t - x;
+ *   4. ranges[b,t,r] = s_begin[t] + r.
+ * Consequences of 2-3: s_begin[0] = 0, 0 <= s_begin[t+1] - s_begin[t] <= 1, 0 <= s_begin <= min(U1-R, max(U_b-R+1, 0)).
+ *
+ * wr_rnnt_prune_gather: am [B,T,C], lm [B,U1,C] of `dtype` -> am_pruned, lm_pruned [B,T,R,C]:
+ * am_pruned[b,t,r] = am[b,t], lm_pruned[b,t,r] = lm[b, ranges[b,t,r]].
+ * wr_rnnt_prune_scatter: its backward.  d_am[b,t] = sum_r g_am_pruned[b,t,r]; d_lm[b,u] = the sum of g_lm_pruned[b,t,r]
+ * over the (t,r) with ranges[b,t,r] == u, in ascending t (one r at most per t), zero where nothing points; fp32
+ * accumulation, one writer per output element.  Either (gradient, output) pair may be NULL.
+ *
+ * wr_rnnt_pruned_stats: logits [B,T,R,V] (fp32, fp16 or bf16, as wr_rnnt_loss_fwd) are the joiner's outputs on the band.
+ * Fills the skewed log-probability array of an RNN-T workspace (wr_rnnt_workspace_bytes(B,T,U1)) with (-inf, -inf), then
+ * one wave per row (b,t,r), u = ranges[b,t,r] (rows with t >= T_b or u > U_b are skipped, their logits never read),
+ * writes denom(t,u) and (blank - denom, emit - denom) at the skew position of the cell (t,u), emit = 0 at u == U_b: the
+ * conventions of pass 1 of wr_rnnt_loss_fwd.  wr_rnnt_loss_sweeps, wr_rnnt_export_lattice and wr_rnnt_align_from_stats
+ * follow unchanged.  A cell outside the band has -inf on both arcs (no path crosses it); an utterance whose band holds
+ * no complete path gets cost +inf (a value, not an error; its gradient is not finite).
+ * wr_rnnt_pruned_grad: grads [B,T,R,V] in the logits' dtype (may alias logits; otherwise at the same address modulo 16,
+ * WR_EINVAL if not: the rows are split into 16-byte vectors by the logits' address) of sum_b grad_costs[b] * cost_b (NULL = 1;
+ * no clamp, as k2), every element written: the expression of wr_rnnt_loss_bwd with the lattice read at u = ranges[b,t,r],
+ * except that a label equal to the blank has both its terms subtracted (the derivative of the loss as defined, k2's
+ * autograd result) where wr_rnnt_loss_bwd keeps torchaudio's first-match chain; grad_costs[b] * 0 in skipped rows.
+ * HBM traffic of the two calls: 3 * sizeof(element) * V bytes per valid row. */
+int wr_rnnt_prune_ranges(const float *px_grad_d, const float *py_grad_d, const int32_t *logit_lengths_d,
+                         const int32_t *target_lengths_d, int B, int T, int U1, int R,
+                         int64_t *ranges_d /* [B,T,R] out */, void *stream);
+
+int wr_rnnt_prune_gather(const void *am_d, const void *lm_d, const int64_t *ranges_d, int dtype, int B, int T, int U1,
+                         int R, int C, void *am_pruned_d /* [B,T,R,C] out */, void *lm_pruned_d /* [B,T,R,C] out */,
+                         void *stream);
+
+int wr_rnnt_prune_scatter(const void *g_am_pruned_d, const void *g_lm_pruned_d, const int64_t *ranges_d, int dtype,
+                          int B, int T, int U1, int R, int C, void *d_am_d /* [B,T,C] out or NULL */,
+                          void *d_lm_d /* [B,U1,C] out or NULL */, void *stream);
+
+int wr_rnnt_pruned_stats(const void *logits_d, int dtype, const int32_t *symbols_d, const int64_t *ranges_d,
+                         const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1, int R,
+                         int V, int blank, void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream);
+
+int wr_rnnt_pruned_grad(const void *logits_d, int dtype, const int32_t *symbols_d, const int64_t *ranges_d,
+                        const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1, int R,
+                        int V, int blank, const float *grad_costs_d /* [B] or NULL */, void *grads_d,
+                        const void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream);
+
 /* CTC forced alignment: Viterbi over the T x (2S+1) lattice, replacing
  * forced_align, wenet/utils/ctc_util.py:27-83 (CLI wenet/bin/alignment.py:215).  logits [B, Tmax, V]: pre-softmax
  * ctc_lo output, or log-posteriors if normalized != 0 (the reference is handed ctc.log_softmax(...)).

@@ -548,22 +548,134 @@ def bench_simple(args):
     print(json.dumps(rec), flush=True)
 
 
+def bench_pruned(args):
+    """Pruned RNN-T training beside the full-lattice paths, fp32, N(0,1) inputs, full lengths, R = 5 (--R):
+      loss:  rnnt_loss_pruned forward + backward on (B,T,R,V) logits  |  rnnt_loss on the (B,T,U+1,V) logits the band was
+             gathered from;
+      step:  simple loss + prune ranges + TransducerJoint.forward_pruned + pruned loss, forward + backward down to the
+             encoder / predictor outputs  |  joint_rnnt_loss on the same joiner (E = P = 256, J = 512, tanh).
+    HIP events around each step after warm-up, the configurations alternating, median of --steps runs (9 for the figures
+    in DESIGN.md); peak memory of each above what its inputs hold.  One JSON line.  --only pruned: the two pruned
+    configurations alone (for a kernel trace)."""
+    import wenet_celoss_amd as w
+    dev = torch.device("cuda:0")
+    B, T, U, V, R = args.B, args.T, args.U, args.V, min(args.R, args.U + 1)
+    E = P = 256
+    J = 512
+    gen = torch.Generator(device=dev).manual_seed(0)
+    sy = torch.randint(1, V, (B, U), device=dev, generator=gen)
+    sy32 = sy.to(torch.int32)
+    ll = torch.full((B,), T, dtype=torch.int32, device=dev)
+    tl = torch.full((B,), U, dtype=torch.int32, device=dev)
+    only = args.only == "pruned"
+
+    # loss: a diagonal band through the lattice
+    start = (torch.arange(T, device=dev) * max(U + 1 - R, 0)) // max(T - 1, 1)
+    ranges = (start[None, :, None] + torch.arange(R, device=dev)).expand(B, T, R).contiguous()
+    if only:
+        band = torch.randn(B, T, R, V, device=dev, generator=gen)
+        full = None
+    else:
+        full = torch.empty(B, T, U + 1, V, device=dev)
+        for b in range(B):
+            full[b].normal_(generator=gen)
+        band = torch.stack([full[b].gather(1, ranges[b, :, :, None].expand(T, R, V)) for b in range(B)])
+        full.requires_grad_(True)
+    band.requires_grad_(True)
+
+    def loss_pruned():
+        band.grad = None
+        loss = w.rnnt_loss_pruned(band, sy, ranges, 0, reduction="mean")
+        loss.backward()
+        return loss
+
+    def loss_full():
+        full.grad = None
+        loss = w.rnnt_loss(full, sy32, ll, tl, blank=0, reduction="mean")
+        loss.backward()
+        return loss
+
+    # step: the whole training step from the encoder / predictor outputs
+    torch.manual_seed(0)
+    joint = w.TransducerJoint(V, E, P, J).to(dev)
+    am_head, lm_head = torch.nn.Linear(E, V).to(dev), torch.nn.Linear(P, V).to(dev)
+    enc = torch.randn(B, T, E, device=dev, generator=gen).requires_grad_(True)
+    pred = torch.randn(B, U + 1, P, device=dev, generator=gen).requires_grad_(True)
+    params = list(joint.parameters()) + list(am_head.parameters()) + list(lm_head.parameters())
+    boundary = torch.tensor([0, 0, U, T], device=dev).repeat(B, 1)
+
+    def clear():
+        enc.grad = pred.grad = None
+        for p in params:
+            p.grad = None
+
+    def step_pruned():
+        clear()
+        simple, (px, py) = w.rnnt_loss_simple(lm_head(pred), am_head(enc), sy, 0, boundary=boundary, reduction="mean",
+                                              return_grad=True)
+        rg = w.get_rnnt_prune_ranges(px, py, boundary, R)
+        loss = w.rnnt_loss_pruned(joint.forward_pruned(enc, pred, rg), sy, rg, 0, boundary=boundary, reduction="mean")
+        (loss + 0.5 * simple).backward()
+        return loss
+
+    def step_full():
+        clear()
+        ep, pp = joint.pre_activation(enc, pred)
+        loss = w.joint_rnnt_loss(ep, pp, joint.ffn_out.weight, joint.ffn_out.bias, sy32, ll, tl, blank=0, reduction="mean",
+                                 precision=joint.precision, activation=joint.activation)
+        loss.backward()
+        return loss
+
+    fns = {"loss_pruned": loss_pruned, "step_pruned": step_pruned}
+    if not only:
+        fns.update({"loss_full": loss_full, "step_full": step_full})
+    peak, loss = {}, {}
+    for name, fn in fns.items():                       # warm-up, and the memory peak of one step
+        fn()
+        clear()
+        band.grad = None
+        if full is not None:
+            full.grad = None
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        loss[name] = float(fn().detach())
+        torch.cuda.synchronize()
+        peak[name] = torch.cuda.max_memory_allocated() - base
+    times = {name: [] for name in fns}
+    for _ in range(max(args.steps, 1)):
+        for name, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); fn(); b.record()
+            torch.cuda.synchronize()
+            times[name].append(a.elapsed_time(b))
+    rec = {"what": "pruned RNN-T training, fwd+bwd", "shape": [B, T, U + 1, V], "R": R, "runs": max(args.steps, 1),
+           "band_logits_gib": round(B * T * R * V * 4 / 2**30, 2), "full_logits_gib": round(B * T * (U + 1) * V * 4 / 2**30, 2)}
+    for name, ts in times.items():
+        rec[name + "_ms"] = round(sorted(ts)[len(ts) // 2], 3)
+        rec[name + "_ms_min_max"] = [round(min(ts), 3), round(max(ts), 3)]
+        rec[name + "_peak_mib"] = round(peak[name] / 2**20, 1)
+        rec[name + "_loss"] = loss[name]
+    print(json.dumps(rec), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align", "simple"])
+    ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align", "simple", "pruned"])
     ap.add_argument("--n-steps", type=int, default=64)
     ap.add_argument("--chunks", type=int, default=4)
-    ap.add_argument("--B", type=int, default=None, help="batch size (default 32; simple: 16)")
+    ap.add_argument("--B", type=int, default=None, help="batch size (default 32; simple, pruned: 16)")
     ap.add_argument("--T", type=int, default=1000)
     ap.add_argument("--U", type=int, default=150)
     ap.add_argument("--V", type=int, default=5000)
     ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--R", type=int, default=5, help="pruned: label positions per frame (s_range)")
     ap.add_argument("--dw", action="store_true", help="joint: also time the library fp32 GEMM on the three contractions (yardstick)")
     ap.add_argument("--fwd-only", action="store_true", help="joint: stop after the exact forward sweep")
     ap.add_argument("--ragged", action="store_true", help="step: frames in [0.8 T, T] sorted, labels in [U/3, U]")
     ap.add_argument("--buckets", type=int, default=4, help="step: label-length groups of the fused node (1 = off)")
     ap.add_argument("--only", default="", help="step: comma-separated subset of the configurations; simple: \"simple\" "
-                                              "skips the composite")
+                                              "skips the composite; pruned: \"pruned\" skips the full-lattice siblings")
     ap.add_argument("--budget-mb", type=float, default=0.0,
                     help="step: time the memory-bounded fused node (logits_budget = this many MiB) beside the plain one, "
                          "fp32 and bf16x3, with max_memory_allocated of each")
@@ -571,9 +683,9 @@ if __name__ == "__main__":
     ap.add_argument("--tile", type=int, default=0, help="lane-GEMM tile policy of the decoders (wr_tune_set key 6)")
     a = ap.parse_args()
     if a.B is None:
-        a.B = 16 if a.what == "simple" else 32
+        a.B = 16 if a.what in ("simple", "pruned") else 32
     if a.tile:
         from wenet_celoss_amd import _lib
         _lib.load().wr_tune_set(6, a.tile)
     {"joint": bench_joint, "ctc": bench_ctc, "greedy": bench_greedy, "beam": bench_beam, "step": bench_step, "ctcdec": bench_ctcdec, "hotword": bench_hotword,
-     "align": bench_align, "simple": bench_simple}[a.what](a)
+     "align": bench_align, "simple": bench_simple, "pruned": bench_pruned}[a.what](a)

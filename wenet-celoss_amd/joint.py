@@ -409,3 +409,16 @@ class TransducerJoint(nn.Module):
         enc_out, pred_out = self.pre_activation(enc_out, pred_out)
         return joint_logits(enc_out, pred_out, self.ffn_out.weight, self.ffn_out.bias, logit_lengths, target_lengths,
                             self.precision, self.activation)
+
+    @torch.jit.unused      # reaches the ctypes library through do_rnnt_pruning
+    def forward_pruned(self, enc_out: torch.Tensor, pred_out: torch.Tensor, ranges: torch.Tensor) -> torch.Tensor:
+        """The joiner on a band of label positions: enc_out (B, T, E), pred_out (B, U+1, P), ranges (B, T, R) as
+        `get_rnnt_prune_ranges` returns them -> logits (B, T, R, V) for `rnnt_loss_pruned`, ``logits[b,t,r]`` the
+        joiner's output at the cell ``(t, ranges[b,t,r])``.  `pre_activation`, the gather of both addends onto the band
+        (`do_rnnt_pruning`), the module's activation on their sum and `ffn_out` (a plain (B*T*R, J) x (J, V) product)."""
+        from .rnnt_pruned import do_rnnt_pruning
+        ep, pp = self.pre_activation(enc_out, pred_out)
+        if ep.dtype != pp.dtype:
+            pp = pp.to(ep.dtype)
+        am_p, lm_p = do_rnnt_pruning(ep, pp, ranges)
+        return self.ffn_out(self.activatoin(am_p + lm_p))

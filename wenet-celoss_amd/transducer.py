@@ -36,6 +36,7 @@ from .joint import TransducerJoint, _call_precision
 from .rnnt_align import joint_rnnt_forced_align, rnnt_forced_align
 from .rnnt_loss import rnnt_loss
 from .rnnt_simple import rnnt_loss_simple, rnnt_simple_forced_align
+from .rnnt_pruned import get_rnnt_prune_ranges, rnnt_loss_pruned
 from .search.greedy_search import basic_greedy_search, basic_greedy_search_both, basic_greedy_search_hw
 from .search.prefix_beam_search import PrefixBeamSearch
 
@@ -78,7 +79,7 @@ class Transducer(nn.Module):
                  context_bias: Optional[nn.Module] = None, ctc_weight: float = 0, ignore_id: int = IGNORE_ID,
                  reverse_weight: float = 0.0, lsm_weight: float = 0.0, length_normalized_loss: bool = False,
                  transducer_weight: float = 1.0, attention_weight: float = 0.0, hw_weight: float = 0.4,
-                 loss_mode: str = "both", simple_loss_weight: float = 0.0) -> None:
+                 loss_mode: str = "both", prune_range: int = 0, simple_loss_weight: float = 0.0) -> None:
         assert attention_weight + ctc_weight + transducer_weight == 1.0          # transducer.py:46 (kept as is)
         super().__init__()
         # ASRModel part (asr_model.py:38-70): sos/eos are the last class
@@ -125,6 +126,16 @@ class Transducer(nn.Module):
         if self.simple_loss_weight > 0.0:
             self.simple_am_proj = nn.Linear(_output_width(encoder, "encoder", joint, "enc_ffn"), vocab_size)
             self.simple_lm_proj = nn.Linear(_output_width(predictor, "predictor", joint, "pred_ffn"), vocab_size)
+        # pruned training (k2 / icefall recipe, rnnt_pruned.py): the simple loss's arc occupancies choose a band of
+        # `prune_range` label positions per frame, and loss_rnnt is the RNN-T loss of the joiner evaluated on that band
+        # only.  0: the full-lattice loss block above.
+        self.prune_range = int(prune_range)
+        if self.prune_range < 0 or self.prune_range == 1:
+            raise ValueError(f"Transducer: prune_range must be 0 (off) or at least 2 (got {prune_range})")
+        if self.prune_range > 0 and not self.simple_loss_weight > 0.0:
+            raise ValueError("Transducer: prune_range > 0 takes its ranges from the simple loss: simple_loss_weight must be > 0")
+        if self.prune_range > 0 and not hasattr(joint, "forward_pruned"):
+            raise ValueError("Transducer: prune_range > 0 needs a joiner with forward_pruned (TransducerJoint)")
 
     # ------------------------------------------------------------- training --
     def _logits_budget(self) -> Optional[int]:
@@ -199,6 +210,19 @@ class Transducer(nn.Module):
         lm, am, symbols, boundary = self._simple_inputs(encoder_out, encoder_out_lens, predictor_out, text, text_lengths)
         return rnnt_loss_simple(lm, am, symbols, self.blank, boundary=boundary, reduction="mean")
 
+    def compute_pruned_loss(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, predictor_out: torch.Tensor,
+                            text: torch.Tensor, text_lengths: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The pruned loss block: (loss_rnnt, loss_simple), both reduction "mean".  The simple loss returns its arc
+        occupancies, `get_rnnt_prune_ranges` turns them into a band of `prune_range` label positions per frame, and
+        loss_rnnt is `rnnt_loss_pruned` on the joiner's outputs on that band."""
+        lm, am, symbols, boundary = self._simple_inputs(encoder_out, encoder_out_lens, predictor_out, text, text_lengths)
+        loss_simple, (px_grad, py_grad) = rnnt_loss_simple(lm, am, symbols, self.blank, boundary=boundary,
+                                                           reduction="mean", return_grad=True)
+        ranges = get_rnnt_prune_ranges(px_grad, py_grad, boundary, self.prune_range)
+        logits = self.joint.forward_pruned(encoder_out, predictor_out, ranges)
+        loss_rnnt = rnnt_loss_pruned(logits, symbols, ranges, self.blank, boundary=boundary, reduction="mean")
+        return loss_rnnt, loss_simple
+
     def _can_fuse_loss(self) -> bool:
         jt = self.joint
         # the AMP single-term modes keep 16-bit logits ("autocast" is one of them under autocast only)
@@ -241,12 +265,16 @@ class Transducer(nn.Module):
          predictor_out_bias) = self._loss_inputs(speech, speech_lengths, text, context_list, context_lengths)
         predictor_out_unbiased = predictor_out.clone()
 
-        _, loss_rnnt = self.compute_loss(encoder_out, encoder_out_lens, predictor_out, text, text_lengths)
-        loss = self.transducer_weight * loss_rnnt
         loss_simple: Optional[torch.Tensor] = None
-        if getattr(self, "simple_loss_weight", 0.0) > 0.0:
-            loss_simple = self.compute_simple_loss(encoder_out, encoder_out_lens, predictor_out, text, text_lengths)
-            loss = loss + self.simple_loss_weight * loss_simple
+        if getattr(self, "prune_range", 0) > 0:
+            loss_rnnt, loss_simple = self.compute_pruned_loss(encoder_out, encoder_out_lens, predictor_out, text, text_lengths)
+            loss = self.transducer_weight * loss_rnnt + self.simple_loss_weight * loss_simple
+        else:
+            _, loss_rnnt = self.compute_loss(encoder_out, encoder_out_lens, predictor_out, text, text_lengths)
+            loss = self.transducer_weight * loss_rnnt
+            if getattr(self, "simple_loss_weight", 0.0) > 0.0:
+                loss_simple = self.compute_simple_loss(encoder_out, encoder_out_lens, predictor_out, text, text_lengths)
+                loss = loss + self.simple_loss_weight * loss_simple
 
         loss_att: Optional[torch.Tensor] = None
         if self.attention_decoder_weight != 0.0 and self.decoder is not None:
