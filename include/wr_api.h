@@ -637,6 +637,57 @@ int wr_rnnt_simple_grad(const float *am_d, const float *lm_d, const int32_t *sym
                         void *simple_workspace_d, size_t simple_workspace_bytes,
                         const void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream);
 
+/* The smoothed additive-joiner loss: k2's rnnt_loss_smoothed, regular lattice.  Shapes, lengths and both workspaces'
+ * roles as wr_rnnt_simple_*; the scratch is larger (wr_rnnt_smoothed_workspace_bytes: it begins with the simple loss's
+ * layout and adds rows of B*T, B*U1 and V floats and a partial-sum area of max(ceil(B*U1/64), B*ceil(T/64)) * V floats).
+ * With ll = lm_only_scale, la = am_only_scale (both >= 0, ll + la <= 1), c = 1 - ll - la:
+ *
+ *   Zl[b,u]   = log sum_v exp(lm[b,u,v])                                  lm-only normaliser
+ *   pbar[v]   = (1 / (B*U1)) sum_{b,u} softmax(lm[b,u,:])[v] + tiny       "unigram"; tiny = smallest normal fp32
+ *   N[b,t]    = log sum_v exp(am[b,t,v]) * pbar[v]                        am-only normaliser
+ *   denom     = log sum_v exp(am[b,t,v] + lm[b,u,v])                      as wr_rnnt_simple_stats
+ *   emit(t,u)  = c*(am[t,y_u] + lm[u,y_u] - denom(t,u)) + ll*(lm[u,y_u] - Zl[u]) + la*(am[t,y_u] + log pbar[y_u] - N[t])
+ *   blank(t,u) = c*(am[t,blank] + lm[u,blank] - denom(t,u)) + ll*(lm[u,blank] - Zl[u]) + la*(am[t,blank] + log pbar[blank] - N[t])
+ *
+ * pbar is the mean over ALL B*U1 rows of lm, rows past U_b included (k2's definition): padded rows of lm must be finite
+ * when la > 0.  A scale that is exactly 0 drops its branch: no term, no kernel (with la == 0 nothing beyond the simple
+ * loss's kernels reads am).  ll == la == 0 runs wr_rnnt_simple_stats / wr_rnnt_simple_grad's kernels and nothing else:
+ * the same bits.
+ *
+ * wr_rnnt_smoothed_stats: wr_rnnt_simple_stats' kernels (the direct repair pass included), then the arcs above written
+ * over the skewed log-probabilities of the RNN-T workspace.  wr_rnnt_loss_sweeps / wr_rnnt_export_lattice follow.
+ *
+ * wr_rnnt_smoothed_grad: the gradient of sum_b g_b * cost_b (g = grad_costs, NULL = 1).  With oe / ob the arc occupancies
+ * of the interpolated lattice, occ = oe + ob, sigma = softmax:
+ *   d am[b,t,v] = g_b*[ c*sum_u occ(t,u)*sigma(am[t]+lm[u])[v] + la*C(t)*q_t[v] - (c+la)*(sum_u oe(t,u)[v=y_u] + sum_u ob(t,u)[v=blank]) ]
+ *                 C(t) = sum_u occ(t,u),  q_t[v] = exp(am[t,v] - N[t]) * pbar[v]
+ *   d lm[b,u,v] = g_b*[ c*sum_t occ(t,u)*sigma(am[t]+lm[u])[v] + ll*R(u)*sigma(lm[u])[v] - (c+ll)*(sum_t oe(t,u)[v=y_u] + sum_t ob(t,u)[v=blank]) ]
+ *                 + (1/(B*U1)) * s[v] * (h[v] - sum_w s[w]*h[w]),  s = sigma(lm[b,u]),  R(u) = sum_t occ(t,u)
+ *   h[v]        = la * sum_b g_b*[ sum_t C_b(t)*exp(am[b,t,v] - N[b,t]) - (sum_{t,u} oe_b(t,u)[v=y_u] + sum_{t,u} ob_b(t,u)[v=blank]) / pbar[v] ]
+ * The h term reaches every row of lm, padded ones included, and couples the utterances of a batch (la > 0 only); with
+ * la == 0 padded rows of d_lm are exactly zero; d_am rows t >= T_b are always exactly zero.  Every arc is subtracted at
+ * its own symbol (a label equal to the blank has both of its cell's arcs subtracted at the blank), which is the
+ * derivative of the arcs as written; wr_rnnt_simple_grad keeps the case chain of wr_rnnt_loss_bwd there.  No float
+ * atomics, fixed summation order: bit-identical run to run.  d_am_d == d_lm_d == NULL: only the occupancies are written
+ * (both occupancy outputs are then required).  Needs wr_rnnt_smoothed_stats + wr_rnnt_loss_sweeps on the same workspaces
+ * and the same two scales. */
+size_t wr_rnnt_smoothed_workspace_bytes(int B, int T, int U1, int V);
+
+int wr_rnnt_smoothed_stats(const float *am_d, const float *lm_d, const int32_t *symbols_d,
+                           const int32_t *logit_lengths_d, const int32_t *target_lengths_d,
+                           int B, int T, int U1, int V, int blank, float lm_only_scale, float am_only_scale,
+                           void *smoothed_workspace_d, size_t smoothed_workspace_bytes,
+                           void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream);
+
+int wr_rnnt_smoothed_grad(const float *am_d, const float *lm_d, const int32_t *symbols_d,
+                          const int32_t *logit_lengths_d, const int32_t *target_lengths_d,
+                          int B, int T, int U1, int V, int blank, float lm_only_scale, float am_only_scale,
+                          const float *grad_costs_d /* [B] or NULL */,
+                          float *d_am_d /* [B,T,V] out */, float *d_lm_d /* [B,U1,V] out */,
+                          float *occ_emit_d /* [B,T,U1] out or NULL */, float *occ_blank_d /* [B,T,U1] out or NULL */,
+                          void *smoothed_workspace_d, size_t smoothed_workspace_bytes,
+                          const void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream);
+
 /* Pruned RNN-T training: k2's get_rnnt_prune_ranges / do_rnnt_pruning / rnnt_loss_pruned for the regular lattice type
  * (the second half of the recipe whose first half is the additive-joiner loss above: its arc occupancies choose, per
  * frame, a band of R label positions on which the real joiner and the real loss are evaluated).  Lengths as

@@ -548,6 +548,52 @@ def bench_simple(args):
     print(json.dumps(rec), flush=True)
 
 
+def bench_smoothed(args):
+    """rnnt_loss_smoothed forward + backward beside rnnt_loss_simple, at the shape and by the timing method of `simple`:
+    N(0,1) inputs, full lengths, HIP events around each step after warm-up, the three alternating, median of --steps
+    runs (9 for the figures in DESIGN.md).  Configurations: simple, smoothed (0.25, 0) -- the icefall setting --, and
+    smoothed (0.1, 0.1) -- k2's defaults.  One JSON line.  --only NAME[,NAME]: a subset (for a kernel trace)."""
+    import wenet_celoss_amd as w
+    dev = torch.device("cuda:0")
+    B, T, U, V = args.B, args.T, args.U, args.V
+    gen = torch.Generator(device=dev).manual_seed(0)
+    am = torch.randn(B, T, V, device=dev, generator=gen).requires_grad_(True)
+    lm = torch.randn(B, U + 1, V, device=dev, generator=gen).requires_grad_(True)
+    sy = torch.randint(1, V, (B, U), device=dev, generator=gen)
+
+    def step(fn):
+        def run():
+            am.grad = lm.grad = None
+            loss = fn()
+            loss.backward()
+            return loss
+        return run
+
+    fns = {"simple": step(lambda: w.rnnt_loss_simple(lm, am, sy, 0, reduction="mean")),
+           "smoothed_0.25_0": step(lambda: w.rnnt_loss_smoothed(lm, am, sy, 0, 0.25, 0.0, reduction="mean")),
+           "smoothed_0.1_0.1": step(lambda: w.rnnt_loss_smoothed(lm, am, sy, 0, 0.1, 0.1, reduction="mean"))}
+    if args.only:
+        fns = {k: v for k, v in fns.items() if k in args.only.split(",")}
+    loss = {}
+    for name, fn in fns.items():                       # warm-up
+        fn()
+        loss[name] = float(fn())
+    torch.cuda.synchronize()
+    times = {name: [] for name in fns}
+    for _ in range(max(args.steps, 1)):
+        for name, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); fn(); b.record()
+            torch.cuda.synchronize()
+            times[name].append(a.elapsed_time(b))
+    rec = {"what": "rnnt_loss_smoothed fwd+bwd", "shape": [B, T, U + 1, V], "runs": max(args.steps, 1)}
+    for name, ts in times.items():
+        rec[name + "_ms"] = round(sorted(ts)[len(ts) // 2], 3)
+        rec[name + "_ms_min_max"] = [round(min(ts), 3), round(max(ts), 3)]
+        rec[name + "_loss"] = loss[name]
+    print(json.dumps(rec), flush=True)
+
+
 def bench_pruned(args):
     """Pruned RNN-T training beside the full-lattice paths, fp32, N(0,1) inputs, full lengths, R = 5 (--R):
       loss:  rnnt_loss_pruned forward + backward on (B,T,R,V) logits  |  rnnt_loss on the (B,T,U+1,V) logits the band was
@@ -661,10 +707,10 @@ def bench_pruned(args):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align", "simple", "pruned"])
+    ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align", "simple", "smoothed", "pruned"])
     ap.add_argument("--n-steps", type=int, default=64)
     ap.add_argument("--chunks", type=int, default=4)
-    ap.add_argument("--B", type=int, default=None, help="batch size (default 32; simple, pruned: 16)")
+    ap.add_argument("--B", type=int, default=None, help="batch size (default 32; simple, smoothed, pruned: 16)")
     ap.add_argument("--T", type=int, default=1000)
     ap.add_argument("--U", type=int, default=150)
     ap.add_argument("--V", type=int, default=5000)
@@ -683,9 +729,9 @@ if __name__ == "__main__":
     ap.add_argument("--tile", type=int, default=0, help="lane-GEMM tile policy of the decoders (wr_tune_set key 6)")
     a = ap.parse_args()
     if a.B is None:
-        a.B = 16 if a.what in ("simple", "pruned") else 32
+        a.B = 16 if a.what in ("simple", "smoothed", "pruned") else 32
     if a.tile:
         from wenet_celoss_amd import _lib
         _lib.load().wr_tune_set(6, a.tile)
     {"joint": bench_joint, "ctc": bench_ctc, "greedy": bench_greedy, "beam": bench_beam, "step": bench_step, "ctcdec": bench_ctcdec, "hotword": bench_hotword,
-     "align": bench_align, "simple": bench_simple, "pruned": bench_pruned}[a.what](a)
+     "align": bench_align, "simple": bench_simple, "smoothed": bench_smoothed, "pruned": bench_pruned}[a.what](a)

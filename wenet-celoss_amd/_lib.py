@@ -111,6 +111,10 @@ SIGNATURES = {
     "wr_rnnt_simple_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp]),
     "wr_rnnt_simple_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz,
                                  _vp]),
+    "wr_rnnt_smoothed_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "wr_rnnt_smoothed_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _sz, _vp, _sz, _vp]),
+    "wr_rnnt_smoothed_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                   _vp, _sz, _vp]),
     "wr_rnnt_prune_ranges": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "wr_rnnt_prune_gather": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "wr_rnnt_prune_scatter": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -232,12 +232,12 @@ __global__ __launch_bounds__(256) void simple_stats_direct_kernel(
 // ------------------------------------------------------------------------------------------- occupancies --
 // One thread per cell.  Exponents are formed in fp64 (the lattice state's precision) and only then rounded, as
 // rnnt_grad_kernel forms its own.  g = G * grad_costs[b]; with the flag raised g holds grad_costs[b] * occ instead (the
-// direct gradient kernel's factor; e^{ma+ml-denom} may overflow there).
+// direct gradient kernel's factor; e^{ma+ml-denom} may overflow there).  g is further scaled by `gscale`.
 __global__ __launch_bounds__(256) void simple_occ_kernel(
     const int32_t *__restrict__ llens, const int32_t *__restrict__ tlens, int B, int T, int U1, int S,
     const double *__restrict__ alpha_skew, const double *__restrict__ beta_skew, const float2 *__restrict__ lp_skew,
     const float *__restrict__ denom, const double *__restrict__ cost_ws, const float *__restrict__ ma,
-    const float *__restrict__ ml, const float *__restrict__ grad_costs, const int32_t *__restrict__ flag,
+    const float *__restrict__ ml, const float *__restrict__ grad_costs, const int32_t *__restrict__ flag, float gscale,
     float *__restrict__ g, float *__restrict__ gt, float *__restrict__ ob, float *__restrict__ oe,
     float *__restrict__ occ_emit_out, float *__restrict__ occ_blank_out)
 {
@@ -265,8 +265,9 @@ __global__ __launch_bounds__(256) void simple_occ_kernel(
         else if (u == Ub) fb = (float)exp(ac + (double)lp.x);   // the final cell: beta := 0
         if (u < Ub) fe = (float)exp(ac + (double)lp.y + beta_skew[dbase + (size_t)(s + 1) * U1 + (u + 1)]);
     }
-    g[r] = gv * go;
-    gt[((size_t)b * U1 + u) * T + t] = gv * go;
+    const float gs = gv * go * gscale;                          // gscale: 1 (exact), or c of the smoothed loss
+    g[r] = gs;
+    gt[((size_t)b * U1 + u) * T + t] = gs;
     ob[r] = fb * go;
     oe[r] = fe * go;
     if (occ_emit_out) occ_emit_out[r] = fe;
@@ -400,10 +401,13 @@ __global__ __launch_bounds__(256) void simple_grad_direct_kernel(
 // d am[t, blank] -= sum_u occ_blank(t,u) ; d am[t, lab_u] -= occ_emit(t,u).  One wave per (b, t).  Positions that share a
 // label are summed along their chain by the first of them (one writer per address); a label equal to the blank joins the
 // blank's sum (last frame only, see above).  wave_sum is a fixed butterfly: the same bits every run.
+// `wgt` weighs what is subtracted (1 here; c + am_only_scale / c + lm_only_scale under smoothing), and `every_arc` drops
+// the case chain: the smoothed loss subtracts every arc at its own symbol, the derivative of its arcs as written.
 __global__ __launch_bounds__(256) void simple_fix_am_kernel(
     const float *__restrict__ ob, const float *__restrict__ oe, const int32_t *__restrict__ nxt,
     const int32_t *__restrict__ head, const int32_t *__restrict__ symbols, const int32_t *__restrict__ llens,
-    const int32_t *__restrict__ tlens, int B, int T, int U1, int V, int blank, float *__restrict__ d_am)
+    const int32_t *__restrict__ tlens, int B, int T, int U1, int V, int blank, float wgt, bool every_arc,
+    float *__restrict__ d_am)
 {
     const int lane = threadIdx.x & (kWave - 1);
     const long r = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -419,16 +423,16 @@ __global__ __launch_bounds__(256) void simple_fix_am_kernel(
     float part = 0.f;
     for (int u = lane; u <= Ub; u += kWave) {
         part += obr[u];
-        if (u < Ub && sy[u] == blank && t == Tb - 1) part += oer[u];
+        if (u < Ub && sy[u] == blank && (every_arc || t == Tb - 1)) part += oer[u];
     }
     const float tot = wave_sum(part);
-    if (lane == 0) row[blank] -= tot;
+    if (lane == 0) row[blank] -= wgt * tot;
     for (int u = lane; u < Ub; u += kWave) {
         const int lab = sy[u];
         if (lab == blank || head[(size_t)b * U1 + u] == 0) continue;
         float s = oer[u];
         for (int j = nx[u]; j >= 0; j = nx[j]) s += oer[j];
-        row[lab] -= s;
+        row[lab] -= wgt * s;
     }
 }
 
@@ -436,8 +440,8 @@ __global__ __launch_bounds__(256) void simple_fix_am_kernel(
 // thread (u, phase) sums t = phase, phase + 4, ... ; the four phases are added in order.
 __global__ __launch_bounds__(256) void simple_fix_lm_kernel(
     const float *__restrict__ ob, const float *__restrict__ oe, const int32_t *__restrict__ symbols,
-    const int32_t *__restrict__ llens, const int32_t *__restrict__ tlens, int T, int U1, int V, int blank,
-    float *__restrict__ d_lm)
+    const int32_t *__restrict__ llens, const int32_t *__restrict__ tlens, int T, int U1, int V, int blank, float wgt,
+    bool every_arc, float *__restrict__ d_lm)
 {
     __shared__ float sb[4][64], se[4][64];
     const int b = blockIdx.y;
@@ -459,10 +463,316 @@ __global__ __launch_bounds__(256) void simple_fix_lm_kernel(
     const float te = ((se[0][ul] + se[1][ul]) + se[2][ul]) + se[3][ul];
     float *__restrict__ row = d_lm + ((size_t)b * U1 + u) * V;
     const int lab = u < Ub ? symbols[(size_t)b * (U1 - 1) + u] : -1;
-    if (lab == blank) row[blank] -= tb + oe[((size_t)b * T + (Tb - 1)) * U1 + u];
+    if (lab == blank) row[blank] -= wgt * (tb + (every_arc ? te : oe[((size_t)b * T + (Tb - 1)) * U1 + u]));
     else {
-        row[blank] -= tb;
-        if (lab >= 0) row[lab] -= te;
+        row[blank] -= wgt * tb;
+        if (lab >= 0) row[lab] -= wgt * te;
+    }
+}
+
+// ================================================================================= the smoothed loss ==
+// k2's rnnt_loss_smoothed (include/wr_api.h has the contract): every arc of the lattice above is interpolated with an
+// lm-only and an am-only estimate,
+//     arc = c * (am + lm - denom) + ll * (lm - Zl[u]) + la * (am + log pbar - N[t]),     c = 1 - ll - la
+// Zl the row log-sum-exp of lm, pbar the mean row softmax of lm over all B * U1 rows (+ the smallest normal float),
+// N[t] = log sum_v e^{am[t,v]} pbar[v].  denom, the sweeps and the contractions stay as they are; what is new is
+//   forward   smooth_lm_rows_kernel     one wave per row of lm: Zl, and the two lm-only arc terms of the row
+//             smooth_colsum_kernel      (la > 0) column sums of the row softmaxes, 64 rows per workgroup, rows ascending
+//             smooth_pbar_kernel        (la > 0) the partial sums added in order: pbar, log pbar
+//             smooth_am_norm_kernel     (la > 0) one wave per row of am: N, and the am-only blank term of the row
+//             smooth_interp_kernel      one thread per skewed position: rewrites the skewed log-probabilities (after the direct
+//                                       repair kernel, so it sees final denom values)
+//   backward  smooth_occ_rows_kernel / smooth_occ_cols_kernel    C(t) = sum_u occ, sum_t occ_blank, sum_t occ_emit
+//             smooth_h_part_kernel / smooth_h_kernel   (la > 0) h[v] pbar[v] over all B * T rows, 64 rows per partial sum
+//             smooth_am_row_kernel      (la > 0) d am[t] += la C(t) q_t
+//             smooth_lm_row_kernel      d lm[u] += sigma(lm[u]) (ll R(u) + (h - <sigma, h>) / (B U1)), the second part for
+//                                       la > 0 only and then for every row of lm, padded ones included
+// A scale that is exactly 0 drops its branch (no launch, no term).  Every sum has one writer and a fixed order.
+constexpr int kSmoothRows = 64;     // rows per partial column sum
+constexpr float kTinyF = 1.17549435e-38f;
+constexpr int kOccPhases = 16;    // phases of t in smooth_occ_cols_kernel (its workgroup has 64 * kOccPhases threads)
+
+struct SmoothWs {
+    SimpleWs s;
+    size_t zl_off, lb_off, le_off, n_off, ab_off, cg_off, rb_off, re_off, pbar_off, lpbar_off, h_off, part_off, total;
+    int lm_chunks, t_chunks;
+};
+
+inline SmoothWs smooth_ws_layout(int B, int T, int U1, int V)
+{
+    SmoothWs w;
+    w.s = simple_ws_layout(B, T, U1);
+    w.lm_chunks = (int)(((long)B * U1 + kSmoothRows - 1) / kSmoothRows);
+    w.t_chunks = (T + kSmoothRows - 1) / kSmoothRows;
+    const size_t bu = (size_t)B * U1 * sizeof(float), bt = (size_t)B * T * sizeof(float), vb = (size_t)V * sizeof(float);
+    const size_t parts = (size_t)w.lm_chunks > (size_t)B * w.t_chunks ? (size_t)w.lm_chunks : (size_t)B * w.t_chunks;
+    size_t off = w.s.total;
+    w.zl_off = off;    off = align_up(off + bu, 256);      // Zl [B,U1]
+    w.lb_off = off;    off = align_up(off + bu, 256);      // lm[u,blank] - Zl[u]
+    w.le_off = off;    off = align_up(off + bu, 256);      // lm[u,y_u] - Zl[u]
+    w.n_off = off;     off = align_up(off + bt, 256);      // N [B,T]
+    w.ab_off = off;    off = align_up(off + bt, 256);      // am[t,blank] + log pbar[blank] - N[t]
+    w.cg_off = off;    off = align_up(off + bt, 256);      // grad_costs * C(t)
+    w.rb_off = off;    off = align_up(off + bu, 256);      // grad_costs * sum_t occ_blank(t,u)
+    w.re_off = off;    off = align_up(off + bu, 256);      // grad_costs * sum_t occ_emit(t,u)
+    w.pbar_off = off;  off = align_up(off + vb, 256);
+    w.lpbar_off = off; off = align_up(off + vb, 256);
+    w.h_off = off;     off = align_up(off + vb, 256);
+    w.part_off = off;  off = align_up(off + parts * vb, 256);
+    w.total = off;
+    return w;
+}
+
+// One wave per row of lm (every row, padded ones too: pbar is defined over all of them).
+__global__ __launch_bounds__(256) void smooth_lm_rows_kernel(
+    const float *__restrict__ lm, const float *__restrict__ ml, const int32_t *__restrict__ symbols,
+    const int32_t *__restrict__ tlens, long rows, int U1, int V, int blank, float *__restrict__ zl,
+    float *__restrict__ lb, float *__restrict__ le)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const long r = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const float *__restrict__ row = lm + (size_t)r * V;
+    const float m = ml[r];
+    float sum = 0.f;
+#pragma unroll 8
+    for (int v = lane; v < V; v += kWave) sum += fast_exp2((row[v] - m) * kLog2e);
+    sum = wave_sum(sum);
+    if (lane != 0) return;
+    const double z = (double)m + (double)logf(sum);
+    zl[r] = (float)z;
+    const int b = (int)(r / U1), u = (int)(r - (long)b * U1);
+    const int Ub = clampi(tlens[b], 0, U1 - 1);
+    float fb = 0.f, fe = 0.f;
+    if (u <= Ub) fb = (float)((double)row[blank] - z);
+    if (u < Ub) fe = (float)((double)row[symbols[(size_t)b * (U1 - 1) + u]] - z);
+    lb[r] = fb;
+    le[r] = fe;
+}
+
+// part[chunk, v] = sum over the chunk's rows (ascending) of e^{x[r,v] - sub[r]} (pbar: x = lm, sub = Zl).
+// grid (chunks, ceil(V/256)).
+__global__ __launch_bounds__(256) void smooth_colsum_kernel(const float *__restrict__ x, const float *__restrict__ sub,
+                                                            long rows, int V, float *__restrict__ part)
+{
+    const int v = blockIdx.y * blockDim.x + threadIdx.x;
+    if (v >= V) return;
+    const long r0 = (long)blockIdx.x * kSmoothRows;
+    const long r1 = r0 + kSmoothRows < rows ? r0 + kSmoothRows : rows;
+    float acc = 0.f;
+#pragma unroll 8
+    for (long r = r0; r < r1; ++r) acc += fast_exp2((x[(size_t)r * V + v] - sub[r]) * kLog2e);
+    part[(size_t)blockIdx.x * V + v] = acc;
+}
+
+__global__ __launch_bounds__(256) void smooth_pbar_kernel(const float *__restrict__ part, int chunks, long rows, int V,
+                                                          float *__restrict__ pbar, float *__restrict__ lpbar)
+{
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= V) return;
+    float acc = 0.f;
+#pragma unroll 16
+    for (int c = 0; c < chunks; ++c) acc += part[(size_t)c * V + v];
+    const float p = acc / (float)rows + kTinyF;
+    pbar[v] = p;
+    lpbar[v] = logf(p);
+}
+
+// One wave per valid row of am: N[t] = ma[t] + log sum_v e^{am[t,v] - ma[t]} pbar[v]; the sum holds the term of am's
+// maximum, pbar >= the smallest normal float, so it is never zero.
+__global__ __launch_bounds__(256) void smooth_am_norm_kernel(
+    const float *__restrict__ am, const float *__restrict__ ma, const float *__restrict__ pbar,
+    const float *__restrict__ lpbar, const int32_t *__restrict__ llens, int B, int T, int V, int blank,
+    float *__restrict__ nrm, float *__restrict__ ab)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const long r = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (r >= (long)B * T) return;
+    const int b = (int)(r / T), t = (int)(r - (long)b * T);
+    if (t >= clampi(llens[b], 0, T)) {
+        if (lane == 0) { nrm[r] = 0.f; ab[r] = 0.f; }
+        return;
+    }
+    const float *__restrict__ row = am + (size_t)r * V;
+    const float m = ma[r];
+    float sum = 0.f;
+#pragma unroll 4
+    for (int v = lane; v < V; v += kWave) sum += fast_exp2((row[v] - m) * kLog2e) * pbar[v];
+    sum = wave_sum(sum);
+    if (lane != 0) return;
+    const double n = (double)m + (double)logf(sum);
+    nrm[r] = (float)n;
+    ab[r] = (float)(((double)row[blank] + (double)lpbar[blank]) - n);
+}
+
+// One thread per position (b, s = t + u, u) of the skewed layout, so that a wave reads and writes whole lines of it
+// (a thread per (b,t,u) touches one 32-byte sector per cell).  AM: the am-only branch is present (the only form that
+// reads am).
+template <bool AM>
+__global__ __launch_bounds__(256) void smooth_interp_kernel(
+    const float *__restrict__ am, const int32_t *__restrict__ symbols, const int32_t *__restrict__ llens,
+    const int32_t *__restrict__ tlens, int B, int T, int U1, int V, int S, float c, float ll, float la,
+    const float *__restrict__ lb, const float *__restrict__ le, const float *__restrict__ nrm,
+    const float *__restrict__ ab, const float *__restrict__ lpbar, float2 *__restrict__ lp_skew)
+{
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= (long)B * S * U1) return;
+    const long diag = (long)S * U1;
+    const int b = (int)(r / diag);
+    const long cc = r - b * diag;
+    const int sd = (int)(cc / U1), u = (int)(cc - (long)sd * U1), t = sd - u;
+    const int Tb = clampi(llens[b], 0, T), Ub = clampi(tlens[b], 0, U1 - 1);
+    if (t < 0 || t >= Tb || u > Ub) return;
+    const size_t idx = (size_t)r;
+    const float2 lp = lp_skew[idx];
+    double x = (double)c * (double)lp.x, y = 0.0;
+    if (ll != 0.f) x += (double)ll * (double)lb[(size_t)b * U1 + u];
+    if (AM) x += (double)la * (double)ab[(size_t)b * T + t];
+    if (u < Ub) {
+        y = (double)c * (double)lp.y;
+        if (ll != 0.f) y += (double)ll * (double)le[(size_t)b * U1 + u];
+        if (AM) {
+            const int lab = symbols[(size_t)b * (U1 - 1) + u];
+            y += (double)la * (((double)am[((size_t)b * T + t) * V + lab] + (double)lpbar[lab]) - (double)nrm[(size_t)b * T + t]);
+        }
+    }
+    lp_skew[idx] = make_float2((float)x, (float)y);
+}
+
+// cg[b,t] = sum_u (ob + oe)(t,u): one wave per (b,t); ob / oe are zero outside the valid region.
+__global__ __launch_bounds__(256) void smooth_occ_rows_kernel(const float *__restrict__ ob, const float *__restrict__ oe,
+                                                              long rows, int U1, float *__restrict__ cg)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const long r = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    float part = 0.f;
+    for (int u = lane; u < U1; u += kWave) part += ob[(size_t)r * U1 + u] + oe[(size_t)r * U1 + u];
+    part = wave_sum(part);
+    if (lane == 0) cg[r] = part;
+}
+
+// rb[b,u] = sum_t ob(t,u), re[b,u] = sum_t oe(t,u): sixteen phases of t per workgroup (the loop is a chain of
+// dependent L2 round trips, so its length is the kernel's time), added in order.  grid (ceil(U1/64), B), 1024 threads.
+__global__ __launch_bounds__(1024) void smooth_occ_cols_kernel(const float *__restrict__ ob, const float *__restrict__ oe,
+                                                              int T, int U1, float *__restrict__ rb, float *__restrict__ re)
+{
+    __shared__ float sb[kOccPhases][64], se[kOccPhases][64];
+    const int b = blockIdx.y;
+    const int ul = threadIdx.x & 63, ph = threadIdx.x >> 6;
+    const int u = blockIdx.x * 64 + ul;
+    float pb = 0.f, pe = 0.f;
+    if (u < U1) {
+#pragma unroll 8
+        for (int t = ph; t < T; t += kOccPhases) {
+            const size_t cell = ((size_t)b * T + t) * U1 + u;
+            pb += ob[cell];
+            pe += oe[cell];
+        }
+    }
+    sb[ph][ul] = pb;
+    se[ph][ul] = pe;
+    __syncthreads();
+    if (ph != 0 || u >= U1) return;
+    float tb = sb[0][ul], te = se[0][ul];
+#pragma unroll
+    for (int p = 1; p < kOccPhases; ++p) { tb += sb[p][ul]; te += se[p][ul]; }
+    rb[(size_t)b * U1 + u] = tb;
+    re[(size_t)b * U1 + u] = te;
+}
+
+// h is kept as hp[v] = h[v] * pbar[v] = la * sum_b (sum_t cg[b,t] q_t[v] - what the arcs of b subtract at v), which is
+// bounded (q_t[v] = e^{am - N + log pbar[v]} <= 1) where h itself overflows for a symbol that lm never predicts.
+// part[b * TC + tc, v] = sum_{t in chunk tc, t < T_b} cg[b,t] q_t[v], and from chunk 0 of every utterance minus what its
+// arcs subtract at v.  grid (ceil(V/256), TC, B).
+__global__ __launch_bounds__(256) void smooth_h_part_kernel(
+    const float *__restrict__ am, const float *__restrict__ nrm, const float *__restrict__ cg,
+    const float *__restrict__ rb, const float *__restrict__ re, const float *__restrict__ lpbar,
+    const int32_t *__restrict__ symbols, const int32_t *__restrict__ llens, const int32_t *__restrict__ tlens, int T,
+    int U1, int V, int blank, float *__restrict__ part)
+{
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= V) return;
+    const int b = blockIdx.z, tc = blockIdx.y;
+    const int Tb = clampi(llens[b], 0, T), Ub = clampi(tlens[b], 0, U1 - 1);
+    const int t0 = tc * kSmoothRows, t1 = min(t0 + kSmoothRows, Tb);
+    const float *__restrict__ amb = am + (size_t)b * T * V + v;
+    const float lp = lpbar[v];
+    float acc = 0.f;
+#pragma unroll 8
+    for (int t = t0; t < t1; ++t)
+        acc += cg[(size_t)b * T + t] * fast_exp2(((amb[(size_t)t * V] - nrm[(size_t)b * T + t]) + lp) * kLog2e);
+    if (tc == 0 && Tb > 0) {
+        float sub = 0.f;
+        for (int u = 0; u <= Ub; ++u) {
+            if (v == blank) sub += rb[(size_t)b * U1 + u];
+            if (u < Ub && symbols[(size_t)b * (U1 - 1) + u] == v) sub += re[(size_t)b * U1 + u];
+        }
+        acc -= sub;
+    }
+    part[((size_t)b * gridDim.y + tc) * V + v] = acc;
+}
+
+__global__ __launch_bounds__(256) void smooth_h_kernel(const float *__restrict__ part, int parts, int V, float la,
+                                                       float *__restrict__ hp)
+{
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= V) return;
+    float acc = 0.f;
+#pragma unroll 16
+    for (int p = 0; p < parts; ++p) acc += part[(size_t)p * V + v];
+    hp[v] = la * acc;
+}
+
+// d am[b,t,v] += la * cg[b,t] * q_t[v],  q_t[v] = e^{am - N + log pbar[v]}, on the valid rows: one wave per row.
+__global__ __launch_bounds__(256) void smooth_am_row_kernel(
+    const float *__restrict__ am, const float *__restrict__ nrm, const float *__restrict__ cg,
+    const float *__restrict__ lpbar, const int32_t *__restrict__ llens, int B, int T, int V, float la,
+    float *__restrict__ d_am)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const long r = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (r >= (long)B * T) return;
+    const int b = (int)(r / T), t = (int)(r - (long)b * T);
+    if (t >= clampi(llens[b], 0, T)) return;
+    const float *__restrict__ row = am + (size_t)r * V;
+    float *__restrict__ out = d_am + (size_t)r * V;
+    const float n = nrm[r], f = la * cg[r];
+#pragma unroll 4
+    for (int v = lane; v < V; v += kWave) out[v] += f * fast_exp2(((row[v] - n) + lpbar[v]) * kLog2e);
+}
+
+// d lm[b,u,v] += s[v] * ll * (rb + re)[b,u] + (r[v] hp[v] - s[v] sum_w r[w] hp[w]) * inv_rows,  s = e^{lm[b,u] - Zl[b,u]},
+// r[v] = s[v] / pbar[v] <= B * U1 (pbar holds s[v] / (B * U1) of this very row).
+// UNI (la > 0): every row of lm; otherwise the valid rows only, and the padded ones stay exactly zero.
+template <bool UNI>
+__global__ __launch_bounds__(256) void smooth_lm_row_kernel(
+    const float *__restrict__ lm, const float *__restrict__ zl, const float *__restrict__ rb,
+    const float *__restrict__ re, const float *__restrict__ hp, const float *__restrict__ pbar,
+    const int32_t *__restrict__ llens,
+    const int32_t *__restrict__ tlens, long rows, int T, int U1, int V, float ll, float inv_rows,
+    float *__restrict__ d_lm)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const long r = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const int b = (int)(r / U1), u = (int)(r - (long)b * U1);
+    const bool valid = clampi(llens[b], 0, T) > 0 && u <= clampi(tlens[b], 0, U1 - 1);
+    if (!UNI && !valid) return;
+    const float *__restrict__ row = lm + (size_t)r * V;
+    float *__restrict__ out = d_lm + (size_t)r * V;
+    const float z = zl[r];
+    const float f = valid ? ll * (rb[r] + re[r]) : 0.f;
+    float dot = 0.f;
+    if (UNI) {
+#pragma unroll 4
+        for (int v = lane; v < V; v += kWave) dot += fast_exp2((row[v] - z) * kLog2e) / pbar[v] * hp[v];
+        dot = wave_sum(dot);
+    }
+#pragma unroll 4
+    for (int v = lane; v < V; v += kWave) {
+        const float s = fast_exp2((row[v] - z) * kLog2e);
+        out[v] += UNI ? s * f + (s / pbar[v] * hp[v] - s * dot) * inv_rows : s * f;
     }
 }
 
@@ -476,6 +786,98 @@ int simple_check(const char *what, int B, int T, int U1, int V, int blank)
     WR_REQUIRE((long)B * T * U1 < (1L << 31), WR_EUNSUPPORTED, "%s: more than 2^31 lattice cells", what);
     WR_REQUIRE(B <= 65535 && T <= 64 * 65535, WR_EUNSUPPORTED, "%s: B is limited to 65535 and T to 64 * 65535 (got %d,%d)",
                what, B, T);
+    return WR_OK;
+}
+
+// The kernels of wr_rnnt_simple_stats (arguments checked by the caller).
+int simple_stats_launch(const float *am_d, const float *lm_d, const int32_t *symbols_d, const int32_t *logit_lengths_d,
+                        const int32_t *target_lengths_d, int B, int T, int U1, int V, int blank, const SimpleWs &sw,
+                        const RnntWs &w, char *sws, char *ws, hipStream_t st)
+{
+    float *ma = reinterpret_cast<float *>(sws + sw.ma_off), *ml = reinterpret_cast<float *>(sws + sw.ml_off);
+    float2 *lp = reinterpret_cast<float2 *>(ws + w.lp_off);
+    float *denom = reinterpret_cast<float *>(ws + w.denom_off);
+    int32_t *flag = reinterpret_cast<int32_t *>(ws + w.flag_off);
+
+    const long rows_am = (long)B * T, rows_lm = (long)B * U1;
+    hipLaunchKernelGGL(simple_rowmax_kernel, dim3((unsigned)((rows_am + rows_lm + 3) / 4)), dim3(256), 0, st, am_d, lm_d,
+                       rows_am, rows_lm, V, ma, ml, flag);
+    WR_CHECK_LAUNCH("simple_rowmax_kernel");
+    hipLaunchKernelGGL(simple_stats_kernel, dim3((U1 + kTile - 1) / kTile, (T + kTile - 1) / kTile, B), dim3(256), 0, st,
+                       am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, T, U1, V, blank, w.S, ma, ml, lp, denom,
+                       flag);
+    WR_CHECK_LAUNCH("simple_stats_kernel");
+    long blocks = ((long)B * T * U1 + 3) / 4;
+    if (blocks > 256L * 16) blocks = 256L * 16;
+    hipLaunchKernelGGL(simple_stats_direct_kernel, dim3((unsigned)blocks), dim3(256), 0, st, am_d, lm_d, symbols_d,
+                       logit_lengths_d, target_lengths_d, B, T, U1, V, blank, w.S, lp, denom, flag);
+    WR_CHECK_LAUNCH("simple_stats_direct_kernel");
+    return WR_OK;
+}
+
+// The occupancies (always) and, unless `occ_only`, the kernels of wr_rnnt_simple_grad up to the contractions: G scaled by
+// `gscale`.  The scatter terms follow in simple_fix_launch, after whatever the caller adds to the rows.
+int simple_grad_launch(const float *am_d, const float *lm_d, const int32_t *symbols_d, const int32_t *logit_lengths_d,
+                       const int32_t *target_lengths_d, int B, int T, int U1, int V, const float *grad_costs_d,
+                       float *d_am_d, float *d_lm_d, float *occ_emit_d, float *occ_blank_d, const SimpleWs &sw,
+                       const RnntWs &w, char *sws, const char *ws, float gscale, bool occ_only, hipStream_t st)
+{
+    const float *ma = reinterpret_cast<const float *>(sws + sw.ma_off), *ml = reinterpret_cast<const float *>(sws + sw.ml_off);
+    float *g = reinterpret_cast<float *>(sws + sw.g_off), *gt = reinterpret_cast<float *>(sws + sw.gt_off);
+    float *ob = reinterpret_cast<float *>(sws + sw.ob_off), *oe = reinterpret_cast<float *>(sws + sw.oe_off);
+    int32_t *nxt = reinterpret_cast<int32_t *>(sws + sw.nxt_off), *head = reinterpret_cast<int32_t *>(sws + sw.head_off);
+    const float *denom = reinterpret_cast<const float *>(ws + w.denom_off);
+    const int32_t *flag = reinterpret_cast<const int32_t *>(ws + w.flag_off);
+    const long cells = (long)B * T * U1;
+
+    hipLaunchKernelGGL(simple_occ_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, logit_lengths_d,
+                       target_lengths_d, B, T, U1, w.S, reinterpret_cast<const double *>(ws + w.alpha_off),
+                       reinterpret_cast<const double *>(ws + w.beta_off), reinterpret_cast<const float2 *>(ws + w.lp_off),
+                       denom, reinterpret_cast<const double *>(ws + w.cost_off), ma, ml, grad_costs_d, flag, gscale, g, gt,
+                       ob, oe, occ_emit_d, occ_blank_d);
+    WR_CHECK_LAUNCH("simple_occ_kernel");
+    if (occ_only) return WR_OK;
+    hipLaunchKernelGGL(simple_chain_kernel, dim3(B), dim3(256), 0, st, symbols_d, target_lengths_d, U1, nxt, head);
+    WR_CHECK_LAUNCH("simple_chain_kernel");
+
+    const unsigned vg = (unsigned)((V + kGemmCols - 1) / kGemmCols), vd = (unsigned)((V + 255) / 256);
+    hipLaunchKernelGGL((simple_grad_gemm_kernel<true>), dim3(vg, (T + kTile - 1) / kTile, B), dim3(256), 0, st, gt, am_d, ma,
+                       lm_d, ml, logit_lengths_d, target_lengths_d, T, U1, V, flag, d_am_d);
+    WR_CHECK_LAUNCH("simple_grad_gemm_kernel<am>");
+    hipLaunchKernelGGL((simple_grad_gemm_kernel<false>), dim3(vg, (U1 + kTile - 1) / kTile, B), dim3(256), 0, st, g, lm_d, ml,
+                       am_d, ma, logit_lengths_d, target_lengths_d, T, U1, V, flag, d_lm_d);
+    WR_CHECK_LAUNCH("simple_grad_gemm_kernel<lm>");
+    hipLaunchKernelGGL((simple_grad_direct_kernel<true>), dim3(vd, T < 64 ? T : 64, B), dim3(256), 0, st, g, denom, am_d, lm_d,
+                       logit_lengths_d, target_lengths_d, T, U1, V, flag, d_am_d);
+    WR_CHECK_LAUNCH("simple_grad_direct_kernel<am>");
+    hipLaunchKernelGGL((simple_grad_direct_kernel<false>), dim3(vd, U1 < 64 ? U1 : 64, B), dim3(256), 0, st, g, denom, lm_d, am_d,
+                       logit_lengths_d, target_lengths_d, T, U1, V, flag, d_lm_d);
+    WR_CHECK_LAUNCH("simple_grad_direct_kernel<lm>");
+    return WR_OK;
+}
+
+int simple_fix_launch(const int32_t *symbols_d, const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B,
+                      int T, int U1, int V, int blank, float *d_am_d, float *d_lm_d, const SimpleWs &sw, char *sws,
+                      float w_am, float w_lm, bool every_arc, hipStream_t st)
+{
+    const float *ob = reinterpret_cast<const float *>(sws + sw.ob_off), *oe = reinterpret_cast<const float *>(sws + sw.oe_off);
+    const int32_t *nxt = reinterpret_cast<const int32_t *>(sws + sw.nxt_off);
+    const int32_t *head = reinterpret_cast<const int32_t *>(sws + sw.head_off);
+    hipLaunchKernelGGL(simple_fix_am_kernel, dim3((unsigned)(((long)B * T + 3) / 4)), dim3(256), 0, st, ob, oe, nxt, head,
+                       symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, w_am, every_arc, d_am_d);
+    WR_CHECK_LAUNCH("simple_fix_am_kernel");
+    hipLaunchKernelGGL(simple_fix_lm_kernel, dim3((U1 + 63) / 64, B), dim3(256), 0, st, ob, oe, symbols_d, logit_lengths_d,
+                       target_lengths_d, T, U1, V, blank, w_lm, every_arc, d_lm_d);
+    WR_CHECK_LAUNCH("simple_fix_lm_kernel");
+    return WR_OK;
+}
+
+int smooth_check(const char *what, float ll, float la, int V)
+{
+    WR_REQUIRE(ll >= 0.f && la >= 0.f, WR_EINVAL, "%s: lm_only_scale %g and am_only_scale %g must not be negative", what,
+               (double)ll, (double)la);
+    WR_REQUIRE(ll + la <= 1.f, WR_EINVAL, "%s: lm_only_scale + am_only_scale = %g exceeds 1", what, (double)(ll + la));
+    WR_REQUIRE(V <= 256 * 65535, WR_EUNSUPPORTED, "%s: V = %d exceeds %d", what, V, 256 * 65535);
     return WR_OK;
 }
 
@@ -505,27 +907,9 @@ extern "C" int wr_rnnt_simple_stats(const float *am_d, const float *lm_d, const 
                simple_workspace_bytes, sw.total);
     WR_REQUIRE(rnnt_workspace_bytes >= w.total, WR_EWORKSPACE, "rnnt_simple_stats: rnnt workspace %zu < required %zu",
                rnnt_workspace_bytes, w.total);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char *sws = static_cast<char *>(simple_workspace_d), *ws = static_cast<char *>(rnnt_workspace_d);
-    float *ma = reinterpret_cast<float *>(sws + sw.ma_off), *ml = reinterpret_cast<float *>(sws + sw.ml_off);
-    float2 *lp = reinterpret_cast<float2 *>(ws + w.lp_off);
-    float *denom = reinterpret_cast<float *>(ws + w.denom_off);
-    int32_t *flag = reinterpret_cast<int32_t *>(ws + w.flag_off);
-
-    const long rows_am = (long)B * T, rows_lm = (long)B * U1;
-    hipLaunchKernelGGL(simple_rowmax_kernel, dim3((unsigned)((rows_am + rows_lm + 3) / 4)), dim3(256), 0, st, am_d, lm_d,
-                       rows_am, rows_lm, V, ma, ml, flag);
-    WR_CHECK_LAUNCH("simple_rowmax_kernel");
-    hipLaunchKernelGGL(simple_stats_kernel, dim3((U1 + kTile - 1) / kTile, (T + kTile - 1) / kTile, B), dim3(256), 0, st,
-                       am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, T, U1, V, blank, w.S, ma, ml, lp, denom,
-                       flag);
-    WR_CHECK_LAUNCH("simple_stats_kernel");
-    long blocks = ((long)B * T * U1 + 3) / 4;
-    if (blocks > 256L * 16) blocks = 256L * 16;
-    hipLaunchKernelGGL(simple_stats_direct_kernel, dim3((unsigned)blocks), dim3(256), 0, st, am_d, lm_d, symbols_d,
-                       logit_lengths_d, target_lengths_d, B, T, U1, V, blank, w.S, lp, denom, flag);
-    WR_CHECK_LAUNCH("simple_stats_direct_kernel");
-    return WR_OK;
+    return simple_stats_launch(am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, sw, w,
+                               static_cast<char *>(simple_workspace_d), static_cast<char *>(rnnt_workspace_d),
+                               static_cast<hipStream_t>(stream));
 }
 
 extern "C" int wr_rnnt_simple_grad(const float *am_d, const float *lm_d, const int32_t *symbols_d,
@@ -547,43 +931,145 @@ extern "C" int wr_rnnt_simple_grad(const float *am_d, const float *lm_d, const i
                rnnt_workspace_bytes, w.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
     char *sws = static_cast<char *>(simple_workspace_d);
-    const char *ws = static_cast<const char *>(rnnt_workspace_d);
-    const float *ma = reinterpret_cast<const float *>(sws + sw.ma_off), *ml = reinterpret_cast<const float *>(sws + sw.ml_off);
-    float *g = reinterpret_cast<float *>(sws + sw.g_off), *gt = reinterpret_cast<float *>(sws + sw.gt_off);
-    float *ob = reinterpret_cast<float *>(sws + sw.ob_off), *oe = reinterpret_cast<float *>(sws + sw.oe_off);
-    int32_t *nxt = reinterpret_cast<int32_t *>(sws + sw.nxt_off), *head = reinterpret_cast<int32_t *>(sws + sw.head_off);
-    const float *denom = reinterpret_cast<const float *>(ws + w.denom_off);
-    const int32_t *flag = reinterpret_cast<const int32_t *>(ws + w.flag_off);
-    const long cells = (long)B * T * U1;
+    if (int rc = simple_grad_launch(am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, grad_costs_d,
+                                    d_am_d, d_lm_d, occ_emit_d, occ_blank_d, sw, w, sws,
+                                    static_cast<const char *>(rnnt_workspace_d), 1.f, false, st))
+        return rc;
+    return simple_fix_launch(symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, d_am_d, d_lm_d, sw, sws, 1.f,
+                             1.f, false, st);
+}
 
-    hipLaunchKernelGGL(simple_occ_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, logit_lengths_d,
-                       target_lengths_d, B, T, U1, w.S, reinterpret_cast<const double *>(ws + w.alpha_off),
-                       reinterpret_cast<const double *>(ws + w.beta_off), reinterpret_cast<const float2 *>(ws + w.lp_off),
-                       denom, reinterpret_cast<const double *>(ws + w.cost_off), ma, ml, grad_costs_d, flag, g, gt, ob, oe,
-                       occ_emit_d, occ_blank_d);
-    WR_CHECK_LAUNCH("simple_occ_kernel");
-    hipLaunchKernelGGL(simple_chain_kernel, dim3(B), dim3(256), 0, st, symbols_d, target_lengths_d, U1, nxt, head);
-    WR_CHECK_LAUNCH("simple_chain_kernel");
+extern "C" size_t wr_rnnt_smoothed_workspace_bytes(int B, int T, int U1, int V)
+{
+    if (B <= 0 || T <= 0 || U1 <= 0 || V <= 0) return 0;
+    return smooth_ws_layout(B, T, U1, V).total;
+}
 
-    const unsigned vg = (unsigned)((V + kGemmCols - 1) / kGemmCols), vd = (unsigned)((V + 255) / 256);
-    hipLaunchKernelGGL((simple_grad_gemm_kernel<true>), dim3(vg, (T + kTile - 1) / kTile, B), dim3(256), 0, st, gt, am_d, ma,
-                       lm_d, ml, logit_lengths_d, target_lengths_d, T, U1, V, flag, d_am_d);
-    WR_CHECK_LAUNCH("simple_grad_gemm_kernel<am>");
-    hipLaunchKernelGGL((simple_grad_gemm_kernel<false>), dim3(vg, (U1 + kTile - 1) / kTile, B), dim3(256), 0, st, g, lm_d, ml,
-                       am_d, ma, logit_lengths_d, target_lengths_d, T, U1, V, flag, d_lm_d);
-    WR_CHECK_LAUNCH("simple_grad_gemm_kernel<lm>");
-    hipLaunchKernelGGL((simple_grad_direct_kernel<true>), dim3(vd, T < 64 ? T : 64, B), dim3(256), 0, st, g, denom, am_d, lm_d,
-                       logit_lengths_d, target_lengths_d, T, U1, V, flag, d_am_d);
-    WR_CHECK_LAUNCH("simple_grad_direct_kernel<am>");
-    hipLaunchKernelGGL((simple_grad_direct_kernel<false>), dim3(vd, U1 < 64 ? U1 : 64, B), dim3(256), 0, st, g, denom, lm_d, am_d,
-                       logit_lengths_d, target_lengths_d, T, U1, V, flag, d_lm_d);
-    WR_CHECK_LAUNCH("simple_grad_direct_kernel<lm>");
+extern "C" int wr_rnnt_smoothed_stats(const float *am_d, const float *lm_d, const int32_t *symbols_d,
+                                      const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T,
+                                      int U1, int V, int blank, float lm_only_scale, float am_only_scale,
+                                      void *smoothed_workspace_d, size_t smoothed_workspace_bytes, void *rnnt_workspace_d,
+                                      size_t rnnt_workspace_bytes, void *stream)
+{
+    const float ll = lm_only_scale, la = am_only_scale;
+    if (int rc = simple_check("rnnt_smoothed_stats", B, T, U1, V, blank)) return rc;
+    if (int rc = smooth_check("rnnt_smoothed_stats", ll, la, V)) return rc;
+    WR_REQUIRE(am_d && lm_d && logit_lengths_d && target_lengths_d && smoothed_workspace_d && rnnt_workspace_d, WR_EINVAL,
+               "rnnt_smoothed_stats: null pointer argument");
+    WR_REQUIRE(symbols_d || U1 == 1, WR_EINVAL, "rnnt_smoothed_stats: symbols is null");
+    const SmoothWs mw = smooth_ws_layout(B, T, U1, V);
+    const RnntWs w = rnnt_ws_layout(B, T, U1);
+    WR_REQUIRE(smoothed_workspace_bytes >= mw.total, WR_EWORKSPACE, "rnnt_smoothed_stats: workspace %zu < required %zu",
+               smoothed_workspace_bytes, mw.total);
+    WR_REQUIRE(rnnt_workspace_bytes >= w.total, WR_EWORKSPACE, "rnnt_smoothed_stats: rnnt workspace %zu < required %zu",
+               rnnt_workspace_bytes, w.total);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char *sws = static_cast<char *>(smoothed_workspace_d), *ws = static_cast<char *>(rnnt_workspace_d);
+    if (int rc = simple_stats_launch(am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, mw.s, w,
+                                     sws, ws, st))
+        return rc;
+    if (ll == 0.f && la == 0.f) return WR_OK;             // rnnt_loss_simple, by the same kernels
 
-    hipLaunchKernelGGL(simple_fix_am_kernel, dim3((unsigned)(((long)B * T + 3) / 4)), dim3(256), 0, st, ob, oe, nxt, head,
-                       symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, d_am_d);
-    WR_CHECK_LAUNCH("simple_fix_am_kernel");
-    hipLaunchKernelGGL(simple_fix_lm_kernel, dim3((U1 + 63) / 64, B), dim3(256), 0, st, ob, oe, symbols_d, logit_lengths_d,
-                       target_lengths_d, T, U1, V, blank, d_lm_d);
-    WR_CHECK_LAUNCH("simple_fix_lm_kernel");
+    const float *ml = reinterpret_cast<const float *>(sws + mw.s.ml_off), *ma = reinterpret_cast<const float *>(sws + mw.s.ma_off);
+    float *zl = reinterpret_cast<float *>(sws + mw.zl_off), *lb = reinterpret_cast<float *>(sws + mw.lb_off);
+    float *le = reinterpret_cast<float *>(sws + mw.le_off), *nrm = reinterpret_cast<float *>(sws + mw.n_off);
+    float *ab = reinterpret_cast<float *>(sws + mw.ab_off), *pbar = reinterpret_cast<float *>(sws + mw.pbar_off);
+    float *lpbar = reinterpret_cast<float *>(sws + mw.lpbar_off), *part = reinterpret_cast<float *>(sws + mw.part_off);
+    const long rows_lm = (long)B * U1, rows_am = (long)B * T, cells = (long)B * w.S * U1;
+    const unsigned vb = (unsigned)((V + 255) / 256);
+    const float c = (float)(1.0 - (double)ll - (double)la);
+
+    hipLaunchKernelGGL(smooth_lm_rows_kernel, dim3((unsigned)((rows_lm + 3) / 4)), dim3(256), 0, st, lm_d, ml, symbols_d,
+                       target_lengths_d, rows_lm, U1, V, blank, zl, lb, le);
+    WR_CHECK_LAUNCH("smooth_lm_rows_kernel");
+    if (la != 0.f) {
+        hipLaunchKernelGGL(smooth_colsum_kernel, dim3(mw.lm_chunks, vb), dim3(256), 0, st, lm_d, zl, rows_lm, V, part);
+        WR_CHECK_LAUNCH("smooth_colsum_kernel");
+        hipLaunchKernelGGL(smooth_pbar_kernel, dim3(vb), dim3(256), 0, st, part, mw.lm_chunks, rows_lm, V, pbar, lpbar);
+        WR_CHECK_LAUNCH("smooth_pbar_kernel");
+        hipLaunchKernelGGL(smooth_am_norm_kernel, dim3((unsigned)((rows_am + 3) / 4)), dim3(256), 0, st, am_d, ma, pbar,
+                           lpbar, logit_lengths_d, B, T, V, blank, nrm, ab);
+        WR_CHECK_LAUNCH("smooth_am_norm_kernel");
+        hipLaunchKernelGGL((smooth_interp_kernel<true>), dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, am_d,
+                           symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, w.S, c, ll, la, lb, le, nrm, ab,
+                           lpbar, reinterpret_cast<float2 *>(ws + w.lp_off));
+        WR_CHECK_LAUNCH("smooth_interp_kernel<am>");
+    } else {
+        hipLaunchKernelGGL((smooth_interp_kernel<false>), dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st,
+                           (const float *)nullptr, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, w.S, c, ll, la,
+                           lb, le, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr,
+                           reinterpret_cast<float2 *>(ws + w.lp_off));
+        WR_CHECK_LAUNCH("smooth_interp_kernel<lm>");
+    }
     return WR_OK;
+}
+
+extern "C" int wr_rnnt_smoothed_grad(const float *am_d, const float *lm_d, const int32_t *symbols_d,
+                                     const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T,
+                                     int U1, int V, int blank, float lm_only_scale, float am_only_scale,
+                                     const float *grad_costs_d, float *d_am_d, float *d_lm_d, float *occ_emit_d,
+                                     float *occ_blank_d, void *smoothed_workspace_d, size_t smoothed_workspace_bytes,
+                                     const void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream)
+{
+    const float ll = lm_only_scale, la = am_only_scale;
+    if (int rc = simple_check("rnnt_smoothed_grad", B, T, U1, V, blank)) return rc;
+    if (int rc = smooth_check("rnnt_smoothed_grad", ll, la, V)) return rc;
+    const bool occ_only = !d_am_d && !d_lm_d;
+    WR_REQUIRE(am_d && lm_d && logit_lengths_d && target_lengths_d && smoothed_workspace_d && rnnt_workspace_d, WR_EINVAL,
+               "rnnt_smoothed_grad: null pointer argument");
+    WR_REQUIRE(occ_only ? (occ_emit_d && occ_blank_d) : (d_am_d && d_lm_d), WR_EINVAL,
+               "rnnt_smoothed_grad: d_am and d_lm go together; without them both occupancy outputs are needed");
+    WR_REQUIRE(symbols_d || U1 == 1, WR_EINVAL, "rnnt_smoothed_grad: symbols is null");
+    const SmoothWs mw = smooth_ws_layout(B, T, U1, V);
+    const RnntWs w = rnnt_ws_layout(B, T, U1);
+    WR_REQUIRE(smoothed_workspace_bytes >= mw.total, WR_EWORKSPACE, "rnnt_smoothed_grad: workspace %zu < required %zu",
+               smoothed_workspace_bytes, mw.total);
+    WR_REQUIRE(rnnt_workspace_bytes >= w.total, WR_EWORKSPACE, "rnnt_smoothed_grad: rnnt workspace %zu < required %zu",
+               rnnt_workspace_bytes, w.total);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char *sws = static_cast<char *>(smoothed_workspace_d);
+    const bool smooth = ll != 0.f || la != 0.f;
+    const float c = smooth ? (float)(1.0 - (double)ll - (double)la) : 1.f;
+    if (int rc = simple_grad_launch(am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, grad_costs_d,
+                                    d_am_d, d_lm_d, occ_emit_d, occ_blank_d, mw.s, w, sws,
+                                    static_cast<const char *>(rnnt_workspace_d), c, occ_only, st))
+        return rc;
+    if (occ_only) return WR_OK;
+    if (smooth) {
+        const float *ob = reinterpret_cast<const float *>(sws + mw.s.ob_off), *oe = reinterpret_cast<const float *>(sws + mw.s.oe_off);
+        const float *zl = reinterpret_cast<const float *>(sws + mw.zl_off), *nrm = reinterpret_cast<const float *>(sws + mw.n_off);
+        const float *pbar = reinterpret_cast<const float *>(sws + mw.pbar_off);
+        const float *lpbar = reinterpret_cast<const float *>(sws + mw.lpbar_off);
+        float *cg = reinterpret_cast<float *>(sws + mw.cg_off), *rb = reinterpret_cast<float *>(sws + mw.rb_off);
+        float *re = reinterpret_cast<float *>(sws + mw.re_off), *h = reinterpret_cast<float *>(sws + mw.h_off);
+        float *part = reinterpret_cast<float *>(sws + mw.part_off);
+        const long rows_lm = (long)B * U1, rows_am = (long)B * T;
+        const unsigned vb = (unsigned)((V + 255) / 256);
+        hipLaunchKernelGGL(smooth_occ_cols_kernel, dim3((U1 + 63) / 64, B), dim3(64 * kOccPhases), 0, st, ob, oe, T, U1, rb, re);
+        WR_CHECK_LAUNCH("smooth_occ_cols_kernel");
+        if (la != 0.f) {
+            hipLaunchKernelGGL(smooth_occ_rows_kernel, dim3((unsigned)((rows_am + 3) / 4)), dim3(256), 0, st, ob, oe, rows_am,
+                               U1, cg);
+            WR_CHECK_LAUNCH("smooth_occ_rows_kernel");
+            hipLaunchKernelGGL(smooth_h_part_kernel, dim3(vb, mw.t_chunks, B), dim3(256), 0, st, am_d, nrm, cg, rb, re, lpbar,
+                               symbols_d, logit_lengths_d, target_lengths_d, T, U1, V, blank, part);
+            WR_CHECK_LAUNCH("smooth_h_part_kernel");
+            hipLaunchKernelGGL(smooth_h_kernel, dim3(vb), dim3(256), 0, st, part, B * mw.t_chunks, V, la, h);
+            WR_CHECK_LAUNCH("smooth_h_kernel");
+            hipLaunchKernelGGL(smooth_am_row_kernel, dim3((unsigned)((rows_am + 3) / 4)), dim3(256), 0, st, am_d, nrm, cg,
+                               lpbar, logit_lengths_d, B, T, V, la, d_am_d);
+            WR_CHECK_LAUNCH("smooth_am_row_kernel");
+            hipLaunchKernelGGL((smooth_lm_row_kernel<true>), dim3((unsigned)((rows_lm + 3) / 4)), dim3(256), 0, st, lm_d, zl,
+                               rb, re, h, pbar, logit_lengths_d, target_lengths_d, rows_lm, T, U1, V, ll, 1.f / (float)rows_lm,
+                               d_lm_d);
+            WR_CHECK_LAUNCH("smooth_lm_row_kernel<unigram>");
+        } else {
+            hipLaunchKernelGGL((smooth_lm_row_kernel<false>), dim3((unsigned)((rows_lm + 3) / 4)), dim3(256), 0, st, lm_d, zl,
+                               rb, re, (const float *)nullptr, (const float *)nullptr, logit_lengths_d, target_lengths_d, rows_lm, T, U1, V, ll, 0.f,
+                               d_lm_d);
+            WR_CHECK_LAUNCH("smooth_lm_row_kernel<rows>");
+        }
+    }
+    return simple_fix_launch(symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, d_am_d, d_lm_d, mw.s, sws,
+                             smooth ? c + la : 1.f, smooth ? c + ll : 1.f, smooth, st);
 }

@@ -36,6 +36,7 @@ from .joint import TransducerJoint, _call_precision
 from .rnnt_align import joint_rnnt_forced_align, rnnt_forced_align
 from .rnnt_loss import rnnt_loss
 from .rnnt_simple import rnnt_loss_simple, rnnt_simple_forced_align
+from .rnnt_smoothed import rnnt_loss_smoothed
 from .rnnt_pruned import get_rnnt_prune_ranges, rnnt_loss_pruned
 from .search.greedy_search import basic_greedy_search, basic_greedy_search_both, basic_greedy_search_hw
 from .search.prefix_beam_search import PrefixBeamSearch
@@ -79,7 +80,8 @@ class Transducer(nn.Module):
                  context_bias: Optional[nn.Module] = None, ctc_weight: float = 0, ignore_id: int = IGNORE_ID,
                  reverse_weight: float = 0.0, lsm_weight: float = 0.0, length_normalized_loss: bool = False,
                  transducer_weight: float = 1.0, attention_weight: float = 0.0, hw_weight: float = 0.4,
-                 loss_mode: str = "both", prune_range: int = 0, simple_loss_weight: float = 0.0) -> None:
+                 loss_mode: str = "both", prune_range: int = 0, lm_only_scale: float = 0.0,
+                 am_only_scale: float = 0.0, simple_loss_weight: float = 0.0) -> None:
         assert attention_weight + ctc_weight + transducer_weight == 1.0          # transducer.py:46 (kept as is)
         super().__init__()
         # ASRModel part (asr_model.py:38-70): sos/eos are the last class
@@ -126,6 +128,14 @@ class Transducer(nn.Module):
         if self.simple_loss_weight > 0.0:
             self.simple_am_proj = nn.Linear(_output_width(encoder, "encoder", joint, "enc_ffn"), vocab_size)
             self.simple_lm_proj = nn.Linear(_output_width(predictor, "predictor", joint, "pred_ffn"), vocab_size)
+        # smoothing of the simple loss (k2's rnnt_loss_smoothed; icefall trains with lm_only_scale = 0.25, am_only_scale
+        # = 0): either scale non-zero and loss_simple (and the occupancies the pruning takes) is rnnt_loss_smoothed's.
+        self.lm_only_scale, self.am_only_scale = float(lm_only_scale), float(am_only_scale)
+        if self.lm_only_scale < 0.0 or self.am_only_scale < 0.0 or self.lm_only_scale + self.am_only_scale > 1.0:
+            raise ValueError(f"Transducer: lm_only_scale and am_only_scale must be >= 0 and sum to at most 1 (got "
+                             f"{lm_only_scale}, {am_only_scale})")
+        if (self.lm_only_scale > 0.0 or self.am_only_scale > 0.0) and not self.simple_loss_weight > 0.0:
+            raise ValueError("Transducer: lm_only_scale / am_only_scale smooth the simple loss: simple_loss_weight must be > 0")
         # pruned training (k2 / icefall recipe, rnnt_pruned.py): the simple loss's arc occupancies choose a band of
         # `prune_range` label positions per frame, and loss_rnnt is the RNN-T loss of the joiner evaluated on that band
         # only.  0: the full-lattice loss block above.
@@ -206,9 +216,17 @@ class Transducer(nn.Module):
 
     def compute_simple_loss(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, predictor_out: torch.Tensor,
                             text: torch.Tensor, text_lengths: torch.Tensor) -> torch.Tensor:
-        """rnnt_loss_simple on the two vocabulary heads, reduction "mean" (transducer_k2_loss.py:147-157)."""
+        """rnnt_loss_simple on the two vocabulary heads, reduction "mean" (transducer_k2_loss.py:147-157);
+        rnnt_loss_smoothed when the model was built with a non-zero lm_only_scale or am_only_scale."""
         lm, am, symbols, boundary = self._simple_inputs(encoder_out, encoder_out_lens, predictor_out, text, text_lengths)
-        return rnnt_loss_simple(lm, am, symbols, self.blank, boundary=boundary, reduction="mean")
+        return self._simple_loss(lm, am, symbols, boundary, return_grad=False)
+
+    def _simple_loss(self, lm, am, symbols, boundary, return_grad: bool):
+        ll, la = self.lm_only_scale, self.am_only_scale
+        if ll != 0.0 or la != 0.0:
+            return rnnt_loss_smoothed(lm, am, symbols, self.blank, lm_only_scale=ll, am_only_scale=la, boundary=boundary,
+                                      reduction="mean", return_grad=return_grad)
+        return rnnt_loss_simple(lm, am, symbols, self.blank, boundary=boundary, reduction="mean", return_grad=return_grad)
 
     def compute_pruned_loss(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, predictor_out: torch.Tensor,
                             text: torch.Tensor, text_lengths: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -216,8 +234,7 @@ class Transducer(nn.Module):
         occupancies, `get_rnnt_prune_ranges` turns them into a band of `prune_range` label positions per frame, and
         loss_rnnt is `rnnt_loss_pruned` on the joiner's outputs on that band."""
         lm, am, symbols, boundary = self._simple_inputs(encoder_out, encoder_out_lens, predictor_out, text, text_lengths)
-        loss_simple, (px_grad, py_grad) = rnnt_loss_simple(lm, am, symbols, self.blank, boundary=boundary,
-                                                           reduction="mean", return_grad=True)
+        loss_simple, (px_grad, py_grad) = self._simple_loss(lm, am, symbols, boundary, return_grad=True)
         ranges = get_rnnt_prune_ranges(px_grad, py_grad, boundary, self.prune_range)
         logits = self.joint.forward_pruned(encoder_out, predictor_out, ranges)
         loss_rnnt = rnnt_loss_pruned(logits, symbols, ranges, self.blank, boundary=boundary, reduction="mean")
