@@ -39,6 +39,9 @@ extern "C" {
 #define WR_API_VERSION 3
 
 enum wr_dtype { WR_F32 = 0, WR_F16 = 1, WR_BF16 = 2 };
+
+/* lattice types of the k2 RNN-T losses ("Lattice types and the delay penalty" below) */
+enum wr_lattice { WR_LATTICE_REGULAR = 0, WR_LATTICE_MODIFIED = 1 };
 /* joiner activation (TransducerJoint(activation=...), wenet/transducer/joint.py:25 -> wenet/utils/common.py:228-242);
  * "tanh" is the shipped configuration, "swish" is torch.nn.SiLU, "gelu" the erf form (torch.nn.GELU default) */
 enum wr_activation { WR_ACT_TANH = 0, WR_ACT_RELU = 1, WR_ACT_HARDTANH = 2, WR_ACT_SELU = 3, WR_ACT_SWISH = 4, WR_ACT_GELU = 5 };
@@ -744,6 +747,69 @@ int wr_rnnt_pruned_grad(const void *logits_d, int dtype, const int32_t *symbols_
                         const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1, int R,
                         int V, int blank, const float *grad_costs_d /* [B] or NULL */, void *grads_d,
                         const void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream);
+
+/* Lattice types and the delay penalty: k2's rnnt_type = "modified" and delay_penalty for the three losses above (the
+ * additive-joiner loss, its smoothed form, the pruned loss).  k2 cannot be built for ROCm; this text is the contract.
+ * blank(t,u) / emit(t,u) are the blank / label log-probabilities of cell (t,u), 0 <= t < T_b, 0 <= u <= U_b, as the
+ * statistics call of the loss leaves them in the RNN-T workspace (for the pruned loss -inf outside the band).
+ *
+ * Delay penalty (either lattice): pen(b,t) = delay_penalty * ((T_b - 1) / 2 - t) is added to every label arc,
+ * emit'(t,u) = emit(t,u) + pen(b,t): formed in fp64, added to the stored fp32 value in fp64, rounded once.  In the smoothed
+ * loss that is after the interpolation.  It applies iff delay_penalty > 0; negative or non-finite values: WR_EINVAL.
+ *
+ * WR_LATTICE_REGULAR: the lattice of wr_rnnt_loss_fwd (a label arc (t,u) -> (t,u+1), a final blank out of (T_b-1,U_b)).
+ * WR_LATTICE_MODIFIED: nodes (t,u), 0 <= t <= T_b; blank arc (t,u) -> (t+1,u) with blank(t,u), label arc (t,u) ->
+ * (t+1,u+1) with emit'(t,u) for u < U_b.  Every frame carries exactly one arc; the last frame may carry a label.
+ *   alpha(0,0) = 0, alpha(0,u>0) = -inf, alpha(t,u) = logadd(alpha(t-1,u) + blank(t-1,u), alpha(t-1,u-1) + emit'(t-1,u-1))
+ *   beta(T_b,U_b) = 0, beta(T_b,u != U_b) = -inf, beta(t,u) = logadd(blank(t,u) + beta(t+1,u), emit'(t,u) + beta(t+1,u+1))
+ *   ll = alpha(T_b,U_b) = beta(0,0), cost = -ll
+ *   occ_blank(t,u) = exp(alpha(t,u) + blank(t,u) + beta(t+1,u) - ll), occ_emit(t,u) = exp(alpha(t,u) + emit'(t,u) +
+ *   beta(t+1,u+1) - ll); occ_blank + occ_emit = exp(alpha + beta - ll) at every cell.
+ *   d cost / d logits[t,u,:] = (occ_blank + occ_emit) softmax - occ_blank [v = blank] - occ_emit [v = label]; a label
+ *   equal to the blank has both terms subtracted (in wr_rnnt_smoothed_grad_lattice whatever the scales).
+ * T_b < U_b has no path: cost +inf for that utterance (a value, not an error; its gradient is not finite, the other
+ * utterances are unaffected).  T_b = 0: cost 0, zero gradient.  A cell no path reaches carries -inf.
+ *
+ * wr_rnnt_lattice_sweeps replaces wr_rnnt_loss_sweeps after wr_rnnt_simple_stats / wr_rnnt_smoothed_stats /
+ * wr_rnnt_pruned_stats, ONCE per statistics call (it rewrites the stored label arcs): adds the penalty, and for the
+ * modified lattice lays the arcs out in plain [b][t][u] rows inside the same workspace and runs the frame-synchronous
+ * sweeps (T_b dependent steps).  alpha / beta (fp64), ll and the costs land where wr_rnnt_loss_sweeps puts them for the
+ * regular lattice; the modified lattice keeps its arrays elsewhere in the workspace, so only the *_lattice calls below,
+ * given the same lattice_type, may read it (wr_rnnt_align_from_stats and wr_rnnt_export_lattice may not).
+ * WR_LATTICE_REGULAR with delay_penalty 0 is wr_rnnt_loss_sweeps.
+ * wr_rnnt_lattice_export: wr_rnnt_export_lattice for either type: alpha / beta [B,T,U1] fp32 (rows t < T_b; zero outside
+ * the boundary).
+ * wr_rnnt_smoothed_grad_lattice: wr_rnnt_smoothed_grad (both scales 0: wr_rnnt_simple_grad, on the smoothed workspace)
+ * reading the lattice of `lattice_type`; the penalty needs no argument, it is inside the stored label arcs.
+ * wr_rnnt_pruned_grad_lattice: wr_rnnt_pruned_grad likewise; it forms the label term from the logits, so it takes the
+ * penalty too (the value given to wr_rnnt_lattice_sweeps).
+ * wr_rnnt_prune_ranges_cols: wr_rnnt_prune_ranges with px_grad [B,U1-1,px_cols], px_cols = T + 1 (regular) or T (the
+ * modified lattice's layout, no extra frame column); only columns t < T are read, the rule is unchanged. */
+int wr_rnnt_lattice_sweeps(const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1,
+                           int lattice_type, double delay_penalty, float *costs_d /* [B] out */, void *workspace_d,
+                           size_t workspace_bytes, void *stream);
+
+int wr_rnnt_lattice_export(const void *workspace_d, size_t workspace_bytes, const int32_t *logit_lengths_d,
+                           const int32_t *target_lengths_d, int B, int T, int U1, int lattice_type,
+                           float *alpha_d /* [B,T,U1] out */, float *beta_d /* [B,T,U1] out */, void *stream);
+
+int wr_rnnt_smoothed_grad_lattice(const float *am_d, const float *lm_d, const int32_t *symbols_d,
+                                  const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1,
+                                  int V, int blank, float lm_only_scale, float am_only_scale, int lattice_type,
+                                  const float *grad_costs_d /* [B] or NULL */, float *d_am_d, float *d_lm_d,
+                                  float *occ_emit_d /* [B,T,U1] out or NULL */, float *occ_blank_d /* [B,T,U1] out or NULL */,
+                                  void *smoothed_workspace_d, size_t smoothed_workspace_bytes,
+                                  const void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream);
+
+int wr_rnnt_pruned_grad_lattice(const void *logits_d, int dtype, const int32_t *symbols_d, const int64_t *ranges_d,
+                                const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1,
+                                int R, int V, int blank, int lattice_type, double delay_penalty,
+                                const float *grad_costs_d /* [B] or NULL */, void *grads_d,
+                                const void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream);
+
+int wr_rnnt_prune_ranges_cols(const float *px_grad_d, int px_cols, const float *py_grad_d,
+                              const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1, int R,
+                              int64_t *ranges_d /* [B,T,R] out */, void *stream);
 
 /* CTC forced alignment: Viterbi over the T x (2S+1) lattice, replacing
  * forced_align, wenet/utils/ctc_util.py:27-83 (CLI wenet/bin/alignment.py:215).  logits [B, Tmax, V]: pre-softmax

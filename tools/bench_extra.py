@@ -488,6 +488,19 @@ def bench_align(args):
             print(json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in rec.items()}), flush=True)
 
 
+def lattice_variants(args):
+    """{suffix: keywords} of the k2 losses' lattice forms to time beside the regular one in the same run (simple, smoothed,
+    pruned): --rnnt-type modified adds "_modified", --delay-penalty x adds "_regular_pen", both add "_modified_pen" too."""
+    out = {}
+    if args.rnnt_type != "regular":
+        out["_" + args.rnnt_type] = {"rnnt_type": args.rnnt_type}
+    if args.delay_penalty > 0:
+        out["_regular_pen"] = {"delay_penalty": args.delay_penalty}
+        if args.rnnt_type != "regular":
+            out["_" + args.rnnt_type + "_pen"] = {"rnnt_type": args.rnnt_type, "delay_penalty": args.delay_penalty}
+    return out
+
+
 def bench_simple(args):
     """The additive-joiner loss step (rnnt_loss_simple forward + backward) beside the composite it replaces:
     am.unsqueeze(2) + lm.unsqueeze(1) -> rnnt_loss, fp32, which writes and re-reads a (B,T,U+1,V) tensor.  N(0,1) inputs,
@@ -516,7 +529,16 @@ def bench_simple(args):
         loss.backward()
         return loss
 
+    def variant(kw):
+        def run():
+            am.grad = lm.grad = None
+            loss = w.k2.rnnt_loss_simple(lm, am, sy, 0, reduction="mean", **kw)
+            loss.backward()
+            return loss
+        return run
+
     fns = {"simple": simple} if args.only == "simple" else {"simple": simple, "composite": composite}
+    fns.update({"simple" + sfx: variant(kw) for sfx, kw in lattice_variants(args).items()})
     peak, loss = {}, {}
     for name, fn in fns.items():                       # warm-up, and the memory peak of one step
         fn()
@@ -545,6 +567,11 @@ def bench_simple(args):
                     "composite_ms_min_max": [round(min(times["composite"]), 3), round(max(times["composite"]), 3)],
                     "composite_peak_mib": round(peak["composite"] / 2**20, 1), "composite_loss": loss["composite"],
                     "composite_over_simple": round(med["composite"] / med["simple"], 1)})
+    for name in fns:
+        if name not in ("simple", "composite"):
+            rec.update({name + "_ms": round(med[name], 3),
+                        name + "_ms_min_max": [round(min(times[name]), 3), round(max(times[name]), 3)],
+                        name + "_peak_mib": round(peak[name] / 2**20, 1), name + "_loss": loss[name]})
     print(json.dumps(rec), flush=True)
 
 
@@ -574,6 +601,8 @@ def bench_smoothed(args):
            "smoothed_0.1_0.1": step(lambda: w.rnnt_loss_smoothed(lm, am, sy, 0, 0.1, 0.1, reduction="mean"))}
     if args.only:
         fns = {k: v for k, v in fns.items() if k in args.only.split(",")}
+    for sfx, kw in lattice_variants(args).items():     # the icefall setting on the other lattice forms
+        fns["smoothed_0.25_0" + sfx] = step(lambda kw=kw: w.k2.rnnt_loss_smoothed(lm, am, sy, 0, 0.25, 0.0, reduction="mean", **kw))
     loss = {}
     for name, fn in fns.items():                       # warm-up
         fn()
@@ -672,9 +701,31 @@ def bench_pruned(args):
         loss.backward()
         return loss
 
+    def loss_pruned_variant(kw):
+        def run():
+            band.grad = None
+            loss = w.rnnt_loss_pruned(band, sy, ranges, 0, reduction="mean", **kw)
+            loss.backward()
+            return loss
+        return run
+
+    def step_pruned_variant(kw):
+        def run():
+            clear()
+            simple, (px, py) = w.k2.rnnt_loss_simple(lm_head(pred), am_head(enc), sy, 0, boundary=boundary,
+                                                     reduction="mean", return_grad=True, **kw)
+            rg = w.k2.get_rnnt_prune_ranges(px, py, boundary, R)
+            loss = w.rnnt_loss_pruned(joint.forward_pruned(enc, pred, rg), sy, rg, 0, boundary=boundary, reduction="mean",
+                                      **kw)
+            (loss + 0.5 * simple).backward()
+            return loss
+        return run
+
     fns = {"loss_pruned": loss_pruned, "step_pruned": step_pruned}
     if not only:
         fns.update({"loss_full": loss_full, "step_full": step_full})
+    for sfx, kw in lattice_variants(args).items():
+        fns.update({"loss_pruned" + sfx: loss_pruned_variant(kw), "step_pruned" + sfx: step_pruned_variant(kw)})
     peak, loss = {}, {}
     for name, fn in fns.items():                       # warm-up, and the memory peak of one step
         fn()
@@ -716,6 +767,10 @@ if __name__ == "__main__":
     ap.add_argument("--V", type=int, default=5000)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--R", type=int, default=5, help="pruned: label positions per frame (s_range)")
+    ap.add_argument("--rnnt-type", default="regular", choices=["regular", "modified"],
+                    help="simple, smoothed, pruned: also time this lattice type beside the regular form")
+    ap.add_argument("--delay-penalty", type=float, default=0.0,
+                    help="simple, smoothed, pruned: also time this delay penalty beside the regular form")
     ap.add_argument("--dw", action="store_true", help="joint: also time the library fp32 GEMM on the three contractions (yardstick)")
     ap.add_argument("--fwd-only", action="store_true", help="joint: stop after the exact forward sweep")
     ap.add_argument("--ragged", action="store_true", help="step: frames in [0.8 T, T] sorted, labels in [U/3, U]")

@@ -24,6 +24,7 @@ _HASH_PATH = LIB_PATH + ".srchash"
 API_VERSION = 3              # include/wr_api.h WR_API_VERSION this binding was written against
 WR_F32, WR_F16, WR_BF16 = 0, 1, 2
 # wr_activation codes (include/wr_api.h), keyed by the names of wenet/utils/common.py:228-242 get_activation
+LATTICES = {"regular": 0, "modified": 1}          # wr_lattice codes (include/wr_api.h), keyed by k2's rnnt_type
 ACTIVATIONS = {"tanh": 0, "relu": 1, "hardtanh": 2, "selu": 3, "swish": 4, "gelu": 5}
 
 _lock = threading.Lock()
@@ -96,7 +97,7 @@ def _build_locked(build_dir: str, verbose: bool) -> str:
 
 
 # name -> (restype, argtypes); must list every symbol include/wr_api.h declares.
-_vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+_vp, _i, _f, _sz, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_double
 SIGNATURES = {
     "wr_api_version": (_i, []),
     "wr_last_error": (ctypes.c_char_p, []),
@@ -120,6 +121,13 @@ SIGNATURES = {
     "wr_rnnt_prune_scatter": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "wr_rnnt_pruned_stats": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "wr_rnnt_pruned_grad": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "wr_rnnt_lattice_sweeps": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _vp, _vp, _sz, _vp]),
+    "wr_rnnt_lattice_export": (_i, [_vp, _sz, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "wr_rnnt_smoothed_grad_lattice": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _sz, _vp, _sz, _vp]),
+    "wr_rnnt_pruned_grad_lattice": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp, _sz,
+                                         _vp]),
+    "wr_rnnt_prune_ranges_cols": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "wr_ctc_workspace_bytes": (_sz, [_i, _i, _i]),
     "wr_ctc_loss_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "wr_ctc_loss_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -13,6 +13,7 @@
 //                         read at u = ranges[b,t,r].  HBM-bound: 3 * sizeof(T) * V bytes per valid row in total.
 // Between the two loss kernels the lattice sweeps of rnnt_loss.hip run unchanged: a cell outside the band carries -inf
 // on both arcs, so no path crosses it.
+#include "rnnt_lattice.hpp"
 #include "row_stream.hpp"
 #include "wr_common.hpp"
 
@@ -46,10 +47,11 @@ __device__ __forceinline__ int block_suffix_min(int v, int carry, int *sw)
 
 // px [B, U1-1, T+1] (emit occupancies), py [B, U1, T] (blank occupancies), both t-minor: a wave reads 64 consecutive
 // frames of one label row.  Frames are visited in chunks of kRangeThreads from the last chunk to the first, so both
-// suffix minima carry one running value from chunk to chunk.
+// suffix minima carry one running value from chunk to chunk.  `px_cols` is px's row length: T + 1 (the regular lattice's
+// layout) or T (the modified lattice's); only columns t < T are read either way.
 __global__ __launch_bounds__(kRangeThreads) void prune_ranges_kernel(
     const float *__restrict__ px, const float *__restrict__ py, const int32_t *__restrict__ tlens_frames,
-    const int32_t *__restrict__ ulens, int T, int U1, int R, long long *__restrict__ ranges)
+    const int32_t *__restrict__ ulens, int T, int U1, int R, int px_cols, long long *__restrict__ ranges)
 {
     __shared__ int sw[kRangeThreads / kWave];
     __shared__ int s_sh[kRangeThreads];
@@ -60,7 +62,7 @@ __global__ __launch_bounds__(kRangeThreads) void prune_ranges_kernel(
     const int pad = max(Ub - R + 1, 0);
     const int n0 = U1 - R;                        // window starts u0 = 0 .. n0
     const float *pyb = py + (size_t)b * U1 * T;
-    const float *pxb = px + (size_t)b * (U1 - 1) * (T + 1);     // never dereferenced when U1 == 1 (n0 == 0)
+    const float *pxb = px + (size_t)b * (U1 - 1) * px_cols;     // never dereferenced when U1 == 1 (n0 == 0)
     int carry_s = 0x7fffffff, carry_x = 0x7fffffff;
     const int nchunks = (T + kRangeThreads - 1) / kRangeThreads;
     for (int c = nchunks - 1; c >= 0; --c) {
@@ -77,7 +79,7 @@ __global__ __launch_bounds__(kRangeThreads) void prune_ranges_kernel(
                 for (int u0 = 0; u0 <= n0; ++u0) {
                     double sc = (double)pyb[(size_t)u0 * T + t];
                     for (int r = 1; r < R; ++r) sc = sc + (double)pyb[(size_t)(u0 + r) * T + t];
-                    if (u0 > 0) sc = sc - (double)pxb[(size_t)(u0 - 1) * (T + 1) + t];
+                    if (u0 > 0) sc = sc - (double)pxb[(size_t)(u0 - 1) * px_cols + t];
                     if (u0 == 0 || sc > best) { best = sc; s = u0; }      // the lowest u0 wins ties
                 }
             }
@@ -243,12 +245,15 @@ __global__ __launch_bounds__(256) void pruned_lse_kernel(
 // The streamed path of rnnt_grad_kernel (rnnt_loss.hip) on band rows.  One difference: a label equal to the blank has
 // both its terms subtracted (the derivative of the loss as written, which is what k2's autograd gives) instead of the
 // first match of torchaudio's case chain.
-template <typename T, bool NT, bool NTS, int UN>
+// LAT (rnnt_lattice.hpp) changes the per-row preamble only, and it is wave-uniform: where the lattice values of the cell
+// and of its two successors are read, and the delay penalty `dp` inside the label term (the stored label arc has it).
+template <typename T, bool NT, bool NTS, int UN, int LAT>
 __global__ __launch_bounds__(256) void pruned_grad_kernel(
     const T *logits, const int32_t *__restrict__ symbols, const long long *__restrict__ ranges,
     const int32_t *__restrict__ llens, const int32_t *__restrict__ tlens, long nrows, int Tmax, int U1max, int R, int V,
     int blank, int S, const double *__restrict__ alpha_skew, const double *__restrict__ beta_skew,
-    const float *__restrict__ denom, const double *__restrict__ cost_ws, const float *__restrict__ grad_costs, T *grads)
+    const float *__restrict__ denom, const double *__restrict__ cost_ws, const float *__restrict__ grad_costs, T *grads,
+    double dp)
 {
     typedef typename VecOf<T>::type vec_t;
     constexpr int N = VecOf<T>::N;
@@ -286,21 +291,27 @@ __global__ __launch_bounds__(256) void pruned_grad_kernel(
         const bool final_cell = t == T_ - 1 && u == U;
         const bool has_b1 = t < T_ - 1;
         const bool blank_special = final_cell || has_b1;
-        const double al = alpha_skew[dbase + (size_t)s * U1max + u];
-        const double be = beta_skew[dbase + (size_t)s * U1max + u];
+        const size_t k = dbase + lat_idx<LAT>(t, u, U1max);
+        const double al = alpha_skew[k];
+        const double be = beta_skew[k];
         const double cost = cost_ws[b];
         const float d = denom[(size_t)bt * U1max + u];
-        const double b1 = has_b1 ? beta_skew[dbase + (size_t)(s + 1) * U1max + u] : 0.0;
+        double b1;
+        if (LAT == kLatModified) b1 = has_b1 ? beta_skew[k + U1max] : 0.0;
+        else b1 = has_b1 ? beta_skew[dbase + (size_t)(s + 1) * U1max + u] : 0.0;
         int lab = -1;
         double b2 = 0.0;
         if (u < U) {
             lab = symbols[(size_t)b * (U1max - 1) + u];
-            b2 = beta_skew[dbase + (size_t)(s + 1) * U1max + (u + 1)];
+            if (LAT == kLatModified)     // the label arc leads to (t+1, u+1); beta(T_b, .) is 0 at U_b, -inf elsewhere
+                b2 = has_b1 ? beta_skew[k + U1max + 1] : (u == U - 1 ? 0.0 : (double)kNegInf);
+            else
+                b2 = beta_skew[dbase + (size_t)(s + 1) * U1max + (u + 1)];
         }
         const double cmd = al + cost - (double)d;      // g = logit + cm
         const float c2 = (float)(cmd + be) * kLog2e;
         const float blank_sub = final_cell ? (float)cmd : (has_b1 ? (float)(cmd + b1) : 0.f);
-        const float lab_sub = (float)(cmd + b2);
+        const float lab_sub = LAT == kLatRegular ? (float)(cmd + b2) : (float)((cmd + b2) + delay_pen(dp, T_, t));
         const int blk = blank_special ? blank : -1;
 
         auto fix = [&](float val, float x, int v) -> float {
@@ -393,19 +404,37 @@ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 
 using namespace wr;
 
+static int prune_ranges_impl(const char *what, const float *px_grad_d, int px_cols, const float *py_grad_d,
+                             const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1, int R,
+                             int64_t *ranges_d, void *stream)
+{
+    if (int rc = check_band(what, B, T, U1, R)) return rc;
+    WR_REQUIRE(px_cols == T || px_cols == T + 1, WR_EINVAL, "%s: px_grad rows hold T = %d or T + 1 frames (got %d)", what, T,
+               px_cols);
+    WR_REQUIRE(py_grad_d && logit_lengths_d && target_lengths_d && ranges_d, WR_EINVAL, "%s: null pointer argument", what);
+    WR_REQUIRE(px_grad_d || U1 == 1, WR_EINVAL, "%s: px_grad is null", what);
+    WR_REQUIRE(aligned16(ranges_d), WR_EINVAL, "%s: ranges must be 16-byte aligned", what);
+    hipLaunchKernelGGL(prune_ranges_kernel, dim3(B), dim3(kRangeThreads), 0, static_cast<hipStream_t>(stream), px_grad_d,
+                       py_grad_d, logit_lengths_d, target_lengths_d, T, U1, R, px_cols,
+                       reinterpret_cast<long long *>(ranges_d));
+    WR_CHECK_LAUNCH("prune_ranges_kernel");
+    return WR_OK;
+}
+
 extern "C" int wr_rnnt_prune_ranges(const float *px_grad_d, const float *py_grad_d, const int32_t *logit_lengths_d,
                                     const int32_t *target_lengths_d, int B, int T, int U1, int R, int64_t *ranges_d,
                                     void *stream)
 {
-    if (int rc = check_band("rnnt_prune_ranges", B, T, U1, R)) return rc;
-    WR_REQUIRE(py_grad_d && logit_lengths_d && target_lengths_d && ranges_d, WR_EINVAL,
-               "rnnt_prune_ranges: null pointer argument");
-    WR_REQUIRE(px_grad_d || U1 == 1, WR_EINVAL, "rnnt_prune_ranges: px_grad is null");
-    WR_REQUIRE(aligned16(ranges_d), WR_EINVAL, "rnnt_prune_ranges: ranges must be 16-byte aligned");
-    hipLaunchKernelGGL(prune_ranges_kernel, dim3(B), dim3(kRangeThreads), 0, static_cast<hipStream_t>(stream), px_grad_d,
-                       py_grad_d, logit_lengths_d, target_lengths_d, T, U1, R, reinterpret_cast<long long *>(ranges_d));
-    WR_CHECK_LAUNCH("prune_ranges_kernel");
-    return WR_OK;
+    return prune_ranges_impl("rnnt_prune_ranges", px_grad_d, T + 1, py_grad_d, logit_lengths_d, target_lengths_d, B, T, U1,
+                             R, ranges_d, stream);
+}
+
+extern "C" int wr_rnnt_prune_ranges_cols(const float *px_grad_d, int px_cols, const float *py_grad_d,
+                                         const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T,
+                                         int U1, int R, int64_t *ranges_d, void *stream)
+{
+    return prune_ranges_impl("rnnt_prune_ranges_cols", px_grad_d, px_cols, py_grad_d, logit_lengths_d, target_lengths_d, B,
+                             T, U1, R, ranges_d, stream);
 }
 
 extern "C" int wr_rnnt_prune_gather(const void *am_d, const void *lm_d, const int64_t *ranges_d, int dtype, int B, int T,
@@ -510,36 +539,69 @@ extern "C" int wr_rnnt_pruned_stats(const void *logits_d, int dtype, const int32
     return WR_OK;
 }
 
-extern "C" int wr_rnnt_pruned_grad(const void *logits_d, int dtype, const int32_t *symbols_d, const int64_t *ranges_d,
-                                   const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1,
-                                   int R, int V, int blank, const float *grad_costs_d, void *grads_d,
-                                   const void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream)
+// wr_rnnt_pruned_grad (lat = kLatRegular) and wr_rnnt_pruned_grad_lattice
+static int pruned_grad_impl(const char *what, const void *logits_d, int dtype, const int32_t *symbols_d,
+                            const int64_t *ranges_d, const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B,
+                            int T, int U1, int R, int V, int blank, int lat, double delay_penalty,
+                            const float *grad_costs_d, void *grads_d, const void *rnnt_workspace_d,
+                            size_t rnnt_workspace_bytes, void *stream)
 {
-    if (int rc = check_loss("rnnt_pruned_grad", B, T, U1, R, V, blank, dtype)) return rc;
+    if (int rc = check_loss(what, B, T, U1, R, V, blank, dtype)) return rc;
     WR_REQUIRE(logits_d && ranges_d && logit_lengths_d && target_lengths_d && grads_d && rnnt_workspace_d, WR_EINVAL,
-               "rnnt_pruned_grad: null pointer argument");
-    WR_REQUIRE(symbols_d || U1 == 1, WR_EINVAL, "rnnt_pruned_grad: symbols is null");
+               "%s: null pointer argument", what);
+    WR_REQUIRE(symbols_d || U1 == 1, WR_EINVAL, "%s: symbols is null", what);
     WR_REQUIRE(((reinterpret_cast<uintptr_t>(logits_d) ^ reinterpret_cast<uintptr_t>(grads_d)) & 15) == 0, WR_EINVAL,
-               "rnnt_pruned_grad: logits and grads must sit at the same offset within a 16-byte line");
+               "%s: logits and grads must sit at the same offset within a 16-byte line", what);
     const RnntWs w = rnnt_ws_layout(B, T, U1);
-    WR_REQUIRE(rnnt_workspace_bytes >= w.total, WR_EWORKSPACE, "rnnt_pruned_grad: workspace %zu < required %zu",
+    WR_REQUIRE(rnnt_workspace_bytes >= w.total, WR_EWORKSPACE, "%s: workspace %zu < required %zu", what,
                rnnt_workspace_bytes, w.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const char *ws = static_cast<const char *>(rnnt_workspace_d);
     const long nrows = (long)B * T * R;
     const size_t row_bytes = (size_t)V * (dtype == WR_F32 ? 4 : 2);
     const dim3 grid(band_grid(nrows, row_bytes, 68 * 1024));
-#define WR_LAUNCH_PGRAD(T_)                                                                                            \
-    hipLaunchKernelGGL((pruned_grad_kernel<T_, true, true, 16>), grid, dim3(256), 0, st,                                \
+    const LatView lv = lattice_view(w, ws, lat == kLatModified);
+#define WR_LAUNCH_PGRAD_L(T_, LAT)                                                                                     \
+    hipLaunchKernelGGL((pruned_grad_kernel<T_, true, true, 16, LAT>), grid, dim3(256), 0, st,                           \
                        static_cast<const T_ *>(logits_d), symbols_d, reinterpret_cast<const long long *>(ranges_d),    \
-                       logit_lengths_d, target_lengths_d, nrows, T, U1, R, V, blank, w.S,                              \
-                       reinterpret_cast<const double *>(ws + w.alpha_off), reinterpret_cast<const double *>(ws + w.beta_off), \
+                       logit_lengths_d, target_lengths_d, nrows, T, U1, R, V, blank, w.S, lv.alpha, lv.beta,           \
                        reinterpret_cast<const float *>(ws + w.denom_off), reinterpret_cast<const double *>(ws + w.cost_off), \
-                       grad_costs_d, static_cast<T_ *>(grads_d))
+                       grad_costs_d, static_cast<T_ *>(grads_d), delay_penalty)
+#define WR_LAUNCH_PGRAD(T_)                                                                                            \
+    do {                                                                                                               \
+        if (lat == kLatModified) WR_LAUNCH_PGRAD_L(T_, kLatModified);                                                  \
+        else if (lat == kLatRegularPen) WR_LAUNCH_PGRAD_L(T_, kLatRegularPen);                                         \
+        else WR_LAUNCH_PGRAD_L(T_, kLatRegular);                                                                       \
+    } while (0)
     if (dtype == WR_F32) WR_LAUNCH_PGRAD(float);
     else if (dtype == WR_F16) WR_LAUNCH_PGRAD(_Float16);
     else WR_LAUNCH_PGRAD(__bf16);
 #undef WR_LAUNCH_PGRAD
+#undef WR_LAUNCH_PGRAD_L
     WR_CHECK_LAUNCH("pruned_grad_kernel");
     return WR_OK;
+}
+
+extern "C" int wr_rnnt_pruned_grad(const void *logits_d, int dtype, const int32_t *symbols_d, const int64_t *ranges_d,
+                                   const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1,
+                                   int R, int V, int blank, const float *grad_costs_d, void *grads_d,
+                                   const void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream)
+{
+    return pruned_grad_impl("rnnt_pruned_grad", logits_d, dtype, symbols_d, ranges_d, logit_lengths_d, target_lengths_d, B,
+                            T, U1, R, V, blank, kLatRegular, 0.0, grad_costs_d, grads_d, rnnt_workspace_d,
+                            rnnt_workspace_bytes, stream);
+}
+
+extern "C" int wr_rnnt_pruned_grad_lattice(const void *logits_d, int dtype, const int32_t *symbols_d,
+                                           const int64_t *ranges_d, const int32_t *logit_lengths_d,
+                                           const int32_t *target_lengths_d, int B, int T, int U1, int R, int V, int blank,
+                                           int lattice_type, double delay_penalty, const float *grad_costs_d,
+                                           void *grads_d, const void *rnnt_workspace_d, size_t rnnt_workspace_bytes,
+                                           void *stream)
+{
+    if (int rc = lattice_check("rnnt_pruned_grad_lattice", lattice_type, delay_penalty)) return rc;
+    const int lat = lattice_type == WR_LATTICE_MODIFIED ? kLatModified : (delay_penalty > 0.0 ? kLatRegularPen : kLatRegular);
+    return pruned_grad_impl("rnnt_pruned_grad_lattice", logits_d, dtype, symbols_d, ranges_d, logit_lengths_d,
+                            target_lengths_d, B, T, U1, R, V, blank, lat, delay_penalty, grad_costs_d, grads_d,
+                            rnnt_workspace_d, rnnt_workspace_bytes, stream);
 }

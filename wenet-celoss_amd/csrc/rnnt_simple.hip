@@ -32,6 +32,7 @@
 // (am's and lm's peaks on different symbols, both tall) raises the flag, and every cell is then redone by the direct
 // kernels -- in the gradient too, where e^{ma+ml-denom} = 1/S would overflow for the same cells.  Nothing is read back
 // on the host.  No float atomics anywhere: every sum has a fixed order, so results are bit-identical run to run.
+#include "rnnt_lattice.hpp"
 #include "row_stream.hpp"
 #include "wr_common.hpp"
 
@@ -233,6 +234,10 @@ __global__ __launch_bounds__(256) void simple_stats_direct_kernel(
 // One thread per cell.  Exponents are formed in fp64 (the lattice state's precision) and only then rounded, as
 // rnnt_grad_kernel forms its own.  g = G * grad_costs[b]; with the flag raised g holds grad_costs[b] * occ instead (the
 // direct gradient kernel's factor; e^{ma+ml-denom} may overflow there).  g is further scaled by `gscale`.
+// LAT: the lattice type (rnnt_lattice.hpp).  kLatModified reads plain rows and a label arc leads to (t+1, u+1): beta of
+// the terminal row T_b is 0 at U_b and -inf elsewhere, so the last frame keeps the blank out of (T_b-1, U_b) and the
+// label out of (T_b-1, U_b-1).  A delay penalty needs nothing here: it is inside the stored label arc.
+template <int LAT>
 __global__ __launch_bounds__(256) void simple_occ_kernel(
     const int32_t *__restrict__ llens, const int32_t *__restrict__ tlens, int B, int T, int U1, int S,
     const double *__restrict__ alpha_skew, const double *__restrict__ beta_skew, const float2 *__restrict__ lp_skew,
@@ -254,16 +259,27 @@ __global__ __launch_bounds__(256) void simple_occ_kernel(
         if (grad_costs) go = grad_costs[b];
         const size_t dbase = (size_t)b * S * U1;
         const int s = t + u;
-        const double al = alpha_skew[dbase + (size_t)s * U1 + u];
-        const double be = beta_skew[dbase + (size_t)s * U1 + u];
+        const size_t k = dbase + lat_idx<LAT>(t, u, U1);
+        const double al = alpha_skew[k];
+        const double be = beta_skew[k];
         const double ac = al + cost_ws[b];                      // cost = -ll
-        const float2 lp = lp_skew[dbase + (size_t)s * U1 + u];
+        const float2 lp = lp_skew[k];
         const double lo = ac + be;                              // log occupancy of the node
         if (*flag != 0) gv = (float)exp(lo);
         else gv = (float)exp(lo + (((double)ma[(size_t)b * T + t] + (double)ml[(size_t)b * U1 + u]) - (double)denom[r]));
-        if (t < Tb - 1) fb = (float)exp(ac + (double)lp.x + beta_skew[dbase + (size_t)(s + 1) * U1 + u]);
-        else if (u == Ub) fb = (float)exp(ac + (double)lp.x);   // the final cell: beta := 0
-        if (u < Ub) fe = (float)exp(ac + (double)lp.y + beta_skew[dbase + (size_t)(s + 1) * U1 + (u + 1)]);
+        if (LAT == kLatModified) {
+            if (t < Tb - 1) {
+                fb = (float)exp(ac + (double)lp.x + beta_skew[k + U1]);
+                if (u < Ub) fe = (float)exp(ac + (double)lp.y + beta_skew[k + U1 + 1]);
+            } else {                                            // the last frame: beta(T_b, .) is 0 at U_b, -inf elsewhere
+                if (u == Ub) fb = (float)exp(ac + (double)lp.x);
+                if (u == Ub - 1) fe = (float)exp(ac + (double)lp.y);
+            }
+        } else {
+            if (t < Tb - 1) fb = (float)exp(ac + (double)lp.x + beta_skew[dbase + (size_t)(s + 1) * U1 + u]);
+            else if (u == Ub) fb = (float)exp(ac + (double)lp.x);   // the final cell: beta := 0
+            if (u < Ub) fe = (float)exp(ac + (double)lp.y + beta_skew[dbase + (size_t)(s + 1) * U1 + (u + 1)]);
+        }
     }
     const float gs = gv * go * gscale;                          // gscale: 1 (exact), or c of the smoothed loss
     g[r] = gs;
@@ -820,7 +836,8 @@ int simple_stats_launch(const float *am_d, const float *lm_d, const int32_t *sym
 int simple_grad_launch(const float *am_d, const float *lm_d, const int32_t *symbols_d, const int32_t *logit_lengths_d,
                        const int32_t *target_lengths_d, int B, int T, int U1, int V, const float *grad_costs_d,
                        float *d_am_d, float *d_lm_d, float *occ_emit_d, float *occ_blank_d, const SimpleWs &sw,
-                       const RnntWs &w, char *sws, const char *ws, float gscale, bool occ_only, hipStream_t st)
+                       const RnntWs &w, char *sws, const char *ws, float gscale, bool occ_only, bool modified,
+                       hipStream_t st)
 {
     const float *ma = reinterpret_cast<const float *>(sws + sw.ma_off), *ml = reinterpret_cast<const float *>(sws + sw.ml_off);
     float *g = reinterpret_cast<float *>(sws + sw.g_off), *gt = reinterpret_cast<float *>(sws + sw.gt_off);
@@ -830,11 +847,15 @@ int simple_grad_launch(const float *am_d, const float *lm_d, const int32_t *symb
     const int32_t *flag = reinterpret_cast<const int32_t *>(ws + w.flag_off);
     const long cells = (long)B * T * U1;
 
-    hipLaunchKernelGGL(simple_occ_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, logit_lengths_d,
-                       target_lengths_d, B, T, U1, w.S, reinterpret_cast<const double *>(ws + w.alpha_off),
-                       reinterpret_cast<const double *>(ws + w.beta_off), reinterpret_cast<const float2 *>(ws + w.lp_off),
-                       denom, reinterpret_cast<const double *>(ws + w.cost_off), ma, ml, grad_costs_d, flag, gscale, g, gt,
-                       ob, oe, occ_emit_d, occ_blank_d);
+    const LatView lv = lattice_view(w, ws, modified);
+#define WR_LAUNCH_OCC(LAT)                                                                                             \
+    hipLaunchKernelGGL((simple_occ_kernel<LAT>), dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, logit_lengths_d, \
+                       target_lengths_d, B, T, U1, w.S, lv.alpha, lv.beta, lv.lp, denom,                               \
+                       reinterpret_cast<const double *>(ws + w.cost_off), ma, ml, grad_costs_d, flag, gscale, g, gt, ob, oe, \
+                       occ_emit_d, occ_blank_d)
+    if (modified) WR_LAUNCH_OCC(kLatModified);
+    else WR_LAUNCH_OCC(kLatRegular);
+#undef WR_LAUNCH_OCC
     WR_CHECK_LAUNCH("simple_occ_kernel");
     if (occ_only) return WR_OK;
     hipLaunchKernelGGL(simple_chain_kernel, dim3(B), dim3(256), 0, st, symbols_d, target_lengths_d, U1, nxt, head);
@@ -933,7 +954,7 @@ extern "C" int wr_rnnt_simple_grad(const float *am_d, const float *lm_d, const i
     char *sws = static_cast<char *>(simple_workspace_d);
     if (int rc = simple_grad_launch(am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, grad_costs_d,
                                     d_am_d, d_lm_d, occ_emit_d, occ_blank_d, sw, w, sws,
-                                    static_cast<const char *>(rnnt_workspace_d), 1.f, false, st))
+                                    static_cast<const char *>(rnnt_workspace_d), 1.f, false, false, st))
         return rc;
     return simple_fix_launch(symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, d_am_d, d_lm_d, sw, sws, 1.f,
                              1.f, false, st);
@@ -1004,12 +1025,14 @@ extern "C" int wr_rnnt_smoothed_stats(const float *am_d, const float *lm_d, cons
     return WR_OK;
 }
 
-extern "C" int wr_rnnt_smoothed_grad(const float *am_d, const float *lm_d, const int32_t *symbols_d,
-                                     const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T,
-                                     int U1, int V, int blank, float lm_only_scale, float am_only_scale,
-                                     const float *grad_costs_d, float *d_am_d, float *d_lm_d, float *occ_emit_d,
-                                     float *occ_blank_d, void *smoothed_workspace_d, size_t smoothed_workspace_bytes,
-                                     const void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream)
+// wr_rnnt_smoothed_grad and wr_rnnt_smoothed_grad_lattice.  On the modified lattice every arc is subtracted at its own
+// symbol whatever the scales (a label equal to the blank has both terms), as under smoothing.
+static int smoothed_grad_impl(const float *am_d, const float *lm_d, const int32_t *symbols_d,
+                              const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1, int V,
+                              int blank, float lm_only_scale, float am_only_scale, const float *grad_costs_d,
+                              float *d_am_d, float *d_lm_d, float *occ_emit_d, float *occ_blank_d,
+                              void *smoothed_workspace_d, size_t smoothed_workspace_bytes, const void *rnnt_workspace_d,
+                              size_t rnnt_workspace_bytes, bool modified, void *stream)
 {
     const float ll = lm_only_scale, la = am_only_scale;
     if (int rc = simple_check("rnnt_smoothed_grad", B, T, U1, V, blank)) return rc;
@@ -1032,7 +1055,7 @@ extern "C" int wr_rnnt_smoothed_grad(const float *am_d, const float *lm_d, const
     const float c = smooth ? (float)(1.0 - (double)ll - (double)la) : 1.f;
     if (int rc = simple_grad_launch(am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, grad_costs_d,
                                     d_am_d, d_lm_d, occ_emit_d, occ_blank_d, mw.s, w, sws,
-                                    static_cast<const char *>(rnnt_workspace_d), c, occ_only, st))
+                                    static_cast<const char *>(rnnt_workspace_d), c, occ_only, modified, st))
         return rc;
     if (occ_only) return WR_OK;
     if (smooth) {
@@ -1071,5 +1094,32 @@ extern "C" int wr_rnnt_smoothed_grad(const float *am_d, const float *lm_d, const
         }
     }
     return simple_fix_launch(symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, d_am_d, d_lm_d, mw.s, sws,
-                             smooth ? c + la : 1.f, smooth ? c + ll : 1.f, smooth, st);
+                             smooth ? c + la : 1.f, smooth ? c + ll : 1.f, smooth || modified, st);
+}
+
+extern "C" int wr_rnnt_smoothed_grad(const float *am_d, const float *lm_d, const int32_t *symbols_d,
+                                     const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T,
+                                     int U1, int V, int blank, float lm_only_scale, float am_only_scale,
+                                     const float *grad_costs_d, float *d_am_d, float *d_lm_d, float *occ_emit_d,
+                                     float *occ_blank_d, void *smoothed_workspace_d, size_t smoothed_workspace_bytes,
+                                     const void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream)
+{
+    return smoothed_grad_impl(am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, lm_only_scale,
+                              am_only_scale, grad_costs_d, d_am_d, d_lm_d, occ_emit_d, occ_blank_d, smoothed_workspace_d,
+                              smoothed_workspace_bytes, rnnt_workspace_d, rnnt_workspace_bytes, false, stream);
+}
+
+extern "C" int wr_rnnt_smoothed_grad_lattice(const float *am_d, const float *lm_d, const int32_t *symbols_d,
+                                             const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B,
+                                             int T, int U1, int V, int blank, float lm_only_scale, float am_only_scale,
+                                             int lattice_type, const float *grad_costs_d, float *d_am_d, float *d_lm_d,
+                                             float *occ_emit_d, float *occ_blank_d, void *smoothed_workspace_d,
+                                             size_t smoothed_workspace_bytes, const void *rnnt_workspace_d,
+                                             size_t rnnt_workspace_bytes, void *stream)
+{
+    if (int rc = lattice_check("rnnt_smoothed_grad_lattice", lattice_type, 0.0)) return rc;
+    return smoothed_grad_impl(am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, lm_only_scale,
+                              am_only_scale, grad_costs_d, d_am_d, d_lm_d, occ_emit_d, occ_blank_d, smoothed_workspace_d,
+                              smoothed_workspace_bytes, rnnt_workspace_d, rnnt_workspace_bytes,
+                              lattice_type == WR_LATTICE_MODIFIED, stream);
 }

@@ -1,5 +1,5 @@
 """Pruned RNN-T training: k2's ``get_rnnt_prune_ranges`` / ``do_rnnt_pruning`` / ``rnnt_loss_pruned`` for the regular
-lattice type, backed by the HIP kernels of csrc/rnnt_pruned.hip ("Pruned RNN-T training").
+and the modified lattice types, backed by the HIP kernels of csrc/rnnt_pruned.hip ("Pruned RNN-T training").
 
 The additive-joiner loss (rnnt_simple.py) is the cheap first pass of the k2 / icefall recipe; its arc occupancies choose,
 per frame, a band of ``s_range`` label positions, and the real joiner and the real loss are evaluated on that band only:
@@ -8,7 +8,8 @@ per frame, a band of ``s_range`` label positions, and the real joiner and the re
   do_rnnt_pruning         the joiner's two addends gathered onto the band: (B, T, R, C) each, differentiable
   rnnt_loss_pruned        the RNN-T loss of logits (B, T, R, V) given on the band (one autograd node)
 
-Not offered: ``rnnt_type`` other than "regular" and ``delay_penalty`` (the arguments do not exist here).
+``rnnt_loss_pruned`` takes ``rnnt_type="modified"`` and ``delay_penalty`` (rnnt_lattice.py); `k2.get_rnnt_prune_ranges`
+(k2.py) also takes the (B, U, T) ``px_grad`` of a modified-lattice simple loss.  Not offered: ``rnnt_type="constrained"``.
 """
 from __future__ import annotations
 
@@ -17,6 +18,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from . import rnnt_lattice as _lat
 
 
 def _check_boundary_rows(rows, B: int, T: int, U: int, what: str) -> None:
@@ -51,21 +53,33 @@ def _require_device(what: str, *tensors) -> None:
 
 def get_rnnt_prune_ranges(px_grad: torch.Tensor, py_grad: torch.Tensor, boundary: torch.Tensor, s_range: int
                           ) -> torch.Tensor:
+    """`prune_ranges` for the regular lattice's ``px_grad`` (B, U, T+1) only, ``s_range >= 2`` (the rule is spelled out
+    there); `k2.get_rnnt_prune_ranges` also takes the modified lattice's (B, U, T)."""
+    return prune_ranges(px_grad, py_grad, boundary, s_range, modified_px=False)
+
+
+def prune_ranges(px_grad: torch.Tensor, py_grad: torch.Tensor, boundary: torch.Tensor, s_range: int,
+                 modified_px: bool = True) -> torch.Tensor:
     """k2.get_rnnt_prune_ranges(px_grad, py_grad, boundary, s_range) -> ranges (B, T, R) int64, R = min(s_range, U + 1).
 
     px_grad (B, U, T+1) and py_grad (B, U+1, T) are the arc occupancies ``rnnt_loss_simple(..., return_grad=True)``
     returns; ``boundary`` (B, 4) int64 rows ``(0, 0, U_b, T_b)`` (None = full lengths).  Per frame the band starts at the
     label position u0 whose window ``sum_{r<R} py[u0+r, t] - px[u0-1, t]`` is largest (float64, lowest u0 on ties), frames
     from T_b - 1 on start at ``max(U_b - R + 1, 0)``, and the starts are then made monotone with steps of at most one
-    (the contract is spelled out in include/wr_api.h).  ``ranges[b, t, r] = s_begin[b, t] + r``."""
+    (the contract is spelled out in include/wr_api.h).  ``ranges[b, t, r] = s_begin[b, t] + r``.
+
+    With ``modified_px`` px_grad may also be (B, U, T), what the losses return with ``rnnt_type="modified"``: the score
+    reads only columns ``t < T``, so the rule is the same; ``s_range >= 1`` is then accepted (k2's rule for that lattice),
+    with the (B, U, T+1) form it stays ``>= 2``."""
     what = "get_rnnt_prune_ranges"
-    if int(s_range) < 2:
-        raise ValueError(f"{what}: s_range must be at least 2 (got {s_range})")
     if px_grad.dim() != 3 or py_grad.dim() != 3:
-        raise ValueError(f"{what}: px_grad must be (B, U, T+1) and py_grad (B, U+1, T)")
+        raise ValueError(f"{what}: px_grad must be (B, U, T+1) or (B, U, T) and py_grad (B, U+1, T)")
     B, U1, T = py_grad.shape
-    if tuple(px_grad.shape) != (B, U1 - 1, T + 1):
+    if tuple(px_grad.shape) not in (((B, U1 - 1, T + 1), (B, U1 - 1, T)) if modified_px else ((B, U1 - 1, T + 1),)):
         raise ValueError(f"{what}: px_grad {tuple(px_grad.shape)} does not match py_grad {tuple(py_grad.shape)}")
+    px_cols = int(px_grad.shape[2])
+    if int(s_range) < (1 if px_cols == T else 2):
+        raise ValueError(f"{what}: s_range must be at least {1 if px_cols == T else 2} (got {s_range})")
     if B < 1 or T < 1:
         raise ValueError(f"{what}: empty batch or no frames")
     _require_device(what, px_grad, py_grad)
@@ -77,8 +91,12 @@ def get_rnnt_prune_ranges(px_grad: torch.Tensor, py_grad: torch.Tensor, boundary
     px = px_grad.detach().to(torch.float32).contiguous()
     py = py_grad.detach().to(torch.float32).contiguous()
     ranges = torch.empty(B, T, R, dtype=torch.int64, device=dev)
-    _lib.call("wr_rnnt_prune_ranges", px if U1 > 1 else None, py, bd[:, 3].to(torch.int32).contiguous(),
-              bd[:, 2].to(torch.int32).contiguous(), B, T, U1, R, ranges, device=dev)
+    if px_cols == T + 1:
+        _lib.call("wr_rnnt_prune_ranges", px if U1 > 1 else None, py, bd[:, 3].to(torch.int32).contiguous(),
+                  bd[:, 2].to(torch.int32).contiguous(), B, T, U1, R, ranges, device=dev)
+    else:
+        _lib.call("wr_rnnt_prune_ranges_cols", px if U1 > 1 else None, px_cols, py, bd[:, 3].to(torch.int32).contiguous(),
+                  bd[:, 2].to(torch.int32).contiguous(), B, T, U1, R, ranges, device=dev)
     return ranges
 
 
@@ -182,7 +200,7 @@ def _prepare(logits, symbols, ranges, termination_symbol, boundary, what: str):
     return sy, bd[:, 3].to(torch.int32).contiguous(), bd[:, 2].to(torch.int32).contiguous(), blank, rg
 
 
-def _stats_and_sweeps(logits, sy, rg, ll, tl, blank):
+def _stats_and_sweeps(logits, sy, rg, ll, tl, blank, lat=0, pen=0.0):
     """Row statistics of the band into a fresh RNN-T workspace, then the lattice sweeps: (costs float32, workspace)."""
     B, T, R, V = logits.shape
     U1 = sy.shape[1] + 1
@@ -191,20 +209,23 @@ def _stats_and_sweeps(logits, sy, rg, ll, tl, blank):
     costs = torch.empty(B, dtype=torch.float32, device=dev)
     _lib.call("wr_rnnt_pruned_stats", logits, _lib.dtype_code(logits.dtype), sy if U1 > 1 else None, rg, ll, tl, B, T, U1, R,
               V, blank, ws, ws.numel(), device=dev)
-    _lib.call("wr_rnnt_loss_sweeps", ll, tl, B, T, U1, costs, ws, ws.numel(), device=dev)
+    if _lat.is_default(lat, pen):
+        _lib.call("wr_rnnt_loss_sweeps", ll, tl, B, T, U1, costs, ws, ws.numel(), device=dev)
+    else:
+        _lib.call("wr_rnnt_lattice_sweeps", ll, tl, B, T, U1, lat, pen, costs, ws, ws.numel(), device=dev)
     return costs, ws
 
 
 class _RNNTPrunedFn(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda")          # fp16/bf16 logits are handled natively (fp32 arithmetic inside)
-    def forward(ctx, logits, sy, rg, ll, tl, blank):
+    def forward(ctx, logits, sy, rg, ll, tl, blank, lat=0, pen=0.0):
         logits = logits.contiguous()
         if logits.data_ptr() % 16:                     # a view at an odd storage offset: the gradient kernel needs logits
             logits = logits.clone()                    # and grads at the same 16-byte phase, and fresh tensors are aligned
-        costs, ws = _stats_and_sweeps(logits, sy, rg, ll, tl, blank)
+        costs, ws = _stats_and_sweeps(logits, sy, rg, ll, tl, blank, lat, pen)
         ctx.save_for_backward(logits, sy, rg, ll, tl, ws)
-        ctx.blank = blank
+        ctx.blank, ctx.lat, ctx.pen = blank, lat, pen
         return costs
 
     @staticmethod
@@ -215,14 +236,19 @@ class _RNNTPrunedFn(torch.autograd.Function):
         U1 = sy.shape[1] + 1
         grads = torch.empty_like(logits)
         gc = grad_costs.to(torch.float32).contiguous()
-        _lib.call("wr_rnnt_pruned_grad", logits, _lib.dtype_code(logits.dtype), sy if U1 > 1 else None, rg, ll, tl, B, T, U1,
-                  R, V, ctx.blank, gc, grads, ws, ws.numel(), device=logits.device)
-        return grads, None, None, None, None, None
+        if _lat.is_default(ctx.lat, ctx.pen):
+            _lib.call("wr_rnnt_pruned_grad", logits, _lib.dtype_code(logits.dtype), sy if U1 > 1 else None, rg, ll, tl, B, T,
+                      U1, R, V, ctx.blank, gc, grads, ws, ws.numel(), device=logits.device)
+        else:
+            _lib.call("wr_rnnt_pruned_grad_lattice", logits, _lib.dtype_code(logits.dtype), sy if U1 > 1 else None, rg, ll,
+                      tl, B, T, U1, R, V, ctx.blank, ctx.lat, ctx.pen, gc, grads, ws, ws.numel(), device=logits.device)
+        return (grads,) + (None,) * (len(ctx.needs_input_grad) - 1)
 
 
 def rnnt_loss_pruned(logits: torch.Tensor, symbols: torch.Tensor, ranges: torch.Tensor, termination_symbol: int,
-                     boundary: Optional[torch.Tensor] = None, reduction: str = "mean") -> torch.Tensor:
-    """k2.rnnt_loss_pruned(logits, symbols, ranges, termination_symbol, boundary, reduction).
+                     boundary: Optional[torch.Tensor] = None, reduction: str = "mean", *, rnnt_type: str = "regular",
+                     delay_penalty: float = 0.0) -> torch.Tensor:
+    """k2.rnnt_loss_pruned(logits, symbols, ranges, termination_symbol, boundary, reduction, rnnt_type=, delay_penalty=).
 
     logits (B, T, R, V) are the joiner's un-normalised outputs on the band (float32, float16 or bfloat16; the gradient
     comes back in the same dtype), ``logits[b,t,r]`` belonging to the lattice cell ``(t, ranges[b,t,r])``; symbols (B, U)
@@ -230,25 +256,35 @@ def rnnt_loss_pruned(logits: torch.Tensor, symbols: torch.Tensor, ranges: torch.
     Returns the negated total log-probability of the paths that stay inside the band (float32), reduced over the batch
     ("none" | "mean" | "sum"; not length-normalised).  A band that holds no complete path gives ``+inf`` for that
     utterance (a value, not an error; its gradient is not finite).  ``ranges`` must be consecutive along r and lie
-    within [0, U] (ValueError otherwise)."""
+    within [0, U] (ValueError otherwise).  ``rnnt_type`` and ``delay_penalty`` as in `rnnt_loss_simple`: the penalty is
+    added to the band's label arcs; on the "modified" lattice a band of one position per frame (R = 1) is legal."""
     what = "rnnt_loss_pruned"
     if reduction not in ("none", "mean", "sum"):
         raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
+    lat, pen = _lat.check_lattice(what, rnnt_type, delay_penalty)
     sy, ll, tl, blank, rg = _prepare(logits, symbols, ranges, termination_symbol, boundary, what)
-    costs = _RNNTPrunedFn.apply(logits, sy, rg, ll, tl, blank)
+    if _lat.is_default(lat, pen):
+        costs = _RNNTPrunedFn.apply(logits, sy, rg, ll, tl, blank)
+    else:
+        costs = _RNNTPrunedFn.apply(logits, sy, rg, ll, tl, blank, lat, pen)
     return costs.mean() if reduction == "mean" else (costs.sum() if reduction == "sum" else costs)
 
 
 @torch.no_grad()
-def rnnt_pruned_lattice(logits, symbols, ranges, termination_symbol, boundary=None):
+def rnnt_pruned_lattice(logits, symbols, ranges, termination_symbol, boundary=None, *, rnnt_type="regular",
+                        delay_penalty=0.0):
     """Diagnostics for tests: (costs, alpha, beta) of the banded lattice, alpha / beta as plain (B, T, U+1) tensors
     (-inf where no path inside the band reaches a cell, zero outside the boundary)."""
+    lat, pen = _lat.check_lattice("rnnt_pruned_lattice", rnnt_type, delay_penalty)
     sy, ll, tl, blank, rg = _prepare(logits, symbols, ranges, termination_symbol, boundary, "rnnt_pruned_lattice")
     logits = logits.detach().contiguous()
     B, T = logits.shape[:2]
     U1 = sy.shape[1] + 1
-    costs, ws = _stats_and_sweeps(logits, sy, rg, ll, tl, blank)
+    costs, ws = _stats_and_sweeps(logits, sy, rg, ll, tl, blank, lat, pen)
     alpha = torch.empty(B, T, U1, dtype=torch.float32, device=logits.device)
     beta = torch.empty_like(alpha)
-    _lib.call("wr_rnnt_export_lattice", ws, ws.numel(), ll, tl, B, T, U1, alpha, beta, device=logits.device)
+    if _lat.is_default(lat, pen):
+        _lib.call("wr_rnnt_export_lattice", ws, ws.numel(), ll, tl, B, T, U1, alpha, beta, device=logits.device)
+    else:
+        _lib.call("wr_rnnt_lattice_export", ws, ws.numel(), ll, tl, B, T, U1, lat, alpha, beta, device=logits.device)
     return costs, alpha, beta

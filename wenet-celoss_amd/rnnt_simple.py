@@ -8,7 +8,8 @@ contractions over one index ("The additive-joiner loss"), and memory 
   rnnt_loss_simple            the loss (one autograd node: forward = row statistics + lattice sweeps, backward = gradient)
   rnnt_simple_forced_align    the best path through the same lattice (row statistics, then `wr_rnnt_align_from_stats`)
 
-Not offered: ``rnnt_type`` other than "regular" and ``delay_penalty`` (the arguments do not exist here).
+``rnnt_type="modified"`` and ``delay_penalty`` are offered by the k2-signature form of the loss, `k2.rnnt_loss_simple`
+(k2.py, rnnt_lattice.py); the function here keeps its signature.  The forced alignment stays on the regular lattice.
 """
 from __future__ import annotations
 
@@ -17,6 +18,7 @@ from typing import Optional, Tuple, Union
 import torch
 
 from . import _lib
+from . import rnnt_lattice as _lat
 
 
 def _prepare(lm, am, symbols, termination_symbol, boundary, what: str):
@@ -126,7 +128,8 @@ def rnnt_loss_simple(lm: torch.Tensor, am: torch.Tensor, symbols: torch.Tensor, 
     a row with a non-zero begin raises ValueError.  Returns the negated total log-probability, reduced over the batch
     ("none" | "mean" | "sum"; not length-normalised).  With ``return_grad`` also ``(px_grad (B, U, T+1), py_grad
     (B, U+1, T))``: the occupancies of the emit and blank arcs in k2's layout (px_grad's last frame column is zero),
-    detached -- what a pruning step takes its ranges from."""
+    detached -- what a pruning step takes its ranges from.  Regular lattice, no delay penalty: `k2.rnnt_loss_simple`
+    takes ``rnnt_type`` and ``delay_penalty``."""
     what = "rnnt_loss_simple"
     if reduction not in ("none", "mean", "sum"):
         raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
@@ -148,8 +151,8 @@ def rnnt_loss_simple(lm: torch.Tensor, am: torch.Tensor, symbols: torch.Tensor, 
 @torch.no_grad()
 def rnnt_simple_forced_align(lm: torch.Tensor, am: torch.Tensor, symbols: torch.Tensor, termination_symbol: int,
                              boundary: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Best path of the lattice `rnnt_loss_simple` sums over, without a logits tensor.  Arguments as rnnt_loss_simple
-    (every T_b >= 1).  Returns what `rnnt_forced_align` returns: (label_frames (B, U) int32, -1 past U_b; scores (B,)
+    """Best path of the regular lattice `rnnt_loss_simple` sums over (the modified lattice and the delay penalty are not
+    offered here), without a logits tensor.  Arguments as rnnt_loss_simple (every T_b >= 1).  Returns what `rnnt_forced_align` returns: (label_frames (B, U) int32, -1 past U_b; scores (B,)
     float64) on the device; `rnnt_frame_tokens` applies to the result."""
     what = "rnnt_simple_forced_align"
     sy, ll, tl, blank, rows = _prepare(lm, am, symbols, termination_symbol, boundary, what)
@@ -168,12 +171,15 @@ def rnnt_simple_forced_align(lm: torch.Tensor, am: torch.Tensor, symbols: torch.
 
 
 @torch.no_grad()
-def rnnt_simple_lattice(lm, am, symbols, termination_symbol, boundary=None):
+def rnnt_simple_lattice(lm, am, symbols, termination_symbol, boundary=None, *, rnnt_type="regular", delay_penalty=0.0):
     """Diagnostics for tests: (costs, alpha, beta, flag) -- alpha / beta as plain (B, T, U+1) tensors, flag the RNN-T
     workspace's "row statistics were redone by the direct kernel" word (a one-element int32 tensor)."""
     what = "rnnt_simple_lattice"
+    lat, pen = _lat.check_lattice(what, rnnt_type, delay_penalty)
     sy, ll, tl, blank, _ = _prepare(lm, am, symbols, termination_symbol, boundary, what)
     _require_device(what, lm, am)
+    if not _lat.is_default(lat, pen):
+        return _lat.lattice(lm, am, sy, ll, tl, blank, 0.0, 0.0, lat, pen)
     lm, am = lm.detach().float().contiguous(), am.detach().float().contiguous()
     B, U1, _ = lm.shape
     T = am.shape[1]

@@ -6,8 +6,8 @@ the contract; DESIGN.md, "The smoothed loss"):
 
     arc = (1 - ll - la) * (am + lm - denom) + ll * (lm - Zl[u]) + la * (am + log pbar - N[t])
 
-so that both vocabulary heads stay usable on their own.  ``rnnt_type`` other than "regular" and ``delay_penalty`` are
-not offered.
+so that both vocabulary heads stay usable on their own.  ``rnnt_type="modified"`` and ``delay_penalty`` are offered by
+the k2-signature form, `k2.rnnt_loss_smoothed` (k2.py, rnnt_lattice.py); the function here keeps its signature.
 """
 from __future__ import annotations
 
@@ -16,6 +16,7 @@ from typing import Optional, Tuple, Union
 import torch
 
 from . import _lib
+from . import rnnt_lattice as _lat
 from .rnnt_simple import _prepare, _require_device, _RNNTSimpleFn
 
 
@@ -99,7 +100,8 @@ def rnnt_loss_smoothed(lm: torch.Tensor, am: torch.Tensor, symbols: torch.Tensor
     rows of ``lm`` must be finite, they receive a gradient, and ``d_lm`` of one utterance depends on the others'.  A
     scale that is exactly 0 drops its branch (k2 substitutes 1e-20 there, below float32 resolution of any finite term);
     both 0 is `rnnt_loss_simple`, bit for bit.  With ``return_grad`` the occupancies are those of the interpolated
-    lattice, in the same ``(px_grad (B, U, T+1), py_grad (B, U+1, T))`` layout."""
+    lattice, in the same ``(px_grad (B, U, T+1), py_grad (B, U+1, T))`` layout.  `k2.rnnt_loss_smoothed` takes
+    ``rnnt_type`` and ``delay_penalty``."""
     what = "rnnt_loss_smoothed"
     if reduction not in ("none", "mean", "sum"):
         raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
@@ -123,12 +125,16 @@ def rnnt_loss_smoothed(lm: torch.Tensor, am: torch.Tensor, symbols: torch.Tensor
 
 
 @torch.no_grad()
-def rnnt_smoothed_lattice(lm, am, symbols, termination_symbol, lm_only_scale=0.1, am_only_scale=0.1, boundary=None):
+def rnnt_smoothed_lattice(lm, am, symbols, termination_symbol, lm_only_scale=0.1, am_only_scale=0.1, boundary=None, *,
+                          rnnt_type="regular", delay_penalty=0.0):
     """Diagnostics for tests, the twin of `rnnt_simple_lattice`: (costs, alpha, beta, flag) of the interpolated lattice."""
     what = "rnnt_smoothed_lattice"
     lm_scale, am_scale = _check_scales(what, lm_only_scale, am_only_scale)
+    lat, pen = _lat.check_lattice(what, rnnt_type, delay_penalty)
     sy, ll, tl, blank, _ = _prepare(lm, am, symbols, termination_symbol, boundary, what)
     _require_device(what, lm, am)
+    if not _lat.is_default(lat, pen):
+        return _lat.lattice(lm, am, sy, ll, tl, blank, lm_scale, am_scale, lat, pen)
     lm, am = lm.detach().float().contiguous(), am.detach().float().contiguous()
     B, U1, _ = lm.shape
     T = am.shape[1]

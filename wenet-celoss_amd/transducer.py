@@ -37,6 +37,8 @@ from .rnnt_align import joint_rnnt_forced_align, rnnt_forced_align
 from .rnnt_loss import rnnt_loss
 from .rnnt_simple import rnnt_loss_simple, rnnt_simple_forced_align
 from .rnnt_smoothed import rnnt_loss_smoothed
+from . import k2
+from .rnnt_lattice import check_lattice, is_default
 from .rnnt_pruned import get_rnnt_prune_ranges, rnnt_loss_pruned
 from .search.greedy_search import basic_greedy_search, basic_greedy_search_both, basic_greedy_search_hw
 from .search.prefix_beam_search import PrefixBeamSearch
@@ -81,7 +83,8 @@ class Transducer(nn.Module):
                  reverse_weight: float = 0.0, lsm_weight: float = 0.0, length_normalized_loss: bool = False,
                  transducer_weight: float = 1.0, attention_weight: float = 0.0, hw_weight: float = 0.4,
                  loss_mode: str = "both", prune_range: int = 0, lm_only_scale: float = 0.0,
-                 am_only_scale: float = 0.0, simple_loss_weight: float = 0.0) -> None:
+                 am_only_scale: float = 0.0, rnnt_type: str = "regular", delay_penalty: float = 0.0,
+                 simple_loss_weight: float = 0.0) -> None:
         assert attention_weight + ctc_weight + transducer_weight == 1.0          # transducer.py:46 (kept as is)
         super().__init__()
         # ASRModel part (asr_model.py:38-70): sos/eos are the last class
@@ -139,6 +142,12 @@ class Transducer(nn.Module):
         # pruned training (k2 / icefall recipe, rnnt_pruned.py): the simple loss's arc occupancies choose a band of
         # `prune_range` label positions per frame, and loss_rnnt is the RNN-T loss of the joiner evaluated on that band
         # only.  0: the full-lattice loss block above.
+        # lattice type and delay penalty of the k2 losses (rnnt_lattice.py): passed to the simple / smoothed loss and to
+        # the pruned loss.  Without a simple loss the main loss is the torchaudio-style one, which has neither.
+        lat, self.delay_penalty = check_lattice("Transducer", rnnt_type, delay_penalty)
+        self.rnnt_type = rnnt_type
+        if not is_default(lat, self.delay_penalty) and not self.simple_loss_weight > 0.0:
+            raise ValueError("Transducer: rnnt_type / delay_penalty belong to the k2 losses: simple_loss_weight must be > 0")
         self.prune_range = int(prune_range)
         if self.prune_range < 0 or self.prune_range == 1:
             raise ValueError(f"Transducer: prune_range must be 0 (off) or at least 2 (got {prune_range})")
@@ -223,10 +232,25 @@ class Transducer(nn.Module):
 
     def _simple_loss(self, lm, am, symbols, boundary, return_grad: bool):
         ll, la = self.lm_only_scale, self.am_only_scale
+        kw = self._lattice_kwargs()
+        if kw:                                                   # the k2-signature forms take the lattice arguments
+            if ll != 0.0 or la != 0.0:
+                return k2.rnnt_loss_smoothed(lm, am, symbols, self.blank, lm_only_scale=ll, am_only_scale=la,
+                                             boundary=boundary, reduction="mean", return_grad=return_grad, **kw)
+            return k2.rnnt_loss_simple(lm, am, symbols, self.blank, boundary=boundary, reduction="mean",
+                                       return_grad=return_grad, **kw)
         if ll != 0.0 or la != 0.0:
             return rnnt_loss_smoothed(lm, am, symbols, self.blank, lm_only_scale=ll, am_only_scale=la, boundary=boundary,
                                       reduction="mean", return_grad=return_grad)
         return rnnt_loss_simple(lm, am, symbols, self.blank, boundary=boundary, reduction="mean", return_grad=return_grad)
+
+    def _lattice_kwargs(self) -> Dict[str, object]:
+        """rnnt_type / delay_penalty for the k2 losses; empty for the defaults (and for a model pickled before they
+        existed)."""
+        rnnt_type, pen = getattr(self, "rnnt_type", "regular"), getattr(self, "delay_penalty", 0.0)
+        if rnnt_type == "regular" and pen == 0.0:
+            return {}
+        return {"rnnt_type": rnnt_type, "delay_penalty": pen}
 
     def compute_pruned_loss(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, predictor_out: torch.Tensor,
                             text: torch.Tensor, text_lengths: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -235,9 +259,11 @@ class Transducer(nn.Module):
         loss_rnnt is `rnnt_loss_pruned` on the joiner's outputs on that band."""
         lm, am, symbols, boundary = self._simple_inputs(encoder_out, encoder_out_lens, predictor_out, text, text_lengths)
         loss_simple, (px_grad, py_grad) = self._simple_loss(lm, am, symbols, boundary, return_grad=True)
-        ranges = get_rnnt_prune_ranges(px_grad, py_grad, boundary, self.prune_range)
+        ranges = (k2.get_rnnt_prune_ranges if self._lattice_kwargs() else get_rnnt_prune_ranges)(
+            px_grad, py_grad, boundary, self.prune_range)
         logits = self.joint.forward_pruned(encoder_out, predictor_out, ranges)
-        loss_rnnt = rnnt_loss_pruned(logits, symbols, ranges, self.blank, boundary=boundary, reduction="mean")
+        loss_rnnt = rnnt_loss_pruned(logits, symbols, ranges, self.blank, boundary=boundary, reduction="mean",
+                                     **self._lattice_kwargs())
         return loss_rnnt, loss_simple
 
     def _can_fuse_loss(self) -> bool:
@@ -336,7 +362,9 @@ class Transducer(nn.Module):
         under a 16-bit (AMP) mode the joiner's logits go to rnnt_forced_align.  Frames are encoder frames (after
         subsampling).  ``head="simple"`` aligns on the lattice of the additive-joiner loss instead (`loss_simple`; the
         model must have been built with `simple_loss_weight > 0`).  Returns (label_frames (B, U) int32, -1 past
-        text_lengths; scores (B,) float64) on the device.  Call it in eval mode unless dropout is wanted."""
+        text_lengths; scores (B,) float64) on the device.  Call it in eval mode unless dropout is wanted.  Both heads
+        align on the regular lattice without a delay penalty, whatever `rnnt_type` / `delay_penalty` the model trains
+        with."""
         if head not in ("joint", "simple"):
             raise ValueError(f"forced_align: head must be \"joint\" or \"simple\", got {head!r}")
         if head == "simple" and not hasattr(self, "simple_am_proj"):
