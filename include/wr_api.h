@@ -815,7 +815,8 @@ int wr_rnnt_prune_ranges_cols(const float *px_grad_d, int px_cols, const float *
  * forced_align, wenet/utils/ctc_util.py:27-83 (CLI wenet/bin/alignment.py:215).  logits [B, Tmax, V]: pre-softmax
  * ctc_lo output, or log-posteriors if normalized != 0 (the reference is handed ctc.log_softmax(...)).
  * alignment [B, Tmax]: the token (blank or label) aligned to each frame, -1 past input_lengths[b].
- * fp32 scores and first-candidate tie rule as the reference; Smax >= 1. */
+ * fp32 scores and first-candidate tie rule as the reference; Smax >= 1.  An utterance with target_lengths[b] <= 0
+ * has the one all-blank path: alignment[b, t] = blank for t < input_lengths[b], whatever targets[b] holds. */
 size_t wr_ctc_align_workspace_bytes(int B, int Tmax, int Smax);
 
 int wr_ctc_forced_align(const float *logits_d, int normalized, const int32_t *targets_d,

@@ -16,11 +16,11 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-def run_hip(logits, targets, ilens, tlens, grad_out=None):
+def run_hip(logits, targets, ilens, tlens, grad_out=None, blank=0):
     import wenet_celoss_amd as w
     x = torch.tensor(logits, device=DEV, requires_grad=True)
     nll = w.ctc_loss(x, torch.tensor(targets, device=DEV), torch.tensor(ilens, device=DEV),
-                     torch.tensor(tlens, device=DEV), reduction="none")
+                     torch.tensor(tlens, device=DEV), blank=blank, reduction="none")
     if grad_out is None:
         nll.sum().backward()
     else:
@@ -163,3 +163,117 @@ def test_full_size_properties():
                                    il.cpu().numpy(), tl.cpu().numpy())
     np.testing.assert_allclose(nll.detach().cpu().numpy(), onll, rtol=1e-5)
     np.testing.assert_allclose(g.cpu().numpy(), og, rtol=1e-4, atol=1e-5)
+
+
+# ------------------------------------------------------------------------------------------- the options of ctc_loss --
+def with_blank(targets, blank):
+    """Labels 1..V-1 of make() with the blank moved to `blank`: that label becomes 0, an ordinary label now (and the
+    first label of utterance 0, which make() gives the full length, is 0 in any case)."""
+    targets = np.where(targets == blank, 0, targets)
+    targets[0, 0] = 0
+    return targets
+
+
+@pytest.mark.parametrize("blank", [3, "last"])
+@pytest.mark.parametrize("B,T,S,V", [(3, 50, 20, 33), (2, 90, 40, 64)])
+def test_blank_position(B, T, S, V, blank):
+    blank = V - 1 if blank == "last" else blank
+    rng = np.random.default_rng(B + T + S + V + blank)
+    logits, targets, ilens, tlens = make(rng, B, T, S, V, repeat=True)
+    targets = with_blank(targets, blank)
+    assert (targets == 0).any() and not (targets == blank).any()
+    nll, grad = run_hip(logits, targets, ilens, tlens, blank=blank)
+    on, og = oracle.ctc_loss_f64(logits, targets, ilens, tlens, blank=blank)
+    np.testing.assert_allclose(nll, on, rtol=1e-5, atol=1e-5)
+    np.testing.assert_allclose(grad, og, rtol=1e-4, atol=1e-5)
+    on0, _ = oracle.ctc_loss_f64(logits, targets, ilens, tlens, blank=0)
+    assert not np.allclose(on, on0, rtol=1e-3)          # the blank's position matters on this input
+
+
+@pytest.mark.parametrize("reduction", ["mean", "sum"])
+def test_reduction_vs_torch_ctcloss_f64(reduction):
+    """reduction 'mean' (nll / max(target length, 1), then the batch mean) and 'sum' against float64 torch.nn.CTCLoss on
+    the CPU, gradients included; utterance 1 has no labels, which is where the clamp acts."""
+    import wenet_celoss_amd as w
+    rng = np.random.default_rng(31)
+    B, T, S, V = 4, 30, 7, 20
+    logits, targets, ilens, tlens = make(rng, B, T, S, V, repeat=True)
+    tlens[1] = 0; targets[1] = -1
+    assert tlens[0] == S and (tlens[2:] > 0).any()
+    x = torch.tensor(logits, device=DEV, requires_grad=True)
+    loss = w.ctc_loss(x, torch.tensor(targets, device=DEV), torch.tensor(ilens, device=DEV), torch.tensor(tlens, device=DEV),
+                      reduction=reduction)
+    loss.backward()
+    x64 = torch.tensor(logits, dtype=torch.float64, requires_grad=True)
+    ref = torch.nn.CTCLoss(reduction=reduction)(x64.transpose(0, 1).log_softmax(2), torch.tensor(np.where(targets < 0, 0, targets)),
+                                                torch.tensor(ilens.astype(np.int64)), torch.tensor(tlens.astype(np.int64)))
+    ref.backward()
+    assert loss.dim() == 0 and loss.dtype == torch.float32
+    np.testing.assert_allclose(loss.item(), ref.item(), rtol=1e-5, atol=1e-5)
+    np.testing.assert_allclose(x.grad.cpu().numpy(), x64.grad.numpy(), rtol=1e-4, atol=1e-5)
+
+
+@pytest.mark.parametrize("autocast", [False, True])
+@pytest.mark.parametrize("dtype,tol", [(torch.float16, 2e-3), (torch.bfloat16, 1.6e-2)])
+def test_half_precision_logits(dtype, tol, autocast):
+    """fp16 / bf16 logits (with and without autocast): fp32 arithmetic inside and an fp32 result, the gradient returned
+    in the input dtype.  Against the oracle on the same rounded logits; the tolerance is the gradient dtype's rounding,
+    the bars of test_rnnt_gpu.py::test_half_precision_logits."""
+    import wenet_celoss_amd as w
+    rng = np.random.default_rng(33)
+    B, T, S, V = 3, 40, 9, 37
+    logits, targets, ilens, tlens = make(rng, B, T, S, V, repeat=True)
+    xh = torch.tensor(logits, device=DEV).to(dtype)
+    x = xh.clone().requires_grad_(True)
+    with torch.autocast("cuda", dtype=dtype, enabled=autocast):
+        nll = w.ctc_loss(x, torch.tensor(targets, device=DEV), torch.tensor(ilens, device=DEV),
+                         torch.tensor(tlens, device=DEV), reduction="none")
+    assert nll.dtype == torch.float32
+    nll.sum().backward()
+    assert x.grad.dtype == dtype
+    on, og = oracle.ctc_loss_f64(xh.float().cpu().numpy(), targets, ilens, tlens)
+    np.testing.assert_allclose(nll.detach().cpu().numpy(), on, rtol=tol)
+    np.testing.assert_allclose(x.grad.float().cpu().numpy(), og, rtol=tol, atol=tol * 1e-1)
+    for b in range(B):
+        assert not x.grad[b, ilens[b]:].any()
+
+
+def test_non_contiguous_logits():
+    """A (T, B, V) tensor transposed to batch-major equals its contiguous copy bit for bit, cost and gradient."""
+    import wenet_celoss_amd as w
+    rng = np.random.default_rng(34)
+    B, T, S, V = 3, 25, 6, 19
+    logits, targets, ilens, tlens = make(rng, B, T, S, V, repeat=True)
+    args = [torch.tensor(a, device=DEV) for a in (targets, ilens, tlens)]
+    tbv = torch.tensor(logits, device=DEV).transpose(0, 1).contiguous().requires_grad_(True)
+    view = tbv.transpose(0, 1)
+    assert not view.is_contiguous()
+    nll_v = w.ctc_loss(view, *args, reduction="none")
+    nll_v.sum().backward()
+    x = torch.tensor(logits, device=DEV, requires_grad=True)
+    nll_c = w.ctc_loss(x, *args, reduction="none")
+    nll_c.sum().backward()
+    assert torch.equal(nll_v, nll_c) and torch.equal(tbv.grad.transpose(0, 1), x.grad)
+    on, og = oracle.ctc_loss_f64(logits, targets, ilens, tlens)
+    np.testing.assert_allclose(nll_c.detach().cpu().numpy(), on, rtol=1e-5, atol=1e-5)
+    np.testing.assert_allclose(x.grad.cpu().numpy(), og, rtol=1e-4, atol=1e-5)
+
+
+@pytest.mark.parametrize("blank", [0, 2])
+def test_zero_width_targets(blank):
+    """targets of shape (B, 0): the blank-only path of every utterance."""
+    import wenet_celoss_amd as w
+    rng = np.random.default_rng(35)
+    B, T, V = 3, 11, 6
+    logits = (rng.normal(size=(B, T, V)) * 2).astype(np.float32)
+    ilens = np.array([T, 1, 6], np.int32)
+    tlens = np.zeros(B, np.int32)
+    x = torch.tensor(logits, device=DEV, requires_grad=True)
+    nll = w.ctc_loss(x, torch.zeros(B, 0, dtype=torch.int64, device=DEV), torch.tensor(ilens, device=DEV),
+                     torch.tensor(tlens, device=DEV), blank=blank, reduction="none")
+    nll.sum().backward()
+    on, og = oracle.ctc_loss_f64(logits, np.zeros((B, 0), np.int32), ilens, tlens, blank=blank)
+    np.testing.assert_allclose(nll.detach().cpu().numpy(), on, rtol=1e-5, atol=1e-5)
+    np.testing.assert_allclose(x.grad.cpu().numpy(), og, rtol=1e-4, atol=1e-5)
+    lp = torch.tensor(logits, dtype=torch.float64).log_softmax(2)[:, :, blank]
+    np.testing.assert_allclose(on, [-lp[b, :ilens[b]].sum().item() for b in range(B)], rtol=1e-12)

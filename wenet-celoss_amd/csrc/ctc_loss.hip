@@ -367,7 +367,11 @@ __global__ __launch_bounds__(kCtcMaxStates) void ctc_viterbi_kernel(
     const int b = blockIdx.x, s = threadIdx.x;
     int T = ilens[b], S = tlens[b];
     T = T < 0 ? 0 : (T > Tmax ? Tmax : T);
-    S = S < 1 ? 1 : (S > Smax ? Smax : S);
+    if (S < 1) {                                                   // no labels: the one path is blank at every frame
+        for (int t = s; t < Tmax; t += blockDim.x) align[(size_t)b * Tmax + t] = t < T ? blank : -1;
+        return;
+    }
+    S = S > Smax ? Smax : S;
     const int NS = 2 * S + 1;
     const float NEG = -__builtin_huge_valf();
     const float *lpb = lp_blank + (size_t)b * Tmax;
