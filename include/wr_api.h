@@ -655,7 +655,12 @@ int wr_rnnt_simple_grad(const float *am_d, const float *lm_d, const int32_t *sym
  * pbar is the mean over ALL B*U1 rows of lm, rows past U_b included (k2's definition): padded rows of lm must be finite
  * when la > 0.  A scale that is exactly 0 drops its branch: no term, no kernel (with la == 0 nothing beyond the simple
  * loss's kernels reads am).  ll == la == 0 runs wr_rnnt_simple_stats / wr_rnnt_simple_grad's kernels and nothing else:
- * the same bits.
+ * the same bits, and the scratch then needs only wr_rnnt_simple_workspace_bytes (the part these calls touch; with a
+ * non-zero scale wr_rnnt_smoothed_workspace_bytes).  wr_rnnt_simple_stats / wr_rnnt_simple_grad are these calls with
+ * ll = la = 0 (wr_rnnt_simple_grad requires d_am and d_lm).  Order of the argument checks in these four calls and wr_rnnt_smoothed_grad_lattice: shapes and
+ * scales (WR_EINVAL / WR_EUNSUPPORTED; the bound V <= 256 * 65535 belongs to the smoothing kernels' grids and applies
+ * only with a non-zero scale), then both workspace sizes (WR_EWORKSPACE), then null pointers (WR_EINVAL): a call with a
+ * null pointer and a workspace that is too small returns WR_EWORKSPACE.
  *
  * wr_rnnt_smoothed_stats: wr_rnnt_simple_stats' kernels (the direct repair pass included), then the arcs above written
  * over the skewed log-probabilities of the RNN-T workspace.  wr_rnnt_loss_sweeps / wr_rnnt_export_lattice follow.
@@ -776,10 +781,13 @@ int wr_rnnt_pruned_grad(const void *logits_d, int dtype, const int32_t *symbols_
  * sweeps (T_b dependent steps).  alpha / beta (fp64), ll and the costs land where wr_rnnt_loss_sweeps puts them for the
  * regular lattice; the modified lattice keeps its arrays elsewhere in the workspace, so only the *_lattice calls below,
  * given the same lattice_type, may read it (wr_rnnt_align_from_stats and wr_rnnt_export_lattice may not).
- * WR_LATTICE_REGULAR with delay_penalty 0 is wr_rnnt_loss_sweeps.
+ * WR_LATTICE_REGULAR with delay_penalty 0 is wr_rnnt_loss_sweeps: the same kernel, the same shapes accepted (the other
+ * settings and wr_rnnt_lattice_export also need B * (T + U1 - 1) * U1 < 2^31).  So is every *_lattice / *_cols call
+ * below with the defaults: they launch the kernels of the plain entry points, which is the one path callers need.
  * wr_rnnt_lattice_export: wr_rnnt_export_lattice for either type: alpha / beta [B,T,U1] fp32 (rows t < T_b; zero outside
  * the boundary).
- * wr_rnnt_smoothed_grad_lattice: wr_rnnt_smoothed_grad (both scales 0: wr_rnnt_simple_grad, on the smoothed workspace)
+ * wr_rnnt_smoothed_grad_lattice: wr_rnnt_smoothed_grad (both scales 0: wr_rnnt_simple_grad, and like
+ * wr_rnnt_smoothed_stats / wr_rnnt_smoothed_grad it then requires only wr_rnnt_simple_workspace_bytes of scratch)
  * reading the lattice of `lattice_type`; the penalty needs no argument, it is inside the stored label arcs.
  * wr_rnnt_pruned_grad_lattice: wr_rnnt_pruned_grad likewise; it forms the label term from the logits, so it takes the
  * penalty too (the value given to wr_rnnt_lattice_sweeps).

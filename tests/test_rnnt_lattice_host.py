@@ -168,3 +168,34 @@ def test_new_entry_points_reject_bad_arguments_without_launch():
     assert ranges(cols=6) == -1
     assert ranges(p=null) == -1 and b"null" in lib.wr_last_error()
     assert ranges(R=4) == -1
+
+
+def test_general_entry_points_accept_what_the_plain_ones_accept_without_launch():
+    """`wr_rnnt_lattice_sweeps(regular, 0)` takes every shape `wr_rnnt_loss_sweeps` takes: the bound on the skewed
+    positions, B * (T + U1 - 1) * U1 < 2^31, belongs to the kernels of the other settings.  With both scales 0 the
+    smoothed calls need the simple loss's scratch only.  Null data pointers: every check precedes the launches."""
+    from wenet_celoss_amd import _lib
+    lib = _lib.load()
+    null = ctypes.c_void_p(None)
+    one = ctypes.c_void_p(256)
+    B, T, U1 = 2047, 1024, 1024
+    assert B * T * U1 < 2 ** 31 <= B * (T + U1 - 1) * U1
+
+    def sweeps(lat=0, dp=0.0):
+        return lib.wr_rnnt_lattice_sweeps(null, null, B, T, U1, lat, dp, null, null, 0, null)
+
+    assert sweeps() == -1 and b"null" in lib.wr_last_error()            # the shape passed
+    assert lib.wr_rnnt_loss_sweeps(null, null, B, T, U1, null, null, 0, null) == -1 and b"null" in lib.wr_last_error()
+    assert sweeps(lat=1) == -2 and b"2^31" in lib.wr_last_error()
+    assert sweeps(dp=0.01) == -2 and b"2^31" in lib.wr_last_error()
+
+    dims = (2, 5, 4, 7)
+    simple = lib.wr_rnnt_simple_workspace_bytes(*dims)
+    assert 0 < simple < lib.wr_rnnt_smoothed_workspace_bytes(*dims)
+
+    def stats(ll, la, sws):                                # a null data pointer: the sizes are checked before it
+        return lib.wr_rnnt_smoothed_stats(null, one, one, one, one, *dims, 0, ll, la, one, sws, one, 1 << 30, null)
+
+    assert stats(0.0, 0.0, simple - 1) == -3 and b"workspace" in lib.wr_last_error()
+    assert stats(0.0, 0.0, simple) == -1 and b"null" in lib.wr_last_error()
+    assert stats(0.1, 0.1, simple) == -3 and b"workspace" in lib.wr_last_error()

@@ -286,3 +286,44 @@ def test_transducer_pruned_block_uses_the_smoothed_loss():
     for head in ("simple_am_proj", "simple_lm_proj"):
         for p in getattr(m, head).parameters():
             assert p.grad is not None and torch.isfinite(p.grad).all() and p.grad.abs().max() > 0
+
+
+@pytest.mark.parametrize("rnnt_type,penalty", [("regular", 0.0), ("modified", 0.01)])
+def test_both_scales_zero_stay_inside_the_simple_workspace(rnnt_type, penalty):
+    """The raw smoothed calls with both scales 0, handed exactly `wr_rnnt_simple_workspace_bytes` of scratch, leave the
+    bytes behind it alone and give the bits of `k2.rnnt_loss_simple`."""
+    import wenet_celoss_amd as w
+    from wenet_celoss_amd import _lib, rnnt_lattice
+    B, T, U, V = 2, 9, 4, 33
+    lm, am, symbols, _, _ = make_case(np.random.default_rng(41), B, T, U, V)
+    t_lens, u_lens = np.array([9, 6]), np.array([3, 4])              # ragged; T_b >= U_b, so the modified lattice has paths
+    lat = _lib.LATTICES[rnnt_type]
+    l, a = torch.tensor(lm, device=DEV), torch.tensor(am, device=DEV)
+    sy = torch.tensor(symbols, device=DEV, dtype=torch.int32)
+    ll = torch.tensor(t_lens, device=DEV, dtype=torch.int32)
+    tl = torch.tensor(u_lens, device=DEV, dtype=torch.int32)
+
+    n = _lib.load().wr_rnnt_simple_workspace_bytes(B, T, U + 1, V)
+    assert 0 < n < _lib.load().wr_rnnt_smoothed_workspace_bytes(B, T, U + 1, V)
+    buf = torch.full((n + 4096,), 0xA5, dtype=torch.uint8, device=DEV)
+    sws = buf[:n]
+    rws = _lib.workspace("wr_rnnt_workspace_bytes", B, T, U + 1, device=DEV)
+    costs = torch.empty(B, dtype=torch.float32, device=DEV)
+    d_am, d_lm = torch.empty_like(a), torch.empty_like(l)
+    occ_emit = torch.empty(B, T, U + 1, dtype=torch.float32, device=DEV)
+    occ_blank = torch.empty_like(occ_emit)
+    _lib.call("wr_rnnt_smoothed_stats", a, l, sy, ll, tl, B, T, U + 1, V, 0, 0.0, 0.0, sws, n, rws, rws.numel(), device=DEV)
+    _lib.call("wr_rnnt_lattice_sweeps", ll, tl, B, T, U + 1, lat, penalty, costs, rws, rws.numel(), device=DEV)
+    _lib.call("wr_rnnt_smoothed_grad_lattice", a, l, sy, ll, tl, B, T, U + 1, V, 0, 0.0, 0.0, lat, None, d_am, d_lm, occ_emit,
+              occ_blank, sws, n, rws, rws.numel(), device=DEV)
+    assert bool((buf[n:] == 0xA5).all())
+
+    l2, a2 = l.clone().requires_grad_(), a.clone().requires_grad_()
+    want, (px_grad, py_grad) = w.k2.rnnt_loss_simple(l2, a2, torch.tensor(symbols, device=DEV), 0,
+                                                     boundary=boundary_of(t_lens, u_lens), reduction="none",
+                                                     return_grad=True, rnnt_type=rnnt_type, delay_penalty=penalty)
+    want.sum().backward()
+    assert torch.isfinite(want).all()
+    assert torch.equal(costs, want.detach()) and torch.equal(d_am, a2.grad) and torch.equal(d_lm, l2.grad)
+    px, py = rnnt_lattice.occupancies_to_k2(occ_emit, occ_blank, lat)
+    assert torch.equal(px, px_grad) and torch.equal(py, py_grad)

@@ -179,12 +179,14 @@ __global__ __launch_bounds__(256) void lattice_export_kernel(
     beta[r] = be;
 }
 
-int lattice_shape(const char *what, int B, int T, int U1)
+// `rows`: a kernel of this file runs (it indexes B * (T + U1 - 1) * U1 positions); without one the limits are those of
+// wr_rnnt_loss_sweeps.
+int lattice_shape(const char *what, int B, int T, int U1, bool rows)
 {
     WR_REQUIRE(B > 0 && T > 0 && U1 > 0, WR_EINVAL, "%s: B, T, U1 must be positive (got %d,%d,%d)", what, B, T, U1);
     WR_REQUIRE(U1 <= kRnntMaxCols, WR_EUNSUPPORTED, "%s: U1=%d exceeds the sweep kernel's limit of %d label columns", what,
                U1, kRnntMaxCols);
-    WR_REQUIRE((long)B * T * U1 < (1L << 31) && (long)B * (T + U1 - 1) * U1 < (1L << 31), WR_EUNSUPPORTED,
+    WR_REQUIRE((long)B * T * U1 < (1L << 31) && (!rows || (long)B * (T + U1 - 1) * U1 < (1L << 31)), WR_EUNSUPPORTED,
                "%s: more than 2^31 lattice positions", what);
     return WR_OK;
 }
@@ -208,7 +210,8 @@ extern "C" int wr_rnnt_lattice_sweeps(const int32_t *logit_lengths_d, const int3
                                       int U1, int lattice_type, double delay_penalty, float *costs_d, void *workspace_d,
                                       size_t workspace_bytes, void *stream)
 {
-    if (int rc = lattice_shape("rnnt_lattice_sweeps", B, T, U1)) return rc;
+    if (int rc = lattice_shape("rnnt_lattice_sweeps", B, T, U1, lattice_type != WR_LATTICE_REGULAR || !(delay_penalty == 0.0)))
+        return rc;
     if (int rc = lattice_check("rnnt_lattice_sweeps", lattice_type, delay_penalty)) return rc;
     WR_REQUIRE(logit_lengths_d && target_lengths_d && costs_d && workspace_d, WR_EINVAL,
                "rnnt_lattice_sweeps: null pointer argument");
@@ -247,7 +250,7 @@ extern "C" int wr_rnnt_lattice_export(const void *workspace_d, size_t workspace_
                                       const int32_t *target_lengths_d, int B, int T, int U1, int lattice_type,
                                       float *alpha_d, float *beta_d, void *stream)
 {
-    if (int rc = lattice_shape("rnnt_lattice_export", B, T, U1)) return rc;
+    if (int rc = lattice_shape("rnnt_lattice_export", B, T, U1, true)) return rc;
     if (int rc = lattice_check("rnnt_lattice_export", lattice_type, 0.0)) return rc;
     WR_REQUIRE(workspace_d && alpha_d && beta_d && logit_lengths_d && target_lengths_d, WR_EINVAL,
                "rnnt_lattice_export: null pointer argument");

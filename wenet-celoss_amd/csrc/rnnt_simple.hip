@@ -898,9 +898,12 @@ int smooth_check(const char *what, float ll, float la, int V)
     WR_REQUIRE(ll >= 0.f && la >= 0.f, WR_EINVAL, "%s: lm_only_scale %g and am_only_scale %g must not be negative", what,
                (double)ll, (double)la);
     WR_REQUIRE(ll + la <= 1.f, WR_EINVAL, "%s: lm_only_scale + am_only_scale = %g exceeds 1", what, (double)(ll + la));
-    WR_REQUIRE(V <= 256 * 65535, WR_EUNSUPPORTED, "%s: V = %d exceeds %d", what, V, 256 * 65535);
+    WR_REQUIRE((ll == 0.f && la == 0.f) || V <= 256 * 65535, WR_EUNSUPPORTED, "%s: V = %d exceeds %d", what, V, 256 * 65535);
     return WR_OK;
 }
+
+// The scratch a call with these scales touches: with both 0 only the simple loss's part, where SmoothWs begins.
+inline size_t smooth_ws_required(const SmoothWs &mw, float ll, float la) { return ll == 0.f && la == 0.f ? mw.s.total : mw.total; }
 
 }  // namespace
 }  // namespace wr
@@ -913,77 +916,32 @@ extern "C" size_t wr_rnnt_simple_workspace_bytes(int B, int T, int U1, int V)
     return simple_ws_layout(B, T, U1).total;
 }
 
-extern "C" int wr_rnnt_simple_stats(const float *am_d, const float *lm_d, const int32_t *symbols_d,
-                                    const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1,
-                                    int V, int blank, void *simple_workspace_d, size_t simple_workspace_bytes,
-                                    void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream)
-{
-    if (int rc = simple_check("rnnt_simple_stats", B, T, U1, V, blank)) return rc;
-    WR_REQUIRE(am_d && lm_d && logit_lengths_d && target_lengths_d && simple_workspace_d && rnnt_workspace_d, WR_EINVAL,
-               "rnnt_simple_stats: null pointer argument");
-    WR_REQUIRE(symbols_d || U1 == 1, WR_EINVAL, "rnnt_simple_stats: symbols is null");
-    const SimpleWs sw = simple_ws_layout(B, T, U1);
-    const RnntWs w = rnnt_ws_layout(B, T, U1);
-    WR_REQUIRE(simple_workspace_bytes >= sw.total, WR_EWORKSPACE, "rnnt_simple_stats: workspace %zu < required %zu",
-               simple_workspace_bytes, sw.total);
-    WR_REQUIRE(rnnt_workspace_bytes >= w.total, WR_EWORKSPACE, "rnnt_simple_stats: rnnt workspace %zu < required %zu",
-               rnnt_workspace_bytes, w.total);
-    return simple_stats_launch(am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, sw, w,
-                               static_cast<char *>(simple_workspace_d), static_cast<char *>(rnnt_workspace_d),
-                               static_cast<hipStream_t>(stream));
-}
-
-extern "C" int wr_rnnt_simple_grad(const float *am_d, const float *lm_d, const int32_t *symbols_d,
-                                   const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1,
-                                   int V, int blank, const float *grad_costs_d, float *d_am_d, float *d_lm_d,
-                                   float *occ_emit_d, float *occ_blank_d, void *simple_workspace_d,
-                                   size_t simple_workspace_bytes, const void *rnnt_workspace_d,
-                                   size_t rnnt_workspace_bytes, void *stream)
-{
-    if (int rc = simple_check("rnnt_simple_grad", B, T, U1, V, blank)) return rc;
-    WR_REQUIRE(am_d && lm_d && logit_lengths_d && target_lengths_d && d_am_d && d_lm_d && simple_workspace_d &&
-                   rnnt_workspace_d, WR_EINVAL, "rnnt_simple_grad: null pointer argument");
-    WR_REQUIRE(symbols_d || U1 == 1, WR_EINVAL, "rnnt_simple_grad: symbols is null");
-    const SimpleWs sw = simple_ws_layout(B, T, U1);
-    const RnntWs w = rnnt_ws_layout(B, T, U1);
-    WR_REQUIRE(simple_workspace_bytes >= sw.total, WR_EWORKSPACE, "rnnt_simple_grad: workspace %zu < required %zu",
-               simple_workspace_bytes, sw.total);
-    WR_REQUIRE(rnnt_workspace_bytes >= w.total, WR_EWORKSPACE, "rnnt_simple_grad: rnnt workspace %zu < required %zu",
-               rnnt_workspace_bytes, w.total);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char *sws = static_cast<char *>(simple_workspace_d);
-    if (int rc = simple_grad_launch(am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, grad_costs_d,
-                                    d_am_d, d_lm_d, occ_emit_d, occ_blank_d, sw, w, sws,
-                                    static_cast<const char *>(rnnt_workspace_d), 1.f, false, false, st))
-        return rc;
-    return simple_fix_launch(symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, d_am_d, d_lm_d, sw, sws, 1.f,
-                             1.f, false, st);
-}
-
 extern "C" size_t wr_rnnt_smoothed_workspace_bytes(int B, int T, int U1, int V)
 {
     if (B <= 0 || T <= 0 || U1 <= 0 || V <= 0) return 0;
     return smooth_ws_layout(B, T, U1, V).total;
 }
 
-extern "C" int wr_rnnt_smoothed_stats(const float *am_d, const float *lm_d, const int32_t *symbols_d,
-                                      const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T,
-                                      int U1, int V, int blank, float lm_only_scale, float am_only_scale,
-                                      void *smoothed_workspace_d, size_t smoothed_workspace_bytes, void *rnnt_workspace_d,
-                                      size_t rnnt_workspace_bytes, void *stream)
+// wr_rnnt_smoothed_stats, and with both scales 0 wr_rnnt_simple_stats; `what` names the entry point in messages.
+static int smoothed_stats_impl(const char *what, const float *am_d, const float *lm_d, const int32_t *symbols_d,
+                               const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1, int V,
+                               int blank, float lm_only_scale, float am_only_scale, void *smoothed_workspace_d,
+                               size_t smoothed_workspace_bytes, void *rnnt_workspace_d, size_t rnnt_workspace_bytes,
+                               void *stream)
 {
     const float ll = lm_only_scale, la = am_only_scale;
-    if (int rc = simple_check("rnnt_smoothed_stats", B, T, U1, V, blank)) return rc;
-    if (int rc = smooth_check("rnnt_smoothed_stats", ll, la, V)) return rc;
-    WR_REQUIRE(am_d && lm_d && logit_lengths_d && target_lengths_d && smoothed_workspace_d && rnnt_workspace_d, WR_EINVAL,
-               "rnnt_smoothed_stats: null pointer argument");
-    WR_REQUIRE(symbols_d || U1 == 1, WR_EINVAL, "rnnt_smoothed_stats: symbols is null");
+    if (int rc = simple_check(what, B, T, U1, V, blank)) return rc;
+    if (int rc = smooth_check(what, ll, la, V)) return rc;
     const SmoothWs mw = smooth_ws_layout(B, T, U1, V);
     const RnntWs w = rnnt_ws_layout(B, T, U1);
-    WR_REQUIRE(smoothed_workspace_bytes >= mw.total, WR_EWORKSPACE, "rnnt_smoothed_stats: workspace %zu < required %zu",
-               smoothed_workspace_bytes, mw.total);
-    WR_REQUIRE(rnnt_workspace_bytes >= w.total, WR_EWORKSPACE, "rnnt_smoothed_stats: rnnt workspace %zu < required %zu",
+    const size_t need = smooth_ws_required(mw, ll, la);
+    WR_REQUIRE(smoothed_workspace_bytes >= need, WR_EWORKSPACE, "%s: workspace %zu < required %zu", what,
+               smoothed_workspace_bytes, need);
+    WR_REQUIRE(rnnt_workspace_bytes >= w.total, WR_EWORKSPACE, "%s: rnnt workspace %zu < required %zu", what,
                rnnt_workspace_bytes, w.total);
+    WR_REQUIRE(am_d && lm_d && logit_lengths_d && target_lengths_d && smoothed_workspace_d && rnnt_workspace_d, WR_EINVAL,
+               "%s: null pointer argument", what);
+    WR_REQUIRE(symbols_d || U1 == 1, WR_EINVAL, "%s: symbols is null", what);
     hipStream_t st = static_cast<hipStream_t>(stream);
     char *sws = static_cast<char *>(smoothed_workspace_d), *ws = static_cast<char *>(rnnt_workspace_d);
     if (int rc = simple_stats_launch(am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, mw.s, w,
@@ -1025,30 +983,32 @@ extern "C" int wr_rnnt_smoothed_stats(const float *am_d, const float *lm_d, cons
     return WR_OK;
 }
 
-// wr_rnnt_smoothed_grad and wr_rnnt_smoothed_grad_lattice.  On the modified lattice every arc is subtracted at its own
-// symbol whatever the scales (a label equal to the blank has both terms), as under smoothing.
-static int smoothed_grad_impl(const float *am_d, const float *lm_d, const int32_t *symbols_d,
-                              const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1, int V,
-                              int blank, float lm_only_scale, float am_only_scale, const float *grad_costs_d,
-                              float *d_am_d, float *d_lm_d, float *occ_emit_d, float *occ_blank_d,
-                              void *smoothed_workspace_d, size_t smoothed_workspace_bytes, const void *rnnt_workspace_d,
-                              size_t rnnt_workspace_bytes, bool modified, void *stream)
+// wr_rnnt_smoothed_grad, wr_rnnt_smoothed_grad_lattice and, with both scales 0 and `need_grads`, wr_rnnt_simple_grad;
+// `what` names the entry point in messages.  On the modified lattice every arc is subtracted at its own symbol whatever
+// the scales (a label equal to the blank has both terms), as under smoothing.
+static int smoothed_grad_impl(const char *what, bool need_grads, const float *am_d, const float *lm_d,
+                              const int32_t *symbols_d, const int32_t *logit_lengths_d, const int32_t *target_lengths_d,
+                              int B, int T, int U1, int V, int blank, float lm_only_scale, float am_only_scale,
+                              const float *grad_costs_d, float *d_am_d, float *d_lm_d, float *occ_emit_d,
+                              float *occ_blank_d, void *smoothed_workspace_d, size_t smoothed_workspace_bytes,
+                              const void *rnnt_workspace_d, size_t rnnt_workspace_bytes, bool modified, void *stream)
 {
     const float ll = lm_only_scale, la = am_only_scale;
-    if (int rc = simple_check("rnnt_smoothed_grad", B, T, U1, V, blank)) return rc;
-    if (int rc = smooth_check("rnnt_smoothed_grad", ll, la, V)) return rc;
-    const bool occ_only = !d_am_d && !d_lm_d;
-    WR_REQUIRE(am_d && lm_d && logit_lengths_d && target_lengths_d && smoothed_workspace_d && rnnt_workspace_d, WR_EINVAL,
-               "rnnt_smoothed_grad: null pointer argument");
-    WR_REQUIRE(occ_only ? (occ_emit_d && occ_blank_d) : (d_am_d && d_lm_d), WR_EINVAL,
-               "rnnt_smoothed_grad: d_am and d_lm go together; without them both occupancy outputs are needed");
-    WR_REQUIRE(symbols_d || U1 == 1, WR_EINVAL, "rnnt_smoothed_grad: symbols is null");
+    if (int rc = simple_check(what, B, T, U1, V, blank)) return rc;
+    if (int rc = smooth_check(what, ll, la, V)) return rc;
     const SmoothWs mw = smooth_ws_layout(B, T, U1, V);
     const RnntWs w = rnnt_ws_layout(B, T, U1);
-    WR_REQUIRE(smoothed_workspace_bytes >= mw.total, WR_EWORKSPACE, "rnnt_smoothed_grad: workspace %zu < required %zu",
-               smoothed_workspace_bytes, mw.total);
-    WR_REQUIRE(rnnt_workspace_bytes >= w.total, WR_EWORKSPACE, "rnnt_smoothed_grad: rnnt workspace %zu < required %zu",
+    const size_t need = smooth_ws_required(mw, ll, la);
+    WR_REQUIRE(smoothed_workspace_bytes >= need, WR_EWORKSPACE, "%s: workspace %zu < required %zu", what,
+               smoothed_workspace_bytes, need);
+    WR_REQUIRE(rnnt_workspace_bytes >= w.total, WR_EWORKSPACE, "%s: rnnt workspace %zu < required %zu", what,
                rnnt_workspace_bytes, w.total);
+    const bool occ_only = !d_am_d && !d_lm_d;
+    WR_REQUIRE(am_d && lm_d && logit_lengths_d && target_lengths_d && smoothed_workspace_d && rnnt_workspace_d &&
+                   (!need_grads || (d_am_d && d_lm_d)), WR_EINVAL, "%s: null pointer argument", what);
+    WR_REQUIRE(occ_only ? (occ_emit_d && occ_blank_d) : (d_am_d && d_lm_d), WR_EINVAL,
+               "%s: d_am and d_lm go together; without them both occupancy outputs are needed", what);
+    WR_REQUIRE(symbols_d || U1 == 1, WR_EINVAL, "%s: symbols is null", what);
     hipStream_t st = static_cast<hipStream_t>(stream);
     char *sws = static_cast<char *>(smoothed_workspace_d);
     const bool smooth = ll != 0.f || la != 0.f;
@@ -1097,6 +1057,39 @@ static int smoothed_grad_impl(const float *am_d, const float *lm_d, const int32_
                              smooth ? c + la : 1.f, smooth ? c + ll : 1.f, smooth || modified, st);
 }
 
+extern "C" int wr_rnnt_smoothed_stats(const float *am_d, const float *lm_d, const int32_t *symbols_d,
+                                      const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T,
+                                      int U1, int V, int blank, float lm_only_scale, float am_only_scale,
+                                      void *smoothed_workspace_d, size_t smoothed_workspace_bytes, void *rnnt_workspace_d,
+                                      size_t rnnt_workspace_bytes, void *stream)
+{
+    return smoothed_stats_impl("rnnt_smoothed_stats", am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V,
+                               blank, lm_only_scale, am_only_scale, smoothed_workspace_d, smoothed_workspace_bytes,
+                               rnnt_workspace_d, rnnt_workspace_bytes, stream);
+}
+
+extern "C" int wr_rnnt_simple_stats(const float *am_d, const float *lm_d, const int32_t *symbols_d,
+                                    const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1,
+                                    int V, int blank, void *simple_workspace_d, size_t simple_workspace_bytes,
+                                    void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream)
+{
+    return smoothed_stats_impl("rnnt_simple_stats", am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V,
+                               blank, 0.f, 0.f, simple_workspace_d, simple_workspace_bytes, rnnt_workspace_d,
+                               rnnt_workspace_bytes, stream);
+}
+
+extern "C" int wr_rnnt_simple_grad(const float *am_d, const float *lm_d, const int32_t *symbols_d,
+                                   const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1,
+                                   int V, int blank, const float *grad_costs_d, float *d_am_d, float *d_lm_d,
+                                   float *occ_emit_d, float *occ_blank_d, void *simple_workspace_d,
+                                   size_t simple_workspace_bytes, const void *rnnt_workspace_d,
+                                   size_t rnnt_workspace_bytes, void *stream)
+{
+    return smoothed_grad_impl("rnnt_simple_grad", true, am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1,
+                              V, blank, 0.f, 0.f, grad_costs_d, d_am_d, d_lm_d, occ_emit_d, occ_blank_d, simple_workspace_d,
+                              simple_workspace_bytes, rnnt_workspace_d, rnnt_workspace_bytes, false, stream);
+}
+
 extern "C" int wr_rnnt_smoothed_grad(const float *am_d, const float *lm_d, const int32_t *symbols_d,
                                      const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T,
                                      int U1, int V, int blank, float lm_only_scale, float am_only_scale,
@@ -1104,9 +1097,10 @@ extern "C" int wr_rnnt_smoothed_grad(const float *am_d, const float *lm_d, const
                                      float *occ_blank_d, void *smoothed_workspace_d, size_t smoothed_workspace_bytes,
                                      const void *rnnt_workspace_d, size_t rnnt_workspace_bytes, void *stream)
 {
-    return smoothed_grad_impl(am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, lm_only_scale,
-                              am_only_scale, grad_costs_d, d_am_d, d_lm_d, occ_emit_d, occ_blank_d, smoothed_workspace_d,
-                              smoothed_workspace_bytes, rnnt_workspace_d, rnnt_workspace_bytes, false, stream);
+    return smoothed_grad_impl("rnnt_smoothed_grad", false, am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T,
+                              U1, V, blank, lm_only_scale, am_only_scale, grad_costs_d, d_am_d, d_lm_d, occ_emit_d,
+                              occ_blank_d, smoothed_workspace_d, smoothed_workspace_bytes, rnnt_workspace_d,
+                              rnnt_workspace_bytes, false, stream);
 }
 
 extern "C" int wr_rnnt_smoothed_grad_lattice(const float *am_d, const float *lm_d, const int32_t *symbols_d,
@@ -1118,8 +1112,8 @@ extern "C" int wr_rnnt_smoothed_grad_lattice(const float *am_d, const float *lm_
                                              size_t rnnt_workspace_bytes, void *stream)
 {
     if (int rc = lattice_check("rnnt_smoothed_grad_lattice", lattice_type, 0.0)) return rc;
-    return smoothed_grad_impl(am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, lm_only_scale,
-                              am_only_scale, grad_costs_d, d_am_d, d_lm_d, occ_emit_d, occ_blank_d, smoothed_workspace_d,
-                              smoothed_workspace_bytes, rnnt_workspace_d, rnnt_workspace_bytes,
-                              lattice_type == WR_LATTICE_MODIFIED, stream);
+    return smoothed_grad_impl("rnnt_smoothed_grad_lattice", false, am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d,
+                              B, T, U1, V, blank, lm_only_scale, am_only_scale, grad_costs_d, d_am_d, d_lm_d, occ_emit_d,
+                              occ_blank_d, smoothed_workspace_d, smoothed_workspace_bytes, rnnt_workspace_d,
+                              rnnt_workspace_bytes, lattice_type == WR_LATTICE_MODIFIED, stream);
 }

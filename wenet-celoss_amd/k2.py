@@ -4,7 +4,8 @@ written against ``k2.rnnt_loss_simple`` / ``rnnt_loss_smoothed`` / ``rnnt_loss_p
 
 The package-level functions of the same names keep the signatures they have always had (regular lattice, no penalty; their
 tests pin those signatures); the functions here add the two keyword-only arguments and, for the prune ranges, the
-(B, U, T) ``px_grad`` of the modified lattice.  With the defaults each is the package-level function, bit for bit.
+(B, U, T) ``px_grad`` of the modified lattice.  Both forms call one body (`rnnt_simple.loss`, `rnnt_pruned.prune_ranges`),
+the package-level ones with the defaults: the same path, the same bits.
 
   rnnt_type = "regular"    a label arc stays on its frame; a final blank leaves (T_b-1, U_b)
   rnnt_type = "modified"   a label arc consumes a frame: exactly one arc per frame, T_b >= U_b (else the cost is +inf)
@@ -15,17 +16,15 @@ include/wr_api.h, "Lattice types and the delay penalty").
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple, Union
+from typing import Optional
 
 import torch
 
-from . import rnnt_lattice as _lat
 from . import rnnt_pruned as _pruned
 from . import rnnt_simple as _simple
-from . import rnnt_smoothed as _smoothed
 from .rnnt_pruned import do_rnnt_pruning, rnnt_loss_pruned  # noqa: F401  (rnnt_loss_pruned has the keywords itself)
 
-_Loss = Union[torch.Tensor, Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]]
+_Loss = _simple._Loss
 
 
 def rnnt_loss_simple(lm: torch.Tensor, am: torch.Tensor, symbols: torch.Tensor, termination_symbol: int,
@@ -35,15 +34,8 @@ def rnnt_loss_simple(lm: torch.Tensor, am: torch.Tensor, symbols: torch.Tensor, 
     delay_penalty=): `wenet_celoss_amd.rnnt_loss_simple` on the lattice of ``rnnt_type`` with the delay penalty.  With
     "modified" ``px_grad`` is (B, U, T), k2's shape for that lattice (no extra frame column); ``py_grad`` stays
     (B, U+1, T).  The two arguments are checked before anything else."""
-    what = "rnnt_loss_simple"
-    lat, pen = _lat.check_lattice(what, rnnt_type, delay_penalty)
-    if _lat.is_default(lat, pen):
-        return _simple.rnnt_loss_simple(lm, am, symbols, termination_symbol, boundary, reduction, return_grad)
-    if reduction not in ("none", "mean", "sum"):
-        raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
-    sy, ll, tl, blank, _ = _simple._prepare(lm, am, symbols, termination_symbol, boundary, what)
-    _simple._require_device(what, lm, am)
-    return _lat.loss(lm, am, sy, ll, tl, blank, 0.0, 0.0, lat, pen, reduction, return_grad)
+    return _simple.loss("rnnt_loss_simple", lm, am, symbols, termination_symbol, 0.0, 0.0, boundary, reduction,
+                        return_grad, rnnt_type, delay_penalty)
 
 
 def rnnt_loss_smoothed(lm: torch.Tensor, am: torch.Tensor, symbols: torch.Tensor, termination_symbol: int,
@@ -53,17 +45,8 @@ def rnnt_loss_smoothed(lm: torch.Tensor, am: torch.Tensor, symbols: torch.Tensor
     """k2.rnnt_loss_smoothed(..., rnnt_type=, delay_penalty=): `wenet_celoss_amd.rnnt_loss_smoothed` on the lattice of
     ``rnnt_type``; the penalty is added to the interpolated label arcs (it is not scaled by ``1 - lm_only_scale -
     am_only_scale``).  ``px_grad`` as in `rnnt_loss_simple` above."""
-    what = "rnnt_loss_smoothed"
-    lat, pen = _lat.check_lattice(what, rnnt_type, delay_penalty)
-    if _lat.is_default(lat, pen):
-        return _smoothed.rnnt_loss_smoothed(lm, am, symbols, termination_symbol, lm_only_scale, am_only_scale, boundary,
-                                            reduction, return_grad)
-    if reduction not in ("none", "mean", "sum"):
-        raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
-    lm_scale, am_scale = _smoothed._check_scales(what, lm_only_scale, am_only_scale)
-    sy, ll, tl, blank, _ = _simple._prepare(lm, am, symbols, termination_symbol, boundary, what)
-    _simple._require_device(what, lm, am)
-    return _lat.loss(lm, am, sy, ll, tl, blank, lm_scale, am_scale, lat, pen, reduction, return_grad)
+    return _simple.loss("rnnt_loss_smoothed", lm, am, symbols, termination_symbol, lm_only_scale, am_only_scale, boundary,
+                        reduction, return_grad, rnnt_type, delay_penalty)
 
 
 def get_rnnt_prune_ranges(px_grad: torch.Tensor, py_grad: torch.Tensor, boundary: torch.Tensor, s_range: int

@@ -1,13 +1,14 @@
-"""Lattice types and the delay penalty of the k2 RNN-T losses: what ``rnnt_type=`` and ``delay_penalty=`` of
-`k2.rnnt_loss_simple`, `k2.rnnt_loss_smoothed` (k2.py) and `rnnt_loss_pruned` route to (csrc/rnnt_lattice.hip; the
-contract is in include/wr_api.h, "Lattice types and the delay penalty"; DESIGN.md, "Modified lattice and delay penalty").
+"""What the k2 RNN-T losses share (rnnt_simple.py, rnnt_smoothed.py, rnnt_pruned.py, k2.py): the ``rnnt_type=`` /
+``delay_penalty=`` arguments, the boundary / symbols preparation with its one host sync and the device check, the lattice
+sweeps, the occupancy layout and the diagnostics (csrc/rnnt_lattice.hip; the contract is in include/wr_api.h, "Lattice
+types and the delay penalty"; DESIGN.md, "Modified lattice and delay penalty").
 
   rnnt_type = "regular"    a label arc stays on its frame, (t,u) -> (t,u+1); a final blank leaves (T_b-1, U_b)
   rnnt_type = "modified"   a label arc consumes a frame, (t,u) -> (t+1,u+1): exactly one arc per frame, T_b >= U_b
   delay_penalty            ``delay_penalty * ((T_b - 1) / 2 - t)`` added to every label arc's log-probability
 
-``"constrained"`` is not offered (NotImplementedError).  The defaults take the code path the functions had before these
-arguments existed.
+``"constrained"`` is not offered (NotImplementedError).  There is one path: every loss hands its lattice type and penalty
+to the `*_lattice` / `*_cols` entry points, which for the defaults launch the kernels of the plain entry points.
 """
 from __future__ import annotations
 
@@ -38,6 +39,58 @@ def is_default(lat: int, pen: float) -> bool:
     return lat == 0 and pen == 0.0
 
 
+def require_device(what: str, who: str, *tensors) -> None:
+    if not all(t.is_cuda for t in tensors):
+        raise RuntimeError(f"wenet_celoss_amd.{what}: {who} must live on a HIP device (this package has no CPU path)")
+
+
+def prepare(what: str, who: str, on, B: int, T: int, U: int, boundary, symbols=None, V: int = 0, more=(),
+            min_frames: int = 0):
+    """Boundary, symbols and device of a k2 loss -> (T_b int32, U_b int32, symbols int32 or None) on the device of
+    ``on[0]``.  ``boundary`` None = rows ``(0, 0, U, T)``.  One host sync checks the rows (begins zero, 0 <= U_b <= U,
+    0 <= T_b <= T), the labels inside each length (within [0, V); those past it become 0), whatever ``more`` adds --
+    (one-element count of violations on the device, error text) pairs -- and T_b >= ``min_frames``.  Full lengths with
+    nothing else to check need no sync.  The device check (``who`` names the tensors ``on``) comes last, so bad values
+    in CPU tensors still raise ValueError."""
+    dev = on[0].device
+    if boundary is None:
+        bd = torch.tensor([0, 0, U, T], dtype=torch.int64, device=dev).repeat(B, 1)
+    else:
+        if boundary.dim() != 2 or boundary.shape[0] != B or boundary.shape[1] != 4:
+            raise ValueError(f"{what}: boundary must be (B, 4) = ({B}, 4), got {tuple(boundary.shape)}")
+        bd = boundary.to(device=dev, dtype=torch.int64)
+    counts, sy = list(more), None
+    if symbols is not None:
+        sy = symbols.to(device=dev)
+        inside = torch.arange(U, device=dev)[None, :] < bd[:, 2:3]
+        counts.insert(0, ((inside & ((sy < 0) | (sy >= V))).sum().reshape(1),
+                          f"{what}: a symbol inside its boundary lies outside [0, {V})"))
+        sy = torch.where(inside, sy, torch.zeros((), dtype=sy.dtype, device=dev)).to(torch.int32).contiguous()
+    if boundary is not None or counts:
+        host = (torch.cat([bd.reshape(-1)] + [c for c, _ in counts]) if counts else bd.reshape(-1)).cpu()  # one host sync
+        rows = host[:4 * B].reshape(B, 4)
+        if B and int(rows[:, :2].abs().max()) != 0:
+            raise ValueError(f"{what}: boundary rows must begin at (0, 0) (got {rows[:, :2].tolist()})")
+        if B and (int(rows[:, 2].min()) < 0 or int(rows[:, 2].max()) > U):
+            raise ValueError(f"{what}: boundary symbol ends must lie in [0, {U}] (got {rows[:, 2].tolist()})")
+        if B and (int(rows[:, 3].min()) < 0 or int(rows[:, 3].max()) > T):
+            raise ValueError(f"{what}: boundary frame ends must lie in [0, {T}] (got {rows[:, 3].tolist()})")
+        for bad, (_, text) in zip(host[4 * B:].tolist(), counts):
+            if bad != 0:
+                raise ValueError(text)
+        if B and int(rows[:, 3].min()) < min_frames:
+            raise ValueError(f"{what}: boundary frame ends must be at least {min_frames} (got {rows[:, 3].tolist()})")
+    require_device(what, who, *on)
+    return bd[:, 3].to(torch.int32).contiguous(), bd[:, 2].to(torch.int32).contiguous(), sy
+
+
+def sweeps(rws: torch.Tensor, ll, tl, B: int, T: int, U1: int, lat: int, pen: float) -> torch.Tensor:
+    """The lattice sweeps over the arcs a statistics call left in the RNN-T workspace ``rws``: costs (B,) float32."""
+    costs = torch.empty(B, dtype=torch.float32, device=rws.device)
+    _lib.call("wr_rnnt_lattice_sweeps", ll, tl, B, T, U1, lat, pen, costs, rws, rws.numel(), device=rws.device)
+    return costs
+
+
 def occupancies_to_k2(occ_emit: torch.Tensor, occ_blank: torch.Tensor, lat: int):
     """(B, T, U+1) arc occupancies -> k2's (px_grad, py_grad): px_grad (B, U, T+1) with a zero last column for the
     regular lattice, (B, U, T) for the modified one; py_grad (B, U+1, T)."""
@@ -50,87 +103,13 @@ def occupancies_to_k2(occ_emit: torch.Tensor, occ_blank: torch.Tensor, lat: int)
     return px_grad, occ_blank.transpose(1, 2).contiguous()
 
 
-def _stats(lm, am, sy, ll, tl, blank, lm_scale, am_scale):
-    """Arcs of the (smoothed; both scales 0: simple) lattice into a fresh RNN-T workspace."""
-    B, U1, V = lm.shape
-    T = am.shape[1]
-    dev = lm.device
-    sws = _lib.workspace("wr_rnnt_smoothed_workspace_bytes", B, T, U1, V, device=dev)
-    rws = _lib.workspace("wr_rnnt_workspace_bytes", B, T, U1, device=dev)
-    _lib.call("wr_rnnt_smoothed_stats", am, lm, sy, ll, tl, B, T, U1, V, blank, lm_scale, am_scale, sws, sws.numel(), rws,
-              rws.numel(), device=dev)
-    return sws, rws
-
-
-class _RNNTLatticeFn(torch.autograd.Function):
-    """`rnnt_loss_simple` / `rnnt_loss_smoothed` with a non-default lattice type or penalty: `_RNNTSmoothedFn` with the
-    sweeps and the gradient of that lattice."""
-
-    @staticmethod
-    def forward(ctx, lm, am, sy, ll, tl, blank, lm_scale, am_scale, lat, pen, want_occ):
-        B, U1, V = lm.shape
-        T = am.shape[1]
-        dev = lm.device
-        lm, am = lm.contiguous(), am.contiguous()
-        sws, rws = _stats(lm, am, sy, ll, tl, blank, lm_scale, am_scale)
-        costs = torch.empty(B, dtype=torch.float32, device=dev)
-        _lib.call("wr_rnnt_lattice_sweeps", ll, tl, B, T, U1, lat, pen, costs, rws, rws.numel(), device=dev)
-        ctx.blank, ctx.scales, ctx.lat, ctx.want_occ = blank, (lm_scale, am_scale), lat, want_occ
-        # the rule of _RNNTSmoothedFn: with am_only_scale > 0 the gradient cannot be taken with unit grad_costs
-        ctx.early = want_occ and am_scale == 0.0
-        if not want_occ:
-            ctx.save_for_backward(lm, am, sy, ll, tl, sws, rws)
-            return costs
-        occ_emit = torch.empty(B, T, U1, dtype=torch.float32, device=dev)
-        occ_blank = torch.empty_like(occ_emit)
-        d_am, d_lm = (torch.empty_like(am), torch.empty_like(lm)) if ctx.early else (None, None)
-        _lib.call("wr_rnnt_smoothed_grad_lattice", am, lm, sy, ll, tl, B, T, U1, V, blank, lm_scale, am_scale, lat, None,
-                  d_am, d_lm, occ_emit, occ_blank, sws, sws.numel(), rws, rws.numel(), device=dev)
-        if ctx.early:
-            ctx.save_for_backward(d_lm, d_am)
-        else:
-            ctx.save_for_backward(lm, am, sy, ll, tl, sws, rws)
-        ctx.mark_non_differentiable(occ_emit, occ_blank)
-        return costs, occ_emit, occ_blank
-
-    @staticmethod
-    def backward(ctx, grad_costs, *unused):
-        gc = grad_costs.to(torch.float32).contiguous()
-        none = (None,) * 9
-        if ctx.early:
-            d_lm, d_am = ctx.saved_tensors
-            return (d_lm * gc[:, None, None], d_am * gc[:, None, None]) + none
-        lm, am, sy, ll, tl, sws, rws = ctx.saved_tensors
-        B, U1, V = lm.shape
-        T = am.shape[1]
-        d_am, d_lm = torch.empty_like(am), torch.empty_like(lm)
-        _lib.call("wr_rnnt_smoothed_grad_lattice", am, lm, sy, ll, tl, B, T, U1, V, ctx.blank, ctx.scales[0],
-                  ctx.scales[1], ctx.lat, gc, d_am, d_lm, None, None, sws, sws.numel(), rws, rws.numel(), device=lm.device)
-        return (d_lm, d_am) + none
-
-
-def loss(lm, am, sy, ll, tl, blank, lm_scale, am_scale, lat, pen, reduction, return_grad):
-    """The tail of rnnt_loss_simple / rnnt_loss_smoothed for a non-default lattice: inputs already checked."""
-    out = _RNNTLatticeFn.apply(lm.float(), am.float(), sy, ll, tl, blank, lm_scale, am_scale, lat, pen, bool(return_grad))
-    costs = out[0] if return_grad else out
-    res = costs.mean() if reduction == "mean" else (costs.sum() if reduction == "sum" else costs)
-    if not return_grad:
-        return res
-    return res, occupancies_to_k2(out[1].detach(), out[2].detach(), lat)
-
-
 @torch.no_grad()
-def lattice(lm, am, sy, ll, tl, blank, lm_scale, am_scale, lat, pen):
-    """Diagnostics: (costs, alpha, beta, flag) of the lattice of type `lat`, alpha / beta plain (B, T, U+1)."""
-    lm, am = lm.detach().float().contiguous(), am.detach().float().contiguous()
-    B, U1, _ = lm.shape
-    T = am.shape[1]
-    dev = lm.device
-    _, rws = _stats(lm, am, sy, ll, tl, blank, lm_scale, am_scale)
-    costs = torch.empty(B, dtype=torch.float32, device=dev)
-    alpha = torch.empty(B, T, U1, dtype=torch.float32, device=dev)
+def lattice(rws: torch.Tensor, ll, tl, B: int, T: int, U1: int, lat: int, pen: float):
+    """Diagnostics: the sweeps, then (costs, alpha, beta, flag) -- alpha / beta as plain (B, T, U+1) tensors, flag the
+    workspace's "row statistics were redone by the direct kernel" word (a one-element int32 tensor)."""
+    costs = sweeps(rws, ll, tl, B, T, U1, lat, pen)
+    alpha = torch.empty(B, T, U1, dtype=torch.float32, device=rws.device)
     beta = torch.empty_like(alpha)
-    _lib.call("wr_rnnt_lattice_sweeps", ll, tl, B, T, U1, lat, pen, costs, rws, rws.numel(), device=dev)
-    _lib.call("wr_rnnt_lattice_export", rws, rws.numel(), ll, tl, B, T, U1, lat, alpha, beta, device=dev)
-    flag = rws[-256:-252].view(torch.int32).clone()
+    _lib.call("wr_rnnt_lattice_export", rws, rws.numel(), ll, tl, B, T, U1, lat, alpha, beta, device=rws.device)
+    flag = rws[-256:-252].view(torch.int32).clone()       # the last 256-byte slot of the workspace (wr_common.hpp RnntWs)
     return costs, alpha, beta, flag

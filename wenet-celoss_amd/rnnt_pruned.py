@@ -8,8 +8,10 @@ per frame, a band of ``s_range`` label positions, and the real joiner and the re
   do_rnnt_pruning         the joiner's two addends gathered onto the band: (B, T, R, C) each, differentiable
   rnnt_loss_pruned        the RNN-T loss of logits (B, T, R, V) given on the band (one autograd node)
 
-``rnnt_loss_pruned`` takes ``rnnt_type="modified"`` and ``delay_penalty`` (rnnt_lattice.py); `k2.get_rnnt_prune_ranges`
-(k2.py) also takes the (B, U, T) ``px_grad`` of a modified-lattice simple loss.  Not offered: ``rnnt_type="constrained"``.
+``rnnt_loss_pruned`` takes ``rnnt_type="modified"`` and ``delay_penalty``; `k2.get_rnnt_prune_ranges` (k2.py) also takes
+the (B, U, T) ``px_grad`` of a modified-lattice simple loss.  Not offered: ``rnnt_type="constrained"``.  The lattice
+arguments, the boundary preparation and the sweeps are rnnt_lattice.py's, shared with the additive-joiner losses; the
+defaults go through the same calls as every other setting.
 """
 from __future__ import annotations
 
@@ -21,34 +23,12 @@ from . import _lib
 from . import rnnt_lattice as _lat
 
 
-def _check_boundary_rows(rows, B: int, T: int, U: int, what: str) -> None:
-    if B and int(rows[:, :2].abs().max()) != 0:
-        raise ValueError(f"{what}: boundary rows must begin at (0, 0) (got {rows[:, :2].tolist()})")
-    if B and (int(rows[:, 2].min()) < 0 or int(rows[:, 2].max()) > U):
-        raise ValueError(f"{what}: boundary symbol ends must lie in [0, {U}] (got {rows[:, 2].tolist()})")
-    if B and (int(rows[:, 3].min()) < 0 or int(rows[:, 3].max()) > T):
-        raise ValueError(f"{what}: boundary frame ends must lie in [0, {T}] (got {rows[:, 3].tolist()})")
-
-
-def _boundary(boundary, B: int, T: int, U: int, dev, what: str) -> torch.Tensor:
-    if boundary is None:
-        return torch.tensor([0, 0, U, T], dtype=torch.int64, device=dev).repeat(B, 1)
-    if boundary.dim() != 2 or boundary.shape[0] != B or boundary.shape[1] != 4:
-        raise ValueError(f"{what}: boundary must be (B, 4) = ({B}, 4), got {tuple(boundary.shape)}")
-    return boundary.to(device=dev, dtype=torch.int64)
-
-
 def _bad_ranges(ranges: torch.Tensor, U1: int) -> torch.Tensor:
     """Number of violations of ``ranges[..., r] == ranges[..., 0] + r`` inside [0, U1 - 1], as a one-element tensor."""
     R = ranges.shape[-1]
     first = ranges[..., :1]
     step = (ranges != first + torch.arange(R, device=ranges.device)).sum()
     return (step + (first < 0).sum() + (first > U1 - R).sum()).reshape(1)
-
-
-def _require_device(what: str, *tensors) -> None:
-    if not all(t.is_cuda for t in tensors):
-        raise RuntimeError(f"wenet_celoss_amd.{what}: the inputs must live on a HIP device (this package has no CPU path)")
 
 
 def get_rnnt_prune_ranges(px_grad: torch.Tensor, py_grad: torch.Tensor, boundary: torch.Tensor, s_range: int
@@ -82,21 +62,14 @@ def prune_ranges(px_grad: torch.Tensor, py_grad: torch.Tensor, boundary: torch.T
         raise ValueError(f"{what}: s_range must be at least {1 if px_cols == T else 2} (got {s_range})")
     if B < 1 or T < 1:
         raise ValueError(f"{what}: empty batch or no frames")
-    _require_device(what, px_grad, py_grad)
     dev = py_grad.device
-    bd = _boundary(boundary, B, T, U1 - 1, dev, what)
-    if boundary is not None:                                                # full lengths need no check and no sync
-        _check_boundary_rows(bd.cpu(), B, T, U1 - 1, what)                  # the one host sync
+    # full lengths need no check and no sync
+    ll, tl, _ = _lat.prepare(what, "the inputs", (py_grad, px_grad), B, T, U1 - 1, boundary)
     R = min(int(s_range), U1)
     px = px_grad.detach().to(torch.float32).contiguous()
     py = py_grad.detach().to(torch.float32).contiguous()
     ranges = torch.empty(B, T, R, dtype=torch.int64, device=dev)
-    if px_cols == T + 1:
-        _lib.call("wr_rnnt_prune_ranges", px if U1 > 1 else None, py, bd[:, 3].to(torch.int32).contiguous(),
-                  bd[:, 2].to(torch.int32).contiguous(), B, T, U1, R, ranges, device=dev)
-    else:
-        _lib.call("wr_rnnt_prune_ranges_cols", px if U1 > 1 else None, px_cols, py, bd[:, 3].to(torch.int32).contiguous(),
-                  bd[:, 2].to(torch.int32).contiguous(), B, T, U1, R, ranges, device=dev)
+    _lib.call("wr_rnnt_prune_ranges_cols", px if U1 > 1 else None, px_cols, py, ll, tl, B, T, U1, R, ranges, device=dev)
     return ranges
 
 
@@ -152,7 +125,7 @@ def do_rnnt_pruning(am: torch.Tensor, lm: torch.Tensor, ranges: torch.Tensor) ->
         raise ValueError(f"{what}: ranges hold R = {R} positions for U + 1 = {U1}")
     if ranges.dtype not in (torch.int32, torch.int64):
         raise ValueError(f"{what}: ranges must be an integer tensor")
-    _require_device(what, am, lm, ranges)
+    _lat.require_device(what, "the inputs", am, lm, ranges)
     rg = ranges.to(torch.int64).contiguous()
     if int(_bad_ranges(rg, U1).item()) != 0:                               # the one host sync
         raise ValueError(f"{what}: ranges must satisfy ranges[..., r] = ranges[..., 0] + r within [0, {U1 - 1}]")
@@ -160,8 +133,8 @@ def do_rnnt_pruning(am: torch.Tensor, lm: torch.Tensor, ranges: torch.Tensor) ->
 
 
 def _prepare(logits, symbols, ranges, termination_symbol, boundary, what: str):
-    """Shapes, blank, boundary, ranges -> (symbols int32, T_b int32, U_b int32, blank, ranges int64), checked with one
-    host sync as `rnnt_simple._prepare` checks its inputs, plus the band's consecutiveness and bounds."""
+    """Shapes, blank, boundary, ranges -> (symbols int32, T_b int32, U_b int32, blank, ranges int64): `rnnt_lattice.prepare`
+    after the shape checks, with the band's consecutiveness and bounds added to its one host sync."""
     if logits.dim() != 4 or ranges.dim() != 3:
         raise ValueError(f"{what}: logits must be (B, T, R, V) and ranges (B, T, R)")
     B, T, R, V = logits.shape
@@ -183,47 +156,31 @@ def _prepare(logits, symbols, ranges, termination_symbol, boundary, what: str):
     blank = int(termination_symbol)
     if not 0 <= blank < V:
         raise ValueError(f"{what}: termination_symbol must be within [0, {V})")
-    _require_device(what, logits)
-    dev = logits.device
-    bd = _boundary(boundary, B, T, U1 - 1, dev, what)
-    sy = symbols.to(device=dev)
-    rg = ranges.to(device=dev, dtype=torch.int64).contiguous()
-    inside = torch.arange(U1 - 1, device=dev)[None, :] < bd[:, 2:3]
-    bad = (inside & ((sy < 0) | (sy >= V))).sum().reshape(1)
-    host = torch.cat([bd.reshape(-1), bad, _bad_ranges(rg, U1)]).cpu()       # the one host sync
-    _check_boundary_rows(host[:-2].reshape(B, 4), B, T, U1 - 1, what)
-    if int(host[-2]) != 0:
-        raise ValueError(f"{what}: a symbol inside its boundary lies outside [0, {V})")
-    if int(host[-1]) != 0:
-        raise ValueError(f"{what}: ranges must satisfy ranges[..., r] = ranges[..., 0] + r within [0, {U1 - 1}]")
-    sy = torch.where(inside, sy, torch.zeros((), dtype=sy.dtype, device=dev)).to(torch.int32).contiguous()
-    return sy, bd[:, 3].to(torch.int32).contiguous(), bd[:, 2].to(torch.int32).contiguous(), blank, rg
+    rg = ranges.to(device=logits.device, dtype=torch.int64).contiguous()
+    more = [(_bad_ranges(rg, U1), f"{what}: ranges must satisfy ranges[..., r] = ranges[..., 0] + r within [0, {U1 - 1}]")]
+    ll, tl, sy = _lat.prepare(what, "the inputs", (logits,), B, T, U1 - 1, boundary, symbols, V, more)
+    return sy, ll, tl, blank, rg
 
 
-def _stats_and_sweeps(logits, sy, rg, ll, tl, blank, lat=0, pen=0.0):
-    """Row statistics of the band into a fresh RNN-T workspace, then the lattice sweeps: (costs float32, workspace)."""
+def _stats(logits, sy, rg, ll, tl, blank):
+    """Row statistics of the band into a fresh RNN-T workspace."""
     B, T, R, V = logits.shape
     U1 = sy.shape[1] + 1
-    dev = logits.device
-    ws = _lib.workspace("wr_rnnt_workspace_bytes", B, T, U1, device=dev)
-    costs = torch.empty(B, dtype=torch.float32, device=dev)
+    ws = _lib.workspace("wr_rnnt_workspace_bytes", B, T, U1, device=logits.device)
     _lib.call("wr_rnnt_pruned_stats", logits, _lib.dtype_code(logits.dtype), sy if U1 > 1 else None, rg, ll, tl, B, T, U1, R,
-              V, blank, ws, ws.numel(), device=dev)
-    if _lat.is_default(lat, pen):
-        _lib.call("wr_rnnt_loss_sweeps", ll, tl, B, T, U1, costs, ws, ws.numel(), device=dev)
-    else:
-        _lib.call("wr_rnnt_lattice_sweeps", ll, tl, B, T, U1, lat, pen, costs, ws, ws.numel(), device=dev)
-    return costs, ws
+              V, blank, ws, ws.numel(), device=logits.device)
+    return ws
 
 
 class _RNNTPrunedFn(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda")          # fp16/bf16 logits are handled natively (fp32 arithmetic inside)
-    def forward(ctx, logits, sy, rg, ll, tl, blank, lat=0, pen=0.0):
+    def forward(ctx, logits, sy, rg, ll, tl, blank, lat, pen):
         logits = logits.contiguous()
         if logits.data_ptr() % 16:                     # a view at an odd storage offset: the gradient kernel needs logits
             logits = logits.clone()                    # and grads at the same 16-byte phase, and fresh tensors are aligned
-        costs, ws = _stats_and_sweeps(logits, sy, rg, ll, tl, blank, lat, pen)
+        ws = _stats(logits, sy, rg, ll, tl, blank)
+        costs = _lat.sweeps(ws, ll, tl, logits.shape[0], logits.shape[1], sy.shape[1] + 1, lat, pen)
         ctx.save_for_backward(logits, sy, rg, ll, tl, ws)
         ctx.blank, ctx.lat, ctx.pen = blank, lat, pen
         return costs
@@ -236,13 +193,9 @@ class _RNNTPrunedFn(torch.autograd.Function):
         U1 = sy.shape[1] + 1
         grads = torch.empty_like(logits)
         gc = grad_costs.to(torch.float32).contiguous()
-        if _lat.is_default(ctx.lat, ctx.pen):
-            _lib.call("wr_rnnt_pruned_grad", logits, _lib.dtype_code(logits.dtype), sy if U1 > 1 else None, rg, ll, tl, B, T,
-                      U1, R, V, ctx.blank, gc, grads, ws, ws.numel(), device=logits.device)
-        else:
-            _lib.call("wr_rnnt_pruned_grad_lattice", logits, _lib.dtype_code(logits.dtype), sy if U1 > 1 else None, rg, ll,
-                      tl, B, T, U1, R, V, ctx.blank, ctx.lat, ctx.pen, gc, grads, ws, ws.numel(), device=logits.device)
-        return (grads,) + (None,) * (len(ctx.needs_input_grad) - 1)
+        _lib.call("wr_rnnt_pruned_grad_lattice", logits, _lib.dtype_code(logits.dtype), sy if U1 > 1 else None, rg, ll, tl,
+                  B, T, U1, R, V, ctx.blank, ctx.lat, ctx.pen, gc, grads, ws, ws.numel(), device=logits.device)
+        return (grads,) + (None,) * 7
 
 
 def rnnt_loss_pruned(logits: torch.Tensor, symbols: torch.Tensor, ranges: torch.Tensor, termination_symbol: int,
@@ -263,10 +216,7 @@ def rnnt_loss_pruned(logits: torch.Tensor, symbols: torch.Tensor, ranges: torch.
         raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
     lat, pen = _lat.check_lattice(what, rnnt_type, delay_penalty)
     sy, ll, tl, blank, rg = _prepare(logits, symbols, ranges, termination_symbol, boundary, what)
-    if _lat.is_default(lat, pen):
-        costs = _RNNTPrunedFn.apply(logits, sy, rg, ll, tl, blank)
-    else:
-        costs = _RNNTPrunedFn.apply(logits, sy, rg, ll, tl, blank, lat, pen)
+    costs = _RNNTPrunedFn.apply(logits, sy, rg, ll, tl, blank, lat, pen)
     return costs.mean() if reduction == "mean" else (costs.sum() if reduction == "sum" else costs)
 
 
@@ -278,13 +228,5 @@ def rnnt_pruned_lattice(logits, symbols, ranges, termination_symbol, boundary=No
     lat, pen = _lat.check_lattice("rnnt_pruned_lattice", rnnt_type, delay_penalty)
     sy, ll, tl, blank, rg = _prepare(logits, symbols, ranges, termination_symbol, boundary, "rnnt_pruned_lattice")
     logits = logits.detach().contiguous()
-    B, T = logits.shape[:2]
-    U1 = sy.shape[1] + 1
-    costs, ws = _stats_and_sweeps(logits, sy, rg, ll, tl, blank, lat, pen)
-    alpha = torch.empty(B, T, U1, dtype=torch.float32, device=logits.device)
-    beta = torch.empty_like(alpha)
-    if _lat.is_default(lat, pen):
-        _lib.call("wr_rnnt_export_lattice", ws, ws.numel(), ll, tl, B, T, U1, alpha, beta, device=logits.device)
-    else:
-        _lib.call("wr_rnnt_lattice_export", ws, ws.numel(), ll, tl, B, T, U1, lat, alpha, beta, device=logits.device)
-    return costs, alpha, beta
+    ws = _stats(logits, sy, rg, ll, tl, blank)
+    return _lat.lattice(ws, ll, tl, logits.shape[0], logits.shape[1], sy.shape[1] + 1, lat, pen)[:3]

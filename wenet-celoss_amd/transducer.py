@@ -35,11 +35,10 @@ from .fused import joint_rnnt_loss, plan_buckets
 from .joint import TransducerJoint, _call_precision
 from .rnnt_align import joint_rnnt_forced_align, rnnt_forced_align
 from .rnnt_loss import rnnt_loss
-from .rnnt_simple import rnnt_loss_simple, rnnt_simple_forced_align
-from .rnnt_smoothed import rnnt_loss_smoothed
+from .rnnt_simple import rnnt_simple_forced_align
 from . import k2
 from .rnnt_lattice import check_lattice, is_default
-from .rnnt_pruned import get_rnnt_prune_ranges, rnnt_loss_pruned
+from .rnnt_pruned import rnnt_loss_pruned
 from .search.greedy_search import basic_greedy_search, basic_greedy_search_both, basic_greedy_search_hw
 from .search.prefix_beam_search import PrefixBeamSearch
 
@@ -233,16 +232,11 @@ class Transducer(nn.Module):
     def _simple_loss(self, lm, am, symbols, boundary, return_grad: bool):
         ll, la = self.lm_only_scale, self.am_only_scale
         kw = self._lattice_kwargs()
-        if kw:                                                   # the k2-signature forms take the lattice arguments
-            if ll != 0.0 or la != 0.0:
-                return k2.rnnt_loss_smoothed(lm, am, symbols, self.blank, lm_only_scale=ll, am_only_scale=la,
-                                             boundary=boundary, reduction="mean", return_grad=return_grad, **kw)
-            return k2.rnnt_loss_simple(lm, am, symbols, self.blank, boundary=boundary, reduction="mean",
-                                       return_grad=return_grad, **kw)
         if ll != 0.0 or la != 0.0:
-            return rnnt_loss_smoothed(lm, am, symbols, self.blank, lm_only_scale=ll, am_only_scale=la, boundary=boundary,
-                                      reduction="mean", return_grad=return_grad)
-        return rnnt_loss_simple(lm, am, symbols, self.blank, boundary=boundary, reduction="mean", return_grad=return_grad)
+            return k2.rnnt_loss_smoothed(lm, am, symbols, self.blank, lm_only_scale=ll, am_only_scale=la, boundary=boundary,
+                                         reduction="mean", return_grad=return_grad, **kw)
+        return k2.rnnt_loss_simple(lm, am, symbols, self.blank, boundary=boundary, reduction="mean",
+                                   return_grad=return_grad, **kw)
 
     def _lattice_kwargs(self) -> Dict[str, object]:
         """rnnt_type / delay_penalty for the k2 losses; empty for the defaults (and for a model pickled before they
@@ -259,8 +253,7 @@ class Transducer(nn.Module):
         loss_rnnt is `rnnt_loss_pruned` on the joiner's outputs on that band."""
         lm, am, symbols, boundary = self._simple_inputs(encoder_out, encoder_out_lens, predictor_out, text, text_lengths)
         loss_simple, (px_grad, py_grad) = self._simple_loss(lm, am, symbols, boundary, return_grad=True)
-        ranges = (k2.get_rnnt_prune_ranges if self._lattice_kwargs() else get_rnnt_prune_ranges)(
-            px_grad, py_grad, boundary, self.prune_range)
+        ranges = k2.get_rnnt_prune_ranges(px_grad, py_grad, boundary, self.prune_range)
         logits = self.joint.forward_pruned(encoder_out, predictor_out, ranges)
         loss_rnnt = rnnt_loss_pruned(logits, symbols, ranges, self.blank, boundary=boundary, reduction="mean",
                                      **self._lattice_kwargs())
