@@ -118,3 +118,56 @@ def test_every_entry_point_rejects_bad_arguments_before_launch(lib):
     assert lib.wr_ctc_prefix_beam_search(null, null, 1, 4, 8, 0, 0, null, null, null, null, null, 0, null) == -1
     assert lib.wr_ctc_forced_align(null, 0, null, null, null, 1, 4, 0, 8, 0, null, null, 0, null) == -1
     assert lib.wr_tune_set(99, 1) == -1
+
+
+LOSS_AND_JOINER_SOURCES = ["joint.hip", "joint_split.hip", "rnnt_loss.hip", "rnnt_pruned.hip", "rnnt_simple.hip",
+                           "rnnt_lattice.hip", "ctc_loss.hip"]
+
+
+@pytest.fixture(scope="module")
+def rejections():
+    """tests/golden/make_abi_rejections.py (the generator) and the table it wrote, tests/golden/abi_rejections.json"""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("make_abi_rejections",
+                                                  os.path.join(ROOT, "tests", "golden", "make_abi_rejections.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(gen.TABLE) as f:
+        return gen, json.load(f)
+
+
+def test_rejection_table_covers_the_loss_and_joiner_entry_points(rejections):
+    gen, table = rejections
+    entry_points = set()
+    for name in LOSS_AND_JOINER_SOURCES:
+        src = open(os.path.join(ROOT, "wenet-celoss_amd", "csrc", name)).read()
+        entry_points |= set(re.findall(r'^extern "C" int (wr_[a-z0-9_]+)\(', src, flags=re.M))
+    entry_points.discard("wr_debug_read_js_stamps")            # only in stamp builds; takes no argument to reject
+    assert {r["fn"] for r in table} == entry_points
+    # the table is what the generator's rows produce: same calls, same order
+    protos = gen.prototypes()
+    calls = []
+    for fn, _, over in gen.all_rows():
+        c = [fn, gen.arguments(protos[fn], over)]
+        if c not in calls:
+            calls.append(c)
+    assert calls == [[r["fn"], r["args"]] for r in table]
+    # no row may have reached a launch when it was recorded
+    assert all(r["rc"] in (-1, -2, -3) and r["error"] for r in table)
+
+
+def test_rejection_table_replays(lib, rejections):
+    """Every row of tests/golden/abi_rejections.json -- one call per class of argument check of every loss and joiner
+    entry point, recorded before the host code was rewritten -- gives the same return code and the same
+    wr_last_error() text.  No GPU is needed and none is used: every row is rejected before the first HIP call (the
+    replay stops at the first row that is not, rather than go on calling with placeholder pointers)."""
+    gen, table = rejections
+    protos = gen.prototypes()
+    wrong = []
+    for r in table:
+        rc, err = gen.call(lib, r["fn"], protos[r["fn"]], r["args"])
+        assert rc in (-1, -2, -3), f"{r['fn']}{r['args']}: returned {rc} ({err!r}), expected {r['rc']} ({r['error']!r})"
+        if (rc, err) != (r["rc"], r["error"]):
+            wrong.append(f"{r['fn']}{r['args']}: ({rc}, {err!r}) != ({r['rc']}, {r['error']!r})")
+    assert not wrong, "\n".join(wrong)

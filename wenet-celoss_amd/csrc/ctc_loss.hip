@@ -23,6 +23,7 @@
 // Algorithmic traffic: 4*V per valid frame (pass 1) + 2*4*V per frame (pass 3).
 #include "row_stream.hpp"
 #include "wr_common.hpp"
+#include "wr_launch.hpp"
 
 namespace wr {
 namespace {
@@ -431,14 +432,14 @@ int ctc_check(int B, int Tmax, int Smax, int V, int blank)
     return WR_OK;
 }
 
-void launch_ctc_sweep(const CtcWs &w, char *ws, const int32_t *targets, const int32_t *ilens, const int32_t *tlens,
-                      int B, int Tmax, int Smax, float *nll, hipStream_t st)
+int launch_ctc_sweep(const CtcWs &w, char *ws, const int32_t *targets, const int32_t *ilens, const int32_t *tlens,
+                     int B, int Tmax, int Smax, float *nll, hipStream_t st)
 {
-    hipLaunchKernelGGL((ctc_sweep_kernel<8>), dim3(B, 2), dim3(64 * w.KS), 0, st,
-                       reinterpret_cast<const float *>(ws + w.lpb_off), reinterpret_cast<const float *>(ws + w.lpl_off),
-                       targets, ilens, tlens, Tmax, Smax > 0 ? Smax : 1, w.SP,
-                       reinterpret_cast<double *>(ws + w.alpha_off), reinterpret_cast<double *>(ws + w.beta_off),
-                       reinterpret_cast<double *>(ws + w.nll_off), nll, reinterpret_cast<double *>(ws + w.dump_off));
+    return launch("ctc_sweep_kernel", ctc_sweep_kernel<8>, dim3(B, 2), dim3(64 * w.KS), 0, st,
+                  reinterpret_cast<const float *>(ws + w.lpb_off), reinterpret_cast<const float *>(ws + w.lpl_off), targets,
+                  ilens, tlens, Tmax, Smax > 0 ? Smax : 1, w.SP, reinterpret_cast<double *>(ws + w.alpha_off),
+                  reinterpret_cast<double *>(ws + w.beta_off), reinterpret_cast<double *>(ws + w.nll_off), nll,
+                  reinterpret_cast<double *>(ws + w.dump_off));
 }
 
 }  // namespace
@@ -472,14 +473,11 @@ extern "C" int wr_ctc_loss_fwd(const void *logits_d, int dtype, const int32_t *t
     long blocks = (nrows + 3) / 4;
     // one frame per wave, workgroups dispatched in frame order (as the RNN-T row pass; 153 us against 158 us with 2 048
     // persistent workgroups at the BASELINE shape)
-    hipLaunchKernelGGL(ctc_lse_kernel, dim3((int)blocks), dim3(256), 0, st, static_cast<const float *>(logits_d),
-                       targets_d, input_lengths_d, target_lengths_d, B, Tmax, SmaxA, V, blank,
-                       reinterpret_cast<float *>(ws + w.denom_off), reinterpret_cast<float *>(ws + w.lpb_off),
-                       reinterpret_cast<float *>(ws + w.lpl_off));
-    WR_CHECK_LAUNCH("ctc_lse_kernel");
-    launch_ctc_sweep(w, ws, targets_d, input_lengths_d, target_lengths_d, B, Tmax, Smax, nll_d, st);
-    WR_CHECK_LAUNCH("ctc_sweep_kernel");
-    return WR_OK;
+    WR_TRY(launch("ctc_lse_kernel", ctc_lse_kernel, dim3((int)blocks), dim3(256), 0, st,
+                  static_cast<const float *>(logits_d), targets_d, input_lengths_d, target_lengths_d, B, Tmax, SmaxA, V,
+                  blank, reinterpret_cast<float *>(ws + w.denom_off), reinterpret_cast<float *>(ws + w.lpb_off),
+                  reinterpret_cast<float *>(ws + w.lpl_off), /* normalized */ 0));
+    return launch_ctc_sweep(w, ws, targets_d, input_lengths_d, target_lengths_d, B, Tmax, Smax, nll_d, st);
 }
 
 extern "C" int wr_ctc_loss_bwd(const void *logits_d, int dtype, const int32_t *targets_d,
@@ -498,17 +496,14 @@ extern "C" int wr_ctc_loss_bwd(const void *logits_d, int dtype, const int32_t *t
     hipStream_t st = static_cast<hipStream_t>(stream);
     const char *ws = static_cast<const char *>(workspace_d);
     const int SmaxA = Smax > 0 ? Smax : 1;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ctc_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)((size_t)(V + 4) * sizeof(float)));      // V = 16384: 16 bytes above the 64 KB default
-    hipLaunchKernelGGL(ctc_grad_kernel, dim3((unsigned)((long)B * Tmax)), dim3(kCtcGradThreads), (size_t)(V + 4) * sizeof(float), st,
-                       static_cast<const float *>(logits_d), targets_d, input_lengths_d, target_lengths_d, B, Tmax,
-                       SmaxA, w.SP, V, blank, reinterpret_cast<const float *>(ws + w.denom_off),
-                       reinterpret_cast<const float *>(ws + w.lpb_off), reinterpret_cast<const float *>(ws + w.lpl_off),
-                       reinterpret_cast<const double *>(ws + w.alpha_off),
-                       reinterpret_cast<const double *>(ws + w.beta_off),
-                       reinterpret_cast<const double *>(ws + w.nll_off), grad_nll_d, static_cast<float *>(grads_d));
-    WR_CHECK_LAUNCH("ctc_grad_kernel");
-    return WR_OK;
+    // V = 16384: 16 bytes above the 64 KB default
+    return launch_lds("ctc_grad_kernel", ctc_grad_kernel, dim3((unsigned)((long)B * Tmax)), dim3(kCtcGradThreads),
+                      (size_t)(V + 4) * sizeof(float), st, static_cast<const float *>(logits_d), targets_d, input_lengths_d,
+                      target_lengths_d, B, Tmax, SmaxA, w.SP, V, blank, reinterpret_cast<const float *>(ws + w.denom_off),
+                      reinterpret_cast<const float *>(ws + w.lpb_off), reinterpret_cast<const float *>(ws + w.lpl_off),
+                      reinterpret_cast<const double *>(ws + w.alpha_off),
+                      reinterpret_cast<const double *>(ws + w.beta_off),
+                      reinterpret_cast<const double *>(ws + w.nll_off), grad_nll_d, static_cast<float *>(grads_d));
 }
 
 extern "C" size_t wr_ctc_align_workspace_bytes(int B, int Tmax, int Smax)
@@ -535,13 +530,11 @@ extern "C" int wr_ctc_forced_align(const float *logits_d, int normalized, const 
     const long nrows = (long)B * Tmax;
     long blocks = (nrows + 3) / 4;
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(ctc_lse_kernel, dim3((int)blocks), dim3(256), 0, st, logits_d, targets_d, input_lengths_d,
-                       target_lengths_d, B, Tmax, Smax, V, blank, reinterpret_cast<float *>(ws + w.denom_off),
-                       reinterpret_cast<float *>(ws + w.lpb_off), reinterpret_cast<float *>(ws + w.lpl_off), normalized);
-    WR_CHECK_LAUNCH("ctc_lse_kernel");
-    hipLaunchKernelGGL(ctc_viterbi_kernel, dim3(B), dim3(64 * w.KS), 0, st, reinterpret_cast<const float *>(ws + w.lpb_off),
-                       reinterpret_cast<const float *>(ws + w.lpl_off), targets_d, input_lengths_d, target_lengths_d, Tmax,
-                       Smax, w.SP, blank, reinterpret_cast<int16_t *>(ws + w.total), alignment_d);
-    WR_CHECK_LAUNCH("ctc_viterbi_kernel");
-    return WR_OK;
+    WR_TRY(launch("ctc_lse_kernel", ctc_lse_kernel, dim3((int)blocks), dim3(256), 0, st, logits_d, targets_d,
+                  input_lengths_d, target_lengths_d, B, Tmax, Smax, V, blank, reinterpret_cast<float *>(ws + w.denom_off),
+                  reinterpret_cast<float *>(ws + w.lpb_off), reinterpret_cast<float *>(ws + w.lpl_off), normalized));
+    return launch("ctc_viterbi_kernel", ctc_viterbi_kernel, dim3(B), dim3(64 * w.KS), 0, st,
+                  reinterpret_cast<const float *>(ws + w.lpb_off), reinterpret_cast<const float *>(ws + w.lpl_off),
+                  targets_d, input_lengths_d, target_lengths_d, Tmax, Smax, w.SP, blank,
+                  reinterpret_cast<int16_t *>(ws + w.total), alignment_d);
 }

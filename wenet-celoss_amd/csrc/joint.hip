@@ -25,6 +25,7 @@
 //   d ep = sum_u dZ and d pp = sum_t dZ are library reductions on the host side.
 #include "wr_common.hpp"
 #include "joint_lse.hpp"
+#include "wr_launch.hpp"
 
 namespace wr {
 namespace {
@@ -691,38 +692,21 @@ int joint_fwd_epi_launch(bool frag, int epi, const float *ep_d, const float *pp_
     const size_t tile = frag ? (size_t)kBM * (Jp + 4) * sizeof(float) : (size_t)Jp * kHPad * sizeof(float);
     const size_t lds = (tile > joint_lse_exchange_bytes(8) ? tile : joint_lse_exchange_bytes(8)) + joint_epi_rows_bytes();
     WR_REQUIRE(lds <= 160 * 1024, WR_EUNSUPPORTED, "joint_fwd: J=%d needs %zu bytes of LDS", J, lds);
-#define WR_LAUNCH_EPI(EPI_, lse_)                                                                                      \
-    do {                                                                                                              \
-        if (frag) {                                                                                                   \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_frag_kernel<EPI_, 1>),                  \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
-            hipLaunchKernelGGL((joint_fwd_frag_kernel<EPI_, 1>), grid, dim3(512), lds, st, ep_d, pp_d,                 \
-                               static_cast<const float4 *>(wsw), b_out_d, llens, tlens, B, T, U1, J, Jp, V, Vp, act,   \
-                               out_d, lse_);                                                                          \
-        } else {                                                                                                      \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_direct_kernel<8, 1, EPI_>),             \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
-            hipLaunchKernelGGL((joint_fwd_direct_kernel<8, 1, EPI_>), grid, dim3(512), lds, st, ep_d, pp_d,            \
-                               static_cast<const float *>(wsw), b_out_d, llens, tlens, B, T, U1, J, Jp, V, Vp, act,    \
-                               out_d, lse_);                                                                          \
-        }                                                                                                             \
-    } while (0)
-    if (epi == kEpiGrad) {
-        WR_LAUNCH_EPI(kEpiGrad, lse);
-        WR_CHECK_LAUNCH("joint_fwd (gradient epilogue)");
-        return WR_OK;
-    }
+    const auto run = [&](const char *name, auto epi_c, const JointLse &l) {
+        if (frag)
+            return launch_lds(name, joint_fwd_frag_kernel<epi_c.value, 1>, grid, dim3(512), lds, st, ep_d, pp_d,
+                              static_cast<const float4 *>(wsw), b_out_d, llens, tlens, B, T, U1, J, Jp, V, Vp, act, out_d, l);
+        return launch_lds(name, joint_fwd_direct_kernel<8, 1, epi_c.value>, grid, dim3(512), lds, st, ep_d, pp_d,
+                          static_cast<const float *>(wsw), b_out_d, llens, tlens, B, T, U1, J, Jp, V, Vp, act, out_d, l);
+    };
+    if (epi == kEpiGrad) return run("joint_fwd (gradient epilogue)", int_c<kEpiGrad>{}, lse);
     (void)hipMemsetAsync(lse.repair, 0, sizeof(int32_t), st);
-    WR_LAUNCH_EPI(kEpiStats, lse);
-    WR_CHECK_LAUNCH("joint_fwd (statistics epilogue)");
+    WR_TRY(run("joint_fwd (statistics epilogue)", int_c<kEpiStats>{}, lse));
     // repair: the same launch with a running maximum, whose workgroups leave at once unless a partial sum overflowed
     JointLse rep = lse;
     rep.run_if = lse.repair;
     rep.online = 1;
-    WR_LAUNCH_EPI(kEpiStats, rep);
-#undef WR_LAUNCH_EPI
-    WR_CHECK_LAUNCH("joint_fwd (statistics epilogue, repair)");
-    return WR_OK;
+    return run("joint_fwd (statistics epilogue, repair)", int_c<kEpiStats>{}, rep);
 }
 
 // shared body of wr_joint_fwd / wr_joint_fwd_lse / wr_joint_rnnt_stats / wr_joint_rnnt_grad (epi: JointEpi; -1 = kEpiStore
@@ -741,53 +725,36 @@ int joint_fwd_launch(const float *ep_d, const float *pp_d, const float *w_out_d,
     // default: the fragment-layout kernel; wr_tune_set(5, 1) selects the first forward kernel (kept for the equivalence test)
     if (tune_get(kTuneJointFwdVariant) != 1) {
         float4 *wf = static_cast<float4 *>(workspace_d);
-        if (!w_ready) hipLaunchKernelGGL(joint_frag_w_kernel, dim3(1024), dim3(256), 0, st, w_out_d, V, J, Jp, Vp, wf);
+        if (!w_ready)
+            WR_TRY(launch("joint_frag_w_kernel", joint_frag_w_kernel, dim3(1024), dim3(256), 0, st, w_out_d, V, J, Jp, Vp, wf));
         const size_t tile2 = (size_t)kBM * (Jp + 4) * sizeof(float);
-        if (epi == kEpiStats || epi == kEpiGrad) {
+        if (epi == kEpiStats || epi == kEpiGrad)
             return joint_fwd_epi_launch(true, epi, ep_d, pp_d, wf, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, Jp,
                                         V, Vp, act, out_d, *lse, st);
-        } else if (lse == nullptr) {
-#define WR_LAUNCH_FRAG(LSE_, CT_, lds_, lse_)                                                                          \
-            do {                                                                                                      \
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_frag_kernel<LSE_, CT_>),             \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_));                    \
-                hipLaunchKernelGGL((joint_fwd_frag_kernel<LSE_, CT_>), grid, dim3(512), lds_, st, ep_d, pp_d, wf, b_out_d, \
-                                   logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, act, out_d, lse_);       \
-            } while (0)
-            WR_LAUNCH_FRAG(kEpiStore, 1, tile2, JointLse{});
-        } else {
-            const size_t lds2 = tile2 > joint_lse_exchange_bytes(8) ? tile2 : joint_lse_exchange_bytes(8);
-            (void)hipMemsetAsync(lse->repair, 0, sizeof(int32_t), st);
-            WR_LAUNCH_FRAG(kEpiStoreLse, 1, lds2, *lse);
-#undef WR_LAUNCH_FRAG
-        }
-        WR_CHECK_LAUNCH("joint_fwd_frag_kernel");
-        return WR_OK;
+        const auto frag = [&](auto epi_c, size_t lds, const JointLse &l) {
+            return launch_lds("joint_fwd_frag_kernel", joint_fwd_frag_kernel<epi_c.value, 1>, grid, dim3(512), lds, st, ep_d,
+                              pp_d, wf, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, act, out_d, l);
+        };
+        if (lse == nullptr) return frag(int_c<kEpiStore>{}, tile2, JointLse{});
+        const size_t lds2 = tile2 > joint_lse_exchange_bytes(8) ? tile2 : joint_lse_exchange_bytes(8);
+        (void)hipMemsetAsync(lse->repair, 0, sizeof(int32_t), st);
+        return frag(int_c<kEpiStoreLse>{}, lds2, *lse);
     }
-    if (!w_ready) {
-        hipLaunchKernelGGL(joint_transpose_w_kernel, dim3(Vp / 32, (Jp + 31) / 32), dim3(256), 0, st, w_out_d, V, J, Jp,
-                           Vp, wt);
-        WR_CHECK_LAUNCH("joint_transpose_w_kernel");
-    }
-    if (epi == kEpiStats || epi == kEpiGrad) {
+    if (!w_ready)
+        WR_TRY(launch("joint_transpose_w_kernel", joint_transpose_w_kernel, dim3(Vp / 32, (Jp + 31) / 32), dim3(256), 0, st,
+                      w_out_d, V, J, Jp, Vp, wt));
+    if (epi == kEpiStats || epi == kEpiGrad)
         return joint_fwd_epi_launch(false, epi, ep_d, pp_d, wt, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V,
                                     Vp, act, out_d, *lse, st);
-    } else if (lse == nullptr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_direct_kernel<8, 1, kEpiStore>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile);
-        hipLaunchKernelGGL((joint_fwd_direct_kernel<8, 1, kEpiStore>), grid, dim3(512), tile, st, ep_d, pp_d, wt, b_out_d,
-                           logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, act, out_d, JointLse{});
-    } else {
-        // the statistics exchange reuses the activation tile's storage
-        const size_t lds = tile > joint_lse_exchange_bytes(8) ? tile : joint_lse_exchange_bytes(8);
-        (void)hipMemsetAsync(lse->repair, 0, sizeof(int32_t), st);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_direct_kernel<8, 1, kEpiStoreLse>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((joint_fwd_direct_kernel<8, 1, kEpiStoreLse>), grid, dim3(512), lds, st, ep_d, pp_d, wt, b_out_d,
-                           logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, act, out_d, *lse);
-    }
-    WR_CHECK_LAUNCH("joint_fwd_direct_kernel");
-    return WR_OK;
+    const auto direct = [&](auto epi_c, size_t lds, const JointLse &l) {
+        return launch_lds("joint_fwd_direct_kernel", joint_fwd_direct_kernel<8, 1, epi_c.value>, grid, dim3(512), lds, st, ep_d,
+                          pp_d, wt, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, act, out_d, l);
+    };
+    if (lse == nullptr) return direct(int_c<kEpiStore>{}, tile, JointLse{});
+    // the statistics exchange reuses the activation tile's storage
+    const size_t lds = tile > joint_lse_exchange_bytes(8) ? tile : joint_lse_exchange_bytes(8);
+    (void)hipMemsetAsync(lse->repair, 0, sizeof(int32_t), st);
+    return direct(int_c<kEpiStoreLse>{}, lds, *lse);
 }
 }  // namespace
 
@@ -798,8 +765,7 @@ extern "C" int wr_joint_fwd(const float *ep_d, const float *pp_d, const float *w
 {
     if (int rc = joint_check(B, T, U1, J, V, activation)) return rc;
     WR_REQUIRE(ep_d && pp_d && w_out_d && b_out_d && out_d && workspace_d, WR_EINVAL, "joint_fwd: null pointer argument");
-    WR_REQUIRE((logit_lengths_d == nullptr) == (target_lengths_d == nullptr), WR_EINVAL,
-               "joint_fwd: pass both length arrays or neither");
+    WR_TRY(check_length_pair("joint_fwd", logit_lengths_d, target_lengths_d));
     return joint_fwd_launch(ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation,
                             out_d, workspace_d, workspace_bytes, nullptr, static_cast<hipStream_t>(stream));
 }
@@ -814,15 +780,8 @@ extern "C" int wr_joint_fwd_lse(const float *ep_d, const float *pp_d, const floa
     WR_REQUIRE(ep_d && pp_d && w_out_d && b_out_d && out_d && workspace_d && rnnt_workspace_d, WR_EINVAL,
                "joint_fwd_lse: null pointer argument");
     WR_REQUIRE(logit_lengths_d && target_lengths_d, WR_EINVAL, "joint_fwd_lse: both length arrays are required");
-    WR_REQUIRE(targets_d || U1 == 1, WR_EINVAL, "joint_fwd_lse: targets is null");
-    WR_REQUIRE(blank >= 0 && blank < V, WR_EINVAL, "joint_fwd_lse: blank %d out of range [0,%d)", blank, V);
-    WR_REQUIRE(U1 <= kRnntMaxCols, WR_EUNSUPPORTED, "joint_fwd_lse: U1=%d exceeds the loss's limit of %d", U1, kRnntMaxCols);
-    const RnntWs w = rnnt_ws_layout(B, T, U1);
-    WR_REQUIRE(rnnt_workspace_bytes >= w.total, WR_EWORKSPACE, "joint_fwd_lse: RNN-T workspace %zu < required %zu",
-               rnnt_workspace_bytes, w.total);
-    char *rws = static_cast<char *>(rnnt_workspace_d);
-    JointLse lse{targets_d, blank, w.S, reinterpret_cast<float2 *>(rws + w.lp_off), reinterpret_cast<float *>(rws + w.denom_off),
-                 reinterpret_cast<int32_t *>(rws + w.flag_off)};
+    WR_TRY(joint_rnnt_side_check("joint_fwd_lse", targets_d, B, T, U1, V, blank, -1, rnnt_workspace_bytes));
+    const JointLse lse = joint_lse_over(targets_d, blank, rnnt_ws_layout(B, T, U1), static_cast<char *>(rnnt_workspace_d));
     return joint_fwd_launch(ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation,
                             out_d, workspace_d, workspace_bytes, &lse, static_cast<hipStream_t>(stream));
 }
@@ -837,22 +796,14 @@ int joint_rnnt_check(const char *what, const float *ep_d, const float *pp_d, con
     if (int rc = joint_check(B, T, U1, J, V, activation)) return rc;
     WR_REQUIRE(ep_d && pp_d && w_out_d && b_out_d && workspace_d && rws && llens && tlens, WR_EINVAL,
                "%s: null pointer argument", what);
-    WR_REQUIRE(targets_d || U1 == 1, WR_EINVAL, "%s: targets is null", what);
-    WR_REQUIRE(terms == 0 || terms == 3, WR_EUNSUPPORTED, "%s: terms must be 0 (exact fp32) or 3 (split), got %d", what, terms);
-    WR_REQUIRE(blank >= 0 && blank < V, WR_EINVAL, "%s: blank %d out of range [0,%d)", what, blank, V);
-    WR_REQUIRE(U1 <= kRnntMaxCols, WR_EUNSUPPORTED, "%s: U1=%d exceeds the loss's limit of %d", what, U1, kRnntMaxCols);
-    WR_REQUIRE((long)B * T * U1 < (1L << 31), WR_EUNSUPPORTED, "%s: more than 2^31 lattice cells", what);
-    const size_t need = rnnt_ws_layout(B, T, U1).total;
-    WR_REQUIRE(rws_bytes >= need, WR_EWORKSPACE, "%s: RNN-T workspace %zu < required %zu", what, rws_bytes, need);
-    return WR_OK;
+    return joint_rnnt_side_check(what, targets_d, B, T, U1, V, blank, terms, rws_bytes);
 }
 
 JointLse joint_rnnt_lse(const int32_t *targets_d, int B, int T, int U1, int blank, void *rnnt_workspace_d)
 {
     const RnntWs w = rnnt_ws_layout(B, T, U1);
     char *rws = static_cast<char *>(rnnt_workspace_d);
-    JointLse lse{targets_d, blank, w.S, reinterpret_cast<float2 *>(rws + w.lp_off), reinterpret_cast<float *>(rws + w.denom_off),
-                 reinterpret_cast<int32_t *>(rws + w.flag_off)};
+    JointLse lse = joint_lse_over(targets_d, blank, w, rws);
     lse.alpha_skew = reinterpret_cast<const double *>(rws + w.alpha_off);
     lse.beta_skew = reinterpret_cast<const double *>(rws + w.beta_off);
     lse.cost = reinterpret_cast<const double *>(rws + w.cost_off);
@@ -912,17 +863,14 @@ extern "C" int wr_joint_bwd_dz(const float *gout_d, const float *ep_d, const flo
 {
     if (int rc = joint_check(B, T, U1, J, V, activation)) return rc;
     WR_REQUIRE(gout_d && ep_d && pp_d && w_out_d && dz_d, WR_EINVAL, "joint_bwd_dz: null pointer argument");
-    WR_REQUIRE((logit_lengths_d == nullptr) == (target_lengths_d == nullptr), WR_EINVAL,
-               "joint_bwd_dz: pass both length arrays or neither");
+    WR_TRY(check_length_pair("joint_bwd_dz", logit_lengths_d, target_lengths_d));
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (V % 4 == 0 && V >= 16 && J % 4 == 0 && tune_get(kTuneDzExact) != 1)   // default: 256 x 256 block tiling (knob 10 = 1: 64-cell tiling)
         return joint_bwd_dz_block(gout_d, ep_d, pp_d, w_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation, dz_d, h_d, st);
     const long M = (long)B * T * U1;
     const dim3 grid((unsigned)((M + kBM - 1) / kBM));
-    hipLaunchKernelGGL(joint_bwd_dz_kernel, grid, dim3(64 * kBwdWaves), 0, st, gout_d, ep_d, pp_d, w_out_d,
-                       logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation, dz_d, h_d);
-    WR_CHECK_LAUNCH("joint_bwd_dz_kernel");
-    return WR_OK;
+    return launch("joint_bwd_dz_kernel", joint_bwd_dz_kernel, grid, dim3(64 * kBwdWaves), 0, st, gout_d, ep_d, pp_d,
+                  w_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation, dz_d, h_d);
 }
 
 extern "C" size_t wr_joint_dw_workspace_bytes(int J, int V)
@@ -937,8 +885,7 @@ extern "C" int wr_joint_bwd_dw(const float *gout_d, const float *h_d, const int3
 {
     if (int rc = joint_check(B, T, U1, J, V)) return rc;
     WR_REQUIRE(gout_d && h_d && dw_d && workspace_d, WR_EINVAL, "joint_bwd_dw: null pointer argument");
-    WR_REQUIRE((logit_lengths_d == nullptr) == (target_lengths_d == nullptr), WR_EINVAL,
-               "joint_bwd_dw: pass both length arrays or neither");
+    WR_TRY(check_length_pair("joint_bwd_dw", logit_lengths_d, target_lengths_d));
     const int parts = dw_parts(V);
     const size_t need = (size_t)parts * ((size_t)V * J + V) * sizeof(float);
     WR_REQUIRE(workspace_bytes >= need, WR_EWORKSPACE, "joint_bwd_dw: workspace %zu < required %zu", workspace_bytes, need);
@@ -953,11 +900,8 @@ extern "C" int wr_joint_bwd_dw(const float *gout_d, const float *h_d, const int3
     rows_per_part = (rows_per_part + per - 1) / per * per;
     float *part_dw = static_cast<float *>(workspace_d);
     float *part_db = part_dw + (size_t)parts * V * J;
-    hipLaunchKernelGGL(joint_bwd_dw_kernel, dim3(nslabs * parts), dim3(512), 0, st, gout_d, h_d, logit_lengths_d,
-                       target_lengths_d, B, T, U1, J, V, nslabs, rows_per_part, part_dw, part_db);
-    WR_CHECK_LAUNCH("joint_bwd_dw_kernel");
-    hipLaunchKernelGGL(joint_dw_reduce_kernel, dim3(1024), dim3(256), 0, st, part_dw, part_db, parts, (long)V * J, V, dw_d,
-                       db_d);
-    WR_CHECK_LAUNCH("joint_dw_reduce_kernel");
-    return WR_OK;
+    WR_TRY(launch("joint_bwd_dw_kernel", joint_bwd_dw_kernel, dim3(nslabs * parts), dim3(512), 0, st, gout_d, h_d,
+                  logit_lengths_d, target_lengths_d, B, T, U1, J, V, nslabs, rows_per_part, part_dw, part_db));
+    return launch("joint_dw_reduce_kernel", joint_dw_reduce_kernel, dim3(1024), dim3(256), 0, st, part_dw, part_db, parts,
+                  (long)V * J, V, dw_d, db_d);
 }

@@ -51,6 +51,31 @@ struct JointLse {
     long m_begin = 0, m_end = 0;
 };
 
+// The row-statistics block over an RNN-T workspace laid out by `w` (what the store and statistics modes need; the
+// gradient mode's fields are the caller's to add).
+inline JointLse joint_lse_over(const int32_t *targets_d, int blank, const RnntWs &w, char *rws)
+{
+    return JointLse{targets_d, blank, w.S, reinterpret_cast<float2 *>(rws + w.lp_off),
+                    reinterpret_cast<float *>(rws + w.denom_off), reinterpret_cast<int32_t *>(rws + w.flag_off)};
+}
+
+// The RNN-T side of a joiner entry point `what` that fills or reads the loss's workspace: labels, blank, the sweep's
+// column limit and the workspace size, in the order every such entry point reports them.  `terms` >= 0 (the rnnt_stats /
+// rnnt_grad entry points, which pick the joiner's precision themselves): that code and the cell count as well.
+inline int joint_rnnt_side_check(const char *what, const int32_t *targets_d, int B, int T, int U1, int V, int blank, int terms,
+                                 size_t rws_bytes)
+{
+    WR_REQUIRE(targets_d || U1 == 1, WR_EINVAL, "%s: targets is null", what);
+    WR_REQUIRE(terms < 0 || terms == 0 || terms == 3, WR_EUNSUPPORTED, "%s: terms must be 0 (exact fp32) or 3 (split), got %d",
+               what, terms);
+    WR_REQUIRE(blank >= 0 && blank < V, WR_EINVAL, "%s: blank %d out of range [0,%d)", what, blank, V);
+    WR_REQUIRE(U1 <= kRnntMaxCols, WR_EUNSUPPORTED, "%s: U1=%d exceeds the loss's limit of %d", what, U1, kRnntMaxCols);
+    WR_REQUIRE(terms < 0 || (long)B * T * U1 < (1L << 31), WR_EUNSUPPORTED, "%s: more than 2^31 lattice cells", what);
+    const size_t need = rnnt_ws_layout(B, T, U1).total;
+    WR_REQUIRE(rws_bytes >= need, WR_EWORKSPACE, "%s: RNN-T workspace %zu < required %zu", what, rws_bytes, need);
+    return WR_OK;
+}
+
 constexpr int kLseRows = 64;  // cells per workgroup (= kBM = kSM)
 
 // Per-row constants of the kEpiStats / kEpiGrad epilogues, in LDS behind everything else the kernel keeps there

@@ -31,6 +31,7 @@
 
 #include "wr_common.hpp"
 #include "joint_lse.hpp"
+#include "wr_launch.hpp"
 
 namespace wr {
 namespace {
@@ -1790,21 +1791,13 @@ int joint_bwd_dz_block(const float *gout_d, const float *ep_d, const float *pp_d
     const long blocks = (M + kZB - 1) / kZB * n_js;
     WR_REQUIRE(blocks < (1L << 31), WR_EUNSUPPORTED, "joint_bwd_dz: too many lattice cells");
     const size_t lds = (size_t)kWStages * (16 * kZApad + 16 * kZB) * sizeof(float) + (size_t)kZB * (2 * sizeof(long) + sizeof(int));
-    if (act == WR_ACT_TANH) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_bwd_dz_block_kernel<false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(joint_bwd_dz_block_kernel<false>, dim3((unsigned)blocks), dim3(256), lds, st, gout_d, ep_d, pp_d, w_d,
-                           llens_d, tlens_d, B, T, U1, J, V, n_js, act, dz_d, h_d);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_bwd_dz_block_kernel<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(joint_bwd_dz_block_kernel<true>, dim3((unsigned)blocks), dim3(256), lds, st, gout_d, ep_d, pp_d, w_d,
-                           llens_d, tlens_d, B, T, U1, J, V, n_js, act, dz_d, h_d);
-        hipLaunchKernelGGL(joint_dz_act_kernel<float>, dim3(256 * 16), dim3(256), 0, st, ep_d, pp_d, llens_d, tlens_d, T, U1, J, M, act,
-                           dz_d, h_d, J);
-    }
-    WR_CHECK_LAUNCH("joint_bwd_dz_block_kernel");
-    return WR_OK;
+    if (act == WR_ACT_TANH)
+        return launch_lds("joint_bwd_dz_block_kernel", joint_bwd_dz_block_kernel<false>, dim3((unsigned)blocks), dim3(256), lds,
+                          st, gout_d, ep_d, pp_d, w_d, llens_d, tlens_d, B, T, U1, J, V, n_js, act, dz_d, h_d);
+    WR_TRY(launch_lds("joint_bwd_dz_block_kernel", joint_bwd_dz_block_kernel<true>, dim3((unsigned)blocks), dim3(256), lds, st,
+                      gout_d, ep_d, pp_d, w_d, llens_d, tlens_d, B, T, U1, J, V, n_js, act, dz_d, h_d));
+    return launch("joint_dz_act_kernel", joint_dz_act_kernel<float>, dim3(256 * 16), dim3(256), 0, st, ep_d, pp_d, llens_d,
+                  tlens_d, T, U1, J, M, act, dz_d, h_d, J);
 }
 
 // Exact-fp32 weight gradient with the block tiling (called by wr_joint_bwd_dw in joint.hip).  `max_parts` is what the
@@ -1821,21 +1814,13 @@ int joint_bwd_dw_block(const float *gout_d, const float *h_d, const int32_t *lle
     long rows_per_part = (M + parts - 1) / parts;
     rows_per_part = (rows_per_part + 15) / 16 * 16;
     const size_t lds = (size_t)kWStages * 2 * 16 * kWB * sizeof(float);
-    if (llens_d != nullptr && tlens_d != nullptr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_bwd_dw_block_kernel<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(joint_bwd_dw_block_kernel<true>, dim3(n_vs * n_js * parts), dim3(256), lds, st, gout_d, h_d, llens_d,
-                           tlens_d, T, U1, M, V, J, n_vs, n_js, rows_per_part, part_dw, part_db);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_bwd_dw_block_kernel<false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(joint_bwd_dw_block_kernel<false>, dim3(n_vs * n_js * parts), dim3(256), lds, st, gout_d, h_d, llens_d,
-                           tlens_d, T, U1, M, V, J, n_vs, n_js, rows_per_part, part_dw, part_db);
-    }
-    WR_CHECK_LAUNCH("joint_bwd_dw_block_kernel");
-    hipLaunchKernelGGL(split_dw_reduce_kernel, dim3(1024), dim3(256), 0, st, part_dw, part_db, parts, (long)V * J, V, dw_d, db_d);
-    WR_CHECK_LAUNCH("split_dw_reduce_kernel");
-    return WR_OK;
+    WR_TRY(with_bool(llens_d != nullptr && tlens_d != nullptr, [&](auto masked) {
+        return launch_lds("joint_bwd_dw_block_kernel", joint_bwd_dw_block_kernel<masked.value>, dim3(n_vs * n_js * parts),
+                          dim3(256), lds, st, gout_d, h_d, llens_d, tlens_d, T, U1, M, V, J, n_vs, n_js, rows_per_part, part_dw,
+                          part_db);
+    }));
+    return launch("split_dw_reduce_kernel", split_dw_reduce_kernel, dim3(1024), dim3(256), 0, st, part_dw, part_db, parts,
+                  (long)V * J, V, dw_d, db_d);
 }
 }  // namespace wr
 
@@ -1869,11 +1854,10 @@ int joint_fwd_split_launch(const float *ep_d, const float *pp_d, const float *w_
     unsigned short *wh = static_cast<unsigned short *>(workspace_d);
     unsigned short *wl = reinterpret_cast<unsigned short *>(static_cast<char *>(workspace_d) + img);
     if (f16) {                                              // f16 operands (terms == 1): one image, the lo half stays unused
-        hipLaunchKernelGGL(split_w_f16_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, Vp, Jp, reinterpret_cast<_Float16 *>(wh));
-        WR_CHECK_LAUNCH("split_w_f16_kernel");
+        WR_TRY(launch("split_w_f16_kernel", split_w_f16_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, Vp, Jp,
+                      reinterpret_cast<_Float16 *>(wh)));
     } else {
-        hipLaunchKernelGGL(split_w_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, Vp, Jp, wh, wl);
-        WR_CHECK_LAUNCH("split_w_kernel");
+        WR_TRY(launch("split_w_kernel", split_w_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, Vp, Jp, wh, wl));
     }
     const long M = (long)B * T * U1;
     // Column slabs per XCD (part = blockIdx % npart) would keep W in each XCD's L2; measured (B=8: 20.8 / 21.5 / 23.0 ms
@@ -1925,78 +1909,38 @@ int joint_fwd_split_launch(const float *ep_d, const float *pp_d, const float *w_
     const int kb_bias = two ? 0 : (int)bias_al, kb_stage = (two || stage_fits) ? 1 : 0;
     WR_REQUIRE(lds <= 160 * 1024, WR_EUNSUPPORTED, "joint_fwd_split: V=%d needs %zu bytes of LDS", V, lds);
     const dim3 grid((unsigned)((M + cells - 1) / cells * npart));
-#define WR_LAUNCH_SPLIT_WIDE(OutT, TRN, OpT)                                                                             \
-    do {                                                                                                              \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<1, OutT, kEpiStore, 4, 1, TRN, kSWaves, OpT>), \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-        hipLaunchKernelGGL((joint_fwd_split_kernel<1, OutT, kEpiStore, 4, 1, TRN, kSWaves, OpT>), grid, dim3(64 * kSWaves), lds, st, \
-                           ep_d, pp_d, reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl), b_out_d, \
-                           logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, npart, act, static_cast<OutT *>(out_d), \
-                           JointLse{}, kb_bias, kb_stage);                                                            \
-    } while (0)
-#define WR_LAUNCH_SPLIT_TWO(OutT, TRN, OpT)                                                                              \
-    do {                                                                                                              \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<1, OutT, kEpiStore, 2, 2, TRN, kSWaves, OpT>), \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-        hipLaunchKernelGGL((joint_fwd_split_kernel<1, OutT, kEpiStore, 2, 2, TRN, kSWaves, OpT>), grid, dim3(64 * kSWaves), lds, st, \
-                           ep_d, pp_d, reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl), b_out_d, \
-                           logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, npart, act, static_cast<OutT *>(out_d), \
-                           JointLse{}, kb_bias, kb_stage);                                                            \
-    } while (0)
-#define WR_LAUNCH_SPLIT(TERMS, OutT, TRN, OpT)                                                                        \
-    do {                                                                                                              \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<TERMS, OutT, kEpiStore, 2, 1, TRN, kSWaves, OpT>), \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-        hipLaunchKernelGGL((joint_fwd_split_kernel<TERMS, OutT, kEpiStore, 2, 1, TRN, kSWaves, OpT>), grid, dim3(64 * kSWaves), lds, \
-                           st, ep_d, pp_d, reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl), b_out_d, \
-                           logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, npart, act, static_cast<OutT *>(out_d), \
-                           JointLse{}, kb_bias, kb_stage);                                                            \
-    } while (0)
-#define WR_LAUNCH_SPLIT_LSE(TERMS)                                                                                    \
-    do {                                                                                                              \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<TERMS, float, kEpiStoreLse>),           \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-        hipLaunchKernelGGL((joint_fwd_split_kernel<TERMS, float, kEpiStoreLse>), grid, dim3(64 * kSWaves), lds, st, ep_d, pp_d, \
-                           reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl), b_out_d,          \
-                           logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, npart, act, static_cast<float *>(out_d), \
-                           *lse);                                                                                     \
-    } while (0)
-#define WR_BY_OUT(LAUNCH, ...)                                                                                        \
-    do {                                                                                                              \
-        if (out_dtype == 0) LAUNCH(float, __VA_ARGS__);                                                               \
-        else if (out_dtype == 1) LAUNCH(_Float16, __VA_ARGS__);                                                       \
-        else LAUNCH(__bf16, __VA_ARGS__);                                                                             \
-    } while (0)
-#define WR_LAUNCH_SPLIT1(OutT, TRN, OpT) WR_LAUNCH_SPLIT(1, OutT, TRN, OpT)
-#define WR_SINGLE_TERM(OpT)                                                                                           \
-    do {                                                                                                              \
-        if (two && trn) WR_BY_OUT(WR_LAUNCH_SPLIT_TWO, true, OpT);                                                    \
-        else if (two) WR_BY_OUT(WR_LAUNCH_SPLIT_TWO, false, OpT);                                                     \
-        else if (wide && trn) WR_BY_OUT(WR_LAUNCH_SPLIT_WIDE, true, OpT);                                             \
-        else if (wide) WR_BY_OUT(WR_LAUNCH_SPLIT_WIDE, false, OpT);                                                   \
-        else if (trn) WR_BY_OUT(WR_LAUNCH_SPLIT1, true, OpT);                                                         \
-        else WR_BY_OUT(WR_LAUNCH_SPLIT1, false, OpT);                                                                 \
-    } while (0)
-    if (lse) {
-        if (terms == 3) WR_LAUNCH_SPLIT_LSE(3); else WR_LAUNCH_SPLIT_LSE(1);
-    } else if (terms == 3) {
-        if (out_dtype == 0) WR_LAUNCH_SPLIT(3, float, false, __bf16);
-        else if (out_dtype == 1) WR_LAUNCH_SPLIT(3, _Float16, false, __bf16);
-        else WR_LAUNCH_SPLIT(3, __bf16, false, __bf16);
-    } else if (f16) {
-        WR_SINGLE_TERM(_Float16);
-    } else {
-        WR_SINGLE_TERM(__bf16);
-    }
-#undef WR_SINGLE_TERM
-#undef WR_LAUNCH_SPLIT1
-#undef WR_BY_OUT
-#undef WR_LAUNCH_SPLIT_WIDE
-#undef WR_LAUNCH_SPLIT_TWO
-#undef WR_LAUNCH_SPLIT
-#undef WR_LAUNCH_SPLIT_LSE
-    WR_CHECK_LAUNCH("joint_fwd_split_kernel");
-    return WR_OK;
+    const u32x4 *whf = reinterpret_cast<const u32x4 *>(wh), *wlf = reinterpret_cast<const u32x4 *>(wl);
+    if (lse)                                                // row statistics: fp32 logits, the 64-cell one-per-CU form
+        return with_int<3, 1>(terms, [&](auto terms_c) {
+            return launch_lds("joint_fwd_split_kernel", joint_fwd_split_kernel<terms_c.value, float, kEpiStoreLse>, grid,
+                              dim3(64 * kSWaves), lds, st, ep_d, pp_d, whf, wlf, b_out_d, logit_lengths_d, target_lengths_d, B,
+                              T, U1, J, Jp, V, Vp, npart, act, static_cast<float *>(out_d), *lse, 0, 0);
+        });
+    // logits only: RT row tiles of 32 cells per workgroup, OCC workgroups per CU, operands of op's type
+    const auto store = [&](auto terms_c, auto out, auto rt, auto occ, auto trn_c, auto op) {
+        using OutT = decltype(out);
+        return launch_lds("joint_fwd_split_kernel",
+                          joint_fwd_split_kernel<terms_c.value, OutT, kEpiStore, rt.value, occ.value, trn_c.value, kSWaves,
+                                                 decltype(op)>,
+                          grid, dim3(64 * kSWaves), lds, st, ep_d, pp_d, whf, wlf, b_out_d, logit_lengths_d, target_lengths_d, B,
+                          T, U1, J, Jp, V, Vp, npart, act, static_cast<OutT *>(out_d), JointLse{}, kb_bias, kb_stage);
+    };
+    if (terms == 3)
+        return with_dtype(out_dtype, [&](auto out) {
+            return store(int_c<3>{}, out, int_c<2>{}, int_c<1>{}, std::false_type{}, __bf16{});
+        });
+    // single-term (AMP) mode, f16 or bf16 operands: two 64-cell workgroups per CU, 128 cells, or the first 64-cell form
+    return with_bool(f16, [&](auto f16_c) {
+        using OpT = std::conditional_t<f16_c.value, _Float16, __bf16>;
+        const auto form = [&](auto rt, auto occ) {
+            return with_bool(trn, [&](auto trn_c) {
+                return with_dtype(out_dtype, [&](auto out) { return store(int_c<1>{}, out, rt, occ, trn_c, OpT{}); });
+            });
+        };
+        if (two) return form(int_c<2>{}, int_c<2>{});
+        if (wide) return form(int_c<4>{}, int_c<1>{});
+        return form(int_c<2>{}, int_c<1>{});
+    });
 }
 }  // namespace
 
@@ -2014,8 +1958,7 @@ int joint_fwd_split_epi(const float *ep_d, const float *pp_d, const float *w_out
     unsigned short *wh = static_cast<unsigned short *>(workspace_d);
     unsigned short *wl = reinterpret_cast<unsigned short *>(static_cast<char *>(workspace_d) + img);
     if (!w_ready) {
-        hipLaunchKernelGGL(split_w_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, Vp, Jp, wh, wl);
-        WR_CHECK_LAUNCH("split_w_kernel");
+        WR_TRY(launch("split_w_kernel", split_w_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, Vp, Jp, wh, wl));
     }
     const long cells = epi == kEpiGrad ? lse.m_end - lse.m_begin : (long)B * T * U1;
     const size_t tile_lds = (size_t)2 * kSM * (Jp + 8) * sizeof(unsigned short);
@@ -2024,30 +1967,19 @@ int joint_fwd_split_epi(const float *ep_d, const float *pp_d, const float *w_out
     const size_t lds = (used > joint_lse_exchange_bytes(kSWaves) ? used : joint_lse_exchange_bytes(kSWaves)) + joint_epi_rows_bytes();
     WR_REQUIRE(lds <= 160 * 1024, WR_EUNSUPPORTED, "joint_fwd_split: V=%d needs %zu bytes of LDS", V, lds);
     const dim3 grid((unsigned)((cells + kSM - 1) / kSM));
-#define WR_LAUNCH_SPLIT_EPI(EPI_, lse_)                                                                                \
-    do {                                                                                                              \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_fwd_split_kernel<3, float, EPI_>),              \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-        hipLaunchKernelGGL((joint_fwd_split_kernel<3, float, EPI_>), grid, dim3(64 * kSWaves), lds, st, ep_d, pp_d,    \
-                           reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl), b_out_d, llens,   \
-                           tlens, B, T, U1, J, Jp, V, Vp, 1, act, out_d, lse_, (int)bias_al, 0);                       \
-    } while (0)
-    if (epi == kEpiGrad) {
-        WR_LAUNCH_SPLIT_EPI(kEpiGrad, lse);
-        WR_CHECK_LAUNCH("joint_fwd_split_kernel (gradient epilogue)");
-        return WR_OK;
-    }
+    const auto run = [&](const char *name, auto epi_c, const JointLse &l) {
+        return launch_lds(name, joint_fwd_split_kernel<3, float, epi_c.value>, grid, dim3(64 * kSWaves), lds, st, ep_d, pp_d,
+                          reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl), b_out_d, llens, tlens, B, T,
+                          U1, J, Jp, V, Vp, 1, act, out_d, l, (int)bias_al, 0);
+    };
+    if (epi == kEpiGrad) return run("joint_fwd_split_kernel (gradient epilogue)", int_c<kEpiGrad>{}, lse);
     (void)hipMemsetAsync(lse.repair, 0, sizeof(int32_t), st);
-    WR_LAUNCH_SPLIT_EPI(kEpiStats, lse);
-    WR_CHECK_LAUNCH("joint_fwd_split_kernel (statistics epilogue)");
+    WR_TRY(run("joint_fwd_split_kernel (statistics epilogue)", int_c<kEpiStats>{}, lse));
     // repair: the same launch with a running maximum, whose workgroups leave at once unless a partial sum overflowed
     JointLse rep = lse;
     rep.run_if = lse.repair;
     rep.online = 1;
-    WR_LAUNCH_SPLIT_EPI(kEpiStats, rep);
-#undef WR_LAUNCH_SPLIT_EPI
-    WR_CHECK_LAUNCH("joint_fwd_split_kernel (statistics epilogue, repair)");
-    return WR_OK;
+    return run("joint_fwd_split_kernel (statistics epilogue, repair)", int_c<kEpiStats>{}, rep);
 }
 }  // namespace wr
 
@@ -2059,8 +1991,7 @@ extern "C" int wr_joint_fwd_split(const float *ep_d, const float *pp_d, const fl
     if (int rc = split_check(B, T, U1, J, V, terms, out_dtype, activation)) return rc;
     WR_REQUIRE(ep_d && pp_d && w_out_d && b_out_d && out_d && workspace_d, WR_EINVAL,
                "joint_fwd_split: null pointer argument");
-    WR_REQUIRE((logit_lengths_d == nullptr) == (target_lengths_d == nullptr), WR_EINVAL,
-               "joint_fwd_split: pass both length arrays or neither");
+    WR_TRY(check_length_pair("joint_fwd_split", logit_lengths_d, target_lengths_d));
     return joint_fwd_split_launch(ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation,
                                   terms, out_d, out_dtype, workspace_d, workspace_bytes, nullptr, static_cast<hipStream_t>(stream));
 }
@@ -2072,8 +2003,7 @@ extern "C" int wr_joint_fwd_f16(const float *ep_d, const float *pp_d, const floa
 {
     if (int rc = split_check(B, T, U1, J, V, 1, out_dtype, activation)) return rc;
     WR_REQUIRE(ep_d && pp_d && w_out_d && b_out_d && out_d && workspace_d, WR_EINVAL, "joint_fwd_f16: null pointer argument");
-    WR_REQUIRE((logit_lengths_d == nullptr) == (target_lengths_d == nullptr), WR_EINVAL,
-               "joint_fwd_f16: pass both length arrays or neither");
+    WR_TRY(check_length_pair("joint_fwd_f16", logit_lengths_d, target_lengths_d));
     return joint_fwd_split_launch(ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation,
                                   1, out_d, out_dtype, workspace_d, workspace_bytes, nullptr, static_cast<hipStream_t>(stream), true);
 }
@@ -2088,15 +2018,8 @@ extern "C" int wr_joint_fwd_split_lse(const float *ep_d, const float *pp_d, cons
     WR_REQUIRE(ep_d && pp_d && w_out_d && b_out_d && out_d && workspace_d && rnnt_workspace_d, WR_EINVAL,
                "joint_fwd_split_lse: null pointer argument");
     WR_REQUIRE(logit_lengths_d && target_lengths_d, WR_EINVAL, "joint_fwd_split_lse: both length arrays are required");
-    WR_REQUIRE(targets_d || U1 == 1, WR_EINVAL, "joint_fwd_split_lse: targets is null");
-    WR_REQUIRE(blank >= 0 && blank < V, WR_EINVAL, "joint_fwd_split_lse: blank %d out of range [0,%d)", blank, V);
-    WR_REQUIRE(U1 <= kRnntMaxCols, WR_EUNSUPPORTED, "joint_fwd_split_lse: U1=%d exceeds the loss's limit of %d", U1, kRnntMaxCols);
-    const RnntWs w = rnnt_ws_layout(B, T, U1);
-    WR_REQUIRE(rnnt_workspace_bytes >= w.total, WR_EWORKSPACE, "joint_fwd_split_lse: RNN-T workspace %zu < required %zu",
-               rnnt_workspace_bytes, w.total);
-    char *rws = static_cast<char *>(rnnt_workspace_d);
-    JointLse lse{targets_d, blank, w.S, reinterpret_cast<float2 *>(rws + w.lp_off), reinterpret_cast<float *>(rws + w.denom_off),
-                 reinterpret_cast<int32_t *>(rws + w.flag_off)};
+    WR_TRY(joint_rnnt_side_check("joint_fwd_split_lse", targets_d, B, T, U1, V, blank, -1, rnnt_workspace_bytes));
+    const JointLse lse = joint_lse_over(targets_d, blank, rnnt_ws_layout(B, T, U1), static_cast<char *>(rnnt_workspace_d));
     return joint_fwd_split_launch(ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation,
                                   terms, out_d, WR_F32, workspace_d, workspace_bytes, &lse, static_cast<hipStream_t>(stream));
 }
@@ -2119,8 +2042,7 @@ int joint_bwd_dz_split_launch(const void *gout_d, bool g16, const float *ep_d, c
                "joint_bwd_dz_split: V=%d not supported (16-byte aligned gradient rows: V a multiple of %d, at least 32)", V,
                g16 ? 8 : 4);
     WR_REQUIRE(gout_d && ep_d && pp_d && w_out_d && dz_d && workspace_d, WR_EINVAL, "joint_bwd_dz_split: null pointer argument");
-    WR_REQUIRE((logit_lengths_d == nullptr) == (target_lengths_d == nullptr), WR_EINVAL,
-               "joint_bwd_dz_split: pass both length arrays or neither");
+    WR_TRY(check_length_pair("joint_bwd_dz_split", logit_lengths_d, target_lengths_d));
     const int n_jt = (J + 31) / 32, D = (V + 31) / 32;
     const size_t img = align_up((size_t)n_jt * D * 2 * 64 * 8 * sizeof(unsigned short), 256);
     WR_REQUIRE(workspace_bytes >= 2 * img, WR_EWORKSPACE, "joint_bwd_dz_split: workspace too small");
@@ -2128,37 +2050,35 @@ int joint_bwd_dz_split_launch(const void *gout_d, bool g16, const float *ep_d, c
     unsigned short *wh = static_cast<unsigned short *>(workspace_d);
     unsigned short *wl = reinterpret_cast<unsigned short *>(static_cast<char *>(workspace_d) + img);
     if (f16) {                                              // f16 operands (terms == 1): one image
-        hipLaunchKernelGGL(split_w_dz_f16_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, D, n_jt, reinterpret_cast<_Float16 *>(wh));
-        WR_CHECK_LAUNCH("split_w_dz_f16_kernel");
+        WR_TRY(launch("split_w_dz_f16_kernel", split_w_dz_f16_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, D, n_jt,
+                      reinterpret_cast<_Float16 *>(wh)));
     } else {
-        hipLaunchKernelGGL(split_w_dz_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, D, n_jt, wh, wl);
-        WR_CHECK_LAUNCH("split_w_dz_kernel");
+        WR_TRY(launch("split_w_dz_kernel", split_w_dz_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, D, n_jt, wh, wl));
     }
     const long M = (long)B * T * U1;
-    const dim3 grid((unsigned)((M + kSM - 1) / kSM));
-    {                                                       // 128-cell tiling, W fragments staged in LDS
-        const size_t lds = (size_t)kZStages * 2 * 16 * 64 * 16 + (size_t)kZM2 * (2 * sizeof(long) + sizeof(int));
-        const dim3 grid2((unsigned)((M + kZM2 - 1) / kZM2));
-#define WR_LAUNCH_DZ2(TERMS, FULL_, GT, OpT)                                                                           \
-        do {                                                                                                          \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_bwd_dz_split128_kernel<TERMS, FULL_, GT, OpT>), \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
-            hipLaunchKernelGGL((joint_bwd_dz_split128_kernel<TERMS, FULL_, GT, OpT>), grid2, dim3(256), lds, st,        \
-                               static_cast<const GT *>(gout_d), ep_d, pp_d,                                            \
-                               reinterpret_cast<const u32x4 *>(wh), reinterpret_cast<const u32x4 *>(wl),               \
-                               logit_lengths_d, target_lengths_d, B, T, U1, J, V, D, n_jt, activation, dz_d, h_d);     \
-        } while (0)
-#define WR_LAUNCH_DZ2_T(TERMS, FULL_) do { if (g16) WR_LAUNCH_DZ2(TERMS, FULL_, __bf16, __bf16); else WR_LAUNCH_DZ2(TERMS, FULL_, float, __bf16); } while (0)
-#define WR_LAUNCH_DZ2_H(FULL_) do { if (g16) WR_LAUNCH_DZ2(1, FULL_, _Float16, _Float16); else WR_LAUNCH_DZ2(1, FULL_, float, _Float16); } while (0)
-        if (f16) { if (n_jt == 16) WR_LAUNCH_DZ2_H(true); else WR_LAUNCH_DZ2_H(false); }
-        else if (n_jt == 16) { if (terms == 3) WR_LAUNCH_DZ2_T(3, true); else WR_LAUNCH_DZ2_T(1, true); }
-        else { if (terms == 3) WR_LAUNCH_DZ2_T(3, false); else WR_LAUNCH_DZ2_T(1, false); }
-#undef WR_LAUNCH_DZ2_H
-#undef WR_LAUNCH_DZ2_T
-#undef WR_LAUNCH_DZ2
-        WR_CHECK_LAUNCH("joint_bwd_dz_split128_kernel");
-    }
-    return WR_OK;
+    // 128-cell tiling, W fragments staged in LDS
+    const size_t lds = (size_t)kZStages * 2 * 16 * 64 * 16 + (size_t)kZM2 * (2 * sizeof(long) + sizeof(int));
+    const dim3 grid2((unsigned)((M + kZM2 - 1) / kZM2));
+    // full: J = 512 (n_jt == 16); g: the incoming gradient's type; op: the operands' type
+    const auto dz = [&](auto terms_c, auto full, auto g, auto op) {
+        using GT = decltype(g);
+        return launch_lds("joint_bwd_dz_split128_kernel",
+                          joint_bwd_dz_split128_kernel<terms_c.value, full.value, GT, decltype(op)>, grid2, dim3(256), lds, st,
+                          static_cast<const GT *>(gout_d), ep_d, pp_d, reinterpret_cast<const u32x4 *>(wh),
+                          reinterpret_cast<const u32x4 *>(wl), logit_lengths_d, target_lengths_d, B, T, U1, J, V, D, n_jt,
+                          activation, dz_d, h_d);
+    };
+    if (f16)                                                // f16 operands: single-term only, a 16-bit gradient is f16
+        return with_bool(n_jt == 16, [&](auto full) {
+            if (g16) return dz(int_c<1>{}, full, _Float16{}, _Float16{});
+            return dz(int_c<1>{}, full, float{}, _Float16{});
+        });
+    return with_bool(n_jt == 16, [&](auto full) {           // bf16 operands: a 16-bit gradient is bf16
+        return with_int<3, 1>(terms, [&](auto terms_c) {
+            if (g16) return dz(terms_c, full, __bf16{}, __bf16{});
+            return dz(terms_c, full, float{}, __bf16{});
+        });
+    });
 }
 }  // namespace
 
@@ -2264,8 +2184,7 @@ int joint_db_16_launch(const void *gout_bf16_d, bool f16, const int32_t *logit_l
     using namespace wr;
     WR_REQUIRE(B > 0 && T > 0 && U1 > 0 && V > 0 && V % 8 == 0, WR_EINVAL, "joint_db_bf16: sizes must be positive, V a multiple of 8");
     WR_REQUIRE(gout_bf16_d && db_d && workspace_d, WR_EINVAL, "joint_db_bf16: null pointer argument");
-    WR_REQUIRE((logit_lengths_d == nullptr) == (target_lengths_d == nullptr), WR_EINVAL,
-               "joint_db_bf16: pass both length arrays or neither");
+    WR_TRY(check_length_pair("joint_db_bf16", logit_lengths_d, target_lengths_d));
     WR_REQUIRE(workspace_bytes >= wr_joint_db_workspace_bytes(B, T, U1, V), WR_EWORKSPACE, "joint_db_bf16: workspace too small");
     const long M = (long)B * T * U1;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2273,21 +2192,18 @@ int joint_db_16_launch(const void *gout_bf16_d, bool f16, const int32_t *logit_l
     unsigned char *mask = nullptr;
     if (logit_lengths_d != nullptr) {
         mask = reinterpret_cast<unsigned char *>(static_cast<char *>(workspace_d) + align_up((size_t)kDbParts * V * sizeof(float), 256));
-        hipLaunchKernelGGL(cell_mask_kernel, dim3(1024), dim3(256), 0, st, logit_lengths_d, target_lengths_d, T, U1, M, mask);
-        WR_CHECK_LAUNCH("cell_mask_kernel");
+        WR_TRY(launch("cell_mask_kernel", cell_mask_kernel, dim3(1024), dim3(256), 0, st, logit_lengths_d, target_lengths_d,
+                      T, U1, M, mask));
     }
     const int parts = M < kDbParts ? (int)M : kDbParts;
     const long rows_per_part = (M + parts - 1) / parts;
-    if (f16)
-        hipLaunchKernelGGL(joint_db_bf16_kernel<_Float16>, dim3((V / 8 + kDbThreads - 1) / kDbThreads, parts), dim3(kDbThreads), 0, st,
-                           static_cast<const _Float16 *>(gout_bf16_d), mask, M, V, rows_per_part, part);
-    else
-        hipLaunchKernelGGL(joint_db_bf16_kernel<__bf16>, dim3((V / 8 + kDbThreads - 1) / kDbThreads, parts), dim3(kDbThreads), 0, st,
-                           static_cast<const __bf16 *>(gout_bf16_d), mask, M, V, rows_per_part, part);
-    WR_CHECK_LAUNCH("joint_db_bf16_kernel");
-    hipLaunchKernelGGL(joint_db_reduce_kernel, dim3((V + 255) / 256), dim3(256), 0, st, part, parts, V, db_d);
-    WR_CHECK_LAUNCH("joint_db_reduce_kernel");
-    return WR_OK;
+    WR_TRY(with_bool(f16, [&](auto f16_c) {
+        using GT = std::conditional_t<f16_c.value, _Float16, __bf16>;
+        return launch("joint_db_bf16_kernel", joint_db_bf16_kernel<GT>, dim3((V / 8 + kDbThreads - 1) / kDbThreads, parts),
+                      dim3(kDbThreads), 0, st, static_cast<const GT *>(gout_bf16_d), mask, M, V, rows_per_part, part);
+    }));
+    return launch("joint_db_reduce_kernel", joint_db_reduce_kernel, dim3((V + 255) / 256), dim3(256), 0, st, part, parts, V,
+                  db_d);
 }
 }  // namespace
 
@@ -2312,23 +2228,19 @@ extern "C" int wr_joint_dz_act(float *dz_d, const float *ep_d, const float *pp_d
     WR_REQUIRE(B > 0 && T > 0 && U1 > 0 && J > 0 && J % 4 == 0, WR_EINVAL, "joint_dz_act: sizes must be positive, J a multiple of 4");
     WR_REQUIRE(activation >= WR_ACT_TANH && activation <= WR_ACT_GELU, WR_EINVAL, "joint_dz_act: unknown activation %d", activation);
     WR_REQUIRE(dz_d && ep_d && pp_d, WR_EINVAL, "joint_dz_act: null pointer argument");
-    WR_REQUIRE((logit_lengths_d == nullptr) == (target_lengths_d == nullptr), WR_EINVAL,
-               "joint_dz_act: pass both length arrays or neither");
+    WR_TRY(check_length_pair("joint_dz_act", logit_lengths_d, target_lengths_d));
     WR_REQUIRE(h_d == nullptr || ((h_dtype == WR_F32 || h_dtype == WR_BF16 || h_dtype == WR_F16) && h_ld >= J && h_ld % 4 == 0),
                WR_EINVAL, "joint_dz_act: h must be fp32, fp16 or bf16 with a row stride >= J that is a multiple of 4");
     const long M = (long)B * T * U1;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (h_d != nullptr && h_dtype == WR_BF16)
-        hipLaunchKernelGGL(joint_dz_act_kernel<__bf16>, dim3(256 * 16), dim3(256), 0, st, ep_d, pp_d, logit_lengths_d,
-                           target_lengths_d, T, U1, J, M, activation, dz_d, static_cast<__bf16 *>(h_d), h_ld);
-    else if (h_d != nullptr && h_dtype == WR_F16)
-        hipLaunchKernelGGL(joint_dz_act_kernel<_Float16>, dim3(256 * 16), dim3(256), 0, st, ep_d, pp_d, logit_lengths_d,
-                           target_lengths_d, T, U1, J, M, activation, dz_d, static_cast<_Float16 *>(h_d), h_ld);
-    else
-        hipLaunchKernelGGL(joint_dz_act_kernel<float>, dim3(256 * 16), dim3(256), 0, st, ep_d, pp_d, logit_lengths_d,
-                           target_lengths_d, T, U1, J, M, activation, dz_d, static_cast<float *>(h_d), h_d ? h_ld : J);
-    WR_CHECK_LAUNCH("joint_dz_act_kernel");
-    return WR_OK;
+    const auto run = [&](auto h, int ld) {
+        using HT = decltype(h);
+        return launch("joint_dz_act_kernel", joint_dz_act_kernel<HT>, dim3(256 * 16), dim3(256), 0, st, ep_d, pp_d,
+                      logit_lengths_d, target_lengths_d, T, U1, J, M, activation, dz_d, static_cast<HT *>(h_d), ld);
+    };
+    if (h_d != nullptr && h_dtype == WR_BF16) return run(__bf16{}, h_ld);
+    if (h_d != nullptr && h_dtype == WR_F16) return run(_Float16{}, h_ld);
+    return run(float{}, h_d ? h_ld : J);
 }
 
 extern "C" size_t wr_joint_dw_split_workspace_bytes(int B, int T, int U1, int J, int V)
@@ -2348,8 +2260,7 @@ int joint_bwd_dw_split_launch(const void *gout_d, bool g16, const float *h_d, co
     WR_REQUIRE(V % 4 == 0 && J % 4 == 0, WR_EUNSUPPORTED,
                "joint_bwd_dw_split: V=%d, J=%d not supported (16-byte aligned rows: multiples of 4)", V, J);
     WR_REQUIRE(gout_d && h_d && dw_d && workspace_d, WR_EINVAL, "joint_bwd_dw_split: null pointer argument");
-    WR_REQUIRE((logit_lengths_d == nullptr) == (target_lengths_d == nullptr), WR_EINVAL,
-               "joint_bwd_dw_split: pass both length arrays or neither");
+    WR_TRY(check_length_pair("joint_bwd_dw_split", logit_lengths_d, target_lengths_d));
     const long M = (long)B * T * U1;
     const int parts = split_dw_parts(V, J);
     const size_t pbytes = align_up((size_t)parts * ((size_t)V * J + V) * sizeof(float), 256);
@@ -2361,29 +2272,26 @@ int joint_bwd_dw_split_launch(const void *gout_d, bool g16, const float *h_d, co
     unsigned char *mask = nullptr;
     if (logit_lengths_d != nullptr) {
         mask = reinterpret_cast<unsigned char *>(static_cast<char *>(workspace_d) + pbytes);
-        hipLaunchKernelGGL(cell_mask_kernel, dim3(1024), dim3(256), 0, st, logit_lengths_d, target_lengths_d, T, U1, M, mask);
-        WR_CHECK_LAUNCH("cell_mask_kernel");
+        WR_TRY(launch("cell_mask_kernel", cell_mask_kernel, dim3(1024), dim3(256), 0, st, logit_lengths_d, target_lengths_d,
+                      T, U1, M, mask));
     }
     const int n_vs = (V + kWB - 1) / kWB, n_js = (J + kWB - 1) / kWB;
     long rows_per_part = (M + parts - 1) / parts;
     rows_per_part = (rows_per_part + 15) / 16 * 16;
     const size_t lds = (size_t)kWStages * 2 * 2 * 2 * 4 * 64 * 16;   // three stages of ready-made fragments
-#define WR_LAUNCH_DW(TERMS, GT, OpT)                                                                                   \
-    do {                                                                                                              \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(joint_bwd_dw_split_kernel<TERMS, GT, OpT>),            \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-        hipLaunchKernelGGL((joint_bwd_dw_split_kernel<TERMS, GT, OpT>), dim3(n_vs * n_js * parts), dim3(512), lds, st,  \
-                           static_cast<const GT *>(gout_d), h_d, mask, M, V, J, n_vs, n_js, rows_per_part, part_dw, part_db); \
-    } while (0)
-    if (f16) { if (g16) WR_LAUNCH_DW(1, _Float16, _Float16); else WR_LAUNCH_DW(1, float, _Float16); }
-    else if (g16) { if (terms == 3) WR_LAUNCH_DW(3, __bf16, __bf16); else WR_LAUNCH_DW(1, __bf16, __bf16); }
-    else { if (terms == 3) WR_LAUNCH_DW(3, float, __bf16); else WR_LAUNCH_DW(1, float, __bf16); }
-#undef WR_LAUNCH_DW
-    WR_CHECK_LAUNCH("joint_bwd_dw_split_kernel");
-    hipLaunchKernelGGL(split_dw_reduce_kernel, dim3(1024), dim3(256), 0, st, part_dw, part_db, parts, (long)V * J, V, dw_d,
-                       db_d);
-    WR_CHECK_LAUNCH("split_dw_reduce_kernel");
-    return WR_OK;
+    // g: the incoming gradient's type; op: the operands' type (f16 operands: single-term only)
+    const auto dw = [&](auto terms_c, auto g, auto op) {
+        using GT = decltype(g);
+        return launch_lds("joint_bwd_dw_split_kernel", joint_bwd_dw_split_kernel<terms_c.value, GT, decltype(op)>,
+                          dim3(n_vs * n_js * parts), dim3(512), lds, st, static_cast<const GT *>(gout_d), h_d, mask, M, V, J,
+                          n_vs, n_js, rows_per_part, part_dw, part_db);
+    };
+    if (f16 && g16) WR_TRY(dw(int_c<1>{}, _Float16{}, _Float16{}));
+    else if (f16) WR_TRY(dw(int_c<1>{}, float{}, _Float16{}));
+    else if (g16) WR_TRY(with_int<3, 1>(terms, [&](auto terms_c) { return dw(terms_c, __bf16{}, __bf16{}); }));
+    else WR_TRY(with_int<3, 1>(terms, [&](auto terms_c) { return dw(terms_c, float{}, __bf16{}); }));
+    return launch("split_dw_reduce_kernel", split_dw_reduce_kernel, dim3(1024), dim3(256), 0, st, part_dw, part_db, parts,
+                  (long)V * J, V, dw_d, db_d);
 }
 }  // namespace
 

@@ -14,6 +14,7 @@
 //                             double-buffered LDS slot plus one barrier across waves.  fp64 state, PF rows in flight.
 //   lattice_export_kernel     alpha / beta of either lattice as plain (B, T, U1) floats, for the tests.
 #include "rnnt_lattice.hpp"
+#include "wr_launch.hpp"
 
 namespace wr {
 namespace {
@@ -224,26 +225,20 @@ extern "C" int wr_rnnt_lattice_sweeps(const int32_t *logit_lengths_d, const int3
     const long cells = (long)B * w.S * U1;
     float2 *lp_skew = reinterpret_cast<float2 *>(ws + w.lp_off);
     if (modified) {
-        hipLaunchKernelGGL((lattice_prepare_kernel<true>), dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st,
-                           logit_lengths_d, target_lengths_d, B, T, U1, w.S, delay_penalty, lp_skew,
-                           reinterpret_cast<float2 *>(ws + w.alpha_off));
-        WR_CHECK_LAUNCH("lattice_prepare_kernel<modified>");
+        WR_TRY(launch("lattice_prepare_kernel<modified>", lattice_prepare_kernel<true>,
+                      dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, logit_lengths_d, target_lengths_d, B, T, U1,
+                      w.S, delay_penalty, lp_skew, reinterpret_cast<float2 *>(ws + w.alpha_off)));
         const LatView v = lattice_view(w, ws, true);
-        hipLaunchKernelGGL((lattice_mod_sweep_kernel<8>), dim3(B, 2), dim3(64 * w.K), 0, st, v.lp, logit_lengths_d,
-                           target_lengths_d, T, U1, w.S, const_cast<double *>(v.alpha), const_cast<double *>(v.beta),
-                           reinterpret_cast<double *>(ws + w.ll_off), reinterpret_cast<double *>(ws + w.cost_off), costs_d,
-                           reinterpret_cast<double *>(ws + w.dump_off));
-        WR_CHECK_LAUNCH("lattice_mod_sweep_kernel");
-        return WR_OK;
+        return launch("lattice_mod_sweep_kernel", lattice_mod_sweep_kernel<8>, dim3(B, 2), dim3(64 * w.K), 0, st, v.lp,
+                      logit_lengths_d, target_lengths_d, T, U1, w.S, const_cast<double *>(v.alpha),
+                      const_cast<double *>(v.beta), reinterpret_cast<double *>(ws + w.ll_off),
+                      reinterpret_cast<double *>(ws + w.cost_off), costs_d, reinterpret_cast<double *>(ws + w.dump_off));
     }
-    if (delay_penalty > 0.0) {
-        hipLaunchKernelGGL((lattice_prepare_kernel<false>), dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st,
-                           logit_lengths_d, target_lengths_d, B, T, U1, w.S, delay_penalty, lp_skew, (float2 *)nullptr);
-        WR_CHECK_LAUNCH("lattice_prepare_kernel<regular>");
-    }
-    rnnt_launch_sweep(w, ws, logit_lengths_d, target_lengths_d, B, T, U1, costs_d, st);
-    WR_CHECK_LAUNCH("rnnt_sweep_kernel");
-    return WR_OK;
+    if (delay_penalty > 0.0)
+        WR_TRY(launch("lattice_prepare_kernel<regular>", lattice_prepare_kernel<false>,
+                      dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, logit_lengths_d, target_lengths_d, B, T, U1,
+                      w.S, delay_penalty, lp_skew, nullptr));
+    return rnnt_launch_sweep(w, ws, logit_lengths_d, target_lengths_d, B, T, U1, costs_d, st);
 }
 
 extern "C" int wr_rnnt_lattice_export(const void *workspace_d, size_t workspace_bytes, const int32_t *logit_lengths_d,
@@ -260,12 +255,11 @@ extern "C" int wr_rnnt_lattice_export(const void *workspace_d, size_t workspace_
     const LatView v = lattice_view(w, static_cast<const char *>(workspace_d), modified);
     const unsigned blocks = (unsigned)(((long)B * T * U1 + 255) / 256);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (modified)
-        hipLaunchKernelGGL((lattice_export_kernel<kLatModified>), dim3(blocks), dim3(256), 0, st, v.alpha, v.beta,
-                           logit_lengths_d, target_lengths_d, B, T, U1, w.S, alpha_d, beta_d);
-    else
-        hipLaunchKernelGGL((lattice_export_kernel<kLatRegular>), dim3(blocks), dim3(256), 0, st, v.alpha, v.beta,
-                           logit_lengths_d, target_lengths_d, B, T, U1, w.S, alpha_d, beta_d);
-    WR_CHECK_LAUNCH("lattice_export_kernel");
-    return WR_OK;
+    // (the modified arm comes first, as it always has: the order of the arms is the order of the kernels in the code
+    // object, which a host-only change leaves byte-identical)
+    return with_bool(modified, [&](auto mod) {
+        constexpr int LAT = mod.value ? kLatModified : kLatRegular;
+        return launch("lattice_export_kernel", lattice_export_kernel<LAT>, dim3(blocks), dim3(256), 0, st, v.alpha, v.beta,
+                      logit_lengths_d, target_lengths_d, B, T, U1, w.S, alpha_d, beta_d);
+    });
 }

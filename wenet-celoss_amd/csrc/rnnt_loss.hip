@@ -33,6 +33,7 @@
 // logits; 2 % faint); the share depends on the data.
 #include "row_stream.hpp"
 #include "wr_common.hpp"
+#include "wr_launch.hpp"
 
 namespace wr {
 namespace {
@@ -458,6 +459,11 @@ int check_shape(int B, int Tmax, int U1max, int V, int blank)
     return WR_OK;
 }
 
+constexpr size_t kLseBytesPerWave = 16 * 1024;     // one row of 5 000 fp32 logits
+constexpr size_t kGradBytesPerWave = 68 * 1024;    // 3.4 such rows on average
+
+}  // namespace
+
 // Grid of a streaming pass: 4-wave workgroups, each wave visits rows r, r + G, r + 2G, ... (G = waves of the grid).
 // Round 1 ran persistent grids (12 workgroups per CU, ~390 rows per wave at the BASELINE shape).  Measured in round 2
 // (tools/tune_rnnt.py SWEEP=grid, sustained fwd + bwd sequence): many short-lived workgroups are faster -- the hardware
@@ -486,19 +492,14 @@ int stream_grid(long nrows, int knob, size_t row_bytes, size_t bytes_per_wave)
     return (int)blocks;
 }
 
-constexpr size_t kLseBytesPerWave = 16 * 1024;     // one row of 5 000 fp32 logits
-constexpr size_t kGradBytesPerWave = 68 * 1024;    // 3.4 such rows on average
-
-}  // namespace
-
-void rnnt_launch_sweep(const RnntWs &w, char *ws, const int32_t *llens, const int32_t *tlens, int B, int Tmax,
-                       int U1max, float *costs, hipStream_t st)
+int rnnt_launch_sweep(const RnntWs &w, char *ws, const int32_t *llens, const int32_t *tlens, int B, int Tmax,
+                      int U1max, float *costs, hipStream_t st)
 {
-    hipLaunchKernelGGL((rnnt_sweep_kernel<8>), dim3(B, 2), dim3(64 * w.K), 0, st,
-                       reinterpret_cast<const float2 *>(ws + w.lp_off), llens, tlens, Tmax, U1max, w.S,
-                       reinterpret_cast<double *>(ws + w.alpha_off), reinterpret_cast<double *>(ws + w.beta_off),
-                       reinterpret_cast<double *>(ws + w.ll_off), reinterpret_cast<double *>(ws + w.cost_off), costs,
-                       reinterpret_cast<double *>(ws + w.dump_off));
+    return launch("rnnt_sweep_kernel", rnnt_sweep_kernel<8>, dim3(B, 2), dim3(64 * w.K), 0, st,
+                  reinterpret_cast<const float2 *>(ws + w.lp_off), llens, tlens, Tmax, U1max, w.S,
+                  reinterpret_cast<double *>(ws + w.alpha_off), reinterpret_cast<double *>(ws + w.beta_off),
+                  reinterpret_cast<double *>(ws + w.ll_off), reinterpret_cast<double *>(ws + w.cost_off), costs,
+                  reinterpret_cast<double *>(ws + w.dump_off));
 }
 
 int rnnt_launch_lse(const RnntWs &w, char *ws, const void *logits_d, int dtype, const int32_t *targets_d,
@@ -508,20 +509,19 @@ int rnnt_launch_lse(const RnntWs &w, char *ws, const void *logits_d, int dtype, 
     const long nrows = (long)B * Tmax * U1max;
     const size_t row_bytes = (size_t)V * (dtype == WR_F32 ? 4 : 2);
     const dim3 grid1(stream_grid(nrows, tune_get(kTuneLseBlocksPerCu), row_bytes, kLseBytesPerWave));
-#define WR_LAUNCH_LSE(T, NT)                                                                                        \
-    if (tune_get(kTuneLseUnroll) >= 16) WR_LAUNCH_LSE_U(T, NT, 16); else if (tune_get(kTuneLseUnroll) >= 8) WR_LAUNCH_LSE_U(T, NT, 8); else WR_LAUNCH_LSE_U(T, NT, 4)
-#define WR_LAUNCH_LSE_U(T, NT, UN)                                                                                  \
-    hipLaunchKernelGGL((rnnt_lse_kernel<T, NT, UN>), grid1, dim3(256), 0, st, static_cast<const T *>(logits_d), targets_d, \
-                       logit_lengths_d, target_lengths_d, B, Tmax, U1max, V, blank, w.K, w.S,                        \
-                       reinterpret_cast<float2 *>(ws + w.lp_off), reinterpret_cast<float *>(ws + w.denom_off), nullptr)
     const bool nt = (tune_get(kTuneNonTemporal) & 4) != 0;
-    if (dtype == WR_F32) { if (nt) { WR_LAUNCH_LSE(float, true); } else { WR_LAUNCH_LSE(float, false); } }
-    else if (dtype == WR_F16) { if (nt) { WR_LAUNCH_LSE(_Float16, true); } else { WR_LAUNCH_LSE(_Float16, false); } }
-    else { if (nt) { WR_LAUNCH_LSE(__bf16, true); } else { WR_LAUNCH_LSE(__bf16, false); } }
-#undef WR_LAUNCH_LSE
-#undef WR_LAUNCH_LSE_U
-    WR_CHECK_LAUNCH("rnnt_lse_kernel");
-    return WR_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return with_bool(nt, [&](auto nt_c) {
+            return with_int<16, 8, 4>(unroll_of(kTuneLseUnroll), [&](auto un) {
+                return launch("rnnt_lse_kernel", rnnt_lse_kernel<T, nt_c.value, un.value>, grid1,
+                              dim3(256), 0, st, static_cast<const T *>(logits_d), targets_d, logit_lengths_d,
+                              target_lengths_d, B, Tmax, U1max, V, blank, w.K, w.S,
+                              reinterpret_cast<float2 *>(ws + w.lp_off), reinterpret_cast<float *>(ws + w.denom_off),
+                              nullptr);
+            });
+        });
+    });
 }
 
 }  // namespace wr
@@ -549,12 +549,9 @@ extern "C" int wr_rnnt_loss_fwd(const void *logits_d, int dtype, const int32_t *
                workspace_bytes, w.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
     char *ws = static_cast<char *>(workspace_d);
-    if (int rc = rnnt_launch_lse(w, ws, logits_d, dtype, targets_d, logit_lengths_d, target_lengths_d, B, Tmax, U1max, V,
-                                 blank, st))
-        return rc;
-    rnnt_launch_sweep(w, ws, logit_lengths_d, target_lengths_d, B, Tmax, U1max, costs_d, st);
-    WR_CHECK_LAUNCH("rnnt_sweep_kernel");
-    return WR_OK;
+    WR_TRY(rnnt_launch_lse(w, ws, logits_d, dtype, targets_d, logit_lengths_d, target_lengths_d, B, Tmax, U1max, V, blank,
+                           st));
+    return rnnt_launch_sweep(w, ws, logit_lengths_d, target_lengths_d, B, Tmax, U1max, costs_d, st);
 }
 
 extern "C" int wr_rnnt_loss_fwd_from_lse(const float *logits_d, const int32_t *targets_d, const int32_t *logit_lengths_d,
@@ -573,14 +570,12 @@ extern "C" int wr_rnnt_loss_fwd_from_lse(const float *logits_d, const int32_t *t
     // repair pass: the stand-alone row statistics, executed only if the joiner's epilogue raised the flag (a partial
     // sum overflowed: more than 88 nats of spread inside one row); otherwise every workgroup leaves at once
     const long nrows = (long)B * Tmax * U1max;
-    hipLaunchKernelGGL((rnnt_lse_kernel<float, false, 8>), dim3(stream_grid(nrows, tune_get(kTuneLseBlocksPerCu), (size_t)V * 4, kLseBytesPerWave)), dim3(256), 0, st,
-                       logits_d, targets_d, logit_lengths_d, target_lengths_d, B, Tmax, U1max, V, blank, w.K, w.S,
-                       reinterpret_cast<float2 *>(ws + w.lp_off), reinterpret_cast<float *>(ws + w.denom_off),
-                       reinterpret_cast<const int32_t *>(ws + w.flag_off));
-    WR_CHECK_LAUNCH("rnnt_lse_kernel (repair)");
-    rnnt_launch_sweep(w, ws, logit_lengths_d, target_lengths_d, B, Tmax, U1max, costs_d, st);
-    WR_CHECK_LAUNCH("rnnt_sweep_kernel");
-    return WR_OK;
+    WR_TRY(launch("rnnt_lse_kernel (repair)", rnnt_lse_kernel<float, false, 8>,
+                  dim3(stream_grid(nrows, tune_get(kTuneLseBlocksPerCu), (size_t)V * 4, kLseBytesPerWave)), dim3(256), 0, st,
+                  logits_d, targets_d, logit_lengths_d, target_lengths_d, B, Tmax, U1max, V, blank, w.K, w.S,
+                  reinterpret_cast<float2 *>(ws + w.lp_off), reinterpret_cast<float *>(ws + w.denom_off),
+                  reinterpret_cast<const int32_t *>(ws + w.flag_off)));
+    return rnnt_launch_sweep(w, ws, logit_lengths_d, target_lengths_d, B, Tmax, U1max, costs_d, st);
 }
 
 extern "C" int wr_rnnt_loss_sweeps(const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax,
@@ -592,10 +587,8 @@ extern "C" int wr_rnnt_loss_sweeps(const int32_t *logit_lengths_d, const int32_t
     const RnntWs w = rnnt_ws_layout(B, Tmax, U1max);
     WR_REQUIRE(workspace_bytes >= w.total, WR_EWORKSPACE, "rnnt_loss_sweeps: workspace %zu < required %zu",
                workspace_bytes, w.total);
-    rnnt_launch_sweep(w, static_cast<char *>(workspace_d), logit_lengths_d, target_lengths_d, B, Tmax, U1max, costs_d,
-                      static_cast<hipStream_t>(stream));
-    WR_CHECK_LAUNCH("rnnt_sweep_kernel");
-    return WR_OK;
+    return rnnt_launch_sweep(w, static_cast<char *>(workspace_d), logit_lengths_d, target_lengths_d, B, Tmax, U1max, costs_d,
+                             static_cast<hipStream_t>(stream));
 }
 
 extern "C" int wr_rnnt_loss_bwd(const void *logits_d, int dtype, const int32_t *targets_d,
@@ -616,32 +609,26 @@ extern "C" int wr_rnnt_loss_bwd(const void *logits_d, int dtype, const int32_t *
     const long nrows = (long)B * Tmax * U1max;
     const size_t row_bytes = (size_t)V * (dtype == WR_F32 ? 4 : 2);
     const dim3 grid3(stream_grid(nrows, tune_get(kTuneGradBlocksPerCu), row_bytes, kGradBytesPerWave));
-#define WR_LAUNCH_GRAD_U(T, NT, UN)                                                                                 \
-    if (nts) WR_LAUNCH_GRAD_US(T, NT, true, UN); else WR_LAUNCH_GRAD_US(T, NT, false, UN)
-#define WR_LAUNCH_GRAD_US(T, NT, NTS, UN)                                                                           \
-    hipLaunchKernelGGL((rnnt_grad_kernel<T, NT, NTS, UN>), grid3, dim3(256), 0, st, static_cast<const T *>(logits_d), targets_d, \
-                       logit_lengths_d, target_lengths_d, B, Tmax, U1max, V, blank, clamp, w.K, w.S,                 \
-                       reinterpret_cast<const double *>(ws + w.alpha_off),                                           \
-                       reinterpret_cast<const double *>(ws + w.beta_off),                                            \
-                       reinterpret_cast<const float *>(ws + w.denom_off),                                            \
-                       reinterpret_cast<const double *>(ws + w.cost_off), grad_costs_d, static_cast<T *>(grads_d), skip)
-#define WR_LAUNCH_GRAD(T, NT)                                             \
-    do {                                                                   \
-        if (tune_get(kTuneGradUnroll) >= 16) { WR_LAUNCH_GRAD_U(T, NT, 16); } \
-        else if (tune_get(kTuneGradUnroll) >= 8) { WR_LAUNCH_GRAD_U(T, NT, 8); } \
-        else { WR_LAUNCH_GRAD_U(T, NT, 4); }                               \
-    } while (0)
     const bool nt = (tune_get(kTuneNonTemporal) & 1) != 0;
     const bool nts = (tune_get(kTuneNonTemporal) & 2) != 0;
     const int skip = tune_get(kTuneGradSkip) != 0 ? 1 : 0;
-    if (dtype == WR_F32) { if (nt) WR_LAUNCH_GRAD(float, true); else WR_LAUNCH_GRAD(float, false); }
-    else if (dtype == WR_F16) { if (nt) WR_LAUNCH_GRAD(_Float16, true); else WR_LAUNCH_GRAD(_Float16, false); }
-    else { if (nt) WR_LAUNCH_GRAD(__bf16, true); else WR_LAUNCH_GRAD(__bf16, false); }
-#undef WR_LAUNCH_GRAD
-#undef WR_LAUNCH_GRAD_U
-#undef WR_LAUNCH_GRAD_US
-    WR_CHECK_LAUNCH("rnnt_grad_kernel");
-    return WR_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return with_bool(nt, [&](auto nt_c) {
+            return with_int<16, 8, 4>(unroll_of(kTuneGradUnroll), [&](auto un) {
+                return with_bool(nts, [&](auto nts_c) {
+                    return launch("rnnt_grad_kernel", rnnt_grad_kernel<T, nt_c.value, nts_c.value, un.value>, grid3,
+                                  dim3(256), 0, st, static_cast<const T *>(logits_d), targets_d, logit_lengths_d,
+                                  target_lengths_d, B, Tmax, U1max, V, blank, clamp, w.K, w.S,
+                                  reinterpret_cast<const double *>(ws + w.alpha_off),
+                                  reinterpret_cast<const double *>(ws + w.beta_off),
+                                  reinterpret_cast<const float *>(ws + w.denom_off),
+                                  reinterpret_cast<const double *>(ws + w.cost_off), grad_costs_d,
+                                  static_cast<T *>(grads_d), skip);
+                });
+            });
+        });
+    });
 }
 
 extern "C" int wr_rnnt_export_lattice(const void *workspace_d, size_t workspace_bytes,
@@ -654,10 +641,7 @@ extern "C" int wr_rnnt_export_lattice(const void *workspace_d, size_t workspace_
     const RnntWs w = rnnt_ws_layout(B, Tmax, U1max);
     WR_REQUIRE(workspace_bytes >= w.total, WR_EWORKSPACE, "rnnt_export_lattice: workspace too small");
     const char *ws = static_cast<const char *>(workspace_d);
-    hipLaunchKernelGGL(rnnt_export_kernel, dim3(256), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       reinterpret_cast<const double *>(ws + w.alpha_off),
-                       reinterpret_cast<const double *>(ws + w.beta_off), logit_lengths_d, target_lengths_d, B, Tmax,
-                       U1max, w.K, w.S, alpha_d, beta_d);
-    WR_CHECK_LAUNCH("rnnt_export_kernel");
-    return WR_OK;
+    return launch("rnnt_export_kernel", rnnt_export_kernel, dim3(256), dim3(256), 0, static_cast<hipStream_t>(stream),
+                  reinterpret_cast<const double *>(ws + w.alpha_off), reinterpret_cast<const double *>(ws + w.beta_off),
+                  logit_lengths_d, target_lengths_d, B, Tmax, U1max, w.K, w.S, alpha_d, beta_d);
 }

@@ -16,6 +16,7 @@
 #include "rnnt_lattice.hpp"
 #include "row_stream.hpp"
 #include "wr_common.hpp"
+#include "wr_launch.hpp"
 
 namespace wr {
 namespace {
@@ -385,18 +386,6 @@ int check_loss(const char *what, int B, int T, int U1, int R, int V, int blank, 
     return WR_OK;
 }
 
-// grid of a streaming pass over `nrows` rows (4-wave workgroups): about `bytes_per_wave` of logits per wave, never
-// fewer workgroups than 12 per CU unless one row per wave needs fewer (the sizing rule of rnnt_loss.hip's stream_grid)
-int band_grid(long nrows, size_t row_bytes, size_t bytes_per_wave)
-{
-    const long all = (nrows + 3) / 4;
-    long blocks = (long)(((double)nrows * (double)row_bytes) / (4.0 * (double)bytes_per_wave)) + 1;
-    if (blocks > all) blocks = all;
-    const long floor_blocks = 256L * 12 < all ? 256L * 12 : all;
-    if (blocks < floor_blocks) blocks = floor_blocks;
-    return (int)(blocks < 1 ? 1 : blocks);
-}
-
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
@@ -414,11 +403,9 @@ static int prune_ranges_impl(const char *what, const float *px_grad_d, int px_co
     WR_REQUIRE(py_grad_d && logit_lengths_d && target_lengths_d && ranges_d, WR_EINVAL, "%s: null pointer argument", what);
     WR_REQUIRE(px_grad_d || U1 == 1, WR_EINVAL, "%s: px_grad is null", what);
     WR_REQUIRE(aligned16(ranges_d), WR_EINVAL, "%s: ranges must be 16-byte aligned", what);
-    hipLaunchKernelGGL(prune_ranges_kernel, dim3(B), dim3(kRangeThreads), 0, static_cast<hipStream_t>(stream), px_grad_d,
-                       py_grad_d, logit_lengths_d, target_lengths_d, T, U1, R, px_cols,
-                       reinterpret_cast<long long *>(ranges_d));
-    WR_CHECK_LAUNCH("prune_ranges_kernel");
-    return WR_OK;
+    return launch("prune_ranges_kernel", prune_ranges_kernel, dim3(B), dim3(kRangeThreads), 0,
+                  static_cast<hipStream_t>(stream), px_grad_d, py_grad_d, logit_lengths_d, target_lengths_d, T, U1, R, px_cols,
+                  reinterpret_cast<long long *>(ranges_d));
 }
 
 extern "C" int wr_rnnt_prune_ranges(const float *px_grad_d, const float *py_grad_d, const int32_t *logit_lengths_d,
@@ -452,16 +439,14 @@ extern "C" int wr_rnnt_prune_gather(const void *am_d, const void *lm_d, const in
     if (blocks > 256L * 32) blocks = 256L * 32;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long *rg = reinterpret_cast<const long long *>(ranges_d);
-    if (esize == 4)
-        hipLaunchKernelGGL((prune_gather_kernel<uint32_t>), dim3((unsigned)blocks), dim3(256), 0, st,
-                           static_cast<const uint32_t *>(am_d), static_cast<const uint32_t *>(lm_d), rg, nrows, T, U1, R, C, vec,
-                           static_cast<uint32_t *>(am_pruned_d), static_cast<uint32_t *>(lm_pruned_d));
-    else
-        hipLaunchKernelGGL((prune_gather_kernel<uint16_t>), dim3((unsigned)blocks), dim3(256), 0, st,
-                           static_cast<const uint16_t *>(am_d), static_cast<const uint16_t *>(lm_d), rg, nrows, T, U1, R, C, vec,
-                           static_cast<uint16_t *>(am_pruned_d), static_cast<uint16_t *>(lm_pruned_d));
-    WR_CHECK_LAUNCH("prune_gather_kernel");
-    return WR_OK;
+    const auto gather = [&](auto e) {             // the rows are copied as 4-byte or 2-byte words, whatever they hold
+        using E = decltype(e);
+        return launch("prune_gather_kernel", prune_gather_kernel<E>, dim3((unsigned)blocks), dim3(256), 0, st,
+                      static_cast<const E *>(am_d), static_cast<const E *>(lm_d), rg, nrows, T, U1, R, C, vec,
+                      static_cast<E *>(am_pruned_d), static_cast<E *>(lm_pruned_d));
+    };
+    if (esize == 4) return gather(uint32_t{});
+    return gather(uint16_t{});
 }
 
 extern "C" int wr_rnnt_prune_scatter(const void *g_am_pruned_d, const void *g_lm_pruned_d, const int64_t *ranges_d, int dtype,
@@ -482,25 +467,16 @@ extern "C" int wr_rnnt_prune_scatter(const void *g_am_pruned_d, const void *g_lm
     const long nwork = (long)B * U1 * cchunks;
     long blocks_lm = (nwork + 3) / 4;
     if (blocks_lm > 256L * 32) blocks_lm = 256L * 32;
-#define WR_LAUNCH_SCATTER(T_)                                                                                          \
-    do {                                                                                                               \
-        if (d_am_d) {                                                                                                  \
-            hipLaunchKernelGGL((prune_sum_r_kernel<T_>), dim3((unsigned)blocks_am), dim3(256), 0, st,                  \
-                               static_cast<const T_ *>(g_am_pruned_d), n_am, R, C, static_cast<T_ *>(d_am_d));         \
-            WR_CHECK_LAUNCH("prune_sum_r_kernel");                                                                     \
-        }                                                                                                              \
-        if (d_lm_d) {                                                                                                  \
-            hipLaunchKernelGGL((prune_scatter_kernel<T_>), dim3((unsigned)blocks_lm), dim3(256), 0, st,                \
-                               static_cast<const T_ *>(g_lm_pruned_d), rg, nwork, T, U1, R, C, cchunks,                \
-                               static_cast<T_ *>(d_lm_d));                                                             \
-            WR_CHECK_LAUNCH("prune_scatter_kernel");                                                                   \
-        }                                                                                                              \
-    } while (0)
-    if (dtype == WR_F32) WR_LAUNCH_SCATTER(float);
-    else if (dtype == WR_F16) WR_LAUNCH_SCATTER(_Float16);
-    else WR_LAUNCH_SCATTER(__bf16);
-#undef WR_LAUNCH_SCATTER
-    return WR_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using E = decltype(t);
+        if (d_am_d)
+            WR_TRY(launch("prune_sum_r_kernel", prune_sum_r_kernel<E>, dim3((unsigned)blocks_am), dim3(256), 0, st,
+                          static_cast<const E *>(g_am_pruned_d), n_am, R, C, static_cast<E *>(d_am_d)));
+        if (d_lm_d)
+            WR_TRY(launch("prune_scatter_kernel", prune_scatter_kernel<E>, dim3((unsigned)blocks_lm), dim3(256), 0, st,
+                          static_cast<const E *>(g_lm_pruned_d), rg, nwork, T, U1, R, C, cchunks, static_cast<E *>(d_lm_d)));
+        return (int)WR_OK;
+    });
 }
 
 extern "C" int wr_rnnt_pruned_stats(const void *logits_d, int dtype, const int32_t *symbols_d, const int64_t *ranges_d,
@@ -522,21 +498,19 @@ extern "C" int wr_rnnt_pruned_stats(const void *logits_d, int dtype, const int32
     size_t fill_blocks = (ncell / 2 + 255) / 256;
     if (fill_blocks > 256 * 8) fill_blocks = 256 * 8;
     if (fill_blocks < 1) fill_blocks = 1;
-    hipLaunchKernelGGL(pruned_fill_kernel, dim3((unsigned)fill_blocks), dim3(256), 0, st, lp, ncell);
-    WR_CHECK_LAUNCH("pruned_fill_kernel");
+    WR_TRY(launch("pruned_fill_kernel", pruned_fill_kernel, dim3((unsigned)fill_blocks), dim3(256), 0, st, lp, ncell));
     const long nrows = (long)B * T * R;
     const size_t row_bytes = (size_t)V * (dtype == WR_F32 ? 4 : 2);
-    const dim3 grid(band_grid(nrows, row_bytes, 16 * 1024));
-#define WR_LAUNCH_PLSE(T_)                                                                                             \
-    hipLaunchKernelGGL((pruned_lse_kernel<T_, true, 16>), grid, dim3(256), 0, st, static_cast<const T_ *>(logits_d),    \
-                       symbols_d, reinterpret_cast<const long long *>(ranges_d), logit_lengths_d, target_lengths_d,    \
-                       nrows, T, U1, R, V, blank, w.S, lp, reinterpret_cast<float *>(ws + w.denom_off))
-    if (dtype == WR_F32) WR_LAUNCH_PLSE(float);
-    else if (dtype == WR_F16) WR_LAUNCH_PLSE(_Float16);
-    else WR_LAUNCH_PLSE(__bf16);
-#undef WR_LAUNCH_PLSE
-    WR_CHECK_LAUNCH("pruned_lse_kernel");
-    return WR_OK;
+    // the automatic sizing of the full-lattice passes (no tuning key): about 16 KB of band logits per wave here, 68 KB in
+    // the gradient pass
+    const dim3 grid(stream_grid(nrows, 0, row_bytes, 16 * 1024));
+    return with_dtype(dtype, [&](auto t) {
+        using E = decltype(t);
+        return launch("pruned_lse_kernel", pruned_lse_kernel<E, true, 16>, grid, dim3(256), 0, st,
+                      static_cast<const E *>(logits_d), symbols_d, reinterpret_cast<const long long *>(ranges_d),
+                      logit_lengths_d, target_lengths_d, nrows, T, U1, R, V, blank, w.S, lp,
+                      reinterpret_cast<float *>(ws + w.denom_off));
+    });
 }
 
 // wr_rnnt_pruned_grad (lat = kLatRegular) and wr_rnnt_pruned_grad_lattice
@@ -559,27 +533,19 @@ static int pruned_grad_impl(const char *what, const void *logits_d, int dtype, c
     const char *ws = static_cast<const char *>(rnnt_workspace_d);
     const long nrows = (long)B * T * R;
     const size_t row_bytes = (size_t)V * (dtype == WR_F32 ? 4 : 2);
-    const dim3 grid(band_grid(nrows, row_bytes, 68 * 1024));
+    const dim3 grid(stream_grid(nrows, 0, row_bytes, 68 * 1024));
     const LatView lv = lattice_view(w, ws, lat == kLatModified);
-#define WR_LAUNCH_PGRAD_L(T_, LAT)                                                                                     \
-    hipLaunchKernelGGL((pruned_grad_kernel<T_, true, true, 16, LAT>), grid, dim3(256), 0, st,                           \
-                       static_cast<const T_ *>(logits_d), symbols_d, reinterpret_cast<const long long *>(ranges_d),    \
-                       logit_lengths_d, target_lengths_d, nrows, T, U1, R, V, blank, w.S, lv.alpha, lv.beta,           \
-                       reinterpret_cast<const float *>(ws + w.denom_off), reinterpret_cast<const double *>(ws + w.cost_off), \
-                       grad_costs_d, static_cast<T_ *>(grads_d), delay_penalty)
-#define WR_LAUNCH_PGRAD(T_)                                                                                            \
-    do {                                                                                                               \
-        if (lat == kLatModified) WR_LAUNCH_PGRAD_L(T_, kLatModified);                                                  \
-        else if (lat == kLatRegularPen) WR_LAUNCH_PGRAD_L(T_, kLatRegularPen);                                         \
-        else WR_LAUNCH_PGRAD_L(T_, kLatRegular);                                                                       \
-    } while (0)
-    if (dtype == WR_F32) WR_LAUNCH_PGRAD(float);
-    else if (dtype == WR_F16) WR_LAUNCH_PGRAD(_Float16);
-    else WR_LAUNCH_PGRAD(__bf16);
-#undef WR_LAUNCH_PGRAD
-#undef WR_LAUNCH_PGRAD_L
-    WR_CHECK_LAUNCH("pruned_grad_kernel");
-    return WR_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using E = decltype(t);
+        return with_int<kLatModified, kLatRegularPen, kLatRegular>(lat, [&](auto lat_c) {
+            return launch("pruned_grad_kernel", pruned_grad_kernel<E, true, true, 16, lat_c.value>, grid, dim3(256), 0, st,
+                          static_cast<const E *>(logits_d), symbols_d, reinterpret_cast<const long long *>(ranges_d),
+                          logit_lengths_d, target_lengths_d, nrows, T, U1, R, V, blank, w.S, lv.alpha, lv.beta,
+                          reinterpret_cast<const float *>(ws + w.denom_off),
+                          reinterpret_cast<const double *>(ws + w.cost_off), grad_costs_d, static_cast<E *>(grads_d),
+                          delay_penalty);
+        });
+    });
 }
 
 extern "C" int wr_rnnt_pruned_grad(const void *logits_d, int dtype, const int32_t *symbols_d, const int64_t *ranges_d,

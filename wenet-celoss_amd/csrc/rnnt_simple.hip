@@ -35,6 +35,7 @@
 #include "rnnt_lattice.hpp"
 #include "row_stream.hpp"
 #include "wr_common.hpp"
+#include "wr_launch.hpp"
 
 namespace wr {
 namespace {
@@ -816,19 +817,15 @@ int simple_stats_launch(const float *am_d, const float *lm_d, const int32_t *sym
     int32_t *flag = reinterpret_cast<int32_t *>(ws + w.flag_off);
 
     const long rows_am = (long)B * T, rows_lm = (long)B * U1;
-    hipLaunchKernelGGL(simple_rowmax_kernel, dim3((unsigned)((rows_am + rows_lm + 3) / 4)), dim3(256), 0, st, am_d, lm_d,
-                       rows_am, rows_lm, V, ma, ml, flag);
-    WR_CHECK_LAUNCH("simple_rowmax_kernel");
-    hipLaunchKernelGGL(simple_stats_kernel, dim3((U1 + kTile - 1) / kTile, (T + kTile - 1) / kTile, B), dim3(256), 0, st,
-                       am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, T, U1, V, blank, w.S, ma, ml, lp, denom,
-                       flag);
-    WR_CHECK_LAUNCH("simple_stats_kernel");
+    WR_TRY(launch("simple_rowmax_kernel", simple_rowmax_kernel, dim3((unsigned)((rows_am + rows_lm + 3) / 4)), dim3(256), 0,
+                  st, am_d, lm_d, rows_am, rows_lm, V, ma, ml, flag));
+    WR_TRY(launch("simple_stats_kernel", simple_stats_kernel, dim3((U1 + kTile - 1) / kTile, (T + kTile - 1) / kTile, B),
+                  dim3(256), 0, st, am_d, lm_d, symbols_d, logit_lengths_d, target_lengths_d, T, U1, V, blank, w.S, ma, ml,
+                  lp, denom, flag));
     long blocks = ((long)B * T * U1 + 3) / 4;
     if (blocks > 256L * 16) blocks = 256L * 16;
-    hipLaunchKernelGGL(simple_stats_direct_kernel, dim3((unsigned)blocks), dim3(256), 0, st, am_d, lm_d, symbols_d,
-                       logit_lengths_d, target_lengths_d, B, T, U1, V, blank, w.S, lp, denom, flag);
-    WR_CHECK_LAUNCH("simple_stats_direct_kernel");
-    return WR_OK;
+    return launch("simple_stats_direct_kernel", simple_stats_direct_kernel, dim3((unsigned)blocks), dim3(256), 0, st, am_d,
+                  lm_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, w.S, lp, denom, flag);
 }
 
 // The occupancies (always) and, unless `occ_only`, the kernels of wr_rnnt_simple_grad up to the contractions: G scaled by
@@ -848,33 +845,27 @@ int simple_grad_launch(const float *am_d, const float *lm_d, const int32_t *symb
     const long cells = (long)B * T * U1;
 
     const LatView lv = lattice_view(w, ws, modified);
-#define WR_LAUNCH_OCC(LAT)                                                                                             \
-    hipLaunchKernelGGL((simple_occ_kernel<LAT>), dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, logit_lengths_d, \
-                       target_lengths_d, B, T, U1, w.S, lv.alpha, lv.beta, lv.lp, denom,                               \
-                       reinterpret_cast<const double *>(ws + w.cost_off), ma, ml, grad_costs_d, flag, gscale, g, gt, ob, oe, \
-                       occ_emit_d, occ_blank_d)
-    if (modified) WR_LAUNCH_OCC(kLatModified);
-    else WR_LAUNCH_OCC(kLatRegular);
-#undef WR_LAUNCH_OCC
-    WR_CHECK_LAUNCH("simple_occ_kernel");
+    // (the modified arm first: the order of the arms is the order of the kernels in the code object)
+    WR_TRY(with_bool(modified, [&](auto mod) {
+        constexpr int LAT = mod.value ? kLatModified : kLatRegular;
+        return launch("simple_occ_kernel", simple_occ_kernel<LAT>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st,
+                      logit_lengths_d, target_lengths_d, B, T, U1, w.S, lv.alpha, lv.beta, lv.lp, denom,
+                      reinterpret_cast<const double *>(ws + w.cost_off), ma, ml, grad_costs_d, flag, gscale, g, gt, ob, oe,
+                      occ_emit_d, occ_blank_d);
+    }));
     if (occ_only) return WR_OK;
-    hipLaunchKernelGGL(simple_chain_kernel, dim3(B), dim3(256), 0, st, symbols_d, target_lengths_d, U1, nxt, head);
-    WR_CHECK_LAUNCH("simple_chain_kernel");
+    WR_TRY(launch("simple_chain_kernel", simple_chain_kernel, dim3(B), dim3(256), 0, st, symbols_d, target_lengths_d, U1,
+                  nxt, head));
 
     const unsigned vg = (unsigned)((V + kGemmCols - 1) / kGemmCols), vd = (unsigned)((V + 255) / 256);
-    hipLaunchKernelGGL((simple_grad_gemm_kernel<true>), dim3(vg, (T + kTile - 1) / kTile, B), dim3(256), 0, st, gt, am_d, ma,
-                       lm_d, ml, logit_lengths_d, target_lengths_d, T, U1, V, flag, d_am_d);
-    WR_CHECK_LAUNCH("simple_grad_gemm_kernel<am>");
-    hipLaunchKernelGGL((simple_grad_gemm_kernel<false>), dim3(vg, (U1 + kTile - 1) / kTile, B), dim3(256), 0, st, g, lm_d, ml,
-                       am_d, ma, logit_lengths_d, target_lengths_d, T, U1, V, flag, d_lm_d);
-    WR_CHECK_LAUNCH("simple_grad_gemm_kernel<lm>");
-    hipLaunchKernelGGL((simple_grad_direct_kernel<true>), dim3(vd, T < 64 ? T : 64, B), dim3(256), 0, st, g, denom, am_d, lm_d,
-                       logit_lengths_d, target_lengths_d, T, U1, V, flag, d_am_d);
-    WR_CHECK_LAUNCH("simple_grad_direct_kernel<am>");
-    hipLaunchKernelGGL((simple_grad_direct_kernel<false>), dim3(vd, U1 < 64 ? U1 : 64, B), dim3(256), 0, st, g, denom, lm_d, am_d,
-                       logit_lengths_d, target_lengths_d, T, U1, V, flag, d_lm_d);
-    WR_CHECK_LAUNCH("simple_grad_direct_kernel<lm>");
-    return WR_OK;
+    WR_TRY(launch("simple_grad_gemm_kernel<am>", simple_grad_gemm_kernel<true>, dim3(vg, (T + kTile - 1) / kTile, B),
+                  dim3(256), 0, st, gt, am_d, ma, lm_d, ml, logit_lengths_d, target_lengths_d, T, U1, V, flag, d_am_d));
+    WR_TRY(launch("simple_grad_gemm_kernel<lm>", simple_grad_gemm_kernel<false>, dim3(vg, (U1 + kTile - 1) / kTile, B),
+                  dim3(256), 0, st, g, lm_d, ml, am_d, ma, logit_lengths_d, target_lengths_d, T, U1, V, flag, d_lm_d));
+    WR_TRY(launch("simple_grad_direct_kernel<am>", simple_grad_direct_kernel<true>, dim3(vd, T < 64 ? T : 64, B), dim3(256),
+                  0, st, g, denom, am_d, lm_d, logit_lengths_d, target_lengths_d, T, U1, V, flag, d_am_d));
+    return launch("simple_grad_direct_kernel<lm>", simple_grad_direct_kernel<false>, dim3(vd, U1 < 64 ? U1 : 64, B),
+                  dim3(256), 0, st, g, denom, lm_d, am_d, logit_lengths_d, target_lengths_d, T, U1, V, flag, d_lm_d);
 }
 
 int simple_fix_launch(const int32_t *symbols_d, const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B,
@@ -884,13 +875,11 @@ int simple_fix_launch(const int32_t *symbols_d, const int32_t *logit_lengths_d, 
     const float *ob = reinterpret_cast<const float *>(sws + sw.ob_off), *oe = reinterpret_cast<const float *>(sws + sw.oe_off);
     const int32_t *nxt = reinterpret_cast<const int32_t *>(sws + sw.nxt_off);
     const int32_t *head = reinterpret_cast<const int32_t *>(sws + sw.head_off);
-    hipLaunchKernelGGL(simple_fix_am_kernel, dim3((unsigned)(((long)B * T + 3) / 4)), dim3(256), 0, st, ob, oe, nxt, head,
-                       symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, w_am, every_arc, d_am_d);
-    WR_CHECK_LAUNCH("simple_fix_am_kernel");
-    hipLaunchKernelGGL(simple_fix_lm_kernel, dim3((U1 + 63) / 64, B), dim3(256), 0, st, ob, oe, symbols_d, logit_lengths_d,
-                       target_lengths_d, T, U1, V, blank, w_lm, every_arc, d_lm_d);
-    WR_CHECK_LAUNCH("simple_fix_lm_kernel");
-    return WR_OK;
+    WR_TRY(launch("simple_fix_am_kernel", simple_fix_am_kernel, dim3((unsigned)(((long)B * T + 3) / 4)), dim3(256), 0, st,
+                  ob, oe, nxt, head, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, w_am, every_arc,
+                  d_am_d));
+    return launch("simple_fix_lm_kernel", simple_fix_lm_kernel, dim3((U1 + 63) / 64, B), dim3(256), 0, st, ob, oe,
+                  symbols_d, logit_lengths_d, target_lengths_d, T, U1, V, blank, w_lm, every_arc, d_lm_d);
 }
 
 int smooth_check(const char *what, float ll, float la, int V)
@@ -958,27 +947,23 @@ static int smoothed_stats_impl(const char *what, const float *am_d, const float 
     const unsigned vb = (unsigned)((V + 255) / 256);
     const float c = (float)(1.0 - (double)ll - (double)la);
 
-    hipLaunchKernelGGL(smooth_lm_rows_kernel, dim3((unsigned)((rows_lm + 3) / 4)), dim3(256), 0, st, lm_d, ml, symbols_d,
-                       target_lengths_d, rows_lm, U1, V, blank, zl, lb, le);
-    WR_CHECK_LAUNCH("smooth_lm_rows_kernel");
+    WR_TRY(launch("smooth_lm_rows_kernel", smooth_lm_rows_kernel, dim3((unsigned)((rows_lm + 3) / 4)), dim3(256), 0, st,
+                  lm_d, ml, symbols_d, target_lengths_d, rows_lm, U1, V, blank, zl, lb, le));
     if (la != 0.f) {
-        hipLaunchKernelGGL(smooth_colsum_kernel, dim3(mw.lm_chunks, vb), dim3(256), 0, st, lm_d, zl, rows_lm, V, part);
-        WR_CHECK_LAUNCH("smooth_colsum_kernel");
-        hipLaunchKernelGGL(smooth_pbar_kernel, dim3(vb), dim3(256), 0, st, part, mw.lm_chunks, rows_lm, V, pbar, lpbar);
-        WR_CHECK_LAUNCH("smooth_pbar_kernel");
-        hipLaunchKernelGGL(smooth_am_norm_kernel, dim3((unsigned)((rows_am + 3) / 4)), dim3(256), 0, st, am_d, ma, pbar,
-                           lpbar, logit_lengths_d, B, T, V, blank, nrm, ab);
-        WR_CHECK_LAUNCH("smooth_am_norm_kernel");
-        hipLaunchKernelGGL((smooth_interp_kernel<true>), dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, am_d,
-                           symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, w.S, c, ll, la, lb, le, nrm, ab,
-                           lpbar, reinterpret_cast<float2 *>(ws + w.lp_off));
-        WR_CHECK_LAUNCH("smooth_interp_kernel<am>");
+        WR_TRY(launch("smooth_colsum_kernel", smooth_colsum_kernel, dim3(mw.lm_chunks, vb), dim3(256), 0, st, lm_d, zl,
+                      rows_lm, V, part));
+        WR_TRY(launch("smooth_pbar_kernel", smooth_pbar_kernel, dim3(vb), dim3(256), 0, st, part, mw.lm_chunks, rows_lm, V,
+                      pbar, lpbar));
+        WR_TRY(launch("smooth_am_norm_kernel", smooth_am_norm_kernel, dim3((unsigned)((rows_am + 3) / 4)), dim3(256), 0, st,
+                      am_d, ma, pbar, lpbar, logit_lengths_d, B, T, V, blank, nrm, ab));
+        WR_TRY(launch("smooth_interp_kernel<am>", smooth_interp_kernel<true>, dim3((unsigned)((cells + 255) / 256)),
+                      dim3(256), 0, st, am_d, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, w.S, c, ll, la, lb,
+                      le, nrm, ab, lpbar, reinterpret_cast<float2 *>(ws + w.lp_off)));
     } else {
-        hipLaunchKernelGGL((smooth_interp_kernel<false>), dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st,
-                           (const float *)nullptr, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, w.S, c, ll, la,
-                           lb, le, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr,
-                           reinterpret_cast<float2 *>(ws + w.lp_off));
-        WR_CHECK_LAUNCH("smooth_interp_kernel<lm>");
+        WR_TRY(launch("smooth_interp_kernel<lm>", smooth_interp_kernel<false>, dim3((unsigned)((cells + 255) / 256)),
+                      dim3(256), 0, st, (const float *)nullptr, symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V,
+                      w.S, c, ll, la, lb, le, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr,
+                      reinterpret_cast<float2 *>(ws + w.lp_off)));
     }
     return WR_OK;
 }
@@ -1028,29 +1013,23 @@ static int smoothed_grad_impl(const char *what, bool need_grads, const float *am
         float *part = reinterpret_cast<float *>(sws + mw.part_off);
         const long rows_lm = (long)B * U1, rows_am = (long)B * T;
         const unsigned vb = (unsigned)((V + 255) / 256);
-        hipLaunchKernelGGL(smooth_occ_cols_kernel, dim3((U1 + 63) / 64, B), dim3(64 * kOccPhases), 0, st, ob, oe, T, U1, rb, re);
-        WR_CHECK_LAUNCH("smooth_occ_cols_kernel");
+        WR_TRY(launch("smooth_occ_cols_kernel", smooth_occ_cols_kernel, dim3((U1 + 63) / 64, B), dim3(64 * kOccPhases), 0,
+                      st, ob, oe, T, U1, rb, re));
         if (la != 0.f) {
-            hipLaunchKernelGGL(smooth_occ_rows_kernel, dim3((unsigned)((rows_am + 3) / 4)), dim3(256), 0, st, ob, oe, rows_am,
-                               U1, cg);
-            WR_CHECK_LAUNCH("smooth_occ_rows_kernel");
-            hipLaunchKernelGGL(smooth_h_part_kernel, dim3(vb, mw.t_chunks, B), dim3(256), 0, st, am_d, nrm, cg, rb, re, lpbar,
-                               symbols_d, logit_lengths_d, target_lengths_d, T, U1, V, blank, part);
-            WR_CHECK_LAUNCH("smooth_h_part_kernel");
-            hipLaunchKernelGGL(smooth_h_kernel, dim3(vb), dim3(256), 0, st, part, B * mw.t_chunks, V, la, h);
-            WR_CHECK_LAUNCH("smooth_h_kernel");
-            hipLaunchKernelGGL(smooth_am_row_kernel, dim3((unsigned)((rows_am + 3) / 4)), dim3(256), 0, st, am_d, nrm, cg,
-                               lpbar, logit_lengths_d, B, T, V, la, d_am_d);
-            WR_CHECK_LAUNCH("smooth_am_row_kernel");
-            hipLaunchKernelGGL((smooth_lm_row_kernel<true>), dim3((unsigned)((rows_lm + 3) / 4)), dim3(256), 0, st, lm_d, zl,
-                               rb, re, h, pbar, logit_lengths_d, target_lengths_d, rows_lm, T, U1, V, ll, 1.f / (float)rows_lm,
-                               d_lm_d);
-            WR_CHECK_LAUNCH("smooth_lm_row_kernel<unigram>");
+            WR_TRY(launch("smooth_occ_rows_kernel", smooth_occ_rows_kernel, dim3((unsigned)((rows_am + 3) / 4)), dim3(256),
+                          0, st, ob, oe, rows_am, U1, cg));
+            WR_TRY(launch("smooth_h_part_kernel", smooth_h_part_kernel, dim3(vb, mw.t_chunks, B), dim3(256), 0, st, am_d,
+                          nrm, cg, rb, re, lpbar, symbols_d, logit_lengths_d, target_lengths_d, T, U1, V, blank, part));
+            WR_TRY(launch("smooth_h_kernel", smooth_h_kernel, dim3(vb), dim3(256), 0, st, part, B * mw.t_chunks, V, la, h));
+            WR_TRY(launch("smooth_am_row_kernel", smooth_am_row_kernel, dim3((unsigned)((rows_am + 3) / 4)), dim3(256), 0,
+                          st, am_d, nrm, cg, lpbar, logit_lengths_d, B, T, V, la, d_am_d));
+            WR_TRY(launch("smooth_lm_row_kernel<unigram>", smooth_lm_row_kernel<true>, dim3((unsigned)((rows_lm + 3) / 4)),
+                          dim3(256), 0, st, lm_d, zl, rb, re, h, pbar, logit_lengths_d, target_lengths_d, rows_lm, T, U1, V,
+                          ll, 1.f / (float)rows_lm, d_lm_d));
         } else {
-            hipLaunchKernelGGL((smooth_lm_row_kernel<false>), dim3((unsigned)((rows_lm + 3) / 4)), dim3(256), 0, st, lm_d, zl,
-                               rb, re, (const float *)nullptr, (const float *)nullptr, logit_lengths_d, target_lengths_d, rows_lm, T, U1, V, ll, 0.f,
-                               d_lm_d);
-            WR_CHECK_LAUNCH("smooth_lm_row_kernel<rows>");
+            WR_TRY(launch("smooth_lm_row_kernel<rows>", smooth_lm_row_kernel<false>, dim3((unsigned)((rows_lm + 3) / 4)),
+                          dim3(256), 0, st, lm_d, zl, rb, re, (const float *)nullptr, (const float *)nullptr,
+                          logit_lengths_d, target_lengths_d, rows_lm, T, U1, V, ll, 0.f, d_lm_d));
         }
     }
     return simple_fix_launch(symbols_d, logit_lengths_d, target_lengths_d, B, T, U1, V, blank, d_am_d, d_lm_d, mw.s, sws,

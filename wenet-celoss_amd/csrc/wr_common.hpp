@@ -38,6 +38,20 @@ void set_error(const char *fmt, ...);
         }                                                                           \
     } while (0)
 
+// pass a callee's error on: `WR_TRY(launch(...));` inside a function that goes on after a success
+#define WR_TRY(...)                              \
+    do {                                         \
+        if (int rc_ = (__VA_ARGS__)) return rc_; \
+    } while (0)
+
+// the valid-length arrays of a joiner entry point `what` are optional, but only together
+inline int check_length_pair(const char *what, const void *logit_lengths_d, const void *target_lengths_d)
+{
+    WR_REQUIRE((logit_lengths_d == nullptr) == (target_lengths_d == nullptr), WR_EINVAL,
+               "%s: pass both length arrays or neither", what);
+    return WR_OK;
+}
+
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // ---- process-wide tuning knobs (wr_tune_set; defaults are the measured best) ----
@@ -84,12 +98,15 @@ inline RnntWs rnnt_ws_layout(int B, int Tmax, int U1max)
 }
 
 // rnnt_loss.hip: lattice sweeps over a workspace whose row statistics (denom, skip/emit log-probs) are in place
-void rnnt_launch_sweep(const RnntWs &w, char *ws, const int32_t *llens, const int32_t *tlens, int B, int Tmax, int U1max,
-                       float *costs, hipStream_t st);
+int rnnt_launch_sweep(const RnntWs &w, char *ws, const int32_t *llens, const int32_t *tlens, int B, int Tmax, int U1max,
+                      float *costs, hipStream_t st);
 // rnnt_loss.hip: pass 1 (row log-sum-exp, skip / emit log-probs into the skewed array) over a logits tensor of `dtype`
 int rnnt_launch_lse(const RnntWs &w, char *ws, const void *logits_d, int dtype, const int32_t *targets_d,
                     const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V,
                     int blank, hipStream_t st);
+
+// rnnt_loss.hip: workgroups of a streaming pass over `nrows` rows of `row_bytes` (the history is with the definition)
+int stream_grid(long nrows, int knob, size_t row_bytes, size_t bytes_per_wave);
 
 // ---- device helpers ---------------------------------------------------------
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
