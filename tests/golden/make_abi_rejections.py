@@ -1,4 +1,4 @@
-"""Record what the loss and joiner entry points answer to bad arguments: tests/golden/abi_rejections.json.
+"""Record what the entry points of the library answer to bad arguments: tests/golden/abi_rejections.json.
 
     python tests/golden/make_abi_rejections.py            # rewrites the table from the library as built
 
@@ -9,8 +9,12 @@ and the launches keeps codes, texts and the order of the checks.  Run it on the 
 Arguments are written by parameter name (include/wr_api.h) over a base call per entry point: small positive sizes,
 every pointer a never-dereferenced placeholder, every workspace size 0.  The base call itself is rejected (its
 workspace is too small, or, where an entry point takes no workspace, a row overrides an argument that is checked).
-Pointers are encoded as "null", "ptr" (16-byte aligned placeholder) or "ptr+8".  A row that comes back WR_OK or
-WR_ELAUNCH reached a launch: the generator refuses to write the table.
+Pointers are encoded as "null", "ptr" (16-byte aligned placeholder) or "ptr+8"; the one pointer that is read, the
+decoder's weight description, as {"weights": {field: value}} over WEIGHTS_BASE (every weight pointer a placeholder).  A
+row that comes back WR_OK or WR_ELAUNCH reached a launch: the generator refuses to write the table.
+
+The size queries of the decoder answer a bad argument with 0 and set no error text: SIZE_ZERO lists those calls, the
+generator checks them and tests/test_abi.py repeats them; they are not rows of the table.
 """
 import ctypes
 import json
@@ -52,10 +56,35 @@ def prototypes():
 
 # base value of an integer / float parameter, by name (every other integer is 0, every float 0.0)
 BASE = {"B": 2, "T": 4, "Tmax": 4, "U1": 3, "U1max": 3, "Smax": 2, "V": 8, "J": 8, "R": 2, "C": 4, "terms": 3, "h_ld": 8,
-        "px_cols": 5, "cell_end": 1, "clamp": -1.0}
+        "px_cols": 5, "cell_end": 1, "clamp": -1.0,
+        "max_lanes": 4, "max_utt": 2, "max_hyp": 8, "max_beam": 2, "beam": 2, "N": 2, "n_steps": 1, "trace_cap": 4,
+        "max_ctx": 2, "n_ctx_hot": 1, "n_ctx_cold": 1}
+
+# wr_transducer_weights of the smallest LSTM decoder; a pointer field is "ptr" unless a row says "null"
+WEIGHTS_BASE = {"vocab_size": 32, "enc_dim": 16, "pred_dim": 16, "embed_dim": 16, "hidden": 16, "n_layers": 1, "join_dim": 32}
+_keep = []              # the weight structs of decoded calls stay alive
+
+
+def weights_struct(over):
+    from wenet_celoss_amd import _lib
+    w = _lib.TransducerWeights()
+    vals = dict(WEIGHTS_BASE, **over)
+    assert not set(vals) - {n for n, _ in w._fields_}, vals
+    for name, ctype in w._fields_:
+        v = vals.get(name)
+        if ctype is ctypes.c_void_p:
+            setattr(w, name, None if v == "null" else PLACEHOLDER)
+        elif issubclass(ctype, ctypes.Array):
+            setattr(w, name, ctype(*([None if v == "null" else PLACEHOLDER] * len(ctype()))))
+        elif v is not None:
+            setattr(w, name, v)
+    _keep.append(w)
+    return ctypes.byref(w)
 
 
 def decode(kind, v):
+    if isinstance(v, dict):
+        return weights_struct(v["weights"])
     if kind == "ptr":
         return None if v == "null" else ctypes.c_void_p(PLACEHOLDER + (8 if v == "ptr+8" else 0))
     return v
@@ -320,6 +349,121 @@ def joint_family():
     row(fn, "activation copy", h_ld=10)
 
 
+def W(**over):
+    return {"weights": over}
+
+
+STATELESS = dict(predictor_type=1, context_size=2, n_layers=1, n_head=2, ln_eps=1e-5)
+
+
+def decoder_family():
+    fn = "wr_decoder_create"
+
+    def create(what, w=None, **over):
+        row(fn, what, w=W() if w is None else w, **over)
+    create("weights null", w=NULLS)
+    create("weight sizes", W(vocab_size=1))
+    create("weight sizes", W(join_dim=0))
+    create("layer count", W(n_layers=0))
+    create("layer count", W(n_layers=5))
+    create("activation code", W(activation=6))
+    create("layer width", W(hidden=1025))
+    create("vocabulary limit", W(vocab_size=16385))
+    create("null weight", W(embed=NULLS))
+    create("null weight", W(out_b=NULLS))
+    create("predictor type", W(predictor_type=3))
+    create("predictor type", W(predictor_type=-1))
+    create("null weight", W(proj_w=NULLS))                    # LSTM
+    create("null weight", W(w_hh=NULLS))
+    create("null weight", W(n_layers=2, b_ih=NULLS))
+    for t in (1, 2):                                          # embedding / conv: the checks the stateless predictors share
+        sl = dict(STATELESS, predictor_type=t)
+        create("context size", W(**dict(sl, context_size=1)))
+        create("context size", W(**dict(sl, context_size=6, n_layers=4)))
+        create("context size", W(**dict(sl, context_size=3)))
+        create("stateless widths", W(**dict(sl, hidden=32)))
+        create("stateless widths", W(**dict(sl, pred_dim=8)))
+        create("activation code", W(**dict(sl, pred_activation=6)))
+        create("layer norm", W(**dict(sl, ln_eps=0.0)))
+        create("layer norm", W(**dict(sl, norm_b=NULLS)))
+        create("workspace size", W(**sl))
+    emb = dict(STATELESS, predictor_type=1)
+    create("head count", W(**dict(emb, n_head=0)))
+    create("head count", W(**dict(emb, n_head=33)))
+    create("null weight", W(**dict(emb, ffn_w=NULLS)))
+    create("null weight", W(**dict(STATELESS, predictor_type=2, conv_w=NULLS)))
+    create("null pointer", out=NULLS)
+    create("null pointer", workspace_d=NULLS)
+    create("lanes", max_lanes=0)
+    create("lanes", max_lanes=1025)
+    create("sizes", max_utt=0)
+    create("sizes", max_utt=5)
+    create("sizes", Tmax=0)
+    create("sizes", max_hyp=-1)
+    create("beam", max_beam=17)
+    create("workspace size")
+    create("workspace size", max_beam=0, workspace_bytes=4096)
+    # everything else a decoder offers needs a handle: the null handle is what can be rejected without one
+    for fn in ("wr_decoder_set_graph", "wr_decoder_set_lookahead", "wr_greedy_search", "wr_greedy_search_chunk",
+               "wr_prefix_beam_search", "wr_predictor_step", "wr_decoder_attach_hotword", "wr_greedy_search_hotword"):
+        row(fn, "null handle", h=NULLS)
+    row("wr_decoder_attach_hotword", "null handle", h=NULLS, hw=NULLS)
+
+
+def ctc_decode_family():
+    for fn in ("wr_ctc_greedy_search", "wr_ctc_prefix_beam_search"):
+        row(fn, "sizes", B=0)
+        row(fn, "sizes", T=-1)
+        row(fn, "sizes", V=1)
+        row(fn, "blank range", blank=8)
+        row(fn, "blank range", blank=-1)
+        row(fn, "vocabulary limit", V=16321)
+        row(fn, "null pointer", logits_d=NULLS)
+        row(fn, "null pointer", workspace_d=NULLS)
+        row(fn, "workspace size")
+        row(fn, "workspace size", workspace_bytes=64)
+    fn = "wr_ctc_prefix_beam_search"
+    row(fn, "null pointer", n_hyps_d=NULLS)
+    row(fn, "beam", beam=0)
+    row(fn, "beam", beam=17, V=32)
+    row(fn, "beam", beam=9)
+
+
+def rnnt_align_family():
+    for fn, ws in (("wr_rnnt_align", "workspace_bytes"), ("wr_rnnt_align_from_stats", "rnnt_workspace_bytes")):
+        row(fn, "sizes", Tmax=0)
+        row(fn, "U1 limit", U1max=1025)
+        row(fn, "cell count", B=1 << 15, Tmax=1 << 15, U1max=4)
+        row(fn, "null pointer", scores_d=NULLS)
+        row(fn, "null pointer", logit_lengths_d=NULLS)
+        row(fn, "targets null", targets_d=NULLS)
+        row(fn, "targets null", label_frames_d=NULLS)
+        row(fn, "workspace size")
+        row(fn, "workspace size", **{ws: 255})
+        row(fn, "workspace size", U1max=1, targets_d=NULLS, label_frames_d=NULLS)
+    fn = "wr_rnnt_align"
+    row(fn, "sizes", V=0)
+    row(fn, "blank range", blank=8)
+    row(fn, "blank range", blank=-1)
+    row(fn, "null pointer", logits_d=NULLS)
+    row(fn, "dtype code", dtype=3)
+    row(fn, "dtype code", dtype=-1)
+
+
+# size queries that answer a bad argument with 0: (entry point, overrides of the base call)
+SIZE_ZERO = [("wr_decoder_workspace_bytes", dict(w=NULLS)), ("wr_decoder_workspace_bytes", dict(w=W(), max_lanes=0)),
+             ("wr_decoder_workspace_bytes", dict(w=W(), max_utt=0)), ("wr_decoder_workspace_bytes", dict(w=W(), Tmax=-1)),
+             ("wr_hotword_workspace_bytes", dict(h=NULLS)), ("wr_ctc_decode_workspace_bytes", dict(B=0)),
+             ("wr_ctc_decode_workspace_bytes", dict(T=0)), ("wr_ctc_decode_workspace_bytes", dict(beam=0))]
+
+
+def size_zero_answers(lib):
+    """[(entry point, overrides, what the library returned)] for SIZE_ZERO"""
+    protos = prototypes()
+    return [(fn, over, getattr(lib, fn)(*[decode(k, a) for (k, _), a in zip(protos[fn], arguments(protos[fn], over))]))
+            for fn, over in SIZE_ZERO]
+
+
 def all_rows():
     del ROWS[:]
     rnnt_loss_family()
@@ -328,6 +472,9 @@ def all_rows():
     simple_family()
     ctc_family()
     joint_family()
+    decoder_family()
+    ctc_decode_family()
+    rnnt_align_family()
     return list(ROWS)
 
 
@@ -342,6 +489,9 @@ def main():
     from wenet_celoss_amd import _lib
     lib = _lib.load()
     protos = prototypes()
+    for fn, over, got in size_zero_answers(lib):
+        if got != 0:
+            raise SystemExit(f"{fn} {over}: returned {got}, not 0")
     table, seen = [], set()
     for fn, what, over in all_rows():
         args = arguments(protos[fn], over)

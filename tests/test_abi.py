@@ -120,8 +120,8 @@ def test_every_entry_point_rejects_bad_arguments_before_launch(lib):
     assert lib.wr_tune_set(99, 1) == -1
 
 
-LOSS_AND_JOINER_SOURCES = ["joint.hip", "joint_split.hip", "rnnt_loss.hip", "rnnt_pruned.hip", "rnnt_simple.hip",
-                           "rnnt_lattice.hip", "ctc_loss.hip"]
+SOURCES = ["joint.hip", "joint_split.hip", "rnnt_loss.hip", "rnnt_pruned.hip", "rnnt_simple.hip", "rnnt_lattice.hip",
+           "ctc_loss.hip", "decode.hip", "ctc_decode.hip", "rnnt_align.hip"]
 
 
 @pytest.fixture(scope="module")
@@ -137,13 +137,16 @@ def rejections():
         return gen, json.load(f)
 
 
-def test_rejection_table_covers_the_loss_and_joiner_entry_points(rejections):
+def test_rejection_table_covers_every_entry_point(lib, rejections):
     gen, table = rejections
+    csrc = os.path.join(ROOT, "wenet-celoss_amd", "csrc")
+    assert sorted(SOURCES) == sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
     entry_points = set()
-    for name in LOSS_AND_JOINER_SOURCES:
-        src = open(os.path.join(ROOT, "wenet-celoss_amd", "csrc", name)).read()
+    for name in SOURCES:
+        src = open(os.path.join(csrc, name)).read()
         entry_points |= set(re.findall(r'^extern "C" int (wr_[a-z0-9_]+)\(', src, flags=re.M))
-    entry_points.discard("wr_debug_read_js_stamps")            # only in stamp builds; takes no argument to reject
+    entry_points -= {"wr_debug_read_js_stamps", "wr_debug_read_stamps"}   # only in stamp builds; no argument to reject
+    entry_points.discard("wr_decoder_destroy")                 # no rejecting check: a null handle is WR_OK
     assert {r["fn"] for r in table} == entry_points
     # the table is what the generator's rows produce: same calls, same order
     protos = gen.prototypes()
@@ -155,6 +158,8 @@ def test_rejection_table_covers_the_loss_and_joiner_entry_points(rejections):
     assert calls == [[r["fn"], r["args"]] for r in table]
     # no row may have reached a launch when it was recorded
     assert all(r["rc"] in (-1, -2, -3) and r["error"] for r in table)
+    # the size queries answer a bad argument with 0
+    assert [got for _, _, got in gen.size_zero_answers(lib)] == [0] * len(gen.SIZE_ZERO)
 
 
 def test_rejection_table_replays(lib, rejections):

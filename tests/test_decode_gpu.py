@@ -818,3 +818,33 @@ def test_greedy_exact_ties_go_to_the_first_index(where):
     assert hi not in ref                                  # the higher index of a tied pair never wins
     if where != "with_blank":
         assert lo in ref                                  # ... and the tie was at the top: the lower index was emitted
+
+
+def test_rejected_calls_on_a_live_handle_keep_their_answers_and_the_handle():
+    """tests/golden/decoder_rejections.json: one call per argument check that needs a handle (capacities, Tmax,
+    n_steps / blank, a chunk call without stream state, beam limits, the look-ahead range, the hot-word search before
+    and after the attach call, the attach call's own limits and a short workspace), recorded by
+    tests/golden/make_decoder_rejections.py before the decoder's host code was rewritten.  Return codes and
+    wr_last_error() texts are compared exactly; none of the calls reaches a launch, and the handle that took them all
+    still decodes a batch to the tokens of a fresh handle."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("make_decoder_rejections", os.path.join(GOLDEN, "make_decoder_rejections.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(gen.TABLE) as f:
+        table = json.load(f)
+    pred, joint = gen.modules()
+    dec = gen.decoder(pred, joint)
+    got = gen.run(dec)
+    assert [(r["fn"], r["args"]) for r in got] == [(r["fn"], r["args"]) for r in table]
+    wrong = [f"{g['fn']}{g['args']}: ({g['rc']}, {g['error']!r}) != ({r['rc']}, {r['error']!r})"
+             for g, r in zip(got, table) if (g["rc"], g["error"]) != (r["rc"], r["error"])]
+    assert not wrong, "\n".join(wrong)
+    assert all(r["rc"] in (-1, -2, -3) for r in table)
+    torch.manual_seed(1)
+    enc = torch.randn(2, 4, gen.E, device=DEV)
+    lens = torch.tensor([4, 3])
+    hyps = dec.greedy(enc, lens, n_steps=2)
+    assert hyps == gen.decoder(pred, joint).greedy(enc, lens, n_steps=2)
+    assert all(len(h) <= gen.MAX_HYP for h in hyps)

@@ -17,6 +17,7 @@
 //                             per thread, all-pairs steps in parallel (see the kernel).
 //                             Prefixes are compared by (length, 64-bit rolling hash) and verified token by token.
 #include "wr_common.hpp"
+#include "wr_launch.hpp"
 
 namespace wr {
 namespace {
@@ -371,13 +372,11 @@ extern "C" int wr_ctc_greedy_search(const float *logits_d, const int32_t *lens_d
     const int rows = B * T;
     int blocks = (rows + 3) / 4;
     blocks = blocks > 2048 ? 2048 : blocks;
-    hipLaunchKernelGGL(ctc_frame_top1_kernel, dim3(blocks), dim3(256), 0, st, logits_d, rows, V,
-                       reinterpret_cast<int32_t *>(ws + w.best_off), reinterpret_cast<float *>(ws + w.top_off));
-    WR_CHECK_LAUNCH("ctc_frame_top1_kernel");
-    hipLaunchKernelGGL(ctc_greedy_collapse_kernel, dim3(B), dim3(256), 0, st, reinterpret_cast<const int32_t *>(ws + w.best_off),
-                       reinterpret_cast<const float *>(ws + w.top_off), lens_d, T, blank, eos, hyps_d, hyp_lens_d, scores_d);
-    WR_CHECK_LAUNCH("ctc_greedy_collapse_kernel");
-    return WR_OK;
+    WR_TRY(launch("ctc_frame_top1_kernel", ctc_frame_top1_kernel, dim3(blocks), dim3(256), 0, st, logits_d, rows, V,
+                  reinterpret_cast<int32_t *>(ws + w.best_off), reinterpret_cast<float *>(ws + w.top_off)));
+    return launch("ctc_greedy_collapse_kernel", ctc_greedy_collapse_kernel, dim3(B), dim3(256), 0, st,
+                  reinterpret_cast<const int32_t *>(ws + w.best_off), reinterpret_cast<const float *>(ws + w.top_off), lens_d, T,
+                  blank, eos, hyps_d, hyp_lens_d, scores_d);
 }
 
 extern "C" int wr_ctc_prefix_beam_search(const float *logits_d, const int32_t *lens_d, int B, int T, int V, int beam,
@@ -393,12 +392,10 @@ extern "C" int wr_ctc_prefix_beam_search(const float *logits_d, const int32_t *l
     WR_REQUIRE(workspace_bytes >= w.total, WR_EWORKSPACE, "ctc_prefix_beam_search: workspace too small");
     hipStream_t st = static_cast<hipStream_t>(stream);
     char *ws = static_cast<char *>(workspace_d);
-    hipLaunchKernelGGL(ctc_frame_topk_kernel, dim3(B * T), dim3(256), (size_t)V * sizeof(float), st, logits_d, V, beam,
-                       reinterpret_cast<float *>(ws + w.tkv_off), reinterpret_cast<int32_t *>(ws + w.tki_off));
-    WR_CHECK_LAUNCH("ctc_frame_topk_kernel");
-    hipLaunchKernelGGL(ctc_prefix_beam_kernel, dim3(B), dim3(256), 0, st, reinterpret_cast<const float *>(ws + w.tkv_off),
-                       reinterpret_cast<const int32_t *>(ws + w.tki_off), lens_d, T, beam, blank,
-                       reinterpret_cast<int32_t *>(ws + w.seq_off), hyps_d, hyp_lens_d, scores_d, n_hyps_d);
-    WR_CHECK_LAUNCH("ctc_prefix_beam_kernel");
-    return WR_OK;
+    // dynamic LDS: one row of logits, under 64 KiB (ctc_dec_check)
+    WR_TRY(launch("ctc_frame_topk_kernel", ctc_frame_topk_kernel, dim3(B * T), dim3(256), (size_t)V * sizeof(float), st, logits_d, V,
+                  beam, reinterpret_cast<float *>(ws + w.tkv_off), reinterpret_cast<int32_t *>(ws + w.tki_off)));
+    return launch("ctc_prefix_beam_kernel", ctc_prefix_beam_kernel, dim3(B), dim3(256), 0, st,
+                  reinterpret_cast<const float *>(ws + w.tkv_off), reinterpret_cast<const int32_t *>(ws + w.tki_off), lens_d, T, beam,
+                  blank, reinterpret_cast<int32_t *>(ws + w.seq_off), hyps_d, hyp_lens_d, scores_d, n_hyps_d);
 }

@@ -38,6 +38,7 @@
 // Micro-steps are replayed from a hipGraph (captured once per decoder handle) so
 // the host only checks a "lanes still active" word every 16 steps.
 #include "wr_common.hpp"
+#include "wr_launch.hpp"
 
 #include <math.h>
 #include <string.h>
@@ -2096,39 +2097,50 @@ __global__ void beam_export_kernel(DevState *s, int32_t *hyps_out, int32_t *lens
 using namespace wr;
 
 // ------------------------------------------------------------ host handle --
+// an executable graph of kStepsPerGraph steps and the shape it was captured for (-1: none, or dropped by a failed call)
+struct GraphSlot {
+    hipGraphExec_t exec = nullptr;
+    int key = -1;
+};
+
 struct wr_decoder {
-    Dims d;
-    DevState host;                // host copy of the device state block
-    DevState *dev;                // device copy (first bytes of the workspace)
-    char *ws;
-    size_t ws_bytes;
-    int max_utt, Tmax, max_hyp, max_beam;
-    size_t zero_range[2];
-    int32_t *h_active;            // pinned host word
-    DevState *h_stage;            // pinned staging slots for the state block (kStageSlots), so that the upload is a
-    hipEvent_t stage_ev[4];       // true async copy: a slot is reused only after the copy that read it has completed
-    int stage_next;
-    hipStream_t work;             // decode work runs here (graph capture is illegal on the legacy default stream)
-    hipEvent_t ev_in, ev_out;     // ordering against the caller's stream, no device-wide sync
-    hipGraphExec_t greedy_graph[kMaxLook + 1];   // one per look-ahead setting
-    int greedy_graph_key[kMaxLook + 1];
-    hipGraphExec_t beam_graph;
-    int beam_graph_lanes;
-    int stream_lanes;             // lanes whose streaming state (cache, token, flags) is live; -1: none
-    int look;                     // greedy look-ahead: frames per micro-step (1..kMaxLook), 0: chosen per replay
+    Dims d{};
+    DevState host{};              // host copy of the device state block
+    DevState *dev = nullptr;      // device copy (first bytes of the workspace)
+    char *ws = nullptr;
+    size_t ws_bytes = 0;
+    int max_utt = 0, Tmax = 0, max_hyp = 0, max_beam = 0;
+    size_t zero_range[2] = {0, 0};
+    int32_t *h_active = nullptr;  // pinned host word
+    DevState *h_stage = nullptr;  // pinned staging slots for the state block (kStageSlots), so that the upload is a
+    hipEvent_t stage_ev[kStageSlots] = {};   // true async copy: a slot is reused only after the copy that read it has completed
+    int stage_next = 0;
+    hipStream_t work = nullptr;   // decode work runs here (graph capture is illegal on the legacy default stream)
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;   // ordering against the caller's stream, no device-wide sync
+    GraphSlot greedy[kMaxLook + 1];   // one per look-ahead setting, keyed by the lanes
+    GraphSlot beam;               // keyed by lanes and beam
+    GraphSlot hotword;            // keyed by the lanes
+    int stream_lanes = -1;        // lanes whose streaming state (cache, token, flags) is live; -1: none
+    int look = 0;                 // greedy look-ahead: frames per micro-step (1..kMaxLook), 0: chosen per replay
     // hot-word greedy (wr_decoder_attach_hotword)
-    bool hw_attached;
-    HwDev hw;
-    float *hw_ep2;                // [2][max_utt * Tmax * J] enc_ffn of the empty-list (0) / hot-word (1) encoder stream
-    int32_t *hw_state;            // cur_gate | gb_flag | gb_end | last_t, NLp each
-    float *hw_biasT;              // [Pp][NLp]
-    hipGraphExec_t hw_graph;
-    int hw_graph_key;
-    bool use_graph;               // greedy micro-steps replayed from a hipGraph (default on)
-    bool use_graph_beam;          // beam frames: plain launches measured faster (no host polling to amortise), default off
+    bool hw_attached = false;
+    HwDev hw{};
+    float *hw_ep2 = nullptr;      // [2][max_utt * Tmax * J] enc_ffn of the empty-list (0) / hot-word (1) encoder stream
+    int32_t *hw_state = nullptr;  // cur_gate | gb_flag | gb_end | last_t, NLp each
+    float *hw_biasT = nullptr;    // [Pp][NLp]
+    bool use_graph = true;        // greedy micro-steps replayed from a hipGraph (default on)
+    bool use_graph_beam = false;  // beam frames: plain launches measured faster (no host polling to amortise), default off
 };
 
 namespace {
+
+template <typename F>
+void for_each_graph(wr_decoder *h, F f)
+{
+    for (GraphSlot &g : h->greedy) f(g);
+    f(h->beam);
+    f(h->hotword);
+}
 
 struct Carver {
     char *base;
@@ -2154,12 +2166,11 @@ size_t carve(const wr_transducer_weights *w, int max_lanes, int max_utt, int Tma
     d.act = w->activation;
     d.ptype = w->predictor_type; d.ctx = w->context_size; d.heads = w->n_head; d.pact = w->pred_activation;
     d.ln_eps = w->ln_eps;
-    auto up = [](int x, int m) { return (x + m - 1) / m * m; };
-    d.Dp = up(d.D, 16); d.Hp = up(d.H, 16); d.Pp = up(d.P, 16); d.Jp = up(d.J, 16);   // K: 8 waves x k-pairs
+    d.Dp = round_up(d.D, 16); d.Hp = round_up(d.H, 16); d.Pp = round_up(d.P, 16); d.Jp = round_up(d.J, 16);   // K: 8 waves x k-pairs
     d.G4p = 4 * d.Hp;                                      // 32-column tiles = i,f,g,o of 8 hidden units
-    d.Vp = up(d.V, 256);
+    d.Vp = round_up(d.V, 256);
     d.NL = max_lanes;
-    d.NLp = max_lanes <= 32 ? 32 : up(max_lanes, 64);     // lane tiles of the GEMM: 32, or pairs of 32
+    d.NLp = max_lanes <= 32 ? 32 : round_up(max_lanes, 64);   // lane tiles of the GEMM: 32, or pairs of 32
     DevState s;
     memset(&s, 0, sizeof(s));
     s.d = d;
@@ -2170,14 +2181,14 @@ size_t carve(const wr_transducer_weights *w, int max_lanes, int max_utt, int Tma
         s.wt_hh[l] = c.take<float>((size_t)d.Hp * d.G4p);
         s.bsum[l] = c.take<float>((size_t)d.G4p);
     }
-    const int Pn = up(d.P, 32), Jn = up(d.J, 32);
+    const int Pn = round_up(d.P, 32), Jn = round_up(d.J, 32);
     if (d.ptype == kPredLstm) {
         s.proj_wt = c.take<float>((size_t)d.Hp * Pn);
         s.projffn_wt = c.take<float>((size_t)d.Hp * Jn);
         s.projffn_b = c.take<float>((size_t)Jn);
     }
     if (d.ptype == kPredEmbedding) {
-        s.pffn_wt = c.take<float>((size_t)d.Dp * up(d.D, 32));
+        s.pffn_wt = c.take<float>((size_t)d.Dp * round_up(d.D, 32));
         s.combT = c.take<float>((size_t)d.Dp * d.NLp);
         s.ffnT = c.take<float>((size_t)d.Dp * d.NLp);
     }
@@ -2264,9 +2275,10 @@ int check_weights(const wr_transducer_weights *w)
     return WR_OK;
 }
 
-void launch_transpose(const float *src, int R, int C, int Rp, int Cp, float *dst, hipStream_t st)
+int launch_transpose(const float *src, int R, int C, int Rp, int Cp, float *dst, hipStream_t st)
 {
-    hipLaunchKernelGGL(transpose_pad_kernel, dim3((Rp + 31) / 32, (Cp + 31) / 32), dim3(256), 0, st, src, R, C, Rp, Cp, dst);
+    return launch("transpose_pad_kernel", transpose_pad_kernel, dim3((Rp + 31) / 32, (Cp + 31) / 32), dim3(256), 0, st, src, R, C,
+                  Rp, Cp, dst);
 }
 
 // a 128-lane workgroup reads A columns lane0 .. lane0 + 127: the k-major arrays must be that wide
@@ -2275,39 +2287,51 @@ inline bool d_nlp_lt128(const GemmArgs &g) { return (g.lda % 128) != 0; }
 // Exact-fp32 MFMA runs at 256 flop/clk/CU, so a 64-lane x 32-column x 512-deep tile already costs 3.4 us on its
 // CU: lane tiles of 32 (more, smaller workgroups) whenever they all fit on the chip at once.
 template <int EPI>
-void launch_gemm(const GemmArgs &g, int n_cols_padded, int n_lanes, hipStream_t st)
+int launch_gemm(const GemmArgs &g, int n_cols_padded, int n_lanes, hipStream_t st)
 {
     const int mt = (n_lanes + 31) / 32, ct = n_cols_padded / 32;
     const int policy = tune_get(kTuneLaneGemmTile);               // 0: by occupancy, 1: 32-lane tiles, 2: 64-lane tiles
-    if (mt == 1 || policy == 1 || (policy == 0 && ct * mt <= 256)) {
-        hipLaunchKernelGGL((lane_gemm_kernel<1, EPI>), dim3(ct, mt), dim3(64 * kGemmWaves), 0, st, g);
-    } else if (policy == 2 || (policy == 0 && ct * ((mt + 1) / 2) <= 256) || !(EPI == kEpiRowMajor || EPI == kEpiRowStats) || d_nlp_lt128(g)) {
-        hipLaunchKernelGGL((lane_gemm_kernel<2, EPI>), dim3(ct, (mt + 1) / 2), dim3(64 * kGemmWaves), 0, st, g);
-    } else {
-        // more tiles than one round of 64-lane workgroups (bit-identical results in every form): 128-lane workgroups
-        // (knob 6 = 3: 4-wave workgroups of 32 lanes, four per CU; 4: one wave per tile)
-        if constexpr (EPI == kEpiRowMajor || EPI == kEpiRowStats) {
-            if (policy == 3)
-                hipLaunchKernelGGL((lane_gemm4_kernel<EPI>), dim3(ct, mt), dim3(64 * kGemmWaves / 2), 0, st, g);
-            else if (policy == 4 && EPI == kEpiRowMajor)
-                hipLaunchKernelGGL((lane_gemm1_kernel<kEpiRowMajor>), dim3(ct, mt), dim3(64), 0, st, g);
-            else
-                hipLaunchKernelGGL((lane_gemm_kernel<4, EPI>), dim3(ct, (mt + 3) / 4), dim3(64 * kGemmWaves), 0, st, g);
-        }
+    const dim3 block(64 * kGemmWaves);
+    if (mt == 1 || policy == 1 || (policy == 0 && ct * mt <= 256))
+        return launch("lane_gemm_kernel", lane_gemm_kernel<1, EPI>, dim3(ct, mt), block, 0, st, g);
+    if (policy == 2 || (policy == 0 && ct * ((mt + 1) / 2) <= 256) || !(EPI == kEpiRowMajor || EPI == kEpiRowStats) || d_nlp_lt128(g))
+        return launch("lane_gemm_kernel", lane_gemm_kernel<2, EPI>, dim3(ct, (mt + 1) / 2), block, 0, st, g);
+    // more tiles than one round of 64-lane workgroups (bit-identical results in every form): 128-lane workgroups
+    // (knob 6 = 3: 4-wave workgroups of 32 lanes, four per CU; 4: one wave per tile)
+    if constexpr (EPI == kEpiRowMajor || EPI == kEpiRowStats) {
+        if (policy == 3)
+            return launch("lane_gemm4_kernel", lane_gemm4_kernel<EPI>, dim3(ct, mt), dim3(64 * kGemmWaves / 2), 0, st, g);
+        if (policy == 4 && EPI == kEpiRowMajor)
+            return launch("lane_gemm1_kernel", lane_gemm1_kernel<kEpiRowMajor>, dim3(ct, mt), dim3(64), 0, st, g);
+        return launch("lane_gemm_kernel", lane_gemm_kernel<4, EPI>, dim3(ct, (mt + 3) / 4), block, 0, st, g);
     }
+    return WR_OK;
 }
 
 // two GEMMs over the same lanes in one launch (lane_gemm_pair_kernel)
 template <int EPI0, int EPI1>
-void launch_gemm_pair(const GemmArgs &g0, int cols0, const GemmArgs &g1, int cols1, int n_lanes, hipStream_t st)
+int launch_gemm_pair(const GemmArgs &g0, int cols0, const GemmArgs &g1, int cols1, int n_lanes, hipStream_t st)
 {
     const int mt = (n_lanes + 31) / 32, ct0 = cols0 / 32, ct = ct0 + cols1 / 32;
     const int policy = tune_get(kTuneLaneGemmTile);
-    if (mt == 1 || policy == 1 || (policy == 0 && ct * mt <= 256)) {
-        hipLaunchKernelGGL((lane_gemm_pair_kernel<1, EPI0, EPI1>), dim3(ct, mt), dim3(64 * kGemmWaves), 0, st, g0, g1, ct0);
-    } else {
-        hipLaunchKernelGGL((lane_gemm_pair_kernel<2, EPI0, EPI1>), dim3(ct, (mt + 1) / 2), dim3(64 * kGemmWaves), 0, st, g0, g1, ct0);
-    }
+    if (mt == 1 || policy == 1 || (policy == 0 && ct * mt <= 256))
+        return launch("lane_gemm_pair_kernel", lane_gemm_pair_kernel<1, EPI0, EPI1>, dim3(ct, mt), dim3(64 * kGemmWaves), 0, st, g0,
+                      g1, ct0);
+    return launch("lane_gemm_pair_kernel", lane_gemm_pair_kernel<2, EPI0, EPI1>, dim3(ct, (mt + 1) / 2), dim3(64 * kGemmWaves), 0,
+                  st, g0, g1, ct0);
+}
+
+// The fields every GEMM job sets.  `stamp` is the job's slot in the stamp array of the diagnostic build (-1: none).
+GemmArgs gemm_job(const float *A0, int lda, int K0, const float *B0, int ldb, const float *bias, float *C, int ldc, int N,
+                  int n_lanes, int stamp = -1)
+{
+    GemmArgs g{};
+    g.A0 = A0; g.lda = lda; g.K0 = K0; g.B0 = B0; g.ldb = ldb; g.bias = bias;
+    g.C = C; g.ldc = ldc; g.N = N; g.n_lanes = n_lanes;
+#ifdef WR_STAMPS
+    g.dbg_slot = stamp;
+#endif
+    return g;
 }
 
 // pool_g[l][new_slot[n]] = W_hh_l . new_h_l[n] + b_l: the recurrent product of the state a lane's step has just produced,
@@ -2316,107 +2340,139 @@ GemmArgs recurrent_job(const wr_decoder *h, int l, int n_lanes, const int32_t *s
 {
     const Dims &d = h->d;
     const DevState &s = h->host;
-    GemmArgs g{};
-    g.A0 = s.new_hT + (size_t)l * d.Hp * d.NLp; g.B0 = s.wt_hh[l]; g.K0 = d.Hp;
-    g.lda = d.NLp; g.ldb = d.G4p; g.bias = s.bsum[l];
-    g.C = s.pool_g + (size_t)l * 2 * d.NLp * d.G4p; g.ldc = d.G4p; g.N = d.G4p; g.n_lanes = n_lanes;
+    GemmArgs g = gemm_job(s.new_hT + (size_t)l * d.Hp * d.NLp, d.NLp, d.Hp, s.wt_hh[l], d.G4p, s.bsum[l],
+                          s.pool_g + (size_t)l * 2 * d.NLp * d.G4p, d.G4p, d.G4p, n_lanes);
     g.slot_idx = slot_idx;
-#ifdef WR_STAMPS
-    g.dbg_slot = -1;
-#endif
     return g;
 }
 
 // predictor step (predicated per lane).  LSTM: layer 0 was evaluated by the kernel that decided the token (or by the init
 // kernel); here layers 1 .. L-1, each one GEMM of depth H with the recurrent product of the layer below in the same
 // launch, and -- unless the caller folds it into pred_ffn -- the projection (with the last layer's recurrent product).
-// Returns true if the last layer's recurrent product is still to be launched (the caller pairs it with its next GEMM).
-bool launch_predictor(wr_decoder *h, int n_lanes, hipStream_t st, bool with_projection = true)
+// `*recurrent_pending` is set if the last layer's recurrent product is still to be launched (the caller pairs it with its
+// next GEMM).
+int launch_predictor(wr_decoder *h, int n_lanes, hipStream_t st, bool with_projection = true, bool *recurrent_pending = nullptr)
 {
     const Dims &d = h->d;
     const DevState &s = h->host;
-    auto up = [](int x, int m) { return (x + m - 1) / m * m; };
     const size_t ls = (size_t)d.Hp * d.NLp;
+    if (recurrent_pending) *recurrent_pending = false;
     if (d.ptype == kPredEmbedding) {            // context weighting -> ffn (lane GEMM) -> LayerNorm + activation
-        hipLaunchKernelGGL(ctx_predictor_kernel<0>, dim3(n_lanes), dim3(kCtxThreads), 0, st, h->dev);
-        GemmArgs g{};
-        g.A0 = s.combT; g.B0 = s.pffn_wt; g.K0 = d.Dp;
-        g.lda = d.NLp; g.ldb = up(d.D, 32); g.bias = s.pffn_b; g.C = s.ffnT; g.ldc = d.NLp; g.N = d.D; g.n_lanes = n_lanes;
-#ifdef WR_STAMPS
-        g.dbg_slot = -1;
-#endif
-        launch_gemm<kEpiKMajor>(g, up(d.D, 32), n_lanes, st);
-        hipLaunchKernelGGL(ctx_predictor_kernel<1>, dim3(n_lanes), dim3(kCtxThreads), 0, st, h->dev);
-        return false;
+        WR_TRY(launch("ctx_predictor_kernel", ctx_predictor_kernel<0>, dim3(n_lanes), dim3(kCtxThreads), 0, st, h->dev));
+        const int Dn = round_up(d.D, 32);
+        WR_TRY(launch_gemm<kEpiKMajor>(gemm_job(s.combT, d.NLp, d.Dp, s.pffn_wt, Dn, s.pffn_b, s.ffnT, d.NLp, d.D, n_lanes), Dn,
+                                       n_lanes, st));
+        return launch("ctx_predictor_kernel", ctx_predictor_kernel<1>, dim3(n_lanes), dim3(kCtxThreads), 0, st, h->dev);
     }
-    if (d.ptype == kPredConv) {
-        hipLaunchKernelGGL(ctx_predictor_kernel<2>, dim3(n_lanes), dim3(kCtxThreads), 0, st, h->dev);
-        return false;
-    }
+    if (d.ptype == kPredConv)
+        return launch("ctx_predictor_kernel", ctx_predictor_kernel<2>, dim3(n_lanes), dim3(kCtxThreads), 0, st, h->dev);
     for (int l = 1; l < d.L; ++l) {
-        GemmArgs g{};
-        g.A0 = s.new_hT + (size_t)(l - 1) * ls; g.B0 = s.wt_ih[l]; g.K0 = d.Hp;
-        g.lda = d.NLp; g.ldb = d.G4p; g.N = d.G4p; g.n_lanes = n_lanes;
+        GemmArgs g = gemm_job(s.new_hT + (size_t)(l - 1) * ls, d.NLp, d.Hp, s.wt_ih[l], d.G4p, nullptr, nullptr, 0, d.G4p, n_lanes,
+                              l < 2 ? l : -1);
         g.lane_active = s.lane_active; g.need_pred = s.need_pred; g.H = d.H; g.Hp = d.Hp; g.G4p = d.G4p;
         g.pool_g = s.pool_g + (size_t)l * 2 * d.NLp * d.G4p; g.pool_c = s.pool_c + (size_t)l * 2 * d.NLp * d.Hp;
         g.comm_slot = s.comm_slot; g.new_slot = s.new_slot; g.new_hT = s.new_hT + (size_t)l * ls;
-#ifdef WR_STAMPS
-        g.dbg_slot = l < 2 ? l : -1;
-#endif
-        launch_gemm_pair<kEpiLstmCell, kEpiSlotRow>(g, d.G4p, recurrent_job(h, l - 1, n_lanes, s.new_slot), d.G4p, n_lanes, st);
+        WR_TRY(launch_gemm_pair<kEpiLstmCell, kEpiSlotRow>(g, d.G4p, recurrent_job(h, l - 1, n_lanes, s.new_slot), d.G4p, n_lanes, st));
     }
-    if (!with_projection) return true;            // the caller applies the composed projection + pred_ffn
-    GemmArgs g{};
-    g.A0 = s.new_hT + (size_t)(d.L - 1) * ls; g.B0 = s.proj_wt; g.K0 = d.Hp;
-    g.lda = d.NLp; g.ldb = up(d.P, 32); g.bias = s.proj_b; g.C = s.outT; g.ldc = d.NLp; g.N = d.P; g.n_lanes = n_lanes;
-#ifdef WR_STAMPS
-    g.dbg_slot = 8;
-#endif
-    launch_gemm_pair<kEpiKMajor, kEpiSlotRow>(g, up(d.P, 32), recurrent_job(h, d.L - 1, n_lanes, s.new_slot), d.G4p, n_lanes, st);
-    return false;
+    if (!with_projection) {                       // the caller applies the composed projection + pred_ffn
+        if (recurrent_pending) *recurrent_pending = true;
+        return WR_OK;
+    }
+    const int Pn = round_up(d.P, 32);
+    return launch_gemm_pair<kEpiKMajor, kEpiSlotRow>(
+        gemm_job(s.new_hT + (size_t)(d.L - 1) * ls, d.NLp, d.Hp, s.proj_wt, Pn, s.proj_b, s.outT, d.NLp, d.P, n_lanes, 8), Pn,
+        recurrent_job(h, d.L - 1, n_lanes, s.new_slot), d.G4p, n_lanes, st);
 }
 
-void launch_predictor_and_joint(wr_decoder *h, int n_lanes, hipStream_t st, int look = 1, bool row_stats = false)
+// pred_ffn over the k-major operand A with the joiner activation as epilogue.  `fold`: A is the last LSTM layer's hidden
+// state and the weight is the composed projection + pred_ffn.  The activation adds enc_ffn of `look` frames from `ep_all`;
+// with `ep_gate` (hot-word search) each lane picks one of the two encoder streams stored behind each other there.
+GemmArgs pred_ffn_job(const wr_decoder *h, const float *A, bool fold, int n_lanes, int look, const float *ep_all,
+                      const int32_t *ep_gate = nullptr)
 {
     const Dims &d = h->d;
     const DevState &s = h->host;
-    auto up = [](int x, int m) { return (x + m - 1) / m * m; };
+    GemmArgs g = gemm_job(A, d.NLp, fold ? d.Hp : d.Pp, fold ? s.projffn_wt : s.predffn_wt, round_up(d.J, 32),
+                          fold ? s.projffn_b : s.predffn_b, s.ht, kMaxLook * d.NLp, d.J, n_lanes, 2);
+    g.st = h->dev; g.lane_active = s.lane_active; g.lane_t = s.lane_t; g.ep_all = ep_all; g.J = d.J;
+    g.look = look; g.lane_stride = d.NLp; g.act = d.act;
+    if (ep_gate) { g.ep_gate = ep_gate; g.ep_gate_stride = (size_t)h->max_utt * h->Tmax * d.J; }
+    return g;
+}
+
+// launch it, together with the last layer's recurrent product where launch_predictor left that pending
+int launch_pred_ffn(const wr_decoder *h, const GemmArgs &g, bool recurrent_pending, int n_lanes, hipStream_t st)
+{
+    const Dims &d = h->d;
+    if (recurrent_pending)
+        return launch_gemm_pair<kEpiJointAct, kEpiSlotRow>(g, round_up(d.J, 32), recurrent_job(h, d.L - 1, n_lanes, h->host.new_slot),
+                                                           d.G4p, n_lanes, st);
+    return launch_gemm<kEpiJointAct>(g, round_up(d.J, 32), n_lanes, st);
+}
+
+// the joiner output for `rows` (frame, lane) columns of ht: rows f * NLp + n of the logits; `row_stats` adds the records
+// the greedy update kernel reads (kEpiRowStats)
+GemmArgs joint_out_job(const wr_decoder *h, int rows, bool row_stats)
+{
+    const Dims &d = h->d;
+    const DevState &s = h->host;
+    GemmArgs g = gemm_job(s.ht, kMaxLook * d.NLp, d.Jp, s.out_wt, d.Vp, s.out_b, s.logits, d.V, d.V, rows, 3);
+    if (row_stats) { g.row_part = s.row_part; g.row_part_ld = s.n_cb; }
+    return g;
+}
+
+int launch_predictor_and_joint(wr_decoder *h, int n_lanes, hipStream_t st, int look = 1, bool row_stats = false)
+{
+    const Dims &d = h->d;
+    const DevState &s = h->host;
     // LSTM predictor: the projection is folded into pred_ffn (one launch less per micro-step; wr_tune_set(11, 1) keeps
     // them apart).  The hot-word search and wr_predictor_step need the projected output itself and keep the two stages.
     const bool fold = d.ptype == kPredLstm && tune_get(kTuneFoldProj) != 1;
-    const bool recurrent_pending = launch_predictor(h, n_lanes, st, !fold);
-    {   // pred_ffn with the joiner activation as epilogue
-        GemmArgs g{};
-        if (fold) {
-            g.A0 = s.new_hT + (size_t)(d.L - 1) * d.Hp * d.NLp; g.B0 = s.projffn_wt; g.K0 = d.Hp; g.bias = s.projffn_b;
-        } else {
-            g.A0 = s.outT; g.B0 = s.predffn_wt; g.K0 = d.Pp; g.bias = s.predffn_b;
-        }
-        g.lda = d.NLp; g.ldb = up(d.J, 32); g.C = s.ht; g.ldc = kMaxLook * d.NLp; g.N = d.J; g.n_lanes = n_lanes;
-        g.st = h->dev; g.lane_active = s.lane_active; g.lane_t = s.lane_t; g.ep_all = s.ep_all; g.J = d.J;
-        g.look = look; g.lane_stride = d.NLp; g.act = d.act;
-#ifdef WR_STAMPS
-        g.dbg_slot = 2;
-#endif
-        if (recurrent_pending)
-            launch_gemm_pair<kEpiJointAct, kEpiSlotRow>(g, up(d.J, 32), recurrent_job(h, d.L - 1, n_lanes, s.new_slot), d.G4p, n_lanes, st);
-        else
-            launch_gemm<kEpiJointAct>(g, up(d.J, 32), n_lanes, st);
-    }
-    GemmArgs g{};
-#ifdef WR_STAMPS
-    g.dbg_slot = 3;
-#endif
-    // the joiner output for every (frame, lane) column of ht: rows f * NLp + n of the logits
+    bool recurrent_pending = false;
+    WR_TRY(launch_predictor(h, n_lanes, st, !fold, &recurrent_pending));
+    const float *A = fold ? s.new_hT + (size_t)(d.L - 1) * d.Hp * d.NLp : s.outT;
+    WR_TRY(launch_pred_ffn(h, pred_ffn_job(h, A, fold, n_lanes, look, s.ep_all), recurrent_pending, n_lanes, st));
     const int rows = (look - 1) * d.NLp + n_lanes;
-    g.A0 = s.ht; g.B0 = s.out_wt; g.K0 = d.Jp;
-    g.lda = kMaxLook * d.NLp; g.ldb = d.Vp; g.bias = s.out_b; g.C = s.logits; g.ldc = d.V; g.N = d.V; g.n_lanes = rows;
-    if (row_stats) {                               // greedy, one frame per micro-step: the update kernel reads the records
-        g.row_part = s.row_part; g.row_part_ld = s.n_cb;
-        launch_gemm<kEpiRowStats>(g, d.Vp, rows, st);
-    } else {
-        launch_gemm<kEpiRowMajor>(g, d.Vp, rows, st);
+    const GemmArgs g = joint_out_job(h, rows, row_stats);
+    if (row_stats) return launch_gemm<kEpiRowStats>(g, d.Vp, rows, st);   // greedy, one frame per micro-step
+    return launch_gemm<kEpiRowMajor>(g, d.Vp, rows, st);
+}
+
+// enc_ffn of `rows` encoder frames: 8 frames per workgroup
+int launch_ep_all(wr_decoder *h, hipStream_t st, long rows, const float *enc, float *out)
+{
+    return launch("ep_all_kernel", ep_all_kernel, dim3((unsigned)((rows + 7) / 8)), dim3(256), (size_t)8 * h->d.E * sizeof(float), st,
+                  h->dev, enc, out);
+}
+
+// the k-major, padded and composed forms of the weights, into the workspace
+int prepare_weights(wr_decoder *h, const wr_transducer_weights *w, hipStream_t st)
+{
+    const Dims &d = h->d;
+    const DevState &s = h->host;
+    if (d.ptype == kPredEmbedding) WR_TRY(launch_transpose(w->ffn_w, d.D, d.D, round_up(d.D, 32), d.Dp, s.pffn_wt, st));
+    for (int l = 0; l < d.L && d.ptype == kPredLstm; ++l) {
+        if (l > 0)
+            WR_TRY(launch("lstm_weight_prep_kernel", lstm_weight_prep_kernel, dim3(256), dim3(256), 0, st, w->w_ih[l], d.H, d.Hp, d.H,
+                          d.Hp, s.wt_ih[l]));
+        else
+            WR_TRY(launch("lstm_etab_kernel", lstm_etab_kernel, dim3(2048), dim3(256), 0, st, w->embed, w->w_ih[0], d.Ve, d.D, d.H,
+                          d.Hp, s.etab));
+        WR_TRY(launch("lstm_weight_prep_kernel", lstm_weight_prep_kernel, dim3(256), dim3(256), 0, st, w->w_hh[l], d.H, d.Hp, d.H,
+                      d.Hp, s.wt_hh[l]));
+        WR_TRY(launch("lstm_bias_prep_kernel", lstm_bias_prep_kernel, dim3((d.G4p + 255) / 256), dim3(256), 0, st, w->b_ih[l],
+                      w->b_hh[l], d.H, d.Hp, s.bsum[l]));
     }
+    if (d.ptype == kPredLstm) {
+        WR_TRY(launch_transpose(w->proj_w, d.P, d.H, round_up(d.P, 32), d.Hp, s.proj_wt, st));
+        const long n = (long)d.H * d.J + d.J;
+        WR_TRY(launch("compose_proj_ffn_kernel", compose_proj_ffn_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                      w->pred_ffn_w, w->pred_ffn_b, w->proj_w, w->proj_b, d.J, d.P, d.H, round_up(d.J, 32), s.projffn_wt,
+                      s.projffn_b));
+    }
+    WR_TRY(launch_transpose(w->pred_ffn_w, d.J, d.P, round_up(d.J, 32), d.Pp, s.predffn_wt, st));
+    WR_TRY(launch_transpose(w->enc_ffn_w, d.J, d.E, d.J, d.E, s.encffn_wt, st));
+    return launch_transpose(w->out_w, d.V, d.J, d.Vp, d.Jp, s.out_wt, st);
 }
 
 }  // namespace
@@ -2447,20 +2503,9 @@ extern "C" int wr_decoder_create(const wr_transducer_weights *w, int max_lanes, 
     carve(w, max_lanes, max_utt, Tmax, max_hyp, max_beam, h->ws, &h->host, &h->dev, h->zero_range);
     h->d = h->host.d;
     h->max_utt = max_utt; h->Tmax = Tmax; h->max_hyp = max_hyp; h->max_beam = max_beam;
-    for (int i = 0; i <= kMaxLook; ++i) { h->greedy_graph[i] = nullptr; h->greedy_graph_key[i] = -1; }
-    h->beam_graph = nullptr; h->beam_graph_lanes = -1;
-    h->hw_attached = false; h->hw_graph = nullptr; h->hw_graph_key = -1;
-    h->use_graph = true;
-    h->use_graph_beam = false;
-    h->look = 0;
-    h->stream_lanes = -1;
-    h->h_active = nullptr;
-    h->h_stage = nullptr;
-    h->stage_next = 0;
     if (hipHostMalloc(reinterpret_cast<void **>(&h->h_active), 64, hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc(reinterpret_cast<void **>(&h->h_stage), kStageSlots * sizeof(DevState), hipHostMallocDefault) != hipSuccess) {
-        if (h->h_active) (void)hipHostFree(h->h_active);
-        delete h;
+        (void)wr_decoder_destroy(h);
         set_error("decoder_create: hipHostMalloc failed");
         return WR_ELAUNCH;
     }
@@ -2469,63 +2514,36 @@ extern "C" int wr_decoder_create(const wr_transducer_weights *w, int max_lanes, 
     if (!ev_ok || hipStreamCreateWithFlags(&h->work, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming) != hipSuccess) {
-        (void)hipHostFree(h->h_active);
-        (void)hipHostFree(h->h_stage);
-        delete h;
+        (void)wr_decoder_destroy(h);
         set_error("decoder_create: stream/event creation failed");
         return WR_ELAUNCH;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const Dims &d = h->d;
     DevState &s = h->host;
     s.embed = w->embed; s.proj_b = w->proj_b; s.predffn_b = w->pred_ffn_b; s.encffn_b = w->enc_ffn_b; s.out_b = w->out_b;
     (void)hipMemsetAsync(h->ws + h->zero_range[0], 0, h->zero_range[1] - h->zero_range[0], st);
-    auto up = [](int x, int m) { return (x + m - 1) / m * m; };
     s.pos_w = w->pos_w; s.pffn_b = w->ffn_b; s.pnorm_w = w->norm_w; s.pnorm_b = w->norm_b; s.conv_w = w->conv_w;
     s.conv_b = w->conv_b;
-    if (d.ptype == kPredEmbedding) launch_transpose(w->ffn_w, d.D, d.D, up(d.D, 32), d.Dp, s.pffn_wt, st);
-    for (int l = 0; l < d.L && d.ptype == kPredLstm; ++l) {
-        if (l > 0)
-            hipLaunchKernelGGL(lstm_weight_prep_kernel, dim3(256), dim3(256), 0, st, w->w_ih[l], d.H, d.Hp, d.H, d.Hp, s.wt_ih[l]);
-        else
-            hipLaunchKernelGGL(lstm_etab_kernel, dim3(2048), dim3(256), 0, st, w->embed, w->w_ih[0], d.Ve, d.D, d.H, d.Hp, s.etab);
-        hipLaunchKernelGGL(lstm_weight_prep_kernel, dim3(256), dim3(256), 0, st, w->w_hh[l], d.H, d.Hp, d.H, d.Hp, s.wt_hh[l]);
-        hipLaunchKernelGGL(lstm_bias_prep_kernel, dim3((d.G4p + 255) / 256), dim3(256), 0, st, w->b_ih[l], w->b_hh[l], d.H, d.Hp,
-                           s.bsum[l]);
-    }
-    if (d.ptype == kPredLstm) {
-        launch_transpose(w->proj_w, d.P, d.H, up(d.P, 32), d.Hp, s.proj_wt, st);
-        const long n = (long)d.H * d.J + d.J;
-        hipLaunchKernelGGL(compose_proj_ffn_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w->pred_ffn_w, w->pred_ffn_b,
-                           w->proj_w, w->proj_b, d.J, d.P, d.H, up(d.J, 32), s.projffn_wt, s.projffn_b);
-    }
-    launch_transpose(w->pred_ffn_w, d.J, d.P, up(d.J, 32), d.Pp, s.predffn_wt, st);
-    launch_transpose(w->enc_ffn_w, d.J, d.E, d.J, d.E, s.encffn_wt, st);
-    launch_transpose(w->out_w, d.V, d.J, d.Vp, d.Jp, s.out_wt, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
+    if (int rc = prepare_weights(h, w, st)) {
         (void)wr_decoder_destroy(h);
-        set_error("decoder_create: weight preparation failed: %s", hipGetErrorString(e));
-        return WR_ELAUNCH;
+        return rc;
     }
     *out = h;
     return WR_OK;
 }
 
+// safe on a partly built handle (the failure paths of wr_decoder_create): whatever was not created is skipped
 extern "C" int wr_decoder_destroy(wr_decoder *h)
 {
     if (!h) return WR_OK;
-    for (int i = 0; i <= kMaxLook; ++i)
-        if (h->greedy_graph[i]) (void)hipGraphExecDestroy(h->greedy_graph[i]);
-    if (h->beam_graph) (void)hipGraphExecDestroy(h->beam_graph);
-    if (h->hw_graph) (void)hipGraphExecDestroy(h->hw_graph);
-    (void)hipStreamSynchronize(h->work);
+    for_each_graph(h, [](GraphSlot &g) { if (g.exec) (void)hipGraphExecDestroy(g.exec); });
+    if (h->work) (void)hipStreamSynchronize(h->work);
     if (h->h_active) (void)hipHostFree(h->h_active);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
-    for (int i = 0; i < kStageSlots; ++i) (void)hipEventDestroy(h->stage_ev[i]);
-    (void)hipEventDestroy(h->ev_in);
-    (void)hipEventDestroy(h->ev_out);
-    (void)hipStreamDestroy(h->work);
+    for (hipEvent_t ev : h->stage_ev) if (ev) (void)hipEventDestroy(ev);
+    if (h->ev_in) (void)hipEventDestroy(h->ev_in);
+    if (h->ev_out) (void)hipEventDestroy(h->ev_out);
+    if (h->work) (void)hipStreamDestroy(h->work);
     delete h;
     return WR_OK;
 }
@@ -2571,38 +2589,36 @@ LaneArgs lane_args(const wr_decoder *h)
 }
 
 template <bool HW>
-void launch_greedy_update(wr_decoder *h, int n_lanes, hipStream_t st)
+int launch_greedy_update(wr_decoder *h, int n_lanes, hipStream_t st)
 {
     const LaneArgs a = lane_args(h);
-    if ((h->d.V + 31) / 32 <= 3 * 64)              // records per lane of a wave: V <= 6144 -> 3, else 8 (V <= 16384)
-        hipLaunchKernelGGL((greedy_update_kernel<HW, 3>), dim3(n_lanes), dim3(256), 0, st, h->dev, a);
-    else
-        hipLaunchKernelGGL((greedy_update_kernel<HW, 8>), dim3(n_lanes), dim3(256), 0, st, h->dev, a);
+    const int recs = (h->d.V + 31) / 32 <= 3 * 64 ? 3 : 8;   // records per lane of a wave: V <= 6144 -> 3, else 8 (V <= 16384)
+    return with_int<3, 8>(recs, [&](auto r) {
+        return launch("greedy_update_kernel", greedy_update_kernel<HW, decltype(r)::value>, dim3(n_lanes), dim3(256), 0, st, h->dev, a);
+    });
 }
 
-void greedy_micro_step(wr_decoder *h, int n_lanes, hipStream_t st, int look)
+int greedy_micro_step(wr_decoder *h, int n_lanes, hipStream_t st, int look)
 {
-    launch_predictor_and_joint(h, n_lanes, st, look, look == 1);
+    WR_TRY(launch_predictor_and_joint(h, n_lanes, st, look, look == 1));
+    if (look == 1) return launch_greedy_update<false>(h, n_lanes, st);
     const int V = h->d.V;                           // <= 16384 (check_weights)
-    if (look == 1) {
-        launch_greedy_update<false>(h, n_lanes, st);
-        return;
-    }
-    const dim3 grid(n_lanes, look);
-    if (V <= 256 * 8) hipLaunchKernelGGL(greedy_rows_kernel<8>, grid, dim3(256), 0, st, h->dev);
-    else if (V <= 256 * 24) hipLaunchKernelGGL(greedy_rows_kernel<24>, grid, dim3(256), 0, st, h->dev);
-    else hipLaunchKernelGGL(greedy_rows_kernel<64>, grid, dim3(256), 0, st, h->dev);
-    hipLaunchKernelGGL(greedy_resolve_kernel, dim3(n_lanes), dim3(256), 0, st, h->dev, look);
+    const int per_thread = V <= 256 * 8 ? 8 : V <= 256 * 24 ? 24 : 64;
+    WR_TRY(with_int<8, 24, 64>(per_thread, [&](auto n) {
+        return launch("greedy_rows_kernel", greedy_rows_kernel<decltype(n)::value>, dim3(n_lanes, look), dim3(256), 0, st, h->dev);
+    }));
+    return launch("greedy_resolve_kernel", greedy_resolve_kernel, dim3(n_lanes), dim3(256), 0, st, h->dev, look);
 }
 
-void beam_frame(wr_decoder *h, int n_lanes, int n_utt, hipStream_t st)
+int beam_frame(wr_decoder *h, int n_lanes, int n_utt, hipStream_t st)
 {
-    launch_predictor_and_joint(h, n_lanes, st);
+    WR_TRY(launch_predictor_and_joint(h, n_lanes, st));
     const int V = h->d.V;                           // <= 16384 (check_weights)
-    if (V <= kTopkThreads * 4) hipLaunchKernelGGL(beam_topk_kernel<4>, dim3(n_lanes), dim3(kTopkThreads), 0, st, h->dev);
-    else if (V <= kTopkThreads * 10) hipLaunchKernelGGL(beam_topk_kernel<10>, dim3(n_lanes), dim3(kTopkThreads), 0, st, h->dev);
-    else hipLaunchKernelGGL(beam_topk_kernel<32>, dim3(n_lanes), dim3(kTopkThreads), 0, st, h->dev);
-    hipLaunchKernelGGL(beam_update_kernel, dim3(n_utt), dim3(kBeamUpdThreads), 0, st, h->dev);
+    const int per_thread = V <= kTopkThreads * 4 ? 4 : V <= kTopkThreads * 10 ? 10 : 32;
+    WR_TRY(with_int<4, 10, 32>(per_thread, [&](auto n) {
+        return launch("beam_topk_kernel", beam_topk_kernel<decltype(n)::value>, dim3(n_lanes), dim3(kTopkThreads), 0, st, h->dev);
+    }));
+    return launch("beam_update_kernel", beam_update_kernel, dim3(n_utt), dim3(kBeamUpdThreads), 0, st, h->dev);
 }
 
 // Order the decoder's work stream after everything already enqueued on the caller's stream ...
@@ -2628,18 +2644,31 @@ struct WorkScope {
     bool good = false;
     WorkScope(wr_decoder *h_, hipStream_t caller_) : h(h_), caller(caller_), st(enter(h_, caller_)) {}
     void ok() { good = true; }
-    ~WorkScope();
+    ~WorkScope()
+    {
+        if (!good) {
+            h->stream_lanes = -1;
+            for_each_graph(h, [](GraphSlot &g) { g.key = -1; });
+        }
+        leave(h, caller);
+    }
 };
 
-// Capture `reps` repetitions of `body` on `st` into an executable graph.
+// Capture `reps` repetitions of `body` on `st` into an executable graph.  A failing body still ends the capture; its
+// code is returned and no graph is kept.
 template <typename F>
 int capture(hipStream_t st, int reps, F body, hipGraphExec_t *out)
 {
     hipGraph_t g = nullptr;
     hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
     if (e != hipSuccess) { set_error("decoder: hipStreamBeginCapture failed: %s", hipGetErrorString(e)); return WR_ELAUNCH; }
-    for (int i = 0; i < reps; ++i) body();
+    int rc = WR_OK;
+    for (int i = 0; i < reps && rc == WR_OK; ++i) rc = body();
     e = hipStreamEndCapture(st, &g);
+    if (rc != WR_OK) {
+        if (g) (void)hipGraphDestroy(g);
+        return rc;
+    }
     if (e != hipSuccess || !g) { set_error("decoder: hipStreamEndCapture failed: %s", hipGetErrorString(e)); return WR_ELAUNCH; }
     e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
@@ -2647,18 +2676,44 @@ int capture(hipStream_t st, int reps, F body, hipGraphExec_t *out)
     return WR_OK;
 }
 
-}  // namespace
-
-namespace {
-WorkScope::~WorkScope()
+// make `slot` hold the graph of kStepsPerGraph repetitions of `body` for `key`
+template <typename F>
+int ensure_graph(GraphSlot &slot, int key, hipStream_t st, F body)
 {
-    if (!good) {
-        h->stream_lanes = -1;
-        for (int i = 0; i <= kMaxLook; ++i) h->greedy_graph_key[i] = -1;
-        h->beam_graph_lanes = -1;
-        h->hw_graph_key = -1;
+    if (slot.key == key) return WR_OK;
+    if (slot.exec) { (void)hipGraphExecDestroy(slot.exec); slot.exec = nullptr; }
+    WR_TRY(capture(st, kStepsPerGraph, body, &slot.exec));
+    slot.key = key;
+    return WR_OK;
+}
+
+// The polling loop of the two greedy searches (`what` names the entry point in the error texts): kStepsPerGraph steps
+// at a time -- replayed from the graph `slot()` holds for `key` when the handle uses graphs -- then the three counters
+// (lanes active, blank decisions, emissions) come back and `after_replay()` may look at them, until no lane is active.
+// Running out of `max_micro` steps is an error, not truncated hypotheses returned as WR_OK; `budget_note` ends its text.
+template <typename Slot, typename Step, typename After>
+int run_until_idle(wr_decoder *h, hipStream_t st, const char *what, int key, long max_micro, const char *budget_note, Slot slot,
+                   Step step, After after_replay)
+{
+    for (long done = 0; done < max_micro; done += kStepsPerGraph) {
+        if (h->use_graph) {
+            GraphSlot &g = slot();
+            WR_TRY(ensure_graph(g, key, st, step));
+            hipError_t e = hipGraphLaunch(g.exec, st);
+            if (e != hipSuccess) { set_error("%s: hipGraphLaunch failed: %s", what, hipGetErrorString(e)); return WR_ELAUNCH; }
+        } else {
+            for (int i = 0; i < kStepsPerGraph; ++i) WR_TRY(step());
+        }
+        // the reference synchronises on every step (.item()); we do once per kStepsPerGraph micro-steps
+        (void)hipMemcpyAsync(h->h_active, h->host.active_count, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+        hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { set_error("%s: stream error: %s", what, hipGetErrorString(e)); return WR_ELAUNCH; }
+        if (h->h_active[0] <= 0) break;
+        after_replay();
     }
-    leave(h, caller);
+    WR_REQUIRE(h->h_active[0] <= 0, WR_ELAUNCH, "%s: %d streams still active after %ld micro-steps%s", what, h->h_active[0],
+               max_micro, budget_note);
+    return WR_OK;
 }
 
 // mode 0: fresh utterances; 1: next chunk, keep the pending predictor state; 2: next chunk, reference quirk
@@ -2680,49 +2735,28 @@ int greedy_run(wr_decoder *h, const float *enc_out_d, const int32_t *enc_lens_d,
     if (int rc = upload_state(h, st)) return rc;
     (void)hipMemsetAsync(s.active_count, 0, 3 * sizeof(int32_t), st);    // lanes active, blank decisions, emissions
     (void)hipMemsetAsync(s.lane_active, 0, sizeof(int32_t) * h->d.NLp, st);
-    hipLaunchKernelGGL(ep_all_kernel, dim3((unsigned)(((long)N * T + 7) / 8)), dim3(256), (size_t)8 * h->d.E * sizeof(float), st,
-                       h->dev, enc_out_d, s.ep_all);
-    if (mode == 0) hipLaunchKernelGGL(greedy_init_kernel, dim3(N), dim3(128), 0, st, h->dev);
-    else hipLaunchKernelGGL(greedy_chunk_init_kernel, dim3(N), dim3(128), 0, st, h->dev, mode == 2 ? 1 : 0);
-    WR_CHECK_LAUNCH("greedy_init");
+    WR_TRY(launch_ep_all(h, st, (long)N * T, enc_out_d, s.ep_all));
+    if (mode == 0) WR_TRY(launch("greedy_init_kernel", greedy_init_kernel, dim3(N), dim3(128), 0, st, h->dev));
+    else WR_TRY(launch("greedy_chunk_init_kernel", greedy_chunk_init_kernel, dim3(N), dim3(128), 0, st, h->dev, mode == 2 ? 1 : 0));
     h->stream_lanes = N;
     // look-ahead per replay: fixed, or (h->look == 0) chosen from the share of blank decisions in the previous
     // replay -- any value gives the same tokens, so switching between replays is safe
     int look = h->look > 0 ? h->look : 1;
     int prev_blank = 0, prev_emit = 0;
+    // every micro-step emits (at most n_steps per frame) or advances the frame, so the budget cannot run out
     const long max_micro = (long)T * ((long)n_steps + 1) + 1;
-    for (long done = 0; done < max_micro; done += kStepsPerGraph) {
-        if (h->use_graph) {
-            if (h->greedy_graph_key[look] != N) {
-                if (h->greedy_graph[look]) { (void)hipGraphExecDestroy(h->greedy_graph[look]); h->greedy_graph[look] = nullptr; }
-                if (int rc = capture(st, kStepsPerGraph, [&] { greedy_micro_step(h, N, st, look); }, &h->greedy_graph[look]))
-                    return rc;
-                h->greedy_graph_key[look] = N;
-            }
-            hipError_t e = hipGraphLaunch(h->greedy_graph[look], st);
-            if (e != hipSuccess) { set_error("greedy_search: hipGraphLaunch failed: %s", hipGetErrorString(e)); return WR_ELAUNCH; }
-        } else {
-            for (int i = 0; i < kStepsPerGraph; ++i) greedy_micro_step(h, N, st, look);
-        }
-        // the reference synchronises on every step (.item()); we do once per kStepsPerGraph micro-steps
-        (void)hipMemcpyAsync(h->h_active, s.active_count, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-        hipError_t e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { set_error("greedy_search: stream error: %s", hipGetErrorString(e)); return WR_ELAUNCH; }
-        if (h->h_active[0] <= 0) break;
-        if (h->look == 0) {
+    WR_TRY(run_until_idle(
+        h, st, "greedy_search", N, max_micro, "", [&]() -> GraphSlot & { return h->greedy[look]; },
+        [&] { return greedy_micro_step(h, N, st, look); },
+        [&] {
+            if (h->look != 0) return;
             const int nb = h->h_active[1] - prev_blank, ne = h->h_active[2] - prev_emit;
             prev_blank = h->h_active[1]; prev_emit = h->h_active[2];
             const float share = (nb + ne) > 0 ? (float)nb / (float)(nb + ne) : 0.f;
             look = share >= 0.75f ? 4 : share >= 0.62f ? 2 : 1;
             // beyond ~256 joiner rows a micro-step is matrix-core bound and extra frames are no longer free
             while (look > 1 && look * N > 256) look >>= 1;
-        }
-    }
-    WR_CHECK_LAUNCH("greedy_search");
-    // every micro-step emits (at most n_steps per frame) or advances the frame, so the budget cannot run out; if it ever
-    // does, say so instead of returning truncated hypotheses as WR_OK
-    WR_REQUIRE(h->h_active[0] <= 0, WR_ELAUNCH, "greedy_search: %d streams still active after %ld micro-steps",
-               h->h_active[0], max_micro);
+        }));
     scope.ok();
     return WR_OK;
 }
@@ -2766,26 +2800,19 @@ extern "C" int wr_prefix_beam_search(wr_decoder *h, const float *enc_out_d, cons
     if (int rc = upload_state(h, st)) return rc;
     (void)hipMemsetAsync(s.lane_active, 0, sizeof(int32_t) * h->d.NLp, st);
     const int NLn = B * beam;
-    hipLaunchKernelGGL(ep_all_kernel, dim3((unsigned)(((long)B * T + 7) / 8)), dim3(256), (size_t)8 * h->d.E * sizeof(float), st,
-                       h->dev, enc_out_d, s.ep_all);
-    hipLaunchKernelGGL(beam_init_kernel, dim3(NLn), dim3(128), 0, st, h->dev);
-    WR_CHECK_LAUNCH("beam_init");
-    const int key = NLn * 1000 + beam;
-    if (h->use_graph_beam && h->beam_graph_lanes != key) {
-        if (h->beam_graph) { (void)hipGraphExecDestroy(h->beam_graph); h->beam_graph = nullptr; }
-        if (int rc = capture(st, kStepsPerGraph, [&] { beam_frame(h, NLn, B, st); }, &h->beam_graph)) return rc;
-        h->beam_graph_lanes = key;
-    }
+    WR_TRY(launch_ep_all(h, st, (long)B * T, enc_out_d, s.ep_all));
+    WR_TRY(launch("beam_init_kernel", beam_init_kernel, dim3(NLn), dim3(128), 0, st, h->dev));
+    const auto frame = [&] { return beam_frame(h, NLn, B, st); };
+    if (h->use_graph_beam) WR_TRY(ensure_graph(h->beam, NLn * 1000 + beam, st, frame));
     for (int f = 0; f < T; f += kStepsPerGraph) {
         if (h->use_graph_beam) {
-            hipError_t e = hipGraphLaunch(h->beam_graph, st);
+            hipError_t e = hipGraphLaunch(h->beam.exec, st);
             if (e != hipSuccess) { set_error("prefix_beam_search: hipGraphLaunch failed: %s", hipGetErrorString(e)); return WR_ELAUNCH; }
         } else {
-            for (int i = 0; i < kStepsPerGraph; ++i) beam_frame(h, NLn, B, st);
+            for (int i = 0; i < kStepsPerGraph; ++i) WR_TRY(frame());
         }
     }
-    hipLaunchKernelGGL(beam_export_kernel, dim3(B), dim3(256), 0, st, h->dev, hyps_d, hyp_lens_d, scores_d, n_hyps_d);
-    WR_CHECK_LAUNCH("prefix_beam_search");
+    WR_TRY(launch("beam_export_kernel", beam_export_kernel, dim3(B), dim3(256), 0, st, h->dev, hyps_d, hyp_lens_d, scores_d, n_hyps_d));
     scope.ok();
     return WR_OK;
 }
@@ -2861,27 +2888,31 @@ extern "C" int wr_predictor_step(wr_decoder *h, const int32_t *tokens_d, const f
     DevState &s = h->host;
     s.n_utt = 1; s.T = 1; s.lanes_per_utt = d.NL; s.n_lanes = N; s.enc = nullptr; s.enc_lens = nullptr;
     if (int rc = upload_state(h, st)) return rc;
-    hipLaunchKernelGGL(step_setup_kernel, dim3(d.NLp), dim3(64), 0, st, h->dev, tokens_d, N);
+    // row-major [L][N][H] -> k-major and back, 64 workgroups
+    const auto to_kmajor = [&](const float *src, float *dst) {
+        return launch("cache_to_kmajor_kernel", cache_to_kmajor_kernel, dim3(64), dim3(256), 0, st, src, N, d.L, d.H, d.Hp, d.NLp, dst);
+    };
+    const auto from_kmajor = [&](const float *src, float *dst) {
+        return launch("cache_from_kmajor_kernel", cache_from_kmajor_kernel, dim3(64), dim3(256), 0, st, src, N, d.L, d.H, d.Hp, d.NLp, dst);
+    };
+    WR_TRY(launch("step_setup_kernel", step_setup_kernel, dim3(d.NLp), dim3(64), 0, st, h->dev, tokens_d, N));
     if (d.ptype == kPredLstm) {
         // the caller's state becomes the lanes' committed slots: cell states as they are, hidden states through their
         // recurrent products (pool_g = W_hh . h + b, one GEMM per layer); then layer 0, layers >= 1, projection
-        hipLaunchKernelGGL(cache_to_kmajor_kernel, dim3(64), dim3(256), 0, st, cache_h_d, N, d.L, d.H, d.Hp, d.NLp, s.new_hT);
-        hipLaunchKernelGGL(pool_c_import_kernel, dim3(64), dim3(256), 0, st, h->dev, cache_c_d, N);
-        for (int l = 0; l < d.L; ++l) launch_gemm<kEpiSlotRow>(recurrent_job(h, l, N, s.comm_slot), d.G4p, N, st);
-        hipLaunchKernelGGL(lstm_layer0_kernel, dim3(N), dim3(256), 0, st, h->dev);
+        WR_TRY(to_kmajor(cache_h_d, s.new_hT));
+        WR_TRY(launch("pool_c_import_kernel", pool_c_import_kernel, dim3(64), dim3(256), 0, st, h->dev, cache_c_d, N));
+        for (int l = 0; l < d.L; ++l) WR_TRY(launch_gemm<kEpiSlotRow>(recurrent_job(h, l, N, s.comm_slot), d.G4p, N, st));
+        WR_TRY(launch("lstm_layer0_kernel", lstm_layer0_kernel, dim3(N), dim3(256), 0, st, h->dev));
     } else {
-        hipLaunchKernelGGL(cache_to_kmajor_kernel, dim3(64), dim3(256), 0, st, cache_h_d, N, d.L, d.H, d.Hp, d.NLp, s.cache_hT);
-        hipLaunchKernelGGL(cache_to_kmajor_kernel, dim3(64), dim3(256), 0, st, cache_c_d, N, d.L, d.H, d.Hp, d.NLp, s.cache_cT);
+        WR_TRY(to_kmajor(cache_h_d, s.cache_hT));
+        WR_TRY(to_kmajor(cache_c_d, s.cache_cT));
     }
-    launch_predictor(h, N, st);
+    WR_TRY(launch_predictor(h, N, st));
     // outT [Pp][NLp] -> out [N][P]: the same index map with L = 1
-    hipLaunchKernelGGL(cache_from_kmajor_kernel, dim3(32), dim3(256), 0, st, s.outT, N, 1, d.P, d.Pp, d.NLp, out_d);
-    hipLaunchKernelGGL(cache_from_kmajor_kernel, dim3(64), dim3(256), 0, st, s.new_hT, N, d.L, d.H, d.Hp, d.NLp, new_h_d);
-    if (d.ptype == kPredLstm)
-        hipLaunchKernelGGL(pool_c_export_kernel, dim3(64), dim3(256), 0, st, h->dev, new_c_d, N);
-    else
-        hipLaunchKernelGGL(cache_from_kmajor_kernel, dim3(64), dim3(256), 0, st, s.new_cT, N, d.L, d.H, d.Hp, d.NLp, new_c_d);
-    WR_CHECK_LAUNCH("predictor_step");
+    WR_TRY(launch("cache_from_kmajor_kernel", cache_from_kmajor_kernel, dim3(32), dim3(256), 0, st, s.outT, N, 1, d.P, d.Pp, d.NLp, out_d));
+    WR_TRY(from_kmajor(s.new_hT, new_h_d));
+    if (d.ptype == kPredLstm) WR_TRY(launch("pool_c_export_kernel", pool_c_export_kernel, dim3(64), dim3(256), 0, st, h->dev, new_c_d, N));
+    else WR_TRY(from_kmajor(s.new_cT, new_c_d));
     scope.ok();
     return WR_OK;
 }
@@ -2889,35 +2920,38 @@ extern "C" int wr_predictor_step(wr_decoder *h, const int32_t *tokens_d, const f
 // ------------------------------------------------------------ hot-word greedy: host side --
 namespace {
 
-struct HwCarve {
-    size_t q_wt, o_wt, c_wt, kbuf[2], vbuf[2], cold_c, mqT[2], mq_c[2], noT[2], c1p_wt, c1p_b, cold_cp, mqpT[2], mqp_c[2], gate_tab,
-        ep2, state, biasT, total;
+// where the hot-word workspace puts things: the device struct's own buffers, and what the handle keeps beside it
+struct HwPlace {
+    HwDev hw;
+    float *q_wt, *o_wt, *c_wt;    // the k-major weights, writable (hw holds them const)
+    float *ep2, *biasT;
+    int32_t *state;
 };
 
-HwCarve hw_carve(const wr_decoder *h, int D, int max_ctx)
+// one pass for the size (null base) and for the pointers; every take is 256-byte aligned
+size_t hw_carve(const wr_decoder *h, int D, int max_ctx, char *base, HwPlace *p)
 {
-    HwCarve c;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = align_up(off, 256); off = o + bytes; return o; };
+    Carver c{base, 0};
     const Dims &d = h->d;
-    c.q_wt = take((size_t)D * D * sizeof(float));
-    c.o_wt = take((size_t)D * D * sizeof(float));
-    c.c_wt = take((size_t)2 * D * D * sizeof(float));
-    for (int i = 0; i < 2; ++i) { c.kbuf[i] = take((size_t)max_ctx * D * sizeof(float)); c.vbuf[i] = take((size_t)max_ctx * D * sizeof(float)); }
-    c.cold_c = take((size_t)D * sizeof(float));
+    HwDev &v = p->hw;
+    const size_t DD = (size_t)D * D, frames = (size_t)h->max_utt * h->Tmax;
+    v.q_wt = p->q_wt = c.take<float>(DD);
+    v.o_wt = p->o_wt = c.take<float>(DD);
+    v.c_wt = p->c_wt = c.take<float>(2 * DD);
+    for (int i = 0; i < 2; ++i) { v.kbuf[i] = c.take<float>((size_t)max_ctx * D); v.vbuf[i] = c.take<float>((size_t)max_ctx * D); }
+    v.cold_c = c.take<float>(D);
     for (int i = 0; i < 2; ++i) {
-        c.mqT[i] = take((size_t)D * D * sizeof(float)); c.mq_c[i] = take((size_t)D * sizeof(float));
-        c.noT[i] = take((size_t)D * D * sizeof(float));
-        c.mqpT[i] = take((size_t)d.Hp * D * sizeof(float)); c.mqp_c[i] = take((size_t)D * sizeof(float));
+        v.mqT[i] = c.take<float>(DD); v.mq_c[i] = c.take<float>(D);
+        v.noT[i] = c.take<float>(DD);
+        v.mqpT[i] = c.take<float>((size_t)d.Hp * D); v.mqp_c[i] = c.take<float>(D);
     }
-    c.c1p_wt = take((size_t)d.Hp * D * sizeof(float)); c.c1p_b = take((size_t)D * sizeof(float));
-    c.cold_cp = take((size_t)D * sizeof(float));
-    c.gate_tab = take((size_t)h->max_utt * h->Tmax * sizeof(int32_t));
-    c.ep2 = take((size_t)2 * h->max_utt * h->Tmax * d.J * sizeof(float));
-    c.state = take((size_t)4 * d.NLp * sizeof(int32_t));
-    c.biasT = take((size_t)d.Pp * d.NLp * sizeof(float));
-    c.total = align_up(off, 256);
-    return c;
+    v.c1p_wt = c.take<float>((size_t)d.Hp * D); v.c1p_b = c.take<float>(D);
+    v.cold_cp = c.take<float>(D);
+    v.gate_tab = c.take<int32_t>(frames);
+    p->ep2 = c.take<float>(2 * frames * d.J);
+    v.cur_gate = p->state = c.take<int32_t>((size_t)4 * d.NLp);      // cur_gate is the first NLp words of the state
+    p->biasT = c.take<float>((size_t)d.Pp * d.NLp);
+    return align_up(c.off, 256);
 }
 
 int hw_check(const wr_decoder *h, const wr_hotword_weights *hw, int max_ctx)
@@ -2941,39 +2975,18 @@ int hw_check(const wr_decoder *h, const wr_hotword_weights *hw, int max_ctx)
     return WR_OK;
 }
 
-void hw_micro_step(wr_decoder *h, int n_lanes, hipStream_t st)
+int hw_micro_step(wr_decoder *h, int n_lanes, hipStream_t st)
 {
     const Dims &d = h->d;
-    const DevState &s = h->host;
-    auto up = [](int x, int m) { return (x + m - 1) / m * m; };
     // LSTM predictor: the projection runs inside hw_bias_kernel; stateless predictors write outT themselves
-    const bool recurrent_pending = launch_predictor(h, n_lanes, st, d.ptype != kPredLstm);
-    const size_t lds = (size_t)(21 * h->hw.D + h->hw.heads * h->hw.max_ctx) * sizeof(float);
-    hipLaunchKernelGGL(hw_bias_kernel, dim3(n_lanes), dim3(kHwThreads), lds, st, h->dev, h->hw);
-    {   // pred_ffn of the biased predictor output; the joiner activation takes the encoder stream the gate selected
-        GemmArgs g{};
-        g.A0 = h->hw_biasT; g.B0 = s.predffn_wt; g.K0 = d.Pp;
-        g.lda = d.NLp; g.ldb = up(d.J, 32); g.bias = s.predffn_b; g.C = s.ht; g.ldc = kMaxLook * d.NLp; g.N = d.J; g.n_lanes = n_lanes;
-        g.st = h->dev; g.lane_active = s.lane_active; g.lane_t = s.lane_t; g.ep_all = h->hw_ep2; g.J = d.J;
-        g.look = 1; g.lane_stride = d.NLp; g.act = d.act;
-        g.ep_gate = h->hw_state; g.ep_gate_stride = (size_t)h->max_utt * h->Tmax * d.J;
-#ifdef WR_STAMPS
-        g.dbg_slot = 2;
-#endif
-        if (recurrent_pending)
-            launch_gemm_pair<kEpiJointAct, kEpiSlotRow>(g, up(d.J, 32), recurrent_job(h, d.L - 1, n_lanes, s.new_slot), d.G4p, n_lanes, st);
-        else
-            launch_gemm<kEpiJointAct>(g, up(d.J, 32), n_lanes, st);
-    }
-    GemmArgs g{};
-#ifdef WR_STAMPS
-    g.dbg_slot = 3;
-#endif
-    g.A0 = s.ht; g.B0 = s.out_wt; g.K0 = d.Jp;
-    g.lda = kMaxLook * d.NLp; g.ldb = d.Vp; g.bias = s.out_b; g.C = s.logits; g.ldc = d.V; g.N = d.V; g.n_lanes = n_lanes;
-    g.row_part = s.row_part; g.row_part_ld = s.n_cb;
-    launch_gemm<kEpiRowStats>(g, d.Vp, n_lanes, st);
-    launch_greedy_update<true>(h, n_lanes, st);
+    bool recurrent_pending = false;
+    WR_TRY(launch_predictor(h, n_lanes, st, d.ptype != kPredLstm, &recurrent_pending));
+    const size_t lds = (size_t)(21 * h->hw.D + h->hw.heads * h->hw.max_ctx) * sizeof(float);   // <= 60 KiB (hw_check)
+    WR_TRY(launch("hw_bias_kernel", hw_bias_kernel, dim3(n_lanes), dim3(kHwThreads), lds, st, h->dev, h->hw));
+    // pred_ffn of the biased predictor output; the joiner activation takes the encoder stream the gate selected
+    WR_TRY(launch_pred_ffn(h, pred_ffn_job(h, h->hw_biasT, false, n_lanes, 1, h->hw_ep2, h->hw_state), recurrent_pending, n_lanes, st));
+    WR_TRY(launch_gemm<kEpiRowStats>(joint_out_job(h, n_lanes, true), d.Vp, n_lanes, st));
+    return launch_greedy_update<true>(h, n_lanes, st);
 }
 
 }  // namespace
@@ -2981,7 +2994,8 @@ void hw_micro_step(wr_decoder *h, int n_lanes, hipStream_t st)
 extern "C" size_t wr_hotword_workspace_bytes(const wr_decoder *h, const wr_hotword_weights *hw, int max_ctx)
 {
     if (!h || !hw || hw->dim <= 0 || max_ctx <= 0) return 0;
-    return hw_carve(h, hw->dim, max_ctx).total;
+    HwPlace p{};
+    return hw_carve(h, hw->dim, max_ctx, nullptr, &p);
 }
 
 extern "C" int wr_decoder_attach_hotword(wr_decoder *h, const wr_hotword_weights *hw, int max_ctx, void *workspace_d,
@@ -2989,59 +3003,36 @@ extern "C" int wr_decoder_attach_hotword(wr_decoder *h, const wr_hotword_weights
 {
     if (int rc = hw_check(h, hw, max_ctx)) return rc;
     WR_REQUIRE(workspace_d != nullptr, WR_EINVAL, "decoder_attach_hotword: null workspace");
-    const HwCarve c = hw_carve(h, hw->dim, max_ctx);
-    WR_REQUIRE(workspace_bytes >= c.total, WR_EWORKSPACE, "decoder_attach_hotword: workspace %zu < required %zu", workspace_bytes,
-               c.total);
+    HwPlace p{};                                  // the handle is written only once everything here has succeeded
+    const size_t need = hw_carve(h, hw->dim, max_ctx, static_cast<char *>(workspace_d), &p);
+    WR_REQUIRE(workspace_bytes >= need, WR_EWORKSPACE, "decoder_attach_hotword: workspace %zu < required %zu", workspace_bytes,
+               need);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char *ws = static_cast<char *>(workspace_d);
     const int D = hw->dim;
-    HwDev &v = h->hw;
+    const Dims &d = h->d;
+    HwDev &v = p.hw;
     v.D = D; v.heads = hw->heads; v.HW = hw->hw_dim; v.NLAB = hw->n_labels; v.max_ctx = max_ctx;
-    float *q_wt = reinterpret_cast<float *>(ws + c.q_wt), *o_wt = reinterpret_cast<float *>(ws + c.o_wt);
-    float *c_wt = reinterpret_cast<float *>(ws + c.c_wt);
-    launch_transpose(hw->q_w, D, D, D, D, q_wt, st);                  // [out][in] -> [in][out]
-    launch_transpose(hw->o_w, D, D, D, D, o_wt, st);
-    launch_transpose(hw->combine_w, D, 2 * D, D, 2 * D, c_wt, st);    // [D][2D] -> [2D][D]
-    WR_CHECK_LAUNCH("decoder_attach_hotword (weight transposes)");
-    v.q_wt = q_wt; v.q_b = hw->q_b; v.k_w = hw->k_w; v.k_b = hw->k_b; v.v_w = hw->v_w; v.v_b = hw->v_b;
-    v.o_wt = o_wt; v.o_b = hw->o_b; v.bn_w = hw->bias_norm_w; v.bn_b = hw->bias_norm_b;
-    v.c_wt = c_wt; v.c_b = hw->combine_b; v.on_w = hw->out_norm_w; v.on_b = hw->out_norm_b;
+    WR_TRY(launch_transpose(hw->q_w, D, D, D, D, p.q_wt, st));                  // [out][in] -> [in][out]
+    WR_TRY(launch_transpose(hw->o_w, D, D, D, D, p.o_wt, st));
+    WR_TRY(launch_transpose(hw->combine_w, D, 2 * D, D, 2 * D, p.c_wt, st));    // [D][2D] -> [2D][D]
+    v.q_b = hw->q_b; v.k_w = hw->k_w; v.k_b = hw->k_b; v.v_w = hw->v_w; v.v_b = hw->v_b;
+    v.o_b = hw->o_b; v.bn_w = hw->bias_norm_w; v.bn_b = hw->bias_norm_b;
+    v.c_b = hw->combine_b; v.on_w = hw->out_norm_w; v.on_b = hw->out_norm_b;
     v.he_w = hw->hw_enc_w; v.he_b = hw->hw_enc_b; v.hv_w = hw->hw_v_w; v.hv_b = hw->hw_v_b; v.ho_w = hw->hw_o_w;
     v.ho_b = hw->hw_o_b; v.hn_w = hw->hw_norm_w; v.hn_b = hw->hw_norm_b; v.hl_w = hw->hw_out_w; v.hl_b = hw->hw_out_b;
-    for (int i = 0; i < 2; ++i) {
-        v.kbuf[i] = reinterpret_cast<float *>(ws + c.kbuf[i]);
-        v.vbuf[i] = reinterpret_cast<float *>(ws + c.vbuf[i]);
-    }
-    v.cold_c = reinterpret_cast<float *>(ws + c.cold_c);
-    for (int i = 0; i < 2; ++i) {
-        v.mqT[i] = reinterpret_cast<float *>(ws + c.mqT[i]); v.mq_c[i] = reinterpret_cast<float *>(ws + c.mq_c[i]);
-        v.noT[i] = reinterpret_cast<float *>(ws + c.noT[i]);
-        v.mqpT[i] = reinterpret_cast<float *>(ws + c.mqpT[i]); v.mqp_c[i] = reinterpret_cast<float *>(ws + c.mqp_c[i]);
-    }
     v.lane_active = h->host.lane_active; v.need_pred = h->host.need_pred;
-    v.cur_gate = reinterpret_cast<const int32_t *>(ws + c.state);          // = h->hw_state (cur_gate is its first NLp words)
-    v.c1p_wt = reinterpret_cast<float *>(ws + c.c1p_wt); v.c1p_b = reinterpret_cast<float *>(ws + c.c1p_b);
-    v.cold_cp = reinterpret_cast<float *>(ws + c.cold_cp);
-    {
-        const Dims &dd = h->d;
-        auto up32 = [](int x) { return (x + 31) / 32 * 32; };
-        v.proj_wt = dd.ptype == kPredLstm ? h->host.proj_wt : nullptr; v.proj_b = h->host.proj_b;
-        v.h_lastT = h->host.new_hT + (size_t)(dd.L - 1) * dd.Hp * dd.NLp;
-        v.Hp = dd.Hp; v.P = dd.P; v.proj_ld = up32(dd.P); v.NLp = dd.NLp;
-        if (v.proj_wt != nullptr && dd.Hp <= D) {
-            const long nn = (long)dd.Hp * D + D;
-            hipLaunchKernelGGL(hw_compose_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, hw->combine_w, hw->combine_b,
-                               v.proj_wt, v.proj_b, D, dd.P, dd.H, dd.Hp, v.proj_ld, v.c1p_wt, v.c1p_b);
-            WR_CHECK_LAUNCH("decoder_attach_hotword (composed projection)");
-        }
+    v.proj_wt = d.ptype == kPredLstm ? h->host.proj_wt : nullptr; v.proj_b = h->host.proj_b;
+    v.h_lastT = h->host.new_hT + (size_t)(d.L - 1) * d.Hp * d.NLp;
+    v.Hp = d.Hp; v.P = d.P; v.proj_ld = round_up(d.P, 32); v.NLp = d.NLp;
+    if (v.proj_wt != nullptr && d.Hp <= D) {
+        const long nn = (long)d.Hp * D + D;
+        WR_TRY(launch("hw_compose_kernel", hw_compose_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, hw->combine_w,
+                      hw->combine_b, v.proj_wt, v.proj_b, D, d.P, d.H, d.Hp, v.proj_ld, v.c1p_wt, v.c1p_b));
     }
-    v.gate_tab = reinterpret_cast<int32_t *>(ws + c.gate_tab);
-    h->hw_ep2 = reinterpret_cast<float *>(ws + c.ep2);
-    h->hw_state = reinterpret_cast<int32_t *>(ws + c.state);
-    h->hw_biasT = reinterpret_cast<float *>(ws + c.biasT);
-    (void)hipMemsetAsync(h->hw_biasT, 0, (size_t)h->d.Pp * h->d.NLp * sizeof(float), st);   // padded rows / lanes stay zero
+    (void)hipMemsetAsync(p.biasT, 0, (size_t)d.Pp * d.NLp * sizeof(float), st);   // padded rows / lanes stay zero
+    h->hw = p.hw; h->hw_ep2 = p.ep2; h->hw_state = p.state; h->hw_biasT = p.biasT;
     h->hw_attached = true;
-    h->hw_graph_key = -1;
+    h->hotword.key = -1;
     return WR_OK;
 }
 
@@ -3063,12 +3054,13 @@ extern "C" int wr_greedy_search_hotword(wr_decoder *h, const float *enc_hot_d, c
     WorkScope scope(h, static_cast<hipStream_t>(stream));
     hipStream_t st = scope.st;
     const Dims &d = h->d;
+    const HwDev &hw = h->hw;
     DevState &s = h->host;
     s.enc = enc_hot_d; s.enc_lens = enc_lens_d; s.ctc_logp = nullptr;
     s.n_utt = N; s.T = T; s.lanes_per_utt = 1; s.n_lanes = N;
     s.hyps = hyps_d; s.hyp_lens = hyp_lens_d; s.max_hyp = h->max_hyp; s.n_steps = n_steps; s.blank = blank; s.beam = 1;
     s.hw_on = 1; s.hw_filter = filter_on ? 1 : 0; s.hw_nctx[0] = n_ctx_cold; s.hw_nctx[1] = n_ctx_hot;
-    s.gate_tab = h->hw.gate_tab;
+    s.gate_tab = hw.gate_tab;
     s.cur_gate = h->hw_state; s.gb_flag = h->hw_state + d.NLp; s.gb_end = h->hw_state + 2 * d.NLp; s.last_t = h->hw_state + 3 * d.NLp;
     s.trace = trace_d; s.trace_len = trace_lens_d; s.trace_cap = trace_cap;
     s.biasT = h->hw_biasT;
@@ -3078,46 +3070,27 @@ extern "C" int wr_greedy_search_hotword(wr_decoder *h, const float *enc_hot_d, c
     (void)hipMemsetAsync(s.active_count, 0, 3 * sizeof(int32_t), st);
     (void)hipMemsetAsync(s.lane_active, 0, sizeof(int32_t) * d.NLp, st);
     // loop-invariant work: list projections, the gate of every frame, enc_ffn of both encoder streams
-    hipLaunchKernelGGL(hw_kv_kernel, dim3(n_ctx_cold, 2), dim3(256), 0, st, h->hw, hidden_cold_d, 0);
-    hipLaunchKernelGGL(hw_kv_kernel, dim3(n_ctx_hot, 2), dim3(256), 0, st, h->hw, hidden_hot_d, 1);
+    WR_TRY(launch("hw_kv_kernel", hw_kv_kernel, dim3(n_ctx_cold, 2), dim3(256), 0, st, hw, hidden_cold_d, 0));
+    WR_TRY(launch("hw_kv_kernel", hw_kv_kernel, dim3(n_ctx_hot, 2), dim3(256), 0, st, hw, hidden_hot_d, 1));
     {   // short lists: fold the query / output projections into K / V once per call
         const int nc[2] = {n_ctx_cold, n_ctx_hot};
         for (int i = 0; i < 2; ++i)
-            if (nc[i] > 1 && h->hw.heads * nc[i] <= h->hw.D)
-                hipLaunchKernelGGL(hw_fold_kernel, dim3(h->hw.heads * nc[i]), dim3(256), 0, st, h->hw, i, nc[i]);
+            if (nc[i] > 1 && hw.heads * nc[i] <= hw.D)
+                WR_TRY(launch("hw_fold_kernel", hw_fold_kernel, dim3(hw.heads * nc[i]), dim3(256), 0, st, hw, i, nc[i]));
     }
     if (n_ctx_cold == 1)
-        hipLaunchKernelGGL(hw_cold_kernel, dim3(1), dim3(kHwThreads), (size_t)(3 + kHwThreads / 64) * h->hw.D * sizeof(float), st, h->hw);
-    hipLaunchKernelGGL(hw_gate_table_kernel, dim3((unsigned)((long)N * T)), dim3(256),
-                       (size_t)(h->hw.D + 2 * h->hw.HW) * sizeof(float), st, h->hw, enc_feat_d, (long)N * T);
-    const size_t ep_stride = (size_t)h->max_utt * h->Tmax * d.J;
-    const dim3 ep_grid((unsigned)(((long)N * T + 7) / 8));
-    hipLaunchKernelGGL(ep_all_kernel, ep_grid, dim3(256), (size_t)8 * d.E * sizeof(float), st, h->dev, enc_cold_d, h->hw_ep2);
-    hipLaunchKernelGGL(ep_all_kernel, ep_grid, dim3(256), (size_t)8 * d.E * sizeof(float), st, h->dev, enc_hot_d, h->hw_ep2 + ep_stride);
-    hipLaunchKernelGGL(greedy_hw_init_kernel, dim3(N), dim3(128), 0, st, h->dev);
-    WR_CHECK_LAUNCH("greedy_search_hotword (setup)");
+        WR_TRY(launch("hw_cold_kernel", hw_cold_kernel, dim3(1), dim3(kHwThreads), (size_t)(3 + kHwThreads / 64) * hw.D * sizeof(float),
+                      st, hw));
+    WR_TRY(launch("hw_gate_table_kernel", hw_gate_table_kernel, dim3((unsigned)((long)N * T)), dim3(256),
+                  (size_t)(hw.D + 2 * hw.HW) * sizeof(float), st, hw, enc_feat_d, (long)N * T));
+    WR_TRY(launch_ep_all(h, st, (long)N * T, enc_cold_d, h->hw_ep2));
+    WR_TRY(launch_ep_all(h, st, (long)N * T, enc_hot_d, h->hw_ep2 + (size_t)h->max_utt * h->Tmax * d.J));
+    WR_TRY(launch("greedy_hw_init_kernel", greedy_hw_init_kernel, dim3(N), dim3(128), 0, st, h->dev));
     // every go-back re-decodes frames, at most once per 0 -> 1 flip of the gate: twice the plain loop's bound
     const long max_micro = 2 * ((long)T * ((long)n_steps + 2) + 1);
-    for (long done = 0; done < max_micro; done += kStepsPerGraph) {
-        if (h->use_graph) {
-            if (h->hw_graph_key != N) {
-                if (h->hw_graph) { (void)hipGraphExecDestroy(h->hw_graph); h->hw_graph = nullptr; }
-                if (int rc = capture(st, kStepsPerGraph, [&] { hw_micro_step(h, N, st); }, &h->hw_graph)) return rc;
-                h->hw_graph_key = N;
-            }
-            hipError_t e = hipGraphLaunch(h->hw_graph, st);
-            if (e != hipSuccess) { set_error("greedy_search_hotword: hipGraphLaunch failed: %s", hipGetErrorString(e)); return WR_ELAUNCH; }
-        } else {
-            for (int i = 0; i < kStepsPerGraph; ++i) hw_micro_step(h, N, st);
-        }
-        (void)hipMemcpyAsync(h->h_active, s.active_count, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-        hipError_t e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { set_error("greedy_search_hotword: stream error: %s", hipGetErrorString(e)); return WR_ELAUNCH; }
-        if (h->h_active[0] <= 0) break;
-    }
-    WR_CHECK_LAUNCH("greedy_search_hotword");
-    WR_REQUIRE(h->h_active[0] <= 0, WR_ELAUNCH, "greedy_search_hotword: %d streams still active after %ld micro-steps "
-               "(go-backs exceeded the budget); hypotheses are incomplete", h->h_active[0], max_micro);
+    WR_TRY(run_until_idle(
+        h, st, "greedy_search_hotword", N, max_micro, " (go-backs exceeded the budget); hypotheses are incomplete",
+        [&]() -> GraphSlot & { return h->hotword; }, [&] { return hw_micro_step(h, N, st); }, [] {}));
     scope.ok();
     return WR_OK;
 }

@@ -20,6 +20,7 @@
 // on equality or when a comparison involves a NaN the blank predecessor wins.  The value is NaN if either candidate is
 // NaN, so a NaN anywhere on the reachable lattice reaches the score, while the decisions still form a monotone path.
 #include "wr_common.hpp"
+#include "wr_launch.hpp"
 
 namespace wr {
 namespace {
@@ -138,11 +139,9 @@ int check_align(const char *what, int B, int Tmax, int U1max)
 int launch_viterbi(const RnntWs &w, char *ws, const int32_t *llens, const int32_t *tlens, int B, int Tmax, int U1max,
                    int32_t *label_frames, double *scores, hipStream_t st)
 {
-    hipLaunchKernelGGL((rnnt_viterbi_kernel<8>), dim3(B), dim3(64 * w.K), 0, st,
-                       reinterpret_cast<const float2 *>(ws + w.lp_off), llens, tlens, Tmax, U1max, w.S,
-                       reinterpret_cast<uint64_t *>(ws + w.beta_off), label_frames, scores);
-    WR_CHECK_LAUNCH("rnnt_viterbi_kernel");
-    return WR_OK;
+    return launch("rnnt_viterbi_kernel", rnnt_viterbi_kernel<8>, dim3(B), dim3(64 * w.K), 0, st,
+                  reinterpret_cast<const float2 *>(ws + w.lp_off), llens, tlens, Tmax, U1max, w.S,
+                  reinterpret_cast<uint64_t *>(ws + w.beta_off), label_frames, scores);
 }
 
 }  // namespace

@@ -53,6 +53,7 @@ inline int check_length_pair(const char *what, const void *logit_lengths_d, cons
 }
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 // ---- process-wide tuning knobs (wr_tune_set; defaults are the measured best) ----
 enum TuneKey { kTuneLseBlocksPerCu = 0, kTuneGradBlocksPerCu = 1, kTuneNonTemporal = 2, kTuneGradUnroll = 3, kTuneLseUnroll = 4, kTuneJointFwdVariant = 5, kTuneLaneGemmTile = 6, kTuneSplitParts = 7, kTuneDzTile = 8, kTuneDwExact = 9, kTuneDzExact = 10, kTuneFoldProj = 11, kTuneSplitFwdCells = 12, kTuneSplitFwdStore = 13, kTuneGradSkip = 14, kTuneCount = 15 };

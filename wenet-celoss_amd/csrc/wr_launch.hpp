@@ -1,5 +1,5 @@
 // Host-only launch layer of libwr_mi355x: one checked kernel launch and the dispatch from run-time codes (dtype, flags,
-// small integer sets) to template arguments.  Every launch of the loss and joiner sources goes through `launch` or
+// small integer sets) to template arguments.  Every launch of the library goes through `launch` or
 // `launch_lds`, so a kernel's template list is written once per launch and a failure is reported under the name of the
 // kernel that failed.
 #pragma once
