@@ -819,6 +819,70 @@ int wr_rnnt_prune_ranges_cols(const float *px_grad_d, int px_cols, const float *
                               const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1, int R,
                               int64_t *ranges_d /* [B,T,R] out */, void *stream);
 
+/* FastEmit and the delay penalty for the full-lattice loss (wr_rnnt_loss_fwd / _bwd, the joiner's fused forms and the
+ * memory-bounded node).  This text is the contract.  Notation as above: cell (t,u) of utterance b, 0 <= t < T_b,
+ * 0 <= u <= U_b; blank(t,u) / emit(t,u) are the log-softmax values at the blank and label columns.  Regular lattice only.
+ *
+ * Delay penalty, delay_penalty = d >= 0: the rule above, emit'(t,u) = emit(t,u) + d * ((T_b - 1) / 2 - t), formed in
+ * fp64, added to the stored fp32 value in fp64 and rounded once; d = 0 gives emit' = emit.  alpha, beta and
+ * cost_b = -alpha-terminal are those of the lattice with emit', so the returned cost includes the penalty, as in k2.  With
+ * lambda = 0 the gradient is the true derivative of that cost.
+ *
+ * FastEmit (Yu et al., ICASSP 2021), fastemit_lambda = lambda >= 0.  Let ll = -cost.
+ *   occ_blank(t,u) = exp(alpha + blank + beta(t+1,u) - ll)      (at the final cell exp(alpha + blank - ll))
+ *   occ_emit(t,u)  = exp(alpha + emit' + beta(t,u+1) - ll),     occ_blank + occ_emit = exp(alpha + beta - ll)
+ * The gradient with respect to the arc log-probabilities is -occ_blank for the blank arc and -(1 + lambda) occ_emit for
+ * the label arc; the gradient with respect to the logits is that, taken exactly through the log-softmax:
+ *   g[t,u,v] = softmax_v (occ_blank + (1 + lambda) occ_emit) - [v = blank] occ_blank - [v = label] (1 + lambda) occ_emit
+ * This is the warp-transducer convention on log-probabilities, not NeMo's fused approximation (which leaves the softmax
+ * term unscaled).  The returned costs do NOT depend on lambda: they are bit-identical to the costs at lambda = 0 with
+ * the same d.  FastEmit is a gradient-level regulariser.
+ * Where the case chain of the plain gradient drops the label term -- the label equals the blank at a cell that has a blank
+ * term, or u = U_b -- there is no FastEmit term either.  clamp, grad_costs, padding (exact zeros) and a gradient written
+ * over the logits behave as in wr_rnnt_loss_bwd.
+ *
+ * In the kernels' terms only per-row constants change.  With cmd = alpha + cost - denom:
+ *   be_eff  = logadd(beta, log lambda + emit' + beta(t,u+1))   fp64, only where the label term exists and lambda > 0;
+ *                                                              else be_eff = beta
+ *   c2      = fl(fl(cmd + be_eff) log2e)
+ *   lab_sub = fl(cmd + beta(t,u+1) + pen(b,t) + log1p(lambda)),   blank_sub unchanged
+ * emit' is read from the workspace (the stored label arc, which after the sweeps below holds the penalised value), never
+ * from the logits.  There is no second exponential per element.  Rows whose exponentials are all provably +0 are skipped
+ * as in wr_rnnt_loss_bwd, by the same quantities: main bound alpha + cost + be_eff, label bound alpha + cost + beta(t,u+1)
+ * + pen + log1p(lambda), blank bound unchanged.
+ *
+ * wr_rnnt_loss_fwd_lattice: wr_rnnt_loss_fwd's row pass, then wr_rnnt_lattice_sweeps (penalty into the stored arcs, the
+ * unchanged sweeps).  wr_rnnt_loss_fwd_from_lse_lattice: wr_rnnt_loss_fwd_from_lse likewise (repair pass, then those
+ * sweeps).  wr_rnnt_loss_bwd_lattice / wr_joint_rnnt_grad_lattice: wr_rnnt_loss_bwd / wr_joint_rnnt_grad over such a
+ * workspace, given the same delay_penalty; the memory-bounded node runs wr_joint_rnnt_stats + wr_rnnt_lattice_sweeps first.
+ * lattice_type: WR_LATTICE_REGULAR; WR_LATTICE_MODIFIED returns WR_EUNSUPPORTED (the argument is there so that it can
+ * follow), any other code WR_EINVAL.  Negative or non-finite delay_penalty / fastemit_lambda: WR_EINVAL.  With a penalty
+ * B * (T + U1 - 1) * U1 < 2^31 is required as well.  With both at 0 every one of the four launches exactly the kernels
+ * and template instantiations of its plain entry point. */
+int wr_rnnt_loss_fwd_lattice(const void *logits_d, int dtype, const int32_t *targets_d,
+                             const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax, int U1max,
+                             int V, int blank, int lattice_type, double delay_penalty, float *costs_d /* [B] out */,
+                             void *workspace_d, size_t workspace_bytes, void *stream);
+
+int wr_rnnt_loss_fwd_from_lse_lattice(const float *logits_d, const int32_t *targets_d, const int32_t *logit_lengths_d,
+                                      const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V, int blank,
+                                      int lattice_type, double delay_penalty, float *costs_d /* [B] out */,
+                                      void *workspace_d, size_t workspace_bytes, void *stream);
+
+int wr_rnnt_loss_bwd_lattice(const void *logits_d, int dtype, const int32_t *targets_d,
+                             const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax, int U1max,
+                             int V, int blank, float clamp, int lattice_type, double delay_penalty, double fastemit_lambda,
+                             const float *grad_costs_d /* [B] or NULL */, void *grads_d, const void *workspace_d,
+                             size_t workspace_bytes, void *stream);
+
+int wr_joint_rnnt_grad_lattice(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
+                               const int32_t *logit_lengths_d, const int32_t *target_lengths_d, const int32_t *targets_d,
+                               int B, int T, int U1, int J, int V, int activation, int blank, float clamp, int terms,
+                               int lattice_type, double delay_penalty, double fastemit_lambda,
+                               const float *grad_costs_d /* [B] or NULL */, const void *rnnt_workspace_d,
+                               size_t rnnt_workspace_bytes, long long cell_begin, long long cell_end, float *g_out_d,
+                               void *workspace_d, size_t workspace_bytes, int w_ready, void *stream);
+
 /* CTC forced alignment: Viterbi over the T x (2S+1) lattice, replacing
  * forced_align, wenet/utils/ctc_util.py:27-83 (CLI wenet/bin/alignment.py:215).  logits [B, Tmax, V]: pre-softmax
  * ctc_lo output, or log-posteriors if normalized != 0 (the reference is handed ctc.log_softmax(...)).

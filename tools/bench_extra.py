@@ -360,10 +360,108 @@ def bench_hotword(args):
     os.environ.pop("WR_HOTWORD_HOST")
 
 
+def latency_settings(args):
+    """step: (fastemit_lambda, delay_penalty) pairs timed beside (0, 0) when --fastemit-lambda / --delay-penalty are given"""
+    out = [(0.0, 0.0)]
+    if args.fastemit_lambda > 0:
+        out.append((args.fastemit_lambda, 0.0))
+    if args.delay_penalty > 0:
+        out.append((0.0, args.delay_penalty))
+    return out if len(out) > 1 else []
+
+
+def alternating(fns, reps):
+    """{key: (median, min, max) ms} of the callables `fns`, one run of each in turn, `reps` rounds after one warm-up"""
+    for fn in fns.values():
+        fn()
+    torch.cuda.synchronize()
+    runs = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); fn(); b.record()
+            torch.cuda.synchronize()
+            runs[k].append(a.elapsed_time(b))
+    return {k: (sorted(v)[len(v) // 2], min(v), max(v)) for k, v in runs.items()}
+
+
+def bench_grad_pass_latency(args, settings):
+    """The gradient pass alone (wr_rnnt_loss_bwd / wr_rnnt_loss_bwd_lattice on fp32 logits, separate gradient buffer) at
+    each setting, alternating, with the share of dead and faint rows: the kernel's three bounds (rnnt_loss.hip) evaluated
+    in float64 from the exported lattice and the log-probabilities of the logits."""
+    import math
+    from wenet_celoss_amd import _lib
+    dev = torch.device("cuda:0")
+    B, T, U, V = args.B, args.T, args.U, args.V
+    U1 = U + 1
+    torch.manual_seed(3)
+    logits = torch.empty(B, T, U1, V, device=dev)
+    for b in range(B):
+        logits[b].normal_()
+    grads = torch.empty_like(logits)
+    y = torch.randint(1, V, (B, U), dtype=torch.int32, device=dev)
+    ll = torch.full((B,), T, dtype=torch.int32, device=dev); tl = torch.full((B,), U, dtype=torch.int32, device=dev)
+    gc = torch.full((B,), 1.0 / B, device=dev)
+    blank_lp = torch.empty(B, T, U1, dtype=torch.float64, device=dev)
+    emit_lp = torch.zeros(B, T, U1, dtype=torch.float64, device=dev)
+    for b in range(B):
+        for t0 in range(0, T, 100):
+            x = logits[b, t0:t0 + 100]
+            d = torch.logsumexp(x, -1)
+            blank_lp[b, t0:t0 + 100] = (x[..., 0] - d).double()
+            emit_lp[b, t0:t0 + 100, :U] = (x[:, :U].gather(-1, y[b].long()[None, :, None].expand(x.shape[0], U, 1))[..., 0]
+                                           - d[:, :U]).double()
+    fns, shares = {}, {}
+    for lam, pen in settings:
+        ws = _lib.workspace("wr_rnnt_workspace_bytes", B, T, U1, device=dev)
+        costs = torch.empty(B, device=dev)
+        _lib.call("wr_rnnt_loss_fwd_lattice", logits, _lib.WR_F32, y, ll, tl, B, T, U1, V, 0, 0, pen, costs, ws, ws.numel(),
+                  device=dev)
+        alpha = torch.empty(B, T, U1, device=dev); beta = torch.empty_like(alpha)
+        _lib.call("wr_rnnt_export_lattice", ws, ws.numel(), ll, tl, B, T, U1, alpha, beta, device=dev)
+        alpha, beta = alpha.double(), beta.double()
+        ninf = torch.full_like(beta[:, :1], -math.inf)
+        b1 = torch.cat([beta[:, 1:], ninf], 1)                              # beta(t+1, u)
+        b2 = torch.cat([beta[:, :, 1:], torch.full_like(beta[:, :, :1], -math.inf)], 2)    # beta(t, u+1)
+        ac = alpha + costs.double()[:, None, None]
+        tt = torch.arange(T, device=dev, dtype=torch.float64)[None, :, None]
+        em = emit_lp + pen * ((T - 1) / 2.0 - tt)
+        has_lab = torch.arange(U1, device=dev)[None, None, :] < U
+        be_eff = torch.logaddexp(beta, math.log(lam) + em + b2) if lam > 0 else beta
+        be_eff = torch.where(has_lab, be_eff, beta)
+        thr = -93.3
+        main_dead = ac + be_eff < thr
+        final = torch.zeros(B, T, U1, dtype=torch.bool, device=dev); final[:, T - 1, U] = True
+        blank_bound = torch.where(final, ac, ac + b1)
+        blank_dead = (blank_bound < thr) | ((tt == T - 1) & ~final)
+        label_dead = ~has_lab | (ac + b2 + pen * ((T - 1) / 2.0 - tt) + math.log1p(lam) < thr)
+        n = float(B * T * U1)
+        shares[(lam, pen)] = (float((main_dead & blank_dead & label_dead).sum()) / n,
+                              float((main_dead & ~(blank_dead & label_dead)).sum()) / n)
+        if lam == 0.0 and pen == 0.0:
+            fns[(lam, pen)] = lambda ws=ws: _lib.call("wr_rnnt_loss_bwd", logits, _lib.WR_F32, y, ll, tl, B, T, U1, V, 0, -1.0,
+                                                      gc, grads, ws, ws.numel(), device=dev)
+        else:
+            fns[(lam, pen)] = lambda ws=ws, lam=lam, pen=pen: _lib.call(
+                "wr_rnnt_loss_bwd_lattice", logits, _lib.WR_F32, y, ll, tl, B, T, U1, V, 0, -1.0, 0, pen, lam, gc, grads, ws,
+                ws.numel(), device=dev)
+    for (lam, pen), (med, lo, hi) in alternating(fns, args.reps).items():
+        print(json.dumps({"what": "rnnt gradient pass (fp32 logits, separate buffer)", "shape": [B, T, U1, V],
+                          "fastemit_lambda": lam, "delay_penalty": pen, "ms": round(med, 3), "ms_min": round(lo, 3),
+                          "ms_max": round(hi, 3), "reps": args.reps, "dead_share": round(shares[(lam, pen)][0], 4),
+                          "faint_share": round(shares[(lam, pen)][1], 4)}), flush=True)
+    del logits, grads
+
+
 def bench_step(args):
     """The loss block of Transducer.forward (transducer.py:131-147) through the autograd path: pre-join
-    projections -> joiner -> RNN-T loss -> backward to enc/pred outputs and all joiner weights."""
+    projections -> joiner -> RNN-T loss -> backward to enc/pred outputs and all joiner weights.
+    --fastemit-lambda / --delay-penalty: also the gradient pass alone and every configuration's step at (0, 0),
+    (lambda, 0) and (0, delta), alternating, median of --reps with min and max."""
     import wenet_celoss_amd as w
+    settings = latency_settings(args)
+    if settings:
+        bench_grad_pass_latency(args, settings)
     dev = torch.device("cuda:0")
     torch.manual_seed(3)
     B, T, U, V, E, P, J = args.B, args.T, args.U, args.V, 256, 256, 512
@@ -395,16 +493,16 @@ def bench_step(args):
             for prm in joint.parameters():
                 prm.copy_(torch.randn_like(prm) * 0.05)
 
-        def step():
+        def step(**kw):
             joint.zero_grad(set_to_none=True); enc.grad = None; pred.grad = None
             with torch.autocast("cuda", dtype=adt, enabled=amp):
                 if fused:
                     loss = w.joint_rnnt_loss(joint.enc_ffn(enc), joint.pred_ffn(pred), joint.ffn_out.weight,
                                              joint.ffn_out.bias, y, ll, tl, blank=0, reduction="mean", precision=jprec,
-                                             buckets=args.buckets, logits_budget=budget)
+                                             buckets=args.buckets, logits_budget=budget, **kw)
                 else:
                     logits = joint(enc, pred, ll, tl) if args.ragged else joint(enc, pred)
-                    loss = w.rnnt_loss(logits, y, ll, tl, blank=0, reduction="mean", inplace_grad=True)
+                    loss = w.rnnt_loss(logits, y, ll, tl, blank=0, reduction="mean", inplace_grad=True, **kw)
             loss.backward()
             return loss
         loss = step()
@@ -426,6 +524,15 @@ def bench_step(args):
                 rec[name + "_max_err_over_rms"] = float((got - ref).abs().max() / rms)
                 rec[name + "_rms_err_over_rms"] = float((got - ref).pow(2).mean().sqrt() / rms)
         print(json.dumps(rec), flush=True)
+        if settings:
+            fns = {(lam, pen): (lambda lam=lam, pen=pen: step(**({} if lam == pen == 0.0 else
+                                                                  {"fastemit_lambda": lam, "delay_penalty": pen})))
+                   for lam, pen in settings}
+            for (lam, pen), (med, lo, hi) in alternating(fns, args.reps).items():
+                print(json.dumps({"what": "joint+rnnt_loss fwd+bwd (autograd), latency options", "precision": prec,
+                                  "shape": [B, T, U + 1, J, V], "fastemit_lambda": lam, "delay_penalty": pen,
+                                  "ms": round(med, 3), "ms_min": round(lo, 3), "ms_max": round(hi, 3), "reps": args.reps}),
+                      flush=True)
         del joint
 
 
@@ -770,7 +877,11 @@ if __name__ == "__main__":
     ap.add_argument("--rnnt-type", default="regular", choices=["regular", "modified"],
                     help="simple, smoothed, pruned: also time this lattice type beside the regular form")
     ap.add_argument("--delay-penalty", type=float, default=0.0,
-                    help="simple, smoothed, pruned: also time this delay penalty beside the regular form")
+                    help="simple, smoothed, pruned: also time this delay penalty beside the regular form; step: the "
+                         "full-lattice loss's delay_penalty, timed beside (0, 0)")
+    ap.add_argument("--fastemit-lambda", type=float, default=0.0,
+                    help="step: the full-lattice loss's fastemit_lambda, timed beside (0, 0)")
+    ap.add_argument("--reps", type=int, default=9, help="step: alternating rounds of the latency-option timings")
     ap.add_argument("--dw", action="store_true", help="joint: also time the library fp32 GEMM on the three contractions (yardstick)")
     ap.add_argument("--fwd-only", action="store_true", help="joint: stop after the exact forward sweep")
     ap.add_argument("--ragged", action="store_true", help="step: frames in [0.8 T, T] sorted, labels in [U/3, U]")

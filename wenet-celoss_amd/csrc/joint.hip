@@ -86,13 +86,14 @@ __device__ __forceinline__ void fill_h_tile(float *__restrict__ Ht, const float 
 // and no LDS write at all -- only the read-only activation tile lives in LDS.
 // LSE = true: the epilogue also produces the RNN-T loss's row statistics (joint_lse.hpp) -- the workgroup owns
 // every column of its 64 cells, so pass 1 of the loss never has to read the logits back.
-template <int PFK, int CT /* 32-column tiles per wave */, int EPI /* JointEpi */, int NW = (CT == 2 ? 4 : 8) /* waves */>
+template <int PFK, int CT /* 32-column tiles per wave */, int EPI /* JointEpi */, int NW = (CT == 2 ? 4 : 8) /* waves */,
+          typename... Reg /* kEpiGradReg: RnntReg */>
 __global__ __launch_bounds__(64 * NW) void joint_fwd_direct_kernel(
     const float *__restrict__ ep, const float *__restrict__ pp, const float *__restrict__ wt /* [Jp, Vp] */,
     const float *__restrict__ bias, const int32_t *__restrict__ llens, const int32_t *__restrict__ tlens,
-    int B, int T, int U1, int J, int Jp, int V, int Vp, int act, float *__restrict__ out, JointLse lse)
+    int B, int T, int U1, int J, int Jp, int V, int Vp, int act, float *__restrict__ out, JointLse lse, Reg... reg_args)
 {
-    constexpr bool LSE = EPI == kEpiStoreLse || EPI == kEpiStats, STORE = EPI <= kEpiStoreLse, GRAD = EPI == kEpiGrad;
+    constexpr bool LSE = EPI == kEpiStoreLse || EPI == kEpiStats, STORE = EPI <= kEpiStoreLse, GRAD = joint_epi_is_grad(EPI);
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *Ht = lds;                                  // [Jp][65]
     if (EPI == kEpiStats && lse.run_if != nullptr && *lse.run_if == 0) return;
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(64 * NW) void joint_fwd_direct_kernel(
     if (!STORE) {
         const size_t tile = (size_t)Jp * kHPad * sizeof(float);
         er = joint_epi_rows(reinterpret_cast<char *>(lds) + (tile > joint_lse_exchange_bytes(NW) ? tile : joint_lse_exchange_bytes(NW)));
-        joint_epi_rows_init<EPI>(lse, er, llens, tlens, m0, M, T, U1);
+        joint_epi_rows_init<EPI>(lse, er, llens, tlens, m0, M, T, U1, reg_args...);
     }
     fill_h_tile(Ht, ep, pp, m0, M, T, U1, J, Jp, act);
     __syncthreads();
@@ -231,13 +232,13 @@ __global__ void joint_frag_w_kernel(const float *__restrict__ w, int V, int J, i
     }
 }
 
-template <int EPI /* JointEpi */, int CT>
+template <int EPI /* JointEpi */, int CT, typename... Reg /* kEpiGradReg: RnntReg */>
 __global__ __launch_bounds__(512) void joint_fwd_frag_kernel(
     const float *__restrict__ ep, const float *__restrict__ pp, const float4 *__restrict__ wf, const float *__restrict__ bias,
     const int32_t *__restrict__ llens, const int32_t *__restrict__ tlens, int B, int T, int U1, int J, int Jp, int V, int Vp,
-    int act, float *__restrict__ out, JointLse lse)
+    int act, float *__restrict__ out, JointLse lse, Reg... reg_args)
 {
-    constexpr bool LSE = EPI == kEpiStoreLse || EPI == kEpiStats, STORE = EPI <= kEpiStoreLse, GRAD = EPI == kEpiGrad;
+    constexpr bool LSE = EPI == kEpiStoreLse || EPI == kEpiStats, STORE = EPI <= kEpiStoreLse, GRAD = joint_epi_is_grad(EPI);
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int AS = Jp + 4;                            // row stride of the activation tile (floats)
     float *Ht = lds;                                  // [64][AS]
@@ -270,7 +271,7 @@ __global__ __launch_bounds__(512) void joint_fwd_frag_kernel(
     if (!STORE) {
         const size_t tile = (size_t)kBM * AS * sizeof(float);
         er = joint_epi_rows(reinterpret_cast<char *>(lds) + (tile > joint_lse_exchange_bytes(8) ? tile : joint_lse_exchange_bytes(8)));
-        joint_epi_rows_init<EPI>(lse, er, llens, tlens, m0, M, T, U1);
+        joint_epi_rows_init<EPI>(lse, er, llens, tlens, m0, M, T, U1, reg_args...);
     }
     // activation tile: Ht[row][k & 1][k >> 1]
     for (int row = wave; row < kBM; row += 8) {
@@ -685,9 +686,9 @@ namespace {
 // forward kernel; W is already re-laid in `wsw` (Wt for the direct kernel, fragments for the frag kernel)
 int joint_fwd_epi_launch(bool frag, int epi, const float *ep_d, const float *pp_d, const void *wsw, const float *b_out_d,
                          const int32_t *llens, const int32_t *tlens, int B, int T, int U1, int J, int Jp, int V, int Vp,
-                         int act, float *out_d, const JointLse &lse, hipStream_t st)
+                         int act, float *out_d, const JointLse &lse, hipStream_t st, const RnntReg *reg = nullptr)
 {
-    const long cells = epi == kEpiGrad ? lse.m_end - lse.m_begin : (long)B * T * U1;
+    const long cells = joint_epi_is_grad(epi) ? lse.m_end - lse.m_begin : (long)B * T * U1;
     const dim3 grid((unsigned)((cells + kBM - 1) / kBM));
     const size_t tile = frag ? (size_t)kBM * (Jp + 4) * sizeof(float) : (size_t)Jp * kHPad * sizeof(float);
     const size_t lds = (tile > joint_lse_exchange_bytes(8) ? tile : joint_lse_exchange_bytes(8)) + joint_epi_rows_bytes();
@@ -700,6 +701,15 @@ int joint_fwd_epi_launch(bool frag, int epi, const float *ep_d, const float *pp_
                           static_cast<const float *>(wsw), b_out_d, llens, tlens, B, T, U1, J, Jp, V, Vp, act, out_d, l);
     };
     if (epi == kEpiGrad) return run("joint_fwd (gradient epilogue)", int_c<kEpiGrad>{}, lse);
+    if (epi == kEpiGradReg) {
+        if (frag)
+            return launch_lds("joint_fwd (regularised gradient epilogue)", joint_fwd_frag_kernel<kEpiGradReg, 1, RnntReg>, grid,
+                              dim3(512), lds, st, ep_d, pp_d, static_cast<const float4 *>(wsw), b_out_d, llens, tlens, B, T, U1,
+                              J, Jp, V, Vp, act, out_d, lse, *reg);
+        return launch_lds("joint_fwd (regularised gradient epilogue)", joint_fwd_direct_kernel<8, 1, kEpiGradReg, 8, RnntReg>,
+                          grid, dim3(512), lds, st, ep_d, pp_d, static_cast<const float *>(wsw), b_out_d, llens, tlens, B, T, U1,
+                          J, Jp, V, Vp, act, out_d, lse, *reg);
+    }
     (void)hipMemsetAsync(lse.repair, 0, sizeof(int32_t), st);
     WR_TRY(run("joint_fwd (statistics epilogue)", int_c<kEpiStats>{}, lse));
     // repair: the same launch with a running maximum, whose workgroups leave at once unless a partial sum overflowed
@@ -714,7 +724,7 @@ int joint_fwd_epi_launch(bool frag, int epi, const float *ep_d, const float *pp_
 int joint_fwd_launch(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
                      const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int T, int U1, int J, int V,
                      int act, float *out_d, void *workspace_d, size_t workspace_bytes, const JointLse *lse, hipStream_t st,
-                     int epi = -1, bool w_ready = false)
+                     int epi = -1, bool w_ready = false, const RnntReg *reg = nullptr)
 {
     const int Vp = joint_vpad(V), Jp = joint_jpad(J);
     WR_REQUIRE(workspace_bytes >= (size_t)Jp * Vp * sizeof(float), WR_EWORKSPACE, "joint_fwd: workspace too small");
@@ -728,9 +738,9 @@ int joint_fwd_launch(const float *ep_d, const float *pp_d, const float *w_out_d,
         if (!w_ready)
             WR_TRY(launch("joint_frag_w_kernel", joint_frag_w_kernel, dim3(1024), dim3(256), 0, st, w_out_d, V, J, Jp, Vp, wf));
         const size_t tile2 = (size_t)kBM * (Jp + 4) * sizeof(float);
-        if (epi == kEpiStats || epi == kEpiGrad)
+        if (epi == kEpiStats || joint_epi_is_grad(epi))
             return joint_fwd_epi_launch(true, epi, ep_d, pp_d, wf, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, Jp,
-                                        V, Vp, act, out_d, *lse, st);
+                                        V, Vp, act, out_d, *lse, st, reg);
         const auto frag = [&](auto epi_c, size_t lds, const JointLse &l) {
             return launch_lds("joint_fwd_frag_kernel", joint_fwd_frag_kernel<epi_c.value, 1>, grid, dim3(512), lds, st, ep_d,
                               pp_d, wf, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, act, out_d, l);
@@ -743,9 +753,9 @@ int joint_fwd_launch(const float *ep_d, const float *pp_d, const float *w_out_d,
     if (!w_ready)
         WR_TRY(launch("joint_transpose_w_kernel", joint_transpose_w_kernel, dim3(Vp / 32, (Jp + 31) / 32), dim3(256), 0, st,
                       w_out_d, V, J, Jp, Vp, wt));
-    if (epi == kEpiStats || epi == kEpiGrad)
+    if (epi == kEpiStats || joint_epi_is_grad(epi))
         return joint_fwd_epi_launch(false, epi, ep_d, pp_d, wt, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V,
-                                    Vp, act, out_d, *lse, st);
+                                    Vp, act, out_d, *lse, st, reg);
     const auto direct = [&](auto epi_c, size_t lds, const JointLse &l) {
         return launch_lds("joint_fwd_direct_kernel", joint_fwd_direct_kernel<8, 1, epi_c.value>, grid, dim3(512), lds, st, ep_d,
                           pp_d, wt, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, Jp, V, Vp, act, out_d, l);
@@ -830,6 +840,35 @@ extern "C" int wr_joint_rnnt_stats(const float *ep_d, const float *pp_d, const f
                             nullptr, workspace_d, workspace_bytes, &lse, st, kEpiStats);
 }
 
+namespace wr {
+int joint_rnnt_grad_body(const char *what, const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
+                         const int32_t *logit_lengths_d, const int32_t *target_lengths_d, const int32_t *targets_d, int B,
+                         int T, int U1, int J, int V, int activation, int blank, float clamp, int terms,
+                         const float *grad_costs_d, const void *rnnt_workspace_d, size_t rnnt_workspace_bytes,
+                         long long cell_begin, long long cell_end, float *g_out_d, void *workspace_d, size_t workspace_bytes,
+                         int w_ready, const RnntReg *reg, void *stream)
+{
+    if (int rc = joint_rnnt_check(what, ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, targets_d, B, T, U1, J,
+                                  V, activation, blank, terms, workspace_d, rnnt_workspace_d, rnnt_workspace_bytes))
+        return rc;
+    WR_REQUIRE(g_out_d, WR_EINVAL, "%s: null pointer argument", what);
+    WR_REQUIRE(0 <= cell_begin && cell_begin < cell_end && cell_end <= (long long)B * T * U1, WR_EINVAL,
+               "%s: cell range [%lld, %lld) outside [0, %lld)", what, cell_begin, cell_end, (long long)B * T * U1);
+    JointLse lse = joint_rnnt_lse(targets_d, B, T, U1, blank, const_cast<void *>(rnnt_workspace_d));
+    lse.grad_costs = grad_costs_d;
+    lse.clamp = clamp;
+    lse.m_begin = (long)cell_begin;
+    lse.m_end = (long)cell_end;
+    const int epi = reg != nullptr ? kEpiGradReg : kEpiGrad;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (terms == 3)
+        return joint_fwd_split_epi(ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation,
+                                   epi, lse, g_out_d, workspace_d, workspace_bytes, st, w_ready != 0, reg);
+    return joint_fwd_launch(ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation,
+                            g_out_d, workspace_d, workspace_bytes, &lse, st, epi, w_ready != 0, reg);
+}
+}  // namespace wr
+
 extern "C" int wr_joint_rnnt_grad(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
                                   const int32_t *logit_lengths_d, const int32_t *target_lengths_d, const int32_t *targets_d,
                                   int B, int T, int U1, int J, int V, int activation, int blank, float clamp, int terms,
@@ -837,24 +876,10 @@ extern "C" int wr_joint_rnnt_grad(const float *ep_d, const float *pp_d, const fl
                                   long long cell_begin, long long cell_end, float *g_out_d, void *workspace_d,
                                   size_t workspace_bytes, int w_ready, void *stream)
 {
-    if (int rc = joint_rnnt_check("joint_rnnt_grad", ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d,
-                                  targets_d, B, T, U1, J, V, activation, blank, terms, workspace_d, rnnt_workspace_d,
-                                  rnnt_workspace_bytes))
-        return rc;
-    WR_REQUIRE(g_out_d, WR_EINVAL, "joint_rnnt_grad: null pointer argument");
-    WR_REQUIRE(0 <= cell_begin && cell_begin < cell_end && cell_end <= (long long)B * T * U1, WR_EINVAL,
-               "joint_rnnt_grad: cell range [%lld, %lld) outside [0, %lld)", cell_begin, cell_end, (long long)B * T * U1);
-    JointLse lse = joint_rnnt_lse(targets_d, B, T, U1, blank, const_cast<void *>(rnnt_workspace_d));
-    lse.grad_costs = grad_costs_d;
-    lse.clamp = clamp;
-    lse.m_begin = (long)cell_begin;
-    lse.m_end = (long)cell_end;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (terms == 3)
-        return joint_fwd_split_epi(ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation,
-                                   kEpiGrad, lse, g_out_d, workspace_d, workspace_bytes, st, w_ready != 0);
-    return joint_fwd_launch(ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation,
-                            g_out_d, workspace_d, workspace_bytes, &lse, st, kEpiGrad, w_ready != 0);
+    return joint_rnnt_grad_body("joint_rnnt_grad", ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, targets_d, B,
+                                T, U1, J, V, activation, blank, clamp, terms, grad_costs_d, rnnt_workspace_d,
+                                rnnt_workspace_bytes, cell_begin, cell_end, g_out_d, workspace_d, workspace_bytes, w_ready,
+                                nullptr, stream);
 }
 
 extern "C" int wr_joint_bwd_dz(const float *gout_d, const float *ep_d, const float *pp_d, const float *w_out_d,

@@ -19,6 +19,7 @@
 // it takes a spread of more than 88 nats inside one row).  The blank / label logits of a row are read back from
 // the logits the workgroup has just written (L2-resident), 128 loads per workgroup.
 #pragma once
+#include "rnnt_latency.hpp"
 #include "wr_common.hpp"
 
 namespace wr {
@@ -32,7 +33,13 @@ namespace wr {
 //                 the formula and case chain of rnnt_grad_kernel (rnnt_loss.hip) with per-row constants from LDS, out row
 //                 m - m_begin.  The logits are recomputed with the same k order, so they are bit-identical to the ones the
 //                 statistics were taken from.
-enum JointEpi : int { kEpiStore = 0, kEpiStoreLse = 1, kEpiStats = 2, kEpiGrad = 3 };
+//   kEpiGradReg   kEpiGrad with FastEmit and / or the delay penalty (wr_joint_rnnt_grad_lattice): only the per-row
+//                 constants differ (joint_epi_rows_init), the per-element epilogue is kEpiGrad's.  The regularisers are
+//                 one more kernel argument (an RnntReg behind the others: the kernels end in a parameter pack that is
+//                 empty in every other mode, so those keep their arguments and their code); lp_skew then holds the
+//                 penalised label arcs.
+enum JointEpi : int { kEpiStore = 0, kEpiStoreLse = 1, kEpiStats = 2, kEpiGrad = 3, kEpiGradReg = 4 };
+constexpr bool joint_epi_is_grad(int epi) { return epi == kEpiGrad || epi == kEpiGradReg; }
 
 struct JointLse {
     const int32_t *targets;   // [B, U1-1]
@@ -104,10 +111,12 @@ __device__ __forceinline__ EpiRows joint_epi_rows(void *base)
 }
 
 // Fill the per-row constants of the 64 cells m0.. (threads 0..63; the caller synchronises before the epilogues read them).
-template <int EPI>
+template <int EPI, typename... Reg>
 __device__ __forceinline__ void joint_epi_rows_init(const JointLse &a, const EpiRows &er, const int32_t *llens,
-                                                    const int32_t *tlens, long m0, long M, int T, int U1)
+                                                    const int32_t *tlens, long m0, long M, int T, int U1,
+                                                    const Reg &...reg_args)
 {
+    static_assert((EPI == kEpiGradReg) == (sizeof...(Reg) == 1), "kEpiGradReg takes the regularisers, no other mode does");
     const int row = threadIdx.x;
     if (row >= kLseRows) return;
     const long m = m0 + row;
@@ -158,9 +167,20 @@ __device__ __forceinline__ void joint_epi_rows_init(const JointLse &a, const Epi
     if (has_lab) b2 = a.beta_skew[dbase + (size_t)(s + 1) * U1 + (u + 1)];
     const double ac = al + cost;
     const double cmd = ac - (double)d;
-    er.c2[row] = (float)(cmd + be) * kLog2e;
+    double bm = be, lpen = 0.0;
+    if constexpr (EPI == kEpiGradReg) {
+        // rnnt_grad_kernel with REG: be_eff in the main term, pen + log1p(lambda) in the label term
+        const RnntReg &reg = only_arg(reg_args...);
+        if (has_lab) {
+            lpen = delay_pen(reg.delay_penalty, T_ > T ? T : T_, t) + reg.log1p_lambda;
+            if (reg.log_lambda > (double)kNegInf)
+                bm = log_add_d(be, reg.log_lambda + (double)a.lp_skew[dbase + (size_t)s * U1 + u].y + b2);
+        }
+    }
+    er.c2[row] = (float)(cmd + bm) * kLog2e;
     er.bsub[row] = final_cell ? (float)cmd : (has_b1 ? (float)(cmd + b1) : 0.f);
-    er.lsub[row] = has_lab ? (float)(cmd + b2) : 0.f;
+    if constexpr (EPI == kEpiGradReg) er.lsub[row] = has_lab ? (float)(cmd + b2 + lpen) : 0.f;
+    else er.lsub[row] = has_lab ? (float)(cmd + b2) : 0.f;
     er.blk[row] = blank_special ? a.blank : -1;
     er.lab[row] = has_lab ? lab : -1;
     er.go[row] = a.grad_costs ? a.grad_costs[b] : 1.f;
@@ -305,6 +325,6 @@ __device__ __forceinline__ void joint_lse_finish(const JointLse &a, float *xch, 
 int joint_fwd_split_epi(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
                         const int32_t *llens, const int32_t *tlens, int B, int T, int U1, int J, int V, int act, int epi,
                         const JointLse &lse, float *out_d, void *workspace_d, size_t workspace_bytes, hipStream_t st,
-                        bool w_ready = false);
+                        bool w_ready = false, const RnntReg *reg = nullptr /* kEpiGradReg */);
 
 }  // namespace wr

@@ -180,15 +180,15 @@ template <> __device__ __forceinline__ __bf16 to_out<__bf16>(float x) { return (
 // against 7.8 for two 64-cell workgroups -- eight accumulator tiles in 256 registers spill in the staged epilogue
 // (26 k cycles per round), the transposed epilogue does not but stores 16-byte pieces -- so it is not instantiated.
 template <int TERMS, typename OutT, int EPI = kEpiStore /* JointEpi */, int RT = 2, int OCC = 1, bool TRN = false,
-          int NW = kSWaves, typename OpT = __bf16>
+          int NW = kSWaves, typename OpT = __bf16, typename... Reg /* kEpiGradReg: RnntReg */>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : OCC) void joint_fwd_split_kernel(
     const float *__restrict__ ep, const float *__restrict__ pp, const u32x4 *__restrict__ wh, const u32x4 *__restrict__ wl,
     const float *__restrict__ bias, const int32_t *__restrict__ llens, const int32_t *__restrict__ tlens, int B, int T,
     int U1, int J, int Jp, int V, int Vp, int npart, int act, OutT *__restrict__ out, JointLse lse = JointLse{},
-    int lds_bias_bytes = 0, int lds_stage = 0)
+    int lds_bias_bytes = 0, int lds_stage = 0, Reg... reg_args)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned short lds_s[];
-    constexpr bool LSE = EPI == kEpiStoreLse || EPI == kEpiStats, STORE = EPI <= kEpiStoreLse, GRAD = EPI == kEpiGrad;
+    constexpr bool LSE = EPI == kEpiStoreLse || EPI == kEpiStats, STORE = EPI <= kEpiStoreLse, GRAD = joint_epi_is_grad(EPI);
     constexpr bool PLAIN = EPI == kEpiStore;               // logits only: the forms below that store nothing else
     static_assert(STORE || (RT == 2 && OCC == 1 && !TRN && NW == kSWaves && std::is_same<OutT, float>::value),
                   "statistics / gradient epilogues: the 64-cell, one-per-CU form with fp32 values");
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : OCC) void joint_fwd_split_ke
     // EpiRows captured by the lambdas below would live in scratch and reach LDS through flat loads.
     const size_t epi_used = (size_t)(TERMS == 3 ? 2 : 1) * SM * JS * sizeof(unsigned short) + lds_bias_bytes;
     const int epi_off = (int)(epi_used > joint_lse_exchange_bytes(NW) ? epi_used : joint_lse_exchange_bytes(NW));
-    if (!STORE) joint_epi_rows_init<EPI>(lse, joint_epi_rows(reinterpret_cast<char *>(lds_s) + epi_off), llens, tlens, m0, M, T, U1);
+    if (!STORE) joint_epi_rows_init<EPI>(lse, joint_epi_rows(reinterpret_cast<char *>(lds_s) + epi_off), llens, tlens, m0, M, T, U1, reg_args...);
     const int S = Jp / 16;                                  // k-steps per column tile; Jp is a multiple of 16 * PF
     const int cpr = S / PF;                               // register sets ("chunks") per round
     const int n_ct = Vp / 32;                               // column tiles
@@ -1950,7 +1950,7 @@ namespace wr {
 int joint_fwd_split_epi(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
                         const int32_t *llens, const int32_t *tlens, int B, int T, int U1, int J, int V, int act, int epi,
                         const JointLse &lse, float *out_d, void *workspace_d, size_t workspace_bytes, hipStream_t st,
-                        bool w_ready)
+                        bool w_ready, const RnntReg *reg)
 {
     const int Vp = split_vpad(V), Jp = split_jpad(J);
     const size_t img = align_up((size_t)Jp * Vp * sizeof(unsigned short), 256);
@@ -1960,7 +1960,7 @@ int joint_fwd_split_epi(const float *ep_d, const float *pp_d, const float *w_out
     if (!w_ready) {
         WR_TRY(launch("split_w_kernel", split_w_kernel, dim3(512), dim3(256), 0, st, w_out_d, V, J, Vp, Jp, wh, wl));
     }
-    const long cells = epi == kEpiGrad ? lse.m_end - lse.m_begin : (long)B * T * U1;
+    const long cells = joint_epi_is_grad(epi) ? lse.m_end - lse.m_begin : (long)B * T * U1;
     const size_t tile_lds = (size_t)2 * kSM * (Jp + 8) * sizeof(unsigned short);
     const size_t bias_al = align_up((size_t)(Vp / (32 * kSCT)) * 32 * kSCT * sizeof(float), 16);
     const size_t used = tile_lds + bias_al;
@@ -1973,6 +1973,12 @@ int joint_fwd_split_epi(const float *ep_d, const float *pp_d, const float *w_out
                           U1, J, Jp, V, Vp, 1, act, out_d, l, (int)bias_al, 0);
     };
     if (epi == kEpiGrad) return run("joint_fwd_split_kernel (gradient epilogue)", int_c<kEpiGrad>{}, lse);
+    if (epi == kEpiGradReg)
+        return launch_lds("joint_fwd_split_kernel (regularised gradient epilogue)",
+                          joint_fwd_split_kernel<3, float, kEpiGradReg, 2, 1, false, kSWaves, __bf16, RnntReg>, grid,
+                          dim3(64 * kSWaves), lds, st, ep_d, pp_d, reinterpret_cast<const u32x4 *>(wh),
+                          reinterpret_cast<const u32x4 *>(wl), b_out_d, llens, tlens, B, T, U1, J, Jp, V, Vp, 1, act, out_d, lse,
+                          (int)bias_al, 0, *reg);
     (void)hipMemsetAsync(lse.repair, 0, sizeof(int32_t), st);
     WR_TRY(run("joint_fwd_split_kernel (statistics epilogue)", int_c<kEpiStats>{}, lse));
     // repair: the same launch with a running maximum, whose workgroups leave at once unless a partial sum overflowed

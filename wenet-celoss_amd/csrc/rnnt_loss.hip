@@ -31,6 +31,7 @@
 // cell, 2 * 4 * V + two sectors read per faint cell (+ 4*V per padded cell).
 // Dead and faint cells are about 38 % of the BASELINE batch (iid N(0,1)
 // logits; 2 % faint); the share depends on the data.
+#include "rnnt_latency.hpp"
 #include "row_stream.hpp"
 #include "wr_common.hpp"
 #include "wr_launch.hpp"
@@ -245,15 +246,31 @@ __device__ __forceinline__ T faint_pick(int v, int sblk, T vblk, int slab, T vla
     return v == sblk ? vblk : (v == slab ? vlab : val);
 }
 
-template <typename T, bool NT /* loads */, bool NTS /* stores */, int UN>
+// The regularised form of the pass (REG: FastEmit and the delay penalty, include/wr_api.h "FastEmit and the delay penalty
+// for the full-lattice loss") is a second instantiation of rnnt_grad_kernel with one more argument; the plain one keeps
+// its code.  The regularisers change three per-row constants and nothing per element:
+//   be_eff  = logadd(beta, log lambda + emit' + beta(t,u+1)) replaces beta in the main term (fp64; emit' is the stored,
+//             already penalised label arc of the workspace, so no logit is read for it and grads may alias logits),
+//   lab_sub = cmd + beta(t,u+1) + pen(b,t) + log1p(lambda), both only where the label term exists; blank_sub is unchanged.
+// Dead / faint rows with them.  The three bounds are the same quantities: main alpha + cost + be_eff, label alpha + cost +
+// beta(t,u+1) + pen + log1p(lambda) (pen can be positive: the bound is still what is compared), blank unchanged.  The
+// rounding argument above kDeadThr carries over term by term: be_eff and pen + log1p(lambda) are formed and added in
+// fp64 before the one rounding to fp32 that c2 / lab_sub always had, so the main argument is again fl(fl(cmd + be_eff)
+// log2e) fma'd with x log2e (three roundings of a quantity of magnitude <= |bound| + |denom|) and the label argument
+// fl(fl(x + lab_sub) log2e) with lab_sub = fl(bound - denom) (three again), and x - denom <= 4u |denom| does not involve
+// them.  For a negative bound every argument is therefore at most log2e * ((1 - 4u) * bound + 12u * |denom|), as before,
+// and bound < kDeadThr gives +0.  A NaN in be_eff or the penalised bound makes the comparison false: live / read.
+// `Reg`: empty (the plain pass: the kernel and its arguments are what they always were) or one RnntRegArgs.
+template <typename T, bool NT /* loads */, bool NTS /* stores */, int UN, typename... Reg>
 __global__ __launch_bounds__(256) void rnnt_grad_kernel(
     const T *logits, const int32_t *__restrict__ targets,
     const int32_t *__restrict__ llens, const int32_t *__restrict__ tlens,
     int B, int Tmax, int U1max, int V, int blank, float clamp, int K, int S,
     const double *__restrict__ alpha_skew, const double *__restrict__ beta_skew,
     const float *__restrict__ denom, const double *__restrict__ cost_ws,
-    const float *__restrict__ grad_costs, T *grads, int skip_dead)
+    const float *__restrict__ grad_costs, T *grads, int skip_dead, Reg... reg_args)
 {
+    constexpr bool REG = sizeof...(Reg) != 0;
     typedef typename VecOf<T>::type vec_t;
     constexpr int N = VecOf<T>::N;
     const int lane = threadIdx.x & (kWave - 1);
@@ -287,6 +304,7 @@ __global__ __launch_bounds__(256) void rnnt_grad_kernel(
         const bool has_b1 = t < T_ - 1;
         const bool blank_special = final_cell || has_b1;
         double al = 0.0, be = 0.0, cost = 0.0, b1 = 0.0, b2 = 0.0;
+        double be_eff = 0.0, lpen = 0.0;                 // REG: see above
         float go = 1.f, d = 0.f;
         int lab = -1;
         bool has_lab = false;
@@ -303,7 +321,21 @@ __global__ __launch_bounds__(256) void rnnt_grad_kernel(
                 else has_lab = true;
             }
             if (has_lab) b2 = beta_skew[dbase + (size_t)(s + 1) * U1max + (u + 1)];
+            if constexpr (REG) {
+                const RnntRegArgs &ra = only_arg(reg_args...);
+                be_eff = be;
+                if (has_lab) {
+                    lpen = delay_pen(ra.reg.delay_penalty, T_ > Tmax ? Tmax : T_, t) + ra.reg.log1p_lambda;
+                    if (ra.reg.log_lambda > (double)kNegInf)
+                        be_eff = log_add_d(be, ra.reg.log_lambda + (double)ra.lp_skew[dbase + (size_t)s * U1max + u].y + b2);
+                }
+            }
         }
+        const double bm = REG ? be_eff : be;             // beta of the main term
+        auto lab_of = [&](double x) -> double {          // exponent of the label term from the one without regularisers
+            if constexpr (REG) return x + lpen;
+            else return x;
+        };
         const double ac = al + cost;
         auto finish = [&](float val) -> float {
             if (clamp > 0.f) val = fminf(fmaxf(val, -clamp), clamp);
@@ -316,17 +348,17 @@ __global__ __launch_bounds__(256) void rnnt_grad_kernel(
         // in a faint row.  Those logits are the only ones read, before anything is stored (grads may alias logits),
         // and their elements are computed by the expressions of c2 / blank_sub / lab_sub / fix() below.
         // A label outside [0, V) matches no element on either path.
-        const bool main_dead = skip_dead != 0 && fabsf(d) < kDeadDenomMax && ac + be < kDeadThr;
+        const bool main_dead = skip_dead != 0 && fabsf(d) < kDeadDenomMax && ac + bm < kDeadThr;
         if (__builtin_amdgcn_readfirstlane((!valid || main_dead) ? 1 : 0)) {
             const T val = valid ? (T)finish(0.f) : (T)0.f;
             const bool blank_dead = !blank_special || (has_b1 ? ac + b1 : ac) < kDeadThr;
-            const bool label_dead = !has_lab || ac + b2 < kDeadThr || lab >= V;
+            const bool label_dead = !has_lab || lab_of(ac + b2) < kDeadThr || lab >= V;
             const int sblk = (valid && !blank_dead) ? blank : -1;
             const int slab = (valid && !label_dead) ? lab : -1;
             // The main term is evaluated for these elements as the streamed row evaluates it (it is +0): written as a
             // literal 0 the compiler folds 0 - e into -e under the clamp, and -0 is not what the streamed row gives.
             const double cmd = ac - (double)d;
-            const float c2 = (float)(cmd + be) * kLog2e;
+            const float c2 = (float)(cmd + bm) * kLog2e;
             T vblk = val, vlab = val;
             if (sblk >= 0) {
                 const float x = (float)row[sblk];
@@ -337,7 +369,7 @@ __global__ __launch_bounds__(256) void rnnt_grad_kernel(
             }
             if (slab >= 0) {
                 const float x = (float)row[slab];
-                const float sub = (float)(cmd + b2);
+                const float sub = (float)lab_of(cmd + b2);
                 float g = fast_exp2(fmaf(x, kLog2e, c2));
                 g -= fast_exp2((x + sub) * kLog2e);
                 vlab = (T)finish(g);
@@ -366,10 +398,10 @@ __global__ __launch_bounds__(256) void rnnt_grad_kernel(
         }
 
         const double cmd = ac - (double)d;          // g = logit + cm
-        const float c2 = (float)(cmd + be) * kLog2e;
+        const float c2 = (float)(cmd + bm) * kLog2e;
         // exponents (natural log) of the subtracted terms, minus the logit
         const float blank_sub = final_cell ? (float)cmd : (has_b1 ? (float)(cmd + b1) : 0.f);
-        const float lab_sub = has_lab ? (float)(cmd + b2) : 0.f;
+        const float lab_sub = has_lab ? (float)lab_of(cmd + b2) : 0.f;
         const int blk = blank_special ? blank : -1;
 
         auto fix = [&](float val, float x, int v) -> float {
@@ -534,37 +566,41 @@ extern "C" size_t wr_rnnt_workspace_bytes(int B, int Tmax, int U1max)
     return rnnt_ws_layout(B, Tmax, U1max).total;
 }
 
-extern "C" int wr_rnnt_loss_fwd(const void *logits_d, int dtype, const int32_t *targets_d,
-                                const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax,
-                                int U1max, int V, int blank, float *costs_d, void *workspace_d,
-                                size_t workspace_bytes, void *stream)
+namespace wr {
+
+int rnnt_loss_fwd_body(const char *what, const void *logits_d, int dtype, const int32_t *targets_d,
+                       const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V,
+                       int blank, double delay_penalty, float *costs_d, void *workspace_d, size_t workspace_bytes,
+                       void *stream)
 {
     if (int rc = check_shape(B, Tmax, U1max, V, blank)) return rc;
     WR_REQUIRE(logits_d && logit_lengths_d && target_lengths_d && costs_d && workspace_d, WR_EINVAL,
-               "rnnt_loss_fwd: null pointer argument");
-    WR_REQUIRE(targets_d || U1max == 1, WR_EINVAL, "rnnt_loss_fwd: targets is null");
-    WR_REQUIRE(dtype == WR_F32 || dtype == WR_F16 || dtype == WR_BF16, WR_EINVAL, "rnnt_loss_fwd: unknown dtype %d", dtype);
+               "%s: null pointer argument", what);
+    WR_REQUIRE(targets_d || U1max == 1, WR_EINVAL, "%s: targets is null", what);
+    WR_REQUIRE(dtype == WR_F32 || dtype == WR_F16 || dtype == WR_BF16, WR_EINVAL, "%s: unknown dtype %d", what, dtype);
     const RnntWs w = rnnt_ws_layout(B, Tmax, U1max);
-    WR_REQUIRE(workspace_bytes >= w.total, WR_EWORKSPACE, "rnnt_loss_fwd: workspace %zu < required %zu",
-               workspace_bytes, w.total);
+    WR_REQUIRE(workspace_bytes >= w.total, WR_EWORKSPACE, "%s: workspace %zu < required %zu", what, workspace_bytes, w.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
     char *ws = static_cast<char *>(workspace_d);
     WR_TRY(rnnt_launch_lse(w, ws, logits_d, dtype, targets_d, logit_lengths_d, target_lengths_d, B, Tmax, U1max, V, blank,
                            st));
+    if (delay_penalty > 0.0)
+        return wr_rnnt_lattice_sweeps(logit_lengths_d, target_lengths_d, B, Tmax, U1max, WR_LATTICE_REGULAR, delay_penalty,
+                                      costs_d, workspace_d, workspace_bytes, stream);
     return rnnt_launch_sweep(w, ws, logit_lengths_d, target_lengths_d, B, Tmax, U1max, costs_d, st);
 }
 
-extern "C" int wr_rnnt_loss_fwd_from_lse(const float *logits_d, const int32_t *targets_d, const int32_t *logit_lengths_d,
-                                         const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V, int blank,
-                                         float *costs_d, void *workspace_d, size_t workspace_bytes, void *stream)
+int rnnt_loss_fwd_from_lse_body(const char *what, const float *logits_d, const int32_t *targets_d,
+                                const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax, int U1max,
+                                int V, int blank, double delay_penalty, float *costs_d, void *workspace_d,
+                                size_t workspace_bytes, void *stream)
 {
     if (int rc = check_shape(B, Tmax, U1max, V, blank)) return rc;
     WR_REQUIRE(logits_d && logit_lengths_d && target_lengths_d && costs_d && workspace_d, WR_EINVAL,
-               "rnnt_loss_fwd_from_lse: null pointer argument");
-    WR_REQUIRE(targets_d || U1max == 1, WR_EINVAL, "rnnt_loss_fwd_from_lse: targets is null");
+               "%s: null pointer argument", what);
+    WR_REQUIRE(targets_d || U1max == 1, WR_EINVAL, "%s: targets is null", what);
     const RnntWs w = rnnt_ws_layout(B, Tmax, U1max);
-    WR_REQUIRE(workspace_bytes >= w.total, WR_EWORKSPACE, "rnnt_loss_fwd_from_lse: workspace %zu < required %zu",
-               workspace_bytes, w.total);
+    WR_REQUIRE(workspace_bytes >= w.total, WR_EWORKSPACE, "%s: workspace %zu < required %zu", what, workspace_bytes, w.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
     char *ws = static_cast<char *>(workspace_d);
     // repair pass: the stand-alone row statistics, executed only if the joiner's epilogue raised the flag (a partial
@@ -575,7 +611,29 @@ extern "C" int wr_rnnt_loss_fwd_from_lse(const float *logits_d, const int32_t *t
                   logits_d, targets_d, logit_lengths_d, target_lengths_d, B, Tmax, U1max, V, blank, w.K, w.S,
                   reinterpret_cast<float2 *>(ws + w.lp_off), reinterpret_cast<float *>(ws + w.denom_off),
                   reinterpret_cast<const int32_t *>(ws + w.flag_off)));
+    if (delay_penalty > 0.0)
+        return wr_rnnt_lattice_sweeps(logit_lengths_d, target_lengths_d, B, Tmax, U1max, WR_LATTICE_REGULAR, delay_penalty,
+                                      costs_d, workspace_d, workspace_bytes, stream);
     return rnnt_launch_sweep(w, ws, logit_lengths_d, target_lengths_d, B, Tmax, U1max, costs_d, st);
+}
+
+}  // namespace wr
+
+extern "C" int wr_rnnt_loss_fwd(const void *logits_d, int dtype, const int32_t *targets_d,
+                                const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax,
+                                int U1max, int V, int blank, float *costs_d, void *workspace_d,
+                                size_t workspace_bytes, void *stream)
+{
+    return rnnt_loss_fwd_body("rnnt_loss_fwd", logits_d, dtype, targets_d, logit_lengths_d, target_lengths_d, B, Tmax, U1max, V,
+                              blank, 0.0, costs_d, workspace_d, workspace_bytes, stream);
+}
+
+extern "C" int wr_rnnt_loss_fwd_from_lse(const float *logits_d, const int32_t *targets_d, const int32_t *logit_lengths_d,
+                                         const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V, int blank,
+                                         float *costs_d, void *workspace_d, size_t workspace_bytes, void *stream)
+{
+    return rnnt_loss_fwd_from_lse_body("rnnt_loss_fwd_from_lse", logits_d, targets_d, logit_lengths_d, target_lengths_d, B, Tmax,
+                                       U1max, V, blank, 0.0, costs_d, workspace_d, workspace_bytes, stream);
 }
 
 extern "C" int wr_rnnt_loss_sweeps(const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax,
@@ -591,19 +649,27 @@ extern "C" int wr_rnnt_loss_sweeps(const int32_t *logit_lengths_d, const int32_t
                              static_cast<hipStream_t>(stream));
 }
 
-extern "C" int wr_rnnt_loss_bwd(const void *logits_d, int dtype, const int32_t *targets_d,
-                                const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax,
-                                int U1max, int V, int blank, float clamp, const float *grad_costs_d, void *grads_d,
-                                const void *workspace_d, size_t workspace_bytes, void *stream)
+namespace wr {
+
+// (defined at the end of the file: the regularised instantiations then follow every kernel the file had before them
+// in the code object, and those keep their places)
+int rnnt_launch_grad_reg(const RnntWs &w, const char *ws, const void *logits_d, int dtype, const int32_t *targets_d,
+                         const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V,
+                         int blank, float clamp, const float *grad_costs_d, void *grads_d, const RnntReg &reg, dim3 grid,
+                         bool nt, bool nts, int skip, hipStream_t st);
+
+int rnnt_loss_bwd_body(const char *what, const void *logits_d, int dtype, const int32_t *targets_d,
+                       const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V,
+                       int blank, float clamp, const float *grad_costs_d, void *grads_d, const void *workspace_d,
+                       size_t workspace_bytes, const RnntReg *reg, void *stream)
 {
     if (int rc = check_shape(B, Tmax, U1max, V, blank)) return rc;
     WR_REQUIRE(logits_d && logit_lengths_d && target_lengths_d && grads_d && workspace_d, WR_EINVAL,
-               "rnnt_loss_bwd: null pointer argument");
-    WR_REQUIRE(targets_d || U1max == 1, WR_EINVAL, "rnnt_loss_bwd: targets is null");
-    WR_REQUIRE(dtype == WR_F32 || dtype == WR_F16 || dtype == WR_BF16, WR_EINVAL, "rnnt_loss_bwd: unknown dtype %d", dtype);
+               "%s: null pointer argument", what);
+    WR_REQUIRE(targets_d || U1max == 1, WR_EINVAL, "%s: targets is null", what);
+    WR_REQUIRE(dtype == WR_F32 || dtype == WR_F16 || dtype == WR_BF16, WR_EINVAL, "%s: unknown dtype %d", what, dtype);
     const RnntWs w = rnnt_ws_layout(B, Tmax, U1max);
-    WR_REQUIRE(workspace_bytes >= w.total, WR_EWORKSPACE, "rnnt_loss_bwd: workspace %zu < required %zu",
-               workspace_bytes, w.total);
+    WR_REQUIRE(workspace_bytes >= w.total, WR_EWORKSPACE, "%s: workspace %zu < required %zu", what, workspace_bytes, w.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const char *ws = static_cast<const char *>(workspace_d);
     const long nrows = (long)B * Tmax * U1max;
@@ -612,6 +678,9 @@ extern "C" int wr_rnnt_loss_bwd(const void *logits_d, int dtype, const int32_t *
     const bool nt = (tune_get(kTuneNonTemporal) & 1) != 0;
     const bool nts = (tune_get(kTuneNonTemporal) & 2) != 0;
     const int skip = tune_get(kTuneGradSkip) != 0 ? 1 : 0;
+    if (reg != nullptr)
+        return rnnt_launch_grad_reg(w, ws, logits_d, dtype, targets_d, logit_lengths_d, target_lengths_d, B, Tmax, U1max, V,
+                                    blank, clamp, grad_costs_d, grads_d, *reg, grid3, nt, nts, skip, st);
     return with_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return with_bool(nt, [&](auto nt_c) {
@@ -631,6 +700,17 @@ extern "C" int wr_rnnt_loss_bwd(const void *logits_d, int dtype, const int32_t *
     });
 }
 
+}  // namespace wr
+
+extern "C" int wr_rnnt_loss_bwd(const void *logits_d, int dtype, const int32_t *targets_d,
+                                const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax,
+                                int U1max, int V, int blank, float clamp, const float *grad_costs_d, void *grads_d,
+                                const void *workspace_d, size_t workspace_bytes, void *stream)
+{
+    return rnnt_loss_bwd_body("rnnt_loss_bwd", logits_d, dtype, targets_d, logit_lengths_d, target_lengths_d, B, Tmax, U1max, V,
+                              blank, clamp, grad_costs_d, grads_d, workspace_d, workspace_bytes, nullptr, stream);
+}
+
 extern "C" int wr_rnnt_export_lattice(const void *workspace_d, size_t workspace_bytes,
                                       const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B,
                                       int Tmax, int U1max, float *alpha_d, float *beta_d, void *stream)
@@ -644,4 +724,30 @@ extern "C" int wr_rnnt_export_lattice(const void *workspace_d, size_t workspace_
     return launch("rnnt_export_kernel", rnnt_export_kernel, dim3(256), dim3(256), 0, static_cast<hipStream_t>(stream),
                   reinterpret_cast<const double *>(ws + w.alpha_off), reinterpret_cast<const double *>(ws + w.beta_off),
                   logit_lengths_d, target_lengths_d, B, Tmax, U1max, w.K, w.S, alpha_d, beta_d);
+}
+
+// the gradient pass with FastEmit and / or the delay penalty: rnnt_loss_bwd_body's launch, regularised instantiation
+int wr::rnnt_launch_grad_reg(const RnntWs &w, const char *ws, const void *logits_d, int dtype, const int32_t *targets_d,
+                             const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax, int U1max,
+                             int V, int blank, float clamp, const float *grad_costs_d, void *grads_d, const RnntReg &reg,
+                             dim3 grid, bool nt, bool nts, int skip, hipStream_t st)
+{
+    const RnntRegArgs ra{reinterpret_cast<const float2 *>(ws + w.lp_off), reg};
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return with_bool(nt, [&](auto nt_c) {
+            return with_int<16, 8, 4>(unroll_of(kTuneGradUnroll), [&](auto un) {
+                return with_bool(nts, [&](auto nts_c) {
+                    return launch("rnnt_grad_kernel (regularised)",
+                                  rnnt_grad_kernel<T, nt_c.value, nts_c.value, un.value, RnntRegArgs>, grid, dim3(256), 0, st,
+                                  static_cast<const T *>(logits_d), targets_d, logit_lengths_d, target_lengths_d, B, Tmax,
+                                  U1max, V, blank, clamp, w.K, w.S, reinterpret_cast<const double *>(ws + w.alpha_off),
+                                  reinterpret_cast<const double *>(ws + w.beta_off),
+                                  reinterpret_cast<const float *>(ws + w.denom_off),
+                                  reinterpret_cast<const double *>(ws + w.cost_off), grad_costs_d, static_cast<T *>(grads_d),
+                                  skip, ra);
+                });
+            });
+        });
+    });
 }

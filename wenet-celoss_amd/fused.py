@@ -33,12 +33,13 @@ import torch
 
 from . import _lib
 from .joint import _PRECISIONS, _call_precision, activation_code, joiner_workspace, joint_backward, joint_forward
+from .rnnt_loss import check_latency
 
 
 class _JointRnntFn(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, ep, pp, w, b, targets, llens, tlens, blank, clamp, terms, act=0):
+    def forward(ctx, ep, pp, w, b, targets, llens, tlens, blank, clamp, terms, act=0, lam=0.0, pen=0.0):
         if not ep.is_cuda:
             raise RuntimeError("wenet_celoss_amd.joint_rnnt_loss: tensors must live on a HIP device "
                                "(this package has no CPU path)")
@@ -58,14 +59,21 @@ class _JointRnntFn(torch.autograd.Function):
         epi = os.environ.get("WR_FUSED_LSE_EPILOGUE")
         epilogue = (terms != 0) if epi is None else (epi == "1")
         joint_forward(ep, pp, w, b, llens, tlens, terms, act, out=logits, stats=(targets, blank, rws) if epilogue else None)
-        if epilogue:
+        if pen != 0.0:             # the delay penalty goes into the stored label arcs before the sweeps
+            if epilogue:
+                _lib.call("wr_rnnt_loss_fwd_from_lse_lattice", logits, targets, llens, tlens, B, T, U1, V, blank, 0, pen,
+                          costs, rws, rws.numel(), device=dev)
+            else:
+                _lib.call("wr_rnnt_loss_fwd_lattice", logits, _lib.WR_F32, targets, llens, tlens, B, T, U1, V, blank, 0, pen,
+                          costs, rws, rws.numel(), device=dev)
+        elif epilogue:
             _lib.call("wr_rnnt_loss_fwd_from_lse", logits, targets, llens, tlens, B, T, U1, V, blank, costs, rws, rws.numel(),
                       device=dev)
         else:
             _lib.call("wr_rnnt_loss_fwd", logits, _lib.WR_F32, targets, llens, tlens, B, T, U1, V, blank, costs, rws,
                       rws.numel(), device=dev)
         ctx.save_for_backward(ep, pp, w, b, targets, llens, tlens, logits, rws)
-        ctx.blank, ctx.clamp, ctx.terms, ctx.act = blank, clamp, terms, act
+        ctx.blank, ctx.clamp, ctx.terms, ctx.act, ctx.lam, ctx.pen = blank, clamp, terms, act, lam, pen
         ctx.logits_hold_gradient = False
         return costs
 
@@ -91,12 +99,16 @@ class _JointRnntFn(torch.autograd.Function):
         # 32-utterance step).  WR_FUSED_INPLACE_BYTES=n keeps a separate buffer below n bytes.
         inplace = logits.numel() * logits.element_size() >= int(os.environ.get("WR_FUSED_INPLACE_BYTES", "0"))
         grads = logits if inplace else torch.empty_like(logits)
-        _lib.call("wr_rnnt_loss_bwd", logits, _lib.WR_F32, targets, llens, tlens, B, T, U1, V, ctx.blank, float(ctx.clamp), gc,
-                  grads, rws, rws.numel(), device=dev)
+        if ctx.lam == 0.0 and ctx.pen == 0.0:
+            _lib.call("wr_rnnt_loss_bwd", logits, _lib.WR_F32, targets, llens, tlens, B, T, U1, V, ctx.blank, float(ctx.clamp),
+                      gc, grads, rws, rws.numel(), device=dev)
+        else:
+            _lib.call("wr_rnnt_loss_bwd_lattice", logits, _lib.WR_F32, targets, llens, tlens, B, T, U1, V, ctx.blank,
+                      float(ctx.clamp), 0, ctx.pen, ctx.lam, gc, grads, rws, rws.numel(), device=dev)
         ctx.logits_hold_gradient = inplace
         d_ep, d_pp, d_w, d_b = joint_backward(grads, ep, pp, w, llens, tlens, ctx.terms, ctx.needs_input_grad[2],
                                               ctx.needs_input_grad[3], gout_zero_in_padding=True, act=ctx.act)
-        return d_ep, d_pp, d_w, d_b, None, None, None, None, None, None, None
+        return d_ep, d_pp, d_w, d_b, None, None, None, None, None, None, None, None, None
 
 
 class Slice(NamedTuple):
@@ -154,7 +166,7 @@ class _JointRnntBoundedFn(torch.autograd.Function):
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, ep, pp, w, b, targets, llens, tlens, blank, clamp, terms, act, slices, host_t, host_u):
+    def forward(ctx, ep, pp, w, b, targets, llens, tlens, blank, clamp, terms, act, slices, host_t, host_u, lam=0.0, pen=0.0):
         if not ep.is_cuda:
             raise RuntimeError("wenet_celoss_amd.joint_rnnt_loss: tensors must live on a HIP device "
                                "(this package has no CPU path)")
@@ -168,7 +180,10 @@ class _JointRnntBoundedFn(torch.autograd.Function):
         ws = joiner_workspace(terms, J, V, dev)
         _lib.call("wr_joint_rnnt_stats", ep, pp, w, b, llens, tlens, targets, B, T, U1, J, V, act, blank, terms, ws, ws.numel(),
                   rws, rws.numel(), device=dev)
-        _lib.call("wr_rnnt_loss_sweeps", llens, tlens, B, T, U1, costs, rws, rws.numel(), device=dev)
+        if pen == 0.0:
+            _lib.call("wr_rnnt_loss_sweeps", llens, tlens, B, T, U1, costs, rws, rws.numel(), device=dev)
+        else:
+            _lib.call("wr_rnnt_lattice_sweeps", llens, tlens, B, T, U1, 0, pen, costs, rws, rws.numel(), device=dev)
         # per-slice length arrays, built once on the host from the caller's length sync: [ll of every slice | tl ...]
         ll_s, tl_s = [], []
         for s in slices:
@@ -181,7 +196,7 @@ class _JointRnntBoundedFn(torch.autograd.Function):
         ctx.save_for_backward(ep, pp, w, b, targets, llens, tlens, rws)
         ctx.slice_lens = lens
         ctx.slices = slices
-        ctx.blank, ctx.clamp, ctx.terms, ctx.act = blank, clamp, terms, act
+        ctx.blank, ctx.clamp, ctx.terms, ctx.act, ctx.lam, ctx.pen = blank, clamp, terms, act, lam, pen
         return costs
 
     @staticmethod
@@ -200,7 +215,7 @@ class _JointRnntBoundedFn(torch.autograd.Function):
         d_b = torch.zeros(V, dtype=torch.float32, device=dev) if need_b else None
         slices = ctx.slices
         if not slices:
-            return d_ep, d_pp, d_w, d_b, None, None, None, None, None, None, None, None, None, None
+            return d_ep, d_pp, d_w, d_b, None, None, None, None, None, None, None, None, None, None, None, None
         nmax = max(s.cells(U1) for s in slices)
         # buffers sized to the largest slice, allocated once per backward
         g = torch.empty(nmax * V, dtype=torch.float32, device=dev)
@@ -213,9 +228,14 @@ class _JointRnntBoundedFn(torch.autograd.Function):
             nb, nt = s.b1 - s.b0, s.t1 - s.t0
             cells = nb * nt * U1
             begin = (s.b0 * T + s.t0) * U1
-            _lib.call("wr_joint_rnnt_grad", ep, pp, w, b, llens, tlens, targets, B, T, U1, J, V, ctx.act, ctx.blank,
-                      float(ctx.clamp), ctx.terms, gc, rws, rws.numel(), begin, begin + cells, g, ws, ws.numel(), int(i > 0),
-                      device=dev)
+            if ctx.lam == 0.0 and ctx.pen == 0.0:
+                _lib.call("wr_joint_rnnt_grad", ep, pp, w, b, llens, tlens, targets, B, T, U1, J, V, ctx.act, ctx.blank,
+                          float(ctx.clamp), ctx.terms, gc, rws, rws.numel(), begin, begin + cells, g, ws, ws.numel(),
+                          int(i > 0), device=dev)
+            else:
+                _lib.call("wr_joint_rnnt_grad_lattice", ep, pp, w, b, llens, tlens, targets, B, T, U1, J, V, ctx.act,
+                          ctx.blank, float(ctx.clamp), ctx.terms, 0, ctx.pen, ctx.lam, gc, rws, rws.numel(), begin,
+                          begin + cells, g, ws, ws.numel(), int(i > 0), device=dev)
             ll = ctx.slice_lens[k:k + nb]
             tl = ctx.slice_lens[nl + k:nl + k + nb]
             k += nb
@@ -230,7 +250,7 @@ class _JointRnntBoundedFn(torch.autograd.Function):
                 d_w += dw
             if need_b:
                 d_b += db
-        return d_ep, d_pp, d_w, d_b, None, None, None, None, None, None, None, None, None, None
+        return d_ep, d_pp, d_w, d_b, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 def plan_buckets(t_lens, u_lens, max_buckets: int = 4, min_gain: float = 0.08, min_cells: int = 20000):
@@ -285,7 +305,8 @@ def joint_rnnt_loss(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Tensor, b_o
                     targets: torch.Tensor, logit_lengths: torch.Tensor, target_lengths: torch.Tensor, blank: int = 0,
                     clamp: float = -1.0, reduction: str = "mean", precision: Optional[str] = None,
                     buckets: Optional[int] = None, activation: str = "tanh",
-                    logits_budget: Optional[int] = None) -> torch.Tensor:
+                    logits_budget: Optional[int] = None, *, fastemit_lambda: float = 0.0,
+                    delay_penalty: float = 0.0) -> torch.Tensor:
     """rnnt_loss(ffn_out(act(ep[:, :, None] + pp[:, None])), targets, logit_lengths, target_lengths) without the
     logits ever leaving the node.  ep (B, T, J) = enc_ffn(encoder_out), pp (B, U+1, J) = pred_ffn(predictor_out);
     targets (B, U) int32 with padding already mapped to a valid class; lengths (B,) int32; requires
@@ -296,9 +317,13 @@ def joint_rnnt_loss(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Tensor, b_o
     WR_FUSED_BUCKETS, 4; 1 = one call for the whole batch).  Costs come back in the caller's utterance order.
     ``logits_budget``: None (default) = the node above; an int = the memory-bounded node (`_JointRnntBoundedFn`): no
     logits tensor, the backward recomputes the logits in slices whose gradient buffer holds at most this many bytes
-    (`plan_slices`; ValueError below one frame row, U1 * V * 4 bytes).  "fp32" and "bf16x3" only, as the node above."""
+    (`plan_slices`; ValueError below one frame row, U1 * V * 4 bytes).  "fp32" and "bf16x3" only, as the node above.
+    ``fastemit_lambda`` / ``delay_penalty``: as `rnnt_loss` takes them, in either node (FastEmit scales the gradient of
+    the label arcs by 1 + lambda and leaves the costs bit-identical; the delay penalty is inside the costs).  The
+    penalty uses each utterance's own length, so buckets and slices do not change it."""
     if reduction not in ("none", "mean", "sum"):
         raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
+    lam, pen = check_latency("joint_rnnt_loss", fastemit_lambda, delay_penalty)
     precision = _call_precision(precision)             # "autocast": "fp32" outside autocast, a 16-bit mode under it
     if precision in ("bf16", "f16"):
         raise ValueError("joint_rnnt_loss: the AMP single-term mode keeps 16-bit logits; use TransducerJoint + rnnt_loss")
@@ -330,10 +355,10 @@ def joint_rnnt_loss(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Tensor, b_o
 
     def node(ep_, pp_, tg_, ll_, tl_, host_t, host_u):
         if logits_budget is None:
-            return _JointRnntFn.apply(ep_, pp_, w_out, b_out, tg_, ll_, tl_, int(blank), float(clamp), terms, act)
+            return _JointRnntFn.apply(ep_, pp_, w_out, b_out, tg_, ll_, tl_, int(blank), float(clamp), terms, act, lam, pen)
         slices = plan_slices(host_t, host_u, ep_.shape[1], pp_.shape[1], V, int(logits_budget))
         return _JointRnntBoundedFn.apply(ep_, pp_, w_out, b_out, tg_, ll_, tl_, int(blank), float(clamp), terms, act,
-                                         slices, host_t, host_u)
+                                         slices, host_t, host_u, lam, pen)
 
     if logits_budget is not None:
         plan_slices(lens[0].tolist(), lens[1].tolist(), T, U1, V, int(logits_budget))   # a bad budget fails before any launch

@@ -18,11 +18,25 @@ so the logits-sized tensor is touched three times in total.
 """
 from __future__ import annotations
 
+import math
 import os
 
 import torch
 
 from . import _lib
+from .rnnt_lattice import check_lattice
+
+
+def check_latency(what: str, fastemit_lambda, delay_penalty):
+    """(fastemit_lambda, delay_penalty) of a full-lattice loss as floats, or ValueError; needs no device."""
+    _, pen = check_lattice(what, "regular", delay_penalty)
+    try:
+        lam = float(fastemit_lambda)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: fastemit_lambda must be a number (got {fastemit_lambda!r})") from None
+    if not (lam >= 0.0 and math.isfinite(lam)):
+        raise ValueError(f"{what}: fastemit_lambda must be finite and not negative (got {fastemit_lambda})")
+    return lam, pen
 
 
 def _validate(logits, targets, logit_lengths, target_lengths, blank):
@@ -60,7 +74,7 @@ def _validate(logits, targets, logit_lengths, target_lengths, blank):
 class _RNNTLossFn(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda")          # fp16/bf16 logits are handled natively (fp32 arithmetic inside)
-    def forward(ctx, logits, targets, logit_lengths, target_lengths, blank, clamp, inplace_grad):
+    def forward(ctx, logits, targets, logit_lengths, target_lengths, blank, clamp, inplace_grad, lam=0.0, pen=0.0):
         if not logits.is_cuda:
             raise RuntimeError("wenet_celoss_amd.rnnt_loss: logits must live on a HIP device "
                                "(this package has no CPU path)")
@@ -68,10 +82,14 @@ class _RNNTLossFn(torch.autograd.Function):
         dev = logits.device
         ws = _lib.workspace("wr_rnnt_workspace_bytes", B, T, U1, device=dev)
         costs = torch.empty(B, dtype=torch.float32, device=dev)
-        _lib.call("wr_rnnt_loss_fwd", logits, _lib.dtype_code(logits.dtype), targets, logit_lengths, target_lengths, B, T, U1,
-                  V, blank, costs, ws, ws.numel(), device=dev)
+        if pen == 0.0:
+            _lib.call("wr_rnnt_loss_fwd", logits, _lib.dtype_code(logits.dtype), targets, logit_lengths, target_lengths, B, T,
+                      U1, V, blank, costs, ws, ws.numel(), device=dev)
+        else:
+            _lib.call("wr_rnnt_loss_fwd_lattice", logits, _lib.dtype_code(logits.dtype), targets, logit_lengths,
+                      target_lengths, B, T, U1, V, blank, 0, pen, costs, ws, ws.numel(), device=dev)
         ctx.save_for_backward(logits, targets, logit_lengths, target_lengths, ws)
-        ctx.blank, ctx.clamp, ctx.inplace_grad = blank, clamp, inplace_grad
+        ctx.blank, ctx.clamp, ctx.inplace_grad, ctx.lam, ctx.pen = blank, clamp, inplace_grad, lam, pen
         return costs.to(logits.dtype) if logits.dtype != torch.float32 else costs
 
     @staticmethod
@@ -82,16 +100,31 @@ class _RNNTLossFn(torch.autograd.Function):
         dev = logits.device
         grads = logits if ctx.inplace_grad else torch.empty_like(logits)
         gc = grad_costs.to(torch.float32).contiguous()
-        _lib.call("wr_rnnt_loss_bwd", logits, _lib.dtype_code(logits.dtype), targets, logit_lengths, target_lengths, B, T, U1,
-                  V, ctx.blank, float(ctx.clamp), gc, grads, ws, ws.numel(), device=dev)
-        return grads, None, None, None, None, None, None
+        if ctx.lam == 0.0 and ctx.pen == 0.0:
+            _lib.call("wr_rnnt_loss_bwd", logits, _lib.dtype_code(logits.dtype), targets, logit_lengths, target_lengths, B, T,
+                      U1, V, ctx.blank, float(ctx.clamp), gc, grads, ws, ws.numel(), device=dev)
+        else:
+            _lib.call("wr_rnnt_loss_bwd_lattice", logits, _lib.dtype_code(logits.dtype), targets, logit_lengths,
+                      target_lengths, B, T, U1, V, ctx.blank, float(ctx.clamp), 0, ctx.pen, ctx.lam, gc, grads, ws,
+                      ws.numel(), device=dev)
+        return grads, None, None, None, None, None, None, None, None
 
 
 def rnnt_loss(logits: torch.Tensor, targets: torch.Tensor, logit_lengths: torch.Tensor,
               target_lengths: torch.Tensor, blank: int = -1, clamp: float = -1, reduction: str = "mean",
-              inplace_grad: bool | None = None) -> torch.Tensor:
+              inplace_grad: bool | None = None, *, fastemit_lambda: float = 0.0,
+              delay_penalty: float = 0.0) -> torch.Tensor:
     """torchaudio.functional.rnnt_loss(logits, targets, logit_lengths,
     target_lengths, blank=-1, clamp=-1, reduction="mean").
+
+    ``fastemit_lambda`` (extension; FastEmit, Yu et al. 2021, as warp-transducer, ESPnet and NeMo name it): a
+    gradient-level regulariser towards early emission -- the gradient of every label arc's log-probability is scaled
+    by ``1 + fastemit_lambda`` and taken exactly through the log-softmax.  The returned costs do NOT depend on it:
+    they are bit-identical to the costs at 0.
+    ``delay_penalty`` (extension; k2's rule, as the k2 losses of this package take it): ``delay_penalty * ((T_b - 1) /
+    2 - t)`` is added to the log-probability of every label arc at frame t; the returned costs include it and the
+    gradient is their derivative.  Both must be finite and not negative (ValueError); with both at 0 this is the call
+    it always was.  The contract is in include/wr_api.h ("FastEmit and the delay penalty for the full-lattice loss").
 
     ``inplace_grad`` (extension; default from env WR_RNNT_INPLACE_GRAD, off):
     write the gradient over the logits storage in backward -- halves the
@@ -100,13 +133,14 @@ def rnnt_loss(logits: torch.Tensor, targets: torch.Tensor, logit_lengths: torch.
     """
     if reduction not in ("none", "mean", "sum"):
         raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
+    lam, pen = check_latency("rnnt_loss", fastemit_lambda, delay_penalty)
     if blank < 0:
         blank = logits.shape[-1] + blank
     _validate(logits, targets, logit_lengths, target_lengths, blank)
     if inplace_grad is None:
         inplace_grad = os.environ.get("WR_RNNT_INPLACE_GRAD", "0") == "1"
     costs = _RNNTLossFn.apply(logits, targets, logit_lengths, target_lengths, int(blank), float(clamp),
-                              bool(inplace_grad))
+                              bool(inplace_grad), lam, pen)
     if reduction == "mean":
         return costs.mean()
     if reduction == "sum":
@@ -117,12 +151,16 @@ def rnnt_loss(logits: torch.Tensor, targets: torch.Tensor, logit_lengths: torch.
 class RNNTLoss(torch.nn.Module):
     """torchaudio.transforms.RNNTLoss counterpart."""
 
-    def __init__(self, blank: int = -1, clamp: float = -1.0, reduction: str = "mean"):
+    def __init__(self, blank: int = -1, clamp: float = -1.0, reduction: str = "mean", fastemit_lambda: float = 0.0,
+                 delay_penalty: float = 0.0):
         super().__init__()
         self.blank, self.clamp, self.reduction = blank, clamp, reduction
+        self.fastemit_lambda, self.delay_penalty = check_latency("RNNTLoss", fastemit_lambda, delay_penalty)
 
     def forward(self, logits, targets, logit_lengths, target_lengths):
-        return rnnt_loss(logits, targets, logit_lengths, target_lengths, self.blank, self.clamp, self.reduction)
+        return rnnt_loss(logits, targets, logit_lengths, target_lengths, self.blank, self.clamp, self.reduction,
+                         fastemit_lambda=getattr(self, "fastemit_lambda", 0.0),
+                         delay_penalty=getattr(self, "delay_penalty", 0.0))
 
 
 def rnnt_lattice(logits, targets, logit_lengths, target_lengths, blank=0):

@@ -34,7 +34,7 @@ from .decoder import DecoderCache
 from .fused import joint_rnnt_loss, plan_buckets
 from .joint import TransducerJoint, _call_precision
 from .rnnt_align import joint_rnnt_forced_align, rnnt_forced_align
-from .rnnt_loss import rnnt_loss
+from .rnnt_loss import check_latency, rnnt_loss
 from .rnnt_simple import rnnt_simple_forced_align
 from . import k2
 from .rnnt_lattice import check_lattice, is_default
@@ -83,7 +83,7 @@ class Transducer(nn.Module):
                  transducer_weight: float = 1.0, attention_weight: float = 0.0, hw_weight: float = 0.4,
                  loss_mode: str = "both", prune_range: int = 0, lm_only_scale: float = 0.0,
                  am_only_scale: float = 0.0, rnnt_type: str = "regular", delay_penalty: float = 0.0,
-                 simple_loss_weight: float = 0.0) -> None:
+                 fastemit_lambda: float = 0.0, rnnt_delay_penalty: float = 0.0, simple_loss_weight: float = 0.0) -> None:
         assert attention_weight + ctc_weight + transducer_weight == 1.0          # transducer.py:46 (kept as is)
         super().__init__()
         # ASRModel part (asr_model.py:38-70): sos/eos are the last class
@@ -147,6 +147,9 @@ class Transducer(nn.Module):
         self.rnnt_type = rnnt_type
         if not is_default(lat, self.delay_penalty) and not self.simple_loss_weight > 0.0:
             raise ValueError("Transducer: rnnt_type / delay_penalty belong to the k2 losses: simple_loss_weight must be > 0")
+        # FastEmit and the delay penalty of the full-lattice term (rnnt_loss / joint_rnnt_loss: plain, fused, bounded and
+        # AMP routes of compute_loss).  `delay_penalty` above stays the k2 losses' own.
+        self.fastemit_lambda, self.rnnt_delay_penalty = check_latency("Transducer", fastemit_lambda, rnnt_delay_penalty)
         self.prune_range = int(prune_range)
         if self.prune_range < 0 or self.prune_range == 1:
             raise ValueError(f"Transducer: prune_range must be 0 (off) or at least 2 (got {prune_range})")
@@ -179,7 +182,8 @@ class Transducer(nn.Module):
             ep, pp = jt.pre_activation(encoder_out, predictor_out)
             loss = joint_rnnt_loss(ep, pp, jt.ffn_out.weight, jt.ffn_out.bias,
                                    rnnt_text, encoder_out_lens, rnnt_text_lengths, blank=self.blank, reduction="mean",
-                                   precision=jt.precision, activation=jt.activation, logits_budget=self._logits_budget())
+                                   precision=jt.precision, activation=jt.activation, logits_budget=self._logits_budget(),
+                                   **self._latency_kwargs())
             return None, loss
         if self._logits_budget() is not None and not getattr(self, "_warned_budget", False):
             # the 16-bit (AMP) joiner modes and the two-op path keep a logits tensor: the budget does not apply to them
@@ -200,7 +204,7 @@ class Transducer(nn.Module):
                     ll, tl = encoder_out_lens[idx].contiguous(), rnnt_text_lengths[idx].contiguous()
                     logits = self.joint(encoder_out[idx, :tg], predictor_out[idx, :ug + 1], ll, tl)
                     parts.append(rnnt_loss(logits, rnnt_text[idx, :ug].contiguous(), ll, tl, blank=self.blank, reduction="none",
-                                           inplace_grad=True))
+                                           inplace_grad=True, **self._latency_kwargs()))
                     index.append(idx)
                 return None, torch.cat(parts).float().mean()
         if skip_padding:
@@ -208,8 +212,16 @@ class Transducer(nn.Module):
         else:
             joint_out = self.joint(encoder_out, predictor_out)
         loss = rnnt_loss(joint_out, rnnt_text.contiguous(), encoder_out_lens.contiguous(),
-                         rnnt_text_lengths.contiguous(), blank=self.blank, reduction="mean")
+                         rnnt_text_lengths.contiguous(), blank=self.blank, reduction="mean", **self._latency_kwargs())
         return joint_out, loss
+
+    def _latency_kwargs(self) -> Dict[str, object]:
+        """fastemit_lambda / delay_penalty for the full-lattice loss; empty for the defaults (and for a model pickled
+        before they existed)."""
+        lam, pen = getattr(self, "fastemit_lambda", 0.0), getattr(self, "rnnt_delay_penalty", 0.0)
+        if lam == 0.0 and pen == 0.0:
+            return {}
+        return {"fastemit_lambda": lam, "delay_penalty": pen}
 
     def _simple_inputs(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, predictor_out: torch.Tensor,
                        text: torch.Tensor, text_lengths: torch.Tensor):
