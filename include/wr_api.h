@@ -883,6 +883,62 @@ int wr_joint_rnnt_grad_lattice(const float *ep_d, const float *pp_d, const float
                                size_t rnnt_workspace_bytes, long long cell_begin, long long cell_end, float *g_out_d,
                                void *workspace_d, size_t workspace_bytes, int w_ready, void *stream);
 
+/* Token-and-duration transducer (TDT; Xu et al., ICML 2023 -- the loss of NeMo's Parakeet-TDT models).  This text is the
+ * contract.  The joiner's output row holds a token part and a duration part; an arc emits a token AND jumps d frames.
+ *
+ * Inputs.  logits [B, Tmax, U1max, V + D], contiguous, of `dtype` (WR_F32 / WR_F16 / WR_BF16): columns [0, V) are token
+ * logits, columns [V, V + D) duration logits.  durations[D]: a HOST array of ints, strictly increasing, 0 <= d <= 8,
+ * 1 <= D <= 9, at least one entry >= 1 (else WR_EINVAL).  targets, logit_lengths (T_b), target_lengths (U_b) as in
+ * wr_rnnt_loss_fwd.  blank in [0, V).  sigma >= 0, finite: NeMo's logit under-normalisation.
+ *
+ * Arc log-probabilities at cell (t,u), t < T_b, u <= U_b:
+ *   tok_k = log_softmax(logits[..., :V])_k - sigma          dur_n = log_softmax(logits[..., V:])_n
+ * Arcs from (t,u), with d = durations[n]:
+ *   blank, d >= 1:                  to (t + d, u),      weight tok_blank + dur_n
+ *   label y_{u+1}, u < U_b, d >= 0: to (t + d, u + 1),  weight tok_label + dur_n
+ * Nodes exist for t < T_b only.  The single terminal is reached by a blank arc from (t, U_b) with t + d == T_b, exactly.
+ * A blank arc with t + d > T_b does not exist; one with t + d == T_b at u < U_b does not exist; a label arc needs
+ * t + d <= T_b - 1.
+ *
+ * cost_b = -log sum over paths from (0,0) to the terminal of exp(sum of arc weights).  No path: cost_b = +inf -- a value,
+ * as for an infeasible band: that utterance's gradient is not finite and the other utterances are unaffected.  T_b = 0:
+ * cost 0, the sweeps' convention.  durations = {1} is k2's modified lattice on the token logits.
+ *
+ * Gradient: the exact derivative of the cost as defined -- no clamp, no FastEmit, no dead-row skip.  With a = alpha(t,u),
+ * ll = -cost, beta(T_b, U_b) = 0, beta(T_b, u != U_b) = -inf:
+ *   ob_n = exp(a + tok_blank + dur_n + beta(t + d, u) - ll)        where that arc exists, else 0
+ *   ol_n = exp(a + tok_label + dur_n + beta(t + d, u + 1) - ll)    where that arc exists, else 0
+ *   Ob = sum ob_n,  Ol = sum ol_n,  O = Ob + Ol = exp(a + beta(t,u) - ll)
+ *   d cost / d token logit k    = softmax_k * O - [k = blank] Ob - [k = label] Ol    (both when the label is the blank)
+ *   d cost / d duration logit n = softmaxD_n * O - (ob_n + ol_n)
+ * A valid cell that no path reaches or leaves (alpha or beta is -inf) gets exactly grad_costs[b] * 0, never NaN.  Cells
+ * with t >= T_b or u > U_b get grad_costs[b] * 0 and are never read.  grads may alias logits (both at the same offset
+ * within a 16-byte line).
+ *
+ * wr_rnnt_tdt_loss_fwd: row statistics, both sweeps (fp64 state), the gradient's per-cell records; costs [B].
+ * wr_rnnt_tdt_loss_bwd: the streamed gradient over a workspace wr_rnnt_tdt_loss_fwd filled for the same arguments.
+ * wr_rnnt_tdt_export_lattice: alpha / beta as plain [B, Tmax, U1max] floats (0 outside the lattice), for tests.
+ * Refused before any launch: D outside [1, 9], a duration outside [0, 8] or not strictly increasing, all durations 0,
+ * negative or non-finite sigma, blank outside [0, V), null pointers (WR_EINVAL); U1max > 1024 or B * (Tmax + U1max - 1) *
+ * U1max >= 2^31 (WR_EUNSUPPORTED); a workspace below wr_rnnt_tdt_workspace_bytes (WR_EWORKSPACE; 0 for a bad shape). */
+size_t wr_rnnt_tdt_workspace_bytes(int B, int Tmax, int U1max, int D);
+
+int wr_rnnt_tdt_loss_fwd(const void *logits_d, int dtype, const int32_t *targets_d, const int32_t *logit_lengths_d,
+                         const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V, int blank,
+                         const int32_t *durations /* [D], host */, int D, double sigma, float *costs_d /* [B] out */,
+                         void *workspace_d, size_t workspace_bytes, void *stream);
+
+int wr_rnnt_tdt_loss_bwd(const void *logits_d, int dtype, const int32_t *targets_d, const int32_t *logit_lengths_d,
+                         const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V, int blank,
+                         const int32_t *durations /* [D], host */, int D, double sigma,
+                         const float *grad_costs_d /* [B] or NULL */, void *grads_d, const void *workspace_d,
+                         size_t workspace_bytes, void *stream);
+
+int wr_rnnt_tdt_export_lattice(const void *workspace_d, size_t workspace_bytes, const int32_t *logit_lengths_d,
+                               const int32_t *target_lengths_d, int B, int Tmax, int U1max, int D,
+                               float *alpha_d /* [B,Tmax,U1max] out */, float *beta_d /* [B,Tmax,U1max] out */,
+                               void *stream);
+
 /* CTC forced alignment: Viterbi over the T x (2S+1) lattice, replacing
  * forced_align, wenet/utils/ctc_util.py:27-83 (CLI wenet/bin/alignment.py:215).  logits [B, Tmax, V]: pre-softmax
  * ctc_lo output, or log-posteriors if normalized != 0 (the reference is handed ctc.log_softmax(...)).

@@ -863,12 +863,66 @@ def bench_pruned(args):
     print(json.dumps(rec), flush=True)
 
 
+def bench_tdt(args):
+    """The token-and-duration loss through the C-ABI on fp32 N(0,1) logits (B, T, U+1, V + D), full lengths, durations
+    0 .. D-1: the forward call (row statistics, sweeps, records) and the gradient pass, each alternating with its sibling of
+    rnnt_loss on the same (B, T, U+1, V + D) tensor with the dead-row skip off (wr_tune_set(14, 0): the TDT kernels have
+    none).  HIP events, median of --steps rounds after one warm-up.  --only tdt runs one TDT step alone (for a profiler)."""
+    import ctypes
+    from wenet_celoss_amd import _lib
+    dev = torch.device("cuda:0")
+    B, T, U, V, D = args.B, args.T, args.U, args.V, args.durations
+    U1, W = U + 1, V + D
+    durs = (ctypes.c_int32 * D)(*range(D))
+    torch.manual_seed(3)
+    logits = torch.empty(B, T, U1, W, device=dev)
+    for b in range(B):
+        logits[b].normal_()
+    grads = torch.empty_like(logits)
+    y = torch.randint(1, V, (B, U), dtype=torch.int32, device=dev)
+    ll = torch.full((B,), T, dtype=torch.int32, device=dev); tl = torch.full((B,), U, dtype=torch.int32, device=dev)
+    gc = torch.full((B,), 1.0 / B, device=dev)
+    tws = _lib.workspace("wr_rnnt_tdt_workspace_bytes", B, T, U1, D, device=dev)
+    rws = _lib.workspace("wr_rnnt_workspace_bytes", B, T, U1, device=dev)
+    tcosts, rcosts = torch.empty(B, device=dev), torch.empty(B, device=dev)
+    fns = {
+        "tdt_fwd": lambda: _lib.call("wr_rnnt_tdt_loss_fwd", logits, _lib.WR_F32, y, ll, tl, B, T, U1, V, 0, durs, D, 0.0,
+                                     tcosts, tws, tws.numel(), device=dev),
+        "rnnt_fwd": lambda: _lib.call("wr_rnnt_loss_fwd", logits, _lib.WR_F32, y, ll, tl, B, T, U1, W, 0, rcosts, rws,
+                                      rws.numel(), device=dev),
+        "tdt_bwd": lambda: _lib.call("wr_rnnt_tdt_loss_bwd", logits, _lib.WR_F32, y, ll, tl, B, T, U1, V, 0, durs, D, 0.0, gc,
+                                     grads, tws, tws.numel(), device=dev),
+        "rnnt_bwd": lambda: _lib.call("wr_rnnt_loss_bwd", logits, _lib.WR_F32, y, ll, tl, B, T, U1, W, 0, -1.0, gc, grads,
+                                      rws, rws.numel(), device=dev),
+    }
+    if args.only == "tdt":
+        fns = {k: f for k, f in fns.items() if k.startswith("tdt")}
+    lib = _lib.load()
+    lib.wr_tune_set(14, 0)
+    try:
+        res = alternating(fns, args.steps)
+    finally:
+        lib.wr_tune_set(14, 1)
+    rec = {"what": "tdt loss vs rnnt_loss (fp32 logits, separate gradient buffer, no dead-row skip)", "shape": [B, T, U1, W],
+           "durations": list(range(D)), "reps": args.steps, "logits_gb": round(logits.numel() * 4 / 1e9, 2),
+           "tdt_workspace_gb": round(tws.numel() / 1e9, 3), "rnnt_workspace_gb": round(rws.numel() / 1e9, 3),
+           "tdt_cost_mean": round(float(tcosts.mean()), 4)}
+    for k, (med, lo, hi) in res.items():
+        rec[k + "_ms"] = round(med, 3)
+        rec[k + "_ms_min_max"] = [round(lo, 3), round(hi, 3)]
+    for k in ("tdt", "rnnt"):
+        if k + "_fwd" in res:
+            rec[k + "_step_ms"] = round(res[k + "_fwd"][0] + res[k + "_bwd"][0], 3)
+    print(json.dumps(rec), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align", "simple", "smoothed", "pruned"])
+    ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align", "simple", "smoothed", "pruned", "tdt"])
+    ap.add_argument("--durations", type=int, default=5, help="tdt: number of durations D (the set is 0 .. D-1)")
     ap.add_argument("--n-steps", type=int, default=64)
     ap.add_argument("--chunks", type=int, default=4)
-    ap.add_argument("--B", type=int, default=None, help="batch size (default 32; simple, smoothed, pruned: 16)")
+    ap.add_argument("--B", type=int, default=None, help="batch size (default 32; simple, smoothed, pruned, tdt: 16)")
     ap.add_argument("--T", type=int, default=1000)
     ap.add_argument("--U", type=int, default=150)
     ap.add_argument("--V", type=int, default=5000)
@@ -895,9 +949,10 @@ if __name__ == "__main__":
     ap.add_argument("--tile", type=int, default=0, help="lane-GEMM tile policy of the decoders (wr_tune_set key 6)")
     a = ap.parse_args()
     if a.B is None:
-        a.B = 16 if a.what in ("simple", "smoothed", "pruned") else 32
+        a.B = 16 if a.what in ("simple", "smoothed", "pruned", "tdt") else 32
     if a.tile:
         from wenet_celoss_amd import _lib
         _lib.load().wr_tune_set(6, a.tile)
     {"joint": bench_joint, "ctc": bench_ctc, "greedy": bench_greedy, "beam": bench_beam, "step": bench_step, "ctcdec": bench_ctcdec, "hotword": bench_hotword,
-     "align": bench_align, "simple": bench_simple, "smoothed": bench_smoothed, "pruned": bench_pruned}[a.what](a)
+     "align": bench_align, "simple": bench_simple, "smoothed": bench_smoothed, "pruned": bench_pruned,
+     "tdt": bench_tdt}[a.what](a)

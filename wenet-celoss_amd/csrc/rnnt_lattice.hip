@@ -13,7 +13,12 @@
 //                             value and its neighbour's previous value (+ arc), by DPP rotate inside a wave and a
 //                             double-buffered LDS slot plus one barrier across waves.  fp64 state, PF rows in flight.
 //   lattice_export_kernel     alpha / beta of either lattice as plain (B, T, U1) floats, for the tests.
+//
+// The token-and-duration transducer (TDT) loss follows at the end of the file: a lattice of its own, whose cells have
+// 2 * D arcs that jump up to 8 frames (include/wr_api.h, "Token-and-duration transducer"; rnnt_tdt.hpp for the arrays).
 #include "rnnt_lattice.hpp"
+#include "rnnt_tdt.hpp"
+#include "row_stream.hpp"
 #include "wr_launch.hpp"
 
 namespace wr {
@@ -263,3 +268,458 @@ extern "C" int wr_rnnt_lattice_export(const void *workspace_d, size_t workspace_
                       logit_lengths_d, target_lengths_d, B, T, U1, w.S, alpha_d, beta_d);
     });
 }
+
+// ---------------------------------------------------------------- token-and-duration transducer (TDT) --
+// Cell (t,u), t < T_b, u <= U_b, of a row of V token logits and D duration logits:
+//   tok_k = log_softmax(row[0 .. V))_k - sigma,   dur_n = log_softmax(row[V .. V + D))_n,   d = durations[n]
+//   blank arc, d >= 1:         (t,u) -> (t + d, u)       tok_blank + dur_n   (t + d == T_b only at u == U_b: the terminal)
+//   label arc, d >= 0, u < U:  (t,u) -> (t + d, u + 1)   tok_label + dur_n   (t + d <= T_b - 1)
+//
+//   tdt_stats_kernel    one wave per row: both log-sum-exps, {tok_blank, tok_label} and the D duration log-probabilities
+//                       into the anti-diagonal arrays.
+//   tdt_sweep_kernel    one workgroup per (utterance, direction), one lane per label column, one anti-diagonal per step
+//                       (a label arc with d = 0 stays on its frame).  fp64 state in two register rings per lane, one
+//                       value exchanged per step (DPP rotate; LDS slot + barrier across waves).
+//   tdt_record_kernel   one thread per cell: the gradient's row constants as 3 + D contiguous floats.
+//   tdt_grad_kernel     one wave per row: pruned_grad_kernel's streamed loop over the token columns, lanes 0 .. D-1 then
+//                       write the duration columns.
+//   tdt_export_kernel   alpha / beta as plain (B, T, U1) floats, for the tests.
+namespace wr {
+namespace {
+
+template <typename T, bool NT, int UN>
+__global__ __launch_bounds__(256) void tdt_stats_kernel(
+    const T *__restrict__ logits, const int32_t *__restrict__ targets, const int32_t *__restrict__ llens,
+    const int32_t *__restrict__ tlens, long nrows, int Tmax, int U1max, int V, int D, int blank, float sigma, int S,
+    float2 *__restrict__ tok, float *__restrict__ dur, float *__restrict__ denom)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long stride = (long)gridDim.x * (blockDim.x >> 6);
+    const int cells = Tmax * U1max;
+    for (long r = (long)blockIdx.x * (blockDim.x >> 6) + wid; r < nrows; r += stride) {
+        const int b = (int)(r / cells);
+        const int c = (int)(r - (long)b * cells);
+        const int t = c / U1max, u = c - t * U1max;
+        const int Tb = clampi(llens[b], 0, Tmax), Ub = clampi(tlens[b], 0, U1max - 1);
+        if (t >= Tb || u > Ub) continue;                      // padding is never read
+        const T *row = logits + (size_t)r * (V + D);
+        const float d = wave_row_lse<T, NT, UN>(row, V, lane);
+        // the D <= 9 duration logits: one per lane
+        float x = kNegInf;
+        if (lane < D) x = (float)row[V + lane];
+        const float y = x * kLog2e;
+        const float M = wave_max(y);
+        const float s = wave_sum(lane < D ? fast_exp2(y - M) : 0.f);
+        const float dd = (M + fast_log2(s)) * kLn2;
+        const size_t k = ((size_t)b * S + t + u) * U1max + u;
+        if (lane < D) dur[k * D + lane] = x - dd;
+        if (lane == 0) {
+            const float xb = (float)row[blank];
+            float em = kNegInf;
+            if (u < Ub) {
+                const int lab = targets[(size_t)b * (U1max - 1) + u];
+                if (lab >= 0 && lab < V) em = ((float)row[lab] - d) - sigma;
+            }
+            denom[r] = d;
+            tok[k] = make_float2((xb - d) - sigma, em);
+        }
+    }
+}
+
+// the arcs of one cell as a sweep lane holds them: the duration log-probabilities by jump d (slots of absent jumps unused)
+struct TdtArc {
+    float tb, tl;
+    float w[kTdtMaxD];
+};
+
+// Forward, lane u on anti-diagonal s at cell (t = s - u, u): own[j] / nbr[j] collect the mass that arcs of finished cells
+// of this column send into (t + j, u) / (t + j, u + 1).  alpha(t,u) = logadd(own[0], what lane u-1 sent a step ago); the
+// cell then pushes its 2 * D arcs into the rings, hands nbr[0] -- complete, every (t' <= t, u) is done -- to lane u + 1, and
+// both rings shift by one frame.  The terminal is own[0] of lane U_b at t = T_b: blank arcs only, exactly at T_b.
+// Backward: own[j] = beta(t + j, u) with beta(T_b, U_b) = 0 and -inf beyond, nb[j] = beta(t + j, u + 1) as received (an
+// idle lane sends -inf, so no label arc reaches frame T_b).  Ring positions are compile-time: the loops over d = 0 .. 8
+// unroll against the wave-uniform table `dd`.
+template <int PF>
+__global__ __launch_bounds__(kRnntMaxCols) void tdt_sweep_kernel(
+    const float2 *__restrict__ tok, const float *__restrict__ dur, const int32_t *__restrict__ llens,
+    const int32_t *__restrict__ tlens, int Tmax, int U1max, int S, const TdtDur dd, double *__restrict__ alpha_skew,
+    double *__restrict__ beta_skew, double *__restrict__ ll_out, double *__restrict__ cost_ws,
+    float *__restrict__ costs_out, double *__restrict__ dump)
+{
+    constexpr double NEG = (double)kNegInf;
+    __shared__ double xch[2][kRnntMaxCols / kWave];
+    const int b = blockIdx.x;
+    const bool backward = blockIdx.y != 0;
+    const int u = threadIdx.x;
+    const int lane = u & (kWave - 1), wave = u >> 6;
+    const int nw = blockDim.x >> 6;
+    const int T = clampi(llens[b], 0, Tmax), U = clampi(tlens[b], 0, U1max - 1);
+
+    if (T == 0) {
+        if (u == 0) {
+            if (backward) { cost_ws[b] = 0.0; costs_out[b] = 0.f; } else ll_out[b] = 0.0;
+        }
+        return;
+    }
+    const bool in_row = u < U1max;
+    const int col = in_row ? u : U1max - 1;
+    const bool ucol = in_row && u <= U;
+    const size_t ub = (size_t)b * S * U1max;
+    const int D = dd.D;
+    const int nsteps = T + U;                // anti-diagonals 0 .. T + U - 1 hold this utterance's cells
+    double *__restrict__ out = (backward ? beta_skew : alpha_skew) + ub + col;
+    double *__restrict__ sink = dump + ((size_t)b * 2 + (backward ? 1 : 0)) * kRnntMaxCols + u;
+
+    // the arcs of this column's cell on anti-diagonal s, its frame clamped into [0, T): always a position of the arrays
+    auto load_arc = [&](int s) -> TdtArc {
+        int t = s - col;
+        t = t < 0 ? 0 : (t >= T ? T - 1 : t);
+        const size_t k = ub + (size_t)(t + col) * U1max + col;
+        TdtArc a;
+        const float2 p = tok[k];
+        a.tb = p.x;
+        a.tl = p.y;
+#pragma unroll
+        for (int d = 0; d < kTdtMaxD; ++d) a.w[d] = dd.slot[d] >= 0 ? dur[k * D + dd.slot[d]] : 0.f;
+        return a;
+    };
+
+    TdtArc ring[PF];
+    double own[kTdtMaxD], nbr[kTdtMaxD];
+#pragma unroll
+    for (int j = 0; j < kTdtMaxD; ++j) own[j] = nbr[j] = NEG;
+    double send = NEG, result = NEG;
+
+    if (!backward) {
+#pragma unroll
+        for (int i = 0; i < PF; ++i) ring[i] = load_arc(i);
+        for (int base = 0; base <= nsteps; base += PF) {          // the cells' anti-diagonals and the terminal's
+#pragma unroll
+            for (int i = 0; i < PF; ++i) {
+                const int s = base + i, t = s - u;                // steps s > T + U have no active lane
+                const TdtArc cur = ring[i];
+                ring[i] = load_arc(s + PF);
+                double recv = lane_rotate_up_d(send);
+                if (lane == 0)       // step 0 has nothing to receive (the LDS slots are still unwritten)
+                    recv = (s == 0 || wave == 0) ? NEG : xch[(s + 1) & 1][wave - 1];
+                const bool active = ucol & (t >= 0) & (t < T);
+                const double own0 = own[0];
+                double v = log_add_exp_d(own0, recv);
+                v = (s == 0 && u == 0) ? 0.0 : v;                 // the origin
+                result = (t == T && u == U) ? own0 : result;      // the terminal: blank arcs that end exactly at T
+                v = active ? v : NEG;
+                double *dst = active ? out + (size_t)s * U1max : sink;
+                *dst = v;
+                const double ab = v + (double)(active ? cur.tb : 0.f);
+                const double al = (u < U) ? v + (double)(active ? cur.tl : 0.f) : NEG;
+#pragma unroll
+                for (int d = 0; d < kTdtMaxD; ++d) {
+                    if (dd.slot[d] >= 0) {
+                        const double w = (double)(active ? cur.w[d] : 0.f);
+                        if (d >= 1) own[d] = log_add_exp_d(own[d], ab + w);
+                        nbr[d] = log_add_exp_d(nbr[d], al + w);
+                    }
+                }
+                send = nbr[0];
+#pragma unroll
+                for (int j = 0; j + 1 < kTdtMaxD; ++j) { own[j] = own[j + 1]; nbr[j] = nbr[j + 1]; }
+                own[kTdtMaxD - 1] = nbr[kTdtMaxD - 1] = NEG;
+                if (lane == kWave - 1) xch[s & 1][wave] = send;
+                if (nw > 1) __syncthreads();
+            }
+        }
+        if (u == U) ll_out[b] = result;
+    } else {
+        const int s0 = nsteps - 1;                // lane U starts at (T - 1, U), below the terminal
+        own[1] = (u == U) ? 0.0 : NEG;            // beta(T, U) = 0
+        if (lane == 0) xch[(s0 + 1) & 1][wave] = NEG;
+        if (nw > 1) __syncthreads();
+#pragma unroll
+        for (int i = 0; i < PF; ++i) ring[i] = load_arc(s0 - i);
+        for (int base = 0; base < nsteps; base += PF) {
+#pragma unroll
+            for (int i = 0; i < PF; ++i) {
+                const int s = s0 - (base + i), t = s - u;         // steps s < 0 have no active lane
+                const TdtArc cur = ring[i];
+                ring[i] = load_arc(s - PF);
+                double recv = lane_rotate_down_d(send);
+                if (lane == kWave - 1) recv = (wave == nw - 1) ? NEG : xch[(s + 1) & 1][wave + 1];
+#pragma unroll
+                for (int j = kTdtMaxD - 1; j >= 1; --j) nbr[j] = nbr[j - 1];
+                nbr[0] = recv;                                    // beta(t, u + 1)
+                const bool active = ucol & (t >= 0) & (t < T);
+                const float tb = active ? cur.tb : 0.f;
+                const float tl = (active && u < U) ? cur.tl : kNegInf;
+                double acc = NEG;
+#pragma unroll
+                for (int d = 0; d < kTdtMaxD; ++d) {
+                    if (dd.slot[d] >= 0) {
+                        const float w = active ? cur.w[d] : 0.f;
+                        if (d >= 1) acc = log_add_exp_d(acc, ((double)tb + (double)w) + own[d]);
+                        acc = log_add_exp_d(acc, ((double)tl + (double)w) + nbr[d]);
+                    }
+                }
+                const double v = active ? acc : NEG;
+                double *dst = active ? out + (size_t)s * U1max : sink;
+                *dst = v;
+                result = (s == 0 && u == 0) ? v : result;
+                send = v;
+#pragma unroll
+                for (int j = kTdtMaxD - 1; j >= 2; --j) own[j] = own[j - 1];
+                own[1] = v;
+                if (lane == 0) xch[s & 1][wave] = send;
+                if (nw > 1) __syncthreads();
+            }
+        }
+        if (u == 0) { cost_ws[b] = -result; costs_out[b] = (float)(-result); }
+    }
+}
+
+// One thread per cell.  With ll = -cost, a = alpha(t,u):
+//   ob_n = exp(a + tok_blank + dur_n + beta(t + d, u) - ll),   ol_n = exp(a + tok_label + dur_n + beta(t + d, u + 1) - ll)
+// where the arc exists, 0 elsewhere;  O = exp(a + beta(t,u) - ll).
+//   rec[0] = a + beta(t,u) - ll - denom    softmax_k * O = exp(logit_k + rec[0])
+//   rec[1] = sum ob_n,  rec[2] = sum ol_n  what the blank / label column subtracts
+//   rec[3 + n] = exp(dur_n) * O - (ob_n + ol_n)     d cost / d duration logit n
+// Everything in fp64, rounded once.  A cell no path crosses has a or beta = -inf against a finite ll: exact zeros.
+__global__ __launch_bounds__(256) void tdt_record_kernel(
+    const float2 *__restrict__ tok, const float *__restrict__ dur, const float *__restrict__ denom,
+    const double *__restrict__ alpha_skew, const double *__restrict__ beta_skew, const double *__restrict__ cost_ws,
+    const int32_t *__restrict__ llens, const int32_t *__restrict__ tlens, int B, int Tmax, int U1max, int S,
+    const TdtDur dd, float *__restrict__ rec)
+{
+    constexpr double NEG = (double)kNegInf;
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= (long)B * Tmax * U1max) return;
+    const int cells = Tmax * U1max;
+    const int b = (int)(r / cells);
+    const int c = (int)(r - (long)b * cells);
+    const int t = c / U1max, u = c - t * U1max;
+    const int T = clampi(llens[b], 0, Tmax), U = clampi(tlens[b], 0, U1max - 1);
+    if (t >= T || u > U) return;
+    const int D = dd.D;
+    const size_t ub = (size_t)b * S * U1max;
+    const size_t k = ub + (size_t)(t + u) * U1max + u;
+    const double a = alpha_skew[k], be = beta_skew[k], ll = -cost_ws[b];
+    const float2 p = tok[k];
+    const double base = a - ll;
+    const double O = exp(base + be);
+    float *o = rec + (size_t)r * (kTdtRec + D);
+    double Ob = 0.0, Ol = 0.0;
+#pragma unroll
+    for (int d = 0; d < kTdtMaxD; ++d) {
+        const int n = dd.slot[d];
+        if (n < 0) continue;
+        const double w = (double)dur[k * D + n];
+        double bb = NEG, bl = NEG;
+        if (d >= 1) {
+            if (t + d < T) bb = beta_skew[ub + (size_t)(t + d + u) * U1max + u];
+            else if (t + d == T && u == U) bb = 0.0;
+        }
+        if (u < U && t + d < T) bl = beta_skew[ub + (size_t)(t + d + u + 1) * U1max + (u + 1)];
+        const double ob = bb == NEG ? 0.0 : exp(((base + (double)p.x) + w) + bb);
+        const double ol = bl == NEG ? 0.0 : exp(((base + (double)p.y) + w) + bl);
+        Ob += ob;
+        Ol += ol;
+        o[kTdtRec + n] = (float)(exp(w) * O - (ob + ol));
+    }
+    o[0] = (float)((base + be) - (double)denom[r]);
+    o[1] = (float)Ob;
+    o[2] = (float)Ol;
+}
+
+// pruned_grad_kernel's streamed loop on rows of V + D logits: g_k = exp(logit_k + rec[0]) over the V token columns, the
+// blank and the label column minus rec[1] / rec[2] (both when they coincide), then lanes 0 .. D-1 write rec[3 + n] into the
+// duration columns.  No clamp, no dead-row skip.  In place: a lane stores an element only after loading it, and the
+// duration columns are not read at all.
+template <typename T, bool NT, bool NTS, int UN>
+__global__ __launch_bounds__(256) void tdt_grad_kernel(
+    const T *logits, const int32_t *__restrict__ targets, const int32_t *__restrict__ llens,
+    const int32_t *__restrict__ tlens, long nrows, int Tmax, int U1max, int V, int D, int blank,
+    const float *__restrict__ rec, const float *__restrict__ grad_costs, T *grads)
+{
+    typedef typename VecOf<T>::type vec_t;
+    constexpr int N = VecOf<T>::N;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long stride = (long)gridDim.x * (blockDim.x >> 6);
+    const int cells = Tmax * U1max;
+    const int W = V + D;
+    for (long r = (long)blockIdx.x * (blockDim.x >> 6) + wid; r < nrows; r += stride) {
+        const int b = (int)(r / cells);
+        const int c = (int)(r - (long)b * cells);
+        const int t = c / U1max, u = c - t * U1max;
+        const int T_ = clampi(llens[b], 0, Tmax), U = clampi(tlens[b], 0, U1max - 1);
+        const T *row = logits + (size_t)r * W;
+        T *grow = grads + (size_t)r * W;
+        const float go = grad_costs ? grad_costs[b] : 1.f;
+
+        const bool valid = t < T_ && u <= U;
+        if (__builtin_amdgcn_readfirstlane(valid ? 0 : 1)) {          // outside the lattice: grad_costs[b] * 0, logits unread
+            const RowSplit<T> sp(row, W);
+            vec_t *gbody = reinterpret_cast<vec_t *>(grow + sp.h);
+            const T val = (T)(go * 0.f);
+            vec_t z;
+#pragma unroll
+            for (int q = 0; q < N; ++q) z[q] = val;
+            if (lane < sp.h) grow[lane] = val;
+            if (lane < sp.tail) grow[sp.h + N * sp.nv + lane] = val;
+            for (int i = lane; i < sp.nv; i += kWave) stv<NTS>(z, gbody + i);
+            continue;
+        }
+        const RowSplit<T> sp(row, V);
+        const int h = sp.h, nv = sp.nv, tail = sp.tail;
+        const vec_t *body = reinterpret_cast<const vec_t *>(row + h);
+        vec_t *gbody = reinterpret_cast<vec_t *>(grow + h);
+        const float *rc = rec + (size_t)r * (kTdtRec + D);            // one contiguous record
+        const float c2 = rc[0] * kLog2e;
+        const float blank_sub = rc[1], lab_sub = rc[2];
+        const float dval = lane < D ? rc[kTdtRec + lane] : 0.f;
+        const int lab = u < U ? targets[(size_t)b * (U1max - 1) + u] : -1;
+
+        auto fix = [&](float val, int v) -> float {
+            if (v == blank) val -= blank_sub;
+            if (v == lab) val -= lab_sub;
+            return val;
+        };
+        if (lane < h) {
+            const float x = (float)row[lane];
+            grow[lane] = (T)(fix(fast_exp2(fmaf(x, kLog2e, c2)), lane) * go);
+        }
+        if (lane < tail) {
+            const int v = h + N * nv + lane;
+            const float x = (float)row[v];
+            grow[v] = (T)(fix(fast_exp2(fmaf(x, kLog2e, c2)), v) * go);
+        }
+        const int iblk = (blank >= h) ? ((blank - h) / N) : -1;
+        const int ilab = (lab >= h) ? ((lab - h) / N) : -1;
+        auto dov = [&](int i, const vec_t x) {
+            float g[N];
+#pragma unroll
+            for (int q = 0; q < N; ++q) g[q] = fast_exp2(fmaf((float)x[q], kLog2e, c2));
+            if (i == iblk || i == ilab) {
+                const int v0 = h + N * i;
+#pragma unroll
+                for (int q = 0; q < N; ++q) g[q] = fix(g[q], v0 + q);
+            }
+            vec_t o;
+#pragma unroll
+            for (int q = 0; q < N; ++q) o[q] = (T)(g[q] * go);
+            stv<NTS>(o, gbody + i);
+        };
+        int i = lane;
+        for (; i + (UN - 1) * kWave < nv; i += UN * kWave) {
+            vec_t x[UN];
+#pragma unroll
+            for (int q = 0; q < UN; ++q) x[q] = ldv<NT>(body + i + q * kWave);
+#pragma unroll
+            for (int q = 0; q < UN; ++q) dov(i + q * kWave, x[q]);
+        }
+        if (i < nv) {                                    // remainder (fewer than UN vectors per lane): one guarded batch
+            vec_t x[UN];
+#pragma unroll
+            for (int q = 0; q < UN; ++q)
+                if (i + q * kWave < nv) x[q] = ldv<NT>(body + i + q * kWave);
+#pragma unroll
+            for (int q = 0; q < UN; ++q)
+                if (i + q * kWave < nv) dov(i + q * kWave, x[q]);
+        }
+        if (lane < D) grow[V + lane] = (T)(dval * go);
+    }
+}
+
+__global__ __launch_bounds__(256) void tdt_export_kernel(
+    const double *__restrict__ alpha_skew, const double *__restrict__ beta_skew, const int32_t *__restrict__ llens,
+    const int32_t *__restrict__ tlens, int B, int T, int U1, int S, float *__restrict__ alpha, float *__restrict__ beta)
+{
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= (long)B * T * U1) return;
+    const int cells = T * U1;
+    const int b = (int)(r / cells);
+    const int c = (int)(r - (long)b * cells);
+    const int t = c / U1, u = c - t * U1;
+    float a = 0.f, be = 0.f;
+    if (t < clampi(llens[b], 0, T) && u <= clampi(tlens[b], 0, U1 - 1)) {
+        const size_t k = (size_t)b * S * U1 + (size_t)(t + u) * U1 + u;
+        a = (float)alpha_skew[k];
+        be = (float)beta_skew[k];
+    }
+    alpha[r] = a;
+    beta[r] = be;
+}
+
+}  // namespace
+
+int tdt_loss_fwd_body(const void *logits_d, int dtype, const int32_t *targets_d, const int32_t *logit_lengths_d,
+                      const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V, int blank, const TdtDur &dur,
+                      double sigma, float *costs_d, void *workspace_d, hipStream_t st)
+{
+    const int D = dur.D;
+    const TdtWs w = tdt_ws_layout(B, Tmax, U1max, D);
+    char *ws = static_cast<char *>(workspace_d);
+    float2 *tok = reinterpret_cast<float2 *>(ws + w.tok_off);
+    float *durp = reinterpret_cast<float *>(ws + w.dur_off);
+    float *denom = reinterpret_cast<float *>(ws + w.denom_off);
+    double *alpha = reinterpret_cast<double *>(ws + w.alpha_off), *beta = reinterpret_cast<double *>(ws + w.beta_off);
+    double *cost = reinterpret_cast<double *>(ws + w.cost_off);
+    const long nrows = (long)B * Tmax * U1max;
+    const size_t row_bytes = (size_t)(V + D) * (dtype == WR_F32 ? 4 : 2);
+    const dim3 grid1(stream_grid(nrows, tune_get(kTuneLseBlocksPerCu), row_bytes, 16 * 1024));
+    const bool nt = (tune_get(kTuneNonTemporal) & 4) != 0;
+    WR_TRY(with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return with_bool(nt, [&](auto nt_c) {
+            return with_int<16, 8, 4>(unroll_of(kTuneLseUnroll), [&](auto un) {
+                return launch("tdt_stats_kernel", tdt_stats_kernel<T, nt_c.value, un.value>, grid1, dim3(256), 0, st,
+                              static_cast<const T *>(logits_d), targets_d, logit_lengths_d, target_lengths_d, nrows, Tmax,
+                              U1max, V, D, blank, (float)sigma, w.S, tok, durp, denom);
+            });
+        });
+    }));
+    WR_TRY(launch("tdt_sweep_kernel", tdt_sweep_kernel<4>, dim3(B, 2), dim3(64 * w.K), 0, st, tok, durp, logit_lengths_d,
+                  target_lengths_d, Tmax, U1max, w.S, dur, alpha, beta, reinterpret_cast<double *>(ws + w.ll_off), cost,
+                  costs_d, reinterpret_cast<double *>(ws + w.dump_off)));
+    return launch("tdt_record_kernel", tdt_record_kernel, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, st, tok, durp,
+                  denom, alpha, beta, cost, logit_lengths_d, target_lengths_d, B, Tmax, U1max, w.S, dur,
+                  reinterpret_cast<float *>(ws + w.rec_off));
+}
+
+int tdt_loss_bwd_body(const void *logits_d, int dtype, const int32_t *targets_d, const int32_t *logit_lengths_d,
+                      const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V, int blank, int D,
+                      const float *grad_costs_d, void *grads_d, const void *workspace_d, hipStream_t st)
+{
+    const TdtWs w = tdt_ws_layout(B, Tmax, U1max, D);
+    const char *ws = static_cast<const char *>(workspace_d);
+    const long nrows = (long)B * Tmax * U1max;
+    const size_t row_bytes = (size_t)(V + D) * (dtype == WR_F32 ? 4 : 2);
+    const dim3 grid3(stream_grid(nrows, tune_get(kTuneGradBlocksPerCu), row_bytes, 68 * 1024));
+    const bool nt = (tune_get(kTuneNonTemporal) & 1) != 0;
+    const bool nts = (tune_get(kTuneNonTemporal) & 2) != 0;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return with_bool(nt, [&](auto nt_c) {
+            return with_int<16, 8, 4>(unroll_of(kTuneGradUnroll), [&](auto un) {
+                return with_bool(nts, [&](auto nts_c) {
+                    return launch("tdt_grad_kernel", tdt_grad_kernel<T, nt_c.value, nts_c.value, un.value>, grid3, dim3(256),
+                                  0, st, static_cast<const T *>(logits_d), targets_d, logit_lengths_d, target_lengths_d,
+                                  nrows, Tmax, U1max, V, D, blank, reinterpret_cast<const float *>(ws + w.rec_off),
+                                  grad_costs_d, static_cast<T *>(grads_d));
+                });
+            });
+        });
+    });
+}
+
+int tdt_export_body(const void *workspace_d, const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B,
+                    int Tmax, int U1max, int D, float *alpha_d, float *beta_d, hipStream_t st)
+{
+    const TdtWs w = tdt_ws_layout(B, Tmax, U1max, D);
+    const char *ws = static_cast<const char *>(workspace_d);
+    return launch("tdt_export_kernel", tdt_export_kernel, dim3((unsigned)(((long)B * Tmax * U1max + 255) / 256)), dim3(256),
+                  0, st, reinterpret_cast<const double *>(ws + w.alpha_off),
+                  reinterpret_cast<const double *>(ws + w.beta_off), logit_lengths_d, target_lengths_d, B, Tmax, U1max, w.S,
+                  alpha_d, beta_d);
+}
+
+}  // namespace wr

@@ -40,6 +40,49 @@ def basic_greedy_search(model: torch.nn.Module, encoder_out: torch.Tensor, encod
     return dec.greedy(encoder_out, lens, n_steps=n_steps, blank=model.blank)
 
 
+def tdt_greedy_search(model: torch.nn.Module, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor,
+                      n_steps: int = 64) -> List[List[int]]:
+    """Greedy search of a token-and-duration model (`model.tdt_durations`; the joiner's row is `vocab_size` token logits
+    followed by one logit per duration): one utterance, host-driven over the HIP step kernels (predictor.forward_step,
+    the joiner).  At frame t: k = argmax of the token part, d = durations[argmax of the duration part]; a blank moves
+    max(d, 1) frames on; a label is emitted, steps the predictor and moves d frames on; after `n_steps` labels without a
+    frame advance the search moves one frame on."""
+    assert encoder_out.size(0) == 1
+    durations = model.tdt_durations
+    V = model.vocab_size
+    dev = encoder_out.device
+    padding = torch.zeros(1, 1, device=dev)
+    tok = torch.tensor([[model.blank]], device=dev)
+    cache = model.predictor.init_state(1, method="zero", device=dev)
+    new_cache = cache
+    T = int(encoder_out_lens)
+    t, emitted_in_frame, step = 0, 0, True
+    hyps: List[int] = []
+    pred_out = None
+    with torch.no_grad():
+        while t < T:
+            if step:
+                pred_out, new_cache = model.predictor.forward_step(tok, padding, cache)
+                step = False
+            row = model.joint(encoder_out[:, t:t + 1, :].contiguous(), pred_out.contiguous()).reshape(-1).float()
+            k, n = torch.stack([row[:V].argmax(), row[V:].argmax()]).tolist()        # one host sync per step
+            d = durations[n]
+            if k == model.blank:
+                t += max(d, 1)
+                emitted_in_frame = 0
+                continue
+            hyps.append(k)
+            tok = torch.tensor([[k]], device=dev)
+            cache = new_cache
+            step = True
+            emitted_in_frame = 0 if d > 0 else emitted_in_frame + 1
+            t += d
+            if emitted_in_frame >= n_steps:
+                t += 1
+                emitted_in_frame = 0
+    return [hyps]
+
+
 # ------------------------------------------------------------------------------------------------
 # The fork's hot-word variants (SURVEY.md section 8f item 3): wenet/transducer/search/greedy_search.py
 #   basic_greedy_search       :34-176   loss_mode 'pred'  -> ([hyps], dist, gate trace)

@@ -39,7 +39,9 @@ from .rnnt_simple import rnnt_simple_forced_align
 from . import k2
 from .rnnt_lattice import check_lattice, is_default
 from .rnnt_pruned import rnnt_loss_pruned
-from .search.greedy_search import basic_greedy_search, basic_greedy_search_both, basic_greedy_search_hw
+from .rnnt_tdt import check_tdt, rnnt_tdt_loss
+from .search.greedy_search import (basic_greedy_search, basic_greedy_search_both, basic_greedy_search_hw,
+                                   tdt_greedy_search)
 from .search.prefix_beam_search import PrefixBeamSearch
 
 
@@ -83,7 +85,8 @@ class Transducer(nn.Module):
                  transducer_weight: float = 1.0, attention_weight: float = 0.0, hw_weight: float = 0.4,
                  loss_mode: str = "both", prune_range: int = 0, lm_only_scale: float = 0.0,
                  am_only_scale: float = 0.0, rnnt_type: str = "regular", delay_penalty: float = 0.0,
-                 fastemit_lambda: float = 0.0, rnnt_delay_penalty: float = 0.0, simple_loss_weight: float = 0.0) -> None:
+                 fastemit_lambda: float = 0.0, rnnt_delay_penalty: float = 0.0, tdt_durations=None,
+                 tdt_sigma: float = 0.0, simple_loss_weight: float = 0.0) -> None:
         assert attention_weight + ctc_weight + transducer_weight == 1.0          # transducer.py:46 (kept as is)
         super().__init__()
         # ASRModel part (asr_model.py:38-70): sos/eos are the last class
@@ -157,6 +160,24 @@ class Transducer(nn.Module):
             raise ValueError("Transducer: prune_range > 0 takes its ranges from the simple loss: simple_loss_weight must be > 0")
         if self.prune_range > 0 and not hasattr(joint, "forward_pruned"):
             raise ValueError("Transducer: prune_range > 0 needs a joiner with forward_pruned (TransducerJoint)")
+        # token-and-duration transducer (rnnt_tdt.py): the joiner has vocab_size + D outputs, the last D of them the
+        # duration logits, and loss_rnnt is rnnt_tdt_loss on its logits.  CTC, attention and the simple loss keep
+        # vocab_size.  None: a plain transducer.
+        self.tdt_durations, self.tdt_sigma = None, 0.0
+        if tdt_durations is not None:
+            self.tdt_durations, self.tdt_sigma = check_tdt("Transducer", tdt_durations, tdt_sigma)
+            for name, on in (("prune_range", self.prune_range > 0), ("fastemit_lambda", self.fastemit_lambda > 0.0),
+                             ("rnnt_delay_penalty", self.rnnt_delay_penalty > 0.0),
+                             ("a context_bias module", context_bias is not None)):
+                if on:
+                    raise ValueError(f"Transducer: tdt_durations cannot be combined with {name}")
+            outputs = getattr(getattr(joint, "ffn_out", None), "out_features", None)
+            if outputs != vocab_size + len(self.tdt_durations):
+                raise ValueError(f"Transducer: with tdt_durations={self.tdt_durations} the joiner must have vocab_size + "
+                                 f"{len(self.tdt_durations)} = {vocab_size + len(self.tdt_durations)} outputs (it has "
+                                 f"{outputs})")
+        elif float(tdt_sigma) != 0.0:
+            raise ValueError("Transducer: tdt_sigma belongs to the TDT loss: tdt_durations must be set")
 
     # ------------------------------------------------------------- training --
     def _logits_budget(self) -> Optional[int]:
@@ -177,6 +198,13 @@ class Transducer(nn.Module):
         rnnt_text = torch.where(rnnt_text == self.ignore_id, 0, rnnt_text).to(torch.int32)
         rnnt_text_lengths = text_lengths.to(torch.int32)
         encoder_out_lens = encoder_out_lens.to(torch.int32)
+        if self._is_tdt():
+            # TDT: the joiner's vocab_size + D logits, in whatever precision it produces them (16-bit under AMP)
+            joint_out = self.joint(encoder_out, predictor_out)
+            loss = rnnt_tdt_loss(joint_out, rnnt_text.contiguous(), encoder_out_lens.contiguous(),
+                                 rnnt_text_lengths.contiguous(), self.tdt_durations, blank=self.blank, sigma=self.tdt_sigma,
+                                 reduction="mean", inplace_grad=True)
+            return None, loss
         if self._can_fuse_loss():
             jt = self.joint
             ep, pp = jt.pre_activation(encoder_out, predictor_out)
@@ -271,7 +299,17 @@ class Transducer(nn.Module):
                                      **self._lattice_kwargs())
         return loss_rnnt, loss_simple
 
+    def _is_tdt(self) -> bool:
+        return getattr(self, "tdt_durations", None) is not None      # absent on a model pickled before it existed
+
+    def _refuse_tdt(self, what: str) -> None:
+        if self._is_tdt():
+            raise NotImplementedError(f"Transducer.{what}: a TDT model (tdt_durations={self.tdt_durations}) decodes with "
+                                      "greedy_search only; the device-resident decoders read vocab_size columns")
+
     def _can_fuse_loss(self) -> bool:
+        if self._is_tdt():
+            return False
         jt = self.joint
         # the AMP single-term modes keep 16-bit logits ("autocast" is one of them under autocast only)
         return (self.fused_loss and isinstance(jt, TransducerJoint)
@@ -600,6 +638,7 @@ class Transducer(nn.Module):
                     ctc_weight: float = 0.3, transducer_weight: float = 0.7, **_ignored):
         """transducer.py:332-377.  Extra keyword arguments (recognize.py:303-304 passes context_list /
         context_lengths, which the reference signature lacks) are accepted and ignored."""
+        self._refuse_tdt("beam_search")
         self.init_bs()
         beam, _ = self.bs.prefix_beam_search(speech, speech_lengths, decoding_chunk_size, beam_size,
                                              num_decoding_left_chunks, simulate_streaming, ctc_weight,
@@ -619,6 +658,8 @@ class Transducer(nn.Module):
             assert hasattr(self.decoder, "right_decoder")
         device = speech.device
         assert speech.shape[0] == 1
+        if beam_search_type == "transducer":
+            self._refuse_tdt("transducer_attention_rescoring(beam_search_type=\"transducer\")")
         self.init_bs()
         if beam_search_type == "transducer":
             beam, encoder_out = self.bs.prefix_beam_search(speech, speech_lengths, decoding_chunk_size=decoding_chunk_size,
@@ -665,6 +706,8 @@ class Transducer(nn.Module):
         _ = simulate_streaming
         encoder_out, encoder_mask = self.encoder(speech, speech_lengths, decoding_chunk_size, num_decoding_left_chunks)
         encoder_out_lens = encoder_mask.squeeze(1).sum()
+        if self._is_tdt():                                  # token-and-duration model: host-driven loop, batch 1
+            return tdt_greedy_search(self, encoder_out, encoder_out_lens, n_steps=n_steps), 0
         if self.context_bias is None:                       # no hot-word module: the variants reduce to the core loop
             return basic_greedy_search(self, encoder_out, encoder_out_lens, n_steps=n_steps), 0
         if self.loss_mode == "pred":                        # transducer.py:559-567
@@ -681,6 +724,7 @@ class Transducer(nn.Module):
     def greedy_search_batch(self, speech: torch.Tensor, speech_lengths: torch.Tensor, decoding_chunk_size: int = -1,
                             num_decoding_left_chunks: int = -1, n_steps: int = 64) -> List[List[int]]:
         """Extension: N independent streams decoded together (BASELINE config 3)."""
+        self._refuse_tdt("greedy_search_batch")
         encoder_out, encoder_mask = self.encoder(speech, speech_lengths, decoding_chunk_size, num_decoding_left_chunks)
         return basic_greedy_search(self, encoder_out, encoder_mask.squeeze(1).sum(1), n_steps=n_steps)
 
@@ -693,6 +737,7 @@ class Transducer(nn.Module):
                               reference_new_cache: bool = True):
         """Decode the next chunk of encoder frames of every stream: encoder_out (N, Tchunk, E) -> tokens of this
         chunk (List[int] for one stream as in the reference, List[List[int]] for several)."""
+        self._refuse_tdt("forward_greedy_search")
         st = getattr(self, "_stream", None)
         if st is None:
             self.reset_cache(encoder_out.size(0))
