@@ -939,6 +939,45 @@ int wr_rnnt_tdt_export_lattice(const void *workspace_d, size_t workspace_bytes, 
                                float *alpha_d /* [B,Tmax,U1max] out */, float *beta_d /* [B,Tmax,U1max] out */,
                                void *stream);
 
+/* TDT greedy search: the greedy decode of a token-and-duration model, batched, with every decision on the device.  This
+ * text is the contract.
+ *
+ * The handle is a wr_decoder built from the model's own modules, so its vocab_size is the joiner's width V + D: columns
+ * [0, V) of a logits row are token logits, columns [V, V + D) duration logits, V = vocab_size - D the token vocabulary.
+ * durations[D]: a HOST array with the loss's contract (1 <= D <= 9, values in [0, 8], strictly increasing, at least one
+ * >= 1).  enc_out [N, T, E] fp32, enc_lens [N]; T_n = min(enc_lens[n], T).  blank in [0, V).
+ *
+ * Every stream n follows this loop on its own, starting with t = 0, the predictor stepped on `blank` from a zero state,
+ * no label since the last frame advance (nb = 0):
+ *   while t < T_n:
+ *     k = argmax of the token part, j = argmax of the duration part of the joiner's row for (frame t, predictor state);
+ *     d = durations[j]
+ *     k == blank:  t += max(d, 1);  nb = 0                                    (the predictor does not step)
+ *     otherwise:   k is emitted, at frame t;  the predictor steps on k;  nb = d > 0 ? 0 : nb + 1;  t += d;
+ *                  if nb >= n_steps:  t += 1, nb = 0                          (at most n_steps labels without an advance)
+ * Ties: both argmaxes are taken on the raw fp32 logits (a log-softmax is monotone within a part) and an exact tie goes to
+ * the lowest index, as numpy / torch argmax.  Overshoot: a jump may carry t past T_n; that ends the stream, it is not an
+ * error, and a label decided at frame t < T_n is emitted whatever its jump.
+ *
+ * Out: hyps [N, max_hyp] / hyp_lens [N] as wr_greedy_search (tokens beyond max_hyp are counted in hyp_lens but not
+ * stored); hyp_frames [N, max_hyp] or NULL: the frame t at which each stored token was emitted (non-decreasing, < T_n).
+ *
+ * wr_decoder_set_graph and wr_decoder_set_lookahead apply: with `frames` look-ahead the joiner rows of frames t .. t +
+ * frames - 1 are evaluated against one predictor state and walked in frame order by the rule above -- a blank with d = 2
+ * consults the row of t + 2 next and never that of t + 1, a blank with d >= frames ends the walk, a label ends it -- so
+ * the tokens and frames do not depend on the setting.  frames = 0 means 1 here: the adaptive rule of wr_greedy_search was
+ * measured no faster than 1 at 64 streams and slower at one (consecutive frames waste the rows a jump skips).  The durations travel in the state block every call uploads, never
+ * in a captured graph: calls with different durations, and wr_greedy_search, may alternate on one handle.
+ *
+ * Refused before any launch, in this order: D outside [1, 9], a null durations array, a duration outside [0, 8] or not
+ * strictly increasing, all durations 0, n_steps < 1, a null enc_out / enc_lens / hyps / hyp_lens, a null handle; then N
+ * or T beyond the handle's capacities, V = vocab_size - D < 2, blank outside [0, V), an embedding table (embed_rows) with
+ * fewer than V rows (all WR_EINVAL). */
+int wr_greedy_search_tdt(wr_decoder *h, const float *enc_out_d, const int32_t *enc_lens_d, int N, int T,
+                         int n_steps, int blank, const int32_t *durations /* [D], host */, int D,
+                         int32_t *hyps_d, int32_t *hyp_lens_d, int32_t *hyp_frames_d /* [N, max_hyp] or NULL */,
+                         void *stream);
+
 /* CTC forced alignment: Viterbi over the T x (2S+1) lattice, replacing
  * forced_align, wenet/utils/ctc_util.py:27-83 (CLI wenet/bin/alignment.py:215).  logits [B, Tmax, V]: pre-softmax
  * ctc_lo output, or log-posteriors if normalized != 0 (the reference is handed ctc.log_softmax(...)).

@@ -916,9 +916,144 @@ def bench_tdt(args):
     print(json.dumps(rec), flush=True)
 
 
+def tdt_decision_traces(model, enc, lens, n_steps):
+    """Every stream's decisions [(frame, token, duration)] by a lock-step torch loop over the HIP step kernels (all streams
+    step together; a stream that has not emitted repeats its predictor step, which gives the same output)."""
+    N, dev = enc.size(0), enc.device
+    V, durs = model.vocab_size, model.tdt_durations
+    pad = torch.zeros(N, 1, device=dev)
+    tok = torch.full((N, 1), model.blank, device=dev)
+    cache = model.predictor.init_state(N, method="zero", device=dev)
+    t, nb, traces = [0] * N, [0] * N, [[] for _ in range(N)]
+    T = [int(x) for x in lens]
+    rows_of = torch.arange(N, device=dev)
+    with torch.no_grad():
+        while any(t[n] < T[n] for n in range(N)):
+            out, new_cache = model.predictor.forward_step(tok, pad, cache)
+            at = torch.tensor([min(t[n], T[n] - 1) for n in range(N)], device=dev)
+            rows = model.joint(enc[rows_of, at][:, None, :].contiguous(), out.contiguous()).reshape(N, -1).float()
+            ks, js = rows[:, :V].argmax(1).tolist(), rows[:, V:].argmax(1).tolist()
+            emitted = []
+            for n in range(N):
+                if t[n] >= T[n]:
+                    continue
+                k, d = ks[n], durs[js[n]]
+                traces[n].append((t[n], k, d))
+                if k == model.blank:
+                    t[n] += max(d, 1)
+                    nb[n] = 0
+                    continue
+                emitted.append(n)
+                nb[n] = 0 if d > 0 else nb[n] + 1
+                t[n] += d
+                if nb[n] >= n_steps:
+                    t[n] += 1
+                    nb[n] = 0
+            if emitted:                                             # commit the stepped state and feed the new token
+                tok[emitted, 0] = torch.tensor([ks[n] for n in emitted], device=dev)
+                for c, nc in zip(cache, new_cache):
+                    c[:, emitted] = nc[:, emitted]
+    return traces
+
+
+def tdt_row_counts(traces, look, blank=0):
+    """Replay of the look-ahead walk over recorded decisions -> (micro-steps, joiner rows evaluated for active streams,
+    rows consulted)."""
+    N = len(traces)
+    pos = [0] * N
+    micro = evaluated = consulted = 0
+    while any(pos[n] < len(traces[n]) for n in range(N)):
+        micro += 1
+        for n in range(N):
+            if pos[n] >= len(traces[n]):
+                continue
+            t0 = traces[n][pos[n]][0]
+            evaluated += look
+            while pos[n] < len(traces[n]) and traces[n][pos[n]][0] - t0 < look:
+                k = traces[n][pos[n]][1]
+                pos[n] += 1
+                consulted += 1
+                if k != blank:
+                    break
+    return micro, evaluated, consulted
+
+
+def bench_tdtdec(args):
+    """TDT greedy search on the device at the shape of the `greedy` sweep: 64 streams, V = 5000 tokens + D durations
+    0 .. D-1, LSTM 2x256, J = 512; look-ahead 1 / 2 / 4 / 0, plain greedy on the same handle, the host-driven loop for one
+    stream.  Per line: ms per call, us per decision, the share of joiner rows evaluated but never consulted."""
+    import time
+    import types
+    import wenet_celoss_amd as w
+    dev = torch.device("cuda:0")
+    torch.manual_seed(5)
+    D = args.durations
+    V, E, P, J, H, L, N = 5000, 256, 256, 512, 256, 2, args.streams
+    T = 16 * args.chunks
+    durations = tuple(range(D))
+    # the embedding table has a row for every joiner column, so that the plain search may run on the same handle
+    pred = w.RNNPredictor(V + D, P, P, 0.1, H, L).to(dev).eval()
+    joint = w.TransducerJoint(V + D, E, P, J).to(dev).eval()
+    with torch.no_grad():
+        joint.ffn_out.weight *= 10
+        joint.ffn_out.bias[0] += 17.0
+    gq = torch.Generator(device=dev).manual_seed(11)                # the speech-like input of the `greedy` sweep
+    quiet = torch.randn(N, T, E, device=dev, generator=gq) * 0.1
+    loud = torch.randn(N, T, E, device=dev, generator=gq) * 2.5
+    spikes = torch.rand(N, T, device=dev, generator=gq) < 0.25
+    enc = torch.where(spikes[..., None], loud, quiet)
+    lens = torch.full((N,), T)
+    n_steps = 2
+
+    def timed(fn):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.steps, out
+
+    for n_str in (N, 1):
+        model = types.SimpleNamespace(blank=0, predictor=pred, joint=joint, vocab_size=V, tdt_durations=durations)
+        e_s, l_s = enc[:n_str].contiguous(), lens[:n_str]
+        traces = tdt_decision_traces(model, e_s, l_s, n_steps)
+        decisions = sum(len(tr) for tr in traces)
+        want = [[k for _, k, _ in tr if k != 0] for tr in traces]
+        taken = sorted({d for tr in traces for _, _, d in tr})
+        w.tdt_greedy_search(model, e_s, l_s, n_steps=n_steps)      # builds the handle
+        dec = model._decoder_cache._dec
+        for look in (1, 2, 4, 0):
+            dec.set_lookahead(look)
+            dt, got = timed(lambda: w.tdt_greedy_search(model, e_s, l_s, n_steps=n_steps))
+            micro, evaluated, consulted = tdt_row_counts(traces, look or 1)      # 0 means 1 for TDT
+            print(json.dumps({"what": "tdt_greedy_search device", "streams": n_str, "frames": T, "durations": durations,
+                              "frames_per_micro_step": look, "tokens": sum(len(h) for h in got), "decisions": decisions,
+                              "durations_taken": taken, "micro_steps": micro, "ms_per_call": round(dt * 1e3, 3),
+                              "us_per_decision": round(dt * 1e6 / max(decisions, 1), 2),
+                              "rows_never_consulted": round(1.0 - consulted / max(evaluated, 1), 3),
+                              "tokens_identical": got == want}), flush=True)
+        dec.set_lookahead(0)
+        if n_str == N:
+            dt, got = timed(lambda: dec.greedy(e_s, l_s, n_steps=n_steps, blank=0))
+            plain_decisions = sum(len(h) for h in got) + n_str * T          # one per token, one blank per frame (an upper bound)
+            print(json.dumps({"what": "greedy_search (plain, same handle, every column a token)", "streams": n_str, "frames": T,
+                              "tokens": sum(len(h) for h in got), "ms_per_call": round(dt * 1e3, 3),
+                              "us_per_decision": round(dt * 1e6 / plain_decisions, 2)}), flush=True)
+    os.environ["WR_TDT_HOST"] = "1"
+    try:
+        dt, got = timed(lambda: w.tdt_greedy_search(model, e_s, l_s, n_steps=n_steps))
+    finally:
+        del os.environ["WR_TDT_HOST"]
+    print(json.dumps({"what": "tdt_greedy_search host-driven loop", "streams": 1, "frames": T, "decisions": decisions,
+                      "ms_per_call": round(dt * 1e3, 2), "us_per_decision": round(dt * 1e6 / max(decisions, 1), 1),
+                      "tokens_identical": got == want}), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align", "simple", "smoothed", "pruned", "tdt"])
+    ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align", "simple", "smoothed", "pruned", "tdt",
+                                     "tdtdec"])
     ap.add_argument("--durations", type=int, default=5, help="tdt: number of durations D (the set is 0 .. D-1)")
     ap.add_argument("--n-steps", type=int, default=64)
     ap.add_argument("--chunks", type=int, default=4)
@@ -955,4 +1090,4 @@ if __name__ == "__main__":
         _lib.load().wr_tune_set(6, a.tile)
     {"joint": bench_joint, "ctc": bench_ctc, "greedy": bench_greedy, "beam": bench_beam, "step": bench_step, "ctcdec": bench_ctcdec, "hotword": bench_hotword,
      "align": bench_align, "simple": bench_simple, "smoothed": bench_smoothed, "pruned": bench_pruned,
-     "tdt": bench_tdt}[a.what](a)
+     "tdt": bench_tdt, "tdtdec": bench_tdtdec}[a.what](a)

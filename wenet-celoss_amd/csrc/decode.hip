@@ -37,6 +37,7 @@
 //
 // Micro-steps are replayed from a hipGraph (captured once per decoder handle) so
 // the host only checks a "lanes still active" word every 16 steps.
+#include "decode_tdt.hpp"
 #include "wr_common.hpp"
 #include "wr_launch.hpp"
 
@@ -165,6 +166,11 @@ struct DevState {
     int32_t *trace, *trace_len;   // [NL, trace_cap] / [NL]: `result`, the gate trace
     int trace_cap;
     float *biasT;                 // [Pp][NLp] biased predictor output (input of pred_ffn in hot-word mode)
+    // token-and-duration greedy (wr_greedy_search_tdt).  The durations travel here, in the state block every call uploads,
+    // and never as a kernel argument: those are baked into the captured graphs
+    unsigned long long tdt_durs;  // durations[j] in bits [4j, 4j + 4)
+    int tdt_D;                    // the logits row is V - tdt_D token columns followed by tdt_D duration columns
+    int32_t *hyp_frames;          // [NL, max_hyp] frame of each emission, or null
 };
 
 struct GemmArgs {
@@ -1215,6 +1221,121 @@ __global__ __launch_bounds__(256) void greedy_resolve_kernel(DevState *sp, int l
     commit_and_feed(S, n, emitted >= 0, commit, emitted, sc, sn);
 }
 
+// ---- token-and-duration (TDT) greedy: the two look-ahead kernels with the TDT decision rule ------------------
+// The logits row is Vt = V - tdt_D token columns followed by tdt_D duration columns.  tdt_rows_kernel takes the argmax
+// of each part of every (frame, lane) row on the raw fp32 logits (a log-softmax is monotone within a part), lowest
+// index on exact ties, and packs them as k | j << 16 into row_tok (V <= 16384).  A part without a finite maximum (NaN
+// logits) decides blank / duration 0 rather than an index outside the tables.
+template <int NV>
+__global__ __launch_bounds__(256) void tdt_rows_kernel(DevState *sp)
+{
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    const DevState S = *sp;
+    const Dims &d = S.d;
+    const int n = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
+    const int act = S.lane_active[n];
+    const int t = S.lane_t[n];
+    const int enc_len = S.enc_lens[n];
+    const int Vt = d.V - S.tdt_D;
+    const float *__restrict__ x = S.logits + ((size_t)f * d.NLp + n) * d.V;
+    float xv[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int v = tid + i * 256;
+        xv[i] = x[v < Vt ? v : Vt - 1];
+    }
+    const float xd = x[Vt + (tid < S.tdt_D ? tid : 0)];       // the duration columns: at most 9, one per lane of a wave
+    const int T = enc_len < S.T ? enc_len : S.T;
+    if (!act || t + f >= T) return;                // frames past the end are never consulted
+    float best = -3.0e38f;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int v = tid + i * 256;
+        if (v < Vt && xv[i] > best) { best = xv[i]; bi = v; }   // strided ascending scan keeps the lowest index per thread
+    }
+    block_argmax(best, bi, sv, si);
+    float dbest = tid < S.tdt_D ? xd : -3.0e38f;
+    int dj = tid < S.tdt_D && xd > -3.0e38f ? tid : 0x7fffffff;
+    wave_argmax_dpp(dbest, dj);                    // every wave holds lanes 0 .. 63 of its own threads: wave 0 has the columns
+    if (tid == 0) {
+        const int k = bi < Vt ? bi : S.blank, j = dj < S.tdt_D ? dj : 0;
+        S.row_tok[(size_t)f * d.NLp + n] = k | (j << 16);
+    }
+}
+
+// One workgroup per lane walks the lane's rows against the one predictor state of this micro-step (t0: the lane's frame
+// at entry; row f belongs to frame t0 + f):
+//   blank:  t += max(d, 1), the emission counter restarts, the walk goes on at row t - t0 (a jump skips rows)
+//   label:  emitted at frame t; the counter restarts if d > 0, else counts; t += d; after n_steps labels without a frame
+//           advance t += 1; the walk stops (the remaining rows belong to a stale predictor state)
+// A lane is done when t >= T_n; a jump may overshoot T_n.  Every micro-step consults row 0, which emits or advances.
+__global__ __launch_bounds__(256) void tdt_resolve_kernel(DevState *sp, int look)
+{
+    const DevState S = *sp;
+    const Dims &d = S.d;
+    const int n = blockIdx.x, tid = threadIdx.x;
+    const int act = S.lane_active[n];
+    int t = S.lane_t[n], nb = S.noblk[n];
+    const int need0 = S.need_pred[n];
+    int nic = S.new_is_cache[n];
+    int len = S.hyp_lens[n];
+    const int enc_len = S.enc_lens[n];
+    const int sc = S.comm_slot[n], sn = S.new_slot[n];
+    int rows[kMaxLook];
+#pragma unroll
+    for (int f = 0; f < kMaxLook; ++f) rows[f] = S.row_tok[(size_t)(f < look ? f : 0) * d.NLp + n];
+    if (!act) return;
+    const int T = enc_len < S.T ? enc_len : S.T;
+    if (need0) nic = 0;                            // the predictor stepped in this micro-step
+    const int t0 = t;
+    int need = need0, emitted = -1, n_blank = 0;
+    bool commit = false;
+#pragma unroll
+    for (int f = 0; f < kMaxLook; ++f) {
+        if (f >= look || emitted >= 0 || t >= T || t - t0 != f) continue;   // consulted: the row of the lane's current frame
+        const int k = rows[f] & 0xffff;
+        const int dur = (int)((S.tdt_durs >> (4 * (rows[f] >> 16))) & 15);
+        if (k == S.blank) {
+            n_blank += 1;
+            t += dur > 1 ? dur : 1;
+            nb = 0;
+            need = 0;
+            continue;
+        }
+        if (tid == 0 && len < S.max_hyp) {
+            S.hyps[(size_t)n * S.max_hyp + len] = k;
+            if (S.hyp_frames) S.hyp_frames[(size_t)n * S.max_hyp + len] = t;
+        }
+        len += 1;
+        need = 1;
+        commit = !nic;
+        emitted = k;
+        nb = dur > 0 ? 0 : nb + 1;
+        t += dur;
+        if (nb >= S.n_steps) {
+            t += 1;
+            nb = 0;
+        }
+    }
+    if (tid == 0) {
+        if (n_blank) atomicAdd(S.active_count + 1, n_blank);         // decision statistics: consulted rows only
+        if (emitted >= 0) atomicAdd(S.active_count + 2, 1);
+        if (need0) S.new_is_cache[n] = 0;
+        S.hyp_lens[n] = len;
+        if (emitted >= 0) S.token[n] = emitted;
+        S.need_pred[n] = need;
+        S.lane_t[n] = t;
+        S.noblk[n] = nb;
+        if (t >= T) {
+            S.lane_active[n] = 0;
+            atomicSub(S.active_count, 1);
+        }
+    }
+    commit_and_feed(S, n, emitted >= 0, commit, emitted, sc, sn);
+}
+
 // ------------------------------------------------------- hot-word greedy --
 // Device copy of the ContextBias weights the greedy loop uses (wenet/transformer/context_bias.py:375-394), re-laid
 // k-major where a thread block streams them (see wr_decoder_attach_hotword).
@@ -2118,6 +2239,7 @@ struct wr_decoder {
     hipStream_t work = nullptr;   // decode work runs here (graph capture is illegal on the legacy default stream)
     hipEvent_t ev_in = nullptr, ev_out = nullptr;   // ordering against the caller's stream, no device-wide sync
     GraphSlot greedy[kMaxLook + 1];   // one per look-ahead setting, keyed by the lanes
+    GraphSlot greedy_tdt[kMaxLook + 1];   // the same for the token-and-duration micro-step
     GraphSlot beam;               // keyed by lanes and beam
     GraphSlot hotword;            // keyed by the lanes
     int stream_lanes = -1;        // lanes whose streaming state (cache, token, flags) is live; -1: none
@@ -2138,6 +2260,7 @@ template <typename F>
 void for_each_graph(wr_decoder *h, F f)
 {
     for (GraphSlot &g : h->greedy) f(g);
+    for (GraphSlot &g : h->greedy_tdt) f(g);
     f(h->beam);
     f(h->hotword);
 }
@@ -2610,6 +2733,18 @@ int greedy_micro_step(wr_decoder *h, int n_lanes, hipStream_t st, int look)
     return launch("greedy_resolve_kernel", greedy_resolve_kernel, dim3(n_lanes), dim3(256), 0, st, h->dev, look);
 }
 
+// token-and-duration model: the two TDT kernels over row-major logits, for every `look` (1 included)
+int tdt_micro_step(wr_decoder *h, int n_lanes, hipStream_t st, int look)
+{
+    WR_TRY(launch_predictor_and_joint(h, n_lanes, st, look, /*row_stats=*/false));
+    const int V = h->d.V;                           // <= 16384 (check_weights)
+    const int per_thread = V <= 256 * 8 ? 8 : V <= 256 * 24 ? 24 : 64;
+    WR_TRY(with_int<8, 24, 64>(per_thread, [&](auto n) {
+        return launch("tdt_rows_kernel", tdt_rows_kernel<decltype(n)::value>, dim3(n_lanes, look), dim3(256), 0, st, h->dev);
+    }));
+    return launch("tdt_resolve_kernel", tdt_resolve_kernel, dim3(n_lanes), dim3(256), 0, st, h->dev, look);
+}
+
 int beam_frame(wr_decoder *h, int n_lanes, int n_utt, hipStream_t st)
 {
     WR_TRY(launch_predictor_and_joint(h, n_lanes, st));
@@ -2716,13 +2851,29 @@ int run_until_idle(wr_decoder *h, hipStream_t st, const char *what, int key, lon
     return WR_OK;
 }
 
-// mode 0: fresh utterances; 1: next chunk, keep the pending predictor state; 2: next chunk, reference quirk
+// what a token-and-duration search adds to a greedy run
+struct TdtRun {
+    unsigned long long durs;      // DevState::tdt_durs
+    int D;
+    int32_t *hyp_frames;          // [N, max_hyp] or null
+};
+
+// mode 0: fresh utterances; 1: next chunk, keep the pending predictor state; 2: next chunk, reference quirk.
+// `tdt` (mode 0 only): the token-and-duration search -- its own micro-step and graph slots, the rest is shared.
 int greedy_run(wr_decoder *h, const float *enc_out_d, const int32_t *enc_lens_d, int N, int T, int n_steps, int blank,
-               int32_t *hyps_d, int32_t *hyp_lens_d, void *stream, int mode)
+               int32_t *hyps_d, int32_t *hyp_lens_d, void *stream, int mode, const TdtRun *tdt = nullptr)
 {
-    WR_REQUIRE(h && enc_out_d && enc_lens_d && hyps_d && hyp_lens_d, WR_EINVAL, "greedy_search: null pointer argument");
-    WR_REQUIRE(N > 0 && N <= h->d.NL && N <= h->max_utt, WR_EINVAL, "greedy_search: N=%d exceeds the decoder's capacity", N);
-    WR_REQUIRE(T > 0 && T <= h->Tmax, WR_EINVAL, "greedy_search: T=%d exceeds the decoder's Tmax=%d", T, h->Tmax);
+    const char *what = tdt ? "greedy_search_tdt" : "greedy_search";
+    WR_REQUIRE(h && enc_out_d && enc_lens_d && hyps_d && hyp_lens_d, WR_EINVAL, "%s: null pointer argument", what);
+    WR_REQUIRE(N > 0 && N <= h->d.NL && N <= h->max_utt, WR_EINVAL, "%s: N=%d exceeds the decoder's capacity", what, N);
+    WR_REQUIRE(T > 0 && T <= h->Tmax, WR_EINVAL, "%s: T=%d exceeds the decoder's Tmax=%d", what, T, h->Tmax);
+    if (tdt) {
+        const int V = h->d.V - tdt->D;             // token columns of the joiner's row
+        WR_REQUIRE(V >= 2, WR_EINVAL, "%s: the joiner has %d outputs, D=%d durations leave %d token columns (2 or more are needed)",
+                   what, h->d.V, tdt->D, V);
+        WR_REQUIRE(blank >= 0 && blank < V, WR_EINVAL, "%s: blank %d out of range [0,%d)", what, blank, V);
+        WR_REQUIRE(h->d.Ve >= V, WR_EINVAL, "%s: the embedding table has %d rows, the token vocabulary %d", what, h->d.Ve, V);
+    }
     WR_REQUIRE(n_steps >= 1 && blank >= 0 && blank < h->d.V, WR_EINVAL, "greedy_search: bad n_steps/blank");
     WR_REQUIRE(mode == 0 || h->stream_lanes == N, WR_EINVAL,
                "greedy_search_chunk: no stream state for %d lanes (call with reset first)", N);
@@ -2732,24 +2883,28 @@ int greedy_run(wr_decoder *h, const float *enc_out_d, const int32_t *enc_lens_d,
     s.enc = enc_out_d; s.enc_lens = enc_lens_d; s.ctc_logp = nullptr;
     s.n_utt = N; s.T = T; s.lanes_per_utt = 1; s.n_lanes = N;
     s.hyps = hyps_d; s.hyp_lens = hyp_lens_d; s.max_hyp = h->max_hyp; s.n_steps = n_steps; s.blank = blank; s.beam = 1;
+    s.tdt_durs = tdt ? tdt->durs : 0; s.tdt_D = tdt ? tdt->D : 0; s.hyp_frames = tdt ? tdt->hyp_frames : nullptr;
     if (int rc = upload_state(h, st)) return rc;
     (void)hipMemsetAsync(s.active_count, 0, 3 * sizeof(int32_t), st);    // lanes active, blank decisions, emissions
     (void)hipMemsetAsync(s.lane_active, 0, sizeof(int32_t) * h->d.NLp, st);
     WR_TRY(launch_ep_all(h, st, (long)N * T, enc_out_d, s.ep_all));
     if (mode == 0) WR_TRY(launch("greedy_init_kernel", greedy_init_kernel, dim3(N), dim3(128), 0, st, h->dev));
     else WR_TRY(launch("greedy_chunk_init_kernel", greedy_chunk_init_kernel, dim3(N), dim3(128), 0, st, h->dev, mode == 2 ? 1 : 0));
-    h->stream_lanes = N;
+    h->stream_lanes = tdt ? -1 : N;               // a TDT run leaves no state a chunk could continue from
     // look-ahead per replay: fixed, or (h->look == 0) chosen from the share of blank decisions in the previous
-    // replay -- any value gives the same tokens, so switching between replays is safe
+    // replay -- any value gives the same tokens, so switching between replays is safe.  TDT: 0 means 1 -- consecutive
+    // frames waste the rows a duration jump skips, and the rule measured no faster than 1 at 64 streams and 18 % slower
+    // at one (profiles/tdt_greedy_search.md)
     int look = h->look > 0 ? h->look : 1;
     int prev_blank = 0, prev_emit = 0;
     // every micro-step emits (at most n_steps per frame) or advances the frame, so the budget cannot run out
     const long max_micro = (long)T * ((long)n_steps + 1) + 1;
     WR_TRY(run_until_idle(
-        h, st, "greedy_search", N, max_micro, "", [&]() -> GraphSlot & { return h->greedy[look]; },
-        [&] { return greedy_micro_step(h, N, st, look); },
+        h, st, tdt ? "greedy_search_tdt" : "greedy_search", N, max_micro, "",
+        [&]() -> GraphSlot & { return tdt ? h->greedy_tdt[look] : h->greedy[look]; },
+        [&] { return tdt ? tdt_micro_step(h, N, st, look) : greedy_micro_step(h, N, st, look); },
         [&] {
-            if (h->look != 0) return;
+            if (h->look != 0 || tdt) return;
             const int nb = h->h_active[1] - prev_blank, ne = h->h_active[2] - prev_emit;
             prev_blank = h->h_active[1]; prev_emit = h->h_active[2];
             const float share = (nb + ne) > 0 ? (float)nb / (float)(nb + ne) : 0.f;
@@ -2761,6 +2916,16 @@ int greedy_run(wr_decoder *h, const float *enc_out_d, const int32_t *enc_lens_d,
     return WR_OK;
 }
 }  // namespace
+
+// decode_tdt.hpp: the search behind wr_greedy_search_tdt (decode_tdt.cpp has checked durations, n_steps, pointers)
+int wr::greedy_tdt_body(wr_decoder *h, const float *enc_out_d, const int32_t *enc_lens_d, int N, int T, int n_steps, int blank,
+                        const TdtDur &dur, int32_t *hyps_d, int32_t *hyp_lens_d, int32_t *hyp_frames_d, void *stream)
+{
+    TdtRun run{0, dur.D, hyp_frames_d};
+    for (int d = 0; d < kTdtMaxD; ++d)
+        if (dur.slot[d] >= 0) run.durs |= (unsigned long long)d << (4 * dur.slot[d]);
+    return greedy_run(h, enc_out_d, enc_lens_d, N, T, n_steps, blank, hyps_d, hyp_lens_d, stream, 0, &run);
+}
 
 extern "C" int wr_greedy_search(wr_decoder *h, const float *enc_out_d, const int32_t *enc_lens_d, int N, int T, int n_steps,
                                 int blank, int32_t *hyps_d, int32_t *hyp_lens_d, void *stream)

@@ -27,6 +27,27 @@ struct TdtDur {
     int D;
 };
 
+// The durations contract of every TDT entry point (the loss here, wr_greedy_search_tdt in decode_tdt.cpp): WR_OK and the
+// table of jumps, or the error of a duration set the lattice does not have.  Host code, no HIP call.
+inline int tdt_durations(const char *what, const int32_t *durations, int D, TdtDur *out)
+{
+    WR_REQUIRE(D >= 1 && D <= kTdtMaxD, WR_EINVAL, "%s: D=%d durations (1 to %d are supported)", what, D, kTdtMaxD);
+    WR_REQUIRE(durations != nullptr, WR_EINVAL, "%s: durations is null", what);
+    for (int d = 0; d < kTdtMaxD; ++d) out->slot[d] = -1;
+    out->D = D;
+    for (int n = 0; n < D; ++n) {
+        WR_REQUIRE(durations[n] >= 0 && durations[n] <= kTdtMaxDur, WR_EINVAL,
+                   "%s: durations[%d]=%d lies outside [0, %d]", what, n, durations[n], kTdtMaxDur);
+        WR_REQUIRE(n == 0 || durations[n] > durations[n - 1], WR_EINVAL,
+                   "%s: durations must be strictly increasing (durations[%d]=%d after %d)", what, n, durations[n],
+                   durations[n - 1]);
+        out->slot[durations[n]] = n;
+    }
+    WR_REQUIRE(durations[D - 1] >= 1, WR_EINVAL, "%s: at least one duration must be 1 or more (no arc would consume a frame)",
+               what);
+    return WR_OK;
+}
+
 struct TdtWs {
     int K;            // waves of a sweep workgroup
     int S;            // anti-diagonals per utterance

@@ -186,6 +186,29 @@ class DeviceDecoder:
             raise RuntimeError(f"greedy search produced {max(hl_c)} tokens but the decoder was sized for {self.max_hyp}")
         return [hy_c[i, :hl_c[i]].tolist() for i in range(N)]
 
+    def greedy_tdt(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, durations, n_steps: int = 64,
+                   blank: int = 0, return_frames: bool = False):
+        """Greedy search of a token-and-duration model (`wr_greedy_search_tdt`): the joiner's row is its width minus
+        len(durations) token logits followed by one logit per duration.  encoder_out (N, T, E) -> one token list per
+        stream; with `return_frames` also the frame at which each token was emitted.  `set_graph` and `set_lookahead`
+        apply; tokens and frames do not depend on them."""
+        enc = _f32(encoder_out)
+        N, T, _ = enc.shape
+        lens = encoder_out_lens.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+        durs = (ctypes.c_int32 * max(len(durations), 1))(*[int(d) for d in durations])
+        hyps = torch.empty(N, max(self.max_hyp, 1), dtype=torch.int32, device=self.device)
+        frames = torch.empty_like(hyps) if return_frames else None
+        hl = torch.empty(N, dtype=torch.int32, device=self.device)
+        self._call("wr_greedy_search_tdt", enc, lens, N, T, int(n_steps), int(blank), durs, len(durations), hyps, hl, frames)
+        hl_c, hy_c = hl.cpu().tolist(), hyps.cpu()
+        if max(hl_c, default=0) > self.max_hyp:
+            raise RuntimeError(f"greedy search produced {max(hl_c)} tokens but the decoder was sized for {self.max_hyp}")
+        toks = [hy_c[i, :hl_c[i]].tolist() for i in range(N)]
+        if not return_frames:
+            return toks
+        fr_c = frames.cpu()
+        return toks, [fr_c[i, :hl_c[i]].tolist() for i in range(N)]
+
     def greedy_chunk(self, encoder_chunk: torch.Tensor, chunk_lens: torch.Tensor, n_steps: int = 64, blank: int = 0,
                      reset: bool = False, reference_new_cache: bool = True) -> List[List[int]]:
         """Streaming greedy search: tokens emitted in this chunk for each stream (state carries over)."""

@@ -1,7 +1,8 @@
 """Transducer greedy search with the upstream core loop's semantics
 (wenet/transducer/search/greedy_search copy.py:6-63),
 for any number of independent streams at once, with the whole loop on the
-device (`wr_greedy_search`).
+device (`wr_greedy_search`); the token-and-duration (TDT) rule likewise
+(`wr_greedy_search_tdt`).
 
 The fork's hot-word variants (greedy_search.py:34-430: context gating and "go-back"
 re-decoding around ContextBias) follow below: the default one (`basic_greedy_search_both`,
@@ -28,6 +29,11 @@ def basic_greedy_search(model: torch.nn.Module, encoder_out: torch.Tensor, encod
     lens = torch.as_tensor(encoder_out_lens).reshape(-1)
     if lens.numel() == 1 and N > 1:
         lens = lens.expand(N)
+    dec = _decoder_cache(model).get(model.predictor, model.joint, lanes=N, utts=N, tmax=T, max_hyp=T * n_steps, beam=1)
+    return dec.greedy(encoder_out, lens, n_steps=n_steps, blank=model.blank)
+
+
+def _decoder_cache(model):
     cache = getattr(model, "_decoder_cache", None)
     if cache is None:
         from ..decoder import DecoderCache
@@ -36,17 +42,36 @@ def basic_greedy_search(model: torch.nn.Module, encoder_out: torch.Tensor, encod
             model._decoder_cache = cache
         except Exception:
             pass
-    dec = cache.get(model.predictor, model.joint, lanes=N, utts=N, tmax=T, max_hyp=T * n_steps, beam=1)
-    return dec.greedy(encoder_out, lens, n_steps=n_steps, blank=model.blank)
+    return cache
 
 
 def tdt_greedy_search(model: torch.nn.Module, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor,
-                      n_steps: int = 64) -> List[List[int]]:
+                      n_steps: int = 64, return_frames: bool = False):
     """Greedy search of a token-and-duration model (`model.tdt_durations`; the joiner's row is `vocab_size` token logits
-    followed by one logit per duration): one utterance, host-driven over the HIP step kernels (predictor.forward_step,
-    the joiner).  At frame t: k = argmax of the token part, d = durations[argmax of the duration part]; a blank moves
-    max(d, 1) frames on; a label is emitted, steps the predictor and moves d frames on; after `n_steps` labels without a
-    frame advance the search moves one frame on."""
+    followed by one logit per duration) for any number of streams at once, with the whole loop on the device
+    (`wr_greedy_search_tdt`).  At frame t: k = argmax of the token part, d = durations[argmax of the duration part]; a
+    blank moves max(d, 1) frames on; a label is emitted, steps the predictor and moves d frames on; after `n_steps` labels
+    without a frame advance the search moves one frame on.
+
+    encoder_out (N, T, E), encoder_out_lens scalar or (N,) -> one token list per stream; with `return_frames` also the
+    frame at which each token was emitted.  Sized like `basic_greedy_search` (max_hyp = T * n_steps).
+    WR_TDT_HOST=1 forces the host-driven loop over the HIP step kernels (one stream)."""
+    import os
+    if os.environ.get("WR_TDT_HOST", "0") == "1":
+        hyps, frames = _tdt_greedy_host(model, encoder_out, encoder_out_lens, n_steps)
+        return ([hyps], [frames]) if return_frames else [hyps]
+    N, T, _ = encoder_out.shape
+    lens = torch.as_tensor(encoder_out_lens).reshape(-1)
+    if lens.numel() == 1 and N > 1:
+        lens = lens.expand(N)
+    dec = _decoder_cache(model).get(model.predictor, model.joint, lanes=N, utts=N, tmax=T, max_hyp=T * n_steps, beam=1)
+    return dec.greedy_tdt(encoder_out, lens, model.tdt_durations, n_steps=n_steps, blank=model.blank,
+                          return_frames=return_frames)
+
+
+def _tdt_greedy_host(model, encoder_out, encoder_out_lens, n_steps):
+    """The rule of `tdt_greedy_search` host-driven, one utterance: one predictor.forward_step, one joiner call and one
+    host synchronisation per decision -> (tokens, frames)."""
     assert encoder_out.size(0) == 1
     durations = model.tdt_durations
     V = model.vocab_size
@@ -58,6 +83,7 @@ def tdt_greedy_search(model: torch.nn.Module, encoder_out: torch.Tensor, encoder
     T = int(encoder_out_lens)
     t, emitted_in_frame, step = 0, 0, True
     hyps: List[int] = []
+    frames: List[int] = []
     pred_out = None
     with torch.no_grad():
         while t < T:
@@ -72,6 +98,7 @@ def tdt_greedy_search(model: torch.nn.Module, encoder_out: torch.Tensor, encoder
                 emitted_in_frame = 0
                 continue
             hyps.append(k)
+            frames.append(t)
             tok = torch.tensor([[k]], device=dev)
             cache = new_cache
             step = True
@@ -80,7 +107,7 @@ def tdt_greedy_search(model: torch.nn.Module, encoder_out: torch.Tensor, encoder
             if emitted_in_frame >= n_steps:
                 t += 1
                 emitted_in_frame = 0
-    return [hyps]
+    return hyps, frames
 
 
 # ------------------------------------------------------------------------------------------------

@@ -305,7 +305,8 @@ class Transducer(nn.Module):
     def _refuse_tdt(self, what: str) -> None:
         if self._is_tdt():
             raise NotImplementedError(f"Transducer.{what}: a TDT model (tdt_durations={self.tdt_durations}) decodes with "
-                                      "greedy_search only; the device-resident decoders read vocab_size columns")
+                                      "greedy_search and tdt_greedy_search_batch; this method reads every joiner column as "
+                                      "a token")
 
     def _can_fuse_loss(self) -> bool:
         if self._is_tdt():
@@ -706,7 +707,7 @@ class Transducer(nn.Module):
         _ = simulate_streaming
         encoder_out, encoder_mask = self.encoder(speech, speech_lengths, decoding_chunk_size, num_decoding_left_chunks)
         encoder_out_lens = encoder_mask.squeeze(1).sum()
-        if self._is_tdt():                                  # token-and-duration model: host-driven loop, batch 1
+        if self._is_tdt():                                  # token-and-duration model: its own device search
             return tdt_greedy_search(self, encoder_out, encoder_out_lens, n_steps=n_steps), 0
         if self.context_bias is None:                       # no hot-word module: the variants reduce to the core loop
             return basic_greedy_search(self, encoder_out, encoder_out_lens, n_steps=n_steps), 0
@@ -727,6 +728,16 @@ class Transducer(nn.Module):
         self._refuse_tdt("greedy_search_batch")
         encoder_out, encoder_mask = self.encoder(speech, speech_lengths, decoding_chunk_size, num_decoding_left_chunks)
         return basic_greedy_search(self, encoder_out, encoder_mask.squeeze(1).sum(1), n_steps=n_steps)
+
+    def tdt_greedy_search_batch(self, speech: torch.Tensor, speech_lengths: torch.Tensor, decoding_chunk_size: int = -1,
+                                num_decoding_left_chunks: int = -1, n_steps: int = 64, return_frames: bool = False):
+        """Extension: N utterances of a token-and-duration model decoded together -> one token list per utterance; with
+        `return_frames` also the encoder frame at which each token was emitted."""
+        if not self._is_tdt():
+            raise ValueError("Transducer.tdt_greedy_search_batch: the model has no tdt_durations (use greedy_search_batch)")
+        encoder_out, encoder_mask = self.encoder(speech, speech_lengths, decoding_chunk_size, num_decoding_left_chunks)
+        return tdt_greedy_search(self, encoder_out, encoder_mask.squeeze(1).sum(1), n_steps=n_steps,
+                                 return_frames=return_frames)
 
     # ------------------------------------- streaming greedy ("transducer ref.py":541-606) --
     def reset_cache(self, n_streams: int = 1, chunk_frames: int = 64, n_steps: int = 64) -> None:
