@@ -939,6 +939,37 @@ int wr_rnnt_tdt_export_lattice(const void *workspace_d, size_t workspace_bytes, 
                                float *alpha_d /* [B,Tmax,U1max] out */, float *beta_d /* [B,Tmax,U1max] out */,
                                void *stream);
 
+/* TDT forced alignment: the single best path through the lattice above.  This text is the contract.  Inputs, arc weights
+ * tok_k and dur_n, sigma, the duration rules and the terminal are exactly those of "Token-and-duration transducer".
+ *
+ * With A(0,0) = 0, A(t,u) is the max over incoming arcs of (A(src) + tok) + dur: blank arcs from (t - d, u), d >= 1, and
+ * label arcs from (t - d, u - 1), d >= 0, the latter for t <= T_b - 1.  score_b is the max over the blank arcs from
+ * (T_b - d, U_b) into the terminal.  All sums are float64, over the float32 arc log-probabilities that the row-statistics
+ * pass stores.  score_b <= -cost_b of wr_rnnt_tdt_loss_fwd.
+ *
+ * Tie rule.  A larger candidate wins.  Between equal candidates a blank arc beats a label arc; within one kind the
+ * smaller d wins.  A NaN candidate never wins, and a cell with no winning candidate is unreachable (-inf).  The terminal
+ * follows the same rule.
+ *
+ * Outputs per utterance.  label_frames[b, u]: the frame t at which the arc that emits label u + 1 leaves;
+ * label_durations[b, u]: that arc's jump d (the value, not its index); both -1 for u >= U_b.  blank_jumps[b, t]
+ * (optional, may be NULL): the jump of the blank arc that leaves frame t on the best path -- a blank has d >= 1, so at
+ * most one does -- 0 if none and 0 for t >= T_b.  scores[b]: score_b.  The three arrays determine the whole path.
+ * No path (durations = {2}, T_b = 3, U_b = 0; or T_b = 0): scores[b] = -inf, labels -1, jumps 0, and the other
+ * utterances are unaffected.  A non-finite logit inside one utterance: the call returns and that utterance's outputs
+ * stay in range -- frames in [-1, T_b), durations in the set or -1, and either a structurally valid path or the no-path
+ * outputs; every other utterance's outputs are bit-identical to those of the same batch without it.
+ *
+ * The workspace is that of wr_rnnt_tdt_workspace_bytes: the decisions take one byte per cell of its beta region.
+ * Refusals, codes and texts are those of wr_rnnt_tdt_loss_fwd under this function's name; a null label_frames or
+ * label_durations (with U1max > 1) or a null scores is WR_EINVAL. */
+int wr_rnnt_tdt_align(const void *logits_d, int dtype, const int32_t *targets_d, const int32_t *logit_lengths_d,
+                      const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V, int blank,
+                      const int32_t *durations /* [D], host */, int D, double sigma,
+                      int32_t *label_frames_d /* [B, U1max-1] out */, int32_t *label_durations_d /* [B, U1max-1] out */,
+                      int32_t *blank_jumps_d /* [B, Tmax] out, or NULL */, double *scores_d /* [B] out */,
+                      void *workspace_d, size_t workspace_bytes, void *stream);
+
 /* TDT greedy search: the greedy decode of a token-and-duration model, batched, with every decision on the device.  This
  * text is the contract.
  *

@@ -916,6 +916,50 @@ def bench_tdt(args):
     print(json.dumps(rec), flush=True)
 
 
+def bench_tdtalign(args):
+    """TDT forced alignment at the `tdt` sweep's shape (fp32 N(0,1) logits (B, T, U+1, V + D), full lengths, durations
+    0 .. D-1): rnnt_tdt_forced_align (Python entry: label check, pass 1, Viterbi + backtrace), wr_rnnt_tdt_align alone and
+    wr_rnnt_tdt_loss_fwd (pass 1, both sweeps, records) on the same logits, alternating.  HIP events, median of --steps
+    rounds after one warm-up.  --only tdtalign runs wr_rnnt_tdt_align and wr_rnnt_tdt_loss_fwd once each (for a profiler)."""
+    import ctypes
+    import wenet_celoss_amd as w
+    from wenet_celoss_amd import _lib
+    dev = torch.device("cuda:0")
+    B, T, U, V, D = args.B, args.T, args.U, args.V, args.durations
+    U1, W = U + 1, V + D
+    durations = tuple(range(D))
+    durs = (ctypes.c_int32 * D)(*durations)
+    torch.manual_seed(3)
+    logits = torch.empty(B, T, U1, W, device=dev)
+    for b in range(B):
+        logits[b].normal_()
+    y = torch.randint(1, V, (B, U), dtype=torch.int32, device=dev)
+    ll = torch.full((B,), T, dtype=torch.int32, device=dev); tl = torch.full((B,), U, dtype=torch.int32, device=dev)
+    ws = _lib.workspace("wr_rnnt_tdt_workspace_bytes", B, T, U1, D, device=dev)
+    frames, jumps_of = (torch.empty(B, U, dtype=torch.int32, device=dev) for _ in range(2))
+    blank_jumps = torch.empty(B, T, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, dtype=torch.float64, device=dev)
+    costs = torch.empty(B, device=dev)
+    fns = {
+        "wr_rnnt_tdt_align": lambda: _lib.call("wr_rnnt_tdt_align", logits, _lib.WR_F32, y, ll, tl, B, T, U1, V, 0, durs, D, 0.0,
+                                               frames, jumps_of, blank_jumps, scores, ws, ws.numel(), device=dev),
+        "wr_rnnt_tdt_loss_fwd": lambda: _lib.call("wr_rnnt_tdt_loss_fwd", logits, _lib.WR_F32, y, ll, tl, B, T, U1, V, 0, durs,
+                                                  D, 0.0, costs, ws, ws.numel(), device=dev),
+        "rnnt_tdt_forced_align": lambda: w.rnnt_tdt_forced_align(logits, y, ll, tl, durations, return_blank_jumps=True),
+    }
+    if args.only == "tdtalign":
+        del fns["rnnt_tdt_forced_align"]
+    res = alternating(fns, 1 if args.only == "tdtalign" else args.steps)
+    rec = {"what": "tdt forced alignment vs tdt loss forward (fp32 logits)", "shape": [B, T, U1, W],
+           "durations": list(durations), "reps": args.steps, "logits_gb": round(logits.numel() * 4 / 1e9, 2),
+           "workspace_gb": round(ws.numel() / 1e9, 3), "score_mean": round(float(scores.mean()), 4),
+           "cost_mean": round(float(costs.mean()), 4)}
+    for k, (med, lo, hi) in res.items():
+        rec[k + "_ms"] = round(med, 3)
+        rec[k + "_ms_min_max"] = [round(lo, 3), round(hi, 3)]
+    print(json.dumps(rec), flush=True)
+
+
 def tdt_decision_traces(model, enc, lens, n_steps):
     """Every stream's decisions [(frame, token, duration)] by a lock-step torch loop over the HIP step kernels (all streams
     step together; a stream that has not emitted repeats its predictor step, which gives the same output)."""
@@ -1053,11 +1097,11 @@ def bench_tdtdec(args):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align", "simple", "smoothed", "pruned", "tdt",
-                                     "tdtdec"])
-    ap.add_argument("--durations", type=int, default=5, help="tdt: number of durations D (the set is 0 .. D-1)")
+                                     "tdtalign", "tdtdec"])
+    ap.add_argument("--durations", type=int, default=5, help="tdt, tdtalign: number of durations D (the set is 0 .. D-1)")
     ap.add_argument("--n-steps", type=int, default=64)
     ap.add_argument("--chunks", type=int, default=4)
-    ap.add_argument("--B", type=int, default=None, help="batch size (default 32; simple, smoothed, pruned, tdt: 16)")
+    ap.add_argument("--B", type=int, default=None, help="batch size (default 32; simple, smoothed, pruned, tdt, tdtalign: 16)")
     ap.add_argument("--T", type=int, default=1000)
     ap.add_argument("--U", type=int, default=150)
     ap.add_argument("--V", type=int, default=5000)
@@ -1076,7 +1120,8 @@ if __name__ == "__main__":
     ap.add_argument("--ragged", action="store_true", help="step: frames in [0.8 T, T] sorted, labels in [U/3, U]")
     ap.add_argument("--buckets", type=int, default=4, help="step: label-length groups of the fused node (1 = off)")
     ap.add_argument("--only", default="", help="step: comma-separated subset of the configurations; simple: \"simple\" "
-                                              "skips the composite; pruned: \"pruned\" skips the full-lattice siblings")
+                                              "skips the composite; pruned: \"pruned\" skips the full-lattice siblings; tdt: \"tdt\", "
+                                              "tdtalign: \"tdtalign\" run one call of each entry point (for a profiler)")
     ap.add_argument("--budget-mb", type=float, default=0.0,
                     help="step: time the memory-bounded fused node (logits_budget = this many MiB) beside the plain one, "
                          "fp32 and bf16x3, with max_memory_allocated of each")
@@ -1084,10 +1129,10 @@ if __name__ == "__main__":
     ap.add_argument("--tile", type=int, default=0, help="lane-GEMM tile policy of the decoders (wr_tune_set key 6)")
     a = ap.parse_args()
     if a.B is None:
-        a.B = 16 if a.what in ("simple", "smoothed", "pruned", "tdt") else 32
+        a.B = 16 if a.what in ("simple", "smoothed", "pruned", "tdt", "tdtalign") else 32
     if a.tile:
         from wenet_celoss_amd import _lib
         _lib.load().wr_tune_set(6, a.tile)
     {"joint": bench_joint, "ctc": bench_ctc, "greedy": bench_greedy, "beam": bench_beam, "step": bench_step, "ctcdec": bench_ctcdec, "hotword": bench_hotword,
      "align": bench_align, "simple": bench_simple, "smoothed": bench_smoothed, "pruned": bench_pruned,
-     "tdt": bench_tdt, "tdtdec": bench_tdtdec}[a.what](a)
+     "tdt": bench_tdt, "tdtalign": bench_tdtalign, "tdtdec": bench_tdtdec}[a.what](a)

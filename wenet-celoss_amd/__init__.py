@@ -14,7 +14,7 @@ from .rnnt_align import joint_rnnt_forced_align, rnnt_forced_align, rnnt_frame_t
 from .rnnt_simple import rnnt_loss_simple, rnnt_simple_forced_align  # noqa: F401
 from .rnnt_smoothed import rnnt_loss_smoothed  # noqa: F401
 from .rnnt_pruned import do_rnnt_pruning, get_rnnt_prune_ranges, rnnt_loss_pruned  # noqa: F401
-from .rnnt_tdt import TDTLoss, rnnt_tdt_lattice, rnnt_tdt_loss  # noqa: F401
+from .rnnt_tdt import TDTLoss, rnnt_tdt_forced_align, rnnt_tdt_lattice, rnnt_tdt_loss  # noqa: F401
 from .predictor import ConvPredictor, EmbeddingPredictor, PredictorBase, RNNPredictor  # noqa: F401
 from .search.greedy_search import (basic_greedy_search, basic_greedy_search_both,  # noqa: F401
                                    basic_greedy_search_hw, edit_distance, tdt_greedy_search)
@@ -29,4 +29,4 @@ __all__ = ["rnnt_loss", "RNNTLoss", "CTC", "ctc_loss", "TransducerJoint", "joint
            "ctc_greedy_search", "ctc_prefix_beam_search", "forced_align", "forced_align_batch", "rnnt_forced_align",
            "joint_rnnt_forced_align", "rnnt_frame_tokens", "rnnt_loss_simple", "rnnt_simple_forced_align", "rnnt_loss_smoothed",
            "get_rnnt_prune_ranges", "do_rnnt_pruning", "rnnt_loss_pruned", "k2",
-           "rnnt_tdt_loss", "TDTLoss", "rnnt_tdt_lattice", "tdt_greedy_search"]
+           "rnnt_tdt_loss", "TDTLoss", "rnnt_tdt_lattice", "tdt_greedy_search", "rnnt_tdt_forced_align"]

@@ -14,8 +14,9 @@
 //                             double-buffered LDS slot plus one barrier across waves.  fp64 state, PF rows in flight.
 //   lattice_export_kernel     alpha / beta of either lattice as plain (B, T, U1) floats, for the tests.
 //
-// The token-and-duration transducer (TDT) loss follows at the end of the file: a lattice of its own, whose cells have
-// 2 * D arcs that jump up to 8 frames (include/wr_api.h, "Token-and-duration transducer"; rnnt_tdt.hpp for the arrays).
+// The token-and-duration transducer (TDT) loss and its forced alignment follow at the end of the file: a lattice of its
+// own, whose cells have 2 * D arcs that jump up to 8 frames (include/wr_api.h, "Token-and-duration transducer";
+// rnnt_tdt.hpp for the arrays).
 #include "rnnt_lattice.hpp"
 #include "rnnt_tdt.hpp"
 #include "row_stream.hpp"
@@ -284,6 +285,8 @@ extern "C" int wr_rnnt_lattice_export(const void *workspace_d, size_t workspace_
 //   tdt_grad_kernel     one wave per row: pruned_grad_kernel's streamed loop over the token columns, lanes 0 .. D-1 then
 //                       write the duration columns.
 //   tdt_export_kernel   alpha / beta as plain (B, T, U1) floats, for the tests.
+//   tdt_viterbi_kernel  forced alignment: the forward sweep with max for log-add and one decision byte per cell, then the
+//                       backtrace by the same workgroup (include/wr_api.h, "TDT forced alignment").
 namespace wr {
 namespace {
 
@@ -649,7 +652,224 @@ __global__ __launch_bounds__(256) void tdt_export_kernel(
     beta[r] = be;
 }
 
+// ---- TDT forced alignment (include/wr_api.h, "TDT forced alignment"): the best path of the lattice above.
+constexpr int kTdtStageBytes = 32768;      // decision bytes staged in LDS per backtrace block ...
+constexpr int kTdtStageDiags = 256;        // ... of at most this many anti-diagonals (at least 32: U1max <= 1024)
+constexpr int kTdtJumpWindow = 2048;       // frames whose blank jumps collect in LDS between two coalesced flushes
+// decision byte of a cell: the winning arc's d in the low nibble, kTdtDecLabel set if it is a label arc; kTdtDecNone where
+// no arc won (the cell is unreachable)
+constexpr unsigned kTdtDecLabel = 0x10;
+constexpr unsigned kTdtDecNone = 0xFF;
+
+// The forward branch of tdt_sweep_kernel with max for log-add: own[j] / nbr[j] hold the best blank / label candidate into
+// (t + j, u) / (t + j, u + 1) and, in nibble j of otags / ntags, the jump d of the arc that holds it.  A push replaces on
+// >=: within one ring entry later pushes come from later frames, so the smaller d wins a tie, and a NaN candidate never
+// replaces anything.  The two rings merge as "label only if strictly greater"; the terminal is own[0] of lane U_b at
+// t = T_b.  Every cell's decision goes out as one byte in anti-diagonal order (`decisions`: the workspace's beta region).
+//
+// Backtrace, same workgroup: rounds of (stage a block of anti-diagonals into LDS, coalesced; thread 0 walks it; all
+// threads flush the blank jumps of the frames walked, coalesced).  Every step lowers t + u, the walk is bounded by
+// T_b + U_b + 1 arcs all the same, and a decision byte that names no arc of this lattice ends it with the no-path outputs.
+template <int PF>
+__global__ __launch_bounds__(kRnntMaxCols) void tdt_viterbi_kernel(
+    const float2 *__restrict__ tok, const float *__restrict__ dur, const int32_t *__restrict__ llens,
+    const int32_t *__restrict__ tlens, int Tmax, int U1max, int S, const TdtDur dd, uint8_t *decisions,
+    int32_t *__restrict__ label_frames, int32_t *__restrict__ label_durations, int32_t *__restrict__ blank_jumps,
+    double *__restrict__ scores)
+{
+    constexpr double NEG = (double)kNegInf;
+    __shared__ double xch[2][kRnntMaxCols / kWave];
+    __shared__ int xtag[2][kRnntMaxCols / kWave];
+    __shared__ uint32_t stage[kTdtStageBytes / 4 + 1];
+    __shared__ int lfr[kRnntMaxCols], ldu[kRnntMaxCols];
+    __shared__ uint8_t jl[kTdtJumpWindow];
+    __shared__ int cur[4];      // the backtrace cursor: t, u, state (0 walking, 1 at the origin, 2 no path), terminal's d
+    const int b = blockIdx.x;
+    const int u = threadIdx.x;
+    const int lane = u & (kWave - 1), wave = u >> 6;
+    const int nw = blockDim.x >> 6;
+    const int T = clampi(llens[b], 0, Tmax), U = clampi(tlens[b], 0, U1max - 1);
+    int32_t *frames_out = label_frames + (size_t)b * (U1max - 1);
+    int32_t *durs_out = label_durations + (size_t)b * (U1max - 1);
+    int32_t *jumps_out = blank_jumps ? blank_jumps + (size_t)b * Tmax : nullptr;
+
+    const bool in_row = u < U1max;
+    const int col = in_row ? u : U1max - 1;
+    const bool ucol = in_row && u <= U;
+    const size_t ub = (size_t)b * S * U1max;
+    const int D = dd.D;
+    const int nsteps = T + U;                // anti-diagonals 0 .. T + U - 1 hold this utterance's cells
+    uint8_t *dec = decisions + ub;
+
+    auto load_arc = [&](int s) -> TdtArc {   // tdt_sweep_kernel's: always a position of the arrays
+        int t = s - col;
+        t = t < 0 ? 0 : (t >= T ? T - 1 : t);
+        const size_t k = ub + (size_t)(t + col) * U1max + col;
+        TdtArc a;
+        const float2 p = tok[k];
+        a.tb = p.x;
+        a.tl = p.y;
+#pragma unroll
+        for (int d = 0; d < kTdtMaxD; ++d) a.w[d] = dd.slot[d] >= 0 ? dur[k * D + dd.slot[d]] : 0.f;
+        return a;
+    };
+
+    double result = NEG;
+    int rdec = 0;
+    if (T > 0) {                             // T_b = 0 has no cell to read: no path (the Python layer refuses it)
+        TdtArc ring[PF];
+        double own[kTdtMaxD], nbr[kTdtMaxD];
+#pragma unroll
+        for (int j = 0; j < kTdtMaxD; ++j) own[j] = nbr[j] = NEG;
+        uint64_t otags = 0, ntags = 0;
+        double send = NEG;
+        int stag = 0;
+#pragma unroll
+        for (int i = 0; i < PF; ++i) ring[i] = load_arc(i);
+        for (int base = 0; base <= nsteps; base += PF) {          // the cells' anti-diagonals and the terminal's
+#pragma unroll
+            for (int i = 0; i < PF; ++i) {
+                const int s = base + i, t = s - u;                // steps s > T + U have no active lane
+                const TdtArc cur_arc = ring[i];
+                ring[i] = load_arc(s + PF);
+                double recv = lane_rotate_up_d(send);
+                int rtag = __builtin_amdgcn_update_dpp(0, stag, 0x13C, 0xf, 0xf, false);
+                if (lane == 0) {     // step 0 has nothing to receive (the LDS slots are still unwritten)
+                    const bool none = s == 0 || wave == 0;
+                    recv = none ? NEG : xch[(s + 1) & 1][wave - 1];
+                    rtag = none ? 0 : xtag[(s + 1) & 1][wave - 1];
+                }
+                const bool active = ucol & (t >= 0) & (t < T);
+                const double own0 = own[0];
+                const int otag0 = (int)(otags & 15);
+                const bool lab = recv > own0;                     // strict: a tie goes to the blank arc
+                double v = lab ? recv : own0;
+                unsigned by = lab ? (kTdtDecLabel | (unsigned)rtag) : (unsigned)otag0;
+                if (s == 0 && u == 0) { v = 0.0; by = 0; }        // the origin
+                if (t == T && u == U) { result = own0; rdec = otag0; }   // the terminal: blank arcs that end exactly at T
+                v = active ? v : NEG;
+                by = (v == NEG) ? kTdtDecNone : by;
+                if (active) dec[(size_t)s * U1max + u] = (uint8_t)by;
+                const double ab = v + (double)(active ? cur_arc.tb : 0.f);
+                const double al = (u < U) ? v + (double)(active ? cur_arc.tl : 0.f) : NEG;
+#pragma unroll
+                for (int d = 0; d < kTdtMaxD; ++d) {
+                    if (dd.slot[d] >= 0) {
+                        const double w = (double)(active ? cur_arc.w[d] : 0.f);
+                        const uint64_t clr = ~((uint64_t)15 << (4 * d)), tag = (uint64_t)d << (4 * d);
+                        if (d >= 1) {
+                            const double c = ab + w;
+                            const bool win = c >= own[d];
+                            own[d] = win ? c : own[d];
+                            otags = win ? ((otags & clr) | tag) : otags;
+                        }
+                        const double c = al + w;
+                        const bool win = c >= nbr[d];
+                        nbr[d] = win ? c : nbr[d];
+                        ntags = win ? ((ntags & clr) | tag) : ntags;
+                    }
+                }
+                send = nbr[0];
+                stag = (int)(ntags & 15);
+#pragma unroll
+                for (int j = 0; j + 1 < kTdtMaxD; ++j) { own[j] = own[j + 1]; nbr[j] = nbr[j + 1]; }
+                own[kTdtMaxD - 1] = nbr[kTdtMaxD - 1] = NEG;
+                otags >>= 4;
+                ntags >>= 4;
+                if (lane == kWave - 1) { xch[s & 1][wave] = send; xtag[s & 1][wave] = stag; }
+                if (nw > 1) __syncthreads();
+            }
+        }
+    }
+    if (u == U) {
+        scores[b] = result;
+        cur[0] = T;
+        cur[1] = U;
+        cur[2] = (result > NEG) ? 0 : 2;
+        cur[3] = rdec;
+    }
+    // every lane stored decision bytes: drain them and drop this CU's cached lines before the workgroup reads them back
+    __threadfence();
+    __syncthreads();
+
+    unsigned dmask = 0;
+#pragma unroll
+    for (int d = 0; d < kTdtMaxD; ++d) dmask |= dd.slot[d] >= 0 ? 1u << d : 0u;
+    const int nd = min(kTdtStageDiags, kTdtStageBytes / U1max);
+    int budget = T + U + 1;                  // thread 0's: arcs of the longest path, the terminal's included
+    while (cur[2] == 0) {
+        const int ct = cur[0], cu = cur[1];  // the cursor (t, u): on diagonal ct + cu, or the terminal (T, U)
+        const int hi = min(ct + cu, nsteps - 1), lo = max(hi - nd + 1, 0);
+        const size_t g0 = ub + (size_t)lo * U1max, a0 = g0 & ~(size_t)3;     // whole words, from the one that holds g0
+        const int nwords = ((hi - lo + 1) * U1max + (int)(g0 - a0) + 3) >> 2;
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(decisions + a0);
+        for (int i = u; i < nwords; i += blockDim.x) stage[i] = src[i];
+        const int fhi = ct - 1, flo = max(fhi - kTdtJumpWindow + 1, 0);      // frames >= ct are final already
+        for (int i = u; i < kTdtJumpWindow; i += blockDim.x) jl[i] = 0;
+        __syncthreads();
+        if (u == 0) {
+            const uint8_t *sb = reinterpret_cast<const uint8_t *>(stage) + (g0 - a0);
+            int t = ct, uu = cu, state = 0;
+            while (true) {
+                if (t == 0 && uu == 0) { state = 1; break; }
+                const int s = t + uu;
+                if (t < T && s < lo) break;                       // the next block
+                const unsigned by = (t == T) ? (unsigned)cur[3] : sb[(s - lo) * U1max + uu];
+                const int d = by & 15, f = t - d;
+                const bool lab = (by & kTdtDecLabel) != 0;
+                const bool arc = (by >> 5) == 0 && ((dmask >> d) & 1) != 0 && f >= 0 && (lab ? uu >= 1 : d >= 1);
+                if (!arc || --budget < 0) { state = 2; break; }
+                if (f < flo) break;                               // the next window of frames
+                if (lab) { --uu; lfr[uu] = f; ldu[uu] = d; } else jl[fhi - f] = (uint8_t)d;
+                t = f;
+            }
+            if (state == 0 && t == ct && uu == cu) state = 2;     // a round always takes a step: nd > 9, the window > 8
+            cur[0] = t;
+            cur[1] = uu;
+            cur[2] = state;
+        }
+        __syncthreads();
+        if (jumps_out)
+            for (int f = cur[0] + u; f <= fhi; f += blockDim.x) jumps_out[f] = jl[fhi - f];
+        __syncthreads();
+    }
+    const bool found = cur[2] == 1;
+    if (!found && u == 0) scores[b] = NEG;
+    for (int i = u; i < U1max - 1; i += blockDim.x) {
+        const bool in = found && i < U;
+        frames_out[i] = in ? lfr[i] : -1;
+        durs_out[i] = in ? ldu[i] : -1;
+    }
+    if (jumps_out)
+        for (int f = (found ? T : 0) + u; f < Tmax; f += blockDim.x) jumps_out[f] = 0;
+}
+
 }  // namespace
+
+// pass 1 of the loss and of the alignment: {tok_blank, tok_label}, the D duration log-probabilities and the token
+// log-sum-exp of every cell
+static int tdt_launch_stats(const TdtWs &w, char *ws, const void *logits_d, int dtype, const int32_t *targets_d,
+                            const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax, int U1max,
+                            int V, int D, int blank, double sigma, hipStream_t st)
+{
+    float2 *tok = reinterpret_cast<float2 *>(ws + w.tok_off);
+    float *durp = reinterpret_cast<float *>(ws + w.dur_off);
+    float *denom = reinterpret_cast<float *>(ws + w.denom_off);
+    const long nrows = (long)B * Tmax * U1max;
+    const size_t row_bytes = (size_t)(V + D) * (dtype == WR_F32 ? 4 : 2);
+    const dim3 grid1(stream_grid(nrows, tune_get(kTuneLseBlocksPerCu), row_bytes, 16 * 1024));
+    const bool nt = (tune_get(kTuneNonTemporal) & 4) != 0;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return with_bool(nt, [&](auto nt_c) {
+            return with_int<16, 8, 4>(unroll_of(kTuneLseUnroll), [&](auto un) {
+                return launch("tdt_stats_kernel", tdt_stats_kernel<T, nt_c.value, un.value>, grid1, dim3(256), 0, st,
+                              static_cast<const T *>(logits_d), targets_d, logit_lengths_d, target_lengths_d, nrows, Tmax,
+                              U1max, V, D, blank, (float)sigma, w.S, tok, durp, denom);
+            });
+        });
+    });
+}
 
 int tdt_loss_fwd_body(const void *logits_d, int dtype, const int32_t *targets_d, const int32_t *logit_lengths_d,
                       const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V, int blank, const TdtDur &dur,
@@ -664,19 +884,8 @@ int tdt_loss_fwd_body(const void *logits_d, int dtype, const int32_t *targets_d,
     double *alpha = reinterpret_cast<double *>(ws + w.alpha_off), *beta = reinterpret_cast<double *>(ws + w.beta_off);
     double *cost = reinterpret_cast<double *>(ws + w.cost_off);
     const long nrows = (long)B * Tmax * U1max;
-    const size_t row_bytes = (size_t)(V + D) * (dtype == WR_F32 ? 4 : 2);
-    const dim3 grid1(stream_grid(nrows, tune_get(kTuneLseBlocksPerCu), row_bytes, 16 * 1024));
-    const bool nt = (tune_get(kTuneNonTemporal) & 4) != 0;
-    WR_TRY(with_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        return with_bool(nt, [&](auto nt_c) {
-            return with_int<16, 8, 4>(unroll_of(kTuneLseUnroll), [&](auto un) {
-                return launch("tdt_stats_kernel", tdt_stats_kernel<T, nt_c.value, un.value>, grid1, dim3(256), 0, st,
-                              static_cast<const T *>(logits_d), targets_d, logit_lengths_d, target_lengths_d, nrows, Tmax,
-                              U1max, V, D, blank, (float)sigma, w.S, tok, durp, denom);
-            });
-        });
-    }));
+    WR_TRY(tdt_launch_stats(w, ws, logits_d, dtype, targets_d, logit_lengths_d, target_lengths_d, B, Tmax, U1max, V, D,
+                            blank, sigma, st));
     WR_TRY(launch("tdt_sweep_kernel", tdt_sweep_kernel<4>, dim3(B, 2), dim3(64 * w.K), 0, st, tok, durp, logit_lengths_d,
                   target_lengths_d, Tmax, U1max, w.S, dur, alpha, beta, reinterpret_cast<double *>(ws + w.ll_off), cost,
                   costs_d, reinterpret_cast<double *>(ws + w.dump_off)));
@@ -720,6 +929,23 @@ int tdt_export_body(const void *workspace_d, const int32_t *logit_lengths_d, con
                   0, st, reinterpret_cast<const double *>(ws + w.alpha_off),
                   reinterpret_cast<const double *>(ws + w.beta_off), logit_lengths_d, target_lengths_d, B, Tmax, U1max, w.S,
                   alpha_d, beta_d);
+}
+
+int tdt_align_body(const void *logits_d, int dtype, const int32_t *targets_d, const int32_t *logit_lengths_d,
+                   const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V, int blank, const TdtDur &dur,
+                   double sigma, int32_t *label_frames_d, int32_t *label_durations_d, int32_t *blank_jumps_d,
+                   double *scores_d, void *workspace_d, hipStream_t st)
+{
+    const TdtWs w = tdt_ws_layout(B, Tmax, U1max, dur.D);
+    char *ws = static_cast<char *>(workspace_d);
+    WR_TRY(tdt_launch_stats(w, ws, logits_d, dtype, targets_d, logit_lengths_d, target_lengths_d, B, Tmax, U1max, V, dur.D,
+                            blank, sigma, st));
+    // one decision byte per cell, in the beta region (8 bytes per cell), which alignment does not use otherwise
+    // (three rows in flight: with the sweep's four the rings and their tags no longer fit 128 VGPRs)
+    return launch("tdt_viterbi_kernel", tdt_viterbi_kernel<3>, dim3(B), dim3(64 * w.K), 0, st,
+                  reinterpret_cast<const float2 *>(ws + w.tok_off), reinterpret_cast<const float *>(ws + w.dur_off),
+                  logit_lengths_d, target_lengths_d, Tmax, U1max, w.S, dur, reinterpret_cast<uint8_t *>(ws + w.beta_off),
+                  label_frames_d, label_durations_d, blank_jumps_d, scores_d);
 }
 
 }  // namespace wr

@@ -1,4 +1,5 @@
-// Token-and-duration transducer (TDT) loss: the entry points (include/wr_api.h, "Token-and-duration transducer").  Host
+// Token-and-duration transducer (TDT) loss and forced alignment: the entry points (include/wr_api.h, "Token-and-duration
+// transducer", "TDT forced alignment").  Host
 // code only: every argument is checked here, before the first HIP call; the kernels and their launches are in
 // rnnt_lattice.hip (rnnt_tdt.hpp).
 #include "rnnt_tdt.hpp"
@@ -71,6 +72,23 @@ extern "C" int wr_rnnt_tdt_loss_bwd(const void *logits_d, int dtype, const int32
                "rnnt_tdt_loss_bwd: logits and grads must sit at the same offset within a 16-byte line");
     return tdt_loss_bwd_body(logits_d, dtype, targets_d, logit_lengths_d, target_lengths_d, B, Tmax, U1max, V, blank, D,
                              grad_costs_d, grads_d, workspace_d, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int wr_rnnt_tdt_align(const void *logits_d, int dtype, const int32_t *targets_d, const int32_t *logit_lengths_d,
+                                 const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V, int blank,
+                                 const int32_t *durations, int D, double sigma, int32_t *label_frames_d,
+                                 int32_t *label_durations_d, int32_t *blank_jumps_d, double *scores_d, void *workspace_d,
+                                 size_t workspace_bytes, void *stream)
+{
+    TdtDur dur;
+    WR_TRY(tdt_check("rnnt_tdt_align", dtype, B, Tmax, U1max, V, blank, durations, D, sigma, workspace_bytes, &dur));
+    WR_REQUIRE(logits_d && logit_lengths_d && target_lengths_d && workspace_d && (targets_d || U1max == 1), WR_EINVAL,
+               "rnnt_tdt_align: null pointer argument");
+    WR_REQUIRE(scores_d && ((label_frames_d && label_durations_d) || U1max == 1), WR_EINVAL,
+               "rnnt_tdt_align: label_frames, label_durations or scores is null");
+    return tdt_align_body(logits_d, dtype, targets_d, logit_lengths_d, target_lengths_d, B, Tmax, U1max, V, blank, dur,
+                          sigma, label_frames_d, label_durations_d, blank_jumps_d, scores_d, workspace_d,
+                          static_cast<hipStream_t>(stream));
 }
 
 extern "C" int wr_rnnt_tdt_export_lattice(const void *workspace_d, size_t workspace_bytes, const int32_t *logit_lengths_d,

@@ -6,7 +6,7 @@
 //   tok     float2 {tok_blank, tok_label}   anti-diagonal    log-softmax over the V token columns, - sigma
 //   dur     float[D]                        anti-diagonal    log-softmax over the D duration columns
 //   alpha   double                          anti-diagonal
-//   beta    double                          anti-diagonal
+//   beta    double                          anti-diagonal    (alignment: one decision byte per cell in its first eighth)
 //   denom   float                           plain            log-sum-exp of the token columns
 //   rec     float[3 + D]                    plain            the gradient's row constants (tdt_record_kernel)
 //   ll, cost  double[B];  dump  double[B][2][kRnntMaxCols]   (absorbs the stores of idle sweep lanes)
@@ -85,5 +85,10 @@ int tdt_loss_bwd_body(const void *logits_d, int dtype, const int32_t *targets_d,
                       const float *grad_costs_d, void *grads_d, const void *workspace_d, hipStream_t st);
 int tdt_export_body(const void *workspace_d, const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B,
                     int Tmax, int U1max, int D, float *alpha_d, float *beta_d, hipStream_t st);
+// Forced alignment: row statistics, then the Viterbi sweep and its backtrace (one decision byte per cell in `beta`).
+int tdt_align_body(const void *logits_d, int dtype, const int32_t *targets_d, const int32_t *logit_lengths_d,
+                   const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V, int blank, const TdtDur &dur,
+                   double sigma, int32_t *label_frames_d, int32_t *label_durations_d, int32_t *blank_jumps_d,
+                   double *scores_d, void *workspace_d, hipStream_t st);
 
 }  // namespace wr

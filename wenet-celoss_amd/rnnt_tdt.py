@@ -1,5 +1,6 @@
-"""Token-and-duration transducer (TDT) loss, backed by the HIP kernels (csrc/rnnt_lattice.hip; the contract is in
-include/wr_api.h, "Token-and-duration transducer"; DESIGN.md, "The token-and-duration loss").
+"""Token-and-duration transducer (TDT) loss and forced alignment, backed by the HIP kernels (csrc/rnnt_lattice.hip; the
+contract is in include/wr_api.h, "Token-and-duration transducer" and "TDT forced alignment"; DESIGN.md, "The
+token-and-duration loss" and "TDT forced alignment").
 
 TDT (Xu et al. 2023, the loss of NeMo's Parakeet-TDT models): the joiner's output row holds ``V`` token logits and, after
 them, ``D = len(durations)`` duration logits with a softmax of their own.  An arc emits a token -- blank or the next label
@@ -18,6 +19,7 @@ from typing import Sequence, Tuple
 import torch
 
 from . import _lib
+from .rnnt_align import _blank, _prepare
 from .rnnt_loss import _validate
 
 MAX_DURATION = 8
@@ -136,6 +138,46 @@ class TDTLoss(torch.nn.Module):
     def forward(self, logits, targets, logit_lengths, target_lengths):
         return rnnt_tdt_loss(logits, targets, logit_lengths, target_lengths, self.durations, self.blank, self.sigma,
                              self.reduction)
+
+
+@torch.no_grad()
+def rnnt_tdt_forced_align(logits: torch.Tensor, targets: torch.Tensor, logit_lengths: torch.Tensor,
+                          target_lengths: torch.Tensor, durations: Sequence[int], blank: int = 0, sigma: float = 0.0,
+                          return_blank_jumps: bool = False):
+    """Best path of the TDT lattice of ``logits`` (B, T, U+1, V + D), float32 / float16 / bfloat16, as ``rnnt_tdt_loss``
+    takes them (include/wr_api.h, "TDT forced alignment": the Viterbi pass and its backtrace run on the device).
+    targets (B, U); lengths (B,) with 1 <= logit_lengths[b] <= T and 0 <= target_lengths[b] <= U.  ``durations`` and
+    ``sigma`` as in ``rnnt_tdt_loss``; ``blank`` in [0, V), negative counts from V.  Returns device tensors
+    (label_frames (B, U) int32: the frame at which the arc emitting label u+1 leaves; label_durations (B, U) int32: the
+    frames that arc jumps; both -1 past target_lengths[b]; scores (B,) float64: the best path's log-probability, -inf
+    for an utterance without a path, whose labels are all -1) and, with ``return_blank_jumps``, blank_jumps (B, T) int32:
+    the jump of the blank arc leaving frame t on the path, 0 where none does.  ``rnnt_frame_tokens`` reads label_frames."""
+    what = "rnnt_tdt_forced_align"
+    durs, sg = check_tdt(what, durations, sigma)
+    if logits.dim() != 4:
+        raise ValueError(f"{what}: logits must be 4-D (batch, time, target, token + duration)")
+    D = len(durs)
+    if logits.shape[-1] <= D:
+        raise ValueError(f"{what}: logits must be (B, T, U+1, V + {D}) with V >= 1 (got {tuple(logits.shape)})")
+    x = logits.detach().contiguous()
+    B, T, U1, W = x.shape
+    V = W - D
+    dev = x.device
+    blank = _blank(blank, V, what)
+    code = _lib.dtype_code(x.dtype)
+    tg, ll, tl = _prepare(targets, logit_lengths, target_lengths, B, T, U1, V, dev, what)
+    if not x.is_cuda:
+        raise RuntimeError(f"wenet_celoss_amd.{what}: logits must live on a HIP device (this package has no CPU path)")
+    frames = torch.empty(B, U1 - 1, dtype=torch.int32, device=dev)
+    jumps_of = torch.empty(B, U1 - 1, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, dtype=torch.float64, device=dev)
+    blank_jumps = torch.empty(B, T, dtype=torch.int32, device=dev) if return_blank_jumps else None
+    ws = _lib.workspace("wr_rnnt_tdt_workspace_bytes", B, T, U1, D, device=dev)
+    _lib.call("wr_rnnt_tdt_align", x, code, tg, ll, tl, B, T, U1, V, blank, _durations_arg(durs), D, sg, frames, jumps_of,
+              blank_jumps, scores, ws, ws.numel(), device=dev)
+    if return_blank_jumps:
+        return frames, jumps_of, scores, blank_jumps
+    return frames, jumps_of, scores
 
 
 @torch.no_grad()

@@ -39,7 +39,7 @@ from .rnnt_simple import rnnt_simple_forced_align
 from . import k2
 from .rnnt_lattice import check_lattice, is_default
 from .rnnt_pruned import rnnt_loss_pruned
-from .rnnt_tdt import check_tdt, rnnt_tdt_loss
+from .rnnt_tdt import check_tdt, rnnt_tdt_forced_align, rnnt_tdt_loss
 from .search.greedy_search import (basic_greedy_search, basic_greedy_search_both, basic_greedy_search_hw,
                                    tdt_greedy_search)
 from .search.prefix_beam_search import PrefixBeamSearch
@@ -408,7 +408,8 @@ class Transducer(nn.Module):
         model must have been built with `simple_loss_weight > 0`).  Returns (label_frames (B, U) int32, -1 past
         text_lengths; scores (B,) float64) on the device.  Call it in eval mode unless dropout is wanted.  Both heads
         align on the regular lattice without a delay penalty, whatever `rnnt_type` / `delay_penalty` the model trains
-        with."""
+        with.  On a token-and-duration model ``head="joint"`` is `tdt_forced_align` (the TDT lattice), of which it
+        returns (label_frames, scores)."""
         if head not in ("joint", "simple"):
             raise ValueError(f"forced_align: head must be \"joint\" or \"simple\", got {head!r}")
         if head == "simple" and not hasattr(self, "simple_am_proj"):
@@ -417,6 +418,10 @@ class Transducer(nn.Module):
         assert (speech.shape[0] == speech_lengths.shape[0] == text.shape[0] == text_lengths.shape[0]), \
             (speech.shape, speech_lengths.shape, text.shape, text_lengths.shape)
         check_limits(text, text_lengths, with_ctc=False)
+        if head == "joint" and self._is_tdt():              # the joiner's columns are tokens and durations: its own lattice
+            frames, _, scores = self.tdt_forced_align(speech, speech_lengths, text, text_lengths, context_list,
+                                                      context_lengths)
+            return frames, scores
         with torch.no_grad():
             _, encoder_out, _, encoder_out_lens, _, predictor_out, _ = self._loss_inputs(
                 speech, speech_lengths, text, context_list, context_lengths)
@@ -436,6 +441,31 @@ class Transducer(nn.Module):
                                                activation=jt.activation)
             logits = self.joint(encoder_out, predictor_out)
             return rnnt_forced_align(logits, rnnt_text, encoder_out_lens, rnnt_text_lengths, blank=self.blank)
+
+    @torch.jit.unused      # HIP-backed, like forward
+    def tdt_forced_align(self, speech: torch.Tensor, speech_lengths: torch.Tensor, text: torch.Tensor,
+                         text_lengths: torch.Tensor, context_list: torch.Tensor = torch.IntTensor([0]),
+                         context_lengths: torch.Tensor = torch.IntTensor([0]), return_blank_jumps: bool = False):
+        """Forced alignment of a token-and-duration model: the best path through the lattice whose negative log-sum
+        `forward` reports as `loss_rnnt` (rnnt_tdt_forced_align on the joiner's logits, in whatever precision it produces
+        them, with the model's `tdt_durations` and `tdt_sigma`) -- the same encoder, predictor and blank / IGNORE_ID
+        label mapping as the loss block.  Returns (label_frames (B, U) int32, label_durations (B, U) int32, both -1 past
+        text_lengths; scores (B,) float64[; blank_jumps (B, T) int32]) on the device; frames are encoder frames."""
+        if not self._is_tdt():
+            raise ValueError("Transducer.tdt_forced_align: the model has no tdt_durations (use forced_align)")
+        assert text_lengths.dim() == 1, text_lengths.shape
+        assert (speech.shape[0] == speech_lengths.shape[0] == text.shape[0] == text_lengths.shape[0]), \
+            (speech.shape, speech_lengths.shape, text.shape, text_lengths.shape)
+        check_limits(text, text_lengths, with_ctc=False)
+        with torch.no_grad():
+            _, encoder_out, _, encoder_out_lens, _, predictor_out, _ = self._loss_inputs(
+                speech, speech_lengths, text, context_list, context_lengths)
+            rnnt_text = text.to(torch.int64)
+            rnnt_text = torch.where(rnnt_text == self.ignore_id, 0, rnnt_text).to(torch.int32)
+            logits = self.joint(encoder_out, predictor_out)
+            return rnnt_tdt_forced_align(logits, rnnt_text, encoder_out_lens.to(torch.int32), text_lengths.to(torch.int32),
+                                         self.tdt_durations, blank=self.blank, sigma=self.tdt_sigma,
+                                         return_blank_jumps=return_blank_jumps)
 
     def _calc_att_loss(self, encoder_out, encoder_mask, ys_pad, ys_pad_lens):
         """asr_model.py:115-148 (attention decoder is whatever module the caller attached)."""
