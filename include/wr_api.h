@@ -939,6 +939,56 @@ int wr_rnnt_tdt_export_lattice(const void *workspace_d, size_t workspace_bytes, 
                                float *alpha_d /* [B,Tmax,U1max] out */, float *beta_d /* [B,Tmax,U1max] out */,
                                void *stream);
 
+/* Joiner + TDT loss without a logits tensor (the memory-bounded TDT node, fused.py `joint_rnnt_tdt_loss`).  This text is
+ * the contract; the loss, its arcs, sigma and the gradient are those of "Token-and-duration transducer" above.
+ *
+ * The joiner (ep, pp, w_out, b_out, activation, J: as wr_joint_fwd) has W = V + D output rows: w_out [W, J], b_out [W];
+ * columns [0, V) of its logits are token logits, [V, W) duration logits.  Exact fp32 only, and only the default forward
+ * kernel: under wr_tune_set(5, 1) these entry points return WR_EUNSUPPORTED.  `workspace_d` as wr_joint_workspace_bytes
+ * (J, W); `tdt_workspace_d` as wr_rnnt_tdt_workspace_bytes(B, T, U1, D).
+ *
+ * wr_joint_tdt_stats: the joiner forward with the row statistics of wr_rnnt_tdt_loss_fwd as its only output.  Per cell
+ * t < T_b, u <= U_b it writes the token log-sum-exp, {tok_blank, tok_label} (tok_label = -inf at u = U_b or for a label
+ * outside [0, V)) and the D duration log-probabilities into the TDT workspace; no logit is stored.  The token sum follows
+ * wr_joint_rnnt_stats: a row that spreads over more than 88 nats raises a flag in the workspace, and a second launch with a
+ * running maximum, whose workgroups leave at once unless the flag is set, repairs it.  The duration log-sum-exp takes a
+ * true maximum.  Then wr_rnnt_tdt_sweeps.
+ *
+ * wr_rnnt_tdt_sweeps: both sweeps and the gradient's per-cell records over statistics that are already in the workspace
+ * (the part of wr_rnnt_tdt_loss_fwd behind its row pass); costs [B] as wr_rnnt_tdt_loss_fwd.
+ *
+ * wr_joint_tdt_grad: grad_costs[b] * d cost_b / d logits of the cells [cell_begin, cell_end) of the flattened (B, T, U1)
+ * lattice into g_out [(cell_end - cell_begin), W], fp32.  Every 64-cell logits tile is recomputed by the same forward
+ * kernel (bit-identical to the logits the statistics came from) and turned into the gradient in its epilogue with the
+ * formula of wr_rnnt_tdt_loss_bwd: no clamp, no FastEmit, no dead-row skip; both subtractions when the label is the blank.
+ * Rows outside [0,T_b) x [0,U_b] are 0.  Needs the TDT workspace after wr_joint_tdt_stats + wr_rnnt_tdt_sweeps and only
+ * reads it.  w_ready as in wr_joint_rnnt_grad.
+ *
+ * Refused before any launch, under the entry point's name: the durations contract with the codes and texts of
+ * wr_rnnt_tdt_loss_fwd; V = W - D < 2; blank outside [0, V); negative or non-finite sigma; null pointers (grad_costs and,
+ * with U1 == 1, targets may be null) (WR_EINVAL); U1 > 1024 or B * (T + U1 - 1) * U1 >= 2^31 (WR_EUNSUPPORTED); either
+ * workspace below its size (WR_EWORKSPACE); cell_begin / cell_end outside [0, B * T * U1] or cell_begin >= cell_end
+ * (WR_EINVAL); what the joiner refuses (join_dim, activation). */
+int wr_joint_tdt_stats(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
+                       const int32_t *logit_lengths_d, const int32_t *target_lengths_d, const int32_t *targets_d,
+                       int B, int T, int U1, int J, int W, int activation, int blank,
+                       const int32_t *durations /* [D], host */, int D, double sigma,
+                       void *workspace_d, size_t workspace_bytes,
+                       void *tdt_workspace_d, size_t tdt_workspace_bytes, void *stream);
+
+int wr_rnnt_tdt_sweeps(const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax, int U1max,
+                       const int32_t *durations /* [D], host */, int D, float *costs_d /* [B] out */,
+                       void *workspace_d, size_t workspace_bytes, void *stream);
+
+int wr_joint_tdt_grad(const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
+                      const int32_t *logit_lengths_d, const int32_t *target_lengths_d, const int32_t *targets_d,
+                      int B, int T, int U1, int J, int W, int activation, int blank,
+                      const int32_t *durations /* [D], host */, int D, double sigma,
+                      const float *grad_costs_d /* [B] or NULL */,
+                      const void *tdt_workspace_d, size_t tdt_workspace_bytes,
+                      long long cell_begin, long long cell_end, float *g_out_d /* [cell_end - cell_begin, W] */,
+                      void *workspace_d, size_t workspace_bytes, int w_ready, void *stream);
+
 /* TDT forced alignment: the single best path through the lattice above.  This text is the contract.  Inputs, arc weights
  * tok_k and dur_n, sigma, the duration rules and the terminal are exactly those of "Token-and-duration transducer".
  *

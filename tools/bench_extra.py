@@ -916,6 +916,69 @@ def bench_tdt(args):
     print(json.dumps(rec), flush=True)
 
 
+def bench_tdtstep(args):
+    """The TDT loss block of Transducer.forward through the autograd path, two ways in one run: the materialised pair
+    (joiner logits (B, T, U+1, V + D) -> rnnt_tdt_loss(inplace_grad=True), what a TDT model runs without a budget) and
+    the memory-bounded node joint_rnnt_tdt_loss(logits_budget=--budget-mb, default 1 GiB).  Forward + backward to enc /
+    pred and all joiner weights, exact fp32 joiner, J = 512, durations 0 .. D-1, full lengths; alternating, HIP events,
+    median of --steps rounds after one warm-up, and the growth of max_memory_allocated over one step of each."""
+    import wenet_celoss_amd as w
+    dev = torch.device("cuda:0")
+    torch.manual_seed(3)
+    B, T, U, V, D, E, P, J = args.B, args.T, args.U, args.V, args.durations, 256, 256, 512
+    durations = tuple(range(D))
+    budget = int((args.budget_mb or 1024.0) * (1 << 20))
+    enc = torch.randn(B, T, E, device=dev, requires_grad=True)
+    pred = torch.randn(B, U + 1, P, device=dev, requires_grad=True)
+    y = torch.randint(1, V, (B, U), dtype=torch.int32, device=dev)
+    ll = torch.full((B,), T, dtype=torch.int32, device=dev); tl = torch.full((B,), U, dtype=torch.int32, device=dev)
+    joint = w.TransducerJoint(V + D, E, P, J, precision="fp32").to(dev)
+    torch.manual_seed(4)
+    with torch.no_grad():
+        for prm in joint.parameters():
+            prm.copy_(torch.randn_like(prm) * 0.05)
+    last = {}
+
+    def step(bounded):
+        joint.zero_grad(set_to_none=True); enc.grad = None; pred.grad = None
+        if bounded:
+            loss = w.joint_rnnt_tdt_loss(joint.enc_ffn(enc), joint.pred_ffn(pred), joint.ffn_out.weight, joint.ffn_out.bias,
+                                         y, ll, tl, durations, blank=0, reduction="mean", logits_budget=budget)
+        else:
+            loss = w.rnnt_tdt_loss(joint(enc, pred), y, ll, tl, durations, blank=0, reduction="mean", inplace_grad=True)
+        loss.backward()
+        last["loss"] = loss.detach()
+
+    fns = {"materialised": lambda: step(False), "bounded": lambda: step(True)}
+    if args.only:
+        fns = {k: f for k, f in fns.items() if k in args.only.split(",")}
+    rec = {"what": "joint+rnnt_tdt_loss fwd+bwd (autograd): materialised logits vs memory-bounded node",
+           "shape": [B, T, U + 1, J, V + D], "durations": list(durations), "budget_mb": budget / (1 << 20), "reps": args.steps,
+           "logits_gb": round(B * T * (U + 1) * (V + D) * 4 / 1e9, 2)}
+    grads = {}
+    for k, fn in fns.items():                          # one step of each alone: loss, gradients, peak memory
+        joint.zero_grad(set_to_none=True); enc.grad = None; pred.grad = None
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        rec[k + "_peak_gb"] = round((torch.cuda.max_memory_allocated() - base) / 1e9, 3)
+        rec[k + "_loss"] = float(last["loss"])
+        grads[k] = (enc.grad.clone(), joint.ffn_out.weight.grad.clone())
+    if len(grads) == 2:
+        for name, i in (("grad_enc", 0), ("grad_w", 1)):
+            got, ref = grads["bounded"][i], grads["materialised"][i]
+            rec[name + "_max_err_over_max"] = float((got - ref).abs().max() / ref.abs().max())
+    del grads
+    for k, (med, lo, hi) in alternating(fns, args.steps).items():
+        rec[k + "_ms"] = round(med, 2)
+        rec[k + "_ms_min_max"] = [round(lo, 2), round(hi, 2)]
+    if len(fns) == 2:
+        rec["bounded_over_materialised"] = round(rec["bounded_ms"] / rec["materialised_ms"], 3)
+    print(json.dumps(rec), flush=True)
+
+
 def bench_tdtalign(args):
     """TDT forced alignment at the `tdt` sweep's shape (fp32 N(0,1) logits (B, T, U+1, V + D), full lengths, durations
     0 .. D-1): rnnt_tdt_forced_align (Python entry: label check, pass 1, Viterbi + backtrace), wr_rnnt_tdt_align alone and
@@ -1097,11 +1160,11 @@ def bench_tdtdec(args):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align", "simple", "smoothed", "pruned", "tdt",
-                                     "tdtalign", "tdtdec"])
-    ap.add_argument("--durations", type=int, default=5, help="tdt, tdtalign: number of durations D (the set is 0 .. D-1)")
+                                     "tdtstep", "tdtalign", "tdtdec"])
+    ap.add_argument("--durations", type=int, default=5, help="tdt, tdtstep, tdtalign: number of durations D (the set is 0 .. D-1)")
     ap.add_argument("--n-steps", type=int, default=64)
     ap.add_argument("--chunks", type=int, default=4)
-    ap.add_argument("--B", type=int, default=None, help="batch size (default 32; simple, smoothed, pruned, tdt, tdtalign: 16)")
+    ap.add_argument("--B", type=int, default=None, help="batch size (default 32; simple, smoothed, pruned, tdt, tdtstep, tdtalign: 16)")
     ap.add_argument("--T", type=int, default=1000)
     ap.add_argument("--U", type=int, default=150)
     ap.add_argument("--V", type=int, default=5000)
@@ -1129,10 +1192,10 @@ if __name__ == "__main__":
     ap.add_argument("--tile", type=int, default=0, help="lane-GEMM tile policy of the decoders (wr_tune_set key 6)")
     a = ap.parse_args()
     if a.B is None:
-        a.B = 16 if a.what in ("simple", "smoothed", "pruned", "tdt", "tdtalign") else 32
+        a.B = 16 if a.what in ("simple", "smoothed", "pruned", "tdt", "tdtstep", "tdtalign") else 32
     if a.tile:
         from wenet_celoss_amd import _lib
         _lib.load().wr_tune_set(6, a.tile)
     {"joint": bench_joint, "ctc": bench_ctc, "greedy": bench_greedy, "beam": bench_beam, "step": bench_step, "ctcdec": bench_ctcdec, "hotword": bench_hotword,
      "align": bench_align, "simple": bench_simple, "smoothed": bench_smoothed, "pruned": bench_pruned,
-     "tdt": bench_tdt, "tdtalign": bench_tdtalign, "tdtdec": bench_tdtdec}[a.what](a)
+     "tdt": bench_tdt, "tdtstep": bench_tdtstep, "tdtalign": bench_tdtalign, "tdtdec": bench_tdtdec}[a.what](a)

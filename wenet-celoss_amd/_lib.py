@@ -138,6 +138,11 @@ SIGNATURES = {
     "wr_rnnt_tdt_loss_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _d, _vp, _vp, _vp, _sz, _vp]),
     "wr_rnnt_tdt_export_lattice": (_i, [_vp, _sz, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "wr_rnnt_tdt_align": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wr_joint_tdt_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _d, _vp, _sz, _vp, _sz,
+                                _vp]),
+    "wr_rnnt_tdt_sweeps": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "wr_joint_tdt_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _d, _vp, _vp, _sz,
+                               ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _sz, _i, _vp]),
     "wr_ctc_workspace_bytes": (_sz, [_i, _i, _i]),
     "wr_ctc_loss_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "wr_ctc_loss_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

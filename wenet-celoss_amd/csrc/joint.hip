@@ -25,6 +25,7 @@
 //   d ep = sum_u dZ and d pp = sum_t dZ are library reductions on the host side.
 #include "wr_common.hpp"
 #include "joint_lse.hpp"
+#include "rnnt_tdt.hpp"
 #include "wr_launch.hpp"
 
 namespace wr {
@@ -36,6 +37,7 @@ constexpr int kBM = 64;        // lattice cells per workgroup
 constexpr int kBN = 256;       // output columns per chunk (4 waves x 64)
 constexpr int kBK = 8;         // k-slice depth of the streamed operand (forward)
 constexpr int kHPad = kBM + 1; // k-major activation tile row stride (floats)
+static_assert(kJointTdtMaxD == kTdtMaxD, "the TDT row block of the epilogue holds one value per duration");
 
 inline int joint_vpad(int V) { return (V + 2 * kBN - 1) / (2 * kBN) * (2 * kBN); }   // whole 512-column chunks (8 waves x 2 tiles)
 inline int joint_jpad(int J) { return (J + 31) / 32 * 32; }   // forward k-depth, zero padded (multiple of 2*PFK)
@@ -232,17 +234,20 @@ __global__ void joint_frag_w_kernel(const float *__restrict__ w, int V, int J, i
     }
 }
 
-template <int EPI /* JointEpi */, int CT, typename... Reg /* kEpiGradReg: RnntReg */>
+template <int EPI /* JointEpi */, int CT, typename... Reg /* kEpiGradReg: RnntReg; the TDT modes: JointTdt */>
 __global__ __launch_bounds__(512) void joint_fwd_frag_kernel(
     const float *__restrict__ ep, const float *__restrict__ pp, const float4 *__restrict__ wf, const float *__restrict__ bias,
     const int32_t *__restrict__ llens, const int32_t *__restrict__ tlens, int B, int T, int U1, int J, int Jp, int V, int Vp,
     int act, float *__restrict__ out, JointLse lse, Reg... reg_args)
 {
-    constexpr bool LSE = EPI == kEpiStoreLse || EPI == kEpiStats, STORE = EPI <= kEpiStoreLse, GRAD = joint_epi_is_grad(EPI);
+    constexpr bool TDT = joint_epi_is_tdt(EPI);
+    constexpr bool LSE = EPI == kEpiStoreLse || EPI == kEpiStats || EPI == kEpiTdtStats, STORE = EPI <= kEpiStoreLse;
+    constexpr bool GRAD = joint_epi_is_grad(EPI) || EPI == kEpiTdtGrad;     // the launch covers cells [m_begin, m_end)
+    static_assert(TDT ? sizeof...(Reg) == 1 : sizeof...(Reg) == (EPI == kEpiGradReg ? 1 : 0), "one trailing argument per mode");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int AS = Jp + 4;                            // row stride of the activation tile (floats)
     float *Ht = lds;                                  // [64][AS]
-    if (EPI == kEpiStats && lse.run_if != nullptr && *lse.run_if == 0) return;
+    if ((EPI == kEpiStats || EPI == kEpiTdtStats) && lse.run_if != nullptr && *lse.run_if == 0) return;
     const long M = GRAD ? lse.m_end : (long)B * T * U1;
     const long mb = GRAD ? lse.m_begin : 0;           // first cell of the launch (out row 0)
     const long m0 = mb + (long)blockIdx.x * kBM;
@@ -268,10 +273,19 @@ __global__ __launch_bounds__(512) void joint_fwd_frag_kernel(
         }
     }
     EpiRows er{};
+    float *xd = nullptr;                              // TDT: the row block behind `er`
+    int vtok = V;                                     // columns that enter the row log-sum-exp (TDT: the token columns)
     if (!STORE) {
         const size_t tile = (size_t)kBM * AS * sizeof(float);
-        er = joint_epi_rows(reinterpret_cast<char *>(lds) + (tile > joint_lse_exchange_bytes(8) ? tile : joint_lse_exchange_bytes(8)));
-        joint_epi_rows_init<EPI>(lse, er, llens, tlens, m0, M, T, U1, reg_args...);
+        char *rows = reinterpret_cast<char *>(lds) + (tile > joint_lse_exchange_bytes(8) ? tile : joint_lse_exchange_bytes(8));
+        er = joint_epi_rows(rows);
+        if constexpr (TDT) {
+            xd = reinterpret_cast<float *>(rows + joint_epi_rows_bytes());
+            vtok = only_arg(reg_args...).V;
+            joint_epi_tdt_rows_init<EPI>(lse, only_arg(reg_args...), er, xd, llens, tlens, m0, M, T, U1);
+        } else {
+            joint_epi_rows_init<EPI>(lse, er, llens, tlens, m0, M, T, U1, reg_args...);
+        }
     }
     // activation tile: Ht[row][k & 1][k >> 1]
     for (int row = wave; row < kBM; row += 8) {
@@ -352,14 +366,22 @@ __global__ __launch_bounds__(512) void joint_fwd_frag_kernel(
                     const long m = m0 + row;
                     const float x = acc[rt][c][r] + bv;
                     if (STORE && m < M && col < V) out[(size_t)m * V + col] = x;
-                    if (LSE) joint_lse_add_mode<EPI>(lse, rm[rt * 16 + r], rs[rt * 16 + r], x, col < V, nc == 0 && c == 0);
+                    if (LSE) joint_lse_add_mode<EPI>(lse, rm[rt * 16 + r], rs[rt * 16 + r], x, col < vtok, nc == 0 && c == 0);
                     if (EPI == kEpiStats) joint_epi_park(er, lse.blank, row, col, x);
-                    if (GRAD && m < M && col < V) out[(size_t)(m - mb) * V + col] = joint_epi_grad(er, lse.clamp, row, col, x);
+                    if (joint_epi_is_grad(EPI) && m < M && col < V)
+                        out[(size_t)(m - mb) * V + col] = joint_epi_grad(er, lse.clamp, row, col, x);
+                    if constexpr (EPI == kEpiTdtStats) joint_epi_tdt_park(er, xd, lse.blank, only_arg(reg_args...), row, col, x);
+                    if constexpr (EPI == kEpiTdtGrad)
+                        if (m < M && col < V)
+                            out[(size_t)(m - mb) * V + col] = joint_epi_tdt_grad(er, xd, lse.blank, vtok, row, col, x);
                 }
         }
     }
 #undef WR_LOADF
-    if (LSE) {
+    if constexpr (EPI == kEpiTdtStats) {
+        __syncthreads();
+        joint_lse_finish<8>(lse, lds, rm, rs, llens, tlens, out, m0, M, T, U1, V, er.xb, er.xl, er.lab, xd, reg_args...);
+    } else if (LSE) {
         __syncthreads();
         joint_lse_finish<8>(lse, lds, rm, rs, llens, tlens, out, m0, M, T, U1, V, EPI == kEpiStats ? er.xb : nullptr,
                             EPI == kEpiStats ? er.xl : nullptr);
@@ -683,16 +705,32 @@ extern "C" size_t wr_joint_workspace_bytes(int J, int V)
 
 namespace {
 // the statistics-only (kEpiStats, one launch plus the repair launch) and gradient (kEpiGrad) modes of either exact
-// forward kernel; W is already re-laid in `wsw` (Wt for the direct kernel, fragments for the frag kernel)
+// forward kernel; W is already re-laid in `wsw` (Wt for the direct kernel, fragments for the frag kernel).  `tdt`: the TDT
+// modes (kEpiTdtStats / kEpiTdtGrad, frag kernel only; V is then the joiner's width).
 int joint_fwd_epi_launch(bool frag, int epi, const float *ep_d, const float *pp_d, const void *wsw, const float *b_out_d,
                          const int32_t *llens, const int32_t *tlens, int B, int T, int U1, int J, int Jp, int V, int Vp,
-                         int act, float *out_d, const JointLse &lse, hipStream_t st, const RnntReg *reg = nullptr)
+                         int act, float *out_d, const JointLse &lse, hipStream_t st, const RnntReg *reg = nullptr,
+                         const JointTdt *tdt = nullptr)
 {
-    const long cells = joint_epi_is_grad(epi) ? lse.m_end - lse.m_begin : (long)B * T * U1;
+    const long cells = joint_epi_is_grad(epi) || epi == kEpiTdtGrad ? lse.m_end - lse.m_begin : (long)B * T * U1;
     const dim3 grid((unsigned)((cells + kBM - 1) / kBM));
     const size_t tile = frag ? (size_t)kBM * (Jp + 4) * sizeof(float) : (size_t)Jp * kHPad * sizeof(float);
-    const size_t lds = (tile > joint_lse_exchange_bytes(8) ? tile : joint_lse_exchange_bytes(8)) + joint_epi_rows_bytes();
+    const size_t lds = (tile > joint_lse_exchange_bytes(8) ? tile : joint_lse_exchange_bytes(8)) + joint_epi_rows_bytes() +
+                       (tdt != nullptr ? joint_epi_tdt_rows_bytes() : 0);
     WR_REQUIRE(lds <= 160 * 1024, WR_EUNSUPPORTED, "joint_fwd: J=%d needs %zu bytes of LDS", J, lds);
+    if (tdt != nullptr) {
+        const auto run_tdt = [&](const char *name, auto epi_c, const JointLse &l) {
+            return launch_lds(name, joint_fwd_frag_kernel<epi_c.value, 1, JointTdt>, grid, dim3(512), lds, st, ep_d, pp_d,
+                              static_cast<const float4 *>(wsw), b_out_d, llens, tlens, B, T, U1, J, Jp, V, Vp, act, out_d, l, *tdt);
+        };
+        if (epi == kEpiTdtGrad) return run_tdt("joint_fwd (TDT gradient epilogue)", int_c<kEpiTdtGrad>{}, lse);
+        (void)hipMemsetAsync(lse.repair, 0, sizeof(int32_t), st);
+        WR_TRY(run_tdt("joint_fwd (TDT statistics epilogue)", int_c<kEpiTdtStats>{}, lse));
+        JointLse rep = lse;                            // the repair launch, as below
+        rep.run_if = lse.repair;
+        rep.online = 1;
+        return run_tdt("joint_fwd (TDT statistics epilogue, repair)", int_c<kEpiTdtStats>{}, rep);
+    }
     const auto run = [&](const char *name, auto epi_c, const JointLse &l) {
         if (frag)
             return launch_lds(name, joint_fwd_frag_kernel<epi_c.value, 1>, grid, dim3(512), lds, st, ep_d, pp_d,
@@ -866,6 +904,36 @@ int joint_rnnt_grad_body(const char *what, const float *ep_d, const float *pp_d,
                                    epi, lse, g_out_d, workspace_d, workspace_bytes, st, w_ready != 0, reg);
     return joint_fwd_launch(ep_d, pp_d, w_out_d, b_out_d, logit_lengths_d, target_lengths_d, B, T, U1, J, V, activation,
                             g_out_d, workspace_d, workspace_bytes, &lse, st, epi, w_ready != 0, reg);
+}
+}  // namespace wr
+
+namespace wr {
+// wr_joint_tdt_stats / wr_joint_tdt_grad (rnnt_tdt.cpp, which has checked the TDT side): the joiner's own refusals, W's
+// re-layout, and the default forward kernel with the TDT statistics / gradient epilogue over the TDT workspace `tws`
+int joint_tdt_epi(const char *what, bool grad, const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
+                  const int32_t *llens, const int32_t *tlens, const int32_t *targets_d, int B, int T, int U1, int J, int W,
+                  int act, int blank, int D, float sigma, const float *grad_costs_d, void *tws, long cell_begin, long cell_end,
+                  float *g_out_d, void *workspace_d, size_t workspace_bytes, bool w_ready, hipStream_t st)
+{
+    if (int rc = joint_check(B, T, U1, J, W, act)) return rc;
+    WR_REQUIRE(tune_get(kTuneJointFwdVariant) != 1, WR_EUNSUPPORTED,
+               "%s: the direct forward kernel (wr_tune_set(5, 1)) has no TDT epilogue, only the default forward carries it", what);
+    const int Vp = joint_vpad(W), Jp = joint_jpad(J);
+    const size_t need = (size_t)Jp * Vp * sizeof(float);
+    WR_REQUIRE(workspace_bytes >= need, WR_EWORKSPACE, "%s: workspace %zu < required %zu", what, workspace_bytes, need);
+    const TdtWs w = tdt_ws_layout(B, T, U1, D);
+    char *ws = static_cast<char *>(tws);
+    JointLse lse{targets_d, blank, w.S, reinterpret_cast<float2 *>(ws + w.tok_off), reinterpret_cast<float *>(ws + w.denom_off),
+                 reinterpret_cast<int32_t *>(ws + w.flag_off)};
+    lse.grad_costs = grad_costs_d;
+    lse.m_begin = cell_begin;
+    lse.m_end = cell_end;
+    const JointTdt td{W - D, D, sigma, reinterpret_cast<float *>(ws + w.dur_off), reinterpret_cast<const float *>(ws + w.rec_off)};
+    float4 *wf = static_cast<float4 *>(workspace_d);
+    if (!w_ready)
+        WR_TRY(launch("joint_frag_w_kernel", joint_frag_w_kernel, dim3(1024), dim3(256), 0, st, w_out_d, W, J, Jp, Vp, wf));
+    return joint_fwd_epi_launch(true, grad ? kEpiTdtGrad : kEpiTdtStats, ep_d, pp_d, wf, b_out_d, llens, tlens, B, T, U1, J, Jp,
+                                W, Vp, act, g_out_d, lse, st, nullptr, &td);
 }
 }  // namespace wr
 

@@ -38,8 +38,16 @@ namespace wr {
 //                 one more kernel argument (an RnntReg behind the others: the kernels end in a parameter pack that is
 //                 empty in every other mode, so those keep their arguments and their code); lp_skew then holds the
 //                 penalised label arcs.
-enum JointEpi : int { kEpiStore = 0, kEpiStoreLse = 1, kEpiStats = 2, kEpiGrad = 3, kEpiGradReg = 4 };
+//   kEpiTdtStats  kEpiStats for the token-and-duration loss (wr_joint_tdt_stats; frag kernel only): the row is V token and D
+//                 duration columns, the partial sums take the token columns alone, and the D duration logits are parked
+//                 beside the blank / label logit; what tdt_stats_kernel (rnnt_lattice.hip) writes goes into a TDT
+//                 workspace.  The TDT side is one more kernel argument (a JointTdt, where kEpiGradReg has its RnntReg).
+//   kEpiTdtGrad   kEpiGrad for that loss (wr_joint_tdt_grad): tdt_grad_kernel's per-element formula over the records of
+//                 tdt_record_kernel, no clamp.
+enum JointEpi : int { kEpiStore = 0, kEpiStoreLse = 1, kEpiStats = 2, kEpiGrad = 3, kEpiGradReg = 4, kEpiTdtStats = 5,
+                      kEpiTdtGrad = 6 };
 constexpr bool joint_epi_is_grad(int epi) { return epi == kEpiGrad || epi == kEpiGradReg; }
+constexpr bool joint_epi_is_tdt(int epi) { return epi == kEpiTdtStats || epi == kEpiTdtGrad; }
 
 struct JointLse {
     const int32_t *targets;   // [B, U1-1]
@@ -57,6 +65,17 @@ struct JointLse {
     float clamp = -1.f;
     long m_begin = 0, m_end = 0;
 };
+
+// The TDT side of kEpiTdtStats / kEpiTdtGrad.  The kernel's V is then the joiner's width V + D; the JointLse beside it
+// carries targets, blank, S, the repair protocol, grad_costs and the cell range, with lp_skew = the workspace's `tok` array
+// (the same anti-diagonal layout) and denom = its `denom`.
+struct JointTdt {
+    int V, D;                 // token columns [0, V), duration columns [V, V + D)
+    float sigma;
+    float *dur;               // [B, S, U1, D]   kEpiTdtStats writes it
+    const float *rec;         // [B, T, U1, 3 + D]   kEpiTdtGrad reads it
+};
+constexpr int kJointTdtMaxD = 9;              // = kTdtMaxD (rnnt_tdt.hpp)
 
 // The row-statistics block over an RNN-T workspace laid out by `w` (what the store and statistics modes need; the
 // gradient mode's fields are the caller's to add).
@@ -94,6 +113,8 @@ struct EpiRows {
     float *xb, *xl, *c2, *bsub, *lsub, *go;
 };
 __host__ __device__ inline size_t joint_epi_rows_bytes() { return (size_t)8 * kLseRows * sizeof(float); }
+// the TDT modes' row block behind it: xd[n][row], the parked duration logit n (statistics) or rec[3 + n] (gradient)
+__host__ __device__ inline size_t joint_epi_tdt_rows_bytes() { return (size_t)kJointTdtMaxD * kLseRows * sizeof(float); }
 
 __device__ __forceinline__ EpiRows joint_epi_rows(void *base)
 {
@@ -116,6 +137,7 @@ __device__ __forceinline__ void joint_epi_rows_init(const JointLse &a, const Epi
                                                     const int32_t *tlens, long m0, long M, int T, int U1,
                                                     const Reg &...reg_args)
 {
+    static_assert(!joint_epi_is_tdt(EPI), "the TDT modes fill their rows with joint_epi_tdt_rows_init");
     static_assert((EPI == kEpiGradReg) == (sizeof...(Reg) == 1), "kEpiGradReg takes the regularisers, no other mode does");
     const int row = threadIdx.x;
     if (row >= kLseRows) return;
@@ -186,6 +208,65 @@ __device__ __forceinline__ void joint_epi_rows_init(const JointLse &a, const Epi
     er.go[row] = a.grad_costs ? a.grad_costs[b] : 1.f;
 }
 
+// The same for the TDT modes.  Statistics: lab = the row's label column (-1: none, or outside the token columns).
+// Gradient (tdt_grad_kernel's names): c2 = rec[0] log2e, bsub / lsub = rec[1] / rec[2] (what the blank / label column
+// subtracts), xd[n][row] = rec[3 + n], go = grad_costs[b]; a padded row has c2 = -inf and zeros.
+template <int EPI>
+__device__ __forceinline__ void joint_epi_tdt_rows_init(const JointLse &a, const JointTdt &td, const EpiRows &er, float *xd,
+                                                        const int32_t *llens, const int32_t *tlens, long m0, long M, int T,
+                                                        int U1)
+{
+    static_assert(joint_epi_is_tdt(EPI), "TDT modes only");
+    const int row = threadIdx.x;
+    if (row >= kLseRows) return;
+    const long m = m0 + row;
+    int b = 0, t = 0, u = 0, T_ = 0, U = -1;
+    if (m < M) {
+        const long bt = m / U1;
+        u = (int)(m - bt * U1);
+        b = (int)(bt / T);
+        t = (int)(bt - (long)b * T);
+        T_ = llens[b];
+        U = tlens[b];
+    }
+    const bool valid = m < M && t < T_ && u <= U;
+    int lab = (valid && u < U) ? a.targets[(size_t)b * (U1 - 1) + u] : -1;
+    if (lab >= td.V) lab = -1;
+    er.lab[row] = lab;
+    if (EPI == kEpiTdtStats) {
+        er.xb[row] = 0.f;
+        er.xl[row] = 0.f;
+        return;
+    }
+    const float *rc = td.rec + (size_t)m * (3 + td.D);
+    er.c2[row] = valid ? rc[0] * kLog2e : kNegInf;
+    er.bsub[row] = valid ? rc[1] : 0.f;
+    er.lsub[row] = valid ? rc[2] : 0.f;
+    er.go[row] = !valid ? 0.f : (a.grad_costs ? a.grad_costs[b] : 1.f);
+    for (int n = 0; n < td.D; ++n) xd[n * kLseRows + row] = valid ? rc[3 + n] : 0.f;
+}
+
+// kEpiTdtStats: joint_epi_park, and the duration logit of column `col` in [V, V + D)
+__device__ __forceinline__ void joint_epi_tdt_park(const EpiRows &er, float *xd, int blank, const JointTdt &td, int row,
+                                                   int col, float x)
+{
+    if (col == blank) er.xb[row] = x;
+    if (col == er.lab[row]) er.xl[row] = x;
+    if (col >= td.V && col < td.V + td.D) xd[(col - td.V) * kLseRows + row] = x;
+}
+
+// kEpiTdtGrad: the gradient of logit x of `row`, column `col` < V + D (tdt_grad_kernel's fix: both subtractions apply when
+// the label is the blank; a duration column takes its record value and the logit is not used)
+__device__ __forceinline__ float joint_epi_tdt_grad(const EpiRows &er, const float *xd, int blank, int vtok, int row, int col,
+                                                    float x)
+{
+    float val = fast_exp2(fmaf(x, kLog2e, er.c2[row]));
+    if (col == blank) val -= er.bsub[row];
+    if (col == er.lab[row]) val -= er.lsub[row];
+    if (col >= vtok) val = xd[(col - vtok) * kLseRows + row];
+    return val * er.go[row];
+}
+
 // kEpiStats: park the blank / label logit of `row` if this lane holds its column
 __device__ __forceinline__ void joint_epi_park(const EpiRows &er, int blank, int row, int col, float x)
 {
@@ -248,8 +329,37 @@ __device__ __forceinline__ void joint_lse_add_online(float &ref, float &s, float
 template <int EPI>
 __device__ __forceinline__ void joint_lse_add_mode(const JointLse &a, float &ref, float &s, float x, bool in, bool first)
 {
-    if (EPI == kEpiStats && a.online) joint_lse_add_online(ref, s, x, in, first);
+    if ((EPI == kEpiStats || EPI == kEpiTdtStats) && a.online) joint_lse_add_online(ref, s, x, in, first);
     else joint_lse_add(ref, s, x, in, first);
+}
+
+// kEpiTdtStats: what tdt_stats_kernel writes for cell m (row `row` of the tile), called by a whole wave with the row's
+// token log-sum-exp `d`.  The duration log-sum-exp is that kernel's, one parked logit per lane with a true maximum.
+__device__ __forceinline__ void joint_tdt_write_row(const JointLse &a, const JointTdt &td, const int *parked_lab,
+                                                    const float *parked_xb, const float *parked_xl, const float *parked_xd,
+                                                    const int32_t *llens, const int32_t *tlens, int row, long m, long M, int T,
+                                                    int U1, float d)
+{
+    const int lane = threadIdx.x & 63;
+    const int D = td.D;
+    float x = kNegInf;
+    if (lane < D) x = parked_xd[lane * kLseRows + row];
+    const float y = x * kLog2e;
+    const float mx = wave_max(y);
+    const float sd = wave_sum(lane < D ? fast_exp2(y - mx) : 0.f);
+    const float dd = (mx + fast_log2(sd)) * kLn2;
+    if (m >= M) return;
+    const long bt = m / U1;
+    const int u = (int)(m - bt * U1);
+    const int b = (int)(bt / T), t = (int)(bt - (long)b * T);
+    if (t >= llens[b] || u > tlens[b]) return;                // same rows as tdt_stats_kernel writes
+    const size_t k = ((size_t)b * a.S + (t + u)) * U1 + u;
+    if (lane < D) td.dur[k * D + lane] = x - dd;
+    if (lane == 0) {
+        const float em = parked_lab[row] >= 0 ? (parked_xl[row] - d) - td.sigma : kNegInf;
+        a.denom[m] = d;
+        a.lp_skew[k] = make_float2((parked_xb[row] - d) - td.sigma, em);
+    }
 }
 
 // Merge and write.  ref/s: this lane's statistics, index rt * 16 + r <-> row 32 rt + (r&3) + 8 (r>>2) + 4 half.
@@ -257,11 +367,14 @@ __device__ __forceinline__ void joint_lse_add_mode(const JointLse &a, float &ref
 // lived there (the caller synchronises before the call); `out` = the logits this workgroup has stored, or null with
 // `parked_xb` / `parked_xl` = the blank / label logits parked in LDS (kEpiStats; EpiRows::xb / xl, passed by value so that
 // they stay LDS addresses).
-template <int WAVES>
+// kEpiTdtStats (`tdt_args` = the JointTdt, with `parked_lab` / `parked_xd` = EpiRows::lab and the TDT row block): a merged
+// row goes to joint_tdt_write_row instead.
+template <int WAVES, typename... Tdt>
 __device__ __forceinline__ void joint_lse_finish(const JointLse &a, float *xch, const float (&ref)[32], const float (&s)[32],
                                                  const int32_t *llens, const int32_t *tlens, const float *out, long m0,
                                                  long M, int T, int U1, int V, const float *parked_xb = nullptr,
-                                                 const float *parked_xl = nullptr)
+                                                 const float *parked_xl = nullptr, const int *parked_lab = nullptr,
+                                                 const float *parked_xd = nullptr, const Tdt &...tdt_args)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
@@ -297,7 +410,10 @@ __device__ __forceinline__ void joint_lse_finish(const JointLse &a, float *xch, 
         for (int j = 0; j < EPL; ++j) sum += fast_exp2(e[j] - mx);
         sum = wave_sum(sum);
         const long m = m0 + row;
-        if (lane == 0 && m < M) {
+        if constexpr (sizeof...(Tdt) == 1) {
+            joint_tdt_write_row(a, only_arg(tdt_args...), parked_lab, parked_xb, parked_xl, parked_xd, llens, tlens, row, m, M, T,
+                                U1, (mx + fast_log2(sum)) * kLn2);
+        } else if (lane == 0 && m < M) {
             const long bt = m / U1;
             const int u = (int)(m - bt * U1);
             const int b = (int)(bt / T), t = (int)(bt - (long)b * T);

@@ -875,8 +875,16 @@ int tdt_loss_fwd_body(const void *logits_d, int dtype, const int32_t *targets_d,
                       const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V, int blank, const TdtDur &dur,
                       double sigma, float *costs_d, void *workspace_d, hipStream_t st)
 {
-    const int D = dur.D;
-    const TdtWs w = tdt_ws_layout(B, Tmax, U1max, D);
+    const TdtWs w = tdt_ws_layout(B, Tmax, U1max, dur.D);
+    WR_TRY(tdt_launch_stats(w, static_cast<char *>(workspace_d), logits_d, dtype, targets_d, logit_lengths_d, target_lengths_d,
+                            B, Tmax, U1max, V, dur.D, blank, sigma, st));
+    return tdt_sweeps_body(logit_lengths_d, target_lengths_d, B, Tmax, U1max, dur, costs_d, workspace_d, st);
+}
+
+int tdt_sweeps_body(const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax, int U1max,
+                    const TdtDur &dur, float *costs_d, void *workspace_d, hipStream_t st)
+{
+    const TdtWs w = tdt_ws_layout(B, Tmax, U1max, dur.D);
     char *ws = static_cast<char *>(workspace_d);
     float2 *tok = reinterpret_cast<float2 *>(ws + w.tok_off);
     float *durp = reinterpret_cast<float *>(ws + w.dur_off);
@@ -884,8 +892,6 @@ int tdt_loss_fwd_body(const void *logits_d, int dtype, const int32_t *targets_d,
     double *alpha = reinterpret_cast<double *>(ws + w.alpha_off), *beta = reinterpret_cast<double *>(ws + w.beta_off);
     double *cost = reinterpret_cast<double *>(ws + w.cost_off);
     const long nrows = (long)B * Tmax * U1max;
-    WR_TRY(tdt_launch_stats(w, ws, logits_d, dtype, targets_d, logit_lengths_d, target_lengths_d, B, Tmax, U1max, V, D,
-                            blank, sigma, st));
     WR_TRY(launch("tdt_sweep_kernel", tdt_sweep_kernel<4>, dim3(B, 2), dim3(64 * w.K), 0, st, tok, durp, logit_lengths_d,
                   target_lengths_d, Tmax, U1max, w.S, dur, alpha, beta, reinterpret_cast<double *>(ws + w.ll_off), cost,
                   costs_d, reinterpret_cast<double *>(ws + w.dump_off)));

@@ -10,6 +10,8 @@
 //   denom   float                           plain            log-sum-exp of the token columns
 //   rec     float[3 + D]                    plain            the gradient's row constants (tdt_record_kernel)
 //   ll, cost  double[B];  dump  double[B][2][kRnntMaxCols]   (absorbs the stores of idle sweep lanes)
+//   flag    int32                                            a partial sum of the joiner's statistics epilogue overflowed
+//                                                            (wr_joint_tdt_stats; joint_lse.hpp has the protocol)
 #pragma once
 
 #include "wr_common.hpp"
@@ -51,7 +53,7 @@ inline int tdt_durations(const char *what, const int32_t *durations, int D, TdtD
 struct TdtWs {
     int K;            // waves of a sweep workgroup
     int S;            // anti-diagonals per utterance
-    size_t tok_off, dur_off, alpha_off, beta_off, denom_off, rec_off, ll_off, cost_off, dump_off, total;
+    size_t tok_off, dur_off, alpha_off, beta_off, denom_off, rec_off, ll_off, cost_off, dump_off, flag_off, total;
 };
 
 inline TdtWs tdt_ws_layout(int B, int Tmax, int U1max, int D)
@@ -71,6 +73,7 @@ inline TdtWs tdt_ws_layout(int B, int Tmax, int U1max, int D)
     w.ll_off = off;    off = align_up(off + (size_t)B * sizeof(double), 256);
     w.cost_off = off;  off = align_up(off + (size_t)B * sizeof(double), 256);
     w.dump_off = off;  off = align_up(off + (size_t)B * 2 * kRnntMaxCols * sizeof(double), 256);
+    w.flag_off = off;  off = align_up(off + sizeof(int32_t), 256);
     w.total = off;
     return w;
 }
@@ -80,6 +83,10 @@ inline TdtWs tdt_ws_layout(int B, int Tmax, int U1max, int D)
 int tdt_loss_fwd_body(const void *logits_d, int dtype, const int32_t *targets_d, const int32_t *logit_lengths_d,
                       const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V, int blank, const TdtDur &dur,
                       double sigma, float *costs_d, void *workspace_d, hipStream_t st);
+// Both sweeps and the per-cell records over a workspace whose row statistics (tok, dur, denom) are in place: the tail of
+// tdt_loss_fwd_body, and all of wr_rnnt_tdt_sweeps.
+int tdt_sweeps_body(const int32_t *logit_lengths_d, const int32_t *target_lengths_d, int B, int Tmax, int U1max,
+                    const TdtDur &dur, float *costs_d, void *workspace_d, hipStream_t st);
 int tdt_loss_bwd_body(const void *logits_d, int dtype, const int32_t *targets_d, const int32_t *logit_lengths_d,
                       const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V, int blank, int D,
                       const float *grad_costs_d, void *grads_d, const void *workspace_d, hipStream_t st);
@@ -90,5 +97,13 @@ int tdt_align_body(const void *logits_d, int dtype, const int32_t *targets_d, co
                    const int32_t *target_lengths_d, int B, int Tmax, int U1max, int V, int blank, const TdtDur &dur,
                    double sigma, int32_t *label_frames_d, int32_t *label_durations_d, int32_t *blank_jumps_d,
                    double *scores_d, void *workspace_d, hipStream_t st);
+
+// joint.hip: the joiner forward with the TDT statistics (grad = false) or gradient (cells [cell_begin, cell_end) into
+// g_out_d) epilogue over the TDT workspace `tws`, for wr_joint_tdt_stats / wr_joint_tdt_grad.  Refuses what the joiner
+// refuses (join_dim, activation, its workspace, the direct forward kernel) before any launch.
+int joint_tdt_epi(const char *what, bool grad, const float *ep_d, const float *pp_d, const float *w_out_d, const float *b_out_d,
+                  const int32_t *llens, const int32_t *tlens, const int32_t *targets_d, int B, int T, int U1, int J, int W,
+                  int act, int blank, int D, float sigma, const float *grad_costs_d, void *tws, long cell_begin, long cell_end,
+                  float *g_out_d, void *workspace_d, size_t workspace_bytes, bool w_ready, hipStream_t st);
 
 }  // namespace wr

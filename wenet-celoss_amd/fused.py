@@ -21,12 +21,13 @@ statistics (`wr_joint_rnnt_stats`: the joiner forward with a statistics-only epi
 (`wr_rnnt_loss_sweeps`); the backward walks the lattice in slices (`plan_slices`) and, per slice, recomputes the logits
 tile by tile and turns them into the loss gradient in the same kernel's epilogue (`wr_joint_rnnt_grad`), then runs the
 joiner backward on that slice.  One extra joiner forward's matrix work buys a footprint that does not grow with the batch
-(DESIGN.md, "The memory-bounded loss block").
+("The memory-bounded loss block").  `joint_rnnt_tdt_loss` / `_JointTdtBoundedFn` is the same node for the
+token-and-duration loss ("The memory-bounded TDT loss block").
 """
 from __future__ import annotations
 
 import os
-from typing import List, NamedTuple, Optional
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -34,6 +35,7 @@ import torch
 from . import _lib
 from .joint import _PRECISIONS, _call_precision, activation_code, joiner_workspace, joint_backward, joint_forward
 from .rnnt_loss import check_latency
+from .rnnt_tdt import _check_blank, _durations_arg, check_tdt
 
 
 class _JointRnntFn(torch.autograd.Function):
@@ -184,17 +186,8 @@ class _JointRnntBoundedFn(torch.autograd.Function):
             _lib.call("wr_rnnt_loss_sweeps", llens, tlens, B, T, U1, costs, rws, rws.numel(), device=dev)
         else:
             _lib.call("wr_rnnt_lattice_sweeps", llens, tlens, B, T, U1, 0, pen, costs, rws, rws.numel(), device=dev)
-        # per-slice length arrays, built once on the host from the caller's length sync: [ll of every slice | tl ...]
-        ll_s, tl_s = [], []
-        for s in slices:
-            for u in range(s.b0, s.b1):
-                ll_s.append(min(host_t[u], s.t1) - s.t0)
-                tl_s.append(host_u[u])
-        lens = torch.tensor(ll_s + tl_s, dtype=torch.int32)
-        with torch.cuda.device(dev):
-            lens = lens.pin_memory().to(dev, non_blocking=True) if lens.numel() else lens.to(dev)
         ctx.save_for_backward(ep, pp, w, b, targets, llens, tlens, rws)
-        ctx.slice_lens = lens
+        ctx.slice_lens = _slice_lengths(slices, host_t, host_u, dev)
         ctx.slices = slices
         ctx.blank, ctx.clamp, ctx.terms, ctx.act, ctx.lam, ctx.pen = blank, clamp, terms, act, lam, pen
         return costs
@@ -251,6 +244,147 @@ class _JointRnntBoundedFn(torch.autograd.Function):
             if need_b:
                 d_b += db
         return d_ep, d_pp, d_w, d_b, None, None, None, None, None, None, None, None, None, None, None, None
+
+
+def _slice_lengths(slices, host_t, host_u, dev):
+    """Per-slice length arrays of a bounded node, built once on the host from the caller's length sync:
+    [ll of every slice's utterances | tl of them], on `dev`."""
+    ll_s, tl_s = [], []
+    for s in slices:
+        for u in range(s.b0, s.b1):
+            ll_s.append(min(host_t[u], s.t1) - s.t0)
+            tl_s.append(host_u[u])
+    lens = torch.tensor(ll_s + tl_s, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        return lens.pin_memory().to(dev, non_blocking=True) if lens.numel() else lens.to(dev)
+
+
+class _JointTdtBoundedFn(torch.autograd.Function):
+    """Joiner + TDT loss with no logits tensor (joint_rnnt_tdt_loss): `_JointRnntBoundedFn` for the token-and-duration
+    loss.  The joiner has W = V + D outputs; forward wr_joint_tdt_stats -> wr_rnnt_tdt_sweeps, backward per slice
+    wr_joint_tdt_grad -> the joiner backward.  Exact fp32 only.  Saves ep, pp, w, b, the lengths and the TDT workspace."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, ep, pp, w, b, targets, llens, tlens, blank, durs, sigma, act, slices, host_t, host_u):
+        if not ep.is_cuda:
+            raise RuntimeError("wenet_celoss_amd.joint_rnnt_tdt_loss: tensors must live on a HIP device "
+                               "(this package has no CPU path)")
+        B, T, J = ep.shape
+        U1 = pp.shape[1]
+        W, D = w.shape[0], len(durs)
+        dev = ep.device
+        ep, pp, w, b = ep.contiguous(), pp.contiguous(), w.contiguous(), b.contiguous()
+        tws = _lib.workspace("wr_rnnt_tdt_workspace_bytes", B, T, U1, D, device=dev)
+        costs = torch.empty(B, dtype=torch.float32, device=dev)
+        ws = joiner_workspace(0, J, W, dev)
+        _lib.call("wr_joint_tdt_stats", ep, pp, w, b, llens, tlens, targets, B, T, U1, J, W, act, blank, _durations_arg(durs), D,
+                  sigma, ws, ws.numel(), tws, tws.numel(), device=dev)
+        _lib.call("wr_rnnt_tdt_sweeps", llens, tlens, B, T, U1, _durations_arg(durs), D, costs, tws, tws.numel(), device=dev)
+        ctx.save_for_backward(ep, pp, w, b, targets, llens, tlens, tws)
+        ctx.slice_lens = _slice_lengths(slices, host_t, host_u, dev)
+        ctx.slices = slices
+        ctx.blank, ctx.durs, ctx.sigma, ctx.act = blank, durs, sigma, act
+        return costs
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_costs):
+        ep, pp, w, b, targets, llens, tlens, tws = ctx.saved_tensors
+        B, T, J = ep.shape
+        U1 = pp.shape[1]
+        W, D = w.shape[0], len(ctx.durs)
+        dev = ep.device
+        need_w, need_b = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        gc = grad_costs.to(torch.float32).contiguous()
+        d_ep = torch.zeros_like(ep)                 # utterances without a slice (no frame) keep zero gradients
+        d_pp = torch.zeros_like(pp)
+        d_w = torch.zeros(W, J, dtype=torch.float32, device=dev) if need_w else None
+        d_b = torch.zeros(W, dtype=torch.float32, device=dev) if need_b else None
+        none = (None,) * 10
+        slices = ctx.slices
+        if not slices:
+            return (d_ep, d_pp, d_w, d_b) + none
+        nmax = max(s.cells(U1) for s in slices)
+        # buffers sized to the largest slice, allocated once per backward
+        g = torch.empty(nmax * W, dtype=torch.float32, device=dev)
+        dz = torch.empty(nmax * J, dtype=torch.float32, device=dev)
+        h = torch.empty(nmax * J, dtype=torch.float32, device=dev) if need_w else None
+        ws = joiner_workspace(0, J, W, dev)
+        durs = _durations_arg(ctx.durs)
+        nl = ctx.slice_lens.numel() // 2
+        k = 0
+        for i, s in enumerate(slices):
+            nb, nt = s.b1 - s.b0, s.t1 - s.t0
+            cells = nb * nt * U1
+            begin = (s.b0 * T + s.t0) * U1
+            _lib.call("wr_joint_tdt_grad", ep, pp, w, b, llens, tlens, targets, B, T, U1, J, W, ctx.act, ctx.blank, durs, D,
+                      ctx.sigma, gc, tws, tws.numel(), begin, begin + cells, g, ws, ws.numel(), int(i > 0), device=dev)
+            ll = ctx.slice_lens[k:k + nb]
+            tl = ctx.slice_lens[nl + k:nl + k + nb]
+            k += nb
+            de, dp, dw, db = joint_backward(g[:cells * W].view(nb, nt, U1, W), ep[s.b0:s.b1, s.t0:s.t1], pp[s.b0:s.b1], w,
+                                            ll, tl, 0, need_w, need_b, gout_zero_in_padding=True, act=ctx.act,
+                                            dz_out=dz[:cells * J].view(nb, nt, U1, J),
+                                            h_out=h[:cells * J].view(nb, nt, U1, J) if need_w else None)
+            d_ep[s.b0:s.b1, s.t0:s.t1] = de
+            d_pp[s.b0:s.b1] += dp
+            if need_w:
+                d_w += dw
+            if need_b:
+                d_b += db
+        return (d_ep, d_pp, d_w, d_b) + none
+
+
+def joint_rnnt_tdt_loss(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tensor,
+                        targets: torch.Tensor, logit_lengths: torch.Tensor, target_lengths: torch.Tensor,
+                        durations: Sequence[int], blank: int = 0, sigma: float = 0.0, reduction: str = "mean",
+                        activation: str = "tanh", precision: str = "fp32", *, logits_budget: int) -> torch.Tensor:
+    """rnnt_tdt_loss(ffn_out(act(ep[:, :, None] + pp[:, None])), targets, logit_lengths, target_lengths, durations) with
+    no logits tensor at all: the memory-bounded node (`_JointTdtBoundedFn`).  ep (B, T, J), pp (B, U+1, J), and a joiner
+    of W = V + len(durations) outputs (w_out (W, J), b_out (W,)): columns [0, V) token logits, the rest duration logits.
+    targets (B, U) int32, lengths (B,) int32, max(logit_lengths) == T and max(target_lengths) == U as in
+    `joint_rnnt_loss`; ``durations``, ``blank`` in [0, V), ``sigma`` and ``reduction`` as in `rnnt_tdt_loss`.  An utterance
+    with T_b = 0 has no slice and costs 0; one without a path costs +inf.
+    ``logits_budget`` (bytes, required): the backward recomputes the logits in slices whose fp32 gradient buffer holds at
+    most this many bytes (`plan_slices` on rows of W floats; ValueError below one frame row, U1 * W * 4 bytes).
+    ``precision``: "fp32" only -- any other joiner precision raises ValueError.  Ragged batches are not bucketed here."""
+    what = "joint_rnnt_tdt_loss"
+    if reduction not in ("none", "mean", "sum"):
+        raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
+    durs, sg = check_tdt(what, durations, sigma)
+    if precision != "fp32":
+        raise ValueError(f"{what}: precision {precision!r} is not supported, the memory-bounded TDT node runs the exact "
+                         "\"fp32\" joiner only")
+    W, D = w_out.shape[0], len(durs)
+    if W - D < 2:
+        raise ValueError(f"{what}: a joiner of {W} outputs with {D} durations leaves {W - D} token columns (at least 2 are "
+                         "needed)")
+    blank = _check_blank(what, blank, W - D)
+    act = activation_code(activation)
+    dev = ep.device
+    tg = targets.to(device=dev, dtype=torch.int32).contiguous()
+    ll = logit_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    tl = target_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    B, T = ep.shape[0], ep.shape[1]
+    U1 = pp.shape[1]
+    if not (tg.dim() == 2 and tg.shape == (B, U1 - 1) and ll.shape == (B,) and tl.shape == (B,)):
+        raise RuntimeError(f"{what}: targets must be (B, U) and lengths (B,) for ep (B,T,J), pp (B,U+1,J)")
+    lens = torch.stack([ll, tl]).cpu()                      # the one host sync, as in joint_rnnt_loss
+    if int(lens[0].max()) != T:
+        raise RuntimeError("input length mismatch")
+    if int(lens[1].max()) + 1 != U1:
+        raise RuntimeError("output length mismatch")
+    if int(lens.min()) < 0:
+        raise RuntimeError("lengths must be non-negative")
+    host_t, host_u = lens[0].tolist(), lens[1].tolist()
+    slices = plan_slices(host_t, host_u, T, U1, W, int(logits_budget))      # a bad budget fails before any launch
+    costs = _JointTdtBoundedFn.apply(ep, pp, w_out, b_out, tg, ll, tl, blank, durs, sg, act, slices, host_t, host_u)
+    if reduction == "mean":
+        return costs.mean()
+    if reduction == "sum":
+        return costs.sum()
+    return costs
 
 
 def plan_buckets(t_lens, u_lens, max_buckets: int = 4, min_gain: float = 0.08, min_cells: int = 20000):

@@ -31,7 +31,7 @@ from torch.nn.utils.rnn import pad_sequence
 
 from .common import IGNORE_ID, LabelSmoothingLoss, add_blank, add_sos_eos, end_blank, reverse_pad_list
 from .decoder import DecoderCache
-from .fused import joint_rnnt_loss, plan_buckets
+from .fused import joint_rnnt_loss, joint_rnnt_tdt_loss, plan_buckets
 from .joint import TransducerJoint, _call_precision
 from .rnnt_align import joint_rnnt_forced_align, rnnt_forced_align
 from .rnnt_loss import check_latency, rnnt_loss
@@ -199,6 +199,17 @@ class Transducer(nn.Module):
         rnnt_text_lengths = text_lengths.to(torch.int32)
         encoder_out_lens = encoder_out_lens.to(torch.int32)
         if self._is_tdt():
+            budget = self._logits_budget()
+            if budget is not None and self._can_bound_tdt_loss():
+                # memory-bounded node: no logits tensor (fused.joint_rnnt_tdt_loss), the exact fp32 joiner only
+                jt = self.joint
+                ep, pp = jt.pre_activation(encoder_out, predictor_out)
+                loss = joint_rnnt_tdt_loss(ep, pp, jt.ffn_out.weight, jt.ffn_out.bias, rnnt_text, encoder_out_lens,
+                                           rnnt_text_lengths, self.tdt_durations, blank=self.blank, sigma=self.tdt_sigma,
+                                           reduction="mean", activation=jt.activation, logits_budget=budget)
+                return None, loss
+            if budget is not None:
+                self._warn_budget()
             # TDT: the joiner's vocab_size + D logits, in whatever precision it produces them (16-bit under AMP)
             joint_out = self.joint(encoder_out, predictor_out)
             loss = rnnt_tdt_loss(joint_out, rnnt_text.contiguous(), encoder_out_lens.contiguous(),
@@ -213,11 +224,8 @@ class Transducer(nn.Module):
                                    precision=jt.precision, activation=jt.activation, logits_budget=self._logits_budget(),
                                    **self._latency_kwargs())
             return None, loss
-        if self._logits_budget() is not None and not getattr(self, "_warned_budget", False):
-            # the 16-bit (AMP) joiner modes and the two-op path keep a logits tensor: the budget does not apply to them
-            warnings.warn("Transducer: logits_budget / WR_FUSED_LOGITS_BUDGET_MB applies to the fused joiner + loss node with "
-                          "the \"fp32\" or \"bf16x3\" joiner only; this step keeps its logits tensor", RuntimeWarning)
-            self._warned_budget = True
+        if self._logits_budget() is not None:
+            self._warn_budget()
         if self.fused_loss and isinstance(self.joint, TransducerJoint):
             # the AMP single-term joiner keeps 16-bit logits (two ops), but a ragged batch is still cut into
             # label-length groups, each padded to its own maxima (fused.plan_buckets): same costs, fewer padded cells
@@ -242,6 +250,14 @@ class Transducer(nn.Module):
         loss = rnnt_loss(joint_out, rnnt_text.contiguous(), encoder_out_lens.contiguous(),
                          rnnt_text_lengths.contiguous(), blank=self.blank, reduction="mean", **self._latency_kwargs())
         return joint_out, loss
+
+    def _warn_budget(self) -> None:
+        """Once per model: a budget is set but this step's joiner keeps a logits tensor (the 16-bit AMP modes, the two-op
+        path; for a TDT model anything but the fused "fp32" joiner), so the budget does not apply to it."""
+        if not getattr(self, "_warned_budget", False):
+            warnings.warn("Transducer: logits_budget / WR_FUSED_LOGITS_BUDGET_MB applies to the fused joiner + loss node with "
+                          "the \"fp32\" or \"bf16x3\" joiner only; this step keeps its logits tensor", RuntimeWarning)
+            self._warned_budget = True
 
     def _latency_kwargs(self) -> Dict[str, object]:
         """fastemit_lambda / delay_penalty for the full-lattice loss; empty for the defaults (and for a model pickled
@@ -311,10 +327,18 @@ class Transducer(nn.Module):
     def _can_fuse_loss(self) -> bool:
         if self._is_tdt():
             return False
+        return self._joiner_can_fuse()
+
+    def _joiner_can_fuse(self) -> bool:
         jt = self.joint
         # the AMP single-term modes keep 16-bit logits ("autocast" is one of them under autocast only)
         return (self.fused_loss and isinstance(jt, TransducerJoint)
                 and _call_precision(jt.precision) not in ("bf16", "f16"))
+
+    def _can_bound_tdt_loss(self) -> bool:
+        """A TDT model whose joiner the memory-bounded TDT node serves: what _can_fuse_loss asks of a plain model's
+        joiner, and the exact fp32 precision (the TDT epilogues exist in that forward kernel only)."""
+        return self._is_tdt() and self._joiner_can_fuse() and _call_precision(self.joint.precision) == "fp32"
 
     def _loss_inputs(self, speech: torch.Tensor, speech_lengths: torch.Tensor, text: torch.Tensor,
                      context_list: torch.Tensor, context_lengths: torch.Tensor):
