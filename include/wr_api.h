@@ -1059,6 +1059,70 @@ int wr_greedy_search_tdt(wr_decoder *h, const float *enc_out_d, const int32_t *e
                          int32_t *hyps_d, int32_t *hyp_lens_d, int32_t *hyp_frames_d /* [N, max_hyp] or NULL */,
                          void *stream);
 
+/* TDT prefix beam search: the prefix beam search of a token-and-duration model, batched, with every decision on the
+ * device: n-best lists, the CTC / transducer score mixture, the input of attention rescoring.  This text is the contract.
+ *
+ * It is the smallest generalisation of wr_prefix_beam_search (one expansion per hypothesis per frame) and time-synchronous
+ * as NeMo's TDT beam search is: in a step only the hypotheses standing at the earliest frame are expanded, the others wait
+ * and compete with their scores as they are.
+ *
+ * The handle, the split of a logits row into V token and D duration columns (V = vocab_size - D), durations[D] (HOST) and
+ * blank are as for wr_greedy_search_tdt.  enc_out [B, T, E] fp32, enc_lens [B]; T_b = min(enc_lens[b], T).  ctc_logp
+ * [B, T, V] = log_softmax(ctc_lo(enc_out)) over the TOKEN vocabulary, or NULL: then (ctc_weight, transducer_weight) must be
+ * (0, 1) and nothing is mixed.
+ *
+ * State, per utterance b: an ordered list (best first) of at most `beam` entries (tokens, t, score, predictor state),
+ * starting as one entry ([blank], 0, 0.0, zero state).  Scores are float64.
+ * One step, while any entry has t < T_b:
+ *   1. f = min t over the entries.  Entries with t == f are ACTIVE, entries with t > f WAIT -- finished ones (t == T_b)
+ *      included, which never become active.
+ *   2. For each active entry the joiner's row for (frame t, predictor stepped on its last token from its state), fp32:
+ *      l = log_softmax(row[0:V]), ld = log_softmax(row[V:V+D]) (the loss's sigma is a training device and is not used);
+ *      mix[k] = l[k] without a posterior, else logf(tw * expf(l[k]) + cw * expf(ctc_logp[b, t, k])): the mixture of
+ *      wr_prefix_beam_search at the ENTRY's frame.
+ *   3. Its candidates: the `beam` best tokens by mix, descending, an exact tie to the lowest index -> ranks r = 0 ..
+ *      beam-1; then of the beam x D pairs with value v = mix[k_r] + ld[j] (one fp32 add) the best `beam` by v, descending,
+ *      ties to the lower r, then the lower j.  An fp32 add is monotone in each operand, so no pair of a token outside the
+ *      first `beam` can precede, under that order, the `beam` pairs its betters form with the same j: this IS the best
+ *      `beam` of all V x D pairs.  The candidate's score is (double)((float)score + v): the reference's fp32 add of a
+ *      float-cast score, as in wr_prefix_beam_search.
+ *   4. Every arc advances: t' = min(t + max(durations[j], 1), T_b).  A blank keeps the tokens and the predictor state, a
+ *      label appends k and takes the stepped state.  A label with duration 0 advances one frame like a blank with duration
+ *      0 (the reference search's one-symbol-per-frame restriction); its duration probability is kept, and it fuses with
+ *      the d = 1 arc of the same label.
+ *   5. The pool, in the order of the current beam: a waiting entry itself (unchanged), an active entry's `beam` candidates
+ *      in the order of 3.
+ *   6. Fusion: candidates with equal tokens AND equal t' are one class (one lattice state); its representative is the first
+ *      in pool order and accumulates the others in pool order with float64 log_add.  A waiting entry may fuse with an
+ *      expansion.
+ *   7. Stable descending sort of the representatives by fused score; the first `beam` are the new beam.
+ * f strictly increases, so the search ends after at most T_b steps, when every entry has t == T_b; entries clamped to T_b
+ * with equal tokens fuse.  With durations = (1,) every entry is active at the same frame and ld = 0 exactly: the rule is
+ * wr_prefix_beam_search on the V token columns.  As there, V >= beam is what the search is built for: with fewer token
+ * columns than `beam` the missing candidates appear with value -inf.
+ *
+ * Out, as wr_prefix_beam_search: hyps [B, beam, Tmax+1] (each begins with the seed blank, padded with -1; a label consumes
+ * a frame, so Tmax + 1 suffices), hyp_lens [B, beam], scores [B, beam] float64 (best first), n_hyps [B].
+ *
+ * The host replays 16 steps, reads back how many utterances still run and stops when none does (jumps make the step count
+ * smaller than T); the budget is T + 1 steps.  wr_decoder_set_graph applies (default: replayed from a graph, as the greedy
+ * searches that poll); the durations travel in the state block every call uploads, never in a captured graph, so calls
+ * with different durations, wr_prefix_beam_search and the greedy searches may alternate on one handle.
+ *
+ * Refused before any HIP call, in this order (all WR_EINVAL): the duration checks of wr_greedy_search_tdt; a null enc_out /
+ * enc_lens / hyps / hyp_lens / scores / n_hyps (ctc_logp may be null); a null handle; beam outside [1, max_beam]; B * beam
+ * or T beyond the handle; V = vocab_size - D < 2; blank outside [0, V); an embedding table with fewer than V rows; a null
+ * ctc_logp with (ctc_weight, transducer_weight) != (0, 1). */
+int wr_prefix_beam_search_tdt(wr_decoder *h, const float *enc_out_d, const int32_t *enc_lens_d,
+                              const float *ctc_logp_d /* [B, T, V] or NULL */, int B, int T, int beam, float ctc_weight,
+                              float transducer_weight, int blank, const int32_t *durations /* [D], host */, int D,
+                              int32_t *hyps_d, int32_t *hyp_lens_d, double *scores_d, int32_t *n_hyps_d, void *stream);
+
+/* Measurement hook: the three counters the last polling search on this handle read back (host memory, no HIP call).
+ * Greedy searches: streams still active, blank decisions, emissions.  wr_prefix_beam_search_tdt: utterances still running
+ * (0 after a successful call), steps taken summed over the utterances, hypotheses expanded. */
+int wr_decoder_last_counters(const wr_decoder *h, int32_t *out /* [3], host */);
+
 /* CTC forced alignment: Viterbi over the T x (2S+1) lattice, replacing
  * forced_align, wenet/utils/ctc_util.py:27-83 (CLI wenet/bin/alignment.py:215).  logits [B, Tmax, V]: pre-softmax
  * ctc_lo output, or log-posteriors if normalized != 0 (the reference is handed ctc.log_softmax(...)).

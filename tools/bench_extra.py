@@ -1157,10 +1157,68 @@ def bench_tdtdec(args):
                       "tokens_identical": got == want}), flush=True)
 
 
+def bench_tdtbeam(args):
+    """TDT prefix beam search at BASELINE config 5 (B = 16, T = 1500, beam 8, LSTM 2x256, J = 512): the plain prefix beam
+    search on a plain joiner of width 5000 (the first 5000 outputs), the TDT search on the joiner of width V + D = 5005
+    with durations 0 .. 4, and the TDT search with durations (1,) on the same handle (then 5004 token columns), all in one
+    run.  Per line: ms per call, us per step, steps taken against T (mean over the utterances), and the share of
+    lane-steps (beam slots of a step) that were expanded."""
+    import time
+    import wenet_celoss_amd as w
+    from wenet_celoss_amd.decoder import DeviceDecoder
+    dev = torch.device("cuda:0")
+    torch.manual_seed(6)
+    D = args.durations
+    V, E, P, J, H, L, beam = 5000, 256, 256, 512, 256, 2, 8
+    B, T = (args.B if args.B != 32 else 16), (args.T if args.T != 1000 else 1500)
+    # the embedding table has a row for every joiner column: with durations (1,) all but one of them are tokens
+    pred = w.RNNPredictor(V + D, P, P, 0.1, H, L).to(dev).eval()
+    joint = w.TransducerJoint(V + D, E, P, J).to(dev).eval()
+    with torch.no_grad():
+        joint.ffn_out.weight *= 10
+        joint.ffn_out.bias[0] += 16.0
+    plain_joint = w.TransducerJoint(V, E, P, J).to(dev).eval()
+    plain_joint.load_state_dict({k: (v[:V] if k.startswith("ffn_out.") else v) for k, v in joint.state_dict().items()})
+    ctc = w.CTC(V, E).to(dev).eval()
+    enc = torch.randn(B, T, E, device=dev)
+    lens = torch.full((B,), T, dtype=torch.int32)
+    with torch.no_grad():
+        ctc_logp = ctc.log_softmax(enc)
+    plain = DeviceDecoder(pred, plain_joint, B * beam, B, T, 0, beam)
+    tdt = DeviceDecoder(pred, joint, B * beam, B, T, 0, beam)
+
+    def timed(fn):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.steps, out
+
+    only = set(args.only.split(",")) if args.only else {"plain", "tdt", "tdt1"}
+    if "plain" in only:
+        dt, out = timed(lambda: plain.prefix_beam(enc, lens, ctc_logp, beam, 0.3, 0.7, 0))
+        print(json.dumps({"what": "prefix_beam_search (plain joiner, width 5000)", "B": B, "T": T, "beam": beam,
+                          "ms_per_call": round(dt * 1e3, 2), "us_per_step": round(dt * 1e6 / T, 1), "steps": T,
+                          "expanded_share": 1.0, "best_len": len(out[0][0][0])}), flush=True)
+    for key, durations in (("tdt", tuple(range(D))), ("tdt1", (1,))):
+        if key not in only:
+            continue
+        dt, out = timed(lambda: tdt.prefix_beam_tdt(enc, lens, durations, beam, 0))
+        _, utt_steps, expanded = tdt.last_counters()
+        steps = utt_steps / B
+        print(json.dumps({"what": "prefix_beam_search_tdt", "durations": durations, "B": B, "T": T, "beam": beam,
+                          "ms_per_call": round(dt * 1e3, 2), "us_per_step": round(dt * 1e6 / max(steps, 1), 1),
+                          "steps": round(steps, 1), "steps_over_T": round(steps / T, 3),
+                          "expanded_share": round(expanded / max(utt_steps * beam, 1), 3),
+                          "best_len": len(out[0][0][0])}), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align", "simple", "smoothed", "pruned", "tdt",
-                                     "tdtstep", "tdtalign", "tdtdec"])
+                                     "tdtstep", "tdtalign", "tdtdec", "tdtbeam"])
     ap.add_argument("--durations", type=int, default=5, help="tdt, tdtstep, tdtalign: number of durations D (the set is 0 .. D-1)")
     ap.add_argument("--n-steps", type=int, default=64)
     ap.add_argument("--chunks", type=int, default=4)
@@ -1198,4 +1256,5 @@ if __name__ == "__main__":
         _lib.load().wr_tune_set(6, a.tile)
     {"joint": bench_joint, "ctc": bench_ctc, "greedy": bench_greedy, "beam": bench_beam, "step": bench_step, "ctcdec": bench_ctcdec, "hotword": bench_hotword,
      "align": bench_align, "simple": bench_simple, "smoothed": bench_smoothed, "pruned": bench_pruned,
-     "tdt": bench_tdt, "tdtstep": bench_tdtstep, "tdtalign": bench_tdtalign, "tdtdec": bench_tdtdec}[a.what](a)
+     "tdt": bench_tdt, "tdtstep": bench_tdtstep, "tdtalign": bench_tdtalign, "tdtdec": bench_tdtdec,
+     "tdtbeam": bench_tdtbeam}[a.what](a)

@@ -18,7 +18,7 @@ from .rnnt_tdt import TDTLoss, rnnt_tdt_forced_align, rnnt_tdt_lattice, rnnt_tdt
 from .predictor import ConvPredictor, EmbeddingPredictor, PredictorBase, RNNPredictor  # noqa: F401
 from .search.greedy_search import (basic_greedy_search, basic_greedy_search_both,  # noqa: F401
                                    basic_greedy_search_hw, edit_distance, tdt_greedy_search)
-from .search.prefix_beam_search import PrefixBeamSearch, Sequence  # noqa: F401
+from .search.prefix_beam_search import PrefixBeamSearch, Sequence, tdt_prefix_beam_search  # noqa: F401
 from . import k2  # noqa: F401  (the k2 functions with k2's signatures: rnnt_type=, delay_penalty=)
 from .transducer import Transducer  # noqa: F401
 from .common import IGNORE_ID, add_blank, log_add  # noqa: F401
@@ -29,4 +29,5 @@ __all__ = ["rnnt_loss", "RNNTLoss", "CTC", "ctc_loss", "TransducerJoint", "joint
            "ctc_greedy_search", "ctc_prefix_beam_search", "forced_align", "forced_align_batch", "rnnt_forced_align",
            "joint_rnnt_forced_align", "rnnt_frame_tokens", "rnnt_loss_simple", "rnnt_simple_forced_align", "rnnt_loss_smoothed",
            "get_rnnt_prune_ranges", "do_rnnt_pruning", "rnnt_loss_pruned", "k2",
-           "rnnt_tdt_loss", "TDTLoss", "rnnt_tdt_lattice", "joint_rnnt_tdt_loss", "tdt_greedy_search", "rnnt_tdt_forced_align"]
+           "rnnt_tdt_loss", "TDTLoss", "rnnt_tdt_lattice", "joint_rnnt_tdt_loss", "tdt_greedy_search", "rnnt_tdt_forced_align",
+           "tdt_prefix_beam_search"]

@@ -34,6 +34,9 @@
 //   beam_topk_kernel /      log-softmax, CTC mixture, top-k from registers; per-utterance
 //   beam_update_kernel      expansion, prefix fusion (float64 log_add), stable prune --
 //                           one candidate per thread
+//   tdt_beam_topk_kernel /  the same for a token-and-duration model: token and duration log-softmax, the best
+//   tdt_beam_update_kernel  (token, duration) pairs of the hypotheses at the utterance's earliest frame; the
+//                           others wait; equal tokens at an equal frame fuse
 //
 // Micro-steps are replayed from a hipGraph (captured once per decoder handle) so
 // the host only checks a "lanes still active" word every 16 steps.
@@ -2192,6 +2195,462 @@ __global__ __launch_bounds__(kBeamUpdThreads) void beam_update_kernel(DevState *
     WR_STAMP_FLUSH(7);
 }
 
+// -------------------------------------------------- token-and-duration beam --
+// include/wr_api.h, "TDT prefix beam search".  The hypotheses of one utterance stand at different frames (lane_t[n]); only
+// those at the earliest frame f = frame[b] are expanded in a step (lane_active), the others wait in the beam as they are.
+// beam_init_kernel starts the lanes; this kernel counts the utterances that have a frame to decode and clears the
+// statistics: active_count = {utterances running, utterance-steps taken, hypotheses expanded}.
+__global__ void tdt_beam_begin_kernel(DevState *s)
+{
+    __shared__ int cnt;
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int b = threadIdx.x; b < s->n_utt; b += blockDim.x) mine += (s->enc_lens[b] > 0 && s->T > 0) ? 1 : 0;
+    if (mine) atomicAdd(&cnt, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) { s->active_count[0] = cnt; s->active_count[1] = 0; s->active_count[2] = 0; }
+}
+
+// per active lane: log-softmax of the V token columns of the row (stride Dims.V = V + D), mixture with the CTC posterior of
+// the LANE's frame, top-`beam` tokens as in beam_topk_kernel; then the log-softmax of the D <= 9 duration columns in one
+// wave and the best `beam` of the beam x D pairs (rank r, duration j) by mix[k_r] + ld[j], ties to the lower r, then the
+// lower j.  Out: topv = the pair's value, topi = k | j << 16 (as tdt_rows_kernel packs a decision).
+template <int NV>
+__global__ __launch_bounds__(kTopkThreads) void tdt_beam_topk_kernel(DevState *sp)
+{
+    constexpr int NW = kTopkThreads / 64;
+    __shared__ float sv[NW];
+    __shared__ float wv[NW * kMaxBeam];
+    __shared__ int wi[NW * kMaxBeam];
+    const DevState S = *sp;
+    const Dims &d = S.d;
+    const int n = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    // no branch before the loads (idle lanes leave after the first reduction)
+    const int act = S.lane_active[n];
+    const int b = n / S.beam;
+    int fr = S.lane_t[n];
+    fr = fr < S.T ? fr : S.T - 1;
+    fr = fr > 0 ? fr : 0;
+    const int D = S.tdt_D, Vt = d.V - D;
+    const bool has_ctc = S.ctc_logp != nullptr;
+    const float *__restrict__ x = S.logits + (size_t)n * d.V;
+    const float *__restrict__ cp = has_ctc ? S.ctc_logp + ((size_t)b * S.T + fr) * Vt : x;
+    const float ninf = -__builtin_huge_valf();
+    float xv[NV], cv[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int v = tid + i * kTopkThreads;
+        xv[i] = x[v < Vt ? v : Vt - 1];
+        cv[i] = 0.f;
+    }
+    if (has_ctc) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int v = tid + i * kTopkThreads;
+            cv[i] = cp[v < Vt ? v : Vt - 1];
+        }
+    }
+    const float xd = x[Vt + (lane < D ? lane : 0)];           // the duration columns, one per lane of every wave
+    float m = -3.0e38f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) m = fmaxf(m, (tid + i * kTopkThreads < Vt) ? xv[i] : -3.0e38f);
+    m = block_max(m, sv);
+    if (!act) return;
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) sum += (tid + i * kTopkThreads < Vt) ? expf(xv[i] - m) : 0.f;
+    sum = block_sum(sum, sv);
+    const float ls = logf(sum);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const float l = (xv[i] - m) - ls;
+        const float mix = has_ctc ? logf(S.tr_weight * expf(l) + S.ctc_weight * expf(cv[i])) : l;
+        xv[i] = (tid + i * kTopkThreads < Vt) ? mix : ninf;
+    }
+    for (int k = 0; k < S.beam; ++k) {
+        float best = ninf;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+            if (xv[i] > best) { best = xv[i]; bi = tid + i * kTopkThreads; }   // ascending scan: lowest index wins ties
+        wave_argmax_dpp(best, bi);
+        if (lane == 0) { wv[wave * S.beam + k] = best; wi[wave * S.beam + k] = bi; }
+        if (bi != 0x7fffffff && (bi % kTopkThreads) == tid) {                     // taken
+#pragma unroll
+            for (int i = 0; i < NV; ++i)
+                if (i == bi / kTopkThreads) xv[i] = ninf;
+        }
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    // duration log-softmax: lanes 0 .. D-1 of this wave hold the columns
+    const float dm = wave_allmax_dpp(lane < D ? xd : -3.0e38f);
+    const float ds = wave_allsum_dpp(lane < D ? expf(xd - dm) : 0.f);
+    const float ldv = (xd - dm) - logf(ds);
+    constexpr int PM = NW * kMaxBeam / 64;      // token survivors per lane
+    constexpr int PP = (kMaxBeam * kTdtMaxD + 63) / 64;   // (rank, duration) pairs per lane: pair p = r * D + j at lane p % 64
+    const int total = NW * S.beam, npair = S.beam * D;
+    float c0[PM], pv[PP], pl[PP];
+    int ci[PM], pk[PP];
+#pragma unroll
+    for (int q = 0; q < PM; ++q) {
+        const int j = lane + q * 64;
+        c0[q] = j < total ? wv[j] : ninf;
+        ci[q] = j < total ? wi[j] : 0x7fffffff;
+    }
+#pragma unroll
+    for (int q = 0; q < PP; ++q) {
+        pl[q] = __shfl(ldv, (lane + q * 64) % D, kWave);
+        pv[q] = ninf;
+        pk[q] = 0;
+    }
+    for (int k = 0; k < S.beam; ++k) {
+        float best = ninf;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int q = 0; q < PM; ++q)
+            if (c0[q] > best || (c0[q] == best && ci[q] < bi)) { best = c0[q]; bi = ci[q]; }
+        wave_argmax_dpp(best, bi);
+#pragma unroll
+        for (int q = 0; q < PP; ++q) {
+            const int p = lane + q * 64;
+            if (p < npair && p / D == k) { pv[q] = best + pl[q]; pk[q] = bi < Vt ? bi : 0; }   // one fp32 add
+        }
+#pragma unroll
+        for (int q = 0; q < PM; ++q)
+            if (ci[q] == bi) c0[q] = ninf;
+    }
+    for (int c = 0; c < S.beam; ++c) {
+        float best = ninf;
+        int bp = 0x7fffffff;
+#pragma unroll
+        for (int q = 0; q < PP; ++q)
+            if (pv[q] > best) { best = pv[q]; bp = lane + q * 64; }              // ascending p: lower r, then lower j
+        wave_argmax_dpp(best, bp);
+        if (bp == 0x7fffffff) {                    // nothing finite is left
+            if (lane == 0) { S.topv[(size_t)n * S.beam + c] = ninf; S.topi[(size_t)n * S.beam + c] = 0; }
+            continue;
+        }
+        if ((bp & 63) == lane) {
+#pragma unroll
+            for (int q = 0; q < PP; ++q)
+                if (q == (bp >> 6)) {
+                    S.topv[(size_t)n * S.beam + c] = best;
+                    S.topi[(size_t)n * S.beam + c] = pk[q] | ((bp % D) << 16);
+                    pv[q] = ninf;
+                }
+        }
+    }
+}
+
+// one workgroup per utterance: the pool (a waiting hypothesis as it is, an active one's `beam` pairs), fusion of equal
+// (tokens, frame) with float64 log_add in pool order, stable prune, the survivors moved as beam_update_kernel moves them
+// (a waiting survivor and a blank extension inherit the committed predictor state, a label the stepped one), each
+// survivor's frame, and which of them stand at the new earliest frame.
+__global__ __launch_bounds__(kBeamUpdThreads) void tdt_beam_update_kernel(DevState *sp)
+{
+    constexpr int NT = kBeamUpdThreads;
+    constexpr int MC = kMaxBeam * kMaxBeam;
+    __shared__ int c_base[MC], c_tok[MC], c_len[MC], c_last[MC], c_t[MC], c_rep[MC], c_rank[MC], order[kMaxBeam];
+    __shared__ unsigned long long c_hash[MC];
+    __shared__ int e_src[kMaxBeam], e_blank[kMaxBeam], e_tok[kMaxBeam], e_last[kMaxBeam], e_lb[kMaxBeam], e_t[kMaxBeam];
+    __shared__ int p_t[kMaxBeam], p_off[kMaxBeam + 1];
+    __shared__ double c_score[MC], f_score[MC];
+    __shared__ int s_keep, s_nact, s_fnext;
+    const DevState S = *sp;
+    const Dims &d = S.d;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int beam = S.beam;
+    const int T = S.enc_lens[b] < S.T ? S.enc_lens[b] : S.T;
+    const int fr = S.frame[b];                     // the earliest frame of the beam
+    if (fr >= T) return;                           // every hypothesis has reached T_b
+    const int N = S.n_hyps[b];
+    const int sel = S.hyp_sel[b];
+    const size_t hstride = (size_t)S.n_utt * beam * S.Lmax;
+    const int32_t *__restrict__ hy = S.bhyps + sel * hstride + (size_t)b * beam * S.Lmax;
+    int32_t *__restrict__ hy2 = S.bhyps + (1 - sel) * hstride + (size_t)b * beam * S.Lmax;
+    const int32_t *__restrict__ hl = S.bhyp_lens + (size_t)sel * S.n_utt * beam + (size_t)b * beam;
+    int32_t *__restrict__ hl2 = S.bhyp_lens + (size_t)(1 - sel) * S.n_utt * beam + (size_t)b * beam;
+    // phase 1: the pool in the order of the beam
+    if (tid < kMaxBeam) {                          // the entries' lengths and frames, requested side by side
+        e_lb[tid] = tid < N ? hl[tid] : 0;
+        p_t[tid] = tid < N ? S.lane_t[b * beam + tid] : 0;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int off = 0, na = 0;
+        for (int e = 0; e < N; ++e) {
+            const int t = p_t[e];
+            p_off[e] = off;
+            off += t == fr ? beam : 1;
+            na += t == fr ? 1 : 0;
+        }
+        p_off[N] = off;
+        s_nact = na;
+        s_keep = 0;
+    }
+    __syncthreads();
+    const int C = p_off[N];                        // <= beam * beam: a waiting hypothesis takes the place of `beam` pairs
+    if (tid < C) {
+        int e = 0;
+        while (e + 1 < N && p_off[e + 1] <= tid) ++e;
+        const int r = tid - p_off[e];
+        const int n = b * beam + e;
+        const int te = p_t[e];
+        const int lb = hl[e];
+        const int last = S.token[n];               // last token of hypothesis e (its predictor input)
+        const unsigned long long hh = S.bhash[n];
+        const double se = S.bscores[(size_t)b * beam + e];
+        int tok = -1, tn = te;                     // tok < 0: nothing appended (a waiting hypothesis or a blank arc)
+        double sc = se;
+        if (te == fr) {
+            const int pair = S.topi[(size_t)n * beam + r];
+            const int k = pair & 0xffff;
+            const int dur = (int)((S.tdt_durs >> (4 * (pair >> 16))) & 15);
+            sc = (double)((float)se + S.topv[(size_t)n * beam + r]);   // the reference's fp32 add of a float-cast score
+            tn = te + (dur > 1 ? dur : 1);
+            tn = tn < T ? tn : T;
+            if (k != S.blank) tok = k;
+        }
+        c_score[tid] = sc;
+        c_base[tid] = e;
+        c_tok[tid] = tok;
+        c_t[tid] = tn;
+        c_len[tid] = lb + (tok >= 0 ? 1 : 0);
+        c_last[tid] = tok >= 0 ? tok : last;
+        c_hash[tid] = tok >= 0 ? hyp_hash_push(hh, tok) : hh;
+        c_rep[tid] = tid;
+        c_rank[tid] = 0;
+    }
+    __syncthreads();
+    // phase 2: class representative = the first pool entry with the same tokens and the same frame
+    for (int p = tid; p < C * C; p += NT) {
+        const int i = p / C, f = p - i * C;
+        if (f >= i || c_t[f] != c_t[i] || c_hash[f] != c_hash[i] || c_len[f] != c_len[i] || c_last[f] != c_last[i]) continue;
+        // equal hashes, lengths and last tokens: the sequences are equal iff the first len-1 tokens of the two base
+        // hypotheses are (both bases hold at least that many)
+        const int32_t *__restrict__ pi = hy + (size_t)c_base[i] * S.Lmax;
+        const int32_t *__restrict__ pf = hy + (size_t)c_base[f] * S.Lmax;
+        const int ncmp = c_len[i] - 1;
+        bool same = true;
+        constexpr int UC = 16;
+        for (int q0 = 0; q0 < ncmp && same; q0 += UC) {
+            int xa[UC], ya[UC];
+#pragma unroll
+            for (int u = 0; u < UC; ++u) {
+                const int q = q0 + u < ncmp ? q0 + u : ncmp - 1;
+                xa[u] = pi[q];
+                ya[u] = pf[q];
+            }
+#pragma unroll
+            for (int u = 0; u < UC; ++u) same = same && (xa[u] == ya[u]);
+        }
+        if (same) atomicMin(&c_rep[i], f);
+    }
+    __syncthreads();
+    // phase 3: a representative accumulates its class in pool order with float64 log_add
+    const int n_dup = __syncthreads_count(tid < C && c_rep[tid] != tid);
+    if (n_dup == 0) {
+        if (tid < C) f_score[tid] = c_score[tid];
+    } else {
+        const int c = (tid & 63) * (NT / 64) + (tid >> 6);     // consecutive entries in different waves
+        if (c < C) {
+            double sc = c_score[c];
+            if (c_rep[c] == c) {
+#pragma unroll 8
+                for (int f = c + 1; f < C; ++f)
+                    if (c_rep[f] == c) sc = log_add2(sc, c_score[f]);
+            }
+            f_score[c] = sc;
+        }
+    }
+    __syncthreads();
+    // phase 4: stable descending rank among the representatives, prune
+    for (int p = tid; p < C * C; p += NT) {
+        const int i = p / C, f = p - i * C;
+        if (c_rep[i] != i || c_rep[f] != f) continue;
+        const double me = f_score[i], ot = f_score[f];
+        if (ot > me || (ot == me && f < i)) atomicAdd(&c_rank[i], 1);
+    }
+    __syncthreads();
+    if (tid < C && c_rep[tid] == tid) {
+        if (c_rank[tid] < beam) order[c_rank[tid]] = tid;
+        atomicAdd(&s_keep, 1);
+    }
+    __syncthreads();
+    const int keep = s_keep < beam ? s_keep : beam;
+    if (tid < keep) {
+        const int f = order[tid];
+        e_src[tid] = c_base[f];
+        e_tok[tid] = c_tok[f];
+        e_blank[tid] = c_tok[f] < 0;
+        e_last[tid] = c_last[f];
+        e_t[tid] = c_t[f];
+        hl2[tid] = c_len[f];
+        S.bscores[(size_t)b * beam + tid] = f_score[f];
+        S.bhash[b * beam + tid] = c_hash[f];
+        S.token[b * beam + tid] = c_last[f];       // the hypothesis' next predictor input: its last token
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int fn = e_t[0];
+        for (int e = 1; e < keep; ++e) fn = e_t[e] < fn ? e_t[e] : fn;
+        s_fnext = fn;
+    }
+    // phase 5: hypotheses into the other buffer
+    {
+        int maxlb = 0;
+        for (int e = 0; e < keep; ++e) maxlb = e_lb[e_src[e]] > maxlb ? e_lb[e_src[e]] : maxlb;
+        constexpr int UN = 4;
+        for (int i0 = 0; i0 < keep * maxlb; i0 += NT * UN) {
+            int val[UN];
+#pragma unroll
+            for (int u = 0; u < UN; ++u) {
+                const int i = i0 + u * NT + tid;
+                const int e = i / maxlb, q = i - e * maxlb;
+                const bool in = e < keep && q < e_lb[e_src[e < keep ? e : 0]];
+                val[u] = in ? hy[(size_t)e_src[e] * S.Lmax + q] : 0;
+            }
+#pragma unroll
+            for (int u = 0; u < UN; ++u) {
+                const int i = i0 + u * NT + tid;
+                const int e = i / maxlb, q = i - e * maxlb;
+                if (e < keep && q < e_lb[e_src[e]]) hy2[(size_t)e * S.Lmax + q] = val[u];
+            }
+        }
+        if (tid < keep) {
+            const int lb = e_lb[e_src[tid]];
+            if (!e_blank[tid] && lb < S.Lmax) hy2[(size_t)tid * S.Lmax + lb] = e_tok[tid];
+        }
+    }
+    if (d.ptype == kPredLstm) {
+        // slot NUMBERS as in beam_update_kernel: the committed slot of the base for a waiting survivor or a blank arc, the
+        // slot of the base's stepped state for a label (only an expanded base has one); every lane gets a free slot; then
+        // layer 0 of every survivor's next step, whenever that step will be consulted
+        __shared__ int s_comm[kMaxBeam], s_new[kMaxBeam], s_oc[kMaxBeam], s_on[kMaxBeam];
+        if (tid < beam) { s_oc[tid] = S.comm_slot[b * beam + tid]; s_on[tid] = S.new_slot[b * beam + tid]; }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned used = 0;                                   // bit j: slot b*beam + j, bit beam + j: slot NLp + b*beam + j
+            for (int e = 0; e < keep; ++e) {
+                const int sl = e_blank[e] ? s_oc[e_src[e]] : s_on[e_src[e]];
+                s_comm[e] = sl;
+                used |= 1u << (sl >= d.NLp ? beam + (sl - d.NLp - b * beam) : sl - b * beam);
+            }
+            int bit = 0;
+            for (int e = 0; e < beam; ++e) {
+                while (used & (1u << bit)) ++bit;
+                s_new[e] = bit < beam ? b * beam + bit : d.NLp + b * beam + (bit - beam);
+                if (e >= keep) s_comm[e] = s_new[e];
+                ++bit;
+            }
+        }
+        __syncthreads();
+        if (tid < beam) { S.comm_slot[b * beam + tid] = s_comm[tid]; S.new_slot[b * beam + tid] = s_new[tid]; }
+        constexpr int UN = 2;
+        const int items = keep * d.H;
+        for (int i0 = 0; i0 < items; i0 += NT * UN) {
+            float ev[UN][4], gv[UN][4], cv[UN];
+#pragma unroll
+            for (int q = 0; q < UN; ++q) {
+                const int i = i0 + q * NT + tid;
+                const int e = i < items ? i / d.H : 0, u = i < items ? i - e * d.H : 0;
+                const int col = (u >> 3) * 32 + (u & 7);
+                const float *__restrict__ er = S.etab + (size_t)e_last[e] * d.G4p + col;
+                const float *__restrict__ gr = S.pool_g + (size_t)s_comm[e] * d.G4p + col;
+#pragma unroll
+                for (int gt = 0; gt < 4; ++gt) { ev[q][gt] = er[gt * 8]; gv[q][gt] = gr[gt * 8]; }
+                cv[q] = S.pool_c[(size_t)s_comm[e] * d.Hp + u];
+            }
+#pragma unroll
+            for (int q = 0; q < UN; ++q) {
+                const int i = i0 + q * NT + tid;
+                if (i >= items) continue;
+                const int e = i / d.H, u = i - e * d.H;
+                const float ig = sigmoidf_(ev[q][0] + gv[q][0]);
+                const float fg = sigmoidf_(ev[q][1] + gv[q][1]);
+                const float gg = tanhf(ev[q][2] + gv[q][2]);
+                const float og = sigmoidf_(ev[q][3] + gv[q][3]);
+                const float c = fg * cv[q] + ig * gg;
+                S.pool_c[(size_t)s_new[e] * d.Hp + u] = c;
+                S.new_hT[(size_t)u * d.NLp + b * beam + e] = og * tanhf(c);
+            }
+        }
+    } else {
+        // next predictor inputs
+        {
+            constexpr int UN = 4;
+            const float *__restrict__ emb = S.embed;
+            for (int i0 = 0; i0 < keep * d.D; i0 += NT * UN) {
+                float val[UN];
+#pragma unroll
+                for (int u = 0; u < UN; ++u) {
+                    const int i = i0 + u * NT + tid;
+                    const int e = i / d.D, k = i - e * d.D;
+                    val[u] = e < keep ? emb[(size_t)e_last[e] * d.D + k] : 0.f;
+                }
+#pragma unroll
+                for (int u = 0; u < UN; ++u) {
+                    const int i = i0 + u * NT + tid;
+                    const int e = i / d.D, k = i - e * d.D;
+                    if (e < keep) S.xT[(size_t)k * d.NLp + b * beam + e] = val[u];
+                }
+            }
+        }
+        // token histories: the base's committed one for a waiting survivor or a blank arc, the stepped one for a label;
+        // read into registers, synchronised, written back in place (beam_update_kernel)
+        {
+            constexpr int UN = 8;
+            const int rows = d.L * d.Hp, per_it = NT / beam;
+            const int e = tid % beam, r0 = tid / beam;
+            const bool on = e < keep && r0 < per_it;
+            const int src = b * beam + (on ? e_src[e] : 0), dst = b * beam + e;
+            const bool bl = on ? e_blank[e] != 0 : true;
+            const float *hsrc = bl ? S.cache_hT : S.new_hT;
+            const float *csrc = bl ? S.cache_cT : S.new_cT;
+            for (int rb = 0; rb < rows; rb += per_it * UN) {
+                float hv[UN], cw[UN];
+#pragma unroll
+                for (int u = 0; u < UN; ++u) {
+                    const int r = rb + u * per_it + r0;
+                    const size_t so = (size_t)(r < rows ? r : 0) * d.NLp + src;
+                    hv[u] = hsrc[so];
+                    cw[u] = csrc[so];
+                }
+                __syncthreads();
+#pragma unroll
+                for (int u = 0; u < UN; ++u) {
+                    const int r = rb + u * per_it + r0;
+                    if (on && r < rows) {
+                        const size_t dst_o = (size_t)r * d.NLp + dst;
+                        S.cache_hT[dst_o] = hv[u];
+                        S.cache_cT[dst_o] = cw[u];
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const int fnext = s_fnext;                     // f strictly increases: every arc advances
+    if (tid < beam) {
+        const int n = b * beam + tid;
+        const int t = tid < keep ? e_t[tid] : fnext;
+        S.lane_active[n] = (tid < keep) && t == fnext && t < T;
+        S.lane_t[n] = t;
+        S.need_pred[n] = 1;
+        if (tid == 0) {
+            S.n_hyps[b] = keep;
+            S.frame[b] = fnext;
+            S.hyp_sel[b] = 1 - sel;
+            atomicAdd(S.active_count + 1, 1);
+            atomicAdd(S.active_count + 2, s_nact);
+            if (fnext >= T) atomicSub(S.active_count, 1);
+        }
+    }
+}
+
 __global__ void beam_export_kernel(DevState *s, int32_t *hyps_out, int32_t *lens_out, double *scores_out, int32_t *n_out)
 {
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -2241,6 +2700,7 @@ struct wr_decoder {
     GraphSlot greedy[kMaxLook + 1];   // one per look-ahead setting, keyed by the lanes
     GraphSlot greedy_tdt[kMaxLook + 1];   // the same for the token-and-duration micro-step
     GraphSlot beam;               // keyed by lanes and beam
+    GraphSlot beam_tdt;           // the token-and-duration beam step, keyed likewise
     GraphSlot hotword;            // keyed by the lanes
     int stream_lanes = -1;        // lanes whose streaming state (cache, token, flags) is live; -1: none
     int look = 0;                 // greedy look-ahead: frames per micro-step (1..kMaxLook), 0: chosen per replay
@@ -2262,6 +2722,7 @@ void for_each_graph(wr_decoder *h, F f)
     for (GraphSlot &g : h->greedy) f(g);
     for (GraphSlot &g : h->greedy_tdt) f(g);
     f(h->beam);
+    f(h->beam_tdt);
     f(h->hotword);
 }
 
@@ -2678,6 +3139,12 @@ extern "C" int wr_decoder_set_graph(wr_decoder *h, int enable)
     return WR_OK;
 }
 
+// decode_tdt.hpp: the counters behind wr_decoder_last_counters -- pinned host memory, complete since the last poll
+void wr::decoder_counters(const wr_decoder *h, int32_t *out)
+{
+    for (int i = 0; i < 3; ++i) out[i] = h->h_active ? h->h_active[i] : 0;
+}
+
 extern "C" int wr_decoder_set_lookahead(wr_decoder *h, int frames)
 {
     WR_REQUIRE(h != nullptr, WR_EINVAL, "decoder_set_lookahead: null handle");
@@ -2754,6 +3221,19 @@ int beam_frame(wr_decoder *h, int n_lanes, int n_utt, hipStream_t st)
         return launch("beam_topk_kernel", beam_topk_kernel<decltype(n)::value>, dim3(n_lanes), dim3(kTopkThreads), 0, st, h->dev);
     }));
     return launch("beam_update_kernel", beam_update_kernel, dim3(n_utt), dim3(kBeamUpdThreads), 0, st, h->dev);
+}
+
+// one step of the token-and-duration beam search: the lane GEMMs take each lane's frame from lane_t, as in the greedy search
+int tdt_beam_step(wr_decoder *h, int n_lanes, int n_utt, hipStream_t st)
+{
+    WR_TRY(launch_predictor_and_joint(h, n_lanes, st));
+    const int V = h->d.V;                           // <= 16384 (check_weights)
+    const int per_thread = V <= kTopkThreads * 4 ? 4 : V <= kTopkThreads * 10 ? 10 : 32;
+    WR_TRY(with_int<4, 10, 32>(per_thread, [&](auto n) {
+        return launch("tdt_beam_topk_kernel", tdt_beam_topk_kernel<decltype(n)::value>, dim3(n_lanes), dim3(kTopkThreads), 0, st,
+                      h->dev);
+    }));
+    return launch("tdt_beam_update_kernel", tdt_beam_update_kernel, dim3(n_utt), dim3(kBeamUpdThreads), 0, st, h->dev);
 }
 
 // Order the decoder's work stream after everything already enqueued on the caller's stream ...
@@ -2851,6 +3331,15 @@ int run_until_idle(wr_decoder *h, hipStream_t st, const char *what, int key, lon
     return WR_OK;
 }
 
+// DevState::tdt_durs of a checked duration set
+unsigned long long pack_durations(const TdtDur &dur)
+{
+    unsigned long long durs = 0;
+    for (int d = 0; d < kTdtMaxD; ++d)
+        if (dur.slot[d] >= 0) durs |= (unsigned long long)d << (4 * dur.slot[d]);
+    return durs;
+}
+
 // what a token-and-duration search adds to a greedy run
 struct TdtRun {
     unsigned long long durs;      // DevState::tdt_durs
@@ -2921,10 +3410,51 @@ int greedy_run(wr_decoder *h, const float *enc_out_d, const int32_t *enc_lens_d,
 int wr::greedy_tdt_body(wr_decoder *h, const float *enc_out_d, const int32_t *enc_lens_d, int N, int T, int n_steps, int blank,
                         const TdtDur &dur, int32_t *hyps_d, int32_t *hyp_lens_d, int32_t *hyp_frames_d, void *stream)
 {
-    TdtRun run{0, dur.D, hyp_frames_d};
-    for (int d = 0; d < kTdtMaxD; ++d)
-        if (dur.slot[d] >= 0) run.durs |= (unsigned long long)d << (4 * dur.slot[d]);
+    TdtRun run{pack_durations(dur), dur.D, hyp_frames_d};
     return greedy_run(h, enc_out_d, enc_lens_d, N, T, n_steps, blank, hyps_d, hyp_lens_d, stream, 0, &run);
+}
+
+// decode_tdt.hpp: the search behind wr_prefix_beam_search_tdt (decode_tdt.cpp has checked durations, pointers, the handle)
+int wr::beam_tdt_body(wr_decoder *h, const float *enc_out_d, const int32_t *enc_lens_d, const float *ctc_logp_d, int B, int T,
+                      int beam, float ctc_weight, float transducer_weight, int blank, const TdtDur &dur, int32_t *hyps_d,
+                      int32_t *hyp_lens_d, double *scores_d, int32_t *n_hyps_d, void *stream)
+{
+    const char *what = "prefix_beam_search_tdt";
+    WR_REQUIRE(beam >= 1 && beam <= h->max_beam, WR_EINVAL, "%s: beam=%d lies outside [1, %d], the decoder's max", what, beam,
+               h->max_beam);
+    WR_REQUIRE(B > 0 && B <= h->max_utt && (long)B * beam <= h->d.NL, WR_EINVAL, "%s: B*beam=%ld exceeds the decoder's capacity",
+               what, (long)B * beam);
+    WR_REQUIRE(T > 0 && T <= h->Tmax, WR_EINVAL, "%s: T=%d exceeds the decoder's Tmax=%d", what, T, h->Tmax);
+    const int V = h->d.V - dur.D;                  // token columns of the joiner's row
+    WR_REQUIRE(V >= 2, WR_EINVAL, "%s: the joiner has %d outputs, D=%d durations leave %d token columns (2 or more are needed)",
+               what, h->d.V, dur.D, V);
+    WR_REQUIRE(blank >= 0 && blank < V, WR_EINVAL, "%s: blank %d out of range [0,%d)", what, blank, V);
+    WR_REQUIRE(h->d.Ve >= V, WR_EINVAL, "%s: the embedding table has %d rows, the token vocabulary %d", what, h->d.Ve, V);
+    WR_REQUIRE(ctc_logp_d || (ctc_weight == 0.f && transducer_weight == 1.f), WR_EINVAL,
+               "%s: no CTC posterior, so (ctc_weight, transducer_weight) must be (0, 1), got (%g, %g)", what, (double)ctc_weight,
+               (double)transducer_weight);
+    h->stream_lanes = -1;                         // the lanes' streaming state (caches, tokens) is overwritten
+    WorkScope scope(h, static_cast<hipStream_t>(stream));
+    hipStream_t st = scope.st;
+    DevState &s = h->host;
+    s.enc = enc_out_d; s.enc_lens = enc_lens_d; s.ctc_logp = ctc_logp_d;
+    s.n_utt = B; s.T = T; s.lanes_per_utt = beam; s.n_lanes = B * beam;
+    s.beam = beam; s.ctc_weight = ctc_weight; s.tr_weight = transducer_weight; s.blank = blank;
+    s.Lmax = h->Tmax + 1;
+    s.tdt_durs = pack_durations(dur); s.tdt_D = dur.D; s.hyp_frames = nullptr;
+    if (int rc = upload_state(h, st)) return rc;
+    (void)hipMemsetAsync(s.lane_active, 0, sizeof(int32_t) * h->d.NLp, st);
+    const int NLn = B * beam;
+    WR_TRY(launch_ep_all(h, st, (long)B * T, enc_out_d, s.ep_all));
+    WR_TRY(launch("beam_init_kernel", beam_init_kernel, dim3(NLn), dim3(128), 0, st, h->dev));
+    WR_TRY(launch("tdt_beam_begin_kernel", tdt_beam_begin_kernel, dim3(1), dim3(256), 0, st, h->dev));
+    // every step moves the earliest frame of every running utterance on, so T steps always suffice
+    WR_TRY(run_until_idle(
+        h, st, what, NLn * 1000 + beam, (long)T + 1, "", [&]() -> GraphSlot & { return h->beam_tdt; },
+        [&] { return tdt_beam_step(h, NLn, B, st); }, [] {}));
+    WR_TRY(launch("beam_export_kernel", beam_export_kernel, dim3(B), dim3(256), 0, st, h->dev, hyps_d, hyp_lens_d, scores_d, n_hyps_d));
+    scope.ok();
+    return WR_OK;
 }
 
 extern "C" int wr_greedy_search(wr_decoder *h, const float *enc_out_d, const int32_t *enc_lens_d, int N, int T, int n_steps,

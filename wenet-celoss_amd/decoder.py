@@ -172,6 +172,14 @@ class DeviceDecoder:
         depend on it."""
         _lib.check(self._lib.wr_decoder_set_lookahead(self._h, int(frames)), "wr_decoder_set_lookahead")
 
+    def last_counters(self) -> Tuple[int, int, int]:
+        """The three counters the last polling search read back (`wr_decoder_last_counters`): greedy searches (lanes
+        still active, blank decisions, emissions); TDT prefix beam search (utterances still running, steps taken summed
+        over the utterances, hypotheses expanded)."""
+        out = (ctypes.c_int32 * 3)()
+        _lib.check(self._lib.wr_decoder_last_counters(self._h, out), "wr_decoder_last_counters")
+        return tuple(out)
+
     def greedy(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, n_steps: int = 64, blank: int = 0
                ) -> List[List[int]]:
         """encoder_out (N, T, E); returns one token list per stream."""
@@ -244,6 +252,28 @@ class DeviceDecoder:
         for b in range(B):
             out.append([(hyps[b, e, :hl[b][e]].tolist(), sc[b][e]) for e in range(nh[b])])
         return out
+
+    def prefix_beam_tdt(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, durations, beam_size: int,
+                        blank: int = 0, ctc_logp: torch.Tensor = None, ctc_weight: float = 0.0,
+                        transducer_weight: float = 1.0) -> List[List[Tuple[List[int], float]]]:
+        """Prefix beam search of a token-and-duration model (`wr_prefix_beam_search_tdt`): the joiner's row is its width
+        minus len(durations) token logits followed by one logit per duration.  encoder_out (B, T, E); ctc_logp (B, T, V)
+        over the token vocabulary or None (then the weights must be (0, 1)).  Per utterance: [(hyp incl. seed blank,
+        score)] best first.  `set_graph` applies; the result does not depend on it."""
+        enc = _f32(encoder_out)
+        ctc = None if ctc_logp is None else _f32(ctc_logp)
+        B, T, _ = enc.shape
+        lens = encoder_out_lens.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+        durs = (ctypes.c_int32 * max(len(durations), 1))(*[int(d) for d in durations])
+        lmax = self.tmax + 1
+        hyps = torch.empty(B, beam_size, lmax, dtype=torch.int32, device=self.device)
+        hl = torch.empty(B, beam_size, dtype=torch.int32, device=self.device)
+        sc = torch.empty(B, beam_size, dtype=torch.float64, device=self.device)
+        nh = torch.empty(B, dtype=torch.int32, device=self.device)
+        self._call("wr_prefix_beam_search_tdt", enc, lens, ctc, B, T, int(beam_size), float(ctc_weight),
+                   float(transducer_weight), int(blank), durs, len(durations), hyps, hl, sc, nh)
+        hyps, hl, sc, nh = hyps.cpu(), hl.cpu().tolist(), sc.cpu().tolist(), nh.cpu().tolist()
+        return [[(hyps[b, e, :hl[b][e]].tolist(), sc[b][e]) for e in range(nh[b])] for b in range(B)]
 
     def predictor_step(self, tokens: torch.Tensor, cache_h: torch.Tensor, cache_c: torch.Tensor):
         """tokens (N,), cache (L, N, H) -> out (N, P), new_h, new_c (L, N, H)."""

@@ -27,6 +27,34 @@ class Sequence:
         self.cache = cache
 
 
+def tdt_prefix_beam_search(model: torch.nn.Module, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor,
+                           beam_size: int = 5, ctc_weight: float = 0.0, transducer_weight: float = 1.0
+                           ) -> List[List[Sequence]]:
+    """Prefix beam search of a token-and-duration model (`model.tdt_durations`; the joiner's row is `vocab_size` token
+    logits followed by one logit per duration) for any number of utterances, with the whole search on the device
+    (`wr_prefix_beam_search_tdt`; the rule is in include/wr_api.h, "TDT prefix beam search").  A hypothesis stands at a
+    frame of its own; each step expands those at the earliest frame with their best `beam_size` (token, duration) pairs,
+    the others wait; hypotheses with equal tokens at an equal frame fuse with float64 log_add.
+
+    encoder_out (B, T, E), encoder_out_lens scalar or (B,) -> per utterance the pruned beam, best first, each hypothesis
+    beginning with the seed blank.  The CTC posterior (`model.ctc`) is computed and mixed in only when
+    (ctc_weight, transducer_weight) != (0, 1)."""
+    from .greedy_search import _decoder_cache
+    B, T, _ = encoder_out.shape
+    lens = torch.as_tensor(encoder_out_lens).reshape(-1)
+    if lens.numel() == 1 and B > 1:
+        lens = lens.expand(B)
+    ctc_logp = None
+    if (float(ctc_weight), float(transducer_weight)) != (0.0, 1.0):
+        with torch.no_grad():
+            ctc_logp = model.ctc.log_softmax(encoder_out)                # (B, T, V), ctc.py:66-75
+    dec = _decoder_cache(model).get(model.predictor, model.joint, lanes=B * beam_size, utts=B, tmax=T, max_hyp=0,
+                                    beam=beam_size)
+    res = dec.prefix_beam_tdt(encoder_out, lens, model.tdt_durations, beam_size, model.blank, ctc_logp=ctc_logp,
+                              ctc_weight=ctc_weight, transducer_weight=transducer_weight)
+    return [[Sequence(hyp=h, score=s, cache=None) for h, s in utt] for utt in res]
+
+
 class PrefixBeamSearch:
     def __init__(self, encoder, predictor, joint, ctc, blank):
         self.encoder = encoder

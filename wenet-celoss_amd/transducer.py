@@ -42,7 +42,7 @@ from .rnnt_pruned import rnnt_loss_pruned
 from .rnnt_tdt import check_tdt, rnnt_tdt_forced_align, rnnt_tdt_loss
 from .search.greedy_search import (basic_greedy_search, basic_greedy_search_both, basic_greedy_search_hw,
                                    tdt_greedy_search)
-from .search.prefix_beam_search import PrefixBeamSearch
+from .search.prefix_beam_search import PrefixBeamSearch, tdt_prefix_beam_search
 
 
 def _output_width(module: nn.Module, role: str, joint: nn.Module, joint_ffn: str) -> int:
@@ -792,6 +792,90 @@ class Transducer(nn.Module):
         encoder_out, encoder_mask = self.encoder(speech, speech_lengths, decoding_chunk_size, num_decoding_left_chunks)
         return tdt_greedy_search(self, encoder_out, encoder_mask.squeeze(1).sum(1), n_steps=n_steps,
                                  return_frames=return_frames)
+
+    # ---------------------------------------------- token-and-duration prefix beam search --
+    def _tdt_beam(self, what: str, speech: torch.Tensor, speech_lengths: torch.Tensor, decoding_chunk_size: int,
+                  beam_size: int, num_decoding_left_chunks: int, simulate_streaming: bool, ctc_weight: float,
+                  transducer_weight: float):
+        """Encoder + `tdt_prefix_beam_search` -> (per utterance the n-best, encoder_out, encoder_mask)."""
+        if not self._is_tdt():
+            plain = {"tdt_attention_rescoring": "transducer_attention_rescoring"}.get(what, what[len("tdt_"):])
+            raise ValueError(f"Transducer.{what}: the model has no tdt_durations (use {plain})")
+        assert speech.shape[0] == speech_lengths.shape[0]
+        assert decoding_chunk_size != 0
+        encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
+                                                          num_decoding_left_chunks, simulate_streaming)
+        nbest = tdt_prefix_beam_search(self, encoder_out, encoder_mask.squeeze(1).sum(1), beam_size=beam_size,
+                                       ctc_weight=ctc_weight, transducer_weight=transducer_weight)
+        return nbest, encoder_out, encoder_mask
+
+    def tdt_beam_search(self, speech: torch.Tensor, speech_lengths: torch.Tensor, decoding_chunk_size: int = -1,
+                        beam_size: int = 5, num_decoding_left_chunks: int = -1, simulate_streaming: bool = False,
+                        ctc_weight: float = 0.0, transducer_weight: float = 1.0, **_ignored):
+        """`beam_search` for a token-and-duration model -> (best hypothesis without the seed blank, its score).  The
+        search is `tdt_prefix_beam_search`.  The defaults are (0, 1), not `beam_search`'s 0.3 / 0.7: a hypothesis
+        that jumps `d` frames is scored with the CTC posterior of the frame it stands at only, and that posterior says
+        nothing about the frames the jump skips, so the mixture is opt-in."""
+        assert speech.shape[0] == 1
+        nbest, _, _ = self._tdt_beam("tdt_beam_search", speech, speech_lengths, decoding_chunk_size, beam_size,
+                                     num_decoding_left_chunks, simulate_streaming, ctc_weight, transducer_weight)
+        return nbest[0][0].hyp[1:], nbest[0][0].score
+
+    def tdt_beam_search_batch(self, speech: torch.Tensor, speech_lengths: torch.Tensor, decoding_chunk_size: int = -1,
+                              beam_size: int = 5, num_decoding_left_chunks: int = -1, simulate_streaming: bool = False,
+                              ctc_weight: float = 0.0, transducer_weight: float = 1.0):
+        """Extension: the n-best of every utterance of a batch -> per utterance [(hypothesis without the seed blank,
+        score)], best first."""
+        nbest, _, _ = self._tdt_beam("tdt_beam_search_batch", speech, speech_lengths, decoding_chunk_size, beam_size,
+                                     num_decoding_left_chunks, simulate_streaming, ctc_weight, transducer_weight)
+        return [[(s.hyp[1:], s.score) for s in utt] for utt in nbest]
+
+    def _cal_tdt_score(self, encoder_out: torch.Tensor, encoder_mask: torch.Tensor, hyps_lens: torch.Tensor,
+                       hyps_pad: torch.Tensor):
+        """-rnnt_tdt_loss(reduction='none') per hypothesis, with the model's durations and sigma: `_cal_transducer_score`
+        for a token-and-duration model."""
+        hyps_pad_blank = add_blank(hyps_pad, self.blank, self.ignore_id)
+        xs_in_lens = encoder_mask.squeeze(1).sum(1).int()
+        predictor_out = self.predictor(hyps_pad_blank)
+        rnnt_text = hyps_pad.to(torch.int64)
+        rnnt_text = torch.where(rnnt_text == self.ignore_id, 0, rnnt_text).to(torch.int32)
+        joint_out = self.joint(encoder_out, predictor_out)
+        loss_td = rnnt_tdt_loss(joint_out, rnnt_text.contiguous(), xs_in_lens.contiguous(), hyps_lens.int().contiguous(),
+                                self.tdt_durations, blank=self.blank, sigma=self.tdt_sigma, reduction="none")
+        return loss_td * -1
+
+    def tdt_attention_rescoring(self, speech: torch.Tensor, speech_lengths: torch.Tensor, beam_size: int,
+                                decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1,
+                                simulate_streaming: bool = False, reverse_weight: float = 0.0, ctc_weight: float = 0.0,
+                                attn_weight: float = 0.0, transducer_weight: float = 0.0, search_ctc_weight: float = 1.0,
+                                search_transducer_weight: float = 0.0):
+        """`transducer_attention_rescoring` for a token-and-duration model: the n-best of `tdt_prefix_beam_search`
+        (searched with search_ctc_weight / search_transducer_weight) rescored as
+        att * attn_weight + beam score * ctc_weight + td_score * transducer_weight, td_score from `_cal_tdt_score`
+        -> (best hypothesis, its score)."""
+        if reverse_weight > 0.0:
+            assert hasattr(self.decoder, "right_decoder")
+        device = speech.device
+        assert speech.shape[0] == 1
+        nbest, encoder_out, _ = self._tdt_beam("tdt_attention_rescoring", speech, speech_lengths, decoding_chunk_size,
+                                               beam_size, num_decoding_left_chunks, simulate_streaming, search_ctc_weight,
+                                               search_transducer_weight)
+        beam_score = [s.score for s in nbest[0]]
+        hyps = [s.hyp[1:] for s in nbest[0]]
+        n = len(hyps)                                       # a short utterance may have fewer than beam_size hypotheses
+        hyps_pad = pad_sequence([torch.tensor(h, device=device, dtype=torch.long) for h in hyps], True, self.ignore_id)
+        hyps_lens = torch.tensor([len(h) for h in hyps], device=device, dtype=torch.long)
+        encoder_out = encoder_out.repeat(n, 1, 1)
+        encoder_mask = torch.ones(n, 1, encoder_out.size(1), dtype=torch.bool, device=device)
+        td_score = self._cal_tdt_score(encoder_out, encoder_mask, hyps_lens, hyps_pad)
+        decoder_out, r_decoder_out = self._cal_attn_score(encoder_out, encoder_mask, hyps_pad, hyps_lens)
+        att = self._attention_scores(hyps, decoder_out, r_decoder_out, reverse_weight)
+        best_score, best_index = -float("inf"), 0
+        for i in range(n):
+            score = att[i] * attn_weight + beam_score[i] * ctc_weight + td_score[i] * transducer_weight
+            if score > best_score:
+                best_score, best_index = score, i
+        return hyps[best_index], best_score
 
     # ------------------------------------- streaming greedy ("transducer ref.py":541-606) --
     def reset_cache(self, n_streams: int = 1, chunk_frames: int = 64, n_steps: int = 64) -> None:
