@@ -11,6 +11,7 @@ from typing import List, Tuple
 import torch
 
 from . import _lib
+from .rnnt_tdt import _durations_arg
 
 
 def _f32(t: torch.Tensor) -> torch.Tensor:
@@ -180,19 +181,30 @@ class DeviceDecoder:
         _lib.check(self._lib.wr_decoder_last_counters(self._h, out), "wr_decoder_last_counters")
         return tuple(out)
 
-    def greedy(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, n_steps: int = 64, blank: int = 0
-               ) -> List[List[int]]:
-        """encoder_out (N, T, E); returns one token list per stream."""
+    def _greedy(self, name: str, encoder_out, lens, *args, frames=None):
+        """The frame of the greedy searches: `name`(encoder_out (N, T, E) as fp32, lens (N,) int32, N, T, *args, tokens,
+        token counts[, frames -- entry points that take that pointer say `frames` True or False]) -> one token list per
+        stream; with `frames` also the list of the frames the entry point reported for them."""
         enc = _f32(encoder_out)
         N, T, _ = enc.shape
-        lens = encoder_out_lens.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+        lens = lens.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
         hyps = torch.empty(N, max(self.max_hyp, 1), dtype=torch.int32, device=self.device)
+        fr = torch.empty_like(hyps) if frames else None
         hl = torch.empty(N, dtype=torch.int32, device=self.device)
-        self._call("wr_greedy_search", enc, lens, N, T, int(n_steps), int(blank), hyps, hl)
+        self._call(name, enc, lens, N, T, *args, hyps, hl, *(() if frames is None else (fr,)))
         hl_c, hy_c = hl.cpu().tolist(), hyps.cpu()
         if max(hl_c, default=0) > self.max_hyp:
             raise RuntimeError(f"greedy search produced {max(hl_c)} tokens but the decoder was sized for {self.max_hyp}")
-        return [hy_c[i, :hl_c[i]].tolist() for i in range(N)]
+        toks = [hy_c[i, :hl_c[i]].tolist() for i in range(N)]
+        if not frames:
+            return toks
+        fr_c = fr.cpu()
+        return toks, [fr_c[i, :hl_c[i]].tolist() for i in range(N)]
+
+    def greedy(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, n_steps: int = 64, blank: int = 0
+               ) -> List[List[int]]:
+        """encoder_out (N, T, E); returns one token list per stream."""
+        return self._greedy("wr_greedy_search", encoder_out, encoder_out_lens, int(n_steps), int(blank))
 
     def greedy_tdt(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, durations, n_steps: int = 64,
                    blank: int = 0, return_frames: bool = False):
@@ -200,58 +212,37 @@ class DeviceDecoder:
         len(durations) token logits followed by one logit per duration.  encoder_out (N, T, E) -> one token list per
         stream; with `return_frames` also the frame at which each token was emitted.  `set_graph` and `set_lookahead`
         apply; tokens and frames do not depend on them."""
-        enc = _f32(encoder_out)
-        N, T, _ = enc.shape
-        lens = encoder_out_lens.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
-        durs = (ctypes.c_int32 * max(len(durations), 1))(*[int(d) for d in durations])
-        hyps = torch.empty(N, max(self.max_hyp, 1), dtype=torch.int32, device=self.device)
-        frames = torch.empty_like(hyps) if return_frames else None
-        hl = torch.empty(N, dtype=torch.int32, device=self.device)
-        self._call("wr_greedy_search_tdt", enc, lens, N, T, int(n_steps), int(blank), durs, len(durations), hyps, hl, frames)
-        hl_c, hy_c = hl.cpu().tolist(), hyps.cpu()
-        if max(hl_c, default=0) > self.max_hyp:
-            raise RuntimeError(f"greedy search produced {max(hl_c)} tokens but the decoder was sized for {self.max_hyp}")
-        toks = [hy_c[i, :hl_c[i]].tolist() for i in range(N)]
-        if not return_frames:
-            return toks
-        fr_c = frames.cpu()
-        return toks, [fr_c[i, :hl_c[i]].tolist() for i in range(N)]
+        return self._greedy("wr_greedy_search_tdt", encoder_out, encoder_out_lens, int(n_steps), int(blank),
+                            _durations_arg(durations), len(durations), frames=bool(return_frames))
 
     def greedy_chunk(self, encoder_chunk: torch.Tensor, chunk_lens: torch.Tensor, n_steps: int = 64, blank: int = 0,
                      reset: bool = False, reference_new_cache: bool = True) -> List[List[int]]:
         """Streaming greedy search: tokens emitted in this chunk for each stream (state carries over)."""
-        enc = _f32(encoder_chunk)
-        N, T, _ = enc.shape
-        lens = chunk_lens.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
-        hyps = torch.empty(N, max(self.max_hyp, 1), dtype=torch.int32, device=self.device)
-        hl = torch.empty(N, dtype=torch.int32, device=self.device)
-        self._call("wr_greedy_search_chunk", enc, lens, N, T, int(n_steps), int(blank), int(reset), int(reference_new_cache),
-                   hyps, hl)
-        hl_c, hy_c = hl.cpu().tolist(), hyps.cpu()
-        if max(hl_c, default=0) > self.max_hyp:
-            raise RuntimeError(f"greedy search produced {max(hl_c)} tokens but the decoder was sized for {self.max_hyp}")
-        return [hy_c[i, :hl_c[i]].tolist() for i in range(N)]
+        return self._greedy("wr_greedy_search_chunk", encoder_chunk, chunk_lens, int(n_steps), int(blank), int(reset),
+                            int(reference_new_cache))
 
-    def prefix_beam(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, ctc_logp: torch.Tensor,
-                    beam_size: int, ctc_weight: float, transducer_weight: float, blank: int = 0
-                    ) -> List[List[Tuple[List[int], float]]]:
-        """encoder_out (B, T, E), ctc_logp (B, T, V).  Per utterance: [(hyp incl. seed blank, score)] best first."""
+    def _beam(self, name: str, encoder_out, lens, ctc_logp, beam_size: int, *args) -> List[List[Tuple[List[int], float]]]:
+        """The frame of the prefix beam searches: `name`(encoder_out (B, T, E) and ctc_logp (B, T, V) or None as fp32,
+        lens (B,) int32, B, T, beam_size, *args, then the n-best buffers) -> per utterance [(hyp, score)] best first."""
         enc = _f32(encoder_out)
-        ctc = _f32(ctc_logp)
+        ctc = None if ctc_logp is None else _f32(ctc_logp)
         B, T, _ = enc.shape
-        lens = encoder_out_lens.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+        lens = lens.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
         lmax = self.tmax + 1
         hyps = torch.empty(B, beam_size, lmax, dtype=torch.int32, device=self.device)
         hl = torch.empty(B, beam_size, dtype=torch.int32, device=self.device)
         sc = torch.empty(B, beam_size, dtype=torch.float64, device=self.device)
         nh = torch.empty(B, dtype=torch.int32, device=self.device)
-        self._call("wr_prefix_beam_search", enc, lens, ctc, B, T, int(beam_size), float(ctc_weight), float(transducer_weight),
-                   int(blank), hyps, hl, sc, nh)
+        self._call(name, enc, lens, ctc, B, T, int(beam_size), *args, hyps, hl, sc, nh)
         hyps, hl, sc, nh = hyps.cpu(), hl.cpu().tolist(), sc.cpu().tolist(), nh.cpu().tolist()
-        out = []
-        for b in range(B):
-            out.append([(hyps[b, e, :hl[b][e]].tolist(), sc[b][e]) for e in range(nh[b])])
-        return out
+        return [[(hyps[b, e, :hl[b][e]].tolist(), sc[b][e]) for e in range(nh[b])] for b in range(B)]
+
+    def prefix_beam(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, ctc_logp: torch.Tensor,
+                    beam_size: int, ctc_weight: float, transducer_weight: float, blank: int = 0
+                    ) -> List[List[Tuple[List[int], float]]]:
+        """encoder_out (B, T, E), ctc_logp (B, T, V).  Per utterance: [(hyp incl. seed blank, score)] best first."""
+        return self._beam("wr_prefix_beam_search", encoder_out, encoder_out_lens, ctc_logp, beam_size, float(ctc_weight),
+                          float(transducer_weight), int(blank))
 
     def prefix_beam_tdt(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, durations, beam_size: int,
                         blank: int = 0, ctc_logp: torch.Tensor = None, ctc_weight: float = 0.0,
@@ -260,20 +251,8 @@ class DeviceDecoder:
         minus len(durations) token logits followed by one logit per duration.  encoder_out (B, T, E); ctc_logp (B, T, V)
         over the token vocabulary or None (then the weights must be (0, 1)).  Per utterance: [(hyp incl. seed blank,
         score)] best first.  `set_graph` applies; the result does not depend on it."""
-        enc = _f32(encoder_out)
-        ctc = None if ctc_logp is None else _f32(ctc_logp)
-        B, T, _ = enc.shape
-        lens = encoder_out_lens.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
-        durs = (ctypes.c_int32 * max(len(durations), 1))(*[int(d) for d in durations])
-        lmax = self.tmax + 1
-        hyps = torch.empty(B, beam_size, lmax, dtype=torch.int32, device=self.device)
-        hl = torch.empty(B, beam_size, dtype=torch.int32, device=self.device)
-        sc = torch.empty(B, beam_size, dtype=torch.float64, device=self.device)
-        nh = torch.empty(B, dtype=torch.int32, device=self.device)
-        self._call("wr_prefix_beam_search_tdt", enc, lens, ctc, B, T, int(beam_size), float(ctc_weight),
-                   float(transducer_weight), int(blank), durs, len(durations), hyps, hl, sc, nh)
-        hyps, hl, sc, nh = hyps.cpu(), hl.cpu().tolist(), sc.cpu().tolist(), nh.cpu().tolist()
-        return [[(hyps[b, e, :hl[b][e]].tolist(), sc[b][e]) for e in range(nh[b])] for b in range(B)]
+        return self._beam("wr_prefix_beam_search_tdt", encoder_out, encoder_out_lens, ctc_logp, beam_size, float(ctc_weight),
+                          float(transducer_weight), int(blank), _durations_arg(durations), len(durations))
 
     def predictor_step(self, tokens: torch.Tensor, cache_h: torch.Tensor, cache_c: torch.Tensor):
         """tokens (N,), cache (L, N, H) -> out (N, P), new_h, new_c (L, N, H)."""

@@ -16,17 +16,18 @@ logits gradient to `joint.joint_backward`, whose dispatch is the table in `joint
 Results: costs and every gradient agree with the unfused path to fp32 rounding of the row log-sum-exp (the
 statistics are merged in a different order); tests/test_fused_gpu.py states the tolerance (1e-6 relative on costs).
 
-Memory-bounded mode (`logits_budget`, `_JointRnntBoundedFn`): no logits tensor at all.  The forward keeps only the row
+Memory-bounded mode (`logits_budget`, `_JointBoundedFn`): no logits tensor at all.  The forward keeps only the row
 statistics (`wr_joint_rnnt_stats`: the joiner forward with a statistics-only epilogue) and runs the lattice sweeps
 (`wr_rnnt_loss_sweeps`); the backward walks the lattice in slices (`plan_slices`) and, per slice, recomputes the logits
 tile by tile and turns them into the loss gradient in the same kernel's epilogue (`wr_joint_rnnt_grad`), then runs the
 joiner backward on that slice.  One extra joiner forward's matrix work buys a footprint that does not grow with the batch
-("The memory-bounded loss block").  `joint_rnnt_tdt_loss` / `_JointTdtBoundedFn` is the same node for the
-token-and-duration loss ("The memory-bounded TDT loss block").
+("The memory-bounded loss block").  `joint_rnnt_tdt_loss` is the same node with the token-and-duration loss
+(`_TdtLoss` in the place of `_RnntLoss`; DESIGN.md, "The memory-bounded TDT loss block").
 """
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
 from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
@@ -34,7 +35,8 @@ import torch
 
 from . import _lib
 from .joint import _PRECISIONS, _call_precision, activation_code, joiner_workspace, joint_backward, joint_forward
-from .rnnt_loss import check_latency
+from .rnnt_lattice import reducer
+from .rnnt_loss import call_regularised, check_latency, loss_backward, loss_forward
 from .rnnt_tdt import _check_blank, _durations_arg, check_tdt
 
 
@@ -61,19 +63,11 @@ class _JointRnntFn(torch.autograd.Function):
         epi = os.environ.get("WR_FUSED_LSE_EPILOGUE")
         epilogue = (terms != 0) if epi is None else (epi == "1")
         joint_forward(ep, pp, w, b, llens, tlens, terms, act, out=logits, stats=(targets, blank, rws) if epilogue else None)
-        if pen != 0.0:             # the delay penalty goes into the stored label arcs before the sweeps
-            if epilogue:
-                _lib.call("wr_rnnt_loss_fwd_from_lse_lattice", logits, targets, llens, tlens, B, T, U1, V, blank, 0, pen,
-                          costs, rws, rws.numel(), device=dev)
-            else:
-                _lib.call("wr_rnnt_loss_fwd_lattice", logits, _lib.WR_F32, targets, llens, tlens, B, T, U1, V, blank, 0, pen,
-                          costs, rws, rws.numel(), device=dev)
-        elif epilogue:
-            _lib.call("wr_rnnt_loss_fwd_from_lse", logits, targets, llens, tlens, B, T, U1, V, blank, costs, rws, rws.numel(),
-                      device=dev)
+        if epilogue:               # a delay penalty goes into the stored label arcs before the sweeps
+            call_regularised("wr_rnnt_loss_fwd_from_lse", (logits, targets, llens, tlens, B, T, U1, V, blank),
+                             (costs, rws, rws.numel()), pen, device=dev)
         else:
-            _lib.call("wr_rnnt_loss_fwd", logits, _lib.WR_F32, targets, llens, tlens, B, T, U1, V, blank, costs, rws,
-                      rws.numel(), device=dev)
+            loss_forward(logits, targets, llens, tlens, blank, pen, costs, rws)
         ctx.save_for_backward(ep, pp, w, b, targets, llens, tlens, logits, rws)
         ctx.blank, ctx.clamp, ctx.terms, ctx.act, ctx.lam, ctx.pen = blank, clamp, terms, act, lam, pen
         ctx.logits_hold_gradient = False
@@ -83,8 +77,6 @@ class _JointRnntFn(torch.autograd.Function):
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_costs):
         ep, pp, w, b, targets, llens, tlens, logits, rws = ctx.saved_tensors
-        B, T, U1, V = logits.shape
-        dev = logits.device
         gc = grad_costs.to(torch.float32).contiguous()
         if ctx.logits_hold_gradient:
             # A second backward through a retained graph (retain_graph=True, per-loss torch.autograd.grad) finds the
@@ -101,12 +93,7 @@ class _JointRnntFn(torch.autograd.Function):
         # 32-utterance step).  WR_FUSED_INPLACE_BYTES=n keeps a separate buffer below n bytes.
         inplace = logits.numel() * logits.element_size() >= int(os.environ.get("WR_FUSED_INPLACE_BYTES", "0"))
         grads = logits if inplace else torch.empty_like(logits)
-        if ctx.lam == 0.0 and ctx.pen == 0.0:
-            _lib.call("wr_rnnt_loss_bwd", logits, _lib.WR_F32, targets, llens, tlens, B, T, U1, V, ctx.blank, float(ctx.clamp),
-                      gc, grads, rws, rws.numel(), device=dev)
-        else:
-            _lib.call("wr_rnnt_loss_bwd_lattice", logits, _lib.WR_F32, targets, llens, tlens, B, T, U1, V, ctx.blank,
-                      float(ctx.clamp), 0, ctx.pen, ctx.lam, gc, grads, rws, rws.numel(), device=dev)
+        loss_backward(logits, targets, llens, tlens, ctx.blank, ctx.clamp, ctx.lam, ctx.pen, gc, grads, rws)
         ctx.logits_hold_gradient = inplace
         d_ep, d_pp, d_w, d_b = joint_backward(grads, ep, pp, w, llens, tlens, ctx.terms, ctx.needs_input_grad[2],
                                               ctx.needs_input_grad[3], gout_zero_in_padding=True, act=ctx.act)
@@ -162,79 +149,120 @@ def plan_slices(t_lens, u_lens, T: int, U1: int, V: int, budget_bytes: int) -> L
     return slices
 
 
-class _JointRnntBoundedFn(torch.autograd.Function):
-    """Joiner + RNN-T loss with no logits tensor (joint_rnnt_loss(..., logits_budget=n)).  Saves ep, pp, w, b, the lengths
-    and the RNN-T workspace; `slices` (plan_slices) and the host lengths come from the caller's one length sync."""
+# What the memory-bounded node asks of its loss.  `head` is (ep, pp, w, b, llens, tlens, targets) and `dims`
+# (B, T, U1, J, row width) throughout: the arguments every joiner + loss entry point begins with.
+@dataclass(frozen=True)
+class _RnntLoss:
+    """The RNN-T loss in the memory-bounded node: rows of V logits, a joiner of `terms`."""
+    blank: int
+    clamp: float
+    terms: int
+    lam: float
+    pen: float
+    what = "joint_rnnt_loss"
+
+    def workspace(self, B, T, U1, dev):
+        return _lib.workspace("wr_rnnt_workspace_bytes", B, T, U1, device=dev)
+
+    def forward(self, head, dims, act, ws, lws, costs, dev):
+        """Row statistics into the loss workspace `lws`, then the lattice sweeps into `costs`."""
+        _lib.call("wr_joint_rnnt_stats", *head, *dims, act, self.blank, self.terms, ws, ws.numel(), lws, lws.numel(),
+                  device=dev)
+        call_regularised("wr_rnnt_loss_sweeps", (head[4], head[5], *dims[:3]), (costs, lws, lws.numel()), self.pen, device=dev)
+
+    def grad(self, head, dims, act, gc, lws, begin, end, g, ws, w_ready, dev):
+        """The loss gradient of the recomputed logits of lattice cells [begin, end) into `g`."""
+        call_regularised("wr_joint_rnnt_grad", (*head, *dims, act, self.blank, float(self.clamp), self.terms),
+                         (gc, lws, lws.numel(), begin, end, g, ws, ws.numel(), w_ready), self.pen, self.lam, device=dev)
+
+
+@dataclass(frozen=True)
+class _TdtLoss:
+    """The token-and-duration loss in the memory-bounded node: rows of W = V + D logits, the exact fp32 joiner only.
+    `durs` is the durations as the library takes them (`_durations_arg`), built once per call of the public function."""
+    blank: int
+    durs: object
+    D: int
+    sigma: float
+    terms = 0
+    what = "joint_rnnt_tdt_loss"
+
+    def workspace(self, B, T, U1, dev):
+        return _lib.workspace("wr_rnnt_tdt_workspace_bytes", B, T, U1, self.D, device=dev)
+
+    def forward(self, head, dims, act, ws, lws, costs, dev):
+        _lib.call("wr_joint_tdt_stats", *head, *dims, act, self.blank, self.durs, self.D, self.sigma, ws, ws.numel(), lws,
+                  lws.numel(), device=dev)
+        _lib.call("wr_rnnt_tdt_sweeps", head[4], head[5], *dims[:3], self.durs, self.D, costs, lws, lws.numel(), device=dev)
+
+    def grad(self, head, dims, act, gc, lws, begin, end, g, ws, w_ready, dev):
+        _lib.call("wr_joint_tdt_grad", *head, *dims, act, self.blank, self.durs, self.D, self.sigma, gc, lws, lws.numel(),
+                  begin, end, g, ws, ws.numel(), w_ready, device=dev)
+
+
+class _JointBoundedFn(torch.autograd.Function):
+    """Joiner + loss with no logits tensor (joint_rnnt_loss(..., logits_budget=n) with an `_RnntLoss`, joint_rnnt_tdt_loss
+    with a `_TdtLoss`).  Saves ep, pp, w, b, the lengths and the loss's workspace; `slices` (plan_slices) and the host
+    lengths come from the caller's one length sync."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, ep, pp, w, b, targets, llens, tlens, blank, clamp, terms, act, slices, host_t, host_u, lam=0.0, pen=0.0):
+    def forward(ctx, ep, pp, w, b, targets, llens, tlens, loss, act, slices, host_t, host_u):
         if not ep.is_cuda:
-            raise RuntimeError("wenet_celoss_amd.joint_rnnt_loss: tensors must live on a HIP device "
+            raise RuntimeError(f"wenet_celoss_amd.{loss.what}: tensors must live on a HIP device "
                                "(this package has no CPU path)")
         B, T, J = ep.shape
         U1 = pp.shape[1]
-        V = w.shape[0]
+        W = w.shape[0]                              # the row width: V, or V + D for the TDT loss
         dev = ep.device
         ep, pp, w, b = ep.contiguous(), pp.contiguous(), w.contiguous(), b.contiguous()
-        rws = _lib.workspace("wr_rnnt_workspace_bytes", B, T, U1, device=dev)
+        lws = loss.workspace(B, T, U1, dev)
         costs = torch.empty(B, dtype=torch.float32, device=dev)
-        ws = joiner_workspace(terms, J, V, dev)
-        _lib.call("wr_joint_rnnt_stats", ep, pp, w, b, llens, tlens, targets, B, T, U1, J, V, act, blank, terms, ws, ws.numel(),
-                  rws, rws.numel(), device=dev)
-        if pen == 0.0:
-            _lib.call("wr_rnnt_loss_sweeps", llens, tlens, B, T, U1, costs, rws, rws.numel(), device=dev)
-        else:
-            _lib.call("wr_rnnt_lattice_sweeps", llens, tlens, B, T, U1, 0, pen, costs, rws, rws.numel(), device=dev)
-        ctx.save_for_backward(ep, pp, w, b, targets, llens, tlens, rws)
+        ws = joiner_workspace(loss.terms, J, W, dev)
+        loss.forward((ep, pp, w, b, llens, tlens, targets), (B, T, U1, J, W), act, ws, lws, costs, dev)
+        ctx.save_for_backward(ep, pp, w, b, targets, llens, tlens, lws)
         ctx.slice_lens = _slice_lengths(slices, host_t, host_u, dev)
-        ctx.slices = slices
-        ctx.blank, ctx.clamp, ctx.terms, ctx.act, ctx.lam, ctx.pen = blank, clamp, terms, act, lam, pen
+        ctx.slices, ctx.loss, ctx.act = slices, loss, act
         return costs
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_costs):
-        ep, pp, w, b, targets, llens, tlens, rws = ctx.saved_tensors
+        ep, pp, w, b, targets, llens, tlens, lws = ctx.saved_tensors
         B, T, J = ep.shape
         U1 = pp.shape[1]
-        V = w.shape[0]
+        W = w.shape[0]
         dev = ep.device
+        loss, act = ctx.loss, ctx.act
         need_w, need_b = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         gc = grad_costs.to(torch.float32).contiguous()
         d_ep = torch.zeros_like(ep)                 # utterances without a slice (no frame) keep zero gradients
         d_pp = torch.zeros_like(pp)
-        d_w = torch.zeros(V, J, dtype=torch.float32, device=dev) if need_w else None
-        d_b = torch.zeros(V, dtype=torch.float32, device=dev) if need_b else None
+        d_w = torch.zeros(W, J, dtype=torch.float32, device=dev) if need_w else None
+        d_b = torch.zeros(W, dtype=torch.float32, device=dev) if need_b else None
+        none = (None,) * 8                          # one per non-tensor input of forward
         slices = ctx.slices
         if not slices:
-            return d_ep, d_pp, d_w, d_b, None, None, None, None, None, None, None, None, None, None, None, None
+            return (d_ep, d_pp, d_w, d_b) + none
         nmax = max(s.cells(U1) for s in slices)
         # buffers sized to the largest slice, allocated once per backward
-        g = torch.empty(nmax * V, dtype=torch.float32, device=dev)
+        g = torch.empty(nmax * W, dtype=torch.float32, device=dev)
         dz = torch.empty(nmax * J, dtype=torch.float32, device=dev)
         h = torch.empty(nmax * J, dtype=torch.float32, device=dev) if need_w else None
-        ws = joiner_workspace(ctx.terms, J, V, dev)
+        ws = joiner_workspace(loss.terms, J, W, dev)
         nl = ctx.slice_lens.numel() // 2
         k = 0
         for i, s in enumerate(slices):
             nb, nt = s.b1 - s.b0, s.t1 - s.t0
             cells = nb * nt * U1
             begin = (s.b0 * T + s.t0) * U1
-            if ctx.lam == 0.0 and ctx.pen == 0.0:
-                _lib.call("wr_joint_rnnt_grad", ep, pp, w, b, llens, tlens, targets, B, T, U1, J, V, ctx.act, ctx.blank,
-                          float(ctx.clamp), ctx.terms, gc, rws, rws.numel(), begin, begin + cells, g, ws, ws.numel(),
-                          int(i > 0), device=dev)
-            else:
-                _lib.call("wr_joint_rnnt_grad_lattice", ep, pp, w, b, llens, tlens, targets, B, T, U1, J, V, ctx.act,
-                          ctx.blank, float(ctx.clamp), ctx.terms, 0, ctx.pen, ctx.lam, gc, rws, rws.numel(), begin,
-                          begin + cells, g, ws, ws.numel(), int(i > 0), device=dev)
+            loss.grad((ep, pp, w, b, llens, tlens, targets), (B, T, U1, J, W), act, gc, lws, begin, begin + cells, g, ws,
+                      int(i > 0), dev)
             ll = ctx.slice_lens[k:k + nb]
             tl = ctx.slice_lens[nl + k:nl + k + nb]
             k += nb
-            de, dp, dw, db = joint_backward(g[:cells * V].view(nb, nt, U1, V), ep[s.b0:s.b1, s.t0:s.t1],
-                                            pp[s.b0:s.b1], w, ll, tl, ctx.terms, need_w, need_b,
-                                            gout_zero_in_padding=True, act=ctx.act,
+            de, dp, dw, db = joint_backward(g[:cells * W].view(nb, nt, U1, W), ep[s.b0:s.b1, s.t0:s.t1], pp[s.b0:s.b1], w,
+                                            ll, tl, loss.terms, need_w, need_b, gout_zero_in_padding=True, act=act,
                                             dz_out=dz[:cells * J].view(nb, nt, U1, J),
                                             h_out=h[:cells * J].view(nb, nt, U1, J) if need_w else None)
             d_ep[s.b0:s.b1, s.t0:s.t1] = de
@@ -243,7 +271,7 @@ class _JointRnntBoundedFn(torch.autograd.Function):
                 d_w += dw
             if need_b:
                 d_b += db
-        return d_ep, d_pp, d_w, d_b, None, None, None, None, None, None, None, None, None, None, None, None
+        return (d_ep, d_pp, d_w, d_b) + none
 
 
 def _slice_lengths(slices, host_t, host_u, dev):
@@ -259,81 +287,26 @@ def _slice_lengths(slices, host_t, host_u, dev):
         return lens.pin_memory().to(dev, non_blocking=True) if lens.numel() else lens.to(dev)
 
 
-class _JointTdtBoundedFn(torch.autograd.Function):
-    """Joiner + TDT loss with no logits tensor (joint_rnnt_tdt_loss): `_JointRnntBoundedFn` for the token-and-duration
-    loss.  The joiner has W = V + D outputs; forward wr_joint_tdt_stats -> wr_rnnt_tdt_sweeps, backward per slice
-    wr_joint_tdt_grad -> the joiner backward.  Exact fp32 only.  Saves ep, pp, w, b, the lengths and the TDT workspace."""
-
-    @staticmethod
-    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, ep, pp, w, b, targets, llens, tlens, blank, durs, sigma, act, slices, host_t, host_u):
-        if not ep.is_cuda:
-            raise RuntimeError("wenet_celoss_amd.joint_rnnt_tdt_loss: tensors must live on a HIP device "
-                               "(this package has no CPU path)")
-        B, T, J = ep.shape
-        U1 = pp.shape[1]
-        W, D = w.shape[0], len(durs)
-        dev = ep.device
-        ep, pp, w, b = ep.contiguous(), pp.contiguous(), w.contiguous(), b.contiguous()
-        tws = _lib.workspace("wr_rnnt_tdt_workspace_bytes", B, T, U1, D, device=dev)
-        costs = torch.empty(B, dtype=torch.float32, device=dev)
-        ws = joiner_workspace(0, J, W, dev)
-        _lib.call("wr_joint_tdt_stats", ep, pp, w, b, llens, tlens, targets, B, T, U1, J, W, act, blank, _durations_arg(durs), D,
-                  sigma, ws, ws.numel(), tws, tws.numel(), device=dev)
-        _lib.call("wr_rnnt_tdt_sweeps", llens, tlens, B, T, U1, _durations_arg(durs), D, costs, tws, tws.numel(), device=dev)
-        ctx.save_for_backward(ep, pp, w, b, targets, llens, tlens, tws)
-        ctx.slice_lens = _slice_lengths(slices, host_t, host_u, dev)
-        ctx.slices = slices
-        ctx.blank, ctx.durs, ctx.sigma, ctx.act = blank, durs, sigma, act
-        return costs
-
-    @staticmethod
-    @torch.amp.custom_bwd(device_type="cuda")
-    def backward(ctx, grad_costs):
-        ep, pp, w, b, targets, llens, tlens, tws = ctx.saved_tensors
-        B, T, J = ep.shape
-        U1 = pp.shape[1]
-        W, D = w.shape[0], len(ctx.durs)
-        dev = ep.device
-        need_w, need_b = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
-        gc = grad_costs.to(torch.float32).contiguous()
-        d_ep = torch.zeros_like(ep)                 # utterances without a slice (no frame) keep zero gradients
-        d_pp = torch.zeros_like(pp)
-        d_w = torch.zeros(W, J, dtype=torch.float32, device=dev) if need_w else None
-        d_b = torch.zeros(W, dtype=torch.float32, device=dev) if need_b else None
-        none = (None,) * 10
-        slices = ctx.slices
-        if not slices:
-            return (d_ep, d_pp, d_w, d_b) + none
-        nmax = max(s.cells(U1) for s in slices)
-        # buffers sized to the largest slice, allocated once per backward
-        g = torch.empty(nmax * W, dtype=torch.float32, device=dev)
-        dz = torch.empty(nmax * J, dtype=torch.float32, device=dev)
-        h = torch.empty(nmax * J, dtype=torch.float32, device=dev) if need_w else None
-        ws = joiner_workspace(0, J, W, dev)
-        durs = _durations_arg(ctx.durs)
-        nl = ctx.slice_lens.numel() // 2
-        k = 0
-        for i, s in enumerate(slices):
-            nb, nt = s.b1 - s.b0, s.t1 - s.t0
-            cells = nb * nt * U1
-            begin = (s.b0 * T + s.t0) * U1
-            _lib.call("wr_joint_tdt_grad", ep, pp, w, b, llens, tlens, targets, B, T, U1, J, W, ctx.act, ctx.blank, durs, D,
-                      ctx.sigma, gc, tws, tws.numel(), begin, begin + cells, g, ws, ws.numel(), int(i > 0), device=dev)
-            ll = ctx.slice_lens[k:k + nb]
-            tl = ctx.slice_lens[nl + k:nl + k + nb]
-            k += nb
-            de, dp, dw, db = joint_backward(g[:cells * W].view(nb, nt, U1, W), ep[s.b0:s.b1, s.t0:s.t1], pp[s.b0:s.b1], w,
-                                            ll, tl, 0, need_w, need_b, gout_zero_in_padding=True, act=ctx.act,
-                                            dz_out=dz[:cells * J].view(nb, nt, U1, J),
-                                            h_out=h[:cells * J].view(nb, nt, U1, J) if need_w else None)
-            d_ep[s.b0:s.b1, s.t0:s.t1] = de
-            d_pp[s.b0:s.b1] += dp
-            if need_w:
-                d_w += dw
-            if need_b:
-                d_b += db
-        return (d_ep, d_pp, d_w, d_b) + none
+def _lengths(what: str, ep, pp, targets, logit_lengths, target_lengths):
+    """The prologue of the two public functions -> (tg, ll, tl, lens): targets, logit_lengths and target_lengths as int32
+    on ep's device, and `lens`, a (2, B) CPU tensor [T_b | U_b] from the one host sync.  Like torchaudio's rnnt_loss it
+    wants max(T_b) == T and max(U_b) + 1 == U1 (RuntimeError)."""
+    dev = ep.device
+    tg = targets.to(device=dev, dtype=torch.int32).contiguous()
+    ll = logit_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    tl = target_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    B, T = ep.shape[0], ep.shape[1]
+    U1 = pp.shape[1]
+    if not (tg.dim() == 2 and tg.shape == (B, U1 - 1) and ll.shape == (B,) and tl.shape == (B,)):
+        raise RuntimeError(f"{what}: targets must be (B, U) and lengths (B,) for ep (B,T,J), pp (B,U+1,J)")
+    lens = torch.stack([ll, tl]).cpu()                      # the one host sync, as in rnnt_loss
+    if int(lens[0].max()) != T:
+        raise RuntimeError("input length mismatch")
+    if int(lens[1].max()) + 1 != U1:
+        raise RuntimeError("output length mismatch")
+    if int(lens.min()) < 0:
+        raise RuntimeError("lengths must be non-negative")
+    return tg, ll, tl, lens
 
 
 def joint_rnnt_tdt_loss(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tensor,
@@ -341,7 +314,7 @@ def joint_rnnt_tdt_loss(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Tensor,
                         durations: Sequence[int], blank: int = 0, sigma: float = 0.0, reduction: str = "mean",
                         activation: str = "tanh", precision: str = "fp32", *, logits_budget: int) -> torch.Tensor:
     """rnnt_tdt_loss(ffn_out(act(ep[:, :, None] + pp[:, None])), targets, logit_lengths, target_lengths, durations) with
-    no logits tensor at all: the memory-bounded node (`_JointTdtBoundedFn`).  ep (B, T, J), pp (B, U+1, J), and a joiner
+    no logits tensor at all: the memory-bounded node (`_JointBoundedFn`).  ep (B, T, J), pp (B, U+1, J), and a joiner
     of W = V + len(durations) outputs (w_out (W, J), b_out (W,)): columns [0, V) token logits, the rest duration logits.
     targets (B, U) int32, lengths (B,) int32, max(logit_lengths) == T and max(target_lengths) == U as in
     `joint_rnnt_loss`; ``durations``, ``blank`` in [0, V), ``sigma`` and ``reduction`` as in `rnnt_tdt_loss`.  An utterance
@@ -350,8 +323,7 @@ def joint_rnnt_tdt_loss(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Tensor,
     most this many bytes (`plan_slices` on rows of W floats; ValueError below one frame row, U1 * W * 4 bytes).
     ``precision``: "fp32" only -- any other joiner precision raises ValueError.  Ragged batches are not bucketed here."""
     what = "joint_rnnt_tdt_loss"
-    if reduction not in ("none", "mean", "sum"):
-        raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
+    reduce = reducer(reduction)
     durs, sg = check_tdt(what, durations, sigma)
     if precision != "fp32":
         raise ValueError(f"{what}: precision {precision!r} is not supported, the memory-bounded TDT node runs the exact "
@@ -362,29 +334,11 @@ def joint_rnnt_tdt_loss(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Tensor,
                          "needed)")
     blank = _check_blank(what, blank, W - D)
     act = activation_code(activation)
-    dev = ep.device
-    tg = targets.to(device=dev, dtype=torch.int32).contiguous()
-    ll = logit_lengths.to(device=dev, dtype=torch.int32).contiguous()
-    tl = target_lengths.to(device=dev, dtype=torch.int32).contiguous()
-    B, T = ep.shape[0], ep.shape[1]
-    U1 = pp.shape[1]
-    if not (tg.dim() == 2 and tg.shape == (B, U1 - 1) and ll.shape == (B,) and tl.shape == (B,)):
-        raise RuntimeError(f"{what}: targets must be (B, U) and lengths (B,) for ep (B,T,J), pp (B,U+1,J)")
-    lens = torch.stack([ll, tl]).cpu()                      # the one host sync, as in joint_rnnt_loss
-    if int(lens[0].max()) != T:
-        raise RuntimeError("input length mismatch")
-    if int(lens[1].max()) + 1 != U1:
-        raise RuntimeError("output length mismatch")
-    if int(lens.min()) < 0:
-        raise RuntimeError("lengths must be non-negative")
+    tg, ll, tl, lens = _lengths(what, ep, pp, targets, logit_lengths, target_lengths)
     host_t, host_u = lens[0].tolist(), lens[1].tolist()
-    slices = plan_slices(host_t, host_u, T, U1, W, int(logits_budget))      # a bad budget fails before any launch
-    costs = _JointTdtBoundedFn.apply(ep, pp, w_out, b_out, tg, ll, tl, blank, durs, sg, act, slices, host_t, host_u)
-    if reduction == "mean":
-        return costs.mean()
-    if reduction == "sum":
-        return costs.sum()
-    return costs
+    slices = plan_slices(host_t, host_u, ep.shape[1], pp.shape[1], W, int(logits_budget))   # a bad budget fails before any launch
+    loss = _TdtLoss(blank, _durations_arg(durs), D, sg)
+    return reduce(_JointBoundedFn.apply(ep, pp, w_out, b_out, tg, ll, tl, loss, act, slices, host_t, host_u))
 
 
 def plan_buckets(t_lens, u_lens, max_buckets: int = 4, min_gain: float = 0.08, min_cells: int = 20000):
@@ -435,6 +389,20 @@ def plan_buckets(t_lens, u_lens, max_buckets: int = 4, min_gain: float = 0.08, m
     return groups[::-1]
 
 
+def per_bucket(groups, lens, dev, part, restore_order: bool = True) -> torch.Tensor:
+    """The costs of the groups of `plan_buckets` as one tensor.  Each group's come from part(idx, g, tmax, umax): its
+    utterances as an index tensor on `dev` and as a list, and its own longest frame and label count, read from the host
+    lengths `lens` (2, B).  They come back in the caller's utterance order (differentiable), or in bucket order with
+    `restore_order` off."""
+    parts, index = [], []
+    for g in groups:
+        idx = torch.tensor(g, device=dev)
+        parts.append(part(idx, g, int(lens[0][g].max()), int(lens[1][g].max())))
+        index.append(idx)
+    costs = torch.cat(parts)
+    return costs[torch.argsort(torch.cat(index))] if restore_order else costs
+
+
 def joint_rnnt_loss(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tensor,
                     targets: torch.Tensor, logit_lengths: torch.Tensor, target_lengths: torch.Tensor, blank: int = 0,
                     clamp: float = -1.0, reduction: str = "mean", precision: Optional[str] = None,
@@ -449,14 +417,13 @@ def joint_rnnt_loss(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Tensor, b_o
     the 16-bit modes are refused; reduction as rnnt_loss.
     ``buckets``: at most this many groups by label length, each padded to its own maxima (`plan_buckets`; default from
     WR_FUSED_BUCKETS, 4; 1 = one call for the whole batch).  Costs come back in the caller's utterance order.
-    ``logits_budget``: None (default) = the node above; an int = the memory-bounded node (`_JointRnntBoundedFn`): no
+    ``logits_budget``: None (default) = the node above; an int = the memory-bounded node (`_JointBoundedFn`): no
     logits tensor, the backward recomputes the logits in slices whose gradient buffer holds at most this many bytes
     (`plan_slices`; ValueError below one frame row, U1 * V * 4 bytes).  "fp32" and "bf16x3" only, as the node above.
     ``fastemit_lambda`` / ``delay_penalty``: as `rnnt_loss` takes them, in either node (FastEmit scales the gradient of
     the label arcs by 1 + lambda and leaves the costs bit-identical; the delay penalty is inside the costs).  The
     penalty uses each utterance's own length, so buckets and slices do not change it."""
-    if reduction not in ("none", "mean", "sum"):
-        raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
+    reduce = reducer(reduction)
     lam, pen = check_latency("joint_rnnt_loss", fastemit_lambda, delay_penalty)
     precision = _call_precision(precision)             # "autocast": "fp32" outside autocast, a 16-bit mode under it
     if precision in ("bf16", "f16"):
@@ -466,21 +433,7 @@ def joint_rnnt_loss(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Tensor, b_o
         blank = V + blank
     if not 0 <= blank < V:
         raise RuntimeError("blank must be within [0, logits.shape[-1])")
-    dev = ep.device
-    tg = targets.to(device=dev, dtype=torch.int32).contiguous()
-    ll = logit_lengths.to(device=dev, dtype=torch.int32).contiguous()
-    tl = target_lengths.to(device=dev, dtype=torch.int32).contiguous()
-    B, T = ep.shape[0], ep.shape[1]
-    U1 = pp.shape[1]
-    if not (tg.dim() == 2 and tg.shape == (B, U1 - 1) and ll.shape == (B,) and tl.shape == (B,)):
-        raise RuntimeError("joint_rnnt_loss: targets must be (B, U) and lengths (B,) for ep (B,T,J), pp (B,U+1,J)")
-    lens = torch.stack([ll, tl]).cpu()                      # the one host sync, as in rnnt_loss
-    if int(lens[0].max()) != T:
-        raise RuntimeError("input length mismatch")
-    if int(lens[1].max()) + 1 != U1:
-        raise RuntimeError("output length mismatch")
-    if int(lens.min()) < 0:
-        raise RuntimeError("lengths must be non-negative")
+    tg, ll, tl, lens = _lengths("joint_rnnt_loss", ep, pp, targets, logit_lengths, target_lengths)
     if buckets is None:
         buckets = int(os.environ.get("WR_FUSED_BUCKETS", "4"))
     groups = plan_buckets(lens[0].tolist(), lens[1].tolist(), max_buckets=buckets) if buckets > 1 else None
@@ -491,25 +444,13 @@ def joint_rnnt_loss(ep: torch.Tensor, pp: torch.Tensor, w_out: torch.Tensor, b_o
         if logits_budget is None:
             return _JointRnntFn.apply(ep_, pp_, w_out, b_out, tg_, ll_, tl_, int(blank), float(clamp), terms, act, lam, pen)
         slices = plan_slices(host_t, host_u, ep_.shape[1], pp_.shape[1], V, int(logits_budget))
-        return _JointRnntBoundedFn.apply(ep_, pp_, w_out, b_out, tg_, ll_, tl_, int(blank), float(clamp), terms, act,
-                                         slices, host_t, host_u, lam, pen)
+        return _JointBoundedFn.apply(ep_, pp_, w_out, b_out, tg_, ll_, tl_,
+                                     _RnntLoss(int(blank), float(clamp), terms, lam, pen), act, slices, host_t, host_u)
 
-    if logits_budget is not None:
-        plan_slices(lens[0].tolist(), lens[1].tolist(), T, U1, V, int(logits_budget))   # a bad budget fails before any launch
+    if logits_budget is not None:      # a bad budget fails before any launch
+        plan_slices(lens[0].tolist(), lens[1].tolist(), ep.shape[1], pp.shape[1], V, int(logits_budget))
     if groups is None:
-        costs = node(ep, pp, tg, ll, tl, lens[0].tolist(), lens[1].tolist())
-    else:
-        costs = torch.empty(B, dtype=torch.float32, device=dev)
-        parts, index = [], []
-        for g in groups:
-            idx = torch.tensor(g, device=dev)
-            tg_max, ug_max = int(lens[0][g].max()), int(lens[1][g].max())
-            parts.append(node(ep[idx, :tg_max], pp[idx, :ug_max + 1], tg[idx, :ug_max].contiguous(), ll[idx].contiguous(),
-                              tl[idx].contiguous(), lens[0][g].tolist(), lens[1][g].tolist()))
-            index.append(idx)
-        costs = torch.cat(parts)[torch.argsort(torch.cat(index))]      # back to the caller's order (differentiable)
-    if reduction == "mean":
-        return costs.mean()
-    if reduction == "sum":
-        return costs.sum()
-    return costs
+        return reduce(node(ep, pp, tg, ll, tl, lens[0].tolist(), lens[1].tolist()))
+    return reduce(per_bucket(groups, lens, ep.device, lambda idx, g, tmax, umax: node(
+        ep[idx, :tmax], pp[idx, :umax + 1], tg[idx, :umax].contiguous(), ll[idx].contiguous(), tl[idx].contiguous(),
+        lens[0][g].tolist(), lens[1][g].tolist())))

@@ -35,6 +35,18 @@ def check_lattice(what: str, rnnt_type, delay_penalty) -> Tuple[int, float]:
     return _lib.LATTICES[rnnt_type], pen
 
 
+_REDUCTIONS = {"none": lambda costs: costs, "mean": torch.Tensor.mean, "sum": torch.Tensor.sum}
+
+
+def reducer(reduction):
+    """The tail of every loss front end: the function that takes the costs (B,) to themselves ("none"), their plain
+    batch mean or their sum; ValueError for any other name.  A front end asks for it where it checks `reduction` and
+    applies it to what its node returns."""
+    if not isinstance(reduction, str) or reduction not in _REDUCTIONS:
+        raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
+    return _REDUCTIONS[reduction]
+
+
 def is_default(lat: int, pen: float) -> bool:
     return lat == 0 and pen == 0.0
 

@@ -24,7 +24,7 @@ import os
 import torch
 
 from . import _lib
-from .rnnt_lattice import check_lattice
+from .rnnt_lattice import check_lattice, reducer
 
 
 def check_latency(what: str, fastemit_lambda, delay_penalty):
@@ -71,6 +71,34 @@ def _validate(logits, targets, logit_lengths, target_lengths, blank):
     req(int(lens.min()) >= 0, "lengths must be non-negative")
 
 
+_LATTICE_FORM = {"wr_rnnt_loss_sweeps": "wr_rnnt_lattice_sweeps"}        # every other entry point appends "_lattice"
+
+
+def call_regularised(name: str, head, tail, pen: float, lam=None, *, device) -> None:
+    """Entry point `name`(*head, *tail) or, with a regulariser on, its `_lattice` form, which takes the lattice type
+    (0: regular), the delay penalty and -- the gradient passes, which give `lam` -- FastEmit's lambda between `head` and
+    `tail`.  With both at 0 it is the plain entry point that runs (and that an error names)."""
+    if pen == 0.0 and not lam:
+        _lib.call(name, *head, *tail, device=device)
+    else:
+        _lib.call(_LATTICE_FORM.get(name, name + "_lattice"), *head, 0, pen, *(() if lam is None else (lam,)), *tail,
+                  device=device)
+
+
+def loss_forward(logits, targets, llens, tlens, blank: int, pen: float, costs, ws) -> None:
+    """Row pass and lattice sweeps of (B, T, U1, V) logits into `costs` and the RNN-T workspace `ws`."""
+    B, T, U1, V = logits.shape
+    call_regularised("wr_rnnt_loss_fwd", (logits, _lib.dtype_code(logits.dtype), targets, llens, tlens, B, T, U1, V, blank),
+                     (costs, ws, ws.numel()), pen, device=logits.device)
+
+
+def loss_backward(logits, targets, llens, tlens, blank: int, clamp: float, lam: float, pen: float, gc, grads, ws) -> None:
+    """gc[b] * d cost_b / d logits into `grads` (which may be `logits`), from the workspace `loss_forward` left."""
+    B, T, U1, V = logits.shape
+    call_regularised("wr_rnnt_loss_bwd", (logits, _lib.dtype_code(logits.dtype), targets, llens, tlens, B, T, U1, V, blank,
+                                          float(clamp)), (gc, grads, ws, ws.numel()), pen, lam, device=logits.device)
+
+
 class _RNNTLossFn(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda")          # fp16/bf16 logits are handled natively (fp32 arithmetic inside)
@@ -82,12 +110,7 @@ class _RNNTLossFn(torch.autograd.Function):
         dev = logits.device
         ws = _lib.workspace("wr_rnnt_workspace_bytes", B, T, U1, device=dev)
         costs = torch.empty(B, dtype=torch.float32, device=dev)
-        if pen == 0.0:
-            _lib.call("wr_rnnt_loss_fwd", logits, _lib.dtype_code(logits.dtype), targets, logit_lengths, target_lengths, B, T,
-                      U1, V, blank, costs, ws, ws.numel(), device=dev)
-        else:
-            _lib.call("wr_rnnt_loss_fwd_lattice", logits, _lib.dtype_code(logits.dtype), targets, logit_lengths,
-                      target_lengths, B, T, U1, V, blank, 0, pen, costs, ws, ws.numel(), device=dev)
+        loss_forward(logits, targets, logit_lengths, target_lengths, blank, pen, costs, ws)
         ctx.save_for_backward(logits, targets, logit_lengths, target_lengths, ws)
         ctx.blank, ctx.clamp, ctx.inplace_grad, ctx.lam, ctx.pen = blank, clamp, inplace_grad, lam, pen
         return costs.to(logits.dtype) if logits.dtype != torch.float32 else costs
@@ -96,17 +119,9 @@ class _RNNTLossFn(torch.autograd.Function):
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_costs):
         logits, targets, logit_lengths, target_lengths, ws = ctx.saved_tensors
-        B, T, U1, V = logits.shape
-        dev = logits.device
         grads = logits if ctx.inplace_grad else torch.empty_like(logits)
         gc = grad_costs.to(torch.float32).contiguous()
-        if ctx.lam == 0.0 and ctx.pen == 0.0:
-            _lib.call("wr_rnnt_loss_bwd", logits, _lib.dtype_code(logits.dtype), targets, logit_lengths, target_lengths, B, T,
-                      U1, V, ctx.blank, float(ctx.clamp), gc, grads, ws, ws.numel(), device=dev)
-        else:
-            _lib.call("wr_rnnt_loss_bwd_lattice", logits, _lib.dtype_code(logits.dtype), targets, logit_lengths,
-                      target_lengths, B, T, U1, V, ctx.blank, float(ctx.clamp), 0, ctx.pen, ctx.lam, gc, grads, ws,
-                      ws.numel(), device=dev)
+        loss_backward(logits, targets, logit_lengths, target_lengths, ctx.blank, ctx.clamp, ctx.lam, ctx.pen, gc, grads, ws)
         return grads, None, None, None, None, None, None, None, None
 
 
@@ -131,21 +146,15 @@ def rnnt_loss(logits: torch.Tensor, targets: torch.Tensor, logit_lengths: torch.
     footprint of the (B,T,U+1,V) tensors when nothing else needs the logits
     (true for the reference's forward, transducer.py:132-147).
     """
-    if reduction not in ("none", "mean", "sum"):
-        raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
+    reduce = reducer(reduction)
     lam, pen = check_latency("rnnt_loss", fastemit_lambda, delay_penalty)
     if blank < 0:
         blank = logits.shape[-1] + blank
     _validate(logits, targets, logit_lengths, target_lengths, blank)
     if inplace_grad is None:
         inplace_grad = os.environ.get("WR_RNNT_INPLACE_GRAD", "0") == "1"
-    costs = _RNNTLossFn.apply(logits, targets, logit_lengths, target_lengths, int(blank), float(clamp),
-                              bool(inplace_grad), lam, pen)
-    if reduction == "mean":
-        return costs.mean()
-    if reduction == "sum":
-        return costs.sum()
-    return costs
+    return reduce(_RNNTLossFn.apply(logits, targets, logit_lengths, target_lengths, int(blank), float(clamp),
+                                    bool(inplace_grad), lam, pen))
 
 
 class RNNTLoss(torch.nn.Module):

@@ -212,12 +212,10 @@ def rnnt_loss_pruned(logits: torch.Tensor, symbols: torch.Tensor, ranges: torch.
     within [0, U] (ValueError otherwise).  ``rnnt_type`` and ``delay_penalty`` as in `rnnt_loss_simple`: the penalty is
     added to the band's label arcs; on the "modified" lattice a band of one position per frame (R = 1) is legal."""
     what = "rnnt_loss_pruned"
-    if reduction not in ("none", "mean", "sum"):
-        raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
+    reduce = _lat.reducer(reduction)
     lat, pen = _lat.check_lattice(what, rnnt_type, delay_penalty)
     sy, ll, tl, blank, rg = _prepare(logits, symbols, ranges, termination_symbol, boundary, what)
-    costs = _RNNTPrunedFn.apply(logits, sy, rg, ll, tl, blank, lat, pen)
-    return costs.mean() if reduction == "mean" else (costs.sum() if reduction == "sum" else costs)
+    return reduce(_RNNTPrunedFn.apply(logits, sy, rg, ll, tl, blank, lat, pen))
 
 
 @torch.no_grad()

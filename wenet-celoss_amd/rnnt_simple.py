@@ -124,13 +124,12 @@ def loss(what: str, lm, am, symbols, termination_symbol, lm_only_scale, am_only_
     document.  Checks in order: lattice arguments, reduction, scales, shapes / boundary / symbols (the one host sync),
     device."""
     lat, pen = _lat.check_lattice(what, rnnt_type, delay_penalty)
-    if reduction not in ("none", "mean", "sum"):
-        raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
+    reduce = _lat.reducer(reduction)
     lm_scale, am_scale = _check_scales(what, lm_only_scale, am_only_scale)
     sy, ll, tl, blank = _prepare(lm, am, symbols, termination_symbol, boundary, what)
     out = _RNNTAdditiveFn.apply(lm.float(), am.float(), sy, ll, tl, blank, lm_scale, am_scale, lat, pen, bool(return_grad))
     costs = out[0] if return_grad else out                # float32 whatever the inputs' precision
-    res = costs.mean() if reduction == "mean" else (costs.sum() if reduction == "sum" else costs)
+    res = reduce(costs)
     if not return_grad:
         return res
     return res, _lat.occupancies_to_k2(out[1].detach(), out[2].detach(), lat)

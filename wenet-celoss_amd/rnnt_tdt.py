@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from .rnnt_align import _blank, _prepare
+from .rnnt_lattice import reducer
 from .rnnt_loss import _validate
 
 MAX_DURATION = 8
@@ -58,7 +59,8 @@ def _check_blank(what: str, blank, V: int) -> int:
 
 
 def _durations_arg(durs):
-    return (ctypes.c_int32 * len(durs))(*durs)
+    """The durations as the library takes them; never empty, so that an empty list still reaches the library's refusal."""
+    return (ctypes.c_int32 * max(len(durs), 1))(*[int(d) for d in durs])
 
 
 def _forward(logits, targets, logit_lengths, target_lengths, blank, durs, sigma):
@@ -108,8 +110,7 @@ def rnnt_tdt_loss(logits: torch.Tensor, targets: torch.Tensor, logit_lengths: to
     ``sigma`` >= 0.  A bad value raises ValueError.  ``reduction`` in {"none", "mean", "sum"}, "mean" a plain batch mean;
     costs come back in the logits' dtype.  ``inplace_grad`` (default from env WR_RNNT_INPLACE_GRAD, off) writes the
     gradient over the logits' storage in backward."""
-    if reduction not in ("none", "mean", "sum"):
-        raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
+    reduce = reducer(reduction)
     durs, sg = check_tdt("rnnt_tdt_loss", durations, sigma)
     if logits.dim() == 4:                               # any other rank is _validate's to refuse
         if logits.shape[-1] <= len(durs):
@@ -119,12 +120,7 @@ def rnnt_tdt_loss(logits: torch.Tensor, targets: torch.Tensor, logit_lengths: to
     _validate(logits, targets, logit_lengths, target_lengths, blank)
     if inplace_grad is None:
         inplace_grad = os.environ.get("WR_RNNT_INPLACE_GRAD", "0") == "1"
-    costs = _TDTLossFn.apply(logits, targets, logit_lengths, target_lengths, blank, durs, sg, bool(inplace_grad))
-    if reduction == "mean":
-        return costs.mean()
-    if reduction == "sum":
-        return costs.sum()
-    return costs
+    return reduce(_TDTLossFn.apply(logits, targets, logit_lengths, target_lengths, blank, durs, sg, bool(inplace_grad)))
 
 
 class TDTLoss(torch.nn.Module):

@@ -25,12 +25,23 @@ def basic_greedy_search(model: torch.nn.Module, encoder_out: torch.Tensor, encod
     `model` needs `.blank`, `.predictor` (RNNPredictor), `.joint` (TransducerJoint) and a
     `_decoder_cache` (wenet_celoss_amd.decoder.DecoderCache); Transducer provides all of them.
     context_* are accepted for signature compatibility and ignored (no hot words)."""
-    N, T, _ = encoder_out.shape
-    lens = torch.as_tensor(encoder_out_lens).reshape(-1)
-    if lens.numel() == 1 and N > 1:
-        lens = lens.expand(N)
-    dec = _decoder_cache(model).get(model.predictor, model.joint, lanes=N, utts=N, tmax=T, max_hyp=T * n_steps, beam=1)
+    lens, dec = lens_and_decoder(model, encoder_out, encoder_out_lens, n_steps)
     return dec.greedy(encoder_out, lens, n_steps=n_steps, blank=model.blank)
+
+
+def expand_lens(encoder_out_lens, N: int) -> torch.Tensor:
+    """Lengths as a 1-D tensor; a scalar stands for all N streams."""
+    lens = torch.as_tensor(encoder_out_lens).reshape(-1)
+    return lens.expand(N) if lens.numel() == 1 and N > 1 else lens
+
+
+def lens_and_decoder(model, encoder_out: torch.Tensor, encoder_out_lens, n_steps: int, tmax: int = 0):
+    """(lengths (N,), the model's cached DeviceDecoder sized for a greedy search of encoder_out (N, T, E)): N lanes,
+    frames up to max(T, tmax), n_steps tokens per frame."""
+    N, T, _ = encoder_out.shape
+    T = max(T, tmax)
+    dec = _decoder_cache(model).get(model.predictor, model.joint, lanes=N, utts=N, tmax=T, max_hyp=T * n_steps, beam=1)
+    return expand_lens(encoder_out_lens, N), dec
 
 
 def _decoder_cache(model):
@@ -60,11 +71,7 @@ def tdt_greedy_search(model: torch.nn.Module, encoder_out: torch.Tensor, encoder
     if os.environ.get("WR_TDT_HOST", "0") == "1":
         hyps, frames = _tdt_greedy_host(model, encoder_out, encoder_out_lens, n_steps)
         return ([hyps], [frames]) if return_frames else [hyps]
-    N, T, _ = encoder_out.shape
-    lens = torch.as_tensor(encoder_out_lens).reshape(-1)
-    if lens.numel() == 1 and N > 1:
-        lens = lens.expand(N)
-    dec = _decoder_cache(model).get(model.predictor, model.joint, lanes=N, utts=N, tmax=T, max_hyp=T * n_steps, beam=1)
+    lens, dec = lens_and_decoder(model, encoder_out, encoder_out_lens, n_steps)
     return dec.greedy_tdt(encoder_out, lens, model.tdt_durations, n_steps=n_steps, blank=model.blank,
                           return_frames=return_frames)
 

@@ -39,20 +39,26 @@ def tdt_prefix_beam_search(model: torch.nn.Module, encoder_out: torch.Tensor, en
     encoder_out (B, T, E), encoder_out_lens scalar or (B,) -> per utterance the pruned beam, best first, each hypothesis
     beginning with the seed blank.  The CTC posterior (`model.ctc`) is computed and mixed in only when
     (ctc_weight, transducer_weight) != (0, 1)."""
-    from .greedy_search import _decoder_cache
+    from .greedy_search import _decoder_cache, expand_lens
+    lens = expand_lens(encoder_out_lens, encoder_out.shape[0])
+    return _search(_decoder_cache(model), model, encoder_out, beam_size,
+                   lambda dec, ctc_logp: dec.prefix_beam_tdt(encoder_out, lens, model.tdt_durations, beam_size, model.blank,
+                                                             ctc_logp=ctc_logp, ctc_weight=ctc_weight,
+                                                             transducer_weight=transducer_weight),
+                   with_ctc=(float(ctc_weight), float(transducer_weight)) != (0.0, 1.0))
+
+
+def _search(cache, owner, encoder_out: torch.Tensor, beam_size: int, search, with_ctc: bool = True) -> List[List[Sequence]]:
+    """search(decoder, ctc_logp) on `cache`'s DeviceDecoder for `owner`'s predictor and joiner, sized for a beam search of
+    encoder_out (B, T, E); ctc_logp is the (B, T, V) posterior of `owner.ctc`, None unless `with_ctc`.  The n-best lists
+    come back as Sequences."""
     B, T, _ = encoder_out.shape
-    lens = torch.as_tensor(encoder_out_lens).reshape(-1)
-    if lens.numel() == 1 and B > 1:
-        lens = lens.expand(B)
     ctc_logp = None
-    if (float(ctc_weight), float(transducer_weight)) != (0.0, 1.0):
+    if with_ctc:
         with torch.no_grad():
-            ctc_logp = model.ctc.log_softmax(encoder_out)                # (B, T, V), ctc.py:66-75
-    dec = _decoder_cache(model).get(model.predictor, model.joint, lanes=B * beam_size, utts=B, tmax=T, max_hyp=0,
-                                    beam=beam_size)
-    res = dec.prefix_beam_tdt(encoder_out, lens, model.tdt_durations, beam_size, model.blank, ctc_logp=ctc_logp,
-                              ctc_weight=ctc_weight, transducer_weight=transducer_weight)
-    return [[Sequence(hyp=h, score=s, cache=None) for h, s in utt] for utt in res]
+            ctc_logp = owner.ctc.log_softmax(encoder_out)                # (B, T, V), ctc.py:66-75
+    dec = cache.get(owner.predictor, owner.joint, lanes=B * beam_size, utts=B, tmax=T, max_hyp=0, beam=beam_size)
+    return [[Sequence(hyp=h, score=s, cache=None) for h, s in utt] for utt in search(dec, ctc_logp)]
 
 
 class PrefixBeamSearch:
@@ -67,13 +73,9 @@ class PrefixBeamSearch:
     def search_encoded(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, beam_size: int = 5,
                        ctc_weight: float = 0.3, transducer_weight: float = 0.7) -> List[List[Sequence]]:
         """encoder_out (B, T, E) already computed -> per utterance the pruned beam (best first)."""
-        B, T, _ = encoder_out.shape
-        with torch.no_grad():
-            ctc_logp = self.ctc.log_softmax(encoder_out)                 # (B, T, V), ctc.py:66-75
-        dec = self._decoder_cache.get(self.predictor, self.joint, lanes=B * beam_size, utts=B, tmax=T, max_hyp=0,
-                                      beam=beam_size)
-        res = dec.prefix_beam(encoder_out, encoder_out_lens, ctc_logp, beam_size, ctc_weight, transducer_weight, self.blank)
-        return [[Sequence(hyp=h, score=s, cache=None) for h, s in utt] for utt in res]
+        return _search(self._decoder_cache, self, encoder_out, beam_size,
+                       lambda dec, ctc_logp: dec.prefix_beam(encoder_out, encoder_out_lens, ctc_logp, beam_size, ctc_weight,
+                                                             transducer_weight, self.blank))
 
     def prefix_beam_search(self, speech: torch.Tensor, speech_lengths: torch.Tensor, decoding_chunk_size: int = -1,
                            beam_size: int = 5, num_decoding_left_chunks: int = -1, simulate_streaming: bool = False,

@@ -31,7 +31,7 @@ from torch.nn.utils.rnn import pad_sequence
 
 from .common import IGNORE_ID, LabelSmoothingLoss, add_blank, add_sos_eos, end_blank, reverse_pad_list
 from .decoder import DecoderCache
-from .fused import joint_rnnt_loss, joint_rnnt_tdt_loss, plan_buckets
+from .fused import joint_rnnt_loss, joint_rnnt_tdt_loss, per_bucket, plan_buckets
 from .joint import TransducerJoint, _call_precision
 from .rnnt_align import joint_rnnt_forced_align, rnnt_forced_align
 from .rnnt_loss import check_latency, rnnt_loss
@@ -41,7 +41,7 @@ from .rnnt_lattice import check_lattice, is_default
 from .rnnt_pruned import rnnt_loss_pruned
 from .rnnt_tdt import check_tdt, rnnt_tdt_forced_align, rnnt_tdt_loss
 from .search.greedy_search import (basic_greedy_search, basic_greedy_search_both, basic_greedy_search_hw,
-                                   tdt_greedy_search)
+                                   lens_and_decoder, tdt_greedy_search)
 from .search.prefix_beam_search import PrefixBeamSearch, tdt_prefix_beam_search
 
 
@@ -194,8 +194,7 @@ class Transducer(nn.Module):
         Returns (joint_out, loss_rnnt).  With `fused_loss` the two run as one autograd node and joint_out is
         None (the logits never leave it); otherwise `skip_padding=True` (extension) lets the joiner skip lattice cells
         that the loss never reads."""
-        rnnt_text = text.to(torch.int64)
-        rnnt_text = torch.where(rnnt_text == self.ignore_id, 0, rnnt_text).to(torch.int32)
+        rnnt_text = self._rnnt_text(text)
         rnnt_text_lengths = text_lengths.to(torch.int32)
         encoder_out_lens = encoder_out_lens.to(torch.int32)
         if self._is_tdt():
@@ -232,17 +231,13 @@ class Transducer(nn.Module):
             lens = torch.stack([encoder_out_lens, rnnt_text_lengths]).cpu()
             groups = plan_buckets(lens[0].tolist(), lens[1].tolist(), max_buckets=int(os.environ.get("WR_FUSED_BUCKETS", "4")))
             if groups is not None:
-                dev = encoder_out.device
-                parts, index = [], []
-                for g in groups:
-                    idx = torch.tensor(g, device=dev)
-                    tg, ug = int(lens[0][g].max()), int(lens[1][g].max())
+                def part(idx, g, tg, ug):
                     ll, tl = encoder_out_lens[idx].contiguous(), rnnt_text_lengths[idx].contiguous()
                     logits = self.joint(encoder_out[idx, :tg], predictor_out[idx, :ug + 1], ll, tl)
-                    parts.append(rnnt_loss(logits, rnnt_text[idx, :ug].contiguous(), ll, tl, blank=self.blank, reduction="none",
-                                           inplace_grad=True, **self._latency_kwargs()))
-                    index.append(idx)
-                return None, torch.cat(parts).float().mean()
+                    return rnnt_loss(logits, rnnt_text[idx, :ug].contiguous(), ll, tl, blank=self.blank, reduction="none",
+                                     inplace_grad=True, **self._latency_kwargs())
+                # averaged in bucket order, as this branch always did: another order moves the mean's last bit
+                return None, per_bucket(groups, lens, encoder_out.device, part, restore_order=False).float().mean()
         if skip_padding:
             joint_out = self.joint(encoder_out, predictor_out, encoder_out_lens, rnnt_text_lengths)
         else:
@@ -250,6 +245,11 @@ class Transducer(nn.Module):
         loss = rnnt_loss(joint_out, rnnt_text.contiguous(), encoder_out_lens.contiguous(),
                          rnnt_text_lengths.contiguous(), blank=self.blank, reduction="mean", **self._latency_kwargs())
         return joint_out, loss
+
+    def _rnnt_text(self, text: torch.Tensor) -> torch.Tensor:
+        """Labels as the loss kernels take them: int32, IGNORE_ID padding mapped to class 0."""
+        text = text.to(torch.int64)
+        return torch.where(text == self.ignore_id, 0, text).to(torch.int32)
 
     def _warn_budget(self) -> None:
         """Once per model: a budget is set but this step's joiner keeps a logits tensor (the 16-bit AMP modes, the two-op
@@ -453,8 +453,7 @@ class Transducer(nn.Module):
                 lm, am, symbols, boundary = self._simple_inputs(encoder_out, encoder_out_lens, predictor_out, text,
                                                                 text_lengths)
                 return rnnt_simple_forced_align(lm, am, symbols, self.blank, boundary=boundary)
-            rnnt_text = text.to(torch.int64)
-            rnnt_text = torch.where(rnnt_text == self.ignore_id, 0, rnnt_text).to(torch.int32)
+            rnnt_text = self._rnnt_text(text)
             rnnt_text_lengths = text_lengths.to(torch.int32)
             encoder_out_lens = encoder_out_lens.to(torch.int32)
             jt = self.joint
@@ -484,8 +483,7 @@ class Transducer(nn.Module):
         with torch.no_grad():
             _, encoder_out, _, encoder_out_lens, _, predictor_out, _ = self._loss_inputs(
                 speech, speech_lengths, text, context_list, context_lengths)
-            rnnt_text = text.to(torch.int64)
-            rnnt_text = torch.where(rnnt_text == self.ignore_id, 0, rnnt_text).to(torch.int32)
+            rnnt_text = self._rnnt_text(text)
             logits = self.joint(encoder_out, predictor_out)
             return rnnt_tdt_forced_align(logits, rnnt_text, encoder_out_lens.to(torch.int32), text_lengths.to(torch.int32),
                                          self.tdt_durations, blank=self.blank, sigma=self.tdt_sigma,
@@ -517,11 +515,7 @@ class Transducer(nn.Module):
     def _cal_transducer_score(self, encoder_out: torch.Tensor, encoder_mask: torch.Tensor, hyps_lens: torch.Tensor,
                               hyps_pad: torch.Tensor):
         """-rnnt_loss(reduction='none') per hypothesis (transducer.py:277-302)."""
-        hyps_pad_blank = add_blank(hyps_pad, self.blank, self.ignore_id)
-        xs_in_lens = encoder_mask.squeeze(1).sum(1).int()
-        predictor_out = self.predictor(hyps_pad_blank)
-        rnnt_text = hyps_pad.to(torch.int64)
-        rnnt_text = torch.where(rnnt_text == self.ignore_id, 0, rnnt_text).to(torch.int32)
+        xs_in_lens, predictor_out, rnnt_text = self._score_inputs(encoder_mask, hyps_pad)
         if self._can_fuse_loss():                   # same node as the training loss block: no pass 1 over the logits
             ep, pp = self.joint.pre_activation(encoder_out, predictor_out)
             loss_td = joint_rnnt_loss(ep, pp, self.joint.ffn_out.weight, self.joint.ffn_out.bias, rnnt_text,
@@ -532,6 +526,12 @@ class Transducer(nn.Module):
         loss_td = rnnt_loss(joint_out, rnnt_text.contiguous(), xs_in_lens.contiguous(), hyps_lens.int().contiguous(),
                             blank=self.blank, reduction="none")
         return loss_td * -1
+
+    def _score_inputs(self, encoder_mask: torch.Tensor, hyps_pad: torch.Tensor):
+        """(encoder lengths int32, predictor output of the blank-prefixed hypotheses, the hypotheses as loss labels)."""
+        hyps_pad_blank = add_blank(hyps_pad, self.blank, self.ignore_id)
+        xs_in_lens = encoder_mask.squeeze(1).sum(1).int()
+        return xs_in_lens, self.predictor(hyps_pad_blank), self._rnnt_text(hyps_pad)
 
     def _cal_attn_score(self, encoder_out, encoder_mask, hyps_pad, hyps_lens, reverse_weight: Optional[float] = None):
         """transducer.py:304-330 (decoder called with self.reverse_weight) and the same block inside
@@ -734,15 +734,24 @@ class Transducer(nn.Module):
         else:
             raise ValueError(f"unknown beam_search_type {beam_search_type!r}")
         assert len(hyps) == beam_size
+        return self._rescore(hyps, beam_score, encoder_out, device, self._cal_transducer_score, reverse_weight, attn_weight,
+                             ctc_weight, transducer_weight)
+
+    def _rescore(self, hyps, beam_score, encoder_out, device, cal_td_score, reverse_weight: float, attn_weight: float,
+                 ctc_weight: float, transducer_weight: float):
+        """The tail of the two rescoring methods: the n-best `hyps` of ONE utterance (encoder_out (1, T, E)) padded, scored
+        by `cal_td_score` and by the attention decoder -> (the hypothesis with the largest att * attn_weight + beam score *
+        ctc_weight + td_score * transducer_weight, that score)."""
+        n = len(hyps)
         hyps_pad = pad_sequence([torch.tensor(h, device=device, dtype=torch.long) for h in hyps], True, self.ignore_id)
         hyps_lens = torch.tensor([len(h) for h in hyps], device=device, dtype=torch.long)
-        encoder_out = encoder_out.repeat(beam_size, 1, 1)
-        encoder_mask = torch.ones(beam_size, 1, encoder_out.size(1), dtype=torch.bool, device=device)
-        td_score = self._cal_transducer_score(encoder_out, encoder_mask, hyps_lens, hyps_pad)
+        encoder_out = encoder_out.repeat(n, 1, 1)
+        encoder_mask = torch.ones(n, 1, encoder_out.size(1), dtype=torch.bool, device=device)
+        td_score = cal_td_score(encoder_out, encoder_mask, hyps_lens, hyps_pad)
         decoder_out, r_decoder_out = self._cal_attn_score(encoder_out, encoder_mask, hyps_pad, hyps_lens)
         att = self._attention_scores(hyps, decoder_out, r_decoder_out, reverse_weight)
         best_score, best_index = -float("inf"), 0
-        for i in range(len(hyps)):
+        for i in range(n):
             score = att[i] * attn_weight + beam_score[i] * ctc_weight + td_score[i] * transducer_weight
             if score > best_score:
                 best_score, best_index = score, i
@@ -834,11 +843,7 @@ class Transducer(nn.Module):
                        hyps_pad: torch.Tensor):
         """-rnnt_tdt_loss(reduction='none') per hypothesis, with the model's durations and sigma: `_cal_transducer_score`
         for a token-and-duration model."""
-        hyps_pad_blank = add_blank(hyps_pad, self.blank, self.ignore_id)
-        xs_in_lens = encoder_mask.squeeze(1).sum(1).int()
-        predictor_out = self.predictor(hyps_pad_blank)
-        rnnt_text = hyps_pad.to(torch.int64)
-        rnnt_text = torch.where(rnnt_text == self.ignore_id, 0, rnnt_text).to(torch.int32)
+        xs_in_lens, predictor_out, rnnt_text = self._score_inputs(encoder_mask, hyps_pad)
         joint_out = self.joint(encoder_out, predictor_out)
         loss_td = rnnt_tdt_loss(joint_out, rnnt_text.contiguous(), xs_in_lens.contiguous(), hyps_lens.int().contiguous(),
                                 self.tdt_durations, blank=self.blank, sigma=self.tdt_sigma, reduction="none")
@@ -862,20 +867,9 @@ class Transducer(nn.Module):
                                                search_transducer_weight)
         beam_score = [s.score for s in nbest[0]]
         hyps = [s.hyp[1:] for s in nbest[0]]
-        n = len(hyps)                                       # a short utterance may have fewer than beam_size hypotheses
-        hyps_pad = pad_sequence([torch.tensor(h, device=device, dtype=torch.long) for h in hyps], True, self.ignore_id)
-        hyps_lens = torch.tensor([len(h) for h in hyps], device=device, dtype=torch.long)
-        encoder_out = encoder_out.repeat(n, 1, 1)
-        encoder_mask = torch.ones(n, 1, encoder_out.size(1), dtype=torch.bool, device=device)
-        td_score = self._cal_tdt_score(encoder_out, encoder_mask, hyps_lens, hyps_pad)
-        decoder_out, r_decoder_out = self._cal_attn_score(encoder_out, encoder_mask, hyps_pad, hyps_lens)
-        att = self._attention_scores(hyps, decoder_out, r_decoder_out, reverse_weight)
-        best_score, best_index = -float("inf"), 0
-        for i in range(n):
-            score = att[i] * attn_weight + beam_score[i] * ctc_weight + td_score[i] * transducer_weight
-            if score > best_score:
-                best_score, best_index = score, i
-        return hyps[best_index], best_score
+        # no assert on len(hyps): a short utterance may have fewer than beam_size hypotheses
+        return self._rescore(hyps, beam_score, encoder_out, device, self._cal_tdt_score, reverse_weight, attn_weight,
+                             ctc_weight, transducer_weight)
 
     # ------------------------------------- streaming greedy ("transducer ref.py":541-606) --
     def reset_cache(self, n_streams: int = 1, chunk_frames: int = 64, n_steps: int = 64) -> None:
@@ -891,13 +885,9 @@ class Transducer(nn.Module):
         if st is None:
             self.reset_cache(encoder_out.size(0))
             st = self._stream
-        N, T, _ = encoder_out.shape
+        N = encoder_out.size(0)
         assert N == st["n"], "call reset_cache(n_streams) before changing the number of streams"
-        lens = torch.as_tensor(encoder_out_lens).reshape(-1)
-        if lens.numel() == 1 and N > 1:
-            lens = lens.expand(N)
-        dec = self._decoder_cache.get(self.predictor, self.joint, lanes=N, utts=N, tmax=max(T, st["tmax"]),
-                                      max_hyp=max(T, st["tmax"]) * n_steps, beam=1)
+        lens, dec = lens_and_decoder(self, encoder_out, encoder_out_lens, n_steps, tmax=st["tmax"])
         if not st["fresh"] and getattr(self, "_stream_dec", None) is not dec:
             raise RuntimeError("the decoder handle was rebuilt (weights changed or capacity grew) in the middle of a "
                                "stream: call reset_cache() with the largest chunk size first")
