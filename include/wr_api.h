@@ -575,6 +575,76 @@ int wr_ctc_prefix_beam_search(const float *logits_d, const int32_t *lens_d, int 
                               int blank, int32_t *hyps_d, int32_t *hyp_lens_d, double *scores_d,
                               int32_t *n_hyps_d, void *workspace_d, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Streaming CTC prefix beam search: the search of wr_ctc_prefix_beam_search continued from a state block across
+ * chunks, for any number of streams at once, with the Viterbi score and one frame index per token of every
+ * hypothesis.  The chunk-driven twin in the reference is runtime/core/decoder/ctc_prefix_beam_search.cc:107-211
+ * (Search() once per encoder chunk, cur_hyps_ / abs_time_step_ kept between calls, viterbi_likelihood() and Times());
+ * its known-answer test is runtime/core/test/ctc_prefix_beam_search_test.cc:30-73.
+ *
+ * State.  Each stream holds the number of frames consumed, a_next, and an ordered list, best first, of at most `beam`
+ * entries.  An entry holds tokens; pb, pnb: float64 blank-ending and non-blank-ending summed scores; vb, vnb: float64
+ * Viterbi scores of the two endings; times_b, times_nb: one frame index per token, for the best blank-ending and
+ * non-blank-ending path.  A fresh stream has a_next = 0 and one entry: tokens = (), pb = 0, pnb = -inf, vb = 0, vnb = 0,
+ * both times lists empty (ctc_prefix_beam_search.cc:44-48; vnb = -inf would give the same results).  Derived:
+ *   vit(e)   = vb > vnb ? vb : vnb
+ *   times(e) = vb > vnb ? times_b : times_nb      (an exact tie takes times_nb, as the reference's `>` does)
+ *
+ * One frame.  Its absolute index is a = a_next.  Its top-`beam` symbols are found exactly as wr_ctc_prefix_beam_search
+ * finds them (the fused fp32 log-softmax, value descending, lower index on a tie, p = (double)logp[s]).  The visiting
+ * order is the Python search's: symbol outer, entries inner in list order.  Contributions go into an insertion-ordered
+ * dictionary `next`; a new key starts with pb = pnb = vb = vnb = -inf, ctp = -inf and empty times.  ctp is the best token
+ * log-probability that set the key's times_nb in this frame; it exists only inside the frame.
+ *   s == blank, key tokens:
+ *       pb = log_add(pb, e.pb + p, e.pnb + p);  vb = vit(e) + p;  times_b = times(e)
+ *   s == last token of e, key tokens:
+ *       pnb = log_add(pnb, e.pnb + p)
+ *       if vnb < e.vnb + p: vnb = e.vnb + p; then, if ctp < p: ctp = p, times_nb = e.times_nb with its last element
+ *       replaced by a
+ *   s == last token of e, also key tokens + (s,):
+ *       pnb = log_add(pnb, e.pb + p)
+ *       if vnb < e.vb + p: vnb = e.vb + p, ctp = p, times_nb = e.times_b + (a,)
+ *   otherwise, key tokens + (s,):
+ *       pnb = log_add(pnb, e.pb + p, e.pnb + p)
+ *       if vnb < vit(e) + p: vnb = vit(e) + p, ctp = p, times_nb = times(e) + (a,)
+ * The sums are float64, left to right (wenet/utils/common.py:268-276); the Viterbi values are plain float64 adds.
+ * After the frame: stable descending sort by log_add(pb, pnb); the first `beam` entries are the new list; a_next += 1.
+ * The Viterbi fields never influence pruning.  (The reference iterates an unordered_map, so its order where two
+ * contributions meet in one key is unspecified; ours is the Python search's.)  Consequence: every hypothesis's times
+ * has as many elements as tokens, is strictly increasing, and lies in [0, a_next).
+ *
+ * One call consumes lens[b] frames of stream b from a chunk logits [B, T, V], 0 <= lens[b] <= T; zero leaves the stream
+ * untouched.  Then it exports, for every stream: hyps [B, beam, Lcap] (padded with -1), hyp_lens [B, beam], scores
+ * [B, beam] float64 = log_add(pb, pnb), viterbi [B, beam] float64 = vit(e), times [B, beam, Lcap] (padded with -1; all
+ * -1 for an entry neither of whose endings has a path, vit(e) = -inf), n_hyps [B], n_frames [B] = a_next.
+ * reset != 0 starts fresh streams before consuming.
+ *
+ * Two equalities define "correct".  (1) For any one-chunk call, hyps / hyp_lens / scores / n_hyps are bit-identical to
+ * wr_ctc_prefix_beam_search on the same logits.  (2) For any split of a stream's frames into chunks -- width 1, chunks
+ * in which some streams have lens[b] = 0, ragged splits across the streams of one call -- every output after the last
+ * chunk is bit-identical to the one-chunk call: a row's log-softmax does not depend on its neighbours and the per-frame
+ * arithmetic is one fixed sequence.
+ *
+ * The state block is caller-owned and opaque, wr_ctc_stream_state_bytes(B, beam, Lcap) bytes; B, beam and Lcap must not
+ * change between the calls of one stream set (a block that no call with this beam and Lcap has written starts fresh,
+ * as after a reset).  frames_done is a host value: the chunk widths T summed over the earlier calls since the reset.
+ * Refused before any HIP call, in this order: the shape checks of the other CTC decode modes (B, T positive, V > 1,
+ * blank inside V: WR_EINVAL; V > 16320: WR_EUNSUPPORTED); a null pointer (WR_EINVAL); beam outside [1, 16] or beam > V
+ * (WR_EUNSUPPORTED); Lcap < 1, frames_done < 0, reset != 0 with frames_done != 0 (WR_EINVAL); frames_done + T > Lcap
+ * (WR_EUNSUPPORTED: a prefix gains at most one token per frame, so Lcap frames can never overflow the sequences); a
+ * state block or workspace below its query's size (WR_EWORKSPACE).  Everything runs on the caller's stream; there is no
+ * device-wide synchronisation and no allocation.  The size queries answer a non-positive argument (or beam > 16) with 0.
+ * These entry points only add to the ABI: WR_API_VERSION stays 3 (see its rule above).
+ * ---------------------------------------------------------------------- */
+size_t wr_ctc_stream_state_bytes(int B, int beam, int Lcap);
+size_t wr_ctc_stream_workspace_bytes(int B, int T, int beam);
+
+int wr_ctc_prefix_beam_search_chunk(const float *logits_d, const int32_t *lens_d, int B, int T, int V, int beam, int blank,
+                                    int reset, int frames_done, int Lcap, void *state_d, size_t state_bytes,
+                                    int32_t *hyps_d, int32_t *hyp_lens_d, double *scores_d, double *viterbi_d,
+                                    int32_t *times_d, int32_t *n_hyps_d, int32_t *n_frames_d, void *workspace_d,
+                                    size_t workspace_bytes, void *stream);
+
 /* RNN-T forced alignment: the single best path through the lattice of wr_rnnt_loss_fwd (a Viterbi pass: the forward
  * sweep with max in place of log-add-exp, one decision bit per cell, and a backtrace).  No reference call site: the
  * reference aligns with the CTC head only (wenet/bin/alignment.py); this is the transducer head's counterpart.

@@ -209,6 +209,84 @@ def bench_ctcdec(args):
                       "frames_per_s": round(200 / cdt)}), flush=True)
 
 
+def bench_ctcstream(args):
+    """Streaming CTC prefix beam search at the BASELINE CTC shape (B=32, T=1000, V=5000, beam=10), in one run: the
+    existing whole-utterance search, the streaming entry point in one chunk, and in 16-frame chunks (total and per
+    chunk).  Device time of the raw entry points on preallocated buffers (median of event timings), then the Python
+    wrappers end to end (they also copy the n-best to the host)."""
+    import time
+    import wenet_celoss_amd as wc
+    from wenet_celoss_amd import _lib
+    dev = torch.device("cuda:0")
+    torch.manual_seed(7)
+    B, T, V, beam, W = args.B, args.T, args.V, 10, 16
+    x = torch.randn(B, T, V, device=dev) * 3
+    x[..., 0] += 14.0                                  # blank-heavy, like a trained CTC head (about one label per 12 frames)
+    lens = torch.full((B,), T, dtype=torch.int32, device=dev)
+    base = {"B": B, "T": T, "V": V, "beam": beam}
+    i32 = dict(dtype=torch.int32, device=dev)
+    hl, nh, nf = torch.empty(B, beam, **i32), torch.empty(B, **i32), torch.empty(B, **i32)
+    sc, vt = torch.empty(B, beam, dtype=torch.float64, device=dev), torch.empty(B, beam, dtype=torch.float64, device=dev)
+    hyps, tm = torch.empty(B, beam, T, **i32), torch.empty(B, beam, T, **i32)
+
+    ws0 = _lib.workspace("wr_ctc_decode_workspace_bytes", B, T, beam, device=dev)
+    ms = timeit(lambda: _lib.call("wr_ctc_prefix_beam_search", x, lens, B, T, V, beam, 0, hyps, hl, sc, nh, ws0, ws0.numel(),
+                                  device=dev), args.steps)
+    old = (hyps.clone(), hl.clone(), sc.clone(), nh.clone())
+    print(json.dumps({"what": "wr_ctc_prefix_beam_search", **base, "ms_per_call": round(ms, 3),
+                      "frames_per_s": round(B * T / ms * 1e3)}), flush=True)
+
+    state = _lib.workspace("wr_ctc_stream_state_bytes", B, beam, T, device=dev)
+    ws1 = _lib.workspace("wr_ctc_stream_workspace_bytes", B, T, beam, device=dev)
+
+    def chunk(xc, ln, Tc, reset, done, ws):
+        _lib.call("wr_ctc_prefix_beam_search_chunk", xc, ln, B, Tc, V, beam, 0, reset, done, T, state, state.numel(), hyps, hl,
+                  sc, vt, tm, nh, nf, ws, ws.numel(), device=dev)
+
+    ms1 = timeit(lambda: chunk(x, lens, T, 1, 0, ws1), args.steps)
+    same = all(torch.equal(a, b) for a, b in zip(old, (hyps, hl, sc, nh)))
+    one = (hyps.clone(), hl.clone(), sc.clone(), vt.clone(), tm.clone())
+    print(json.dumps({"what": "wr_ctc_prefix_beam_search_chunk, one chunk", **base, "ms_per_call": round(ms1, 3),
+                      "frames_per_s": round(B * T / ms1 * 1e3), "vs_existing": round(ms1 / ms, 3),
+                      "bit_identical_to_existing": same}), flush=True)
+
+    parts = [x[:, t0:t0 + W].contiguous() for t0 in range(0, T, W)]
+    plens = [torch.full((B,), p.shape[1], dtype=torch.int32, device=dev) for p in parts]
+    wsc = _lib.workspace("wr_ctc_stream_workspace_bytes", B, W, beam, device=dev)
+
+    def chunked():
+        done = 0
+        for p, ln in zip(parts, plens):
+            chunk(p, ln, p.shape[1], int(done == 0), done, wsc)
+            done += p.shape[1]
+
+    msc = timeit(chunked, args.steps)
+    same = all(torch.equal(a, b) for a, b in zip(one, (hyps, hl, sc, vt, tm)))
+    print(json.dumps({"what": "wr_ctc_prefix_beam_search_chunk, 16-frame chunks", **base, "chunks": len(parts),
+                      "ms_total": round(msc, 3), "ms_per_chunk": round(msc / len(parts), 4),
+                      "frames_per_s": round(B * T / msc * 1e3), "vs_one_chunk": round(msc / ms1, 3),
+                      "bit_identical_to_one_chunk": same}), flush=True)
+
+    def timed(fn, n):
+        fn(); torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3
+
+    def stream_py():
+        s = wc.CtcPrefixBeamStream(B, beam, T)
+        for p, ln in zip(parts, plens):
+            s.search(p, ln)
+
+    print(json.dumps({"what": "python wrappers end to end", **base,
+                      "ctc_prefix_beam_search_ms": round(timed(lambda: wc.ctc_prefix_beam_search(x, lens, beam), args.steps), 3),
+                      "ctc_prefix_beam_search_times_ms": round(timed(lambda: wc.ctc_prefix_beam_search_times(x, lens, beam),
+                                                                     args.steps), 3),
+                      "CtcPrefixBeamStream_16_frame_chunks_ms": round(timed(stream_py, args.steps), 3)}), flush=True)
+
+
 def bench_greedy(args):
     """BASELINE config 3: B=64 streams, chunks of 16 encoder frames, V=5000, LSTM 2x256, J=512, n_steps=64."""
     import time
@@ -1218,7 +1296,7 @@ def bench_tdtbeam(args):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align", "simple", "smoothed", "pruned", "tdt",
-                                     "tdtstep", "tdtalign", "tdtdec", "tdtbeam"])
+                                     "tdtstep", "tdtalign", "tdtdec", "tdtbeam", "ctcstream"])
     ap.add_argument("--durations", type=int, default=5, help="tdt, tdtstep, tdtalign: number of durations D (the set is 0 .. D-1)")
     ap.add_argument("--n-steps", type=int, default=64)
     ap.add_argument("--chunks", type=int, default=4)
@@ -1257,4 +1335,4 @@ if __name__ == "__main__":
     {"joint": bench_joint, "ctc": bench_ctc, "greedy": bench_greedy, "beam": bench_beam, "step": bench_step, "ctcdec": bench_ctcdec, "hotword": bench_hotword,
      "align": bench_align, "simple": bench_simple, "smoothed": bench_smoothed, "pruned": bench_pruned,
      "tdt": bench_tdt, "tdtstep": bench_tdtstep, "tdtalign": bench_tdtalign, "tdtdec": bench_tdtdec,
-     "tdtbeam": bench_tdtbeam}[a.what](a)
+     "tdtbeam": bench_tdtbeam, "ctcstream": bench_ctcstream}[a.what](a)

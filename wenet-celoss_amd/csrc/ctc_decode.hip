@@ -16,6 +16,9 @@
 //                             wenet/utils/common.py:268-276), insertion-ordered, stable prune -- one contribution
 //                             per thread, all-pairs steps in parallel (see the kernel).
 //                             Prefixes are compared by (length, 64-bit rolling hash) and verified token by token.
+//   ctc_prefix_beam_chunk_kernel  the same search continued from a state block, one chunk of frames per launch, with the
+//                             Viterbi score and the frame of every token of each prefix (the runtime's Search()).
+#include "ctc_stream.hpp"
 #include "wr_common.hpp"
 #include "wr_launch.hpp"
 
@@ -23,6 +26,7 @@ namespace wr {
 namespace {
 
 constexpr int kMaxCtcBeam = 16;
+static_assert(kMaxCtcBeam == kCtcStreamMaxBeam, "ctc_stream.hpp sizes the state block for the same beam limit");
 
 struct CtcDecWs {
     size_t best_off, top_off, tkv_off, tki_off, seq_off, total;
@@ -339,6 +343,264 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_kernel(
     if (tid == 0) n_hyps[b] = n;
 }
 
+// ---- the streaming form (include/wr_api.h, "Streaming CTC prefix beam search") ----
+// The same slot scheme, started from a state block and stopped after this chunk's frames, with the Viterbi riders of
+// runtime/core/decoder/ctc_prefix_beam_search.cc:107-211: per entry the best single path's score for each ending
+// (vb, vnb) and the frame of every token on it (times_b, times_nb).  Step C applies a key's slots in slot order, which
+// is the order the riders need; what it keeps per key is two SOURCES, the slot whose base entry's list becomes the
+// key's times_b and the one that becomes its times_nb.  A slot names the base entry, which of its two lists, and (by
+// its operation) whether the list is copied (blank), has the frame appended (a new token) or has its last element
+// replaced by the frame (the same token again).  Step E copies tokens and both lists of the kept entries through their
+// sources; nothing is copied per slot.  The summed scores take the arithmetic of ctc_prefix_beam_kernel statement for
+// statement: a one-chunk call gives its hypotheses and scores bit for bit.
+__global__ __launch_bounds__(256) void ctc_prefix_beam_chunk_kernel(
+    const float *__restrict__ tkv, const int32_t *__restrict__ tki, const int32_t *__restrict__ lens, int T, int beam,
+    int blank, int reset, int Lcap, char *__restrict__ state, CtcStreamState lay,
+    int32_t *__restrict__ hyps /* [B][beam][Lcap] */, int32_t *__restrict__ hyp_lens, double *__restrict__ scores,
+    double *__restrict__ viterbi, int32_t *__restrict__ times /* [B][beam][Lcap] */, int32_t *__restrict__ n_hyps,
+    int32_t *__restrict__ n_frames)
+{
+    // current beam
+    __shared__ int c_len[kMaxCtcBeam], c_last[kMaxCtcBeam];
+    __shared__ unsigned long long c_hash[kMaxCtcBeam];
+    __shared__ double c_pb[kMaxCtcBeam], c_pnb[kMaxCtcBeam], c_vb[kMaxCtcBeam], c_vnb[kMaxCtcBeam];
+    // slots of this frame; s_v / s_p / s_list are the riders: Viterbi candidate, token log-probability, source list
+    __shared__ int s_base[kMaxSlots], s_tok[kMaxSlots], s_len[kMaxSlots], s_op[kMaxSlots], s_rep[kMaxSlots], s_rank[kMaxSlots];
+    __shared__ int s_list[kMaxSlots];
+    __shared__ float s_p[kMaxSlots];
+    __shared__ unsigned long long s_hash[kMaxSlots];
+    __shared__ double s_a[kMaxSlots], s_b[kMaxSlots], s_v[kMaxSlots];
+    // representatives: summed scores, Viterbi scores, the source slots of times_b / times_nb (-1: none)
+    __shared__ double r_pb[kMaxSlots], r_pnb[kMaxSlots], r_score[kMaxSlots], r_vb[kMaxSlots], r_vnb[kMaxSlots];
+    __shared__ int r_sb[kMaxSlots], r_snb[kMaxSlots];
+    __shared__ int order[kMaxCtcBeam];
+    __shared__ int s_nrep, s_wtot[4];
+    // next beam (staged so that the current one stays readable while it is built); t_sb / t_snb: base entry | list << 8
+    __shared__ int t_len[kMaxCtcBeam], t_last[kMaxCtcBeam], t_base[kMaxCtcBeam], t_tok[kMaxCtcBeam], t_sb[kMaxCtcBeam],
+        t_snb[kMaxCtcBeam];
+    __shared__ unsigned long long t_hash[kMaxCtcBeam];
+    __shared__ double t_pb[kMaxCtcBeam], t_pnb[kMaxCtcBeam], t_vb[kMaxCtcBeam], t_vnb[kMaxCtcBeam];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const double NINF = -__builtin_huge_val();
+    char *sb = state + (size_t)b * lay.stride;
+    int32_t *head = reinterpret_cast<int32_t *>(sb);
+    double *g_pb = reinterpret_cast<double *>(sb + lay.pb_off), *g_pnb = reinterpret_cast<double *>(sb + lay.pnb_off);
+    double *g_vb = reinterpret_cast<double *>(sb + lay.vb_off), *g_vnb = reinterpret_cast<double *>(sb + lay.vnb_off);
+    unsigned long long *g_hash = reinterpret_cast<unsigned long long *>(sb + lay.hash_off);
+    int32_t *g_len = reinterpret_cast<int32_t *>(sb + lay.len_off), *g_last = reinterpret_cast<int32_t *>(sb + lay.last_off);
+    int32_t *sq = reinterpret_cast<int32_t *>(sb + lay.seq_off);          // [list][buffer][beam][Lcap]
+    const size_t LB = (size_t)beam * Lcap;
+    // A block that no call with this (beam, Lcap) has written starts fresh, as after a reset: nothing read from it is
+    // used as an index before it has been checked.
+    const int marker = (int)(0x43544331u ^ ((unsigned)beam * 0x01000193u) ^ ((unsigned)Lcap * 0x9E3779B1u));
+    int a_next = head[1], ncur = head[2], sel = head[3] & 1;
+    const bool fresh = reset != 0 || head[0] != marker || a_next < 0 || a_next > Lcap || ncur < 1 || ncur > beam;
+    if (fresh) { a_next = 0; ncur = 1; sel = 0; }
+    if (fresh) {
+        if (tid == 0) {
+            c_len[0] = 0; c_last[0] = -1; c_hash[0] = 1469598103934665603ULL;
+            c_pb[0] = 0.0; c_pnb[0] = NINF; c_vb[0] = 0.0; c_vnb[0] = 0.0;
+        }
+    } else if (tid < ncur) {
+        const int l = g_len[tid];
+        c_len[tid] = l < 0 ? 0 : (l > a_next ? a_next : l);
+        c_last[tid] = g_last[tid]; c_hash[tid] = g_hash[tid];
+        c_pb[tid] = g_pb[tid]; c_pnb[tid] = g_pnb[tid]; c_vb[tid] = g_vb[tid]; c_vnb[tid] = g_vnb[tid];
+    }
+    int len = lens[b];
+    len = len < 0 ? 0 : (len > T ? T : len);
+    len = len > Lcap - a_next ? Lcap - a_next : len;                   // a prefix gains at most one token per frame
+    __syncthreads();
+    for (int t = 0; t < len; ++t) {
+        const int a = a_next + t;                                      // the frame's absolute index
+        const int32_t *cur = sq + (size_t)sel * LB;                    // tokens of the current beam
+        const size_t row = ((size_t)b * T + t) * beam;
+        // ---- A: slots, written densely in the reference's visiting order (one (symbol, prefix) pair per thread) ----
+        const int C = beam * ncur;                                    // <= 256
+        int tok0 = -1, op0 = kOpNone, tok1 = -1, op1 = kOpNone, pi = 0, ls0 = 1;
+        double a0 = NINF, b0 = NINF, a1 = NINF, v0 = NINF, v1 = NINF;
+        float pf = 0.f;
+        if (tid < C) {
+            const int k = tid / ncur;
+            pi = tid - k * ncur;
+            const int sym = tki[row + k];
+            pf = tkv[row + k];
+            const double ps = (double)pf;                             // logp[s].item()
+            const double pb = c_pb[pi], pnb = c_pnb[pi], vb = c_vb[pi], vnb = c_vnb[pi];
+            const bool from_b = vb > vnb;                             // vit(e), times(e): a tie takes the non-blank side
+            const double vit = from_b ? vb : vnb;
+            if (sym == blank) { op0 = kOpPb3; a0 = pb + ps; b0 = pnb + ps; v0 = vit + ps; ls0 = from_b ? 0 : 1; }
+            else if (sym == c_last[pi]) {
+                op0 = kOpPnb2; a0 = pnb + ps; v0 = vnb + ps; ls0 = 1;             // *ss -> *s
+                tok1 = sym; op1 = kOpPnb2; a1 = pb + ps; v1 = vb + ps;             // *s-s -> *ss
+            } else { tok0 = sym; op0 = kOpPnb3; a0 = pb + ps; b0 = pnb + ps; v0 = vit + ps; ls0 = from_b ? 0 : 1; }
+        }
+        const int lane = tid & 63, wave = tid >> 6;
+        const unsigned long long extra_mask = __ballot(op1 != kOpNone);
+        if (lane == 0) s_wtot[wave] = __popcll(extra_mask);
+        if (tid == 0) s_nrep = 0;
+        __syncthreads();
+        int dpos = tid + __popcll(extra_mask & ((1ull << lane) - 1ull));
+        for (int w = 0; w < wave; ++w) dpos += s_wtot[w];
+        const int nslot = C + s_wtot[0] + s_wtot[1] + s_wtot[2] + s_wtot[3];
+        if (tid < C) {
+            s_base[dpos] = pi; s_tok[dpos] = tok0; s_op[dpos] = op0; s_a[dpos] = a0; s_b[dpos] = b0;
+            s_v[dpos] = v0; s_p[dpos] = pf; s_list[dpos] = ls0;
+            s_len[dpos] = c_len[pi] + (tok0 >= 0 ? 1 : 0);
+            s_hash[dpos] = tok0 >= 0 ? c_hash[pi] * 1099511628211ULL + (unsigned long long)(tok0 + 1) : c_hash[pi];
+            s_rep[dpos] = dpos; s_rank[dpos] = 0;
+            if (op1 != kOpNone) {
+                const int d1 = dpos + 1;
+                s_base[d1] = pi; s_tok[d1] = tok1; s_op[d1] = op1; s_a[d1] = a1; s_b[d1] = NINF;
+                s_v[d1] = v1; s_p[d1] = pf; s_list[d1] = 0;
+                s_len[d1] = c_len[pi] + 1;
+                s_hash[d1] = c_hash[pi] * 1099511628211ULL + (unsigned long long)(tok1 + 1);
+                s_rep[d1] = d1; s_rank[d1] = 0;
+            }
+        }
+        __syncthreads();
+        // ---- B: representative = first slot with the same key (four threads per slot i, f < i) ----
+        for (int i = tid >> 2; i < nslot; i += 64) {
+            const int li_ = s_len[i];
+            const unsigned long long hi_ = s_hash[i];
+            for (int f = tid & 3; f < i; f += 4) {
+                if (s_len[f] != li_ || s_hash[f] != hi_) continue;
+                bool same = (s_base[f] == s_base[i] && s_tok[f] == s_tok[i]);
+                if (!same) {                                           // different spelling of (maybe) the same prefix
+                    const int bi = s_base[i], bf = s_base[f], ti = s_tok[i], tf = s_tok[f];
+                    const int li = c_len[bi], lf = c_len[bf];
+                    same = true;
+                    for (int q = li_ - 1; q >= 0 && same; --q) {
+                        const int x = q < li ? cur[(size_t)bi * Lcap + q] : ti;
+                        const int y = q < lf ? cur[(size_t)bf * Lcap + q] : tf;
+                        same = (x == y);
+                    }
+                }
+                if (same) atomicMin(&s_rep[i], f);
+            }
+        }
+        __syncthreads();
+        // ---- C: a representative applies its slots' operations, and their riders, in slot order ----
+        for (int i = tid; i < nslot; i += 256) {
+            if (s_rep[i] != i) continue;
+            double pb = NINF, pnb = NINF, vb = NINF, vnb = NINF;
+            float ctp = -__builtin_huge_valf();                        // best token log-probability that set times_nb
+            int sb_ = -1, snb = -1;
+            for (int f = i; f < nslot; ++f) {
+                if (s_rep[f] != i) continue;
+                const double v = s_v[f];
+                if (s_op[f] == kOpPb3) {
+                    pb = py_log_add3(pb, s_a[f], s_b[f]);
+                    vb = v; sb_ = f;
+                } else {
+                    if (s_op[f] == kOpPnb2) pnb = py_log_add2(pnb, s_a[f]);
+                    else pnb = py_log_add3(pnb, s_a[f], s_b[f]);
+                    if (vnb < v) {
+                        vnb = v;
+                        if (s_tok[f] >= 0) { ctp = s_p[f]; snb = f; }                 // a new last token at this frame
+                        else if (ctp < s_p[f]) { ctp = s_p[f]; snb = f; }             // the same token again: the better one
+                    }
+                }
+            }
+            r_pb[i] = pb; r_pnb[i] = pnb; r_vb[i] = vb; r_vnb[i] = vnb; r_sb[i] = sb_; r_snb[i] = snb;
+            r_score[i] = py_log_add2(pb, pnb);
+            atomicAdd(&s_nrep, 1);
+        }
+        __syncthreads();
+        // ---- D: stable descending rank among representatives (sorted(..., reverse=True) keeps insertion order on ties) ----
+        for (int i = tid >> 2; i < nslot; i += 64) {
+            if (s_rep[i] != i) continue;
+            const double me = r_score[i];
+            int cnt = 0;
+            for (int f = tid & 3; f < nslot; f += 4) {
+                if (s_rep[f] != f) continue;
+                const double ot = r_score[f];
+                cnt += (ot > me || (ot == me && f < i)) ? 1 : 0;
+            }
+            if (cnt) atomicAdd(&s_rank[i], cnt);
+        }
+        __syncthreads();
+        const int keep = s_nrep < beam ? s_nrep : beam;
+        for (int i = tid; i < nslot; i += 256)
+            if (s_rep[i] == i && s_rank[i] < beam) order[s_rank[i]] = i;
+        __syncthreads();
+        // ---- E: the next beam; tokens and both times lists go into the other buffers through their sources ----
+        if (tid < keep) {
+            const int f = order[tid];
+            t_base[tid] = s_base[f]; t_tok[tid] = s_tok[f];
+            t_len[tid] = s_len[f]; t_hash[tid] = s_hash[f]; t_pb[tid] = r_pb[f]; t_pnb[tid] = r_pnb[f];
+            t_vb[tid] = r_vb[f]; t_vnb[tid] = r_vnb[f];
+            t_last[tid] = s_tok[f] >= 0 ? s_tok[f] : c_last[s_base[f]];
+            const int gb = r_sb[f], gn = r_snb[f];
+            t_sb[tid] = gb >= 0 ? (s_base[gb] | (s_list[gb] << 8)) : -1;
+            t_snb[tid] = gn >= 0 ? (s_base[gn] | (s_list[gn] << 8)) : -1;
+        }
+        __syncthreads();
+        {
+            int maxn = 0;
+            for (int e = 0; e < keep; ++e) maxn = t_len[e] > maxn ? t_len[e] : maxn;
+            const int per = kCtcStreamLists * maxn;
+            for (int i = tid; i < keep * per; i += 256) {
+                const int e = i / per, r = i - e * per;
+                const int l = r / maxn, q = r - l * maxn;              // list, position
+                const int n = t_len[e];
+                if (q >= n || q >= Lcap) continue;
+                int val;
+                if (l == 0) {
+                    const int bs = t_base[e];
+                    val = q < c_len[bs] ? cur[(size_t)bs * Lcap + q] : t_tok[e];
+                } else {
+                    const int src = l == 1 ? t_sb[e] : t_snb[e];
+                    if (src < 0) continue;                             // that ending has no path: the list is never read
+                    // times_b: a copy.  times_nb: n - 1 elements of the source, then this frame (appended to a list of
+                    // n - 1, or in place of the last of n).
+                    const int32_t *sp = sq + (size_t)((1 + (src >> 8)) * 2 + sel) * LB + (size_t)(src & 255) * Lcap;
+                    val = (l == 2 && q == n - 1) ? a : sp[q];
+                }
+                sq[(size_t)(l * 2 + (1 - sel)) * LB + (size_t)e * Lcap + q] = val;
+            }
+        }
+        __syncthreads();
+        if (tid < keep) {
+            c_len[tid] = t_len[tid]; c_hash[tid] = t_hash[tid]; c_pb[tid] = t_pb[tid]; c_pnb[tid] = t_pnb[tid];
+            c_vb[tid] = t_vb[tid]; c_vnb[tid] = t_vnb[tid];
+            c_last[tid] = t_last[tid];
+        }
+        ncur = keep;
+        sel = 1 - sel;
+        __syncthreads();
+    }
+    a_next += len;
+    // ---- the beam goes back into the state block ----
+    if (tid < ncur) {
+        g_len[tid] = c_len[tid]; g_last[tid] = c_last[tid]; g_hash[tid] = c_hash[tid];
+        g_pb[tid] = c_pb[tid]; g_pnb[tid] = c_pnb[tid]; g_vb[tid] = c_vb[tid]; g_vnb[tid] = c_vnb[tid];
+    }
+    if (tid == 0) { head[0] = marker; head[1] = a_next; head[2] = ncur; head[3] = sel; }
+    // ---- export ----
+    const int n = ncur;
+    for (int i = tid; i < beam * Lcap; i += 256) {
+        const int e = i / Lcap, q = i - e * Lcap;
+        const bool in = e < n && q < c_len[e];
+        const size_t o = ((size_t)b * beam + e) * Lcap + q;
+        int tok = -1, tm = -1;
+        if (in) {
+            const double vb = c_vb[e], vnb = c_vnb[e];
+            const int li = vb > vnb ? 0 : 1;
+            tok = sq[(size_t)sel * LB + (size_t)e * Lcap + q];
+            if ((vb > vnb ? vb : vnb) > NINF) tm = sq[(size_t)((1 + li) * 2 + sel) * LB + (size_t)e * Lcap + q];
+        }
+        hyps[o] = tok;
+        times[o] = tm;
+    }
+    if (tid < beam) {
+        hyp_lens[(size_t)b * beam + tid] = tid < n ? c_len[tid] : 0;
+        scores[(size_t)b * beam + tid] = tid < n ? py_log_add2(c_pb[tid], c_pnb[tid]) : NINF;
+        viterbi[(size_t)b * beam + tid] = tid < n ? (c_vb[tid] > c_vnb[tid] ? c_vb[tid] : c_vnb[tid]) : NINF;
+    }
+    if (tid == 0) { n_hyps[b] = n; n_frames[b] = a_next; }
+}
+
 int ctc_dec_check(int B, int T, int V, int blank)
 {
     WR_REQUIRE(B > 0 && T > 0 && V > 1, WR_EINVAL, "ctc decode: B, T must be positive and V > 1 (got %d,%d,%d)", B, T, V);
@@ -348,6 +610,26 @@ int ctc_dec_check(int B, int T, int V, int blank)
 }
 
 }  // namespace
+
+int ctc_decode_check_shape(int B, int T, int V, int blank) { return ctc_dec_check(B, T, V, blank); }
+
+int ctc_prefix_beam_chunk_launch(const float *logits_d, const int32_t *lens_d, int B, int T, int V, int beam, int blank,
+                                 int reset, int Lcap, void *state_d, int32_t *hyps_d, int32_t *hyp_lens_d, double *scores_d,
+                                 double *viterbi_d, int32_t *times_d, int32_t *n_hyps_d, int32_t *n_frames_d,
+                                 void *workspace_d, void *stream)
+{
+    const CtcStreamWs w = ctc_stream_ws_layout(B, T, beam);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char *ws = static_cast<char *>(workspace_d);
+    // the frames' top-`beam` exactly as wr_ctc_prefix_beam_search finds them (dynamic LDS: one row of logits)
+    WR_TRY(launch("ctc_frame_topk_kernel", ctc_frame_topk_kernel, dim3(B * T), dim3(256), (size_t)V * sizeof(float), st, logits_d, V,
+                  beam, reinterpret_cast<float *>(ws + w.tkv_off), reinterpret_cast<int32_t *>(ws + w.tki_off)));
+    return launch("ctc_prefix_beam_chunk_kernel", ctc_prefix_beam_chunk_kernel, dim3(B), dim3(256), 0, st,
+                  reinterpret_cast<const float *>(ws + w.tkv_off), reinterpret_cast<const int32_t *>(ws + w.tki_off), lens_d, T, beam,
+                  blank, reset, Lcap, static_cast<char *>(state_d), ctc_stream_state_layout(beam, Lcap), hyps_d, hyp_lens_d,
+                  scores_d, viterbi_d, times_d, n_hyps_d, n_frames_d);
+}
+
 }  // namespace wr
 
 using namespace wr;

@@ -132,6 +132,88 @@ def ctc_prefix_beam_search(logits: torch.Tensor, lens: torch.Tensor, beam_size: 
     return [[(tuple(hc[b, e, :lc[b][e]].tolist()), scc[b][e]) for e in range(nc[b])] for b in range(B)]
 
 
+class CtcPrefixBeamStream:
+    """CTC prefix beam search continued chunk by chunk, for `n_streams` streams at once, with the Viterbi score and
+    the frame of every token of each hypothesis (runtime/core/decoder/ctc_prefix_beam_search.cc:107-211: `Search()` per
+    encoder chunk, `viterbi_likelihood()`, `Times()`; the contract is in include/wr_api.h, "Streaming CTC prefix beam
+    search").  Owns the state block; `max_frames` bounds the frames (chunk widths summed) between two resets.
+
+    search(logits_chunk (n_streams, T, V) pre-softmax, lens (n_streams,)) consumes lens[b] <= T frames of stream b
+    (0 leaves it untouched) and returns per stream [(tokens tuple, score, viterbi_score, times tuple)], best first;
+    `frames` then holds the frames each stream has consumed.  `state`: a caller's uint8 device tensor to use as the
+    state block (at least wr_ctc_stream_state_bytes(n_streams, beam_size, max_frames) bytes) instead of one allocated by
+    the first search; whatever it holds, a new object or a reset() starts every stream fresh."""
+
+    def __init__(self, n_streams: int, beam_size: int, max_frames: int, blank: int = 0, state: torch.Tensor = None):
+        self.n_streams, self.beam_size, self.max_frames, self.blank = int(n_streams), int(beam_size), int(max_frames), int(blank)
+        if self.n_streams < 1 or self.max_frames < 1 or not 1 <= self.beam_size <= 16:
+            raise RuntimeError(f"CtcPrefixBeamStream: n_streams={n_streams}, beam_size={beam_size} (1..16), "
+                               f"max_frames={max_frames} must be positive")
+        self._state = state             # allocated by the first search (on the chunk's device) unless the caller lends one
+        self._vocab = None
+        self.frames = [0] * self.n_streams
+        self.reset()
+
+    def reset(self) -> None:
+        """Every stream starts fresh with the next search."""
+        self._fresh = True
+        self._frames_done = 0
+        self.frames = [0] * self.n_streams
+
+    def search(self, logits_chunk: torch.Tensor, lens: torch.Tensor):
+        if logits_chunk.dim() != 3:
+            raise RuntimeError("CtcPrefixBeamStream: the chunk must be (n_streams, frames, vocab)")
+        B, T, V = logits_chunk.shape
+        if B != self.n_streams:
+            raise RuntimeError(f"CtcPrefixBeamStream: chunk has {B} streams, the stream set has {self.n_streams}")
+        if self._vocab is not None and V != self._vocab:
+            raise RuntimeError(f"CtcPrefixBeamStream: vocabulary changed from {self._vocab} to {V}")
+        if self._frames_done + T > self.max_frames:
+            raise RuntimeError(f"CtcPrefixBeamStream: {self._frames_done} frames done + a chunk of {T} exceeds "
+                               f"max_frames={self.max_frames}")
+        if not logits_chunk.is_cuda:
+            raise RuntimeError("wenet_celoss_amd.CtcPrefixBeamStream: logits must live on a HIP device (no CPU path)")
+        x = logits_chunk.detach().float().contiguous()
+        dev = x.device
+        beam, cap = self.beam_size, self.max_frames
+        need = _lib.load().wr_ctc_stream_state_bytes(B, beam, cap)
+        if self._state is None:
+            self._state = torch.empty(need, dtype=torch.uint8, device=dev)
+        elif self._state.device != dev or self._state.numel() < need or self._state.dtype != torch.uint8:
+            raise RuntimeError(f"CtcPrefixBeamStream: the state tensor must be uint8 on {dev} with at least {need} bytes")
+        ln = lens.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        if ln.numel() != B:
+            raise RuntimeError(f"CtcPrefixBeamStream: lens has {ln.numel()} elements for {B} streams")
+        ws = _lib.workspace("wr_ctc_stream_workspace_bytes", B, T, beam, device=dev)
+        hyps = torch.empty(B, beam, cap, dtype=torch.int32, device=dev)
+        tm = torch.empty(B, beam, cap, dtype=torch.int32, device=dev)
+        hl = torch.empty(B, beam, dtype=torch.int32, device=dev)
+        sc = torch.empty(B, beam, dtype=torch.float64, device=dev)
+        vt = torch.empty(B, beam, dtype=torch.float64, device=dev)
+        nh = torch.empty(B, dtype=torch.int32, device=dev)
+        nf = torch.empty(B, dtype=torch.int32, device=dev)
+        _lib.call("wr_ctc_prefix_beam_search_chunk", x, ln, B, T, V, beam, self.blank, int(self._fresh), self._frames_done,
+                  cap, self._state, self._state.numel(), hyps, hl, sc, vt, tm, nh, nf, ws, ws.numel(), device=dev)
+        self._fresh = False
+        self._frames_done += T
+        self._vocab = V
+        lc, scc, vtc, nc = hl.cpu().tolist(), sc.cpu().tolist(), vt.cpu().tolist(), nh.cpu().tolist()
+        self.frames = nf.cpu().tolist()
+        width = max(max(row) for row in lc)
+        hc, tc = hyps[:, :, :width].cpu().tolist(), tm[:, :, :width].cpu().tolist()      # nested lists: one conversion each
+        return [[(tuple(hc[b][e][:lc[b][e]]), scc[b][e], vtc[b][e], tuple(tc[b][e][:lc[b][e]]))
+                 for e in range(nc[b])] for b in range(B)]
+
+
+def ctc_prefix_beam_search_times(logits: torch.Tensor, lens: torch.Tensor, beam_size: int, blank: int = 0):
+    """ctc_prefix_beam_search over whole utterances (B, T, V) with, per hypothesis, the Viterbi score and the frame of
+    every token: per utterance [(prefix tuple, score, viterbi_score, times tuple)] best first.  Prefixes and scores
+    are those of ctc_prefix_beam_search, which stays the entry point when the times are not needed."""
+    if not logits.is_cuda:
+        raise RuntimeError("wenet_celoss_amd.ctc_prefix_beam_search_times: logits must live on a HIP device (no CPU path)")
+    return CtcPrefixBeamStream(logits.shape[0], beam_size, logits.shape[1], blank=blank).search(logits, lens)
+
+
 def forced_align(ctc_probs: torch.Tensor, y: torch.Tensor, blank_id: int = 0) -> list:
     """wenet/utils/ctc_util.py:27-83: ctc_probs (T, D) log-posteriors, y (L,) label ids -> per-frame token list."""
     return forced_align_batch(ctc_probs.unsqueeze(0), y.reshape(1, -1), torch.tensor([ctc_probs.size(0)]),

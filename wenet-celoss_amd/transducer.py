@@ -613,6 +613,22 @@ class Transducer(nn.Module):
                                                num_decoding_left_chunks, simulate_streaming)
         return hyps[0]
 
+    def ctc_prefix_beam_search_times(self, speech: torch.Tensor, speech_lengths: torch.Tensor, beam_size: int,
+                                     decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1,
+                                     simulate_streaming: bool = False):
+        """The n-best of ctc_prefix_beam_search with, per hypothesis, the Viterbi score and the frame of every token
+        (the runtime's viterbi_likelihood() / Times(), ctc_prefix_beam_search.cc:107-211), for any batch size:
+        per utterance [(prefix, score, viterbi_score, times)] best first."""
+        from .ctc import ctc_prefix_beam_search_times
+        assert speech.shape[0] == speech_lengths.shape[0]
+        assert decoding_chunk_size != 0
+        encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
+                                                          num_decoding_left_chunks, simulate_streaming)
+        encoder_out_lens = encoder_mask.squeeze(1).sum(1)
+        with torch.no_grad():
+            logits = self.ctc.ctc_lo(encoder_out)
+        return ctc_prefix_beam_search_times(logits, encoder_out_lens, beam_size)
+
     # ------------------------------------------- ASRModel surface the reference class inherits (asr_model.py) --
     # The reference's Transducer IS an ASRModel (transducer.py:20), so wenet/bin/recognize.py may call `recognize`
     # (--mode attention, recognize.py:259) and `attention_rescoring` (--mode attention_rescoring, :351) on it, and
@@ -896,6 +912,23 @@ class Transducer(nn.Module):
         st["fresh"] = False
         self._stream_dec = dec
         return hyps[0] if N == 1 else hyps
+
+    # ------------------- streaming CTC prefix beam search (runtime/core/decoder/ctc_prefix_beam_search.cc:107-211) --
+    def reset_ctc_stream(self, n_streams: int = 1, beam_size: int = 10, max_frames: int = 4096) -> None:
+        """Start `n_streams` fresh CTC prefix-beam streams; `max_frames` bounds the encoder frames (chunk widths summed)
+        a stream may take before the next reset."""
+        from .ctc import CtcPrefixBeamStream
+        self._ctc_stream = CtcPrefixBeamStream(n_streams, beam_size, max_frames, blank=0)
+
+    def forward_ctc_prefix_beam_search(self, encoder_out_chunk: torch.Tensor, encoder_out_lens: torch.Tensor):
+        """Feed the next chunk of encoder frames of every stream, encoder_out_chunk (N, Tchunk, E) with encoder_out_lens
+        (N,) valid frames each (0: the stream is left untouched) -> the partial n-best of every stream,
+        [(prefix, score, viterbi_score, times)] best first; times are encoder frames since the reset."""
+        if getattr(self, "_ctc_stream", None) is None:
+            self.reset_ctc_stream(encoder_out_chunk.size(0))
+        with torch.no_grad():
+            logits = self.ctc.ctc_lo(encoder_out_chunk)
+        return self._ctc_stream.search(logits, encoder_out_lens)
 
     # ----------------------------------------------------- step exports (:600-629) --
     # @torch.jit.export as in the reference, so that torch.jit.script(model) (train.py:203-205, export_jit.py) yields an
