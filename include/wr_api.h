@@ -645,6 +645,63 @@ int wr_ctc_prefix_beam_search_chunk(const float *logits_d, const int32_t *lens_d
                                     int32_t *times_d, int32_t *n_hyps_d, int32_t *n_frames_d, void *workspace_d,
                                     size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Context-graph biasing in the CTC prefix beam search: the streaming search above with the classical phrase biasing of
+ * the reference runtime (runtime/core/decoder/context_graph.{h,cc}, ctc_prefix_beam_search.h:53-83 and
+ * ctc_prefix_beam_search.cc:137-193, 213-234: UpdateContext / CopyContext, total_score(), UpdateFinalContext()).
+ * Everything the contract above says of a frame holds unchanged -- the top-`beam` symbols, the visiting order, the
+ * float64 sums, the Viterbi riders, the times; what follows is what is added.
+ *
+ * The graph is a deterministic table of S states in device memory, state 0 the root:
+ *   arc_begin int32[S+1]  CSR offsets into the arcs      arc_token int32[A]  strictly increasing within a state
+ *   arc_next  int32[A]                                   arc_score float32[A]
+ *   escape    float32[S], escape[0] = 0                  final     int32[S], final[0] = 1
+ *   next(state, token) = (arc_next, arc_score, state == 0, final[arc_next] != 0)   if state has an arc on token
+ *                      = (0, escape[state], false, false)                           otherwise
+ * (context_graph.cc:86-108: the token that breaks a partial match is not retried from the root.)
+ *
+ * Every entry also holds ctx_state (int32), ctx_score (float64) and tags, one int32 per token: bit 0 a start boundary
+ * at this token, bit 1 an end boundary at this token.  A fresh stream's entry has ctx_state = 0, ctx_score = 0, no tags.
+ * A contribution that leaves the prefix unchanged (a blank, the same token again) copies the three fields of its source
+ * entry e; one that appends token s takes (st, sc, start, end) = next(e.ctx_state, s) and sets ctx_state = st,
+ * ctx_score = e.ctx_score + (double)sc, tags = e.tags + (start | end << 1,).  The table is deterministic and copies keep
+ * the state, so the three fields are a function of the token sequence alone: every contributor to a key sets the same
+ * values (the reference lets the first one set them).  After the frame: stable descending sort by
+ * total = log_add(pb, pnb) + ctx_score, in float64; the first `beam` entries are the new list.
+ *
+ * Export.  Beside the plain call's outputs: ctc_scores [B, beam] float64 = log_add(pb, pnb); context_scores [B, beam]
+ * float64; tags [B, beam, Lcap] (padded with -1); context_states [B, beam] (the entry's ctx_state as the stream holds
+ * it).  scores = ctc_scores + context_scores, the float64 add of the prune.  finalize != 0 exports "as if the stream
+ * ended here" (UpdateFinalContext): for every entry with ctx_state != 0 the exported context score gains
+ * (double)escape[ctx_state], then the exported list is sorted again, stable and descending, by the new totals.  Tags
+ * are not touched (a start tag of an abandoned match stays, as in the reference), and neither is the state block: the
+ * caller may go on feeding chunks.  A chunk with every lens[b] == 0 is legal: it finalises without new frames.
+ *
+ * Two departures from the reference, both deliberate: the bonus is summed in float64 (the reference's is a float), and
+ * the graph is whatever table the caller built -- the Python builder commits a phrase that is a proper prefix of
+ * another at its last token, where determinising the reference's FST would take that bonus back.
+ *
+ * The state block has its own layout (a fourth double-buffered list for the tags, two more scalars per entry) and its
+ * own size query; the plain block and wr_ctc_stream_state_bytes are unchanged, and a block written by one form starts
+ * fresh under the other.  The workspace is wr_ctc_stream_workspace_bytes(B, T, beam).  Refused before any HIP call, in
+ * this order: everything wr_ctc_prefix_beam_search_chunk refuses, in its order (a null output among the four new ones
+ * counts with the null pointers); S < 1 or A < 0, then a null table pointer (WR_EINVAL); S > 65536 or A > 1048576
+ * (WR_EUNSUPPORTED).  The table's contents are the builder's responsibility: the kernel clamps every arc_next it reads
+ * into [0, S) and every CSR bound into [0, A] before using it as an index, so a bad table gives wrong bonuses, never an
+ * out-of-range access.  Addition only: WR_API_VERSION stays 3.
+ * ---------------------------------------------------------------------- */
+size_t wr_ctc_context_stream_state_bytes(int B, int beam, int Lcap);
+
+int wr_ctc_prefix_beam_search_context_chunk(const float *logits_d, const int32_t *lens_d, int B, int T, int V, int beam,
+                                            int blank, int reset, int frames_done, int Lcap, void *state_d,
+                                            size_t state_bytes, const int32_t *arc_begin_d, const int32_t *arc_token_d,
+                                            const int32_t *arc_next_d, const float *arc_score_d, const float *escape_d,
+                                            const int32_t *final_d, int S, int A, int finalize, int32_t *hyps_d,
+                                            int32_t *hyp_lens_d, double *scores_d, double *viterbi_d, int32_t *times_d,
+                                            int32_t *n_hyps_d, int32_t *n_frames_d, double *ctc_scores_d,
+                                            double *context_scores_d, int32_t *tags_d, int32_t *context_states_d,
+                                            void *workspace_d, size_t workspace_bytes, void *stream);
+
 /* RNN-T forced alignment: the single best path through the lattice of wr_rnnt_loss_fwd (a Viterbi pass: the forward
  * sweep with max in place of log-add-exp, one decision bit per cell, and a backtrace).  No reference call site: the
  * reference aligns with the CTC head only (wenet/bin/alignment.py); this is the transducer head's counterpart.

@@ -287,6 +287,71 @@ def bench_ctcstream(args):
                       "CtcPrefixBeamStream_16_frame_chunks_ms": round(timed(stream_py, args.steps), 3)}), flush=True)
 
 
+def bench_ctcctx(args):
+    """The biased chunk call beside the plain one on the shape of `ctcstream` (B=32 streams x T=1000 frames, V=5000,
+    beam 10, 16-frame chunks), the graph 1000 random 3-token phrases: device time of the raw entry points on preallocated
+    buffers (median of event timings), in one chunk and in 16-frame chunks, and the biased call again with an empty
+    graph, which isolates what the added state traffic and export cost from what the arc lookups cost."""
+    import numpy as np
+    import wenet_celoss_amd as wc
+    from wenet_celoss_amd import _lib
+    dev = torch.device("cuda:0")
+    torch.manual_seed(7)
+    B, T, V, beam, W = args.B, args.T, args.V, 10, 16
+    x = torch.randn(B, T, V, device=dev) * 3
+    x[..., 0] += 14.0                                  # the input of bench_ctcstream
+    lens = torch.full((B,), T, dtype=torch.int32, device=dev)
+    base = {"B": B, "T": T, "V": V, "beam": beam}
+    i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
+    hl, cs, nh, nf = torch.empty(B, beam, **i32), torch.empty(B, beam, **i32), torch.empty(B, **i32), torch.empty(B, **i32)
+    sc, vt, cc, cx = (torch.empty(B, beam, **f64) for _ in range(4))
+    hyps, tm, tg = (torch.empty(B, beam, T, **i32) for _ in range(3))
+    rng = np.random.default_rng(11)
+    graph = wc.ContextGraph(rng.integers(1, V, size=(1000, 3)).tolist(), 3.0)
+    empty = wc.ContextGraph([])
+    state = _lib.workspace("wr_ctc_stream_state_bytes", B, beam, T, device=dev)
+    cstate = _lib.workspace("wr_ctc_context_stream_state_bytes", B, beam, T, device=dev)
+
+    def plain(xc, ln, Tc, reset, done, ws):
+        _lib.call("wr_ctc_prefix_beam_search_chunk", xc, ln, B, Tc, V, beam, 0, reset, done, T, state, state.numel(), hyps, hl,
+                  sc, vt, tm, nh, nf, ws, ws.numel(), device=dev)
+
+    def biased(g):
+        def call(xc, ln, Tc, reset, done, ws):
+            _lib.call("wr_ctc_prefix_beam_search_context_chunk", xc, ln, B, Tc, V, beam, 0, reset, done, T, cstate,
+                      cstate.numel(), *g.to(dev), g.n_states, g.n_arcs, 0, hyps, hl, sc, vt, tm, nh, nf, cc, cx, tg, cs, ws,
+                      ws.numel(), device=dev)
+        return call
+
+    ws1 = _lib.workspace("wr_ctc_stream_workspace_bytes", B, T, beam, device=dev)
+    wsc = _lib.workspace("wr_ctc_stream_workspace_bytes", B, W, beam, device=dev)
+    parts = [x[:, t0:t0 + W].contiguous() for t0 in range(0, T, W)]
+    plens = [torch.full((B,), p.shape[1], dtype=torch.int32, device=dev) for p in parts]
+
+    def chunked(call):
+        done = 0
+        for p, ln in zip(parts, plens):
+            call(p, ln, p.shape[1], int(done == 0), done, wsc)
+            done += p.shape[1]
+
+    rows = {}
+    for name, call in (("plain", plain), ("biased", biased(graph)), ("biased, empty graph", biased(empty))):
+        one = timeit(lambda: call(x, lens, T, 1, 0, ws1), args.steps)
+        ref = (hyps.clone(), sc.clone())
+        many = timeit(lambda: chunked(call), args.steps)
+        rows[name] = (one, many)
+        extra = {}
+        if name != "plain":
+            extra = {"one_chunk_vs_plain": round(one / rows["plain"][0], 3), "chunks_vs_plain": round(many / rows["plain"][1], 3),
+                     "chunked_bit_identical_to_one_chunk": bool(torch.equal(ref[0], hyps) and torch.equal(ref[1], sc))}
+        if name == "biased":
+            extra.update({"states": graph.n_states, "arcs": graph.n_arcs, "hyps_with_a_bonus": int((cx != 0).sum()),
+                          "tokens_per_hyp": round(float(hl.float().mean()), 1)})
+        print(json.dumps({"what": f"ctc prefix beam chunk call, {name}", **base, "one_chunk_ms": round(one, 3),
+                          "chunks": len(parts), "chunks_ms_total": round(many, 3), "ms_per_chunk": round(many / len(parts), 4),
+                          **extra}), flush=True)
+
+
 def bench_greedy(args):
     """BASELINE config 3: B=64 streams, chunks of 16 encoder frames, V=5000, LSTM 2x256, J=512, n_steps=64."""
     import time
@@ -1296,7 +1361,7 @@ def bench_tdtbeam(args):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align", "simple", "smoothed", "pruned", "tdt",
-                                     "tdtstep", "tdtalign", "tdtdec", "tdtbeam", "ctcstream"])
+                                     "tdtstep", "tdtalign", "tdtdec", "tdtbeam", "ctcstream", "ctcctx"])
     ap.add_argument("--durations", type=int, default=5, help="tdt, tdtstep, tdtalign: number of durations D (the set is 0 .. D-1)")
     ap.add_argument("--n-steps", type=int, default=64)
     ap.add_argument("--chunks", type=int, default=4)
@@ -1335,4 +1400,4 @@ if __name__ == "__main__":
     {"joint": bench_joint, "ctc": bench_ctc, "greedy": bench_greedy, "beam": bench_beam, "step": bench_step, "ctcdec": bench_ctcdec, "hotword": bench_hotword,
      "align": bench_align, "simple": bench_simple, "smoothed": bench_smoothed, "pruned": bench_pruned,
      "tdt": bench_tdt, "tdtstep": bench_tdtstep, "tdtalign": bench_tdtalign, "tdtdec": bench_tdtdec,
-     "tdtbeam": bench_tdtbeam, "ctcstream": bench_ctcstream}[a.what](a)
+     "tdtbeam": bench_tdtbeam, "ctcstream": bench_ctcstream, "ctcctx": bench_ctcctx}[a.what](a)

@@ -9,6 +9,8 @@ from . import _lib  # noqa: F401
 from .rnnt_loss import rnnt_loss, RNNTLoss  # noqa: F401
 from .ctc import CTC, ctc_loss, ctc_greedy_search, ctc_prefix_beam_search, forced_align, forced_align_batch  # noqa: F401
 from .ctc import CtcPrefixBeamStream, ctc_prefix_beam_search_times  # noqa: F401
+from .ctc import CtcContextPrefixBeamStream, ctc_context_prefix_beam_search  # noqa: F401
+from .context_graph import ContextGraph  # noqa: F401
 from .joint import TransducerJoint, joint_logits  # noqa: F401
 from .fused import joint_rnnt_loss, joint_rnnt_tdt_loss  # noqa: F401
 from .rnnt_align import joint_rnnt_forced_align, rnnt_forced_align, rnnt_frame_tokens  # noqa: F401
@@ -31,4 +33,5 @@ __all__ = ["rnnt_loss", "RNNTLoss", "CTC", "ctc_loss", "TransducerJoint", "joint
            "joint_rnnt_forced_align", "rnnt_frame_tokens", "rnnt_loss_simple", "rnnt_simple_forced_align", "rnnt_loss_smoothed",
            "get_rnnt_prune_ranges", "do_rnnt_pruning", "rnnt_loss_pruned", "k2",
            "rnnt_tdt_loss", "TDTLoss", "rnnt_tdt_lattice", "joint_rnnt_tdt_loss", "tdt_greedy_search", "rnnt_tdt_forced_align",
-           "tdt_prefix_beam_search", "CtcPrefixBeamStream", "ctc_prefix_beam_search_times"]
+           "tdt_prefix_beam_search", "CtcPrefixBeamStream", "ctc_prefix_beam_search_times",
+           "ContextGraph", "CtcContextPrefixBeamStream", "ctc_context_prefix_beam_search"]

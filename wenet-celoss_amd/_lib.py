@@ -197,6 +197,11 @@ SIGNATURES = {
     "wr_ctc_stream_workspace_bytes": (_sz, [_i, _i, _i]),
     "wr_ctc_prefix_beam_search_chunk": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp,
                                              _vp, _vp, _sz, _vp]),
+    "wr_ctc_context_stream_state_bytes": (_sz, [_i, _i, _i]),
+    "wr_ctc_prefix_beam_search_context_chunk": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz,
+                                                     _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i,
+                                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                     _vp, _sz, _vp]),
 }
 
 

@@ -353,13 +353,48 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_kernel(
 // replaced by the frame (the same token again).  Step E copies tokens and both lists of the kept entries through their
 // sources; nothing is copied per slot.  The summed scores take the arithmetic of ctc_prefix_beam_kernel statement for
 // statement: a one-chunk call gives its hypotheses and scores bit for bit.
+//
+// CTX = true is the biased twin (include/wr_api.h, "Context-graph biasing in the CTC prefix beam search").  An entry
+// also carries a context-graph state, a float64 bonus and one tag per token; all three are a function of the token
+// sequence alone, so nothing is kept per slot: step C looks the arc up once for a key's representative and ranks by
+// log_add(pb, pnb) + bonus, step E looks it up again for the at most `beam` kept entries, and the tags are a fourth list
+// that travels with the tokens.  CTX = false compiles to the plain search: every added statement is under `if constexpr`.
+
+// next(state, token) of the context graph: runtime/core/decoder/context_graph.cc:86-108 on a table.  `state` is inside
+// [0, S); every CSR bound is clamped into [0, A] and every arc_next into [0, S) before it is used as an index.
+__device__ __forceinline__ void ctc_context_next(const CtcContextGraph &g, int state, int tok, int &st, float &sc, int &tag)
+{
+    int lo = g.arc_begin[state], end = g.arc_begin[state + 1];
+    lo = lo < 0 ? 0 : (lo > g.A ? g.A : lo);
+    end = end < lo ? lo : (end > g.A ? g.A : end);
+    int hi = end;
+    while (lo < hi) {                                                  // first arc whose token is >= tok
+        const int mid = (lo + hi) >> 1;
+        if (g.arc_token[mid] < tok) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo < end && g.arc_token[lo] == tok) {
+        int nx = g.arc_next[lo];
+        nx = nx < 0 ? 0 : (nx >= g.S ? g.S - 1 : nx);
+        st = nx; sc = g.arc_score[lo];
+        tag = (state == 0 ? 1 : 0) | (g.final_[nx] != 0 ? 2 : 0);
+    } else { st = 0; sc = g.escape[state]; tag = 0; }                 // the breaking token is not retried from the root
+}
+
+template <bool CTX>
 __global__ __launch_bounds__(256) void ctc_prefix_beam_chunk_kernel(
     const float *__restrict__ tkv, const int32_t *__restrict__ tki, const int32_t *__restrict__ lens, int T, int beam,
     int blank, int reset, int Lcap, char *__restrict__ state, CtcStreamState lay,
     int32_t *__restrict__ hyps /* [B][beam][Lcap] */, int32_t *__restrict__ hyp_lens, double *__restrict__ scores,
     double *__restrict__ viterbi, int32_t *__restrict__ times /* [B][beam][Lcap] */, int32_t *__restrict__ n_hyps,
-    int32_t *__restrict__ n_frames)
+    int32_t *__restrict__ n_frames, CtcContextGraph cg, CtcContextOut cx)
 {
+    constexpr int kLists = CTX ? kCtcContextLists : kCtcStreamLists;
+    // the context of the current and the next beam, and the export order after finalisation (CTX only; 16 entries each)
+    __shared__ int c_cst[CTX ? kMaxCtcBeam : 1], t_cst[CTX ? kMaxCtcBeam : 1], t_tag[CTX ? kMaxCtcBeam : 1],
+        x_pos[CTX ? kMaxCtcBeam : 1];
+    __shared__ double c_csc[CTX ? kMaxCtcBeam : 1], t_csc[CTX ? kMaxCtcBeam : 1], x_ctc[CTX ? kMaxCtcBeam : 1],
+        x_ctx[CTX ? kMaxCtcBeam : 1];
     // current beam
     __shared__ int c_len[kMaxCtcBeam], c_last[kMaxCtcBeam];
     __shared__ unsigned long long c_hash[kMaxCtcBeam];
@@ -392,7 +427,10 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_chunk_kernel(
     const size_t LB = (size_t)beam * Lcap;
     // A block that no call with this (beam, Lcap) has written starts fresh, as after a reset: nothing read from it is
     // used as an index before it has been checked.
-    const int marker = (int)(0x43544331u ^ ((unsigned)beam * 0x01000193u) ^ ((unsigned)Lcap * 0x9E3779B1u));
+    const int marker = (int)((CTX ? 0x43544358u : 0x43544331u) ^ ((unsigned)beam * 0x01000193u) ^ ((unsigned)Lcap * 0x9E3779B1u));
+    int32_t *g_cst = reinterpret_cast<int32_t *>(sb + lay.cst_off);       // CTX only
+    double *g_csc = reinterpret_cast<double *>(sb + lay.csc_off);
+    int32_t *tq = reinterpret_cast<int32_t *>(sb + lay.tag_off);         // [buffer][beam][Lcap], CTX only
     int a_next = head[1], ncur = head[2], sel = head[3] & 1;
     const bool fresh = reset != 0 || head[0] != marker || a_next < 0 || a_next > Lcap || ncur < 1 || ncur > beam;
     if (fresh) { a_next = 0; ncur = 1; sel = 0; }
@@ -400,12 +438,18 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_chunk_kernel(
         if (tid == 0) {
             c_len[0] = 0; c_last[0] = -1; c_hash[0] = 1469598103934665603ULL;
             c_pb[0] = 0.0; c_pnb[0] = NINF; c_vb[0] = 0.0; c_vnb[0] = 0.0;
+            if constexpr (CTX) { c_cst[0] = 0; c_csc[0] = 0.0; }
         }
     } else if (tid < ncur) {
         const int l = g_len[tid];
         c_len[tid] = l < 0 ? 0 : (l > a_next ? a_next : l);
         c_last[tid] = g_last[tid]; c_hash[tid] = g_hash[tid];
         c_pb[tid] = g_pb[tid]; c_pnb[tid] = g_pnb[tid]; c_vb[tid] = g_vb[tid]; c_vnb[tid] = g_vnb[tid];
+        if constexpr (CTX) {
+            const int cs = g_cst[tid];                                 // an index into the table: clamped like every other
+            c_cst[tid] = cs < 0 ? 0 : (cs >= cg.S ? cg.S - 1 : cs);
+            c_csc[tid] = g_csc[tid];
+        }
     }
     int len = lens[b];
     len = len < 0 ? 0 : (len > T ? T : len);
@@ -504,6 +548,17 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_chunk_kernel(
             }
             r_pb[i] = pb; r_pnb[i] = pnb; r_vb[i] = vb; r_vnb[i] = vnb; r_sb[i] = sb_; r_snb[i] = snb;
             r_score[i] = py_log_add2(pb, pnb);
+            if constexpr (CTX) {                                       // total_score(): the prune ranks by score + bonus
+                const int e = s_base[i], tk = s_tok[i];
+                double bonus = c_csc[e];
+                if (tk >= 0) {
+                    int st_, tg_;
+                    float sc_;
+                    ctc_context_next(cg, c_cst[e], tk, st_, sc_, tg_);
+                    bonus += (double)sc_;
+                }
+                r_score[i] = r_score[i] + bonus;
+            }
             atomicAdd(&s_nrep, 1);
         }
         __syncthreads();
@@ -527,6 +582,17 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_chunk_kernel(
         // ---- E: the next beam; tokens and both times lists go into the other buffers through their sources ----
         if (tid < keep) {
             const int f = order[tid];
+            if constexpr (CTX) {                                       // the kept entries look their arc up again
+                const int e = s_base[f], tk = s_tok[f];
+                int st_ = c_cst[e], tg_ = 0;
+                double bonus = c_csc[e];
+                if (tk >= 0) {
+                    float sc_;
+                    ctc_context_next(cg, c_cst[e], tk, st_, sc_, tg_);
+                    bonus += (double)sc_;
+                }
+                t_cst[tid] = st_; t_csc[tid] = bonus; t_tag[tid] = tg_;
+            }
             t_base[tid] = s_base[f]; t_tok[tid] = s_tok[f];
             t_len[tid] = s_len[f]; t_hash[tid] = s_hash[f]; t_pb[tid] = r_pb[f]; t_pnb[tid] = r_pnb[f];
             t_vb[tid] = r_vb[f]; t_vnb[tid] = r_vnb[f];
@@ -539,7 +605,7 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_chunk_kernel(
         {
             int maxn = 0;
             for (int e = 0; e < keep; ++e) maxn = t_len[e] > maxn ? t_len[e] : maxn;
-            const int per = kCtcStreamLists * maxn;
+            const int per = kLists * maxn;
             for (int i = tid; i < keep * per; i += 256) {
                 const int e = i / per, r = i - e * per;
                 const int l = r / maxn, q = r - l * maxn;              // list, position
@@ -549,6 +615,10 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_chunk_kernel(
                 if (l == 0) {
                     const int bs = t_base[e];
                     val = q < c_len[bs] ? cur[(size_t)bs * Lcap + q] : t_tok[e];
+                } else if (CTX && l == 3) {                            // the tags: the tokens' source, the same double buffer
+                    const int bs = t_base[e];
+                    if (q < c_len[bs]) tq[(size_t)(1 - sel) * LB + (size_t)e * Lcap + q] = tq[(size_t)sel * LB + (size_t)bs * Lcap + q];
+                    continue;                                          // the appended token's tag follows the loop
                 } else {
                     const int src = l == 1 ? t_sb[e] : t_snb[e];
                     if (src < 0) continue;                             // that ending has no path: the list is never read
@@ -559,12 +629,19 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_chunk_kernel(
                 }
                 sq[(size_t)(l * 2 + (1 - sel)) * LB + (size_t)e * Lcap + q] = val;
             }
+            if constexpr (CTX) {
+                if (tid < keep && t_tok[tid] >= 0) {
+                    const int lb = c_len[t_base[tid]];
+                    if (lb < Lcap) tq[(size_t)(1 - sel) * LB + (size_t)tid * Lcap + lb] = t_tag[tid];
+                }
+            }
         }
         __syncthreads();
         if (tid < keep) {
             c_len[tid] = t_len[tid]; c_hash[tid] = t_hash[tid]; c_pb[tid] = t_pb[tid]; c_pnb[tid] = t_pnb[tid];
             c_vb[tid] = t_vb[tid]; c_vnb[tid] = t_vnb[tid];
             c_last[tid] = t_last[tid];
+            if constexpr (CTX) { c_cst[tid] = t_cst[tid]; c_csc[tid] = t_csc[tid]; }
         }
         ncur = keep;
         sel = 1 - sel;
@@ -575,10 +652,62 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_chunk_kernel(
     if (tid < ncur) {
         g_len[tid] = c_len[tid]; g_last[tid] = c_last[tid]; g_hash[tid] = c_hash[tid];
         g_pb[tid] = c_pb[tid]; g_pnb[tid] = c_pnb[tid]; g_vb[tid] = c_vb[tid]; g_vnb[tid] = c_vnb[tid];
+        if constexpr (CTX) { g_cst[tid] = c_cst[tid]; g_csc[tid] = c_csc[tid]; }
     }
     if (tid == 0) { head[0] = marker; head[1] = a_next; head[2] = ncur; head[3] = sel; }
     // ---- export ----
     const int n = ncur;
+    if constexpr (CTX) {
+        // UpdateFinalContext in the export only: an entry inside a partial match gives the bonus of that match back, the
+        // list is sorted again (stable, descending, by the new totals), and the state block keeps what it held.
+        if (tid < n) {
+            double bonus = c_csc[tid];
+            if (cx.finalize && c_cst[tid] != 0) bonus += (double)cg.escape[c_cst[tid]];
+            x_ctc[tid] = py_log_add2(c_pb[tid], c_pnb[tid]);
+            x_ctx[tid] = bonus;
+        }
+        __syncthreads();
+        if (tid < n) {
+            int pos = tid;
+            if (cx.finalize) {
+                const double me = x_ctc[tid] + x_ctx[tid];
+                pos = 0;
+                for (int f = 0; f < n; ++f) {
+                    const double ot = x_ctc[f] + x_ctx[f];
+                    pos += (ot > me || (ot == me && f < tid)) ? 1 : 0;
+                }
+            }
+            x_pos[tid] = pos;
+        }
+        __syncthreads();
+        for (int i = tid; i < beam * Lcap; i += 256) {
+            const int e = i / Lcap, q = i - e * Lcap;
+            const bool in = e < n && q < c_len[e];
+            const size_t o = ((size_t)b * beam + (e < n ? x_pos[e] : e)) * Lcap + q;
+            int tok = -1, tm = -1, tg = -1;
+            if (in) {
+                const double vb = c_vb[e], vnb = c_vnb[e];
+                const int li = vb > vnb ? 0 : 1;
+                tok = sq[(size_t)sel * LB + (size_t)e * Lcap + q];
+                tg = tq[(size_t)sel * LB + (size_t)e * Lcap + q];
+                if ((vb > vnb ? vb : vnb) > NINF) tm = sq[(size_t)((1 + li) * 2 + sel) * LB + (size_t)e * Lcap + q];
+            }
+            hyps[o] = tok;
+            times[o] = tm;
+            cx.tags[o] = tg;
+        }
+        if (tid < beam) {
+            const size_t o = (size_t)b * beam + (tid < n ? x_pos[tid] : tid);
+            hyp_lens[o] = tid < n ? c_len[tid] : 0;
+            cx.ctc_scores[o] = tid < n ? x_ctc[tid] : NINF;
+            cx.context_scores[o] = tid < n ? x_ctx[tid] : 0.0;
+            scores[o] = tid < n ? x_ctc[tid] + x_ctx[tid] : NINF;
+            viterbi[o] = tid < n ? (c_vb[tid] > c_vnb[tid] ? c_vb[tid] : c_vnb[tid]) : NINF;
+            cx.context_states[o] = tid < n ? c_cst[tid] : 0;
+        }
+        if (tid == 0) { n_hyps[b] = n; n_frames[b] = a_next; }
+        return;
+    }
     for (int i = tid; i < beam * Lcap; i += 256) {
         const int e = i / Lcap, q = i - e * Lcap;
         const bool in = e < n && q < c_len[e];
@@ -624,10 +753,27 @@ int ctc_prefix_beam_chunk_launch(const float *logits_d, const int32_t *lens_d, i
     // the frames' top-`beam` exactly as wr_ctc_prefix_beam_search finds them (dynamic LDS: one row of logits)
     WR_TRY(launch("ctc_frame_topk_kernel", ctc_frame_topk_kernel, dim3(B * T), dim3(256), (size_t)V * sizeof(float), st, logits_d, V,
                   beam, reinterpret_cast<float *>(ws + w.tkv_off), reinterpret_cast<int32_t *>(ws + w.tki_off)));
-    return launch("ctc_prefix_beam_chunk_kernel", ctc_prefix_beam_chunk_kernel, dim3(B), dim3(256), 0, st,
+    return launch("ctc_prefix_beam_chunk_kernel", ctc_prefix_beam_chunk_kernel<false>, dim3(B), dim3(256), 0, st,
                   reinterpret_cast<const float *>(ws + w.tkv_off), reinterpret_cast<const int32_t *>(ws + w.tki_off), lens_d, T, beam,
                   blank, reset, Lcap, static_cast<char *>(state_d), ctc_stream_state_layout(beam, Lcap), hyps_d, hyp_lens_d,
-                  scores_d, viterbi_d, times_d, n_hyps_d, n_frames_d);
+                  scores_d, viterbi_d, times_d, n_hyps_d, n_frames_d, CtcContextGraph{}, CtcContextOut{});
+}
+
+int ctc_prefix_beam_context_chunk_launch(const float *logits_d, const int32_t *lens_d, int B, int T, int V, int beam, int blank,
+                                         int reset, int Lcap, void *state_d, const CtcContextGraph &graph,
+                                         const CtcContextOut &ctx, int32_t *hyps_d, int32_t *hyp_lens_d, double *scores_d,
+                                         double *viterbi_d, int32_t *times_d, int32_t *n_hyps_d, int32_t *n_frames_d,
+                                         void *workspace_d, void *stream)
+{
+    const CtcStreamWs w = ctc_stream_ws_layout(B, T, beam);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char *ws = static_cast<char *>(workspace_d);
+    WR_TRY(launch("ctc_frame_topk_kernel", ctc_frame_topk_kernel, dim3(B * T), dim3(256), (size_t)V * sizeof(float), st, logits_d, V,
+                  beam, reinterpret_cast<float *>(ws + w.tkv_off), reinterpret_cast<int32_t *>(ws + w.tki_off)));
+    return launch("ctc_prefix_beam_chunk_kernel<context>", ctc_prefix_beam_chunk_kernel<true>, dim3(B), dim3(256), 0, st,
+                  reinterpret_cast<const float *>(ws + w.tkv_off), reinterpret_cast<const int32_t *>(ws + w.tki_off), lens_d, T, beam,
+                  blank, reset, Lcap, static_cast<char *>(state_d), ctc_context_state_layout(beam, Lcap), hyps_d, hyp_lens_d,
+                  scores_d, viterbi_d, times_d, n_hyps_d, n_frames_d, graph, ctx);
 }
 
 }  // namespace wr

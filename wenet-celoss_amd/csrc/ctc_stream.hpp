@@ -13,13 +13,19 @@ constexpr int kCtcStreamLists = 3;             // tokens, times_b, times_nb
 //   head    int32[4]: a marker made of (beam, Lcap), a_next, the number of entries, the sequence buffer in use
 //   pb, pnb, vb, vnb  double[beam];  hash  uint64[beam];  len, last  int32[beam]
 //   seq     int32[3][2][beam][Lcap]: tokens / times_b / times_nb, each double-buffered
+// The biased search's block (ctc_context_state_layout) has its own layout: the plain one, then, behind the plain stride,
+//   csc     double[beam]: the entries' bonuses;  cst  int32[beam]: their context-graph states
+//   tag     int32[2][beam][Lcap]: a fourth list, the tags, double-buffered like the tokens it travels with
+// so it is larger than the plain block for every (beam, Lcap).  csc_off / cst_off / tag_off are 0 in the plain layout,
+// whose kernel instantiation never reads them.
 struct CtcStreamState {
-    size_t pb_off, pnb_off, vb_off, vnb_off, hash_off, len_off, last_off, seq_off, stride;
+    size_t pb_off, pnb_off, vb_off, vnb_off, hash_off, len_off, last_off, seq_off, stride, csc_off, cst_off, tag_off;
 };
 
 __host__ __device__ inline CtcStreamState ctc_stream_state_layout(int beam, int Lcap)
 {
     CtcStreamState s;
+    s.csc_off = 0; s.cst_off = 0; s.tag_off = 0;
     size_t off = 16;
     s.pb_off = off;   off += (size_t)beam * sizeof(double);
     s.pnb_off = off;  off += (size_t)beam * sizeof(double);
@@ -33,6 +39,38 @@ __host__ __device__ inline CtcStreamState ctc_stream_state_layout(int beam, int 
     s.stride = (off + 255) / 256 * 256;
     return s;
 }
+
+constexpr int kCtcContextLists = 4;            // tokens, times_b, times_nb, tags
+constexpr int kCtcContextMaxStates = 65536;
+constexpr int kCtcContextMaxArcs = 1048576;
+
+__host__ __device__ inline CtcStreamState ctc_context_state_layout(int beam, int Lcap)
+{
+    CtcStreamState s = ctc_stream_state_layout(beam, Lcap);
+    size_t off = s.stride;
+    s.csc_off = off;  off += (size_t)beam * sizeof(double);
+    s.cst_off = off;  off += (size_t)beam * sizeof(int32_t);
+    off = (off + 15) / 16 * 16;
+    s.tag_off = off;  off += (size_t)2 * beam * Lcap * sizeof(int32_t);
+    s.stride = (off + 255) / 256 * 256;
+    return s;
+}
+
+// The context graph as the kernel reads it (include/wr_api.h, "Context-graph biasing"): a deterministic table, state 0
+// the root.  The plain search passes an empty one.
+struct CtcContextGraph {
+    const int32_t *arc_begin, *arc_token, *arc_next;
+    const float *arc_score, *escape;
+    const int32_t *final_;
+    int S, A;
+};
+
+// What the biased call adds to the plain one's arguments: the flag and the four outputs.
+struct CtcContextOut {
+    int finalize;
+    double *ctc_scores, *context_scores;
+    int32_t *tags, *context_states;
+};
 
 struct CtcStreamWs {
     size_t tkv_off, tki_off, total;
@@ -59,5 +97,13 @@ int ctc_prefix_beam_chunk_launch(const float *logits_d, const int32_t *lens_d, i
                                  int reset, int Lcap, void *state_d, int32_t *hyps_d, int32_t *hyp_lens_d, double *scores_d,
                                  double *viterbi_d, int32_t *times_d, int32_t *n_hyps_d, int32_t *n_frames_d,
                                  void *workspace_d, void *stream);
+
+// ctc_decode.hip: the same two launches behind wr_ctc_prefix_beam_search_context_chunk, with the kernel's biased
+// instantiation and the state layout of ctc_context_state_layout.
+int ctc_prefix_beam_context_chunk_launch(const float *logits_d, const int32_t *lens_d, int B, int T, int V, int beam, int blank,
+                                         int reset, int Lcap, void *state_d, const CtcContextGraph &graph,
+                                         const CtcContextOut &ctx, int32_t *hyps_d, int32_t *hyp_lens_d, double *scores_d,
+                                         double *viterbi_d, int32_t *times_d, int32_t *n_hyps_d, int32_t *n_frames_d,
+                                         void *workspace_d, void *stream);
 
 }  // namespace wr

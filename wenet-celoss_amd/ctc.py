@@ -214,6 +214,129 @@ def ctc_prefix_beam_search_times(logits: torch.Tensor, lens: torch.Tensor, beam_
     return CtcPrefixBeamStream(logits.shape[0], beam_size, logits.shape[1], blank=blank).search(logits, lens)
 
 
+class CtcContextPrefixBeamStream:
+    """CtcPrefixBeamStream with the context-graph phrase biasing of the reference runtime (context_graph.cc,
+    ctc_prefix_beam_search.cc:137-193, 213-234; the contract is in include/wr_api.h, "Context-graph biasing in the CTC
+    prefix beam search"): every hypothesis walks `context_graph` (a ContextGraph) and the beam is pruned by score plus
+    bonus.  Owns its own state block (wr_ctc_context_stream_state_bytes); `state` lends one, as in CtcPrefixBeamStream.
+
+    search(logits_chunk, lens, finalize=False) returns per stream [(tokens, score, viterbi_score, times, ctc_score,
+    context_score, tags)], best first, with score = ctc_score + context_score and one tag per token (bit 0: a phrase
+    starts at this token, bit 1: a phrase ends at it).  finalize=True exports as if the stream ended here: a partial
+    match gives its bonus back and the list is sorted again; the stream itself is not changed, so it may go on.
+    finalize() does that without new frames.  `context_states` holds, per stream, the graph states of the last result."""
+
+    def __init__(self, n_streams: int, beam_size: int, max_frames: int, context_graph, blank: int = 0,
+                 state: torch.Tensor = None):
+        from .context_graph import ContextGraph
+        self.n_streams, self.beam_size, self.max_frames, self.blank = int(n_streams), int(beam_size), int(max_frames), int(blank)
+        if self.n_streams < 1 or self.max_frames < 1 or not 1 <= self.beam_size <= 16:
+            raise RuntimeError(f"CtcContextPrefixBeamStream: n_streams={n_streams}, beam_size={beam_size} (1..16), "
+                               f"max_frames={max_frames} must be positive")
+        if not isinstance(context_graph, ContextGraph):
+            raise RuntimeError("CtcContextPrefixBeamStream: context_graph must be a ContextGraph")
+        if context_graph.blank != self.blank:
+            raise RuntimeError(f"CtcContextPrefixBeamStream: the graph was built for blank {context_graph.blank}, "
+                               f"the search uses {self.blank}")
+        self.context_graph = context_graph
+        self._state = state
+        self._vocab = None
+        self._dev = None
+        self.frames = [0] * self.n_streams
+        self.context_states = [[] for _ in range(self.n_streams)]
+        self.reset()
+
+    def reset(self) -> None:
+        """Every stream starts fresh with the next search."""
+        self._fresh = True
+        self._frames_done = 0
+        self.frames = [0] * self.n_streams
+
+    def search(self, logits_chunk: torch.Tensor, lens: torch.Tensor, finalize: bool = False):
+        if logits_chunk.dim() != 3:
+            raise RuntimeError("CtcContextPrefixBeamStream: the chunk must be (n_streams, frames, vocab)")
+        B, T, V = logits_chunk.shape
+        if B != self.n_streams:
+            raise RuntimeError(f"CtcContextPrefixBeamStream: chunk has {B} streams, the stream set has {self.n_streams}")
+        if self._vocab is not None and V != self._vocab:
+            raise RuntimeError(f"CtcContextPrefixBeamStream: vocabulary changed from {self._vocab} to {V}")
+        if self._frames_done + T > self.max_frames:
+            raise RuntimeError(f"CtcContextPrefixBeamStream: {self._frames_done} frames done + a chunk of {T} exceeds "
+                               f"max_frames={self.max_frames}")
+        if not logits_chunk.is_cuda:
+            raise RuntimeError("wenet_celoss_amd.CtcContextPrefixBeamStream: logits must live on a HIP device (no CPU path)")
+        out = self._call(logits_chunk.detach().float().contiguous(), lens, self._frames_done, finalize)
+        self._frames_done += T
+        self._vocab = V
+        return out
+
+    def finalize(self):
+        """The finalised n-best of every stream without new frames: a chunk in which every stream has lens = 0."""
+        if self._vocab is None:
+            raise RuntimeError("CtcContextPrefixBeamStream: finalize() before the first search")
+        x = torch.zeros(self.n_streams, 1, self._vocab, dtype=torch.float32, device=self._dev)
+        # the chunk is one frame wide and none of it is consumed: it counts against no capacity
+        return self._call(x, torch.zeros(self.n_streams, dtype=torch.int32), min(self._frames_done, self.max_frames - 1), True)
+
+    def _call(self, x, lens, frames_done, finalize):
+        B, T, V = x.shape
+        dev = x.device
+        beam, cap, g = self.beam_size, self.max_frames, self.context_graph
+        need = _lib.load().wr_ctc_context_stream_state_bytes(B, beam, cap)
+        if self._state is None:
+            self._state = torch.empty(need, dtype=torch.uint8, device=dev)
+        elif self._state.device != dev or self._state.numel() < need or self._state.dtype != torch.uint8:
+            raise RuntimeError(f"CtcContextPrefixBeamStream: the state tensor must be uint8 on {dev} with at least {need} bytes")
+        ln = lens.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        if ln.numel() != B:
+            raise RuntimeError(f"CtcContextPrefixBeamStream: lens has {ln.numel()} elements for {B} streams")
+        ws = _lib.workspace("wr_ctc_stream_workspace_bytes", B, T, beam, device=dev)
+        i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
+        hyps, tm, tg = torch.empty(B, beam, cap, **i32), torch.empty(B, beam, cap, **i32), torch.empty(B, beam, cap, **i32)
+        hl, cs, nh, nf = torch.empty(B, beam, **i32), torch.empty(B, beam, **i32), torch.empty(B, **i32), torch.empty(B, **i32)
+        sc, vt, cc, cx = (torch.empty(B, beam, **f64) for _ in range(4))
+        _lib.call("wr_ctc_prefix_beam_search_context_chunk", x, ln, B, T, V, beam, self.blank, int(self._fresh), frames_done,
+                  cap, self._state, self._state.numel(), *g.to(dev), g.n_states, g.n_arcs, int(bool(finalize)), hyps, hl, sc,
+                  vt, tm, nh, nf, cc, cx, tg, cs, ws, ws.numel(), device=dev)
+        self._fresh = False
+        self._dev = dev
+        lc, nc = hl.cpu().tolist(), nh.cpu().tolist()
+        scc, vtc, ccc, cxc = sc.cpu().tolist(), vt.cpu().tolist(), cc.cpu().tolist(), cx.cpu().tolist()
+        self.frames = nf.cpu().tolist()
+        csc = cs.cpu().tolist()
+        self.context_states = [csc[b][:nc[b]] for b in range(B)]
+        width = max(max(row) for row in lc)
+        hc, tc, gc = (t[:, :, :width].cpu().tolist() for t in (hyps, tm, tg))
+        return [[(tuple(hc[b][e][:lc[b][e]]), scc[b][e], vtc[b][e], tuple(tc[b][e][:lc[b][e]]), ccc[b][e], cxc[b][e],
+                  tuple(gc[b][e][:lc[b][e]])) for e in range(nc[b])] for b in range(B)]
+
+    @staticmethod
+    def outputs(result, start_tag_id: int, end_tag_id: int):
+        """UpdateOutputs (ctc_prefix_beam_search.cc:63-84) on one stream's result: per hypothesis the tokens with
+        `start_tag_id` in front of every token that starts a phrase and `end_tag_id` behind every token that ends one."""
+        outs = []
+        for hyp in result:
+            tokens, tags = hyp[0], hyp[6]
+            o = []
+            for tok, tag in zip(tokens, tags):
+                if tag & 1:
+                    o.append(start_tag_id)
+                o.append(tok)
+                if tag & 2:
+                    o.append(end_tag_id)
+            outs.append(o)
+        return outs
+
+
+def ctc_context_prefix_beam_search(logits: torch.Tensor, lens: torch.Tensor, beam_size: int, context_graph, blank: int = 0):
+    """The biased search over whole utterances (B, T, V) in one chunk, finalised: per utterance [(prefix tuple, score,
+    viterbi_score, times tuple, ctc_score, context_score, tags tuple)] best first."""
+    if not logits.is_cuda:
+        raise RuntimeError("wenet_celoss_amd.ctc_context_prefix_beam_search: logits must live on a HIP device (no CPU path)")
+    return CtcContextPrefixBeamStream(logits.shape[0], beam_size, logits.shape[1], context_graph, blank=blank).search(
+        logits, lens, finalize=True)
+
+
 def forced_align(ctc_probs: torch.Tensor, y: torch.Tensor, blank_id: int = 0) -> list:
     """wenet/utils/ctc_util.py:27-83: ctc_probs (T, D) log-posteriors, y (L,) label ids -> per-frame token list."""
     return forced_align_batch(ctc_probs.unsqueeze(0), y.reshape(1, -1), torch.tensor([ctc_probs.size(0)]),

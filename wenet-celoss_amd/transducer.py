@@ -629,6 +629,22 @@ class Transducer(nn.Module):
             logits = self.ctc.ctc_lo(encoder_out)
         return ctc_prefix_beam_search_times(logits, encoder_out_lens, beam_size)
 
+    def ctc_context_prefix_beam_search(self, speech: torch.Tensor, speech_lengths: torch.Tensor, beam_size: int,
+                                       context_graph, decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1,
+                                       simulate_streaming: bool = False):
+        """ctc_prefix_beam_search_times with the context-graph phrase biasing of the runtime (--context_path /
+        --context_score), finalised: per utterance [(prefix, score, viterbi_score, times, ctc_score, context_score,
+        tags)] best first, score = ctc_score + context_score."""
+        from .ctc import ctc_context_prefix_beam_search
+        assert speech.shape[0] == speech_lengths.shape[0]
+        assert decoding_chunk_size != 0
+        encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
+                                                          num_decoding_left_chunks, simulate_streaming)
+        encoder_out_lens = encoder_mask.squeeze(1).sum(1)
+        with torch.no_grad():
+            logits = self.ctc.ctc_lo(encoder_out)
+        return ctc_context_prefix_beam_search(logits, encoder_out_lens, beam_size, context_graph)
+
     # ------------------------------------------- ASRModel surface the reference class inherits (asr_model.py) --
     # The reference's Transducer IS an ASRModel (transducer.py:20), so wenet/bin/recognize.py may call `recognize`
     # (--mode attention, recognize.py:259) and `attention_rescoring` (--mode attention_rescoring, :351) on it, and
@@ -929,6 +945,22 @@ class Transducer(nn.Module):
         with torch.no_grad():
             logits = self.ctc.ctc_lo(encoder_out_chunk)
         return self._ctc_stream.search(logits, encoder_out_lens)
+
+    # ---- the same with context-graph phrase biasing (context_graph.cc, ctc_prefix_beam_search.cc:137-193, 213-234) --
+    def reset_ctc_context_stream(self, n_streams: int, beam_size: int, max_frames: int, context_graph) -> None:
+        """Start `n_streams` fresh biased CTC prefix-beam streams that walk `context_graph` (a ContextGraph)."""
+        from .ctc import CtcContextPrefixBeamStream
+        self._ctc_context_stream = CtcContextPrefixBeamStream(n_streams, beam_size, max_frames, context_graph, blank=0)
+
+    def forward_ctc_context_prefix_beam_search(self, encoder_out_chunk: torch.Tensor, encoder_out_lens: torch.Tensor,
+                                               finalize: bool = False):
+        """forward_ctc_prefix_beam_search on the biased streams -> per stream [(prefix, score, viterbi_score, times,
+        ctc_score, context_score, tags)] best first; finalize=True exports as if every stream ended with this chunk."""
+        if getattr(self, "_ctc_context_stream", None) is None:
+            raise RuntimeError("call reset_ctc_context_stream(n_streams, beam_size, max_frames, context_graph) first")
+        with torch.no_grad():
+            logits = self.ctc.ctc_lo(encoder_out_chunk)
+        return self._ctc_context_stream.search(logits, encoder_out_lens, finalize=finalize)
 
     # ----------------------------------------------------- step exports (:600-629) --
     # @torch.jit.export as in the reference, so that torch.jit.script(model) (train.py:203-205, export_jit.py) yields an
