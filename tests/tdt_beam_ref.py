@@ -25,8 +25,9 @@ import torch
 
 # beam: [(tokens incl. the seed blank, t, score)] best first; margin: the smallest gap that decided anything visible -- at
 # the token rank-`beam` boundary and the pair rank-`beam` boundary of every expansion, and between neighbours of the sorted
-# fused classes down to the first pruned one, over all steps; steps: steps taken; expanded: entries expanded in all
-Result = namedtuple("Result", "beam margin steps expanded")
+# fused classes down to the first pruned one, over all steps; steps: steps taken; expanded: entries expanded in all;
+# fused: pool entries that joined an earlier entry's class, in all steps
+Result = namedtuple("Result", "beam margin steps expanded fused")
 
 
 def log_softmax(x):
@@ -52,7 +53,7 @@ def search(source, T, V, durations, beam, blank=0, ctc_logp=None, ctc_weight=0.0
     D = len(durations)
     tw, cw = float(np.float32(transducer_weight)), float(np.float32(ctc_weight))
     entries = [((blank,), 0, 0.0)]
-    margin, steps, expanded = math.inf, 0, 0
+    margin, steps, expanded, n_fused = math.inf, 0, 0, 0
 
     def gap(a, b):
         nonlocal margin
@@ -93,6 +94,7 @@ def search(source, T, V, durations, beam, blank=0, ctc_logp=None, ctc_weight=0.0
             for c in fused:
                 if c[0] == toks and c[1] == t:
                     c[2] = log_add(c[2], sc)
+                    n_fused += 1
                     break
             else:
                 fused.append([toks, t, sc])
@@ -103,7 +105,7 @@ def search(source, T, V, durations, beam, blank=0, ctc_logp=None, ctc_weight=0.0
         steps += 1
         if trace is not None:
             trace.append(list(entries))
-    return Result(entries, margin, steps, expanded)
+    return Result(entries, margin, steps, expanded, n_fused)
 
 
 class Scripted:

@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import test_tdt_beam_ref as cases
-from test_tdt_beam_ref import LENS, MARGIN, MIN_QUALIFY, SPEC, SPECS
+from test_tdt_beam_ref import DUR1_SPECS, LENS, MARGIN, MIN_QUALIFY, SPEC, SPECS
 
 pytestmark = pytest.mark.gpu
 
@@ -69,11 +69,13 @@ def test_exact_ties_go_to_the_lower_index_and_equal_duration_arcs_fuse():
 
 
 # ------------------------------------------------------------------------------------------------ cross-checks --
-def test_durations_1_equals_the_plain_prefix_beam_search():
-    """durations = (1,): the plain search over the joiner's first V outputs gives the same hypotheses and scores."""
+@pytest.mark.parametrize("spec", DUR1_SPECS, ids=[s.name for s in DUR1_SPECS])
+def test_durations_1_equals_the_plain_prefix_beam_search(spec):
+    """durations = (1,): the plain search over the joiner's first V outputs gives the same hypotheses and scores, and
+    they are those of the float64 rule."""
     import wenet_celoss_amd as w
-    spec = SPEC["dur1-ctc"]
     c, want = cases.make_case(spec), cases.reference(spec)
+    assert cases.case_conditions(spec, want) == []
     tdt = run(decoder(c.pred, c.joint, spec.beam), c)
     plain_joint = w.TransducerJoint(c.V, cases.E, cases.P, cases.J).eval()
     state = {k: (v[:c.V] if k.startswith("ffn_out.") else v) for k, v in c.joint.state_dict().items()}
@@ -88,6 +90,7 @@ def test_durations_1_equals_the_plain_prefix_beam_search():
             assert [h for h, _ in tdt[b]] == [h for h, _ in plain[b]], b
             np.testing.assert_allclose([s for _, s in tdt[b]], [s for _, s in plain[b]], rtol=1e-5)
     assert compared >= MIN_QUALIFY
+    check(plain, want, spec.name + " plain")
 
 
 def test_beam_1_gives_the_tokens_of_the_greedy_search():

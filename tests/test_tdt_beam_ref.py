@@ -153,7 +153,15 @@ SPECS = (
     Spec("embedding", "embedding", 305, (1, 2, 4), 3, False, 0, 0),
     Spec("conv-blank5", "conv", 305, (0, 1, 2, 3, 4), 3, False, 5, 0),
     Spec("dur1-ctc", "lstm", 301, (1,), 8, True, 0, 1),
+    # beam 16 (beam^2 = 256 candidates: the all-pairs steps of the update kernels take more than one pass) over 40 tokens,
+    # where equal prefixes meet at every frame; the durations-(1,) cases are also run through the plain search
+    # (the list's shape, five utterances of up to 40 frames, is kept: MIN_QUALIFY asks for four utterances with a clear
+    # margin, and a case still runs in under 3 s on the device)
+    Spec("dur1-beam16-ctc", "lstm", 41, (1,), 16, True, 0, 2),
+    Spec("dur1-beam16-embedding-ctc", "embedding", 41, (1,), 16, True, 0, 4),
+    Spec("beam16-embedding", "embedding", 43, (0, 1, 2), 16, True, 0, 5),
 )
+DUR1_SPECS = tuple(s for s in SPECS if s.durations == (1,))
 TIE_SPEC = Spec("ties", "lstm", 305, (0, 1, 2, 3, 4), 3, False, 0, 1)
 SPEC = {s.name: s for s in SPECS}
 
@@ -202,6 +210,8 @@ def case_conditions(spec, want):
         bad.append(f"fewer than {MIN_QUALIFY} utterances with a margin above {MARGIN}: {[r.margin for r in want]}")
     if not any(len(h) > 1 for r in want for h, _, _ in r.beam):
         bad.append("no label in any hypothesis")
+    if spec.beam == 16 and not all(r.fused for r, n in zip(want, LENS) if n > 1):
+        bad.append(f"an utterance without a fused duplicate at beam 16: {[r.fused for r in want]}")
     if spec.beam > 1 and not any(r.expanded < r.steps * min(spec.beam, len(r.beam)) for r in want):
         bad.append("no hypothesis ever waited")
     jumps = max(spec.durations) > 1

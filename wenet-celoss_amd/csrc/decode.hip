@@ -37,6 +37,8 @@
 //   tdt_beam_topk_kernel /  the same for a token-and-duration model: token and duration log-softmax, the best
 //   tdt_beam_update_kernel  (token, duration) pairs of the hypotheses at the utterance's earliest frame; the
 //                           others wait; equal tokens at an equal frame fuse
+//                           What a twin does as the plain kernel does exists once: topk_row_max / _log_sum / _mix_select,
+//                           topk_merge, the beam_* phases over one BeamUpdLds, ResolveLane (both look-ahead resolve kernels)
 //
 // Micro-steps are replayed from a hipGraph (captured once per decoder handle) so
 // the host only checks a "lanes still active" word every 16 steps.
@@ -1166,62 +1168,77 @@ __global__ __launch_bounds__(256) void greedy_rows_kernel(DevState *sp)
     if (tid == 0) S.row_tok[(size_t)f * d.NLp + n] = bi;
 }
 
+// What both look-ahead resolve kernels start from and end with.  The constructor requests the lane's scalars and its
+// `look` row decisions in one batch, before the caller's `!act` return; T = the lane's frame count; nic = whether the pending
+// predictor state still equals the committed one.  The kernel's walk advances t / nb / len / need and notes n_blank (rows
+// answered blank), `emitted` (the one label, or -1) and `commit`.  store: thread 0 writes that back, then commit_and_feed.
+struct ResolveLane {
+    int act, t, nb, need0, nic, len, T, sc, sn, rows[kMaxLook];
+    int need, emitted = -1, n_blank = 0;
+    bool commit = false;
+    __device__ __forceinline__ ResolveLane(const DevState &S, int n, int look)
+    {
+        act = S.lane_active[n];
+        t = S.lane_t[n], nb = S.noblk[n];
+        need = need0 = S.need_pred[n];
+        nic = S.new_is_cache[n];
+        len = S.hyp_lens[n];
+        const int enc_len = S.enc_lens[n];
+        sc = S.comm_slot[n], sn = S.new_slot[n];
+#pragma unroll
+        for (int f = 0; f < kMaxLook; ++f) rows[f] = S.row_tok[(size_t)(f < look ? f : 0) * S.d.NLp + n];
+        T = enc_len < S.T ? enc_len : S.T;
+        if (need0) nic = 0;                        // the predictor stepped in this micro-step
+    }
+    __device__ __forceinline__ void store(const DevState &S, int n, int tid) const
+    {
+        if (tid == 0) {
+            if (n_blank) atomicAdd(S.active_count + 1, n_blank);     // decision statistics for the look-ahead policy
+            if (emitted >= 0) atomicAdd(S.active_count + 2, 1);      // (consulted rows only)
+            if (need0) S.new_is_cache[n] = 0;
+            S.hyp_lens[n] = len;
+            if (emitted >= 0) S.token[n] = emitted;
+            S.need_pred[n] = need;
+            S.lane_t[n] = t;
+            S.noblk[n] = nb;
+            if (t >= T) {
+                S.lane_active[n] = 0;
+                atomicSub(S.active_count, 1);
+            }
+        }
+        commit_and_feed(S, n, emitted >= 0, commit, emitted, sc, sn);
+    }
+};
+
 __global__ __launch_bounds__(256) void greedy_resolve_kernel(DevState *sp, int look)
 {
     const DevState S = *sp;
-    const Dims &d = S.d;
     const int n = blockIdx.x, tid = threadIdx.x;
-    const int act = S.lane_active[n];
-    int t = S.lane_t[n], nb = S.noblk[n];
-    const int need0 = S.need_pred[n];
-    int nic = S.new_is_cache[n];
-    int len = S.hyp_lens[n];
-    const int enc_len = S.enc_lens[n];
-    const int sc = S.comm_slot[n], sn = S.new_slot[n];
-    int toks[kMaxLook];
-#pragma unroll
-    for (int f = 0; f < kMaxLook; ++f) toks[f] = S.row_tok[(size_t)(f < look ? f : 0) * d.NLp + n];
-    if (!act) return;
-    const int T = enc_len < S.T ? enc_len : S.T;
-    if (need0) nic = 0;                            // the predictor stepped in this micro-step
-    int need = need0, emitted = -1, n_blank = 0;
-    bool commit = false, done = false;
+    ResolveLane ln(S, n, look);
+    if (!ln.act) return;
+    bool done = false;
 #pragma unroll
     for (int f = 0; f < kMaxLook; ++f) {
         if (f >= look || done) continue;
-        const int k = toks[f];
+        const int k = ln.rows[f];
         const bool emit = (k != S.blank);
-        n_blank += emit ? 0 : 1;
+        ln.n_blank += emit ? 0 : 1;
         if (emit) {
-            if (tid == 0 && len < S.max_hyp) S.hyps[(size_t)n * S.max_hyp + len] = k;
-            len += 1;
-            need = 1;
-            nb += 1;
-            commit = !nic;
-            emitted = k;
+            if (tid == 0 && ln.len < S.max_hyp) S.hyps[(size_t)n * S.max_hyp + ln.len] = k;
+            ln.len += 1;
+            ln.need = 1;
+            ln.nb += 1;
+            ln.commit = !ln.nic;
+            ln.emitted = k;
         }
-        if (!emit || nb >= S.n_steps) {
-            if (!emit) need = 0;
-            t += 1;
-            nb = 0;
+        if (!emit || ln.nb >= S.n_steps) {
+            if (!emit) ln.need = 0;
+            ln.t += 1;
+            ln.nb = 0;
         }
-        done = emit || t >= T;                     // after an emission the remaining rows belong to a stale predictor state
+        done = emit || ln.t >= ln.T;               // after an emission the remaining rows belong to a stale predictor state
     }
-    if (tid == 0) {
-        if (n_blank) atomicAdd(S.active_count + 1, n_blank);         // decision statistics for the look-ahead policy
-        if (emitted >= 0) atomicAdd(S.active_count + 2, 1);
-        if (need0) S.new_is_cache[n] = 0;
-        S.hyp_lens[n] = len;
-        if (emitted >= 0) S.token[n] = emitted;
-        S.need_pred[n] = need;
-        S.lane_t[n] = t;
-        S.noblk[n] = nb;
-        if (t >= T) {
-            S.lane_active[n] = 0;
-            atomicSub(S.active_count, 1);
-        }
-    }
-    commit_and_feed(S, n, emitted >= 0, commit, emitted, sc, sn);
+    ln.store(S, n, tid);
 }
 
 // ---- token-and-duration (TDT) greedy: the two look-ahead kernels with the TDT decision rule ------------------
@@ -1277,66 +1294,38 @@ __global__ __launch_bounds__(256) void tdt_rows_kernel(DevState *sp)
 __global__ __launch_bounds__(256) void tdt_resolve_kernel(DevState *sp, int look)
 {
     const DevState S = *sp;
-    const Dims &d = S.d;
     const int n = blockIdx.x, tid = threadIdx.x;
-    const int act = S.lane_active[n];
-    int t = S.lane_t[n], nb = S.noblk[n];
-    const int need0 = S.need_pred[n];
-    int nic = S.new_is_cache[n];
-    int len = S.hyp_lens[n];
-    const int enc_len = S.enc_lens[n];
-    const int sc = S.comm_slot[n], sn = S.new_slot[n];
-    int rows[kMaxLook];
-#pragma unroll
-    for (int f = 0; f < kMaxLook; ++f) rows[f] = S.row_tok[(size_t)(f < look ? f : 0) * d.NLp + n];
-    if (!act) return;
-    const int T = enc_len < S.T ? enc_len : S.T;
-    if (need0) nic = 0;                            // the predictor stepped in this micro-step
-    const int t0 = t;
-    int need = need0, emitted = -1, n_blank = 0;
-    bool commit = false;
+    ResolveLane ln(S, n, look);
+    if (!ln.act) return;
+    const int t0 = ln.t;
 #pragma unroll
     for (int f = 0; f < kMaxLook; ++f) {
-        if (f >= look || emitted >= 0 || t >= T || t - t0 != f) continue;   // consulted: the row of the lane's current frame
-        const int k = rows[f] & 0xffff;
-        const int dur = (int)((S.tdt_durs >> (4 * (rows[f] >> 16))) & 15);
+        if (f >= look || ln.emitted >= 0 || ln.t >= ln.T || ln.t - t0 != f) continue;   // consulted: the row of the lane's current frame
+        const int k = ln.rows[f] & 0xffff;
+        const int dur = (int)((S.tdt_durs >> (4 * (ln.rows[f] >> 16))) & 15);
         if (k == S.blank) {
-            n_blank += 1;
-            t += dur > 1 ? dur : 1;
-            nb = 0;
-            need = 0;
+            ln.n_blank += 1;
+            ln.t += dur > 1 ? dur : 1;
+            ln.nb = 0;
+            ln.need = 0;
             continue;
         }
-        if (tid == 0 && len < S.max_hyp) {
-            S.hyps[(size_t)n * S.max_hyp + len] = k;
-            if (S.hyp_frames) S.hyp_frames[(size_t)n * S.max_hyp + len] = t;
+        if (tid == 0 && ln.len < S.max_hyp) {
+            S.hyps[(size_t)n * S.max_hyp + ln.len] = k;
+            if (S.hyp_frames) S.hyp_frames[(size_t)n * S.max_hyp + ln.len] = ln.t;
         }
-        len += 1;
-        need = 1;
-        commit = !nic;
-        emitted = k;
-        nb = dur > 0 ? 0 : nb + 1;
-        t += dur;
-        if (nb >= S.n_steps) {
-            t += 1;
-            nb = 0;
-        }
-    }
-    if (tid == 0) {
-        if (n_blank) atomicAdd(S.active_count + 1, n_blank);         // decision statistics: consulted rows only
-        if (emitted >= 0) atomicAdd(S.active_count + 2, 1);
-        if (need0) S.new_is_cache[n] = 0;
-        S.hyp_lens[n] = len;
-        if (emitted >= 0) S.token[n] = emitted;
-        S.need_pred[n] = need;
-        S.lane_t[n] = t;
-        S.noblk[n] = nb;
-        if (t >= T) {
-            S.lane_active[n] = 0;
-            atomicSub(S.active_count, 1);
+        ln.len += 1;
+        ln.need = 1;
+        ln.commit = !ln.nic;
+        ln.emitted = k;
+        ln.nb = dur > 0 ? 0 : ln.nb + 1;
+        ln.t += dur;
+        if (ln.nb >= S.n_steps) {
+            ln.t += 1;
+            ln.nb = 0;
         }
     }
-    commit_and_feed(S, n, emitted >= 0, commit, emitted, sc, sn);
+    ln.store(S, n, tid);
 }
 
 // ------------------------------------------------------- hot-word greedy --
@@ -1785,52 +1774,38 @@ __global__ void beam_init_kernel(DevState *s)
 // wave-local argmax rounds (DPP, no barriers), wave 0 merges the 16 x beam survivors.  Ties go to the lowest index
 // throughout.
 constexpr int kTopkThreads = 512;
+// What both top-k kernels do with a row in registers (xv: the Vn token columns, strided over the workgroup; cv: the CTC
+// posterior's row beside it): its block maximum m, ls = log sum exp(x - m), then the mixture (CTC_OPT = false: always; true:
+// only if has_ctc) and `beam` wave-local argmax rounds (DPP, no barriers): wave w's k-th best into wv / wi[w * beam + k].
+// The loads stay in the kernels: issued from a helper of any form they cost the <32> instantiations 26 to 33 VGPRs and a
+// wave per SIMD (profiles/decode_twins_ab.md).
 template <int NV>
-__global__ __launch_bounds__(kTopkThreads) void beam_topk_kernel(DevState *sp)
+__device__ __forceinline__ float topk_row_max(const float (&xv)[NV], int Vn, int tid, float *sv)
 {
-    constexpr int NW = kTopkThreads / 64;
-    __shared__ float sv[NW];
-    __shared__ float wv[NW * kMaxBeam];
-    __shared__ int wi[NW * kMaxBeam];
-    WR_STAMP_DECL;
-    WR_STAMP_RT(7);
-    WR_STAMP(0);
-    const DevState S = *sp;
-    const Dims &d = S.d;
-    const int n = blockIdx.x, tid = threadIdx.x;
-    // no branch before the loads: the lane's scalars and both rows are requested in one batch (idle lanes leave
-    // after the first reduction)
-    const int act = S.lane_active[n];
-    const int b = n / S.beam;
-    int fr = S.frame[b];
-    fr = fr < S.T ? fr : S.T - 1;
-    const float *__restrict__ x = S.logits + (size_t)n * d.V;
-    const float *__restrict__ cp = S.ctc_logp + ((size_t)b * S.T + fr) * d.V;
-    const float ninf = -__builtin_huge_valf();
-    float xv[NV], cv[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int v = tid + i * kTopkThreads;
-        xv[i] = x[v < d.V ? v : d.V - 1];
-        cv[i] = cp[v < d.V ? v : d.V - 1];
-    }
     float m = -3.0e38f;
 #pragma unroll
-    for (int i = 0; i < NV; ++i) m = fmaxf(m, (tid + i * kTopkThreads < d.V) ? xv[i] : -3.0e38f);
-    m = block_max(m, sv);
-    WR_STAMP(1);                                   // rows arrived, first reduction done
-    if (!act) return;
+    for (int i = 0; i < NV; ++i) m = fmaxf(m, (tid + i * kTopkThreads < Vn) ? xv[i] : -3.0e38f);
+    return block_max(m, sv);
+}
+template <int NV>
+__device__ __forceinline__ float topk_row_log_sum(const float (&xv)[NV], float m, int Vn, int tid, float *sv)
+{
     float sum = 0.f;
 #pragma unroll
-    for (int i = 0; i < NV; ++i) sum += (tid + i * kTopkThreads < d.V) ? expf(xv[i] - m) : 0.f;
-    sum = block_sum(sum, sv);
-    const float ls = logf(sum);
-    WR_STAMP(2);
+    for (int i = 0; i < NV; ++i) sum += (tid + i * kTopkThreads < Vn) ? expf(xv[i] - m) : 0.f;
+    return logf(block_sum(sum, sv));
+}
+template <int NV, bool CTC_OPT>
+__device__ __forceinline__ void topk_mix_select(const DevState &S, float (&xv)[NV], const float (&cv)[NV], float m, float ls, bool has_ctc,
+                                                int Vn, int tid, float *wv, int *wi)
+{
+    const float ninf = -__builtin_huge_valf();
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const float l = (xv[i] - m) - ls;
         // prefix_beam_search.py:99-101: log(tw * exp(logp) + cw * exp(ctc[i]))
-        xv[i] = (tid + i * kTopkThreads < d.V) ? logf(S.tr_weight * expf(l) + S.ctc_weight * expf(cv[i])) : ninf;
+        const float mix = (!CTC_OPT || has_ctc) ? logf(S.tr_weight * expf(l) + S.ctc_weight * expf(cv[i])) : l;
+        xv[i] = (tid + i * kTopkThreads < Vn) ? mix : ninf;
     }
     const int lane = tid & 63, wave = tid >> 6;
     for (int k = 0; k < S.beam; ++k) {
@@ -1847,6 +1822,72 @@ __global__ __launch_bounds__(kTopkThreads) void beam_topk_kernel(DevState *sp)
                 if (i == bi / kTopkThreads) xv[i] = ninf;
         }
     }
+}
+
+// wave 0 merges the waves' survivors (wv / wi, after a barrier): kth(k, best, bi) for k = 0 .. beam-1 in descending order,
+// every lane of the wave holding the k-th best value and its index; ties go to the lower index
+template <typename F>
+__device__ __forceinline__ void topk_merge(const float *wv, const int *wi, int beam, int lane, F &&kth)
+{
+    constexpr int NW = kTopkThreads / 64;
+    constexpr int PM = NW * kMaxBeam / 64;          // survivors per lane of wave 0
+    const float ninf = -__builtin_huge_valf();
+    const int total = NW * beam;
+    float c0[PM];
+    int ci[PM];
+#pragma unroll
+    for (int q = 0; q < PM; ++q) {
+        const int j = lane + q * 64;
+        c0[q] = j < total ? wv[j] : ninf;
+        ci[q] = j < total ? wi[j] : 0x7fffffff;
+    }
+    for (int k = 0; k < beam; ++k) {
+        float best = ninf;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int q = 0; q < PM; ++q)
+            if (c0[q] > best || (c0[q] == best && ci[q] < bi)) { best = c0[q]; bi = ci[q]; }
+        wave_argmax_dpp(best, bi);
+        kth(k, best, bi);
+#pragma unroll
+        for (int q = 0; q < PM; ++q)
+            if (ci[q] == bi) c0[q] = ninf;
+    }
+}
+
+template <int NV>
+__global__ __launch_bounds__(kTopkThreads) void beam_topk_kernel(DevState *sp)
+{
+    constexpr int NW = kTopkThreads / 64;
+    __shared__ float sv[NW], wv[NW * kMaxBeam];
+    __shared__ int wi[NW * kMaxBeam];
+    WR_STAMP_DECL;
+    WR_STAMP_RT(7);
+    WR_STAMP(0);
+    const DevState S = *sp;
+    const Dims &d = S.d;
+    const int n = blockIdx.x, tid = threadIdx.x;
+    // no branch before the loads: the lane's scalars and both rows are requested in one batch (idle lanes leave
+    // after the first reduction)
+    const int act = S.lane_active[n];
+    const int b = n / S.beam;
+    int fr = S.frame[b];
+    fr = fr < S.T ? fr : S.T - 1;
+    const float *__restrict__ x = S.logits + (size_t)n * d.V;
+    const float *__restrict__ cp = S.ctc_logp + ((size_t)b * S.T + fr) * d.V;
+    float xv[NV], cv[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int v = tid + i * kTopkThreads;
+        xv[i] = x[v < d.V ? v : d.V - 1];
+        cv[i] = cp[v < d.V ? v : d.V - 1];
+    }
+    const float m = topk_row_max(xv, d.V, tid, sv);
+    WR_STAMP(1);                                   // rows arrived, first reduction done
+    if (!act) return;
+    const float ls = topk_row_log_sum(xv, m, d.V, tid, sv);
+    WR_STAMP(2);
+    topk_mix_select<NV, false>(S, xv, cv, m, ls, true, d.V, tid, wv, wi);
     // touch the next frame's CTC row (one word per 128-byte line) so that it is already in the Infinity Cache and
     // its translation cached when the next micro-step asks for it
     if (fr + 1 < S.T && tid * 32 < d.V) {
@@ -1856,33 +1897,13 @@ __global__ __launch_bounds__(kTopkThreads) void beam_topk_kernel(DevState *sp)
     WR_STAMP(3);                                   // per-wave selection rounds done
     __syncthreads();
     WR_STAMP(4);
-    if (wave == 0) {
-        constexpr int PM = NW * kMaxBeam / 64;      // survivors per lane of wave 0
-        const int total = NW * S.beam;
-        float c0[PM];
-        int ci[PM];
-#pragma unroll
-        for (int q = 0; q < PM; ++q) {
-            const int j = lane + q * 64;
-            c0[q] = j < total ? wv[j] : ninf;
-            ci[q] = j < total ? wi[j] : 0x7fffffff;
-        }
-        for (int k = 0; k < S.beam; ++k) {
-            float best = ninf;
-            int bi = 0x7fffffff;
-#pragma unroll
-            for (int q = 0; q < PM; ++q)
-                if (c0[q] > best || (c0[q] == best && ci[q] < bi)) { best = c0[q]; bi = ci[q]; }
-            wave_argmax_dpp(best, bi);
-            if (lane == 0) {
+    if (tid < 64)
+        topk_merge(wv, wi, S.beam, tid, [&](int k, float best, int bi) {
+            if (tid == 0) {
                 S.topv[(size_t)n * S.beam + k] = best;
                 S.topi[(size_t)n * S.beam + k] = (bi < d.V) ? bi : 0;
             }
-#pragma unroll
-            for (int q = 0; q < PM; ++q)
-                if (ci[q] == bi) c0[q] = ninf;
-        }
-    }
+        });
     WR_STAMP(5);
     WR_STAMP_DRAIN();
     WR_STAMP(6);
@@ -1909,66 +1930,29 @@ __device__ __forceinline__ double log_add2(double a, double b)
 // so each batch of rows is read into registers, synchronised and written back in place).
 constexpr int kBeamUpdThreads = 1024;   // one workgroup per utterance; 256 threads in round 2 (the all-pairs steps and the
                                         // layer-0 cells of the survivors are 4 x as parallel now)
-__global__ __launch_bounds__(kBeamUpdThreads) void beam_update_kernel(DevState *sp)
+// The workgroup's LDS record of the candidates (c_*, f_score) and of the pruned beam (order, e_*) that the shared phases
+// below work on; both update kernels fill c_* and e_lb in their own phase 1.
+struct BeamUpdLds {
+    static constexpr int MC = kMaxBeam * kMaxBeam;
+    double c_score[MC], f_score[MC];
+    unsigned long long c_hash[MC];
+    int c_base[MC], c_tok[MC], c_len[MC], c_last[MC], c_rep[MC], c_rank[MC], order[kMaxBeam];
+    int e_src[kMaxBeam], e_blank[kMaxBeam], e_tok[kMaxBeam], e_last[kMaxBeam], e_lb[kMaxBeam];
+};
+
+// phase 2: class representative = the first candidate with the same token sequence (:130-142) -- and, WITH_FRAME, the same
+// frame c_t (c_t is not read otherwise)
+template <bool WITH_FRAME>
+__device__ __forceinline__ void beam_find_classes(BeamUpdLds &L, const int *c_t, const int32_t *__restrict__ hy, int Lmax, int C, int tid)
 {
-    constexpr int NT = kBeamUpdThreads;
-    constexpr int MC = kMaxBeam * kMaxBeam;
-    __shared__ int c_base[MC], c_tok[MC], c_len[MC], c_last[MC], c_rep[MC], c_rank[MC], order[kMaxBeam];
-    __shared__ unsigned long long c_hash[MC];
-    __shared__ int e_src[kMaxBeam], e_blank[kMaxBeam], e_tok[kMaxBeam], e_last[kMaxBeam], e_lb[kMaxBeam];
-    __shared__ double c_score[MC], f_score[MC];
-    __shared__ int s_keep;
-    WR_STAMP_DECL;
-    WR_STAMP_RT(7);
-    WR_STAMP(0);
-    const DevState S = *sp;
-    const Dims &d = S.d;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int beam = S.beam;
-    const int T = S.enc_lens[b] < S.T ? S.enc_lens[b] : S.T;
-    const int fr = S.frame[b];
-    if (fr >= T) return;
-    const int N = S.n_hyps[b];
-    const int C = N * beam;
-    const int sel = S.hyp_sel[b];
-    const size_t hstride = (size_t)S.n_utt * beam * S.Lmax;
-    const int32_t *__restrict__ hy = S.bhyps + sel * hstride + (size_t)b * beam * S.Lmax;
-    int32_t *__restrict__ hy2 = S.bhyps + (1 - sel) * hstride + (size_t)b * beam * S.Lmax;
-    const int32_t *__restrict__ hl = S.bhyp_lens + (size_t)sel * S.n_utt * beam + (size_t)b * beam;
-    int32_t *__restrict__ hl2 = S.bhyp_lens + (size_t)(1 - sel) * S.n_utt * beam + (size_t)b * beam;
-    // phase 1: candidates in the reference's order (hypothesis-major, then top-k rank; :109-127)
-    if (tid < kMaxBeam) e_lb[tid] = tid < N ? hl[tid] : 0;
-    if (tid == 0) s_keep = 0;
-    if (tid < C) {
-        const int j = tid / beam, t = tid - j * beam;
-        const int n = b * beam + j;
-        const int tok = S.topi[(size_t)n * beam + t];
-        // scores tensor is fp32 built from Python floats (:86); add in fp32 (:105); .item() -> float64 (:116)
-        const float sj = (float)S.bscores[(size_t)b * beam + j];
-        const float tv = S.topv[(size_t)n * beam + t];
-        const int lb = hl[j];
-        const int last = S.token[n];               // last token of hypothesis j (this frame's predictor input)
-        const unsigned long long hh = S.bhash[n];
-        c_score[tid] = (double)(sj + tv);
-        c_base[tid] = j;
-        c_tok[tid] = tok;
-        c_len[tid] = lb + (tok != S.blank ? 1 : 0);
-        c_last[tid] = (tok != S.blank) ? tok : last;
-        c_hash[tid] = (tok != S.blank) ? hyp_hash_push(hh, tok) : hh;
-        c_rep[tid] = tid;
-        c_rank[tid] = 0;
-    }
-    __syncthreads();
-    WR_STAMP(1);                                   // candidates built
-    // phase 2: class representative = the first candidate with the same token sequence (:130-142)
-    for (int p = tid; p < C * C; p += NT) {
+    for (int p = tid; p < C * C; p += kBeamUpdThreads) {
         const int i = p / C, f = p - i * C;
-        if (f >= i || c_hash[f] != c_hash[i] || c_len[f] != c_len[i] || c_last[f] != c_last[i]) continue;
+        if (f >= i || (WITH_FRAME && c_t[f] != c_t[i]) || L.c_hash[f] != L.c_hash[i] || L.c_len[f] != L.c_len[i] || L.c_last[f] != L.c_last[i]) continue;
         // equal hashes, lengths and last tokens: the sequences are equal iff the first len-1 tokens of the two base
         // hypotheses are (both bases hold at least that many); compared in batches of independent loads
-        const int32_t *__restrict__ pi = hy + (size_t)c_base[i] * S.Lmax;
-        const int32_t *__restrict__ pf = hy + (size_t)c_base[f] * S.Lmax;
-        const int ncmp = c_len[i] - 1;
+        const int32_t *__restrict__ pi = hy + (size_t)L.c_base[i] * Lmax;
+        const int32_t *__restrict__ pf = hy + (size_t)L.c_base[f] * Lmax;
+        const int ncmp = L.c_len[i] - 1;
         bool same = true;
         constexpr int UC = 16;
         for (int q0 = 0; q0 < ncmp && same; q0 += UC) {
@@ -1982,98 +1966,122 @@ __global__ __launch_bounds__(kBeamUpdThreads) void beam_update_kernel(DevState *
 #pragma unroll
             for (int u = 0; u < UC; ++u) same = same && (xa[u] == ya[u]);
         }
-        if (same) atomicMin(&c_rep[i], f);
+        if (same) atomicMin(&L.c_rep[i], f);
     }
     __syncthreads();
-    WR_STAMP(2);                                   // classes known
-    // phase 3: a representative accumulates its duplicates' scores in candidate order with float64 log_add
-    // (a float64 exp + log is ~2 us of dependent instructions and a wave runs it for one lane at a time: consecutive
-    // candidates sit in different waves, so that the few duplicates of a frame are summed side by side)
-    // Most frames have no duplicate at all: then the fused scores are the candidates' own (one count over the workgroup
-    // instead of every candidate scanning all later ones).
-    const int n_dup = __syncthreads_count(tid < C && c_rep[tid] != tid);
+}
+
+// phase 3: a representative accumulates its duplicates' scores in candidate order with float64 log_add
+// (a float64 exp + log is ~2 us of dependent instructions and a wave runs it for one lane at a time: consecutive
+// candidates sit in different waves, so that the few duplicates of a frame are summed side by side)
+// Most frames have no duplicate at all: then the fused scores are the candidates' own (one count over the workgroup
+// instead of every candidate scanning all later ones).
+__device__ __forceinline__ void beam_fuse_scores(BeamUpdLds &L, int C, int tid)
+{
+    const int n_dup = __syncthreads_count(tid < C && L.c_rep[tid] != tid);
     if (n_dup == 0) {
-        if (tid < C) f_score[tid] = c_score[tid];
+        if (tid < C) L.f_score[tid] = L.c_score[tid];
     } else {
-        const int c = (tid & 63) * (NT / 64) + (tid >> 6);
+        const int c = (tid & 63) * (kBeamUpdThreads / 64) + (tid >> 6);
         if (c < C) {
-            double sc = c_score[c];
-            if (c_rep[c] == c) {
+            double sc = L.c_score[c];
+            if (L.c_rep[c] == c) {
 #pragma unroll 8
                 for (int f = c + 1; f < C; ++f)
-                    if (c_rep[f] == c) sc = log_add2(sc, c_score[f]);
+                    if (L.c_rep[f] == c) sc = log_add2(sc, L.c_score[f]);
             }
-            f_score[c] = sc;
+            L.f_score[c] = sc;
         }
     }
     __syncthreads();
-    WR_STAMP(9);                                   // duplicates' scores summed
-    // phase 4: stable descending sort position among representatives (list.sort(reverse=True) keeps order on ties)
-    for (int p = tid; p < C * C; p += NT) {
+}
+
+// phase 4: stable descending sort position among representatives (list.sort(reverse=True) keeps order on ties), the prune
+// to `beam`, and the survivors' record: e_* in LDS, length / score / hash / next predictor input of lane b * beam + rank.
+// not_appended(c_tok) says whether a candidate added no token to its base.  Returns the survivor count; the caller
+// synchronises before anyone reads e_*.  Called once per kernel: the count lives in s_keep, zeroed here behind the barrier.
+template <typename F>
+__device__ __forceinline__ int beam_rank_prune(const DevState &S, BeamUpdLds &L, int32_t *__restrict__ hl2, int b, int C, int tid, F &&not_appended)
+{
+    __shared__ int s_keep;
+    const int beam = S.beam;
+    if (tid == 0) s_keep = 0;
+    for (int p = tid; p < C * C; p += kBeamUpdThreads) {
         const int i = p / C, f = p - i * C;
-        if (c_rep[i] != i || c_rep[f] != f) continue;
-        const double me = f_score[i], ot = f_score[f];
-        if (ot > me || (ot == me && f < i)) atomicAdd(&c_rank[i], 1);
+        if (L.c_rep[i] != i || L.c_rep[f] != f) continue;
+        const double me = L.f_score[i], ot = L.f_score[f];
+        if (ot > me || (ot == me && f < i)) atomicAdd(&L.c_rank[i], 1);
     }
     __syncthreads();
-    if (tid < C && c_rep[tid] == tid) {
-        if (c_rank[tid] < beam) order[c_rank[tid]] = tid;
+    if (tid < C && L.c_rep[tid] == tid) {
+        if (L.c_rank[tid] < beam) L.order[L.c_rank[tid]] = tid;
         atomicAdd(&s_keep, 1);
     }
     __syncthreads();
     const int keep = s_keep < beam ? s_keep : beam;
     if (tid < keep) {
-        const int f = order[tid];
-        e_src[tid] = c_base[f];
-        e_tok[tid] = c_tok[f];
-        e_blank[tid] = (c_tok[f] == S.blank);
-        e_last[tid] = c_last[f];
-        hl2[tid] = c_len[f];
-        S.bscores[(size_t)b * beam + tid] = f_score[f];
-        S.bhash[b * beam + tid] = c_hash[f];
-        S.token[b * beam + tid] = c_last[f];       // next frame's predictor input: last token of the hypothesis (:78-80)
+        const int f = L.order[tid];
+        L.e_src[tid] = L.c_base[f];
+        L.e_tok[tid] = L.c_tok[f];
+        L.e_blank[tid] = not_appended(L.c_tok[f]);
+        L.e_last[tid] = L.c_last[f];
+        hl2[tid] = L.c_len[f];
+        S.bscores[(size_t)b * beam + tid] = L.f_score[f];
+        S.bhash[b * beam + tid] = L.c_hash[f];
+        S.token[b * beam + tid] = L.c_last[f];     // next frame's predictor input: last token of the hypothesis (:78-80)
     }
-    __syncthreads();
-    WR_STAMP(3);                                   // fused, ranked, pruned
-    // phase 5: the pruned beam -- hypotheses into the other buffer, (survivor, position) pairs in flight together
-    {
-        int maxlb = 0;
-        for (int e = 0; e < keep; ++e) maxlb = e_lb[e_src[e]] > maxlb ? e_lb[e_src[e]] : maxlb;
-        constexpr int UN = 4;
-        for (int i0 = 0; i0 < keep * maxlb; i0 += NT * UN) {
-            int val[UN];
+    return keep;
+}
+
+// phase 5: the pruned beam -- hypotheses into the other buffer, (survivor, position) pairs in flight together
+__device__ __forceinline__ void beam_move_hyps(const BeamUpdLds &L, const int32_t *__restrict__ hy, int32_t *__restrict__ hy2, int Lmax, int keep, int tid)
+{
+    constexpr int NT = kBeamUpdThreads;
+    int maxlb = 0;
+    for (int e = 0; e < keep; ++e) maxlb = L.e_lb[L.e_src[e]] > maxlb ? L.e_lb[L.e_src[e]] : maxlb;
+    constexpr int UN = 4;
+    for (int i0 = 0; i0 < keep * maxlb; i0 += NT * UN) {
+        int val[UN];
 #pragma unroll
-            for (int u = 0; u < UN; ++u) {
-                const int i = i0 + u * NT + tid;
-                const int e = i / maxlb, q = i - e * maxlb;
-                const bool in = e < keep && q < e_lb[e_src[e < keep ? e : 0]];
-                val[u] = in ? hy[(size_t)e_src[e] * S.Lmax + q] : 0;
-            }
-#pragma unroll
-            for (int u = 0; u < UN; ++u) {
-                const int i = i0 + u * NT + tid;
-                const int e = i / maxlb, q = i - e * maxlb;
-                if (e < keep && q < e_lb[e_src[e]]) hy2[(size_t)e * S.Lmax + q] = val[u];
-            }
+        for (int u = 0; u < UN; ++u) {
+            const int i = i0 + u * NT + tid;
+            const int e = i / maxlb, q = i - e * maxlb;
+            const bool in = e < keep && q < L.e_lb[L.e_src[e < keep ? e : 0]];
+            val[u] = in ? hy[(size_t)L.e_src[e] * Lmax + q] : 0;
         }
-        if (tid < keep) {
-            const int lb = e_lb[e_src[tid]];
-            if (!e_blank[tid] && lb < S.Lmax) hy2[(size_t)tid * S.Lmax + lb] = e_tok[tid];
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            const int i = i0 + u * NT + tid;
+            const int e = i / maxlb, q = i - e * maxlb;
+            if (e < keep && q < L.e_lb[L.e_src[e]]) hy2[(size_t)e * Lmax + q] = val[u];
         }
     }
-    WR_STAMP(4);                                   // hypotheses moved
+    if (tid < keep) {
+        const int lb = L.e_lb[L.e_src[tid]];
+        if (!L.e_blank[tid] && lb < Lmax) hy2[(size_t)tid * Lmax + lb] = L.e_tok[tid];
+    }
+}
+
+// the survivors' predictor state and next predictor input.  A survivor that appended nothing (e_blank: a blank extension,
+// or a hypothesis that waited) inherits its base hypothesis' committed state, a label the state the predictor stepped to.
+__device__ __forceinline__ void beam_move_predictor(const DevState &S, const BeamUpdLds &L, int b, int keep, int tid)
+{
+    constexpr int NT = kBeamUpdThreads;
+    const Dims &d = S.d;
+    const int beam = S.beam;
     if (d.ptype == kPredLstm) {
         // LSTM predictor: a survivor inherits a slot NUMBER -- its base hypothesis' committed slot for a blank extension,
-        // the slot of the base's new state for a label (:111-124; several survivors may share one) -- and gets a free slot
-        // of the utterance's 2 * beam for its own next step; then layer 0 of that step (lstm_layer0_cell).  Nothing is
-        // copied.  Slots of utterance b: lanes' numbers b * beam + j and NLp + b * beam + j.
+        // the slot of the base's new state for a label (:111-124; several survivors may share one; only an expanded base
+        // has one) -- and gets a free slot of the utterance's 2 * beam for its own next step; then layer 0 of that step
+        // (lstm_layer0_cell), whenever that step will be consulted.  Nothing is copied.  Slots of utterance b: lanes'
+        // numbers b * beam + j and NLp + b * beam + j.
         __shared__ int s_comm[kMaxBeam], s_new[kMaxBeam], s_oc[kMaxBeam], s_on[kMaxBeam];
         if (tid < beam) { s_oc[tid] = S.comm_slot[b * beam + tid]; s_on[tid] = S.new_slot[b * beam + tid]; }
         __syncthreads();
         if (tid == 0) {
             unsigned used = 0;                                   // bit j: slot b*beam + j, bit beam + j: slot NLp + b*beam + j
             for (int e = 0; e < keep; ++e) {
-                const int sl = e_blank[e] ? s_oc[e_src[e]] : s_on[e_src[e]];
+                const int sl = L.e_blank[e] ? s_oc[L.e_src[e]] : s_on[L.e_src[e]];
                 s_comm[e] = sl;
                 used |= 1u << (sl >= d.NLp ? beam + (sl - d.NLp - b * beam) : sl - b * beam);
             }
@@ -2091,91 +2099,140 @@ __global__ __launch_bounds__(kBeamUpdThreads) void beam_update_kernel(DevState *
         if (tid < beam) { S.comm_slot[b * beam + tid] = s_comm[tid]; S.new_slot[b * beam + tid] = s_new[tid]; }
         // layer 0 of every survivor's next step (lstm_layer0_cell), (survivor, unit) pairs spread over the workgroup with
         // the loads of two pairs per thread in flight together
-        {
-            constexpr int UN = 2;
-            const int items = keep * d.H;
-            for (int i0 = 0; i0 < items; i0 += NT * UN) {
-                float ev[UN][4], gv[UN][4], cv[UN];
+        constexpr int UN = 2;
+        const int items = keep * d.H;
+        for (int i0 = 0; i0 < items; i0 += NT * UN) {
+            float ev[UN][4], gv[UN][4], cv[UN];
 #pragma unroll
-                for (int q = 0; q < UN; ++q) {
-                    const int i = i0 + q * NT + tid;
-                    const int e = i < items ? i / d.H : 0, u = i < items ? i - e * d.H : 0;
-                    const int col = (u >> 3) * 32 + (u & 7);
-                    const float *__restrict__ er = S.etab + (size_t)e_last[e] * d.G4p + col;
-                    const float *__restrict__ gr = S.pool_g + (size_t)s_comm[e] * d.G4p + col;
+            for (int q = 0; q < UN; ++q) {
+                const int i = i0 + q * NT + tid;
+                const int e = i < items ? i / d.H : 0, u = i < items ? i - e * d.H : 0;
+                const int col = (u >> 3) * 32 + (u & 7);
+                const float *__restrict__ er = S.etab + (size_t)L.e_last[e] * d.G4p + col;
+                const float *__restrict__ gr = S.pool_g + (size_t)s_comm[e] * d.G4p + col;
 #pragma unroll
-                    for (int gt = 0; gt < 4; ++gt) { ev[q][gt] = er[gt * 8]; gv[q][gt] = gr[gt * 8]; }
-                    cv[q] = S.pool_c[(size_t)s_comm[e] * d.Hp + u];
-                }
+                for (int gt = 0; gt < 4; ++gt) { ev[q][gt] = er[gt * 8]; gv[q][gt] = gr[gt * 8]; }
+                cv[q] = S.pool_c[(size_t)s_comm[e] * d.Hp + u];
+            }
 #pragma unroll
-                for (int q = 0; q < UN; ++q) {
-                    const int i = i0 + q * NT + tid;
-                    if (i >= items) continue;
-                    const int e = i / d.H, u = i - e * d.H;
-                    const float ig = sigmoidf_(ev[q][0] + gv[q][0]);
-                    const float fg = sigmoidf_(ev[q][1] + gv[q][1]);
-                    const float gg = tanhf(ev[q][2] + gv[q][2]);
-                    const float og = sigmoidf_(ev[q][3] + gv[q][3]);
-                    const float c = fg * cv[q] + ig * gg;
-                    S.pool_c[(size_t)s_new[e] * d.Hp + u] = c;
-                    S.new_hT[(size_t)u * d.NLp + b * beam + e] = og * tanhf(c);
-                }
+            for (int q = 0; q < UN; ++q) {
+                const int i = i0 + q * NT + tid;
+                if (i >= items) continue;
+                const int e = i / d.H, u = i - e * d.H;
+                const float ig = sigmoidf_(ev[q][0] + gv[q][0]);
+                const float fg = sigmoidf_(ev[q][1] + gv[q][1]);
+                const float gg = tanhf(ev[q][2] + gv[q][2]);
+                const float og = sigmoidf_(ev[q][3] + gv[q][3]);
+                const float c = __builtin_fmaf(ig, gg, fg * cv[q]);    // ig * gg fused, fg * c rounded: stated, not left to -ffp-contract
+                S.pool_c[(size_t)s_new[e] * d.Hp + u] = c;
+                S.new_hT[(size_t)u * d.NLp + b * beam + e] = og * tanhf(c);
             }
         }
-    } else {
+        return;
+    }
     // next predictor inputs
-    {
-        constexpr int UN = 4;
-        const float *__restrict__ emb = S.embed;
-        for (int i0 = 0; i0 < keep * d.D; i0 += NT * UN) {
-            float val[UN];
+    constexpr int UI = 4;
+    const float *__restrict__ emb = S.embed;
+    for (int i0 = 0; i0 < keep * d.D; i0 += NT * UI) {
+        float val[UI];
 #pragma unroll
-            for (int u = 0; u < UN; ++u) {
-                const int i = i0 + u * NT + tid;
-                const int e = i / d.D, k = i - e * d.D;
-                val[u] = e < keep ? emb[(size_t)e_last[e] * d.D + k] : 0.f;
-            }
+        for (int u = 0; u < UI; ++u) {
+            const int i = i0 + u * NT + tid;
+            const int e = i / d.D, k = i - e * d.D;
+            val[u] = e < keep ? emb[(size_t)L.e_last[e] * d.D + k] : 0.f;
+        }
 #pragma unroll
-            for (int u = 0; u < UN; ++u) {
-                const int i = i0 + u * NT + tid;
-                const int e = i / d.D, k = i - e * d.D;
-                if (e < keep) S.xT[(size_t)k * d.NLp + b * beam + e] = val[u];
+        for (int u = 0; u < UI; ++u) {
+            const int i = i0 + u * NT + tid;
+            const int e = i / d.D, k = i - e * d.D;
+            if (e < keep) S.xT[(size_t)k * d.NLp + b * beam + e] = val[u];
+        }
+    }
+    // predictor caches (token histories): a blank extension keeps the base hypothesis' cache, a label takes the predictor's
+    // new cache (:111-124).  Rows i of [L*Hp][NLp]; a thread owns (row, survivor) pairs, `beam` survivors per row; each
+    // batch of rows is read into registers, synchronised and written back in place.
+    constexpr int UN = 8;
+    const int rows = d.L * d.Hp, per_it = NT / beam;           // rows per pass of the workgroup
+    const int e = tid % beam, r0 = tid / beam;
+    const bool on = e < keep && r0 < per_it;
+    const int src = b * beam + (on ? L.e_src[e] : 0), dst = b * beam + e;
+    const bool bl = on ? L.e_blank[e] != 0 : true;
+    const float *hsrc = bl ? S.cache_hT : S.new_hT;
+    const float *csrc = bl ? S.cache_cT : S.new_cT;
+    for (int rb = 0; rb < rows; rb += per_it * UN) {
+        float hv[UN], cw[UN];
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            const int r = rb + u * per_it + r0;
+            const size_t so = (size_t)(r < rows ? r : 0) * d.NLp + src;
+            hv[u] = hsrc[so];
+            cw[u] = csrc[so];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            const int r = rb + u * per_it + r0;
+            if (on && r < rows) {
+                const size_t dst_o = (size_t)r * d.NLp + dst;
+                S.cache_hT[dst_o] = hv[u];
+                S.cache_cT[dst_o] = cw[u];
             }
         }
     }
-    // predictor caches: a blank extension keeps the base hypothesis' cache, a label takes the predictor's new
-    // cache (:111-124).  Rows i of [L*Hp][NLp]; a thread owns (row, survivor) pairs, `beam` survivors per row.
-    {
-        constexpr int UN = 8;
-        const int rows = d.L * d.Hp, per_it = NT / beam;           // rows per pass of the workgroup
-        const int e = tid % beam, r0 = tid / beam;
-        const bool on = e < keep && r0 < per_it;
-        const int src = b * beam + (on ? e_src[e] : 0), dst = b * beam + e;
-        const bool bl = on ? e_blank[e] != 0 : true;
-        const float *hsrc = bl ? S.cache_hT : S.new_hT;
-        const float *csrc = bl ? S.cache_cT : S.new_cT;
-        for (int rb = 0; rb < rows; rb += per_it * UN) {
-            float hv[UN], cw[UN];
-#pragma unroll
-            for (int u = 0; u < UN; ++u) {
-                const int r = rb + u * per_it + r0;
-                const size_t so = (size_t)(r < rows ? r : 0) * d.NLp + src;
-                hv[u] = hsrc[so];
-                cw[u] = csrc[so];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int u = 0; u < UN; ++u) {
-                const int r = rb + u * per_it + r0;
-                if (on && r < rows) {
-                    const size_t dst_o = (size_t)r * d.NLp + dst;
-                    S.cache_hT[dst_o] = hv[u];
-                    S.cache_cT[dst_o] = cw[u];
-                }
-            }
-        }
+}
+
+__global__ __launch_bounds__(kBeamUpdThreads) void beam_update_kernel(DevState *sp)
+{
+    __shared__ BeamUpdLds L;
+    WR_STAMP_DECL;
+    WR_STAMP_RT(7);
+    WR_STAMP(0);
+    const DevState S = *sp;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int beam = S.beam;
+    const int T = S.enc_lens[b] < S.T ? S.enc_lens[b] : S.T;
+    const int fr = S.frame[b];
+    if (fr >= T) return;
+    const int N = S.n_hyps[b], C = N * beam;
+    const int sel = S.hyp_sel[b];
+    const size_t hstride = (size_t)S.n_utt * beam * S.Lmax;
+    const int32_t *__restrict__ hy = S.bhyps + sel * hstride + (size_t)b * beam * S.Lmax;
+    int32_t *__restrict__ hy2 = S.bhyps + (1 - sel) * hstride + (size_t)b * beam * S.Lmax;
+    const int32_t *__restrict__ hl = S.bhyp_lens + (size_t)sel * S.n_utt * beam + (size_t)b * beam;
+    int32_t *__restrict__ hl2 = S.bhyp_lens + (size_t)(1 - sel) * S.n_utt * beam + (size_t)b * beam;
+    // phase 1: candidates in the reference's order (hypothesis-major, then top-k rank; :109-127)
+    if (tid < kMaxBeam) L.e_lb[tid] = tid < N ? hl[tid] : 0;
+    if (tid < C) {
+        const int j = tid / beam, t = tid - j * beam;
+        const int n = b * beam + j;
+        const int tok = S.topi[(size_t)n * beam + t];
+        // scores tensor is fp32 built from Python floats (:86); add in fp32 (:105); .item() -> float64 (:116)
+        const float sj = (float)S.bscores[(size_t)b * beam + j];
+        const float tv = S.topv[(size_t)n * beam + t];
+        const int lb = hl[j];
+        const int last = S.token[n];               // last token of hypothesis j (this frame's predictor input)
+        const unsigned long long hh = S.bhash[n];
+        L.c_score[tid] = (double)(sj + tv);
+        L.c_base[tid] = j;
+        L.c_tok[tid] = tok;
+        L.c_len[tid] = lb + (tok != S.blank ? 1 : 0);
+        L.c_last[tid] = (tok != S.blank) ? tok : last;
+        L.c_hash[tid] = (tok != S.blank) ? hyp_hash_push(hh, tok) : hh;
+        L.c_rep[tid] = tid;
+        L.c_rank[tid] = 0;
     }
-    }
+    __syncthreads();
+    WR_STAMP(1);                                   // candidates built
+    beam_find_classes<false>(L, nullptr, hy, S.Lmax, C, tid);
+    WR_STAMP(2);                                   // classes known
+    beam_fuse_scores(L, C, tid);
+    WR_STAMP(9);                                   // duplicates' scores summed
+    const int keep = beam_rank_prune(S, L, hl2, b, C, tid, [&](int tok) { return tok == S.blank; });
+    __syncthreads();
+    WR_STAMP(3);                                   // fused, ranked, pruned
+    beam_move_hyps(L, hy, hy2, S.Lmax, keep, tid);
+    WR_STAMP(4);                                   // hypotheses moved
+    beam_move_predictor(S, L, b, keep, tid);
     if (tid < beam) {
         const int nfr = fr + 1;
         const int n = b * beam + tid;
@@ -2220,8 +2277,7 @@ template <int NV>
 __global__ __launch_bounds__(kTopkThreads) void tdt_beam_topk_kernel(DevState *sp)
 {
     constexpr int NW = kTopkThreads / 64;
-    __shared__ float sv[NW];
-    __shared__ float wv[NW * kMaxBeam];
+    __shared__ float sv[NW], wv[NW * kMaxBeam];
     __shared__ int wi[NW * kMaxBeam];
     const DevState S = *sp;
     const Dims &d = S.d;
@@ -2253,75 +2309,33 @@ __global__ __launch_bounds__(kTopkThreads) void tdt_beam_topk_kernel(DevState *s
         }
     }
     const float xd = x[Vt + (lane < D ? lane : 0)];           // the duration columns, one per lane of every wave
-    float m = -3.0e38f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) m = fmaxf(m, (tid + i * kTopkThreads < Vt) ? xv[i] : -3.0e38f);
-    m = block_max(m, sv);
+    const float m = topk_row_max(xv, Vt, tid, sv);
     if (!act) return;
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) sum += (tid + i * kTopkThreads < Vt) ? expf(xv[i] - m) : 0.f;
-    sum = block_sum(sum, sv);
-    const float ls = logf(sum);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const float l = (xv[i] - m) - ls;
-        const float mix = has_ctc ? logf(S.tr_weight * expf(l) + S.ctc_weight * expf(cv[i])) : l;
-        xv[i] = (tid + i * kTopkThreads < Vt) ? mix : ninf;
-    }
-    for (int k = 0; k < S.beam; ++k) {
-        float best = ninf;
-        int bi = 0x7fffffff;
-#pragma unroll
-        for (int i = 0; i < NV; ++i)
-            if (xv[i] > best) { best = xv[i]; bi = tid + i * kTopkThreads; }   // ascending scan: lowest index wins ties
-        wave_argmax_dpp(best, bi);
-        if (lane == 0) { wv[wave * S.beam + k] = best; wi[wave * S.beam + k] = bi; }
-        if (bi != 0x7fffffff && (bi % kTopkThreads) == tid) {                     // taken
-#pragma unroll
-            for (int i = 0; i < NV; ++i)
-                if (i == bi / kTopkThreads) xv[i] = ninf;
-        }
-    }
+    const float ls = topk_row_log_sum(xv, m, Vt, tid, sv);
+    topk_mix_select<NV, true>(S, xv, cv, m, ls, has_ctc, Vt, tid, wv, wi);
     __syncthreads();
     if (wave != 0) return;
     // duration log-softmax: lanes 0 .. D-1 of this wave hold the columns
     const float dm = wave_allmax_dpp(lane < D ? xd : -3.0e38f);
     const float ds = wave_allsum_dpp(lane < D ? expf(xd - dm) : 0.f);
     const float ldv = (xd - dm) - logf(ds);
-    constexpr int PM = NW * kMaxBeam / 64;      // token survivors per lane
     constexpr int PP = (kMaxBeam * kTdtMaxD + 63) / 64;   // (rank, duration) pairs per lane: pair p = r * D + j at lane p % 64
-    const int total = NW * S.beam, npair = S.beam * D;
-    float c0[PM], pv[PP], pl[PP];
-    int ci[PM], pk[PP];
-#pragma unroll
-    for (int q = 0; q < PM; ++q) {
-        const int j = lane + q * 64;
-        c0[q] = j < total ? wv[j] : ninf;
-        ci[q] = j < total ? wi[j] : 0x7fffffff;
-    }
+    const int npair = S.beam * D;
+    float pv[PP], pl[PP];
+    int pk[PP];
 #pragma unroll
     for (int q = 0; q < PP; ++q) {
         pl[q] = __shfl(ldv, (lane + q * 64) % D, kWave);
         pv[q] = ninf;
         pk[q] = 0;
     }
-    for (int k = 0; k < S.beam; ++k) {
-        float best = ninf;
-        int bi = 0x7fffffff;
-#pragma unroll
-        for (int q = 0; q < PM; ++q)
-            if (c0[q] > best || (c0[q] == best && ci[q] < bi)) { best = c0[q]; bi = ci[q]; }
-        wave_argmax_dpp(best, bi);
+    topk_merge(wv, wi, S.beam, lane, [&](int k, float best, int bi) {
 #pragma unroll
         for (int q = 0; q < PP; ++q) {
             const int p = lane + q * 64;
             if (p < npair && p / D == k) { pv[q] = best + pl[q]; pk[q] = bi < Vt ? bi : 0; }   // one fp32 add
         }
-#pragma unroll
-        for (int q = 0; q < PM; ++q)
-            if (ci[q] == bi) c0[q] = ninf;
-    }
+    });
     for (int c = 0; c < S.beam; ++c) {
         float best = ninf;
         int bp = 0x7fffffff;
@@ -2345,22 +2359,16 @@ __global__ __launch_bounds__(kTopkThreads) void tdt_beam_topk_kernel(DevState *s
     }
 }
 
-// one workgroup per utterance: the pool (a waiting hypothesis as it is, an active one's `beam` pairs), fusion of equal
-// (tokens, frame) with float64 log_add in pool order, stable prune, the survivors moved as beam_update_kernel moves them
-// (a waiting survivor and a blank extension inherit the committed predictor state, a label the stepped one), each
-// survivor's frame, and which of them stand at the new earliest frame.
+// one workgroup per utterance: the pool (a waiting hypothesis as it is, an active one's `beam` pairs), then the phases of
+// beam_update_kernel with the frame as part of a class's key -- the first pool entry with the same tokens and the same frame
+// represents the class and accumulates it in pool order (float64 log_add), stable prune, the survivors moved by
+// beam_move_hyps / beam_move_predictor (a waiting survivor and a blank extension inherit the committed predictor state, a
+// label the stepped one) -- then each survivor's frame, and which of them stand at the new earliest frame.
 __global__ __launch_bounds__(kBeamUpdThreads) void tdt_beam_update_kernel(DevState *sp)
 {
-    constexpr int NT = kBeamUpdThreads;
-    constexpr int MC = kMaxBeam * kMaxBeam;
-    __shared__ int c_base[MC], c_tok[MC], c_len[MC], c_last[MC], c_t[MC], c_rep[MC], c_rank[MC], order[kMaxBeam];
-    __shared__ unsigned long long c_hash[MC];
-    __shared__ int e_src[kMaxBeam], e_blank[kMaxBeam], e_tok[kMaxBeam], e_last[kMaxBeam], e_lb[kMaxBeam], e_t[kMaxBeam];
-    __shared__ int p_t[kMaxBeam], p_off[kMaxBeam + 1];
-    __shared__ double c_score[MC], f_score[MC];
-    __shared__ int s_keep, s_nact, s_fnext;
+    __shared__ BeamUpdLds L;
+    __shared__ int c_t[BeamUpdLds::MC], e_t[kMaxBeam], p_t[kMaxBeam], p_off[kMaxBeam + 1], s_nact, s_fnext;
     const DevState S = *sp;
-    const Dims &d = S.d;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int beam = S.beam;
     const int T = S.enc_lens[b] < S.T ? S.enc_lens[b] : S.T;
@@ -2375,7 +2383,7 @@ __global__ __launch_bounds__(kBeamUpdThreads) void tdt_beam_update_kernel(DevSta
     int32_t *__restrict__ hl2 = S.bhyp_lens + (size_t)(1 - sel) * S.n_utt * beam + (size_t)b * beam;
     // phase 1: the pool in the order of the beam
     if (tid < kMaxBeam) {                          // the entries' lengths and frames, requested side by side
-        e_lb[tid] = tid < N ? hl[tid] : 0;
+        L.e_lb[tid] = tid < N ? hl[tid] : 0;
         p_t[tid] = tid < N ? S.lane_t[b * beam + tid] : 0;
     }
     __syncthreads();
@@ -2389,7 +2397,6 @@ __global__ __launch_bounds__(kBeamUpdThreads) void tdt_beam_update_kernel(DevSta
         }
         p_off[N] = off;
         s_nact = na;
-        s_keep = 0;
     }
     __syncthreads();
     const int C = p_off[N];                        // <= beam * beam: a waiting hypothesis takes the place of `beam` pairs
@@ -2414,224 +2421,29 @@ __global__ __launch_bounds__(kBeamUpdThreads) void tdt_beam_update_kernel(DevSta
             tn = tn < T ? tn : T;
             if (k != S.blank) tok = k;
         }
-        c_score[tid] = sc;
-        c_base[tid] = e;
-        c_tok[tid] = tok;
+        L.c_score[tid] = sc;
+        L.c_base[tid] = e;
+        L.c_tok[tid] = tok;
         c_t[tid] = tn;
-        c_len[tid] = lb + (tok >= 0 ? 1 : 0);
-        c_last[tid] = tok >= 0 ? tok : last;
-        c_hash[tid] = tok >= 0 ? hyp_hash_push(hh, tok) : hh;
-        c_rep[tid] = tid;
-        c_rank[tid] = 0;
+        L.c_len[tid] = lb + (tok >= 0 ? 1 : 0);
+        L.c_last[tid] = tok >= 0 ? tok : last;
+        L.c_hash[tid] = tok >= 0 ? hyp_hash_push(hh, tok) : hh;
+        L.c_rep[tid] = tid;
+        L.c_rank[tid] = 0;
     }
     __syncthreads();
-    // phase 2: class representative = the first pool entry with the same tokens and the same frame
-    for (int p = tid; p < C * C; p += NT) {
-        const int i = p / C, f = p - i * C;
-        if (f >= i || c_t[f] != c_t[i] || c_hash[f] != c_hash[i] || c_len[f] != c_len[i] || c_last[f] != c_last[i]) continue;
-        // equal hashes, lengths and last tokens: the sequences are equal iff the first len-1 tokens of the two base
-        // hypotheses are (both bases hold at least that many)
-        const int32_t *__restrict__ pi = hy + (size_t)c_base[i] * S.Lmax;
-        const int32_t *__restrict__ pf = hy + (size_t)c_base[f] * S.Lmax;
-        const int ncmp = c_len[i] - 1;
-        bool same = true;
-        constexpr int UC = 16;
-        for (int q0 = 0; q0 < ncmp && same; q0 += UC) {
-            int xa[UC], ya[UC];
-#pragma unroll
-            for (int u = 0; u < UC; ++u) {
-                const int q = q0 + u < ncmp ? q0 + u : ncmp - 1;
-                xa[u] = pi[q];
-                ya[u] = pf[q];
-            }
-#pragma unroll
-            for (int u = 0; u < UC; ++u) same = same && (xa[u] == ya[u]);
-        }
-        if (same) atomicMin(&c_rep[i], f);
-    }
-    __syncthreads();
-    // phase 3: a representative accumulates its class in pool order with float64 log_add
-    const int n_dup = __syncthreads_count(tid < C && c_rep[tid] != tid);
-    if (n_dup == 0) {
-        if (tid < C) f_score[tid] = c_score[tid];
-    } else {
-        const int c = (tid & 63) * (NT / 64) + (tid >> 6);     // consecutive entries in different waves
-        if (c < C) {
-            double sc = c_score[c];
-            if (c_rep[c] == c) {
-#pragma unroll 8
-                for (int f = c + 1; f < C; ++f)
-                    if (c_rep[f] == c) sc = log_add2(sc, c_score[f]);
-            }
-            f_score[c] = sc;
-        }
-    }
-    __syncthreads();
-    // phase 4: stable descending rank among the representatives, prune
-    for (int p = tid; p < C * C; p += NT) {
-        const int i = p / C, f = p - i * C;
-        if (c_rep[i] != i || c_rep[f] != f) continue;
-        const double me = f_score[i], ot = f_score[f];
-        if (ot > me || (ot == me && f < i)) atomicAdd(&c_rank[i], 1);
-    }
-    __syncthreads();
-    if (tid < C && c_rep[tid] == tid) {
-        if (c_rank[tid] < beam) order[c_rank[tid]] = tid;
-        atomicAdd(&s_keep, 1);
-    }
-    __syncthreads();
-    const int keep = s_keep < beam ? s_keep : beam;
-    if (tid < keep) {
-        const int f = order[tid];
-        e_src[tid] = c_base[f];
-        e_tok[tid] = c_tok[f];
-        e_blank[tid] = c_tok[f] < 0;
-        e_last[tid] = c_last[f];
-        e_t[tid] = c_t[f];
-        hl2[tid] = c_len[f];
-        S.bscores[(size_t)b * beam + tid] = f_score[f];
-        S.bhash[b * beam + tid] = c_hash[f];
-        S.token[b * beam + tid] = c_last[f];       // the hypothesis' next predictor input: its last token
-    }
+    beam_find_classes<true>(L, c_t, hy, S.Lmax, C, tid);
+    beam_fuse_scores(L, C, tid);
+    const int keep = beam_rank_prune(S, L, hl2, b, C, tid, [](int tok) { return tok < 0; });
+    if (tid < keep) e_t[tid] = c_t[L.order[tid]];
     __syncthreads();
     if (tid == 0) {
         int fn = e_t[0];
         for (int e = 1; e < keep; ++e) fn = e_t[e] < fn ? e_t[e] : fn;
         s_fnext = fn;
     }
-    // phase 5: hypotheses into the other buffer
-    {
-        int maxlb = 0;
-        for (int e = 0; e < keep; ++e) maxlb = e_lb[e_src[e]] > maxlb ? e_lb[e_src[e]] : maxlb;
-        constexpr int UN = 4;
-        for (int i0 = 0; i0 < keep * maxlb; i0 += NT * UN) {
-            int val[UN];
-#pragma unroll
-            for (int u = 0; u < UN; ++u) {
-                const int i = i0 + u * NT + tid;
-                const int e = i / maxlb, q = i - e * maxlb;
-                const bool in = e < keep && q < e_lb[e_src[e < keep ? e : 0]];
-                val[u] = in ? hy[(size_t)e_src[e] * S.Lmax + q] : 0;
-            }
-#pragma unroll
-            for (int u = 0; u < UN; ++u) {
-                const int i = i0 + u * NT + tid;
-                const int e = i / maxlb, q = i - e * maxlb;
-                if (e < keep && q < e_lb[e_src[e]]) hy2[(size_t)e * S.Lmax + q] = val[u];
-            }
-        }
-        if (tid < keep) {
-            const int lb = e_lb[e_src[tid]];
-            if (!e_blank[tid] && lb < S.Lmax) hy2[(size_t)tid * S.Lmax + lb] = e_tok[tid];
-        }
-    }
-    if (d.ptype == kPredLstm) {
-        // slot NUMBERS as in beam_update_kernel: the committed slot of the base for a waiting survivor or a blank arc, the
-        // slot of the base's stepped state for a label (only an expanded base has one); every lane gets a free slot; then
-        // layer 0 of every survivor's next step, whenever that step will be consulted
-        __shared__ int s_comm[kMaxBeam], s_new[kMaxBeam], s_oc[kMaxBeam], s_on[kMaxBeam];
-        if (tid < beam) { s_oc[tid] = S.comm_slot[b * beam + tid]; s_on[tid] = S.new_slot[b * beam + tid]; }
-        __syncthreads();
-        if (tid == 0) {
-            unsigned used = 0;                                   // bit j: slot b*beam + j, bit beam + j: slot NLp + b*beam + j
-            for (int e = 0; e < keep; ++e) {
-                const int sl = e_blank[e] ? s_oc[e_src[e]] : s_on[e_src[e]];
-                s_comm[e] = sl;
-                used |= 1u << (sl >= d.NLp ? beam + (sl - d.NLp - b * beam) : sl - b * beam);
-            }
-            int bit = 0;
-            for (int e = 0; e < beam; ++e) {
-                while (used & (1u << bit)) ++bit;
-                s_new[e] = bit < beam ? b * beam + bit : d.NLp + b * beam + (bit - beam);
-                if (e >= keep) s_comm[e] = s_new[e];
-                ++bit;
-            }
-        }
-        __syncthreads();
-        if (tid < beam) { S.comm_slot[b * beam + tid] = s_comm[tid]; S.new_slot[b * beam + tid] = s_new[tid]; }
-        constexpr int UN = 2;
-        const int items = keep * d.H;
-        for (int i0 = 0; i0 < items; i0 += NT * UN) {
-            float ev[UN][4], gv[UN][4], cv[UN];
-#pragma unroll
-            for (int q = 0; q < UN; ++q) {
-                const int i = i0 + q * NT + tid;
-                const int e = i < items ? i / d.H : 0, u = i < items ? i - e * d.H : 0;
-                const int col = (u >> 3) * 32 + (u & 7);
-                const float *__restrict__ er = S.etab + (size_t)e_last[e] * d.G4p + col;
-                const float *__restrict__ gr = S.pool_g + (size_t)s_comm[e] * d.G4p + col;
-#pragma unroll
-                for (int gt = 0; gt < 4; ++gt) { ev[q][gt] = er[gt * 8]; gv[q][gt] = gr[gt * 8]; }
-                cv[q] = S.pool_c[(size_t)s_comm[e] * d.Hp + u];
-            }
-#pragma unroll
-            for (int q = 0; q < UN; ++q) {
-                const int i = i0 + q * NT + tid;
-                if (i >= items) continue;
-                const int e = i / d.H, u = i - e * d.H;
-                const float ig = sigmoidf_(ev[q][0] + gv[q][0]);
-                const float fg = sigmoidf_(ev[q][1] + gv[q][1]);
-                const float gg = tanhf(ev[q][2] + gv[q][2]);
-                const float og = sigmoidf_(ev[q][3] + gv[q][3]);
-                const float c = fg * cv[q] + ig * gg;
-                S.pool_c[(size_t)s_new[e] * d.Hp + u] = c;
-                S.new_hT[(size_t)u * d.NLp + b * beam + e] = og * tanhf(c);
-            }
-        }
-    } else {
-        // next predictor inputs
-        {
-            constexpr int UN = 4;
-            const float *__restrict__ emb = S.embed;
-            for (int i0 = 0; i0 < keep * d.D; i0 += NT * UN) {
-                float val[UN];
-#pragma unroll
-                for (int u = 0; u < UN; ++u) {
-                    const int i = i0 + u * NT + tid;
-                    const int e = i / d.D, k = i - e * d.D;
-                    val[u] = e < keep ? emb[(size_t)e_last[e] * d.D + k] : 0.f;
-                }
-#pragma unroll
-                for (int u = 0; u < UN; ++u) {
-                    const int i = i0 + u * NT + tid;
-                    const int e = i / d.D, k = i - e * d.D;
-                    if (e < keep) S.xT[(size_t)k * d.NLp + b * beam + e] = val[u];
-                }
-            }
-        }
-        // token histories: the base's committed one for a waiting survivor or a blank arc, the stepped one for a label;
-        // read into registers, synchronised, written back in place (beam_update_kernel)
-        {
-            constexpr int UN = 8;
-            const int rows = d.L * d.Hp, per_it = NT / beam;
-            const int e = tid % beam, r0 = tid / beam;
-            const bool on = e < keep && r0 < per_it;
-            const int src = b * beam + (on ? e_src[e] : 0), dst = b * beam + e;
-            const bool bl = on ? e_blank[e] != 0 : true;
-            const float *hsrc = bl ? S.cache_hT : S.new_hT;
-            const float *csrc = bl ? S.cache_cT : S.new_cT;
-            for (int rb = 0; rb < rows; rb += per_it * UN) {
-                float hv[UN], cw[UN];
-#pragma unroll
-                for (int u = 0; u < UN; ++u) {
-                    const int r = rb + u * per_it + r0;
-                    const size_t so = (size_t)(r < rows ? r : 0) * d.NLp + src;
-                    hv[u] = hsrc[so];
-                    cw[u] = csrc[so];
-                }
-                __syncthreads();
-#pragma unroll
-                for (int u = 0; u < UN; ++u) {
-                    const int r = rb + u * per_it + r0;
-                    if (on && r < rows) {
-                        const size_t dst_o = (size_t)r * d.NLp + dst;
-                        S.cache_hT[dst_o] = hv[u];
-                        S.cache_cT[dst_o] = cw[u];
-                    }
-                }
-            }
-        }
-    }
+    beam_move_hyps(L, hy, hy2, S.Lmax, keep, tid);
+    beam_move_predictor(S, L, b, keep, tid);
     __syncthreads();
     const int fnext = s_fnext;                     // f strictly increases: every arc advances
     if (tid < beam) {
