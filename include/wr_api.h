@@ -1245,6 +1245,74 @@ int wr_prefix_beam_search_tdt(wr_decoder *h, const float *enc_out_d, const int32
                               float transducer_weight, int blank, const int32_t *durations /* [D], host */, int D,
                               int32_t *hyps_d, int32_t *hyp_lens_d, double *scores_d, int32_t *n_hyps_d, void *stream);
 
+/* Streaming transducer prefix beam search: the prefix beam search of a plain or a token-and-duration transducer continued
+ * chunk by chunk, for B streams at once, where every hypothesis carries its summed score, a Viterbi score and the absolute
+ * encoder frame at which each of its tokens was emitted, and the current n-best is exported after every chunk.  This text
+ * is the contract.  Addition only: WR_API_VERSION stays 3.
+ *
+ * Search steps.  Steps 1-7 of "TDT prefix beam search" above apply unchanged; the plain search (durations NULL, D = 0) is
+ * that rule with durations = (1,) and no duration columns, i.e. wr_prefix_beam_search.  Frames t are absolute, counted
+ * from the stream's reset.
+ * Viterbi score and times.  Every entry additionally carries vscore (float64, 0.0 at the seed) and times[], one frame per
+ * token after the seed blank.  A candidate made from an entry with frame t and pair value v has
+ * vscore' = (double)((float)vscore + v), the same fp32 add as the score; its times are the entry's, a label appends t (the
+ * frame it was emitted at, not t'), a blank appends nothing.  A waiting entry keeps both.
+ * Fusion (step 6).  The class's score is accumulated as before.  Its vscore is the maximum over its members; its times are
+ * those of the member holding that maximum, an exact tie going to the first in pool order.  Its tokens, t' and predictor
+ * state stay the representative's (all members agree on them).
+ * Non-final chunks.  A chunk adds lens[b] = min(chunk_lens[b], T) frames to stream b; F_b is the number of frames received
+ * so far.  Steps run while some entry has t < F_b; entries with t >= F_b wait for the next chunk.  In a call not flagged
+ * final nothing is clamped: t' = t + max(d, 1).
+ * Final chunks.  Before its first step a call flagged final for stream b sets T_b = F_b (after adding its frames), clamps
+ * every t > T_b to T_b (a no-op for the plain search), and fuses and stably re-sorts the beam in beam order exactly as a step
+ * does; it then steps with t' = min(..., T_b).  A final call with lens[b] = 0 does only the clamp, fuse and sort.  After it
+ * the stream accepts nothing until it is reset: whatever chunk_lens says, the device leaves it as it is.
+ * Untouched streams.  With lens[b] = 0 and no flag the stream is left untouched.
+ *
+ * Consequences.  One call with reset and final over a whole utterance gives the hyps, lens, scores and n_hyps of
+ * wr_prefix_beam_search (plain) / wr_prefix_beam_search_tdt (durations), bit for bit.  Any chunking of a stream's frames
+ * with the final flag on the chunk that holds its last frame equals the one-chunk call in every output: always for the plain
+ * search, and for a token-and-duration model whenever that final chunk holds at least max(durations) frames of the stream
+ * (or is its first chunk), since then no arc made earlier reaches past the end.  With a shorter final chunk -- a final call
+ * of no frames is the extreme -- an arc made before the end was known may stand beyond T_b until the final call clamps it;
+ * the result is the rule above and may differ from the whole-utterance search, which clamps at once and so fuses before
+ * it prunes.
+ *
+ * State.  wr_decoder_attach_beam_stream gives the handle a caller-owned block (wr_decoder_beam_stream_workspace_bytes) for
+ * max_streams streams of `beam` entries and at most max_frames frames each: the hypotheses, times, lengths, scores and
+ * Viterbi scores, with Lcap = max_frames + 1 slots per hypothesis.  The block must stay alive and untouched while the streams
+ * run; attaching again replaces it and ends every stream.  wr_decoder_create's signature and workspace are as before.  The
+ * predictor state of the entries lives in the handle's lanes: any other search or wr_predictor_step on the handle
+ * overwrites it, after which every stream must be reset before its next chunk.
+ *
+ * The chunk call.  enc_chunk [B, T, E] fp32, chunk_lens [B]; ctc_logp_chunk [B, T, V] as in the whole-utterance searches
+ * (required by the plain search; NULL for a token-and-duration model needs weights (0, 1)); durations[D] HOST, or NULL with
+ * D = 0 for a plain model; flags HOST int32 [B] or NULL (all 0): bit 0 resets the stream first, bit 1 marks the call final.
+ * Out: hyps [B, beam, Lcap] (each begins with the seed blank, padded with -1), times [B, beam, Lcap] (the seed's slot -1,
+ * padding -1), hyp_lens [B, beam], scores and vscores [B, beam] float64 (best first by score), n_hyps [B] -- the current
+ * n-best of every stream, untouched and finished ones included.  wr_decoder_set_graph applies as to the whole-utterance
+ * searches; chunk-dependent values travel in the uploaded state block, never in a captured graph.
+ *
+ * Refused before any HIP call, in this order (WR_EINVAL): the duration checks of wr_greedy_search_tdt (when durations or D
+ * is given); a null enc_chunk / chunk_lens / output pointer; a null handle; no attached stream state; B or beam different
+ * from the attached ones; T outside [1, Tmax]; V = vocab_size - D < 2; an embedding table with fewer than V rows; a missing
+ * posterior (see above); blank outside [0, V); flag bits beyond 3; then per stream: a reset whose chunk exceeds max_frames;
+ * a stream without the reset flag that was never reset, or whose lanes another search has overwritten; a final flag for a
+ * stream that has had its final call; chunk widths T summed since the stream's reset exceeding max_frames (counted on the
+ * host for every running stream, whatever chunk_lens holds); durations or blank different from those a running stream was
+ * started with. */
+size_t wr_decoder_beam_stream_workspace_bytes(const wr_decoder *h, int max_streams, int beam, int max_frames);
+
+int wr_decoder_attach_beam_stream(wr_decoder *h, int max_streams, int beam, int max_frames, void *workspace_d,
+                                  size_t workspace_bytes);
+
+int wr_prefix_beam_search_chunk(wr_decoder *h, const float *enc_chunk_d, const int32_t *chunk_lens_d,
+                                const float *ctc_logp_chunk_d /* [B, T, V] or NULL */, int B, int T, int beam,
+                                float ctc_weight, float transducer_weight, int blank,
+                                const int32_t *durations /* [D], host; NULL with D = 0: plain */, int D,
+                                const int32_t *flags /* [B], host, or NULL */, int32_t *hyps_d, int32_t *times_d,
+                                int32_t *hyp_lens_d, double *scores_d, double *vscores_d, int32_t *n_hyps_d, void *stream);
+
 /* Measurement hook: the three counters the last polling search on this handle read back (host memory, no HIP call).
  * Greedy searches: streams still active, blank decisions, emissions.  wr_prefix_beam_search_tdt: utterances still running
  * (0 after a successful call), steps taken summed over the utterances, hypotheses expanded. */

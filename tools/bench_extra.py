@@ -1358,10 +1358,88 @@ def bench_tdtbeam(args):
                           "best_len": len(out[0][0][0])}), flush=True)
 
 
+def bench_beamstream(args):
+    """Streaming transducer prefix beam search at the shape of `beam` / `tdtbeam` (B = 16, T = 1500, beam 8, LSTM 2x256,
+    J = 512, V = 5000), plain (joiner of width 5000) and token-and-duration (width 5005, durations 0 .. 4), in one run per
+    model: the whole-utterance search, one reset-and-final chunk call over the whole utterance, and the utterance in chunks
+    of --chunk-frames frames (16), with the time per chunk call.  Per line: ms per utterance batch and, for the chunked
+    run, us per chunk."""
+    import time
+    import wenet_celoss_amd as w
+    from wenet_celoss_amd.decoder import DeviceDecoder
+    dev = torch.device("cuda:0")
+    torch.manual_seed(6)
+    D = args.durations
+    V, E, P, J, H, L, beam = 5000, 256, 256, 512, 256, 2, 8
+    B, T = (args.B if args.B != 32 else 16), (args.T if args.T != 1000 else 1500)
+    C = args.chunk_frames
+    pred = w.RNNPredictor(V + D, P, P, 0.1, H, L).to(dev).eval()
+    joint = w.TransducerJoint(V + D, E, P, J).to(dev).eval()
+    with torch.no_grad():
+        joint.ffn_out.weight *= 10
+        joint.ffn_out.bias[0] += 16.0
+    plain_joint = w.TransducerJoint(V, E, P, J).to(dev).eval()
+    plain_joint.load_state_dict({k: (v[:V] if k.startswith("ffn_out.") else v) for k, v in joint.state_dict().items()})
+    ctc = w.CTC(V, E).to(dev).eval()
+    enc = torch.randn(B, T, E, device=dev)
+    lens = torch.full((B,), T, dtype=torch.int32)
+    with torch.no_grad():
+        ctc_logp = ctc.log_softmax(enc)
+    starts = list(range(0, T, C))
+    chunks = [(enc[:, p:p + C].contiguous(), ctc_logp[:, p:p + C].contiguous(),
+               torch.full((B,), min(C, T - p), dtype=torch.int32, device=dev)) for p in starts]
+
+    def timed(fn):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.steps, out
+
+    for name, jn, durations, mix in (("plain", plain_joint, None, (0.3, 0.7)), ("tdt", joint, tuple(range(D)), (0.0, 1.0))):
+        if args.only and name not in args.only.split(","):
+            continue
+        dec = DeviceDecoder(pred, jn, B * beam, B, T, 0, beam)
+        dec.attach_beam_stream(B, beam, T)
+        post = (lambda c: c) if durations is None else (lambda c: None)
+
+        def whole():
+            if durations is None:
+                return dec.prefix_beam(enc, lens, ctc_logp, beam, *mix, 0)
+            return dec.prefix_beam_tdt(enc, lens, durations, beam, 0)
+
+        def one_chunk():
+            return dec.prefix_beam_chunk(enc, lens, beam, 0, ctc_logp=post(ctc_logp), ctc_weight=mix[0], transducer_weight=mix[1],
+                                         durations=durations, reset=True, final=True)
+
+        def chunked():
+            out = None
+            for i, (e, c, n) in enumerate(chunks):
+                out = dec.prefix_beam_chunk(e, n, beam, 0, ctc_logp=post(c), ctc_weight=mix[0], transducer_weight=mix[1],
+                                            durations=durations, reset=i == 0, final=i == len(chunks) - 1)
+            return out
+
+        t_whole, out_w = timed(whole)
+        t_one, out_1 = timed(one_chunk)
+        t_chunked, out_c = timed(chunked)
+        base = {"model": name, "durations": durations, "B": B, "T": T, "beam": beam}
+        print(json.dumps({"what": "whole-utterance search", **base, "ms_per_call": round(t_whole * 1e3, 2)}), flush=True)
+        print(json.dumps({"what": "prefix_beam_search_chunk, one reset-and-final call", **base,
+                          "ms_per_call": round(t_one * 1e3, 2), "over_whole": round(t_one / t_whole, 3),
+                          "equals_whole": [[(h, s) for h, s, _, _ in u] for u in out_1] == out_w}), flush=True)
+        print(json.dumps({"what": "prefix_beam_search_chunk, chunked", **base, "chunk_frames": C, "chunks": len(chunks),
+                          "ms_per_utterance": round(t_chunked * 1e3, 2), "us_per_chunk": round(t_chunked * 1e6 / len(chunks), 1),
+                          "over_one_chunk": round(t_chunked / t_one, 3), "over_whole": round(t_chunked / t_whole, 3),
+                          "equals_one_chunk": out_c == out_1}), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align", "simple", "smoothed", "pruned", "tdt",
-                                     "tdtstep", "tdtalign", "tdtdec", "tdtbeam", "ctcstream", "ctcctx"])
+                                     "tdtstep", "tdtalign", "tdtdec", "tdtbeam", "ctcstream", "ctcctx", "beamstream"])
+    ap.add_argument("--chunk-frames", type=int, default=16, help="beamstream: encoder frames per chunk")
     ap.add_argument("--durations", type=int, default=5, help="tdt, tdtstep, tdtalign: number of durations D (the set is 0 .. D-1)")
     ap.add_argument("--n-steps", type=int, default=64)
     ap.add_argument("--chunks", type=int, default=4)
@@ -1400,4 +1478,4 @@ if __name__ == "__main__":
     {"joint": bench_joint, "ctc": bench_ctc, "greedy": bench_greedy, "beam": bench_beam, "step": bench_step, "ctcdec": bench_ctcdec, "hotword": bench_hotword,
      "align": bench_align, "simple": bench_simple, "smoothed": bench_smoothed, "pruned": bench_pruned,
      "tdt": bench_tdt, "tdtstep": bench_tdtstep, "tdtalign": bench_tdtalign, "tdtdec": bench_tdtdec,
-     "tdtbeam": bench_tdtbeam, "ctcstream": bench_ctcstream, "ctcctx": bench_ctcctx}[a.what](a)
+     "tdtbeam": bench_tdtbeam, "ctcstream": bench_ctcstream, "ctcctx": bench_ctcctx, "beamstream": bench_beamstream}[a.what](a)

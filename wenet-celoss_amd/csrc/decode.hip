@@ -39,9 +39,14 @@
 //                           others wait; equal tokens at an equal frame fuse
 //                           What a twin does as the plain kernel does exists once: topk_row_max / _log_sum / _mix_select,
 //                           topk_merge, the beam_* phases over one BeamUpdLds, ResolveLane (both look-ahead resolve kernels)
+//   beam_chunk_begin_kernel /   the streaming form of both beam searches (wr_prefix_beam_search_chunk): the update kernels'
+//   beam_stream_export_kernel   <TIMES> instantiations carry a Viterbi score and the frame of every token, the begin kernel
+//                           continues each stream from the state its previous chunk left (and clamps, fuses and re-sorts
+//                           for a final call), the export kernel writes the n-best with times after every chunk
 //
 // Micro-steps are replayed from a hipGraph (captured once per decoder handle) so
 // the host only checks a "lanes still active" word every 16 steps.
+#include "decode_stream.hpp"
 #include "decode_tdt.hpp"
 #include "wr_common.hpp"
 #include "wr_launch.hpp"
@@ -176,6 +181,14 @@ struct DevState {
     unsigned long long tdt_durs;  // durations[j] in bits [4j, 4j + 4)
     int tdt_D;                    // the logits row is V - tdt_D token columns followed by tdt_D duration columns
     int32_t *hyp_frames;          // [NL, max_hyp] frame of each emission, or null
+    // streaming prefix beam search (wr_prefix_beam_search_chunk): the block wr_decoder_attach_beam_stream was given, which
+    // also holds bhyps / bhyp_lens / bscores while a chunk call runs; null in every other search.  lane_t and frame[] count
+    // from the first frame of the stream's latest chunk, bs_base[b] is that frame's absolute number
+    int32_t *btimes;              // [2, n_utt, beam, Lmax]  frame of each token of a hypothesis (slot 0, the seed: -1)
+    double *bvscores;             // [n_utt, beam]           Viterbi score
+    int32_t *bs_base, *bs_F;      // [n_utt] absolute frame of the latest chunk's first frame / frames received (F_b)
+    int32_t *bs_state;            // [n_utt] bit 1: the stream has had its final call
+    const int32_t *bs_flags;      // [n_utt] this call: bit 0 reset the stream first, bit 1 final
 };
 
 struct GemmArgs {
@@ -1744,6 +1757,7 @@ __global__ void beam_init_kernel(DevState *s)
     const Dims &d = s->d;
     const int n = blockIdx.x, tid = threadIdx.x;
     const int b = n / s->beam, j = n % s->beam;
+    if (s->bs_flags && !(s->bs_flags[b] & 1)) return;      // a chunk call starts only the streams it resets
     for (int i = tid; i < d.L * d.Hp; i += blockDim.x) {
         const size_t o = (size_t)i * d.NLp + n;
         s->cache_hT[o] = 0.f; s->cache_cT[o] = 0.f;
@@ -1938,6 +1952,11 @@ struct BeamUpdLds {
     unsigned long long c_hash[MC];
     int c_base[MC], c_tok[MC], c_len[MC], c_last[MC], c_rep[MC], c_rank[MC], order[kMaxBeam];
     int e_src[kMaxBeam], e_blank[kMaxBeam], e_tok[kMaxBeam], e_last[kMaxBeam], e_lb[kMaxBeam];
+    // TIMES (the streaming search) only: a candidate's Viterbi score -- after beam_fuse_scores a representative's is its
+    // class's maximum and c_vbest the member that holds it -- and, per survivor, that member's base hypothesis (whose times
+    // it takes) and whether the member appended a token
+    double c_vscore[MC];
+    int c_vbest[MC], e_vsrc[kMaxBeam], e_vapp[kMaxBeam];
 };
 
 // phase 2: class representative = the first candidate with the same token sequence (:130-142) -- and, WITH_FRAME, the same
@@ -1976,19 +1995,32 @@ __device__ __forceinline__ void beam_find_classes(BeamUpdLds &L, const int *c_t,
 // candidates sit in different waves, so that the few duplicates of a frame are summed side by side)
 // Most frames have no duplicate at all: then the fused scores are the candidates' own (one count over the workgroup
 // instead of every candidate scanning all later ones).
+// TIMES: beside the sum, the class's Viterbi score -- the maximum of its members' c_vscore, an exact tie to the first in
+// pool order -- and the member holding it (c_vbest); only a representative's own c_vscore is rewritten, which no other
+// thread reads.
+template <bool TIMES>
 __device__ __forceinline__ void beam_fuse_scores(BeamUpdLds &L, int C, int tid)
 {
     const int n_dup = __syncthreads_count(tid < C && L.c_rep[tid] != tid);
     if (n_dup == 0) {
-        if (tid < C) L.f_score[tid] = L.c_score[tid];
+        if (tid < C) {
+            L.f_score[tid] = L.c_score[tid];
+            if (TIMES) L.c_vbest[tid] = tid;
+        }
     } else {
         const int c = (tid & 63) * (kBeamUpdThreads / 64) + (tid >> 6);
         if (c < C) {
             double sc = L.c_score[c];
+            double vb = TIMES ? L.c_vscore[c] : 0.0;
+            int vi = c;
             if (L.c_rep[c] == c) {
 #pragma unroll 8
                 for (int f = c + 1; f < C; ++f)
-                    if (L.c_rep[f] == c) sc = log_add2(sc, L.c_score[f]);
+                    if (L.c_rep[f] == c) {
+                        sc = log_add2(sc, L.c_score[f]);
+                        if (TIMES && L.c_vscore[f] > vb) { vb = L.c_vscore[f]; vi = f; }
+                    }
+                if (TIMES) { L.c_vscore[c] = vb; L.c_vbest[c] = vi; }
             }
             L.f_score[c] = sc;
         }
@@ -2000,7 +2032,8 @@ __device__ __forceinline__ void beam_fuse_scores(BeamUpdLds &L, int C, int tid)
 // to `beam`, and the survivors' record: e_* in LDS, length / score / hash / next predictor input of lane b * beam + rank.
 // not_appended(c_tok) says whether a candidate added no token to its base.  Returns the survivor count; the caller
 // synchronises before anyone reads e_*.  Called once per kernel: the count lives in s_keep, zeroed here behind the barrier.
-template <typename F>
+// TIMES: also the survivor's Viterbi score, and whose times it takes (e_vsrc, e_vapp).
+template <bool TIMES, typename F>
 __device__ __forceinline__ int beam_rank_prune(const DevState &S, BeamUpdLds &L, int32_t *__restrict__ hl2, int b, int C, int tid, F &&not_appended)
 {
     __shared__ int s_keep;
@@ -2029,12 +2062,22 @@ __device__ __forceinline__ int beam_rank_prune(const DevState &S, BeamUpdLds &L,
         S.bscores[(size_t)b * beam + tid] = L.f_score[f];
         S.bhash[b * beam + tid] = L.c_hash[f];
         S.token[b * beam + tid] = L.c_last[f];     // next frame's predictor input: last token of the hypothesis (:78-80)
+        if (TIMES) {
+            const int vb = L.c_vbest[f];
+            L.e_vsrc[tid] = L.c_base[vb];
+            L.e_vapp[tid] = !not_appended(L.c_tok[vb]);
+            S.bvscores[(size_t)b * beam + tid] = L.c_vscore[f];
+        }
     }
     return keep;
 }
 
-// phase 5: the pruned beam -- hypotheses into the other buffer, (survivor, position) pairs in flight together
-__device__ __forceinline__ void beam_move_hyps(const BeamUpdLds &L, const int32_t *__restrict__ hy, int32_t *__restrict__ hy2, int Lmax, int keep, int tid)
+// phase 5: the pruned beam -- hypotheses into the other buffer, (survivor, position) pairs in flight together.
+// TIMES: and each survivor's times (tm -> tm2, laid out like the hypotheses) from the base of its class's Viterbi-best
+// member, which need not be e_src; a member that appended a token appends `frame`, the frame it was expanded at.
+template <bool TIMES>
+__device__ __forceinline__ void beam_move_hyps(const BeamUpdLds &L, const int32_t *__restrict__ hy, int32_t *__restrict__ hy2, int Lmax, int keep, int tid,
+                                               const int32_t *__restrict__ tm = nullptr, int32_t *__restrict__ tm2 = nullptr, int frame = 0)
 {
     constexpr int NT = kBeamUpdThreads;
     int maxlb = 0;
@@ -2059,6 +2102,18 @@ __device__ __forceinline__ void beam_move_hyps(const BeamUpdLds &L, const int32_
     if (tid < keep) {
         const int lb = L.e_lb[L.e_src[tid]];
         if (!L.e_blank[tid] && lb < Lmax) hy2[(size_t)tid * Lmax + lb] = L.e_tok[tid];
+    }
+    if (TIMES) {
+        int maxlv = 0;
+        for (int e = 0; e < keep; ++e) maxlv = L.e_lb[L.e_vsrc[e]] > maxlv ? L.e_lb[L.e_vsrc[e]] : maxlv;
+        for (int i = tid; i < keep * maxlv; i += NT) {
+            const int e = i / maxlv, q = i - e * maxlv;
+            if (q < L.e_lb[L.e_vsrc[e]]) tm2[(size_t)e * Lmax + q] = tm[(size_t)L.e_vsrc[e] * Lmax + q];
+        }
+        if (tid < keep) {
+            const int lv = L.e_lb[L.e_vsrc[tid]];
+            if (L.e_vapp[tid] && lv < Lmax) tm2[(size_t)tid * Lmax + lv] = frame;
+        }
     }
 }
 
@@ -2181,6 +2236,9 @@ __device__ __forceinline__ void beam_move_predictor(const DevState &S, const Bea
     }
 }
 
+// TIMES: the streaming form (wr_prefix_beam_search_chunk).  The frames of this chunk are T_b = F_b - base_b, frame[b] counts
+// from the chunk's first frame, and every candidate carries a Viterbi score and its class the times of its best member.
+template <bool TIMES>
 __global__ __launch_bounds__(kBeamUpdThreads) void beam_update_kernel(DevState *sp)
 {
     __shared__ BeamUpdLds L;
@@ -2190,7 +2248,7 @@ __global__ __launch_bounds__(kBeamUpdThreads) void beam_update_kernel(DevState *
     const DevState S = *sp;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int beam = S.beam;
-    const int T = S.enc_lens[b] < S.T ? S.enc_lens[b] : S.T;
+    const int T = TIMES ? S.bs_F[b] - S.bs_base[b] : (S.enc_lens[b] < S.T ? S.enc_lens[b] : S.T);
     const int fr = S.frame[b];
     if (fr >= T) return;
     const int N = S.n_hyps[b], C = N * beam;
@@ -2213,6 +2271,7 @@ __global__ __launch_bounds__(kBeamUpdThreads) void beam_update_kernel(DevState *
         const int last = S.token[n];               // last token of hypothesis j (this frame's predictor input)
         const unsigned long long hh = S.bhash[n];
         L.c_score[tid] = (double)(sj + tv);
+        if (TIMES) L.c_vscore[tid] = (double)((float)S.bvscores[(size_t)b * beam + j] + tv);
         L.c_base[tid] = j;
         L.c_tok[tid] = tok;
         L.c_len[tid] = lb + (tok != S.blank ? 1 : 0);
@@ -2225,12 +2284,16 @@ __global__ __launch_bounds__(kBeamUpdThreads) void beam_update_kernel(DevState *
     WR_STAMP(1);                                   // candidates built
     beam_find_classes<false>(L, nullptr, hy, S.Lmax, C, tid);
     WR_STAMP(2);                                   // classes known
-    beam_fuse_scores(L, C, tid);
+    beam_fuse_scores<TIMES>(L, C, tid);
     WR_STAMP(9);                                   // duplicates' scores summed
-    const int keep = beam_rank_prune(S, L, hl2, b, C, tid, [&](int tok) { return tok == S.blank; });
+    const int keep = beam_rank_prune<TIMES>(S, L, hl2, b, C, tid, [&](int tok) { return tok == S.blank; });
     __syncthreads();
     WR_STAMP(3);                                   // fused, ranked, pruned
-    beam_move_hyps(L, hy, hy2, S.Lmax, keep, tid);
+    if (TIMES)
+        beam_move_hyps<true>(L, hy, hy2, S.Lmax, keep, tid, S.btimes + sel * hstride + (size_t)b * beam * S.Lmax,
+                             S.btimes + (1 - sel) * hstride + (size_t)b * beam * S.Lmax, S.bs_base[b] + fr);
+    else
+        beam_move_hyps<false>(L, hy, hy2, S.Lmax, keep, tid);
     WR_STAMP(4);                                   // hypotheses moved
     beam_move_predictor(S, L, b, keep, tid);
     if (tid < beam) {
@@ -2364,16 +2427,22 @@ __global__ __launch_bounds__(kTopkThreads) void tdt_beam_topk_kernel(DevState *s
 // represents the class and accumulates it in pool order (float64 log_add), stable prune, the survivors moved by
 // beam_move_hyps / beam_move_predictor (a waiting survivor and a blank extension inherit the committed predictor state, a
 // label the stepped one) -- then each survivor's frame, and which of them stand at the new earliest frame.
-__global__ __launch_bounds__(kBeamUpdThreads) void tdt_beam_update_kernel(DevState *sp)
+// MODE kTdtWhole: a step of wr_prefix_beam_search_tdt.  The streaming search (include/wr_api.h, "Streaming transducer prefix
+// beam search"; frames count from the chunk's first, T = F_b - base_b, Viterbi scores and times are carried):
+// kTdtStream, a step -- arcs are clamped to T only once the stream has had its final call; kTdtFinal, what a final call does
+// before its first step -- nothing is expanded, every frame beyond T is clamped to T, and the beam is fused and re-sorted.
+enum TdtUpdateMode { kTdtWhole = 0, kTdtStream = 1, kTdtFinal = 2 };
+template <int MODE>
+__device__ __forceinline__ void tdt_beam_update(const DevState &S, BeamUpdLds &L, int b)
 {
-    __shared__ BeamUpdLds L;
+    constexpr bool TIMES = MODE != kTdtWhole;
     __shared__ int c_t[BeamUpdLds::MC], e_t[kMaxBeam], p_t[kMaxBeam], p_off[kMaxBeam + 1], s_nact, s_fnext;
-    const DevState S = *sp;
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     const int beam = S.beam;
-    const int T = S.enc_lens[b] < S.T ? S.enc_lens[b] : S.T;
+    const int T = TIMES ? S.bs_F[b] - S.bs_base[b] : (S.enc_lens[b] < S.T ? S.enc_lens[b] : S.T);
+    const bool clamp = !TIMES || (S.bs_state[b] & 2);
     const int fr = S.frame[b];                     // the earliest frame of the beam
-    if (fr >= T) return;                           // every hypothesis has reached T_b
+    if (MODE != kTdtFinal && fr >= T) return;      // every hypothesis has reached T_b
     const int N = S.n_hyps[b];
     const int sel = S.hyp_sel[b];
     const size_t hstride = (size_t)S.n_utt * beam * S.Lmax;
@@ -2392,8 +2461,9 @@ __global__ __launch_bounds__(kBeamUpdThreads) void tdt_beam_update_kernel(DevSta
         for (int e = 0; e < N; ++e) {
             const int t = p_t[e];
             p_off[e] = off;
-            off += t == fr ? beam : 1;
-            na += t == fr ? 1 : 0;
+            const bool expand = MODE != kTdtFinal && t == fr;
+            off += expand ? beam : 1;
+            na += expand ? 1 : 0;
         }
         p_off[N] = off;
         s_nact = na;
@@ -2411,17 +2481,21 @@ __global__ __launch_bounds__(kBeamUpdThreads) void tdt_beam_update_kernel(DevSta
         const unsigned long long hh = S.bhash[n];
         const double se = S.bscores[(size_t)b * beam + e];
         int tok = -1, tn = te;                     // tok < 0: nothing appended (a waiting hypothesis or a blank arc)
-        double sc = se;
-        if (te == fr) {
+        double sc = se, vs = TIMES ? S.bvscores[(size_t)b * beam + e] : 0.0;
+        if (MODE != kTdtFinal && te == fr) {
             const int pair = S.topi[(size_t)n * beam + r];
             const int k = pair & 0xffff;
             const int dur = (int)((S.tdt_durs >> (4 * (pair >> 16))) & 15);
-            sc = (double)((float)se + S.topv[(size_t)n * beam + r]);   // the reference's fp32 add of a float-cast score
+            const float v = S.topv[(size_t)n * beam + r];
+            sc = (double)((float)se + v);          // the reference's fp32 add of a float-cast score
+            if (TIMES) vs = (double)((float)vs + v);
             tn = te + (dur > 1 ? dur : 1);
-            tn = tn < T ? tn : T;
+            if (clamp) tn = tn < T ? tn : T;
             if (k != S.blank) tok = k;
         }
+        if (MODE == kTdtFinal) tn = tn < T ? tn : T;
         L.c_score[tid] = sc;
+        if (TIMES) L.c_vscore[tid] = vs;
         L.c_base[tid] = e;
         L.c_tok[tid] = tok;
         c_t[tid] = tn;
@@ -2433,8 +2507,8 @@ __global__ __launch_bounds__(kBeamUpdThreads) void tdt_beam_update_kernel(DevSta
     }
     __syncthreads();
     beam_find_classes<true>(L, c_t, hy, S.Lmax, C, tid);
-    beam_fuse_scores(L, C, tid);
-    const int keep = beam_rank_prune(S, L, hl2, b, C, tid, [](int tok) { return tok < 0; });
+    beam_fuse_scores<TIMES>(L, C, tid);
+    const int keep = beam_rank_prune<TIMES>(S, L, hl2, b, C, tid, [](int tok) { return tok < 0; });
     if (tid < keep) e_t[tid] = c_t[L.order[tid]];
     __syncthreads();
     if (tid == 0) {
@@ -2442,7 +2516,11 @@ __global__ __launch_bounds__(kBeamUpdThreads) void tdt_beam_update_kernel(DevSta
         for (int e = 1; e < keep; ++e) fn = e_t[e] < fn ? e_t[e] : fn;
         s_fnext = fn;
     }
-    beam_move_hyps(L, hy, hy2, S.Lmax, keep, tid);
+    if (TIMES)
+        beam_move_hyps<true>(L, hy, hy2, S.Lmax, keep, tid, S.btimes + sel * hstride + (size_t)b * beam * S.Lmax,
+                             S.btimes + (1 - sel) * hstride + (size_t)b * beam * S.Lmax, S.bs_base[b] + fr);
+    else
+        beam_move_hyps<false>(L, hy, hy2, S.Lmax, keep, tid);
     beam_move_predictor(S, L, b, keep, tid);
     __syncthreads();
     const int fnext = s_fnext;                     // f strictly increases: every arc advances
@@ -2456,11 +2534,68 @@ __global__ __launch_bounds__(kBeamUpdThreads) void tdt_beam_update_kernel(DevSta
             S.n_hyps[b] = keep;
             S.frame[b] = fnext;
             S.hyp_sel[b] = 1 - sel;
-            atomicAdd(S.active_count + 1, 1);
-            atomicAdd(S.active_count + 2, s_nact);
-            if (fnext >= T) atomicSub(S.active_count, 1);
+            if (MODE == kTdtFinal) {               // the call's begin: the utterance is counted here if it has a frame to decode
+                if (fnext < T) atomicAdd(S.active_count, 1);
+            } else {
+                atomicAdd(S.active_count + 1, 1);
+                atomicAdd(S.active_count + 2, s_nact);
+                if (fnext >= T) atomicSub(S.active_count, 1);
+            }
         }
     }
+}
+
+template <bool TIMES>
+__global__ __launch_bounds__(kBeamUpdThreads) void tdt_beam_update_kernel(DevState *sp)
+{
+    __shared__ BeamUpdLds L;
+    const DevState S = *sp;
+    tdt_beam_update<TIMES ? kTdtStream : kTdtWhole>(S, L, blockIdx.x);
+}
+
+// The begin of a chunk call (wr_prefix_beam_search_chunk), one workgroup per stream, after beam_init_kernel has started the
+// streams the call resets.  A stream that has had its final call, or gets no frame and no flag, is left as it is.  Otherwise:
+// the chunk's lens[b] frames are added (base_b = the old F_b, F_b += lens[b]) and the entries' frames, which count from the
+// chunk's first frame, are moved to the new base; a reset starts the seed's Viterbi score and times slot; a final call of a
+// token-and-duration stream clamps, fuses and re-sorts (tdt_beam_update<kTdtFinal>); then the lanes at the earliest frame
+// that have a frame of the chunk to decode are active, and active_count[0] counts the streams with such a lane.
+template <bool TDT>
+__global__ __launch_bounds__(kBeamUpdThreads) void beam_chunk_begin_kernel(DevState *sp)
+{
+    __shared__ BeamUpdLds L;
+    const DevState S = *sp;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int beam = S.beam;
+    const int flags = S.bs_flags[b];
+    const bool reset = flags & 1;
+    int len = S.enc_lens[b];
+    len = len > 0 ? len : 0;
+    len = len < S.T ? len : S.T;
+    if (!reset && ((S.bs_state[b] & 2) || (flags == 0 && len == 0))) return;
+    const int F0 = reset ? 0 : S.bs_F[b];
+    const int shift = reset ? 0 : F0 - S.bs_base[b];      // the frames of the stream's previous chunk
+    const int fr = S.frame[b] - shift;
+    const int N = S.n_hyps[b];
+    const int lt = tid < beam ? S.lane_t[b * beam + tid] - shift : 0;
+    __syncthreads();                               // everything above is read before anything below is written
+    if (tid < beam) S.lane_t[b * beam + tid] = lt;
+    if (tid == 0) {
+        S.bs_base[b] = F0;
+        S.bs_F[b] = F0 + len;
+        S.bs_state[b] = flags & 2;
+        S.frame[b] = fr;
+        if (reset) {                               // beam_init_kernel left the seed in buffer 0
+            S.bvscores[(size_t)b * beam] = 0.0;
+            S.btimes[(size_t)b * beam * S.Lmax] = -1;
+        }
+    }
+    if (TDT && (flags & 2)) {
+        __syncthreads();                           // the state written above is read through global memory
+        tdt_beam_update<kTdtFinal>(S, L, b);
+        return;
+    }
+    if (tid < beam) S.lane_active[b * beam + tid] = tid < N && lt == fr && lt < len;
+    if (tid == 0 && fr < len) atomicAdd(S.active_count, 1);
 }
 
 __global__ void beam_export_kernel(DevState *s, int32_t *hyps_out, int32_t *lens_out, double *scores_out, int32_t *n_out)
@@ -2483,6 +2618,33 @@ __global__ void beam_export_kernel(DevState *s, int32_t *hyps_out, int32_t *lens
     if (tid == 0) n_out[b] = N;
 }
 
+// the same for the streaming search, with each hypothesis' times (absolute frames; the seed's slot and the padding -1) and
+// Viterbi score
+__global__ void beam_stream_export_kernel(DevState *s, int32_t *hyps_out, int32_t *times_out, int32_t *lens_out, double *scores_out,
+                                          double *vscores_out, int32_t *n_out)
+{
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int beam = s->beam;
+    const int sel = s->hyp_sel[b];
+    const size_t hstride = (size_t)s->n_utt * beam * s->Lmax;
+    const int32_t *hy = s->bhyps + sel * hstride + (size_t)b * beam * s->Lmax;
+    const int32_t *tm = s->btimes + sel * hstride + (size_t)b * beam * s->Lmax;
+    const int32_t *hl = s->bhyp_lens + (size_t)sel * s->n_utt * beam + (size_t)b * beam;
+    const int N = s->n_hyps[b];
+    for (int i = tid; i < beam * s->Lmax; i += blockDim.x) {
+        const int e = i / s->Lmax, q = i % s->Lmax;
+        const bool in = e < N && q < hl[e];
+        hyps_out[((size_t)b * beam + e) * s->Lmax + q] = in ? hy[(size_t)e * s->Lmax + q] : -1;
+        times_out[((size_t)b * beam + e) * s->Lmax + q] = in ? tm[(size_t)e * s->Lmax + q] : -1;
+    }
+    if (tid < beam) {
+        lens_out[(size_t)b * beam + tid] = (tid < N) ? hl[tid] : 0;
+        scores_out[(size_t)b * beam + tid] = (tid < N) ? s->bscores[(size_t)b * beam + tid] : -__builtin_huge_val();
+        vscores_out[(size_t)b * beam + tid] = (tid < N) ? s->bvscores[(size_t)b * beam + tid] : -__builtin_huge_val();
+    }
+    if (tid == 0) n_out[b] = N;
+}
+
 }  // namespace
 }  // namespace wr
 
@@ -2493,6 +2655,24 @@ using namespace wr;
 struct GraphSlot {
     hipGraphExec_t exec = nullptr;
     int key = -1;
+};
+
+// The streams of wr_prefix_beam_search_chunk: the caller's block, and what the host knows of each stream.  The lanes'
+// predictor state lives in the handle's workspace, so the streams are live only while wr_decoder::stream_lanes says so
+// (kBeamStreamLanes: the last search on the handle was a chunk call).
+constexpr int kBeamStreamLanes = -2;
+struct BeamStreams {
+    bool attached = false;
+    int n = 0, beam = 0, max_frames = 0;
+    int32_t *bhyps = nullptr, *btimes = nullptr, *bhyp_lens = nullptr, *base = nullptr, *F = nullptr, *state = nullptr,
+            *flags = nullptr;                      // device, carved from the caller's block
+    double *bscores = nullptr, *bvscores = nullptr;
+    int32_t *h_flags = nullptr;   // pinned, [kStageSlots][n]: the flags of a call on their way to `flags`
+    std::vector<int> phase;       // per stream: 0 never reset (or overwritten by another search), 1 running, 2 had its final call
+    std::vector<long> frames;     // per stream: chunk widths summed since its reset
+    bool overwritten = false;     // the streams were live when another search took the lanes (for the refusal's text)
+    int blank = 0, D = 0;         // what the running streams are searched with
+    unsigned long long durs = 0;
 };
 
 struct wr_decoder {
@@ -2522,6 +2702,9 @@ struct wr_decoder {
     float *hw_ep2 = nullptr;      // [2][max_utt * Tmax * J] enc_ffn of the empty-list (0) / hot-word (1) encoder stream
     int32_t *hw_state = nullptr;  // cur_gate | gb_flag | gb_end | last_t, NLp each
     float *hw_biasT = nullptr;    // [Pp][NLp]
+    // streaming prefix beam search (wr_decoder_attach_beam_stream)
+    GraphSlot beam_stream, beam_tdt_stream;   // the streaming forms of `beam` / `beam_tdt`, keyed likewise
+    BeamStreams bs;
     bool use_graph = true;        // greedy micro-steps replayed from a hipGraph (default on)
     bool use_graph_beam = false;  // beam frames: plain launches measured faster (no host polling to amortise), default off
 };
@@ -2535,6 +2718,8 @@ void for_each_graph(wr_decoder *h, F f)
     for (GraphSlot &g : h->greedy_tdt) f(g);
     f(h->beam);
     f(h->beam_tdt);
+    f(h->beam_stream);
+    f(h->beam_tdt_stream);
     f(h->hotword);
 }
 
@@ -2936,6 +3121,7 @@ extern "C" int wr_decoder_destroy(wr_decoder *h)
     if (h->work) (void)hipStreamSynchronize(h->work);
     if (h->h_active) (void)hipHostFree(h->h_active);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
+    if (h->bs.h_flags) (void)hipHostFree(h->bs.h_flags);
     for (hipEvent_t ev : h->stage_ev) if (ev) (void)hipEventDestroy(ev);
     if (h->ev_in) (void)hipEventDestroy(h->ev_in);
     if (h->ev_out) (void)hipEventDestroy(h->ev_out);
@@ -3024,7 +3210,8 @@ int tdt_micro_step(wr_decoder *h, int n_lanes, hipStream_t st, int look)
     return launch("tdt_resolve_kernel", tdt_resolve_kernel, dim3(n_lanes), dim3(256), 0, st, h->dev, look);
 }
 
-int beam_frame(wr_decoder *h, int n_lanes, int n_utt, hipStream_t st)
+// `times`: the streaming forms of the update kernels (wr_prefix_beam_search_chunk)
+int beam_frame(wr_decoder *h, int n_lanes, int n_utt, hipStream_t st, bool times = false)
 {
     WR_TRY(launch_predictor_and_joint(h, n_lanes, st));
     const int V = h->d.V;                           // <= 16384 (check_weights)
@@ -3032,11 +3219,12 @@ int beam_frame(wr_decoder *h, int n_lanes, int n_utt, hipStream_t st)
     WR_TRY(with_int<4, 10, 32>(per_thread, [&](auto n) {
         return launch("beam_topk_kernel", beam_topk_kernel<decltype(n)::value>, dim3(n_lanes), dim3(kTopkThreads), 0, st, h->dev);
     }));
-    return launch("beam_update_kernel", beam_update_kernel, dim3(n_utt), dim3(kBeamUpdThreads), 0, st, h->dev);
+    if (times) return launch("beam_update_kernel", beam_update_kernel<true>, dim3(n_utt), dim3(kBeamUpdThreads), 0, st, h->dev);
+    return launch("beam_update_kernel", beam_update_kernel<false>, dim3(n_utt), dim3(kBeamUpdThreads), 0, st, h->dev);
 }
 
 // one step of the token-and-duration beam search: the lane GEMMs take each lane's frame from lane_t, as in the greedy search
-int tdt_beam_step(wr_decoder *h, int n_lanes, int n_utt, hipStream_t st)
+int tdt_beam_step(wr_decoder *h, int n_lanes, int n_utt, hipStream_t st, bool times = false)
 {
     WR_TRY(launch_predictor_and_joint(h, n_lanes, st));
     const int V = h->d.V;                           // <= 16384 (check_weights)
@@ -3045,7 +3233,9 @@ int tdt_beam_step(wr_decoder *h, int n_lanes, int n_utt, hipStream_t st)
         return launch("tdt_beam_topk_kernel", tdt_beam_topk_kernel<decltype(n)::value>, dim3(n_lanes), dim3(kTopkThreads), 0, st,
                       h->dev);
     }));
-    return launch("tdt_beam_update_kernel", tdt_beam_update_kernel, dim3(n_utt), dim3(kBeamUpdThreads), 0, st, h->dev);
+    if (times)
+        return launch("tdt_beam_update_kernel", tdt_beam_update_kernel<true>, dim3(n_utt), dim3(kBeamUpdThreads), 0, st, h->dev);
+    return launch("tdt_beam_update_kernel", tdt_beam_update_kernel<false>, dim3(n_utt), dim3(kBeamUpdThreads), 0, st, h->dev);
 }
 
 // Order the decoder's work stream after everything already enqueued on the caller's stream ...
@@ -3150,6 +3340,33 @@ unsigned long long pack_durations(const TdtDur &dur)
     for (int d = 0; d < kTdtMaxD; ++d)
         if (dur.slot[d] >= 0) durs |= (unsigned long long)d << (4 * dur.slot[d]);
     return durs;
+}
+
+// The steps of the plain prefix beam searches (`what` names the entry point in the error texts; `times`: the streaming
+// form): the fixed count of T frames, kStepsPerGraph at a time, replayed from a graph if the handle says so.
+int beam_plain_steps(wr_decoder *h, hipStream_t st, const char *what, int NLn, int B, int T, int beam, bool times)
+{
+    GraphSlot &slot = times ? h->beam_stream : h->beam;
+    const auto frame = [&] { return beam_frame(h, NLn, B, st, times); };
+    if (h->use_graph_beam) WR_TRY(ensure_graph(slot, NLn * 1000 + beam, st, frame));
+    for (int f = 0; f < T; f += kStepsPerGraph) {
+        if (h->use_graph_beam) {
+            hipError_t e = hipGraphLaunch(slot.exec, st);
+            if (e != hipSuccess) { set_error("%s: hipGraphLaunch failed: %s", what, hipGetErrorString(e)); return WR_ELAUNCH; }
+        } else {
+            for (int i = 0; i < kStepsPerGraph; ++i) WR_TRY(frame());
+        }
+    }
+    return WR_OK;
+}
+
+// The steps of the token-and-duration prefix beam searches: until no utterance has an entry below its frame count.  Every
+// step moves the earliest frame of every running utterance on, so T steps always suffice.
+int beam_tdt_steps(wr_decoder *h, hipStream_t st, const char *what, int NLn, int B, int T, int beam, bool times)
+{
+    return run_until_idle(
+        h, st, what, NLn * 1000 + beam, (long)T + 1, "", [&]() -> GraphSlot & { return times ? h->beam_tdt_stream : h->beam_tdt; },
+        [&] { return tdt_beam_step(h, NLn, B, st, times); }, [] {});
 }
 
 // what a token-and-duration search adds to a greedy run
@@ -3260,10 +3477,7 @@ int wr::beam_tdt_body(wr_decoder *h, const float *enc_out_d, const int32_t *enc_
     WR_TRY(launch_ep_all(h, st, (long)B * T, enc_out_d, s.ep_all));
     WR_TRY(launch("beam_init_kernel", beam_init_kernel, dim3(NLn), dim3(128), 0, st, h->dev));
     WR_TRY(launch("tdt_beam_begin_kernel", tdt_beam_begin_kernel, dim3(1), dim3(256), 0, st, h->dev));
-    // every step moves the earliest frame of every running utterance on, so T steps always suffice
-    WR_TRY(run_until_idle(
-        h, st, what, NLn * 1000 + beam, (long)T + 1, "", [&]() -> GraphSlot & { return h->beam_tdt; },
-        [&] { return tdt_beam_step(h, NLn, B, st); }, [] {}));
+    WR_TRY(beam_tdt_steps(h, st, what, NLn, B, T, beam, false));
     WR_TRY(launch("beam_export_kernel", beam_export_kernel, dim3(B), dim3(256), 0, st, h->dev, hyps_d, hyp_lens_d, scores_d, n_hyps_d));
     scope.ok();
     return WR_OK;
@@ -3309,18 +3523,198 @@ extern "C" int wr_prefix_beam_search(wr_decoder *h, const float *enc_out_d, cons
     const int NLn = B * beam;
     WR_TRY(launch_ep_all(h, st, (long)B * T, enc_out_d, s.ep_all));
     WR_TRY(launch("beam_init_kernel", beam_init_kernel, dim3(NLn), dim3(128), 0, st, h->dev));
-    const auto frame = [&] { return beam_frame(h, NLn, B, st); };
-    if (h->use_graph_beam) WR_TRY(ensure_graph(h->beam, NLn * 1000 + beam, st, frame));
-    for (int f = 0; f < T; f += kStepsPerGraph) {
-        if (h->use_graph_beam) {
-            hipError_t e = hipGraphLaunch(h->beam.exec, st);
-            if (e != hipSuccess) { set_error("prefix_beam_search: hipGraphLaunch failed: %s", hipGetErrorString(e)); return WR_ELAUNCH; }
-        } else {
-            for (int i = 0; i < kStepsPerGraph; ++i) WR_TRY(frame());
-        }
-    }
+    WR_TRY(beam_plain_steps(h, st, "prefix_beam_search", NLn, B, T, beam, false));
     WR_TRY(launch("beam_export_kernel", beam_export_kernel, dim3(B), dim3(256), 0, st, h->dev, hyps_d, hyp_lens_d, scores_d, n_hyps_d));
     scope.ok();
+    return WR_OK;
+}
+
+// ------------------------------------------------ streaming prefix beam search: host side --
+namespace {
+
+// where the caller's block puts things: one pass for the size (null base) and for the pointers
+size_t beam_stream_carve(int n, int beam, int max_frames, char *base, BeamStreams *p)
+{
+    Carver c{base, 0};
+    const size_t Lcap = (size_t)max_frames + 1, nb = (size_t)n * beam;
+    p->bhyps = c.take<int32_t>(2 * nb * Lcap);
+    p->btimes = c.take<int32_t>(2 * nb * Lcap);
+    p->bhyp_lens = c.take<int32_t>(2 * nb);
+    p->bscores = c.take<double>(nb);
+    p->bvscores = c.take<double>(nb);
+    p->base = c.take<int32_t>(n); p->F = c.take<int32_t>(n); p->state = c.take<int32_t>(n); p->flags = c.take<int32_t>(n);
+    return align_up(c.off, 256);
+}
+
+int beam_stream_check(const char *what, const wr_decoder *h, int max_streams, int beam, int max_frames)
+{
+    WR_REQUIRE(h != nullptr, WR_EINVAL, "%s: null handle", what);
+    WR_REQUIRE(beam >= 1 && beam <= h->max_beam, WR_EINVAL, "%s: beam=%d lies outside [1, %d], the decoder's max", what, beam,
+               h->max_beam);
+    WR_REQUIRE(max_streams >= 1 && max_streams <= h->max_utt && (long)max_streams * beam <= h->d.NL, WR_EINVAL,
+               "%s: max_streams=%d with beam %d exceeds the decoder's capacity", what, max_streams, beam);
+    WR_REQUIRE(max_frames >= 1 && max_frames < (1 << 30), WR_EINVAL, "%s: max_frames=%d must be 1 or more", what, max_frames);
+    return WR_OK;
+}
+
+// While a chunk call builds and uploads its state block the handle's hypothesis buffers are the attached ones; every other
+// search finds the handle's own again.
+struct BeamStreamState {
+    DevState &s;
+    DevState saved;
+    BeamStreamState(wr_decoder *h) : s(h->host), saved(h->host)
+    {
+        const BeamStreams &bs = h->bs;
+        s.bhyps = bs.bhyps; s.btimes = bs.btimes; s.bhyp_lens = bs.bhyp_lens; s.bscores = bs.bscores; s.bvscores = bs.bvscores;
+        s.bs_base = bs.base; s.bs_F = bs.F; s.bs_state = bs.state; s.bs_flags = bs.flags;
+        s.Lmax = bs.max_frames + 1;
+    }
+    ~BeamStreamState()
+    {
+        s.bhyps = saved.bhyps; s.btimes = nullptr; s.bhyp_lens = saved.bhyp_lens; s.bscores = saved.bscores; s.bvscores = nullptr;
+        s.bs_base = s.bs_F = s.bs_state = nullptr; s.bs_flags = nullptr;
+        s.Lmax = saved.Lmax;
+    }
+};
+
+}  // namespace
+
+// decode_stream.hpp: the size behind wr_decoder_beam_stream_workspace_bytes (0 for sizes no handle can have)
+size_t wr::beam_stream_bytes(int max_streams, int beam, int max_frames)
+{
+    if (max_streams < 1 || beam < 1 || beam > kMaxBeam || max_frames < 1 || max_frames >= (1 << 30)) return 0;
+    BeamStreams p;
+    return beam_stream_carve(max_streams, beam, max_frames, nullptr, &p);
+}
+
+// decode_stream.hpp: wr_decoder_attach_beam_stream
+int wr::beam_stream_attach(wr_decoder *h, int max_streams, int beam, int max_frames, void *workspace_d, size_t workspace_bytes)
+{
+    const char *what = "decoder_attach_beam_stream";
+    WR_TRY(beam_stream_check(what, h, max_streams, beam, max_frames));
+    WR_REQUIRE(workspace_d != nullptr, WR_EINVAL, "%s: null workspace", what);
+    BeamStreams p;                                // the handle is written only once everything here has succeeded
+    const size_t need = beam_stream_carve(max_streams, beam, max_frames, static_cast<char *>(workspace_d), &p);
+    WR_REQUIRE(workspace_bytes >= need, WR_EWORKSPACE, "%s: workspace %zu < required %zu", what, workspace_bytes, need);
+    if (hipHostMalloc(reinterpret_cast<void **>(&p.h_flags), (size_t)kStageSlots * max_streams * sizeof(int32_t),
+                      hipHostMallocDefault) != hipSuccess) {
+        set_error("%s: hipHostMalloc failed", what);
+        return WR_ELAUNCH;
+    }
+    if (h->work) (void)hipStreamSynchronize(h->work);       // no copy still reads the flags of the block being replaced
+    if (h->bs.h_flags) (void)hipHostFree(h->bs.h_flags);
+    p.attached = true;
+    p.n = max_streams; p.beam = beam; p.max_frames = max_frames;
+    p.phase.assign(max_streams, 0);
+    p.frames.assign(max_streams, 0);
+    h->bs = p;
+    if (h->stream_lanes == kBeamStreamLanes) h->stream_lanes = -1;
+    return WR_OK;
+}
+
+// decode_stream.hpp: the search behind wr_prefix_beam_search_chunk (decode_stream.cpp has checked the durations -- `dur`
+// holds them by jump, D = 0 for a plain model --, every pointer and the handle).  Checks what needs the handle and the
+// host's record of the streams, all before the first HIP call, then runs the chunk.
+int wr::beam_stream_chunk_body(wr_decoder *h, const float *enc_chunk_d, const int32_t *chunk_lens_d, const float *ctc_logp_chunk_d,
+                               int B, int T, int beam, float ctc_weight, float transducer_weight, int blank, const TdtDur &dur,
+                               const int32_t *flags, int32_t *hyps_d, int32_t *times_d, int32_t *hyp_lens_d, double *scores_d,
+                               double *vscores_d, int32_t *n_hyps_d, void *stream)
+{
+    const char *what = "prefix_beam_search_chunk";
+    const bool tdt = dur.D > 0;
+    BeamStreams &bs = h->bs;
+    WR_REQUIRE(bs.attached, WR_EINVAL, "%s: no stream state is attached (wr_decoder_attach_beam_stream comes first)", what);
+    WR_REQUIRE(B == bs.n && beam == bs.beam, WR_EINVAL, "%s: B=%d, beam=%d differ from the attached %d streams of beam %d", what,
+               B, beam, bs.n, bs.beam);
+    WR_REQUIRE(T > 0 && T <= h->Tmax, WR_EINVAL, "%s: T=%d exceeds the decoder's Tmax=%d", what, T, h->Tmax);
+    const int V = h->d.V - dur.D;                  // token columns of the joiner's row
+    if (tdt) {
+        WR_REQUIRE(V >= 2, WR_EINVAL, "%s: the joiner has %d outputs, D=%d durations leave %d token columns (2 or more are needed)",
+                   what, h->d.V, dur.D, V);
+        WR_REQUIRE(h->d.Ve >= V, WR_EINVAL, "%s: the embedding table has %d rows, the token vocabulary %d", what, h->d.Ve, V);
+        WR_REQUIRE(ctc_logp_chunk_d || (ctc_weight == 0.f && transducer_weight == 1.f), WR_EINVAL,
+                   "%s: no CTC posterior, so (ctc_weight, transducer_weight) must be (0, 1), got (%g, %g)", what, (double)ctc_weight,
+                   (double)transducer_weight);
+    } else {
+        WR_REQUIRE(ctc_logp_chunk_d != nullptr, WR_EINVAL,
+                   "%s: the plain search mixes the CTC posterior into every frame, as wr_prefix_beam_search does: it may not be null",
+                   what);
+    }
+    WR_REQUIRE(blank >= 0 && blank < V, WR_EINVAL, "%s: blank %d out of range [0,%d)", what, blank, V);
+    // the streams: another search on the handle has overwritten the lanes' predictor slots
+    if (h->stream_lanes != kBeamStreamLanes) {
+        for (int &p : bs.phase) { bs.overwritten = bs.overwritten || p != 0; p = 0; }
+    }
+    const unsigned long long durs = tdt ? pack_durations(dur) : 0;
+    bool continues = false;
+    for (int b = 0; b < B; ++b) {
+        const int f = flags ? flags[b] : 0;
+        WR_REQUIRE((f & ~3) == 0, WR_EINVAL, "%s: flags[%d]=%d has bits beyond reset (1) and final (2)", what, b, f);
+        if (f & 1) {
+            WR_REQUIRE(T <= bs.max_frames, WR_EINVAL, "%s: stream %d: a chunk of %d frames exceeds max_frames=%d", what, b, T,
+                       bs.max_frames);
+            continue;
+        }
+        WR_REQUIRE(bs.phase[b] != 0 || !bs.overwritten, WR_EINVAL,
+                   "%s: stream %d continues, but another search or wr_predictor_step on the handle has overwritten the streams "
+                   "since (reset every stream)", what, b);
+        WR_REQUIRE(bs.phase[b] != 0, WR_EINVAL, "%s: stream %d continues without ever having been reset", what, b);
+        if (bs.phase[b] == 2) {
+            WR_REQUIRE(!(f & 2), WR_EINVAL, "%s: stream %d is fed after its final call (reset it first)", what, b);
+            continue;                              // finished: the device leaves it as it is
+        }
+        WR_REQUIRE(bs.frames[b] + T <= bs.max_frames, WR_EINVAL,
+                   "%s: stream %d: %ld frames since its reset + a chunk of %d exceed max_frames=%d", what, b, bs.frames[b], T,
+                   bs.max_frames);
+        continues = true;
+    }
+    WR_REQUIRE(!continues || (bs.blank == blank && bs.D == dur.D && bs.durs == durs), WR_EINVAL,
+               "%s: durations or blank changed in the middle of a stream (blank %d -> %d, D %d -> %d)", what, bs.blank, blank,
+               bs.D, dur.D);
+    // ---- nothing is refused below this line; the host's record of the streams follows the call
+    for (int b = 0; b < B; ++b) {
+        const int f = flags ? flags[b] : 0;
+        if (f & 1) { bs.phase[b] = 1; bs.frames[b] = 0; }
+        if (bs.phase[b] == 1) { bs.frames[b] += T; if (f & 2) bs.phase[b] = 2; }
+    }
+    bs.overwritten = false;
+    bs.blank = blank; bs.D = dur.D; bs.durs = durs;
+    h->stream_lanes = -1;                         // until the call has succeeded
+    WorkScope scope(h, static_cast<hipStream_t>(stream));
+    hipStream_t st = scope.st;
+    BeamStreamState swap(h);
+    DevState &s = h->host;
+    s.enc = enc_chunk_d; s.enc_lens = chunk_lens_d; s.ctc_logp = ctc_logp_chunk_d;
+    s.n_utt = B; s.T = T; s.lanes_per_utt = beam; s.n_lanes = B * beam;
+    s.beam = beam; s.ctc_weight = ctc_weight; s.tr_weight = transducer_weight; s.blank = blank;
+    s.tdt_durs = durs; s.tdt_D = dur.D; s.hyp_frames = nullptr;
+    // the flags ride in the pinned slot of the state block's upload (upload_state waits for the slot's last copy, then
+    // records the event behind both copies)
+    const int slot = h->stage_next;
+    (void)hipEventSynchronize(h->stage_ev[slot]);
+    int32_t *hf = bs.h_flags + (size_t)slot * B;
+    for (int b = 0; b < B; ++b) hf[b] = flags ? flags[b] : 0;
+    if (hipMemcpyAsync(bs.flags, hf, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess) {
+        set_error("%s: flags upload failed", what);
+        return WR_ELAUNCH;
+    }
+    if (int rc = upload_state(h, st)) return rc;
+    (void)hipMemsetAsync(s.active_count, 0, 3 * sizeof(int32_t), st);
+    (void)hipMemsetAsync(s.lane_active, 0, sizeof(int32_t) * h->d.NLp, st);
+    const int NLn = B * beam;
+    WR_TRY(launch_ep_all(h, st, (long)B * T, enc_chunk_d, s.ep_all));
+    WR_TRY(launch("beam_init_kernel", beam_init_kernel, dim3(NLn), dim3(128), 0, st, h->dev));
+    if (tdt) {
+        WR_TRY(launch("beam_chunk_begin_kernel", beam_chunk_begin_kernel<true>, dim3(B), dim3(kBeamUpdThreads), 0, st, h->dev));
+        WR_TRY(beam_tdt_steps(h, st, what, NLn, B, T, beam, true));
+    } else {
+        WR_TRY(launch("beam_chunk_begin_kernel", beam_chunk_begin_kernel<false>, dim3(B), dim3(kBeamUpdThreads), 0, st, h->dev));
+        WR_TRY(beam_plain_steps(h, st, what, NLn, B, T, beam, true));
+    }
+    WR_TRY(launch("beam_stream_export_kernel", beam_stream_export_kernel, dim3(B), dim3(256), 0, st, h->dev, hyps_d, times_d,
+                  hyp_lens_d, scores_d, vscores_d, n_hyps_d));
+    scope.ok();
+    h->stream_lanes = kBeamStreamLanes;
     return WR_OK;
 }
 

@@ -254,6 +254,63 @@ class DeviceDecoder:
         return self._beam("wr_prefix_beam_search_tdt", encoder_out, encoder_out_lens, ctc_logp, beam_size, float(ctc_weight),
                           float(transducer_weight), int(blank), _durations_arg(durations), len(durations))
 
+    def attach_beam_stream(self, n_streams: int, beam: int, max_frames: int) -> None:
+        """Give the handle the state of `n_streams` streams of `prefix_beam_chunk` (`wr_decoder_attach_beam_stream`): beam
+        `beam`, at most `max_frames` encoder frames (chunk widths summed) between two resets of a stream.  Attaching
+        again replaces the state and ends every stream."""
+        n_streams, beam, max_frames = int(n_streams), int(beam), int(max_frames)
+        nbytes = self._lib.wr_decoder_beam_stream_workspace_bytes(self._h, n_streams, beam, max_frames)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self._lib.wr_decoder_attach_beam_stream(self._h, n_streams, beam, max_frames, _lib.ptr(ws), nbytes)
+        _lib.check(rc, "wr_decoder_attach_beam_stream")
+        self._beam_stream_ws = ws
+        self.beam_stream = (n_streams, beam, max_frames)
+
+    beam_stream = None
+
+    def prefix_beam_chunk(self, encoder_chunk: torch.Tensor, chunk_lens: torch.Tensor, beam_size: int, blank: int = 0,
+                          ctc_logp: torch.Tensor = None, ctc_weight: float = 0.0, transducer_weight: float = 1.0,
+                          durations=None, reset=False, final=False):
+        """The next chunk of every stream of the streaming prefix beam search (`wr_prefix_beam_search_chunk`; the rule is
+        in include/wr_api.h, "Streaming transducer prefix beam search").  encoder_chunk (B, T, E) with chunk_lens (B,)
+        valid frames each; ctc_logp (B, T, V) of the chunk, or None for a token-and-duration model searched with weights
+        (0, 1); `durations` None: a plain model.  `reset` / `final`: a bool for all streams or one per stream -- reset
+        the stream before the chunk / the chunk is the stream's last.  Per stream the current n-best, best first:
+        [(tokens incl. the seed blank, score, viterbi_score, times)], times[i] the absolute encoder frame at which token
+        i + 1 was emitted.  `set_graph` applies; the result does not depend on it."""
+        if self.beam_stream is None:
+            raise RuntimeError("DeviceDecoder.prefix_beam_chunk: call attach_beam_stream(n_streams, beam, max_frames) first")
+        enc = _f32(encoder_chunk)
+        ctc = None if ctc_logp is None else _f32(ctc_logp)
+        B, T, _ = enc.shape
+
+        def mask(x):
+            return [bool(x)] * B if isinstance(x, (bool, int)) else [bool(v) for v in x]
+
+        rs, fin = mask(reset), mask(final)
+        if len(rs) != B or len(fin) != B:
+            raise RuntimeError(f"DeviceDecoder.prefix_beam_chunk: reset / final masks must have one entry per stream ({B})")
+        flags = (ctypes.c_int32 * B)(*[int(r) | (int(f) << 1) for r, f in zip(rs, fin)])
+        lens = chunk_lens.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+        if lens.numel() != B:
+            raise RuntimeError(f"DeviceDecoder.prefix_beam_chunk: chunk_lens has {lens.numel()} elements for {B} streams")
+        cap = self.beam_stream[2] + 1
+        beam_size = int(beam_size)
+        hyps = torch.empty(B, beam_size, cap, dtype=torch.int32, device=self.device)
+        tm = torch.empty(B, beam_size, cap, dtype=torch.int32, device=self.device)
+        hl = torch.empty(B, beam_size, dtype=torch.int32, device=self.device)
+        sc = torch.empty(B, beam_size, dtype=torch.float64, device=self.device)
+        vs = torch.empty(B, beam_size, dtype=torch.float64, device=self.device)
+        nh = torch.empty(B, dtype=torch.int32, device=self.device)
+        dur = (None, 0) if durations is None else (_durations_arg(durations), len(durations))
+        self._call("wr_prefix_beam_search_chunk", enc, lens, ctc, B, T, beam_size, float(ctc_weight),
+                   float(transducer_weight), int(blank), *dur, flags, hyps, tm, hl, sc, vs, nh)
+        hl, sc, vs, nh = hl.cpu().tolist(), sc.cpu().tolist(), vs.cpu().tolist(), nh.cpu().tolist()
+        width = max(max(row) for row in hl)
+        hyps, tm = hyps[:, :, :width].cpu().tolist(), tm[:, :, :width].cpu().tolist()
+        return [[(hyps[b][e][:hl[b][e]], sc[b][e], vs[b][e], tm[b][e][1:hl[b][e]]) for e in range(nh[b])] for b in range(B)]
+
     def predictor_step(self, tokens: torch.Tensor, cache_h: torch.Tensor, cache_c: torch.Tensor):
         """tokens (N,), cache (L, N, H) -> out (N, P), new_h, new_c (L, N, H)."""
         N = tokens.numel()

@@ -61,6 +61,100 @@ def _search(cache, owner, encoder_out: torch.Tensor, beam_size: int, search, wit
     return [[Sequence(hyp=h, score=s, cache=None) for h, s in utt] for utt in search(dec, ctc_logp)]
 
 
+class TransducerPrefixBeamStream:
+    """Transducer prefix beam search continued chunk by chunk, for `n_streams` streams at once, with the Viterbi score and
+    the frame of every token of each hypothesis (`wr_prefix_beam_search_chunk`; the rule is in include/wr_api.h,
+    "Streaming transducer prefix beam search").  `model` is a Transducer, plain or with `tdt_durations`; `max_frames`
+    bounds the encoder frames (chunk widths summed) a stream may take between two resets, `chunk_frames` the width of a
+    chunk.  ctc_weight / transducer_weight None: 0.3 / 0.7 for a plain model (`beam_search`), 0 / 1 for a
+    token-and-duration model (`tdt_beam_search`).
+
+    reset(streams=None) starts the given streams (all of them by default) fresh with the next search.
+    search(encoder_out_chunk (n_streams, T, E), lens, final=False) consumes lens[b] <= T frames of stream b (0 and no
+    final flag leaves it untouched; `final` is a bool or one per stream) and returns per stream the current n-best, best
+    first: [(tokens incl. the seed blank, score, viterbi_score, times)].  The CTC posterior of the chunk (`model.ctc`) is
+    computed here whenever it is mixed in: always for a plain model, and for a token-and-duration model when ctc_weight is
+    not 0."""
+
+    def __init__(self, model, n_streams: int, beam_size: int, max_frames: int, chunk_frames: int = 64,
+                 ctc_weight: float = None, transducer_weight: float = None):
+        self.model = model
+        self.n_streams, self.beam_size = int(n_streams), int(beam_size)
+        self.max_frames, self.chunk_frames = int(max_frames), int(chunk_frames)
+        if self.n_streams < 1 or self.max_frames < 1 or self.chunk_frames < 1 or not 1 <= self.beam_size <= 16:
+            raise RuntimeError(f"TransducerPrefixBeamStream: n_streams={n_streams}, beam_size={beam_size} (1..16), "
+                               f"max_frames={max_frames}, chunk_frames={chunk_frames} must be positive")
+        self.durations = getattr(model, "tdt_durations", None)
+        tdt = self.durations is not None
+        self.ctc_weight = float((0.0 if tdt else 0.3) if ctc_weight is None else ctc_weight)
+        self.transducer_weight = float((1.0 if tdt else 0.7) if transducer_weight is None else transducer_weight)
+        self._with_ctc = not tdt or self.ctc_weight != 0.0
+        self._dec = None
+        self._phase = [0] * self.n_streams          # 0: resets with the next search, 1: running, 2: had its final chunk
+        self.frames = [0] * self.n_streams          # chunk widths summed since the stream's reset
+
+    def reset(self, streams=None) -> None:
+        for b in (range(self.n_streams) if streams is None else streams):
+            self._phase[int(b)] = 0
+            self.frames[int(b)] = 0
+
+    def search(self, encoder_out_chunk: torch.Tensor, lens, final=False):
+        from .greedy_search import _decoder_cache, expand_lens
+        if encoder_out_chunk.dim() != 3:
+            raise RuntimeError("TransducerPrefixBeamStream: the chunk must be (n_streams, frames, encoder dim)")
+        B, T, _ = encoder_out_chunk.shape
+        if B != self.n_streams:
+            raise RuntimeError(f"TransducerPrefixBeamStream: chunk has {B} streams, the stream set has {self.n_streams}")
+        if T > self.chunk_frames:
+            raise RuntimeError(f"TransducerPrefixBeamStream: a chunk of {T} frames exceeds chunk_frames={self.chunk_frames}")
+        fin = [bool(final)] * B if isinstance(final, (bool, int)) else [bool(f) for f in final]
+        if len(fin) != B:
+            raise RuntimeError(f"TransducerPrefixBeamStream: final has {len(fin)} entries for {B} streams")
+        ln = expand_lens(lens, B).reshape(-1)
+        if ln.numel() != B:
+            raise RuntimeError(f"TransducerPrefixBeamStream: lens has {ln.numel()} elements for {B} streams")
+        fed = [int(v) > 0 for v in ln.cpu().tolist()]
+        for b in range(B):
+            if self._phase[b] == 2 and (fed[b] or fin[b]):
+                raise RuntimeError(f"TransducerPrefixBeamStream: stream {b} is fed after its final chunk (reset it first)")
+            if self._phase[b] != 2 and self.frames[b] + T > self.max_frames:
+                raise RuntimeError(f"TransducerPrefixBeamStream: stream {b}: {self.frames[b]} frames done + a chunk of {T} "
+                                   f"exceeds max_frames={self.max_frames}")
+        if not encoder_out_chunk.is_cuda:
+            raise RuntimeError("wenet_celoss_amd.TransducerPrefixBeamStream: the chunk must live on a HIP device (no CPU path)")
+        model = self.model
+        dec = _decoder_cache(model).get(model.predictor, model.joint, lanes=B * self.beam_size, utts=B, tmax=self.chunk_frames,
+                                        max_hyp=0, beam=self.beam_size)
+        if dec is not self._dec:
+            if any(p == 1 for p in self._phase):
+                raise RuntimeError("the decoder handle was rebuilt (weights changed or capacity grew) in the middle of a "
+                                   "stream: call reset() first")
+            self._phase = [0] * B                   # finished streams lived on the old handle too
+        if dec.beam_stream != (B, self.beam_size, self.max_frames) or dec is not self._dec:
+            dec.attach_beam_stream(B, self.beam_size, self.max_frames)
+        self._dec = dec
+        ctc_logp = None
+        if self._with_ctc:
+            with torch.no_grad():
+                ctc_logp = model.ctc.log_softmax(encoder_out_chunk)
+        reset = [p == 0 for p in self._phase]
+        try:
+            out = dec.prefix_beam_chunk(encoder_out_chunk, ln, self.beam_size, model.blank, ctc_logp=ctc_logp,
+                                        ctc_weight=self.ctc_weight, transducer_weight=self.transducer_weight,
+                                        durations=self.durations, reset=reset, final=fin)
+        except RuntimeError:
+            _decoder_cache(model).discard(dec)
+            raise
+        for b in range(B):
+            if reset[b]:
+                self._phase[b], self.frames[b] = 1, 0
+            if self._phase[b] == 1:
+                self.frames[b] += T
+                if fin[b]:
+                    self._phase[b] = 2
+        return out
+
+
 class PrefixBeamSearch:
     def __init__(self, encoder, predictor, joint, ctc, blank):
         self.encoder = encoder

@@ -929,6 +929,43 @@ class Transducer(nn.Module):
         self._stream_dec = dec
         return hyps[0] if N == 1 else hyps
 
+    # ----- streaming transducer prefix beam search (what runtime/core/decoder/rnnt_prefix_beam_search.{h,cc} drafts) --
+    def reset_beam_stream(self, n_streams: int = 1, beam_size: int = 5, max_frames: int = 4096, chunk_frames: int = 64,
+                          ctc_weight: Optional[float] = None, transducer_weight: Optional[float] = None) -> None:
+        """Start `n_streams` fresh streams of the transducer prefix beam search, plain or token-and-duration
+        (`TransducerPrefixBeamStream`).  `max_frames` bounds the encoder frames (chunk widths summed) a stream may take
+        before its next reset, `chunk_frames` the width of a chunk.  The weights default to `beam_search`'s 0.3 / 0.7 for
+        a plain model and to `tdt_beam_search`'s 0 / 1 for a model with tdt_durations."""
+        from .search.prefix_beam_search import TransducerPrefixBeamStream
+        self._beam_stream = TransducerPrefixBeamStream(self, n_streams, beam_size, max_frames, chunk_frames, ctc_weight,
+                                                       transducer_weight)
+
+    def forward_prefix_beam_search(self, encoder_out_chunk: torch.Tensor, encoder_out_lens: torch.Tensor, final=False):
+        """Feed the next chunk of encoder frames of every stream, encoder_out_chunk (N, Tchunk, E) with encoder_out_lens
+        (N,) valid frames each (0 without `final`: the stream is left untouched); `final` (a bool or one per stream) marks
+        a stream's last chunk -> the current n-best of every stream, [(tokens incl. the seed blank, score, viterbi_score,
+        times)] best first; times are encoder frames since the stream's reset."""
+        if getattr(self, "_beam_stream", None) is None:
+            self.reset_beam_stream(encoder_out_chunk.size(0), chunk_frames=max(64, encoder_out_chunk.size(1)))
+        return self._beam_stream.search(encoder_out_chunk, encoder_out_lens, final=final)
+
+    def beam_search_times(self, speech: torch.Tensor, speech_lengths: torch.Tensor, beam_size: int = 5,
+                          ctc_weight: Optional[float] = None, transducer_weight: Optional[float] = None,
+                          decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1,
+                          simulate_streaming: bool = False):
+        """The n-best of `beam_search` (plain model) / `tdt_beam_search` (tdt_durations) over whole utterances, any batch
+        size, with the Viterbi score and the encoder frame of every token: per utterance [(tokens without the seed blank,
+        score, viterbi_score, times)] best first.  One reset-and-final chunk of the streaming search."""
+        from .search.prefix_beam_search import TransducerPrefixBeamStream
+        assert speech.shape[0] == speech_lengths.shape[0]
+        assert decoding_chunk_size != 0
+        encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
+                                                          num_decoding_left_chunks, simulate_streaming)
+        B, T, _ = encoder_out.shape
+        stream = TransducerPrefixBeamStream(self, B, beam_size, T, T, ctc_weight, transducer_weight)
+        nbest = stream.search(encoder_out, encoder_mask.squeeze(1).sum(1), final=True)
+        return [[(h[1:], s, v, t) for h, s, v, t in utt] for utt in nbest]
+
     # ------------------- streaming CTC prefix beam search (runtime/core/decoder/ctc_prefix_beam_search.cc:107-211) --
     def reset_ctc_stream(self, n_streams: int = 1, beam_size: int = 10, max_frames: int = 4096) -> None:
         """Start `n_streams` fresh CTC prefix-beam streams; `max_frames` bounds the encoder frames (chunk widths summed)
