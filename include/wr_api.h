@@ -1313,6 +1313,83 @@ int wr_prefix_beam_search_chunk(wr_decoder *h, const float *enc_chunk_d, const i
                                 const int32_t *flags /* [B], host, or NULL */, int32_t *hyps_d, int32_t *times_d,
                                 int32_t *hyp_lens_d, double *scores_d, double *vscores_d, int32_t *n_hyps_d, void *stream);
 
+/* Context-graph biasing in the streaming transducer prefix beam search: the search of "Streaming transducer prefix beam
+ * search" above, plain or token-and-duration, with the phrase biasing of "Context-graph biasing in the CTC prefix beam
+ * search".  The reference runtime drafts it (runtime/core/decoder/rnnt_prefix_beam_search.{h,cc}: a context_graph_ member,
+ * a commented-out UpdateOutputs with start / end boundaries, FinalizeSearch() -> UpdateFinalContext()) and does not finish
+ * it.  Both contracts hold unchanged; this text states only what is added.  Addition only: WR_API_VERSION stays 3.
+ *
+ * Graph.  The table of the CTC contract, unchanged: arc_begin[S+1], arc_token[A] strictly increasing within a state,
+ * arc_next[A], arc_score[A] float32, escape[S], final[S]; state 0 is the root; next(state, token) as defined there, the
+ * token that breaks a partial match not being retried from the root.  For a token-and-duration model the tokens are
+ * token-column indices < V = vocab_size - D.  The table must be the same from a stream's reset to its end: that is the
+ * caller's responsibility.
+ * Per-entry fields.  Every entry of a stream additionally carries ctx_state (int32, 0 at the seed), ctx_score (float64, 0.0
+ * at the seed) and tags[], one int32 per token after the seed blank: bit 0 a start boundary at this token, bit 1 an end
+ * boundary at this token.  The seed's slot is -1, as for times.
+ * Candidates (steps 3-4 of the TDT rule).  A waiting entry and a blank arc copy the three fields of the source entry e.  A
+ * label arc appending token k, whatever its duration (0 and jumps beyond 1 included: the graph is walked once per token),
+ * takes (st, sc, start, end) = next(e.ctx_state, k) and sets ctx_state = st, ctx_score = e.ctx_score + (double)sc,
+ * tags = e.tags + (start | end << 1,).  The candidate's score and vscore are computed exactly as before,
+ * (double)((float)score + v): the bonus never enters the fp32 cast, and score stays the pure transducer (or mixed) score.
+ * The first prune -- the top-`beam` tokens or pairs of steps 2-3 -- is unbiased, as first_beam is in the CTC search.
+ * Fusion (step 6).  Unchanged.  The three fields are a function of the token sequence alone (the table is deterministic and
+ * copies keep the state), so all members of a class agree on them; the class takes them from its representative.  Its times
+ * still come from the Viterbi-best member.
+ * Prune (step 7), and the fuse-and-re-sort a final call does before its first step: a stable descending sort of the
+ * representatives by total = fused_score + ctx_score, one float64 add; the first `beam` are the new beam, in that order.
+ *
+ * Export.  Beside the outputs of wr_prefix_beam_search_chunk: trans_scores [B, beam] float64 (the pure fused score),
+ * context_scores [B, beam] float64, tags [B, beam, Lcap] (the seed's slot -1, padded with -1), context_states [B, beam]
+ * (the entry's ctx_state as the stream holds it).  scores = trans_scores + context_scores, the add of the prune; vscores
+ * stay pure.  Beyond n_hyps[b]: scores and trans_scores -inf, context_scores 0.0, context_states 0.
+ * Flag bit 2 (value 4), per stream, exports that stream "as if it ended here" (UpdateFinalContext): every entry with
+ * ctx_state != 0 gains (double)escape[ctx_state] in the exported context score, and the exported list of that stream is
+ * sorted again, stable and descending, by the new totals.  Tags and the state block are not touched, and the stream goes
+ * on.  Bit 2 is independent of bit 1, the final flag: bit 1 ends the stream's frames and clamps arcs, bit 2 is about the
+ * exported bonus only.  A call with lens[b] == 0 and only bit 2 for stream b steps nothing and exports it finalised (its
+ * chunk width T still counts against max_frames on the host, as every call's does).
+ *
+ * Consequences.  With an empty graph (S = 1, A = 0) every output of wr_prefix_beam_search_chunk is reproduced bit for bit;
+ * tags are all 0 and context scores all 0.0.  With a graph whose arc scores are all 0.0 the same outputs are bit for bit,
+ * but tags are set: the graph is still walked.  Any chunking equals the one-chunk call bit for bit in all outputs, under the
+ * existing condition for token-and-duration streams.  Bit 2 in the middle of a stream does not change what later chunks
+ * return.
+ * Departures, as for the CTC form: the bonus is summed in float64, and nested phrases commit at the shorter phrase's last
+ * token (the table is whatever the caller built).
+ *
+ * State.  wr_decoder_attach_beam_context_stream gives the handle a block of the biased form's own layout
+ * (wr_decoder_beam_context_stream_workspace_bytes): the plain block's contents, then ctx_score, ctx_state and a
+ * double-buffered int32 [2][B * beam][Lcap] tag list -- larger than the plain block for every shape.  The plain size query,
+ * attach and layout are unchanged.  Attaching one form replaces the other and ends every stream; a plain chunk call cannot
+ * continue a biased stream or the reverse.  As for the plain streams, any other search or wr_predictor_step on the handle
+ * in between means every stream must be reset.
+ *
+ * The chunk call takes the arguments of wr_prefix_beam_search_chunk up to n_hyps, then the six table pointers (device), S,
+ * A, the four new outputs, and the stream.  The table pointers, S, A and the flags travel in the uploaded state block, never
+ * in a captured graph.  The kernels clamp every arc_next into [0, S), every CSR bound into [0, A] and every stored
+ * ctx_state into [0, S) before use as an index: a bad table gives wrong bonuses, never an out-of-range access.
+ *
+ * Refused before any HIP call, in this order: everything wr_prefix_beam_search_chunk refuses, in its order ("no attached
+ * stream state" means the biased form's; a null among the four new outputs counts with the null outputs; flag bits beyond
+ * 7 instead of beyond 3); S < 1 or A < 0, then a null table pointer (WR_EINVAL); S > 65536 or A > 1048576
+ * (WR_EUNSUPPORTED).  wr_prefix_beam_search_chunk itself keeps refusing flag bits beyond 3. */
+size_t wr_decoder_beam_context_stream_workspace_bytes(const wr_decoder *h, int max_streams, int beam, int max_frames);
+
+int wr_decoder_attach_beam_context_stream(wr_decoder *h, int max_streams, int beam, int max_frames, void *workspace_d,
+                                          size_t workspace_bytes);
+
+int wr_prefix_beam_search_context_chunk(wr_decoder *h, const float *enc_chunk_d, const int32_t *chunk_lens_d,
+                                        const float *ctc_logp_chunk_d /* [B, T, V] or NULL */, int B, int T, int beam,
+                                        float ctc_weight, float transducer_weight, int blank,
+                                        const int32_t *durations /* [D], host; NULL with D = 0: plain */, int D,
+                                        const int32_t *flags /* [B], host, or NULL */, int32_t *hyps_d, int32_t *times_d,
+                                        int32_t *hyp_lens_d, double *scores_d, double *vscores_d, int32_t *n_hyps_d,
+                                        const int32_t *arc_begin_d, const int32_t *arc_token_d, const int32_t *arc_next_d,
+                                        const float *arc_score_d, const float *escape_d, const int32_t *final_d, int S, int A,
+                                        double *trans_scores_d, double *context_scores_d, int32_t *tags_d,
+                                        int32_t *context_states_d, void *stream);
+
 /* Measurement hook: the three counters the last polling search on this handle read back (host memory, no HIP call).
  * Greedy searches: streams still active, blank decisions, emissions.  wr_prefix_beam_search_tdt: utterances still running
  * (0 after a successful call), steps taken summed over the utterances, hypotheses expanded. */

@@ -1435,10 +1435,88 @@ def bench_beamstream(args):
                           "equals_one_chunk": out_c == out_1}), flush=True)
 
 
+def bench_beamctx(args):
+    """Context-graph biasing in the streaming transducer prefix beam search, at the shape of `beamstream` (16 streams x
+    1500 frames, beam 8, V = 5000, chunks of --chunk-frames = 16 frames; a plain model and durations 0 .. 4): the unbiased
+    stream, the biased stream with an empty graph and with 1000 random three-token phrases, in the same process and
+    alternating, --reps rounds after one warm-up round.  Per line: the median ms per utterance batch, ms per chunk call,
+    and the ratio to the unbiased stream of the same model (the median of the per-round ratios)."""
+    import statistics
+    import time
+    import wenet_celoss_amd as w
+    from wenet_celoss_amd.decoder import DeviceDecoder
+    dev = torch.device("cuda:0")
+    torch.manual_seed(6)
+    D = args.durations
+    V, E, P, J, H, L, beam = 5000, 256, 256, 512, 256, 2, 8
+    B, T = (args.B if args.B != 32 else 16), (args.T if args.T != 1000 else 1500)
+    C = args.chunk_frames
+    pred = w.RNNPredictor(V + D, P, P, 0.1, H, L).to(dev).eval()
+    joint = w.TransducerJoint(V + D, E, P, J).to(dev).eval()
+    with torch.no_grad():
+        joint.ffn_out.weight *= 10
+        joint.ffn_out.bias[0] += 16.0
+    plain_joint = w.TransducerJoint(V, E, P, J).to(dev).eval()
+    plain_joint.load_state_dict({k: (v[:V] if k.startswith("ffn_out.") else v) for k, v in joint.state_dict().items()})
+    ctc = w.CTC(V, E).to(dev).eval()
+    enc = torch.randn(B, T, E, device=dev)
+    with torch.no_grad():
+        ctc_logp = ctc.log_softmax(enc)
+    chunks = [(enc[:, p:p + C].contiguous(), ctc_logp[:, p:p + C].contiguous(),
+               torch.full((B,), min(C, T - p), dtype=torch.int32, device=dev)) for p in range(0, T, C)]
+    phrases = torch.randint(1, V, (1000, 3), generator=torch.Generator().manual_seed(7)).tolist()
+    graphs = {"empty graph": w.ContextGraph([], 3.0), "1000 phrases": w.ContextGraph(phrases, 3.0)}
+
+    for name, jn, durations, mix in (("plain", plain_joint, None, (0.3, 0.7)), ("tdt", joint, tuple(range(D)), (0.0, 1.0))):
+        if args.only and name not in args.only.split(","):
+            continue
+        plain_dec, ctx_dec = DeviceDecoder(pred, jn, B * beam, B, T, 0, beam), DeviceDecoder(pred, jn, B * beam, B, T, 0, beam)
+        plain_dec.attach_beam_stream(B, beam, T)
+        ctx_dec.attach_beam_context_stream(B, beam, T)
+        post = (lambda c: c) if durations is None else (lambda c: None)
+
+        def run(graph):
+            out = None
+            for i, (e, c, n) in enumerate(chunks):
+                kw = dict(ctc_logp=post(c), ctc_weight=mix[0], transducer_weight=mix[1], durations=durations, reset=i == 0,
+                          final=i == len(chunks) - 1)
+                if graph is None:
+                    out = plain_dec.prefix_beam_chunk(e, n, beam, 0, **kw)
+                else:
+                    out = ctx_dec.prefix_beam_context_chunk(e, n, beam, 0, graph, finalize=i == len(chunks) - 1, **kw)
+            return out
+
+        variants = [("unbiased stream", None)] + list(graphs.items())
+        times = {k: [] for k, _ in variants}
+        outs = {}
+        for r in range(args.reps + 1):
+            for k, g in variants:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                outs[k] = run(g)
+                torch.cuda.synchronize()
+                if r > 0:
+                    times[k].append(time.perf_counter() - t0)
+        base = {"model": name, "durations": durations, "B": B, "T": T, "beam": beam, "chunk_frames": C, "chunks": len(chunks),
+                "rounds": args.reps}
+        for k, g in variants:
+            med = statistics.median(times[k])
+            line = {"what": k, **base, "ms_per_utterance": round(med * 1e3, 2), "ms_per_chunk": round(med * 1e3 / len(chunks), 4),
+                    "min_ms": round(min(times[k]) * 1e3, 2), "max_ms": round(max(times[k]) * 1e3, 2)}
+            if g is not None:
+                line["over_unbiased"] = round(statistics.median(a / b for a, b in zip(times[k], times["unbiased stream"])), 4)
+                line["states"], line["arcs"] = g.n_states, g.n_arcs
+                if g.n_arcs == 0:
+                    line["equals_unbiased"] = [[x[:4] for x in u] for u in outs[k]] == outs["unbiased stream"]
+                else:
+                    line["hyps_with_bonus"] = sum(1 for u in outs[k] for x in u if x[5] != 0.0)
+            print(json.dumps(line), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["joint", "ctc", "ctcdec", "greedy", "beam", "step", "hotword", "align", "simple", "smoothed", "pruned", "tdt",
-                                     "tdtstep", "tdtalign", "tdtdec", "tdtbeam", "ctcstream", "ctcctx", "beamstream"])
+                                     "tdtstep", "tdtalign", "tdtdec", "tdtbeam", "ctcstream", "ctcctx", "beamstream", "beamctx"])
     ap.add_argument("--chunk-frames", type=int, default=16, help="beamstream: encoder frames per chunk")
     ap.add_argument("--durations", type=int, default=5, help="tdt, tdtstep, tdtalign: number of durations D (the set is 0 .. D-1)")
     ap.add_argument("--n-steps", type=int, default=64)
@@ -1478,4 +1556,5 @@ if __name__ == "__main__":
     {"joint": bench_joint, "ctc": bench_ctc, "greedy": bench_greedy, "beam": bench_beam, "step": bench_step, "ctcdec": bench_ctcdec, "hotword": bench_hotword,
      "align": bench_align, "simple": bench_simple, "smoothed": bench_smoothed, "pruned": bench_pruned,
      "tdt": bench_tdt, "tdtstep": bench_tdtstep, "tdtalign": bench_tdtalign, "tdtdec": bench_tdtdec,
-     "tdtbeam": bench_tdtbeam, "ctcstream": bench_ctcstream, "ctcctx": bench_ctcctx, "beamstream": bench_beamstream}[a.what](a)
+     "tdtbeam": bench_tdtbeam, "ctcstream": bench_ctcstream, "ctcctx": bench_ctcctx, "beamstream": bench_beamstream,
+     "beamctx": bench_beamctx}[a.what](a)

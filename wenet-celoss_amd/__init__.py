@@ -21,8 +21,8 @@ from .rnnt_tdt import TDTLoss, rnnt_tdt_forced_align, rnnt_tdt_lattice, rnnt_tdt
 from .predictor import ConvPredictor, EmbeddingPredictor, PredictorBase, RNNPredictor  # noqa: F401
 from .search.greedy_search import (basic_greedy_search, basic_greedy_search_both,  # noqa: F401
                                    basic_greedy_search_hw, edit_distance, tdt_greedy_search)
-from .search.prefix_beam_search import (PrefixBeamSearch, Sequence, TransducerPrefixBeamStream,  # noqa: F401
-                                        tdt_prefix_beam_search)
+from .search.prefix_beam_search import (PrefixBeamSearch, Sequence, TransducerContextPrefixBeamStream,  # noqa: F401
+                                        TransducerPrefixBeamStream, tdt_prefix_beam_search)
 from . import k2  # noqa: F401  (the k2 functions with k2's signatures: rnnt_type=, delay_penalty=)
 from .transducer import Transducer  # noqa: F401
 from .common import IGNORE_ID, add_blank, log_add  # noqa: F401
@@ -35,4 +35,5 @@ __all__ = ["rnnt_loss", "RNNTLoss", "CTC", "ctc_loss", "TransducerJoint", "joint
            "get_rnnt_prune_ranges", "do_rnnt_pruning", "rnnt_loss_pruned", "k2",
            "rnnt_tdt_loss", "TDTLoss", "rnnt_tdt_lattice", "joint_rnnt_tdt_loss", "tdt_greedy_search", "rnnt_tdt_forced_align",
            "tdt_prefix_beam_search", "CtcPrefixBeamStream", "ctc_prefix_beam_search_times",
-           "ContextGraph", "CtcContextPrefixBeamStream", "ctc_context_prefix_beam_search", "TransducerPrefixBeamStream"]
+           "ContextGraph", "CtcContextPrefixBeamStream", "ctc_context_prefix_beam_search", "TransducerPrefixBeamStream",
+           "TransducerContextPrefixBeamStream"]

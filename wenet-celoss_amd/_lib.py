@@ -188,6 +188,10 @@ SIGNATURES = {
     "wr_decoder_attach_beam_stream": (_i, [_vp, _i, _i, _i, _vp, _sz]),
     "wr_prefix_beam_search_chunk": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _vp]),
+    "wr_decoder_beam_context_stream_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "wr_decoder_attach_beam_context_stream": (_i, [_vp, _i, _i, _i, _vp, _sz]),
+    "wr_prefix_beam_search_context_chunk": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "wr_hotword_workspace_bytes": (_sz, [_vp, _vp, _i]),
     "wr_decoder_attach_hotword": (_i, [_vp, _vp, _i, _vp, _sz, _vp]),
     "wr_greedy_search_hotword": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),

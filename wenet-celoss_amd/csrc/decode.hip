@@ -189,6 +189,14 @@ struct DevState {
     int32_t *bs_base, *bs_F;      // [n_utt] absolute frame of the latest chunk's first frame / frames received (F_b)
     int32_t *bs_state;            // [n_utt] bit 1: the stream has had its final call
     const int32_t *bs_flags;      // [n_utt] this call: bit 0 reset the stream first, bit 1 final
+    // context-graph biasing in that search (wr_prefix_beam_search_context_chunk; bs_flags bit 2: export the stream finalised);
+    // null / 0 in every other search.  The table is the caller's, S states and A arcs
+    double *bctx_score;           // [n_utt, beam]           bonus of the entry
+    int32_t *bctx_state;          // [n_utt, beam]           graph state of the entry
+    int32_t *btags;               // [2, n_utt, beam, Lmax]  tag of each token of a hypothesis (slot 0, the seed: -1)
+    const int32_t *cg_begin, *cg_token, *cg_next, *cg_final;
+    const float *cg_score, *cg_escape;
+    int cg_S, cg_A;
 };
 
 struct GemmArgs {
@@ -1772,6 +1780,11 @@ __global__ void beam_init_kernel(DevState *s)
         s->bhyp_lens[(size_t)b * s->beam + j] = (j == 0) ? 1 : 0;
         s->bhyps[((size_t)b * s->beam + j) * s->Lmax] = s->blank;
         s->bhash[n] = hyp_hash_push(0ull, s->blank);
+        if (s->btags) {                            // a biased stream: at the root, no bonus, the seed's tag slot
+            s->bctx_state[(size_t)b * s->beam + j] = 0;
+            s->bctx_score[(size_t)b * s->beam + j] = 0.0;
+            s->btags[((size_t)b * s->beam + j) * s->Lmax] = -1;
+        }
         if (j == 0) {
             s->n_hyps[b] = 1;
             s->frame[b] = 0;
@@ -1959,6 +1972,46 @@ struct BeamUpdLds {
     int c_vbest[MC], e_vsrc[kMaxBeam], e_vapp[kMaxBeam];
 };
 
+// CTX (include/wr_api.h, "Context-graph biasing in the streaming transducer prefix beam search"): the record of the biased
+// instantiations, which alone carry these arrays in their LDS.  A candidate's graph state, bonus and the tag of the token it
+// appended; all members of a class agree on them (they are a function of the tokens), so the representative's are the
+// class's.  e_ctag: the tag a survivor appends.
+struct BeamCtxLds : BeamUpdLds {
+    double c_cscore[MC];
+    int c_cstate[MC], c_ctag[MC], e_ctag[kMaxBeam];
+};
+template <bool CTX>
+using BeamLds = std::conditional_t<CTX, BeamCtxLds, BeamUpdLds>;
+
+// next(state, token) of the context graph for an entry at `state` with bonus `score` that appends `tok`: the arc is found by
+// one binary search over the state's arcs (strictly increasing tokens).  Every CSR bound is clamped into [0, A], every
+// arc_next and the incoming state into [0, S) before it is used as an index.
+__device__ __forceinline__ void ctx_graph_next(const DevState &S, int state, double score, int tok, int *st_out, double *sc_out,
+                                               int *tag_out)
+{
+    const int ns = S.cg_S, na = S.cg_A;
+    state = state < 0 ? 0 : (state < ns ? state : ns - 1);
+    int lo = S.cg_begin[state], hi = S.cg_begin[state + 1];
+    lo = lo < 0 ? 0 : (lo < na ? lo : na);
+    hi = hi < lo ? lo : (hi < na ? hi : na);
+    const int end = hi;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (S.cg_token[mid] < tok) lo = mid + 1; else hi = mid;
+    }
+    if (lo < end && S.cg_token[lo] == tok) {
+        int nx = S.cg_next[lo];
+        nx = nx < 0 ? 0 : (nx < ns ? nx : ns - 1);
+        *st_out = nx;
+        *sc_out = score + (double)S.cg_score[lo];
+        *tag_out = (state == 0 ? 1 : 0) | (S.cg_final[nx] != 0 ? 2 : 0);
+    } else {
+        *st_out = 0;
+        *sc_out = score + (double)S.cg_escape[state];
+        *tag_out = 0;
+    }
+}
+
 // phase 2: class representative = the first candidate with the same token sequence (:130-142) -- and, WITH_FRAME, the same
 // frame c_t (c_t is not read otherwise)
 template <bool WITH_FRAME>
@@ -2033,16 +2086,20 @@ __device__ __forceinline__ void beam_fuse_scores(BeamUpdLds &L, int C, int tid)
 // not_appended(c_tok) says whether a candidate added no token to its base.  Returns the survivor count; the caller
 // synchronises before anyone reads e_*.  Called once per kernel: the count lives in s_keep, zeroed here behind the barrier.
 // TIMES: also the survivor's Viterbi score, and whose times it takes (e_vsrc, e_vapp).
-template <bool TIMES, typename F>
-__device__ __forceinline__ int beam_rank_prune(const DevState &S, BeamUpdLds &L, int32_t *__restrict__ hl2, int b, int C, int tid, F &&not_appended)
+// CTX (implies TIMES): the rank is by total = fused score + bonus, one float64 add; the stored score stays the fused one, and
+// the survivor's graph state, bonus and the tag it appends (e_ctag) are the representative's.
+template <bool TIMES, bool CTX = false, typename F>
+__device__ __forceinline__ int beam_rank_prune(const DevState &S, BeamLds<CTX> &L, int32_t *__restrict__ hl2, int b, int C, int tid, F &&not_appended)
 {
+    static_assert(!CTX || TIMES, "the biased search is a streaming search");
     __shared__ int s_keep;
     const int beam = S.beam;
     if (tid == 0) s_keep = 0;
     for (int p = tid; p < C * C; p += kBeamUpdThreads) {
         const int i = p / C, f = p - i * C;
         if (L.c_rep[i] != i || L.c_rep[f] != f) continue;
-        const double me = L.f_score[i], ot = L.f_score[f];
+        double me = L.f_score[i], ot = L.f_score[f];
+        if constexpr (CTX) { me += L.c_cscore[i]; ot += L.c_cscore[f]; }
         if (ot > me || (ot == me && f < i)) atomicAdd(&L.c_rank[i], 1);
     }
     __syncthreads();
@@ -2068,6 +2125,11 @@ __device__ __forceinline__ int beam_rank_prune(const DevState &S, BeamUpdLds &L,
             L.e_vapp[tid] = !not_appended(L.c_tok[vb]);
             S.bvscores[(size_t)b * beam + tid] = L.c_vscore[f];
         }
+        if constexpr (CTX) {
+            S.bctx_state[(size_t)b * beam + tid] = L.c_cstate[f];
+            S.bctx_score[(size_t)b * beam + tid] = L.c_cscore[f];
+            L.e_ctag[tid] = L.c_ctag[f];
+        }
     }
     return keep;
 }
@@ -2075,9 +2137,13 @@ __device__ __forceinline__ int beam_rank_prune(const DevState &S, BeamUpdLds &L,
 // phase 5: the pruned beam -- hypotheses into the other buffer, (survivor, position) pairs in flight together.
 // TIMES: and each survivor's times (tm -> tm2, laid out like the hypotheses) from the base of its class's Viterbi-best
 // member, which need not be e_src; a member that appended a token appends `frame`, the frame it was expanded at.
-template <bool TIMES>
-__device__ __forceinline__ void beam_move_hyps(const BeamUpdLds &L, const int32_t *__restrict__ hy, int32_t *__restrict__ hy2, int Lmax, int keep, int tid,
-                                               const int32_t *__restrict__ tm = nullptr, int32_t *__restrict__ tm2 = nullptr, int frame = 0)
+// CTX: and each survivor's tags (tg -> tg2, laid out likewise) from e_src, the representative's base -- the tags are a function
+// of the tokens, so they travel with the hypothesis, not with the Viterbi-best member; a survivor that appended a token
+// appends e_ctag.
+template <bool TIMES, bool CTX = false>
+__device__ __forceinline__ void beam_move_hyps(const BeamLds<CTX> &L, const int32_t *__restrict__ hy, int32_t *__restrict__ hy2, int Lmax, int keep, int tid,
+                                               const int32_t *__restrict__ tm = nullptr, int32_t *__restrict__ tm2 = nullptr, int frame = 0,
+                                               const int32_t *__restrict__ tg = nullptr, int32_t *__restrict__ tg2 = nullptr)
 {
     constexpr int NT = kBeamUpdThreads;
     int maxlb = 0;
@@ -2113,6 +2179,16 @@ __device__ __forceinline__ void beam_move_hyps(const BeamUpdLds &L, const int32_
         if (tid < keep) {
             const int lv = L.e_lb[L.e_vsrc[tid]];
             if (L.e_vapp[tid] && lv < Lmax) tm2[(size_t)tid * Lmax + lv] = frame;
+        }
+    }
+    if constexpr (CTX) {
+        for (int i = tid; i < keep * maxlb; i += NT) {
+            const int e = i / maxlb, q = i - e * maxlb;
+            if (q < L.e_lb[L.e_src[e]]) tg2[(size_t)e * Lmax + q] = tg[(size_t)L.e_src[e] * Lmax + q];
+        }
+        if (tid < keep) {
+            const int lb = L.e_lb[L.e_src[tid]];
+            if (!L.e_blank[tid] && lb < Lmax) tg2[(size_t)tid * Lmax + lb] = L.e_ctag[tid];
         }
     }
 }
@@ -2238,10 +2314,11 @@ __device__ __forceinline__ void beam_move_predictor(const DevState &S, const Bea
 
 // TIMES: the streaming form (wr_prefix_beam_search_chunk).  The frames of this chunk are T_b = F_b - base_b, frame[b] counts
 // from the chunk's first frame, and every candidate carries a Viterbi score and its class the times of its best member.
-template <bool TIMES>
+// CTX: the biased form of it (wr_prefix_beam_search_context_chunk): a candidate that appends a token walks the context graph.
+template <bool TIMES, bool CTX = false>
 __global__ __launch_bounds__(kBeamUpdThreads) void beam_update_kernel(DevState *sp)
 {
-    __shared__ BeamUpdLds L;
+    __shared__ BeamLds<CTX> L;
     WR_STAMP_DECL;
     WR_STAMP_RT(7);
     WR_STAMP(0);
@@ -2279,6 +2356,14 @@ __global__ __launch_bounds__(kBeamUpdThreads) void beam_update_kernel(DevState *
         L.c_hash[tid] = (tok != S.blank) ? hyp_hash_push(hh, tok) : hh;
         L.c_rep[tid] = tid;
         L.c_rank[tid] = 0;
+        if constexpr (CTX) {                       // a blank copies the entry's fields, a label takes next(state, token)
+            int cst = S.bctx_state[(size_t)b * beam + j], ctag = 0;
+            double csc = S.bctx_score[(size_t)b * beam + j];
+            if (tok != S.blank) ctx_graph_next(S, cst, csc, tok, &cst, &csc, &ctag);
+            L.c_cstate[tid] = cst;
+            L.c_cscore[tid] = csc;
+            L.c_ctag[tid] = ctag;
+        }
     }
     __syncthreads();
     WR_STAMP(1);                                   // candidates built
@@ -2286,10 +2371,15 @@ __global__ __launch_bounds__(kBeamUpdThreads) void beam_update_kernel(DevState *
     WR_STAMP(2);                                   // classes known
     beam_fuse_scores<TIMES>(L, C, tid);
     WR_STAMP(9);                                   // duplicates' scores summed
-    const int keep = beam_rank_prune<TIMES>(S, L, hl2, b, C, tid, [&](int tok) { return tok == S.blank; });
+    const int keep = beam_rank_prune<TIMES, CTX>(S, L, hl2, b, C, tid, [&](int tok) { return tok == S.blank; });
     __syncthreads();
     WR_STAMP(3);                                   // fused, ranked, pruned
-    if (TIMES)
+    if constexpr (CTX)
+        beam_move_hyps<true, true>(L, hy, hy2, S.Lmax, keep, tid, S.btimes + sel * hstride + (size_t)b * beam * S.Lmax,
+                                   S.btimes + (1 - sel) * hstride + (size_t)b * beam * S.Lmax, S.bs_base[b] + fr,
+                                   S.btags + sel * hstride + (size_t)b * beam * S.Lmax,
+                                   S.btags + (1 - sel) * hstride + (size_t)b * beam * S.Lmax);
+    else if (TIMES)
         beam_move_hyps<true>(L, hy, hy2, S.Lmax, keep, tid, S.btimes + sel * hstride + (size_t)b * beam * S.Lmax,
                              S.btimes + (1 - sel) * hstride + (size_t)b * beam * S.Lmax, S.bs_base[b] + fr);
     else
@@ -2432,8 +2522,9 @@ __global__ __launch_bounds__(kTopkThreads) void tdt_beam_topk_kernel(DevState *s
 // kTdtStream, a step -- arcs are clamped to T only once the stream has had its final call; kTdtFinal, what a final call does
 // before its first step -- nothing is expanded, every frame beyond T is clamped to T, and the beam is fused and re-sorted.
 enum TdtUpdateMode { kTdtWhole = 0, kTdtStream = 1, kTdtFinal = 2 };
-template <int MODE>
-__device__ __forceinline__ void tdt_beam_update(const DevState &S, BeamUpdLds &L, int b)
+// CTX: the biased form of the two streaming modes; a label arc walks the context graph once, whatever its duration.
+template <int MODE, bool CTX = false>
+__device__ __forceinline__ void tdt_beam_update(const DevState &S, BeamLds<CTX> &L, int b)
 {
     constexpr bool TIMES = MODE != kTdtWhole;
     __shared__ int c_t[BeamUpdLds::MC], e_t[kMaxBeam], p_t[kMaxBeam], p_off[kMaxBeam + 1], s_nact, s_fnext;
@@ -2504,11 +2595,19 @@ __device__ __forceinline__ void tdt_beam_update(const DevState &S, BeamUpdLds &L
         L.c_hash[tid] = tok >= 0 ? hyp_hash_push(hh, tok) : hh;
         L.c_rep[tid] = tid;
         L.c_rank[tid] = 0;
+        if constexpr (CTX) {                       // a waiting entry and a blank arc copy the entry's fields
+            int cst = S.bctx_state[(size_t)b * beam + e], ctag = 0;
+            double csc = S.bctx_score[(size_t)b * beam + e];
+            if (tok >= 0) ctx_graph_next(S, cst, csc, tok, &cst, &csc, &ctag);
+            L.c_cstate[tid] = cst;
+            L.c_cscore[tid] = csc;
+            L.c_ctag[tid] = ctag;
+        }
     }
     __syncthreads();
     beam_find_classes<true>(L, c_t, hy, S.Lmax, C, tid);
     beam_fuse_scores<TIMES>(L, C, tid);
-    const int keep = beam_rank_prune<TIMES>(S, L, hl2, b, C, tid, [](int tok) { return tok < 0; });
+    const int keep = beam_rank_prune<TIMES, CTX>(S, L, hl2, b, C, tid, [](int tok) { return tok < 0; });
     if (tid < keep) e_t[tid] = c_t[L.order[tid]];
     __syncthreads();
     if (tid == 0) {
@@ -2516,7 +2615,12 @@ __device__ __forceinline__ void tdt_beam_update(const DevState &S, BeamUpdLds &L
         for (int e = 1; e < keep; ++e) fn = e_t[e] < fn ? e_t[e] : fn;
         s_fnext = fn;
     }
-    if (TIMES)
+    if constexpr (CTX)
+        beam_move_hyps<true, true>(L, hy, hy2, S.Lmax, keep, tid, S.btimes + sel * hstride + (size_t)b * beam * S.Lmax,
+                                   S.btimes + (1 - sel) * hstride + (size_t)b * beam * S.Lmax, S.bs_base[b] + fr,
+                                   S.btags + sel * hstride + (size_t)b * beam * S.Lmax,
+                                   S.btags + (1 - sel) * hstride + (size_t)b * beam * S.Lmax);
+    else if (TIMES)
         beam_move_hyps<true>(L, hy, hy2, S.Lmax, keep, tid, S.btimes + sel * hstride + (size_t)b * beam * S.Lmax,
                              S.btimes + (1 - sel) * hstride + (size_t)b * beam * S.Lmax, S.bs_base[b] + fr);
     else
@@ -2545,12 +2649,12 @@ __device__ __forceinline__ void tdt_beam_update(const DevState &S, BeamUpdLds &L
     }
 }
 
-template <bool TIMES>
+template <bool TIMES, bool CTX = false>
 __global__ __launch_bounds__(kBeamUpdThreads) void tdt_beam_update_kernel(DevState *sp)
 {
-    __shared__ BeamUpdLds L;
+    __shared__ BeamLds<CTX> L;
     const DevState S = *sp;
-    tdt_beam_update<TIMES ? kTdtStream : kTdtWhole>(S, L, blockIdx.x);
+    tdt_beam_update<TIMES ? kTdtStream : kTdtWhole, CTX>(S, L, blockIdx.x);
 }
 
 // The begin of a chunk call (wr_prefix_beam_search_chunk), one workgroup per stream, after beam_init_kernel has started the
@@ -2559,14 +2663,16 @@ __global__ __launch_bounds__(kBeamUpdThreads) void tdt_beam_update_kernel(DevSta
 // chunk's first frame, are moved to the new base; a reset starts the seed's Viterbi score and times slot; a final call of a
 // token-and-duration stream clamps, fuses and re-sorts (tdt_beam_update<kTdtFinal>); then the lanes at the earliest frame
 // that have a frame of the chunk to decode are active, and active_count[0] counts the streams with such a lane.
-template <bool TDT>
+// CTX: the biased streams; flag bit 2 concerns the export alone and is masked here (beam_init_kernel has seeded the graph
+// state, the bonus and the tag slot of a stream that is reset).
+template <bool TDT, bool CTX = false>
 __global__ __launch_bounds__(kBeamUpdThreads) void beam_chunk_begin_kernel(DevState *sp)
 {
-    __shared__ BeamUpdLds L;
+    __shared__ BeamLds<CTX> L;
     const DevState S = *sp;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int beam = S.beam;
-    const int flags = S.bs_flags[b];
+    const int flags = CTX ? S.bs_flags[b] & 3 : S.bs_flags[b];
     const bool reset = flags & 1;
     int len = S.enc_lens[b];
     len = len > 0 ? len : 0;
@@ -2591,7 +2697,7 @@ __global__ __launch_bounds__(kBeamUpdThreads) void beam_chunk_begin_kernel(DevSt
     }
     if (TDT && (flags & 2)) {
         __syncthreads();                           // the state written above is read through global memory
-        tdt_beam_update<kTdtFinal>(S, L, b);
+        tdt_beam_update<kTdtFinal, CTX>(S, L, b);
         return;
     }
     if (tid < beam) S.lane_active[b * beam + tid] = tid < N && lt == fr && lt < len;
@@ -2645,6 +2751,69 @@ __global__ void beam_stream_export_kernel(DevState *s, int32_t *hyps_out, int32_
     if (tid == 0) n_out[b] = N;
 }
 
+// the same for the biased streaming search: beside the above the pure fused score, the bonus, the tags and the graph state of
+// every hypothesis; scores = trans_scores + context_scores, the add of the prune.  A stream flagged bit 2 is exported "as if
+// it ended here": an entry away from the root gains (double)escape[state] in the exported bonus and the exported list is
+// sorted again, stable and descending, by the new totals.  The state block is only read.
+__global__ void beam_context_export_kernel(DevState *s, int32_t *hyps_out, int32_t *times_out, int32_t *lens_out, double *scores_out,
+                                           double *vscores_out, int32_t *n_out, double *trans_out, double *ctx_out, int32_t *tags_out,
+                                           int32_t *states_out)
+{
+    __shared__ double s_ctx[kMaxBeam], s_tot[kMaxBeam];
+    __shared__ int s_row[kMaxBeam];                // the exported row of entry e
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int beam = s->beam;
+    const int sel = s->hyp_sel[b];
+    const size_t hstride = (size_t)s->n_utt * beam * s->Lmax;
+    const int32_t *hy = s->bhyps + sel * hstride + (size_t)b * beam * s->Lmax;
+    const int32_t *tm = s->btimes + sel * hstride + (size_t)b * beam * s->Lmax;
+    const int32_t *tg = s->btags + sel * hstride + (size_t)b * beam * s->Lmax;
+    const int32_t *hl = s->bhyp_lens + (size_t)sel * s->n_utt * beam + (size_t)b * beam;
+    const int N = s->n_hyps[b];
+    const bool fin = s->bs_flags[b] & 4;
+    if (tid < beam) {
+        double cx = 0.0, tot = -__builtin_huge_val();
+        if (tid < N) {
+            int st = s->bctx_state[(size_t)b * beam + tid];
+            st = st < 0 ? 0 : (st < s->cg_S ? st : s->cg_S - 1);
+            cx = s->bctx_score[(size_t)b * beam + tid];
+            if (fin && st != 0) cx += (double)s->cg_escape[st];
+            tot = s->bscores[(size_t)b * beam + tid] + cx;
+        }
+        s_ctx[tid] = cx;
+        s_tot[tid] = tot;
+    }
+    __syncthreads();
+    if (tid < beam) {
+        int r = tid;
+        if (fin && tid < N) {
+            r = 0;
+            for (int f = 0; f < N; ++f) r += (s_tot[f] > s_tot[tid] || (s_tot[f] == s_tot[tid] && f < tid)) ? 1 : 0;
+        }
+        s_row[tid] = r;
+    }
+    __syncthreads();
+    for (int i = tid; i < beam * s->Lmax; i += blockDim.x) {
+        const int e = i / s->Lmax, q = i % s->Lmax;
+        const bool in = e < N && q < hl[e];
+        const size_t o = ((size_t)b * beam + s_row[e]) * s->Lmax + q;
+        hyps_out[o] = in ? hy[(size_t)e * s->Lmax + q] : -1;
+        times_out[o] = in ? tm[(size_t)e * s->Lmax + q] : -1;
+        tags_out[o] = in ? tg[(size_t)e * s->Lmax + q] : -1;
+    }
+    if (tid < beam) {
+        const size_t o = (size_t)b * beam + s_row[tid];
+        const bool in = tid < N;
+        lens_out[o] = in ? hl[tid] : 0;
+        scores_out[o] = s_tot[tid];
+        trans_out[o] = in ? s->bscores[(size_t)b * beam + tid] : -__builtin_huge_val();
+        vscores_out[o] = in ? s->bvscores[(size_t)b * beam + tid] : -__builtin_huge_val();
+        ctx_out[o] = s_ctx[tid];
+        states_out[o] = in ? s->bctx_state[(size_t)b * beam + tid] : 0;
+    }
+    if (tid == 0) n_out[b] = N;
+}
+
 }  // namespace
 }  // namespace wr
 
@@ -2661,8 +2830,12 @@ struct GraphSlot {
 // predictor state lives in the handle's workspace, so the streams are live only while wr_decoder::stream_lanes says so
 // (kBeamStreamLanes: the last search on the handle was a chunk call).
 constexpr int kBeamStreamLanes = -2;
+constexpr int kBeamCtxStreamLanes = -3;       // the same for the biased form: neither form continues the other's streams
 struct BeamStreams {
     bool attached = false;
+    bool ctx = false;             // attached by wr_decoder_attach_beam_context_stream: the block also holds the three below
+    double *ctx_score = nullptr;
+    int32_t *ctx_state = nullptr, *btags = nullptr;
     int n = 0, beam = 0, max_frames = 0;
     int32_t *bhyps = nullptr, *btimes = nullptr, *bhyp_lens = nullptr, *base = nullptr, *F = nullptr, *state = nullptr,
             *flags = nullptr;                      // device, carved from the caller's block
@@ -2704,6 +2877,7 @@ struct wr_decoder {
     float *hw_biasT = nullptr;    // [Pp][NLp]
     // streaming prefix beam search (wr_decoder_attach_beam_stream)
     GraphSlot beam_stream, beam_tdt_stream;   // the streaming forms of `beam` / `beam_tdt`, keyed likewise
+    GraphSlot beam_ctx_stream, beam_tdt_ctx_stream;   // and their biased forms (wr_prefix_beam_search_context_chunk)
     BeamStreams bs;
     bool use_graph = true;        // greedy micro-steps replayed from a hipGraph (default on)
     bool use_graph_beam = false;  // beam frames: plain launches measured faster (no host polling to amortise), default off
@@ -2720,6 +2894,8 @@ void for_each_graph(wr_decoder *h, F f)
     f(h->beam_tdt);
     f(h->beam_stream);
     f(h->beam_tdt_stream);
+    f(h->beam_ctx_stream);
+    f(h->beam_tdt_ctx_stream);
     f(h->hotword);
 }
 
@@ -3210,8 +3386,8 @@ int tdt_micro_step(wr_decoder *h, int n_lanes, hipStream_t st, int look)
     return launch("tdt_resolve_kernel", tdt_resolve_kernel, dim3(n_lanes), dim3(256), 0, st, h->dev, look);
 }
 
-// `times`: the streaming forms of the update kernels (wr_prefix_beam_search_chunk)
-int beam_frame(wr_decoder *h, int n_lanes, int n_utt, hipStream_t st, bool times = false)
+// `times`: the streaming forms of the update kernels (wr_prefix_beam_search_chunk); `ctx` (with `times`): their biased forms
+int beam_frame(wr_decoder *h, int n_lanes, int n_utt, hipStream_t st, bool times = false, bool ctx = false)
 {
     WR_TRY(launch_predictor_and_joint(h, n_lanes, st));
     const int V = h->d.V;                           // <= 16384 (check_weights)
@@ -3219,12 +3395,13 @@ int beam_frame(wr_decoder *h, int n_lanes, int n_utt, hipStream_t st, bool times
     WR_TRY(with_int<4, 10, 32>(per_thread, [&](auto n) {
         return launch("beam_topk_kernel", beam_topk_kernel<decltype(n)::value>, dim3(n_lanes), dim3(kTopkThreads), 0, st, h->dev);
     }));
+    if (ctx) return launch("beam_update_kernel", beam_update_kernel<true, true>, dim3(n_utt), dim3(kBeamUpdThreads), 0, st, h->dev);
     if (times) return launch("beam_update_kernel", beam_update_kernel<true>, dim3(n_utt), dim3(kBeamUpdThreads), 0, st, h->dev);
     return launch("beam_update_kernel", beam_update_kernel<false>, dim3(n_utt), dim3(kBeamUpdThreads), 0, st, h->dev);
 }
 
 // one step of the token-and-duration beam search: the lane GEMMs take each lane's frame from lane_t, as in the greedy search
-int tdt_beam_step(wr_decoder *h, int n_lanes, int n_utt, hipStream_t st, bool times = false)
+int tdt_beam_step(wr_decoder *h, int n_lanes, int n_utt, hipStream_t st, bool times = false, bool ctx = false)
 {
     WR_TRY(launch_predictor_and_joint(h, n_lanes, st));
     const int V = h->d.V;                           // <= 16384 (check_weights)
@@ -3233,6 +3410,9 @@ int tdt_beam_step(wr_decoder *h, int n_lanes, int n_utt, hipStream_t st, bool ti
         return launch("tdt_beam_topk_kernel", tdt_beam_topk_kernel<decltype(n)::value>, dim3(n_lanes), dim3(kTopkThreads), 0, st,
                       h->dev);
     }));
+    if (ctx)
+        return launch("tdt_beam_update_kernel", tdt_beam_update_kernel<true, true>, dim3(n_utt), dim3(kBeamUpdThreads), 0, st,
+                      h->dev);
     if (times)
         return launch("tdt_beam_update_kernel", tdt_beam_update_kernel<true>, dim3(n_utt), dim3(kBeamUpdThreads), 0, st, h->dev);
     return launch("tdt_beam_update_kernel", tdt_beam_update_kernel<false>, dim3(n_utt), dim3(kBeamUpdThreads), 0, st, h->dev);
@@ -3344,10 +3524,10 @@ unsigned long long pack_durations(const TdtDur &dur)
 
 // The steps of the plain prefix beam searches (`what` names the entry point in the error texts; `times`: the streaming
 // form): the fixed count of T frames, kStepsPerGraph at a time, replayed from a graph if the handle says so.
-int beam_plain_steps(wr_decoder *h, hipStream_t st, const char *what, int NLn, int B, int T, int beam, bool times)
+int beam_plain_steps(wr_decoder *h, hipStream_t st, const char *what, int NLn, int B, int T, int beam, bool times, bool ctx = false)
 {
-    GraphSlot &slot = times ? h->beam_stream : h->beam;
-    const auto frame = [&] { return beam_frame(h, NLn, B, st, times); };
+    GraphSlot &slot = ctx ? h->beam_ctx_stream : times ? h->beam_stream : h->beam;
+    const auto frame = [&] { return beam_frame(h, NLn, B, st, times, ctx); };
     if (h->use_graph_beam) WR_TRY(ensure_graph(slot, NLn * 1000 + beam, st, frame));
     for (int f = 0; f < T; f += kStepsPerGraph) {
         if (h->use_graph_beam) {
@@ -3362,11 +3542,12 @@ int beam_plain_steps(wr_decoder *h, hipStream_t st, const char *what, int NLn, i
 
 // The steps of the token-and-duration prefix beam searches: until no utterance has an entry below its frame count.  Every
 // step moves the earliest frame of every running utterance on, so T steps always suffice.
-int beam_tdt_steps(wr_decoder *h, hipStream_t st, const char *what, int NLn, int B, int T, int beam, bool times)
+int beam_tdt_steps(wr_decoder *h, hipStream_t st, const char *what, int NLn, int B, int T, int beam, bool times, bool ctx = false)
 {
     return run_until_idle(
-        h, st, what, NLn * 1000 + beam, (long)T + 1, "", [&]() -> GraphSlot & { return times ? h->beam_tdt_stream : h->beam_tdt; },
-        [&] { return tdt_beam_step(h, NLn, B, st, times); }, [] {});
+        h, st, what, NLn * 1000 + beam, (long)T + 1, "",
+        [&]() -> GraphSlot & { return ctx ? h->beam_tdt_ctx_stream : times ? h->beam_tdt_stream : h->beam_tdt; },
+        [&] { return tdt_beam_step(h, NLn, B, st, times, ctx); }, [] {});
 }
 
 // what a token-and-duration search adds to a greedy run
@@ -3533,7 +3714,8 @@ extern "C" int wr_prefix_beam_search(wr_decoder *h, const float *enc_out_d, cons
 namespace {
 
 // where the caller's block puts things: one pass for the size (null base) and for the pointers
-size_t beam_stream_carve(int n, int beam, int max_frames, char *base, BeamStreams *p)
+// (`ctx`: the biased form's block -- the plain block's contents, then the bonus, the graph state and the tags of every entry)
+size_t beam_stream_carve(int n, int beam, int max_frames, char *base, BeamStreams *p, bool ctx = false)
 {
     Carver c{base, 0};
     const size_t Lcap = (size_t)max_frames + 1, nb = (size_t)n * beam;
@@ -3543,6 +3725,11 @@ size_t beam_stream_carve(int n, int beam, int max_frames, char *base, BeamStream
     p->bscores = c.take<double>(nb);
     p->bvscores = c.take<double>(nb);
     p->base = c.take<int32_t>(n); p->F = c.take<int32_t>(n); p->state = c.take<int32_t>(n); p->flags = c.take<int32_t>(n);
+    if (ctx) {
+        p->ctx_score = c.take<double>(nb);
+        p->ctx_state = c.take<int32_t>(nb);
+        p->btags = c.take<int32_t>(2 * nb * Lcap);
+    }
     return align_up(c.off, 256);
 }
 
@@ -3567,12 +3754,16 @@ struct BeamStreamState {
         const BeamStreams &bs = h->bs;
         s.bhyps = bs.bhyps; s.btimes = bs.btimes; s.bhyp_lens = bs.bhyp_lens; s.bscores = bs.bscores; s.bvscores = bs.bvscores;
         s.bs_base = bs.base; s.bs_F = bs.F; s.bs_state = bs.state; s.bs_flags = bs.flags;
+        s.bctx_score = bs.ctx_score; s.bctx_state = bs.ctx_state; s.btags = bs.btags;      // null unless the block is a biased one
         s.Lmax = bs.max_frames + 1;
     }
     ~BeamStreamState()
     {
         s.bhyps = saved.bhyps; s.btimes = nullptr; s.bhyp_lens = saved.bhyp_lens; s.bscores = saved.bscores; s.bvscores = nullptr;
         s.bs_base = s.bs_F = s.bs_state = nullptr; s.bs_flags = nullptr;
+        s.bctx_score = nullptr; s.bctx_state = nullptr; s.btags = nullptr;
+        s.cg_begin = s.cg_token = s.cg_next = s.cg_final = nullptr; s.cg_score = s.cg_escape = nullptr;
+        s.cg_S = s.cg_A = 0;
         s.Lmax = saved.Lmax;
     }
 };
@@ -3580,21 +3771,22 @@ struct BeamStreamState {
 }  // namespace
 
 // decode_stream.hpp: the size behind wr_decoder_beam_stream_workspace_bytes (0 for sizes no handle can have)
-size_t wr::beam_stream_bytes(int max_streams, int beam, int max_frames)
+size_t wr::beam_stream_bytes(int max_streams, int beam, int max_frames, bool ctx)
 {
     if (max_streams < 1 || beam < 1 || beam > kMaxBeam || max_frames < 1 || max_frames >= (1 << 30)) return 0;
     BeamStreams p;
-    return beam_stream_carve(max_streams, beam, max_frames, nullptr, &p);
+    return beam_stream_carve(max_streams, beam, max_frames, nullptr, &p, ctx);
 }
 
 // decode_stream.hpp: wr_decoder_attach_beam_stream
-int wr::beam_stream_attach(wr_decoder *h, int max_streams, int beam, int max_frames, void *workspace_d, size_t workspace_bytes)
+int wr::beam_stream_attach(wr_decoder *h, int max_streams, int beam, int max_frames, void *workspace_d, size_t workspace_bytes,
+                           bool ctx)
 {
-    const char *what = "decoder_attach_beam_stream";
+    const char *what = ctx ? "decoder_attach_beam_context_stream" : "decoder_attach_beam_stream";
     WR_TRY(beam_stream_check(what, h, max_streams, beam, max_frames));
     WR_REQUIRE(workspace_d != nullptr, WR_EINVAL, "%s: null workspace", what);
     BeamStreams p;                                // the handle is written only once everything here has succeeded
-    const size_t need = beam_stream_carve(max_streams, beam, max_frames, static_cast<char *>(workspace_d), &p);
+    const size_t need = beam_stream_carve(max_streams, beam, max_frames, static_cast<char *>(workspace_d), &p, ctx);
     WR_REQUIRE(workspace_bytes >= need, WR_EWORKSPACE, "%s: workspace %zu < required %zu", what, workspace_bytes, need);
     if (hipHostMalloc(reinterpret_cast<void **>(&p.h_flags), (size_t)kStageSlots * max_streams * sizeof(int32_t),
                       hipHostMallocDefault) != hipSuccess) {
@@ -3604,11 +3796,12 @@ int wr::beam_stream_attach(wr_decoder *h, int max_streams, int beam, int max_fra
     if (h->work) (void)hipStreamSynchronize(h->work);       // no copy still reads the flags of the block being replaced
     if (h->bs.h_flags) (void)hipHostFree(h->bs.h_flags);
     p.attached = true;
+    p.ctx = ctx;
     p.n = max_streams; p.beam = beam; p.max_frames = max_frames;
     p.phase.assign(max_streams, 0);
     p.frames.assign(max_streams, 0);
     h->bs = p;
-    if (h->stream_lanes == kBeamStreamLanes) h->stream_lanes = -1;
+    if (h->stream_lanes == kBeamStreamLanes || h->stream_lanes == kBeamCtxStreamLanes) h->stream_lanes = -1;
     return WR_OK;
 }
 
@@ -3618,12 +3811,14 @@ int wr::beam_stream_attach(wr_decoder *h, int max_streams, int beam, int max_fra
 int wr::beam_stream_chunk_body(wr_decoder *h, const float *enc_chunk_d, const int32_t *chunk_lens_d, const float *ctc_logp_chunk_d,
                                int B, int T, int beam, float ctc_weight, float transducer_weight, int blank, const TdtDur &dur,
                                const int32_t *flags, int32_t *hyps_d, int32_t *times_d, int32_t *hyp_lens_d, double *scores_d,
-                               double *vscores_d, int32_t *n_hyps_d, void *stream)
+                               double *vscores_d, int32_t *n_hyps_d, void *stream, const BeamCtxArgs *cx)
 {
-    const char *what = "prefix_beam_search_chunk";
+    const char *what = cx ? "prefix_beam_search_context_chunk" : "prefix_beam_search_chunk";
     const bool tdt = dur.D > 0;
+    const int my_lanes = cx ? kBeamCtxStreamLanes : kBeamStreamLanes;
     BeamStreams &bs = h->bs;
-    WR_REQUIRE(bs.attached, WR_EINVAL, "%s: no stream state is attached (wr_decoder_attach_beam_stream comes first)", what);
+    WR_REQUIRE(bs.attached && bs.ctx == (cx != nullptr), WR_EINVAL, "%s: no stream state is attached (%s comes first)", what,
+               cx ? "wr_decoder_attach_beam_context_stream" : "wr_decoder_attach_beam_stream");
     WR_REQUIRE(B == bs.n && beam == bs.beam, WR_EINVAL, "%s: B=%d, beam=%d differ from the attached %d streams of beam %d", what,
                B, beam, bs.n, bs.beam);
     WR_REQUIRE(T > 0 && T <= h->Tmax, WR_EINVAL, "%s: T=%d exceeds the decoder's Tmax=%d", what, T, h->Tmax);
@@ -3642,14 +3837,15 @@ int wr::beam_stream_chunk_body(wr_decoder *h, const float *enc_chunk_d, const in
     }
     WR_REQUIRE(blank >= 0 && blank < V, WR_EINVAL, "%s: blank %d out of range [0,%d)", what, blank, V);
     // the streams: another search on the handle has overwritten the lanes' predictor slots
-    if (h->stream_lanes != kBeamStreamLanes) {
+    if (h->stream_lanes != my_lanes) {
         for (int &p : bs.phase) { bs.overwritten = bs.overwritten || p != 0; p = 0; }
     }
     const unsigned long long durs = tdt ? pack_durations(dur) : 0;
     bool continues = false;
     for (int b = 0; b < B; ++b) {
         const int f = flags ? flags[b] : 0;
-        WR_REQUIRE((f & ~3) == 0, WR_EINVAL, "%s: flags[%d]=%d has bits beyond reset (1) and final (2)", what, b, f);
+        WR_REQUIRE((f & ~(cx ? 7 : 3)) == 0, WR_EINVAL, "%s: flags[%d]=%d has bits beyond reset (1)%s final (2)%s", what, b, f,
+                   cx ? "," : " and", cx ? " and finalised export (4)" : "");
         if (f & 1) {
             WR_REQUIRE(T <= bs.max_frames, WR_EINVAL, "%s: stream %d: a chunk of %d frames exceeds max_frames=%d", what, b, T,
                        bs.max_frames);
@@ -3671,6 +3867,14 @@ int wr::beam_stream_chunk_body(wr_decoder *h, const float *enc_chunk_d, const in
     WR_REQUIRE(!continues || (bs.blank == blank && bs.D == dur.D && bs.durs == durs), WR_EINVAL,
                "%s: durations or blank changed in the middle of a stream (blank %d -> %d, D %d -> %d)", what, bs.blank, blank,
                bs.D, dur.D);
+    if (cx) {
+        WR_REQUIRE(cx->S >= 1 && cx->A >= 0, WR_EINVAL, "%s: a context graph of S=%d states and A=%d arcs (S >= 1, A >= 0)", what,
+                   cx->S, cx->A);
+        WR_REQUIRE(cx->arc_begin && cx->arc_token && cx->arc_next && cx->arc_score && cx->escape && cx->final, WR_EINVAL,
+                   "%s: null context-graph table pointer", what);
+        WR_REQUIRE(cx->S <= 65536 && cx->A <= 1048576, WR_EUNSUPPORTED,
+                   "%s: a context graph of S=%d states and A=%d arcs exceeds 65536 states / 1048576 arcs", what, cx->S, cx->A);
+    }
     // ---- nothing is refused below this line; the host's record of the streams follows the call
     for (int b = 0; b < B; ++b) {
         const int f = flags ? flags[b] : 0;
@@ -3688,6 +3892,10 @@ int wr::beam_stream_chunk_body(wr_decoder *h, const float *enc_chunk_d, const in
     s.n_utt = B; s.T = T; s.lanes_per_utt = beam; s.n_lanes = B * beam;
     s.beam = beam; s.ctc_weight = ctc_weight; s.tr_weight = transducer_weight; s.blank = blank;
     s.tdt_durs = durs; s.tdt_D = dur.D; s.hyp_frames = nullptr;
+    if (cx) {                                      // the table travels in the state block, never in a captured graph
+        s.cg_begin = cx->arc_begin; s.cg_token = cx->arc_token; s.cg_next = cx->arc_next; s.cg_score = cx->arc_score;
+        s.cg_escape = cx->escape; s.cg_final = cx->final; s.cg_S = cx->S; s.cg_A = cx->A;
+    }
     // the flags ride in the pinned slot of the state block's upload (upload_state waits for the slot's last copy, then
     // records the event behind both copies)
     const int slot = h->stage_next;
@@ -3704,17 +3912,32 @@ int wr::beam_stream_chunk_body(wr_decoder *h, const float *enc_chunk_d, const in
     const int NLn = B * beam;
     WR_TRY(launch_ep_all(h, st, (long)B * T, enc_chunk_d, s.ep_all));
     WR_TRY(launch("beam_init_kernel", beam_init_kernel, dim3(NLn), dim3(128), 0, st, h->dev));
-    if (tdt) {
-        WR_TRY(launch("beam_chunk_begin_kernel", beam_chunk_begin_kernel<true>, dim3(B), dim3(kBeamUpdThreads), 0, st, h->dev));
-        WR_TRY(beam_tdt_steps(h, st, what, NLn, B, T, beam, true));
+    if (cx) {
+        if (tdt) {
+            WR_TRY(launch("beam_chunk_begin_kernel", beam_chunk_begin_kernel<true, true>, dim3(B), dim3(kBeamUpdThreads), 0, st,
+                          h->dev));
+            WR_TRY(beam_tdt_steps(h, st, what, NLn, B, T, beam, true, true));
+        } else {
+            WR_TRY(launch("beam_chunk_begin_kernel", beam_chunk_begin_kernel<false, true>, dim3(B), dim3(kBeamUpdThreads), 0, st,
+                          h->dev));
+            WR_TRY(beam_plain_steps(h, st, what, NLn, B, T, beam, true, true));
+        }
+        WR_TRY(launch("beam_context_export_kernel", beam_context_export_kernel, dim3(B), dim3(256), 0, st, h->dev, hyps_d, times_d,
+                      hyp_lens_d, scores_d, vscores_d, n_hyps_d, cx->trans_scores, cx->context_scores, cx->tags,
+                      cx->context_states));
     } else {
-        WR_TRY(launch("beam_chunk_begin_kernel", beam_chunk_begin_kernel<false>, dim3(B), dim3(kBeamUpdThreads), 0, st, h->dev));
-        WR_TRY(beam_plain_steps(h, st, what, NLn, B, T, beam, true));
+        if (tdt) {
+            WR_TRY(launch("beam_chunk_begin_kernel", beam_chunk_begin_kernel<true>, dim3(B), dim3(kBeamUpdThreads), 0, st, h->dev));
+            WR_TRY(beam_tdt_steps(h, st, what, NLn, B, T, beam, true));
+        } else {
+            WR_TRY(launch("beam_chunk_begin_kernel", beam_chunk_begin_kernel<false>, dim3(B), dim3(kBeamUpdThreads), 0, st, h->dev));
+            WR_TRY(beam_plain_steps(h, st, what, NLn, B, T, beam, true));
+        }
+        WR_TRY(launch("beam_stream_export_kernel", beam_stream_export_kernel, dim3(B), dim3(256), 0, st, h->dev, hyps_d, times_d,
+                      hyp_lens_d, scores_d, vscores_d, n_hyps_d));
     }
-    WR_TRY(launch("beam_stream_export_kernel", beam_stream_export_kernel, dim3(B), dim3(256), 0, st, h->dev, hyps_d, times_d,
-                  hyp_lens_d, scores_d, vscores_d, n_hyps_d));
     scope.ok();
-    h->stream_lanes = kBeamStreamLanes;
+    h->stream_lanes = my_lanes;
     return WR_OK;
 }
 

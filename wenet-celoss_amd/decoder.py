@@ -266,6 +266,7 @@ class DeviceDecoder:
         _lib.check(rc, "wr_decoder_attach_beam_stream")
         self._beam_stream_ws = ws
         self.beam_stream = (n_streams, beam, max_frames)
+        self.beam_context_stream = None             # the handle holds one form's block at a time
 
     beam_stream = None
 
@@ -310,6 +311,66 @@ class DeviceDecoder:
         width = max(max(row) for row in hl)
         hyps, tm = hyps[:, :, :width].cpu().tolist(), tm[:, :, :width].cpu().tolist()
         return [[(hyps[b][e][:hl[b][e]], sc[b][e], vs[b][e], tm[b][e][1:hl[b][e]]) for e in range(nh[b])] for b in range(B)]
+
+    def attach_beam_context_stream(self, n_streams: int, beam: int, max_frames: int) -> None:
+        """`attach_beam_stream` for the biased streams of `prefix_beam_context_chunk`
+        (`wr_decoder_attach_beam_context_stream`).  Attaching one form replaces the other and ends every stream."""
+        n_streams, beam, max_frames = int(n_streams), int(beam), int(max_frames)
+        nbytes = self._lib.wr_decoder_beam_context_stream_workspace_bytes(self._h, n_streams, beam, max_frames)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self._lib.wr_decoder_attach_beam_context_stream(self._h, n_streams, beam, max_frames, _lib.ptr(ws), nbytes)
+        _lib.check(rc, "wr_decoder_attach_beam_context_stream")
+        self._beam_stream_ws = ws
+        self.beam_stream = None
+        self.beam_context_stream = (n_streams, beam, max_frames)
+
+    beam_context_stream = None
+
+    def prefix_beam_context_chunk(self, encoder_chunk: torch.Tensor, chunk_lens: torch.Tensor, beam_size: int, blank: int,
+                                  graph, ctc_logp: torch.Tensor = None, ctc_weight: float = 0.0,
+                                  transducer_weight: float = 1.0, durations=None, reset=False, final=False, finalize=False):
+        """`prefix_beam_chunk` with context-graph phrase biasing (`wr_prefix_beam_search_context_chunk`; the rule is in
+        include/wr_api.h, "Context-graph biasing in the streaming transducer prefix beam search").  `graph` is a
+        ContextGraph, the same from a stream's reset to its end.  `reset` / `final` / `finalize`: a bool for all streams or
+        one per stream; `finalize` exports the stream as if it ended here (a partial match gives its bonus back and the list
+        is sorted again) without changing it.  Per stream the current n-best, best first: [(tokens incl. the seed blank,
+        score, viterbi_score, times, trans_score, context_score, tags, context_state)] with score = trans_score +
+        context_score and one tag per token after the seed (bit 0: a phrase starts at it, bit 1: a phrase ends at it)."""
+        if self.beam_context_stream is None:
+            raise RuntimeError("DeviceDecoder.prefix_beam_context_chunk: call attach_beam_context_stream(n_streams, beam, "
+                               "max_frames) first")
+        enc = _f32(encoder_chunk)
+        ctc = None if ctc_logp is None else _f32(ctc_logp)
+        B, T, _ = enc.shape
+
+        def mask(x):
+            return [bool(x)] * B if isinstance(x, (bool, int)) else [bool(v) for v in x]
+
+        rs, fin, fz = mask(reset), mask(final), mask(finalize)
+        if len(rs) != B or len(fin) != B or len(fz) != B:
+            raise RuntimeError("DeviceDecoder.prefix_beam_context_chunk: reset / final / finalize masks must have one entry "
+                               f"per stream ({B})")
+        flags = (ctypes.c_int32 * B)(*[int(r) | (int(f) << 1) | (int(z) << 2) for r, f, z in zip(rs, fin, fz)])
+        lens = chunk_lens.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+        if lens.numel() != B:
+            raise RuntimeError(f"DeviceDecoder.prefix_beam_context_chunk: chunk_lens has {lens.numel()} elements for {B} streams")
+        cap = self.beam_context_stream[2] + 1
+        beam_size = int(beam_size)
+        i32, f64 = dict(dtype=torch.int32, device=self.device), dict(dtype=torch.float64, device=self.device)
+        hyps, tm, tg = (torch.empty(B, beam_size, cap, **i32) for _ in range(3))
+        hl, cs, nh = torch.empty(B, beam_size, **i32), torch.empty(B, beam_size, **i32), torch.empty(B, **i32)
+        sc, vs, ts, cx = (torch.empty(B, beam_size, **f64) for _ in range(4))
+        dur = (None, 0) if durations is None else (_durations_arg(durations), len(durations))
+        self._call("wr_prefix_beam_search_context_chunk", enc, lens, ctc, B, T, beam_size, float(ctc_weight),
+                   float(transducer_weight), int(blank), *dur, flags, hyps, tm, hl, sc, vs, nh, *graph.to(self.device),
+                   graph.n_states, graph.n_arcs, ts, cx, tg, cs)
+        hl, nh, cs = hl.cpu().tolist(), nh.cpu().tolist(), cs.cpu().tolist()
+        sc, vs, ts, cx = (t.cpu().tolist() for t in (sc, vs, ts, cx))
+        width = max(max(row) for row in hl)
+        hyps, tm, tg = (t[:, :, :width].cpu().tolist() for t in (hyps, tm, tg))
+        return [[(hyps[b][e][:hl[b][e]], sc[b][e], vs[b][e], tm[b][e][1:hl[b][e]], ts[b][e], cx[b][e], tg[b][e][1:hl[b][e]],
+                  cs[b][e]) for e in range(nh[b])] for b in range(B)]
 
     def predictor_step(self, tokens: torch.Tensor, cache_h: torch.Tensor, cache_c: torch.Tensor):
         """tokens (N,), cache (L, N, H) -> out (N, P), new_h, new_c (L, N, H)."""

@@ -98,6 +98,18 @@ class TransducerPrefixBeamStream:
             self._phase[int(b)] = 0
             self.frames[int(b)] = 0
 
+    # what the biased stream (TransducerContextPrefixBeamStream) does differently: the block it attaches and the call
+    def _attached(self, dec):
+        return dec.beam_stream
+
+    def _attach(self, dec, B):
+        dec.attach_beam_stream(B, self.beam_size, self.max_frames)
+
+    def _chunk(self, dec, encoder_out_chunk, ln, ctc_logp, reset, fin):
+        return dec.prefix_beam_chunk(encoder_out_chunk, ln, self.beam_size, self.model.blank, ctc_logp=ctc_logp,
+                                     ctc_weight=self.ctc_weight, transducer_weight=self.transducer_weight,
+                                     durations=self.durations, reset=reset, final=fin)
+
     def search(self, encoder_out_chunk: torch.Tensor, lens, final=False):
         from .greedy_search import _decoder_cache, expand_lens
         if encoder_out_chunk.dim() != 3:
@@ -130,8 +142,8 @@ class TransducerPrefixBeamStream:
                 raise RuntimeError("the decoder handle was rebuilt (weights changed or capacity grew) in the middle of a "
                                    "stream: call reset() first")
             self._phase = [0] * B                   # finished streams lived on the old handle too
-        if dec.beam_stream != (B, self.beam_size, self.max_frames) or dec is not self._dec:
-            dec.attach_beam_stream(B, self.beam_size, self.max_frames)
+        if self._attached(dec) != (B, self.beam_size, self.max_frames) or dec is not self._dec:
+            self._attach(dec, B)
         self._dec = dec
         ctc_logp = None
         if self._with_ctc:
@@ -139,9 +151,7 @@ class TransducerPrefixBeamStream:
                 ctc_logp = model.ctc.log_softmax(encoder_out_chunk)
         reset = [p == 0 for p in self._phase]
         try:
-            out = dec.prefix_beam_chunk(encoder_out_chunk, ln, self.beam_size, model.blank, ctc_logp=ctc_logp,
-                                        ctc_weight=self.ctc_weight, transducer_weight=self.transducer_weight,
-                                        durations=self.durations, reset=reset, final=fin)
+            out = self._chunk(dec, encoder_out_chunk, ln, ctc_logp, reset, fin)
         except RuntimeError:
             _decoder_cache(model).discard(dec)
             raise
@@ -153,6 +163,75 @@ class TransducerPrefixBeamStream:
                 if fin[b]:
                     self._phase[b] = 2
         return out
+
+
+class TransducerContextPrefixBeamStream(TransducerPrefixBeamStream):
+    """TransducerPrefixBeamStream with context-graph phrase biasing (`wr_prefix_beam_search_context_chunk`; the rule is in
+    include/wr_api.h, "Context-graph biasing in the streaming transducer prefix beam search"): every hypothesis walks
+    `context_graph` (a ContextGraph, fixed here for the life of the streams) and the beam is pruned by score plus bonus.
+
+    search(encoder_out_chunk, lens, final=False, finalize=None) returns per stream [(tokens incl. the seed blank, score,
+    viterbi_score, times, trans_score, context_score, tags, context_state)] best first, score = trans_score +
+    context_score, one tag per token after the seed (bit 0: a phrase starts at it, bit 1: a phrase ends at it).
+    `finalize` (a bool or one per stream) exports a stream as if it ended here: a partial match gives its bonus back and the
+    list is sorted again; the stream itself is not changed.  By default it follows `final`, and stays on for a stream that
+    has had its final chunk, so that a finished stream keeps being exported as it ended.  The record of the streams and the
+    refusals are TransducerPrefixBeamStream's."""
+
+    def __init__(self, model, n_streams: int, beam_size: int, max_frames: int, chunk_frames: int = 64, context_graph=None,
+                 ctc_weight: float = None, transducer_weight: float = None):
+        from ..context_graph import ContextGraph
+        super().__init__(model, n_streams, beam_size, max_frames, chunk_frames, ctc_weight, transducer_weight)
+        if not isinstance(context_graph, ContextGraph):
+            raise ValueError("TransducerContextPrefixBeamStream: context_graph must be a ContextGraph")
+        if context_graph.blank != int(model.blank):
+            raise ValueError(f"TransducerContextPrefixBeamStream: the graph was built for blank {context_graph.blank}, "
+                             f"the model's is {model.blank}")
+        vocab = int(model.vocab_size)
+        worst = int(context_graph.arc_token.max()) if context_graph.n_arcs else -1
+        if worst >= vocab:
+            raise ValueError(f"TransducerContextPrefixBeamStream: phrase token {worst} lies outside the token vocabulary "
+                             f"[0, {vocab})")
+        self.context_graph = context_graph
+
+    def _attached(self, dec):
+        return dec.beam_context_stream
+
+    def _attach(self, dec, B):
+        dec.attach_beam_context_stream(B, self.beam_size, self.max_frames)
+
+    def _chunk(self, dec, encoder_out_chunk, ln, ctc_logp, reset, fin):
+        return dec.prefix_beam_context_chunk(encoder_out_chunk, ln, self.beam_size, self.model.blank, self.context_graph,
+                                             ctc_logp=ctc_logp, ctc_weight=self.ctc_weight,
+                                             transducer_weight=self.transducer_weight, durations=self.durations, reset=reset,
+                                             final=fin, finalize=self._finalize)
+
+    def search(self, encoder_out_chunk: torch.Tensor, lens, final=False, finalize=None):
+        B = self.n_streams
+        fz = final if finalize is None else finalize
+        fz = [bool(fz)] * B if isinstance(fz, (bool, int)) else [bool(f) for f in fz]
+        if finalize is None:                        # (a `final` of the wrong length is reported below, as `final`)
+            fz = [f or p == 2 for f, p in zip(fz + [False] * B, self._phase)]
+        elif len(fz) != B:
+            raise RuntimeError(f"TransducerContextPrefixBeamStream: finalize has {len(fz)} entries for {B} streams")
+        self._finalize = fz                         # read by _chunk
+        return super().search(encoder_out_chunk, lens, final=final)
+
+    @staticmethod
+    def outputs(result, start_tag_id: int, end_tag_id: int):
+        """UpdateOutputs on one stream's result: per hypothesis the tokens after the seed blank with `start_tag_id` in front
+        of every token that starts a phrase and `end_tag_id` behind every token that ends one."""
+        outs = []
+        for hyp in result:
+            o = []
+            for tok, tag in zip(hyp[0][1:], hyp[6]):
+                if tag & 1:
+                    o.append(start_tag_id)
+                o.append(tok)
+                if tag & 2:
+                    o.append(end_tag_id)
+            outs.append(o)
+        return outs
 
 
 class PrefixBeamSearch:

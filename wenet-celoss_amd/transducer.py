@@ -966,6 +966,42 @@ class Transducer(nn.Module):
         nbest = stream.search(encoder_out, encoder_mask.squeeze(1).sum(1), final=True)
         return [[(h[1:], s, v, t) for h, s, v, t in utt] for utt in nbest]
 
+    # ---- the same with context-graph phrase biasing (the context_graph_ member rnnt_prefix_beam_search.h drafts) --
+    def reset_beam_context_stream(self, n_streams: int, beam_size: int, max_frames: int, chunk_frames: int, context_graph,
+                                  ctc_weight: Optional[float] = None, transducer_weight: Optional[float] = None) -> None:
+        """Start `n_streams` fresh biased streams of the transducer prefix beam search, plain or token-and-duration, that
+        walk `context_graph` (a ContextGraph); the other arguments are those of `reset_beam_stream`."""
+        from .search.prefix_beam_search import TransducerContextPrefixBeamStream
+        self._beam_context_stream = TransducerContextPrefixBeamStream(self, n_streams, beam_size, max_frames, chunk_frames,
+                                                                      context_graph, ctc_weight, transducer_weight)
+
+    def forward_context_prefix_beam_search(self, encoder_out_chunk: torch.Tensor, encoder_out_lens: torch.Tensor, final=False,
+                                           finalize=None):
+        """forward_prefix_beam_search on the biased streams -> per stream [(tokens incl. the seed blank, score,
+        viterbi_score, times, trans_score, context_score, tags, context_state)] best first.  `finalize` (default: `final`)
+        exports a stream as if it ended with this chunk; the stream itself goes on unchanged."""
+        if getattr(self, "_beam_context_stream", None) is None:
+            raise RuntimeError("call reset_beam_context_stream(n_streams, beam_size, max_frames, chunk_frames, context_graph) "
+                               "first")
+        return self._beam_context_stream.search(encoder_out_chunk, encoder_out_lens, final=final, finalize=finalize)
+
+    def beam_search_context(self, speech: torch.Tensor, speech_lengths: torch.Tensor, beam_size: int, context_graph,
+                            ctc_weight: Optional[float] = None, transducer_weight: Optional[float] = None,
+                            decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1,
+                            simulate_streaming: bool = False):
+        """`beam_search_times` with context-graph phrase biasing, whole utterances of any batch size: per utterance
+        [(tokens without the seed blank, score, viterbi_score, times, trans_score, context_score, tags, context_state)]
+        best first.  One reset, final and finalised chunk of the biased streaming search."""
+        from .search.prefix_beam_search import TransducerContextPrefixBeamStream
+        assert speech.shape[0] == speech_lengths.shape[0]
+        assert decoding_chunk_size != 0
+        encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
+                                                          num_decoding_left_chunks, simulate_streaming)
+        B, T, _ = encoder_out.shape
+        stream = TransducerContextPrefixBeamStream(self, B, beam_size, T, T, context_graph, ctc_weight, transducer_weight)
+        nbest = stream.search(encoder_out, encoder_mask.squeeze(1).sum(1), final=True, finalize=True)
+        return [[(r[0][1:],) + tuple(r[1:]) for r in utt] for utt in nbest]
+
     # ------------------- streaming CTC prefix beam search (runtime/core/decoder/ctc_prefix_beam_search.cc:107-211) --
     def reset_ctc_stream(self, n_streams: int = 1, beam_size: int = 10, max_frames: int = 4096) -> None:
         """Start `n_streams` fresh CTC prefix-beam streams; `max_frames` bounds the encoder frames (chunk widths summed)
