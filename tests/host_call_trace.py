@@ -5,9 +5,9 @@ functions of that layer, the k2-style losses among them, refuse bad calls.
 Used twice, like tests/joint_call_trace.py: tests/golden/make_host_calls.py runs it over a checkout of the commit the
 fixture is recorded from, tests/test_host_calls_host.py over the working tree; the two records must be identical.
 
-The seams are those of joint_call_trace.py: `_lib.load` returns a recorder (every `*_workspace_bytes` query answers
-WS_BYTES, everything else 0), `_lib.current_stream` returns None, `torch.cuda.device` is a null context.  Added here:
-`torch.Tensor.pin_memory` is the identity, `torch.empty` / `torch.empty_like` are `torch.zeros` / `torch.zeros_like` (so
+The seams are those of joint_call_trace.py: `_lib.load` returns a recorder (every `*_workspace_bytes` and every
+`*_state_bytes` query answers WS_BYTES, everything else 0), `_lib.current_stream` returns None, `torch.cuda.device` is a
+null context.  Added here: `torch.Tensor.pin_memory` is the identity, `torch.empty` / `torch.empty_like` are `torch.zeros` / `torch.zeros_like` (so
 that read-backs are defined), and the inputs -- and what `torch.empty` allocates, the joiner's logits among it -- are CPU
 tensors seen through a `torch.Tensor` subclass whose `is_cuda` is True.  A `DeviceDecoder` is made with `object.__new__`
 (its constructor refuses a module that is not on a HIP device), and the search functions get it from a stand-in for
@@ -15,7 +15,8 @@ their `DecoderCache` that records the capacities they ask for.
 
 The recorder also plays the library where the host reads results back: the full-lattice forward and the sweeps write
 cost_b = 100 * U_b + T_b, so that the order of the costs of a bucketed call can be read off them, and the searches write
-token counts, tokens, frames, scores and n-best counts (`_EFFECTS`).
+token counts, tokens, frames, scores and n-best counts, the streaming searches n-best lists of differing lengths
+(`_EFFECTS`).
 
 A record is {"calls": [...], "result" or "raises": ...}.  A call lists the entry point, its scalar arguments in order,
 the positions of its null pointers, the contents of its host arrays (the durations), the two length arrays it was given
@@ -77,6 +78,26 @@ def _write_beam(rec, B, beam, hyps, hl, sc, nh):
                 _i32(hyps, B * beam * lmax)[(b * beam + e) * lmax + j] = 100 * b + 10 * e + j
 
 
+def _write_nbest(B, beam, width, hl, nh, lists=(), scores=(), entries=(), streams=()):
+    """The n-best lists of a streaming search, of differing lengths: stream b has max(beam - b, 1) hypotheses, hypothesis e
+    min(e + 1, width) tokens.  `lists` are int32 [B][beam][width], `scores` double [B][beam], `entries` int32 [B][beam],
+    `streams` int32 [B]; every array gets values of its own."""
+    for b in range(B):
+        _i32(nh, B)[b] = max(beam - b, 1)
+        for k, p in enumerate(streams):
+            _i32(p, B)[b] = 7 + b + k
+        for e in range(beam):
+            i = b * beam + e
+            _i32(hl, B * beam)[i] = min(e + 1, width)
+            for k, p in enumerate(scores):
+                (ctypes.c_double * (B * beam)).from_address(p)[i] = -(10 * b + e) - 0.5 - 0.125 * k
+            for k, p in enumerate(entries):
+                _i32(p, B * beam)[i] = 1000 * (k + 1) + 10 * b + e
+            for k, p in enumerate(lists):
+                for j in range(width):
+                    _i32(p, B * beam * width)[i * width + j] = 1000 * k + 100 * b + 10 * e + j
+
+
 # entry point -> what the recorder writes through the pointers it was given (arguments as the library receives them)
 _EFFECTS = {
     "wr_rnnt_loss_fwd": lambda r, a: _write_costs(a[3], a[4], a[5], a[10]),
@@ -86,6 +107,17 @@ _EFFECTS = {
     "wr_greedy_search_chunk": lambda r, a: _write_greedy(r, a[3], a[9], a[10]),
     "wr_prefix_beam_search": lambda r, a: _write_beam(r, a[4], a[6], a[10], a[11], a[12], a[13]),
     "wr_prefix_beam_search_tdt": lambda r, a: _write_beam(r, a[4], a[6], a[12], a[13], a[14], a[15]),
+    # the streaming searches (the transducer's lists are max_frames + 1 wide; the cases attach max_frames = tmax)
+    "wr_ctc_prefix_beam_search_chunk": lambda r, a: _write_nbest(
+        a[2], a[5], a[9], a[13], a[17], lists=(a[12], a[16]), scores=(a[14], a[15]), streams=(a[18],)),
+    "wr_ctc_prefix_beam_search_context_chunk": lambda r, a: _write_nbest(
+        a[2], a[5], a[9], a[22], a[26], lists=(a[21], a[25], a[30]), scores=(a[23], a[24], a[28], a[29]), entries=(a[31],),
+        streams=(a[27],)),
+    "wr_prefix_beam_search_chunk": lambda r, a: _write_nbest(
+        a[4], a[6], r.tmax + 1, a[15], a[18], lists=(a[13], a[14]), scores=(a[16], a[17])),
+    "wr_prefix_beam_search_context_chunk": lambda r, a: _write_nbest(
+        a[4], a[6], r.tmax + 1, a[15], a[18], lists=(a[13], a[14], a[29]), scores=(a[16], a[17], a[27], a[28]),
+        entries=(a[30],)),
 }
 
 
@@ -137,7 +169,7 @@ class Recorder:
             self.calls.append(rec)
             if name in _EFFECTS:
                 _EFFECTS[name](self, plain)
-            return WS_BYTES if name.endswith("_workspace_bytes") else 0
+            return WS_BYTES if name.endswith(("_workspace_bytes", "_state_bytes")) else 0
         return fn
 
 
@@ -293,6 +325,9 @@ class _Cache:
         self.rec.calls.append({"name": "DecoderCache.get", "capacities": capacities})
         return self.dec
 
+    def discard(self, dec):
+        self.rec.calls.append({"name": "DecoderCache.discard"})
+
 
 def _search(pkg, rec, what, lens, **kw):
     """The functions of search/ and `Transducer.forward_greedy_search` over a `_Cache`."""
@@ -324,6 +359,10 @@ class _Enc(torch.nn.Module):
     def output_size(self):
         return self.proj.out_features
 
+    def forward(self, speech, speech_lengths, decoding_chunk_size=-1, num_decoding_left_chunks=-1):
+        mask = torch.arange(speech.shape[1])[None, None, :] < torch.as_tensor(speech_lengths).reshape(-1, 1, 1)
+        return dev(self.proj(speech)), mask
+
 
 def model(pkg, joint_outputs=23, **kw):
     """The tiny model of tests/test_rnnt_tdt_host.py (`_model`)."""
@@ -351,6 +390,265 @@ def _score(pkg, rec, tdt, fused=True):
     with torch.no_grad():
         fn = m._cal_tdt_score if tdt else m._cal_transducer_score
         return plain(fn(enc, mask, hyps_lens, hyps_pad))
+
+
+# --------------------------------------------------------- the streaming searches, plain and context-biased --
+PHRASES = ((2, 3), (3, 4, 2), (2,))             # one phrase a proper prefix of another; tokens inside DV and 23
+
+
+def _graph(pkg, blank=1, phrases=PHRASES):
+    return pkg.ContextGraph(phrases, 2.0, blank=blank)
+
+
+def _beam_stream(pkg, rec, ctx, chunks, attach=("own",), beam=BEAM):
+    """`DeviceDecoder`'s streaming prefix beam search: the attach calls of `attach` ("own": the form `ctx` says, "other":
+    its twin), then one chunk call per entry of `chunks` (its keywords; `streams`, `lens` and `ctc` shape the inputs)."""
+    d = decoder(pkg, rec)
+    try:
+        for which in attach:
+            biased = bool(ctx) == (which == "own")
+            (d.attach_beam_context_stream if biased else d.attach_beam_stream)(DN, beam, rec.tmax)
+        out = [plain([d.beam_stream, d.beam_context_stream])]
+        for kw in chunks:
+            kw = dict(kw)
+            n, lens = kw.pop("streams", DN), kw.pop("lens", torch.tensor([3, 2]))
+            if kw.pop("ctc", False):
+                kw["ctc_logp"] = dev(torch.zeros(n, 3, DV))
+            enc = dev(torch.zeros(n, 3, DE))
+            if ctx:
+                out.append(plain(d.prefix_beam_context_chunk(enc, lens, beam, 1, _graph(pkg), **kw)))
+            else:
+                out.append(plain(d.prefix_beam_chunk(enc, lens, beam, 1, **kw)))
+        return out
+    finally:
+        d._h = None
+
+
+def _ctc_stream(pkg, rec, ctx, chunks, state=None, graph=None, blank=0, streams=DN, beam=BEAM, max_frames=8, vocab=DV,
+                on_device=True, then=()):
+    """A `CtcPrefixBeamStream` / `CtcContextPrefixBeamStream` (`ctx`) over chunks of the widths `chunks` (a pair: width and
+    the keywords of `search`); `state`: the bytes of a lent state tensor, or a tensor.  `then`: "finalize", "reset" and
+    further chunks, in order.  The result lists what every call returned and, after each, `frames` / `context_states`."""
+    if isinstance(state, int):
+        state = dev(torch.zeros(state, dtype=torch.uint8))
+    if ctx:
+        s = pkg.CtcContextPrefixBeamStream(streams, beam, max_frames, _graph(pkg, blank) if graph is None else graph,
+                                           blank=blank, state=state)
+    else:
+        s = pkg.CtcPrefixBeamStream(streams, beam, max_frames, blank=blank, state=state)
+    out = []
+    for step in tuple(chunks) + tuple(then):
+        if step == "reset":
+            s.reset()
+        elif step == "finalize":
+            out.append(plain(s.finalize()))
+        else:
+            width, kw = step if isinstance(step, tuple) else (step, {})
+            kw = dict(kw)
+            x = torch.zeros(kw.pop("shape", (kw.pop("streams", DN), width, kw.pop("vocab", vocab))))
+            lens = kw.pop("lens", torch.tensor([width, width - 1]))
+            out.append(plain(s.search(x if kw.pop("cpu", not on_device) else dev(x), lens, **kw)))
+        out.append(plain([s.frames, getattr(s, "context_states", None)]))
+    return out
+
+
+def _asr(pkg, tdt=False, **kw):
+    """`model` with a CTC head, for the decode modes that run the encoder."""
+    m = model(pkg, 26, tdt_durations=(0, 1, 2), **kw) if tdt else model(pkg, **kw)
+    m.ctc = pkg.CTC(23, 12)
+    return m
+
+
+def _decode_mode(pkg, rec, method, *args, tdt=False, blank=0, **kw):
+    """A decode mode of `Transducer` from the speech on: the encoder, then the search."""
+    m = _asr(pkg, tdt)
+    m.blank = blank
+    cache = m._decoder_cache = _Cache(pkg, rec)
+    try:
+        with torch.no_grad():
+            return plain(getattr(m, method)(dev(torch.zeros(DN, DT, 8)), torch.tensor([6, 4]), *args, **kw))
+    finally:
+        cache.dec._h = None
+
+
+def _model_streams(pkg, rec, what, tdt=False):
+    """The streaming methods of `Transducer`: a reset, then two chunks."""
+    m = _asr(pkg, tdt)
+    m.blank = 1
+    cache = m._decoder_cache = _Cache(pkg, rec)
+    enc, lens = dev(torch.zeros(DN, 3, 12)), torch.tensor([3, 2])
+    try:
+        with torch.no_grad():
+            if what == "ctc":
+                m.reset_ctc_stream(DN, BEAM, 8)
+                return [plain(m.forward_ctc_prefix_beam_search(enc, lens)) for _ in range(2)]
+            if what == "ctc context":
+                m.reset_ctc_context_stream(DN, BEAM, 8, _graph(pkg, 0))
+                return [plain(m.forward_ctc_context_prefix_beam_search(enc, lens, finalize=f)) for f in (False, True)]
+            if what == "beam":
+                m.reset_beam_stream(DN, BEAM, rec.tmax, 3)
+                return [plain(m.forward_prefix_beam_search(enc, lens, final=f)) for f in (False, [True, False])]
+            m.reset_beam_context_stream(DN, BEAM, rec.tmax, 3, _graph(pkg))
+            return [plain(m.forward_context_prefix_beam_search(enc, lens, **kw))
+                    for kw in (dict(finalize=[False, True]), dict(final=[True, False]))]
+    finally:
+        cache.dec._h = None
+
+
+def _stream_refusals(pkg, out):
+    """The errors the streaming wrappers raise on their own, before or without the library."""
+    z = torch.zeros
+    for ctx, name in ((False, "CtcPrefixBeamStream"), (True, "CtcContextPrefixBeamStream")):
+        def ctc(chunks, ctx=ctx, **kw):
+            return lambda rec: _ctc_stream(pkg, rec, ctx, chunks, **kw)
+        out[f"{name} beam 17"] = ctc((), beam=17)
+        out[f"{name} no stream"] = ctc((), streams=0)
+        out[f"{name} max_frames 0"] = ctc((), max_frames=0)
+        out[f"{name} chunk rank"] = ctc(((2, dict(shape=(DN, DV))),))
+        out[f"{name} wrong stream count"] = ctc(((2, dict(streams=3, lens=torch.tensor([2, 2, 2]))),))
+        out[f"{name} vocabulary change"] = ctc((2, (2, dict(vocab=DV + 1))))
+        out[f"{name} capacity"] = ctc((5, 4))
+        out[f"{name} capacity after reset"] = ctc((5, "reset", 5, 4))
+        out[f"{name} cpu"] = ctc((2,), on_device=False)
+        out[f"{name} state too small"] = ctc((2,), state=WS_BYTES - 1)
+        out[f"{name} state dtype"] = ctc((2,), state=dev(z(WS_BYTES, dtype=torch.int8)))
+        out[f"{name} lens length"] = ctc(((2, dict(lens=torch.tensor([2, 2, 2]))),))
+        out[f"{name} order: stream count before vocabulary before capacity"] = ctc(
+            (2, (7, dict(streams=3, vocab=DV + 1))))
+        out[f"{name} order: vocabulary before capacity before cpu"] = ctc((2, (7, dict(vocab=DV + 1, cpu=True))))
+        out[f"{name} order: state before lens"] = ctc(((2, dict(lens=torch.tensor([2]))),), state=1)
+    cctx = lambda chunks, **kw: (lambda rec: _ctc_stream(pkg, rec, True, chunks, **kw))                    # noqa: E731
+    out["CtcContextPrefixBeamStream graph type"] = cctx((), graph=[[2, 3]])
+    out["CtcContextPrefixBeamStream graph blank"] = cctx((), graph=_graph(pkg, 1))
+    out["CtcContextPrefixBeamStream order: sizes before graph"] = cctx((), graph="phrases", beam=0)
+    out["CtcContextPrefixBeamStream finalize() before a search"] = cctx(("finalize",))
+    out["CtcContextPrefixBeamStream finalize() before a search, after a reset"] = cctx(("reset", "finalize"))
+    out["ctc_prefix_beam_search_times cpu"] = lambda rec: pkg.ctc_prefix_beam_search_times(
+        z(DN, DT, DV), torch.tensor([6, 4]), BEAM)
+    out["ctc_context_prefix_beam_search cpu"] = lambda rec: pkg.ctc_context_prefix_beam_search(
+        z(DN, DT, DV), torch.tensor([6, 4]), BEAM, _graph(pkg, 0))
+    out["ctc_context_prefix_beam_search graph type"] = lambda rec: pkg.ctc_context_prefix_beam_search(
+        dev(z(DN, DT, DV)), torch.tensor([6, 4]), BEAM, None)
+    out["ctc_prefix_beam_search_times beam 17"] = lambda rec: pkg.ctc_prefix_beam_search_times(
+        dev(z(DN, DT, DV)), torch.tensor([6, 4]), 17)
+    # DeviceDecoder
+    for ctx, name in ((False, "prefix_beam_chunk"), (True, "prefix_beam_context_chunk")):
+        def dec(chunks, ctx=ctx, **kw):
+            return lambda rec: _beam_stream(pkg, rec, ctx, chunks, **kw)
+        out[f"DeviceDecoder.{name} not attached"] = dec(({},), attach=())
+        out[f"DeviceDecoder.{name} the other form attached"] = dec(({},), attach=("other",))
+        out[f"DeviceDecoder.{name} the other form attached last"] = dec(({},), attach=("own", "other"))
+        out[f"DeviceDecoder.{name} reset mask length"] = dec((dict(reset=[True]),))
+        out[f"DeviceDecoder.{name} final mask length"] = dec((dict(final=[True, False, True]),))
+        out[f"DeviceDecoder.{name} lens length"] = dec((dict(reset=True, lens=torch.tensor([3, 2, 1])),))
+        out[f"DeviceDecoder.{name} order: mask before lens"] = dec((dict(reset=[True], lens=torch.tensor([3])),))
+    out["DeviceDecoder.prefix_beam_context_chunk finalize mask length"] = lambda rec: _beam_stream(
+        pkg, rec, True, (dict(finalize=[True]),))
+    # the stream classes of search/prefix_beam_search.py and the Transducer methods that need a reset first
+    for ctx, name in ((False, "TransducerPrefixBeamStream"), (True, "TransducerContextPrefixBeamStream")):
+        def stream(ctx=ctx, model_kw=None, graph=None, blank=1, **kw):
+            m = _asr(pkg, **(model_kw or {}))
+            m.blank = blank
+            if ctx:
+                return pkg.TransducerContextPrefixBeamStream(m, context_graph=_graph(pkg) if graph is None else graph, **kw)
+            return pkg.TransducerPrefixBeamStream(m, **kw)
+
+        def run(steps, stream=stream, ctx=ctx, **kw):
+            def fn(rec):
+                s = stream(**dict(dict(n_streams=DN, beam_size=BEAM, max_frames=rec.tmax, chunk_frames=3), **kw))
+                cache = s.model._decoder_cache = _Cache(pkg, rec)
+                try:
+                    return [plain(s.search(dev(z(*shape)), lens, **skw)) for shape, lens, skw in steps]
+                finally:
+                    cache.dec._h = None
+            return fn
+        chunk, lens = (DN, 3, 12), torch.tensor([3, 2])
+        out[f"{name} beam 17"] = run((), beam_size=17)
+        out[f"{name} chunk_frames 0"] = run((), chunk_frames=0)
+        out[f"{name} chunk rank"] = run((((DN, 12), lens, {}),))
+        out[f"{name} wrong stream count"] = run((((3, 3, 12), lens, {}),))
+        out[f"{name} chunk wider than chunk_frames"] = run((((DN, 4, 12), lens, {}),))
+        out[f"{name} final length"] = run(((chunk, lens, dict(final=[True])),))
+        out[f"{name} lens length"] = run(((chunk, torch.tensor([3, 2, 1]), {}),))
+        out[f"{name} fed after final"] = run(((chunk, lens, dict(final=[True, False])), (chunk, lens, {})))
+        out[f"{name} final again after final"] = run(((chunk, lens, dict(final=True)),
+                                                     (chunk, torch.tensor([0, 0]), dict(final=[False, True]))))
+        out[f"{name} capacity"] = run(((chunk, lens, {}), (chunk, lens, {}), (chunk, lens, {})))
+        out[f"{name} cpu"] = lambda rec, stream=stream: stream(n_streams=DN, beam_size=BEAM, max_frames=6).search(
+            z(*chunk), lens)
+    tctx = lambda **kw: (lambda rec: pkg.TransducerContextPrefixBeamStream(                               # noqa: E731
+        _asr(pkg), DN, BEAM, 6, 3, **kw))
+    out["TransducerContextPrefixBeamStream graph type"] = tctx(context_graph=[[2, 3]])
+    out["TransducerContextPrefixBeamStream no graph"] = tctx()
+    out["TransducerContextPrefixBeamStream graph blank"] = tctx(context_graph=_graph(pkg, 1))
+    out["TransducerContextPrefixBeamStream phrase token outside the vocabulary"] = tctx(
+        context_graph=_graph(pkg, 0, ((2, 3), (23,))))
+    out["TransducerContextPrefixBeamStream order: sizes before graph"] = lambda rec: pkg.TransducerContextPrefixBeamStream(
+        _asr(pkg), DN, 17, 6, 3, None)
+
+    def finalize_length(rec):
+        s = pkg.TransducerContextPrefixBeamStream(_asr(pkg), DN, BEAM, 6, 3, _graph(pkg, 0))
+        return s.search(dev(z(DN, 3, 12)), torch.tensor([3, 2]), finalize=[True])
+    out["TransducerContextPrefixBeamStream finalize length"] = finalize_length
+    out["Transducer.forward_context_prefix_beam_search before a reset"] = lambda rec: _asr(
+        pkg).forward_context_prefix_beam_search(dev(z(DN, 3, 12)), torch.tensor([3, 2]))
+    out["Transducer.forward_ctc_context_prefix_beam_search before a reset"] = lambda rec: _asr(
+        pkg).forward_ctc_context_prefix_beam_search(dev(z(DN, 3, 12)), torch.tensor([3, 2]))
+
+
+def _stream_cases(pkg, add):
+    sized = dict(max_hyp=8, tmax=DT)
+    # DeviceDecoder: attach, then three chunks -- scalar masks, per-stream masks, the last chunk
+    for ctx, durations, ctc in itertools.product((False, True), (None, (0, 1, 2)), (False, True)):
+        weights = dict(ctc=True, ctc_weight=0.3, transducer_weight=0.7) if ctc else {}
+        last = dict(finalize=True) if ctx else {}
+        mixed = dict(finalize=[False, True]) if ctx else {}
+        chunks = (dict(reset=True, durations=durations, **weights),
+                  dict(reset=[False, True], final=[True, False], durations=durations, **weights, **mixed),
+                  dict(final=True, reset=0, durations=durations, **weights, **last))
+        add(f"DeviceDecoder streaming prefix beam context={int(bool(ctx))} durations={durations} ctc={int(bool(ctc))}",
+            lambda rec, a=(ctx, chunks): _beam_stream(pkg, rec, a[0], a[1]), **sized)
+    for ctx in (False, True):
+        add(f"DeviceDecoder streaming prefix beam context={int(bool(ctx))} attached after the other form",
+            lambda rec, c=ctx: _beam_stream(pkg, rec, c, (dict(reset=True, ctc=True),), attach=("other", "own")), **sized)
+        add(f"DeviceDecoder streaming prefix beam context={int(bool(ctx))} beam 1",
+            lambda rec, c=ctx: _beam_stream(pkg, rec, c, (dict(reset=True, ctc=True),), beam=1), **sized)
+    # the CTC streams: a state tensor of their own or a lent one, two chunks, a reset, a third
+    for ctx, lent in itertools.product((False, True), (False, True)):
+        fz = (lambda f: dict(finalize=f)) if ctx else (lambda f: {})
+        add(f"Ctc{'Context' if ctx else ''}PrefixBeamStream lent={int(bool(lent))}",
+            lambda rec, a=(ctx, lent, fz): _ctc_stream(
+                pkg, rec, a[0], ((2, a[2](False)), (3, a[2](True))), state=WS_BYTES + 8 if a[1] else None,
+                then=(("finalize",) if a[0] else ()) + ("reset", (1, dict(lens=torch.tensor([0, 1]))))))
+    add("CtcContextPrefixBeamStream finalize at capacity",
+        lambda rec: _ctc_stream(pkg, rec, True, (8,), then=("finalize",)))
+    add("CtcContextPrefixBeamStream blank=1 empty graph",
+        lambda rec: _ctc_stream(pkg, rec, True, (2,), blank=1, graph=_graph(pkg, 1, ())))
+    add("CtcPrefixBeamStream blank=1 beam 1", lambda rec: _ctc_stream(pkg, rec, False, (2,), blank=1, beam=1))
+    for blank in (0, 1):
+        add(f"ctc_prefix_beam_search_times blank={blank}", lambda rec, b=blank: plain(pkg.ctc_prefix_beam_search_times(
+            dev(torch.zeros(DN, DT, DV)), torch.tensor([6, 4]), BEAM, blank=b)))
+        add(f"ctc_context_prefix_beam_search blank={blank}", lambda rec, b=blank: plain(pkg.ctc_context_prefix_beam_search(
+            dev(torch.zeros(DN, DT, DV)), torch.tensor([6, 4]), BEAM, _graph(pkg, b), blank=b)))
+    # Transducer: the decode modes from the speech on, and the streaming methods
+    add("Transducer.ctc_greedy_search", lambda rec: _decode_mode(pkg, rec, "ctc_greedy_search"), **sized)
+    add("Transducer.ctc_greedy_search chunked", lambda rec: _decode_mode(pkg, rec, "ctc_greedy_search", 4, 2), **sized)
+    add("Transducer.ctc_prefix_beam_search_times", lambda rec: _decode_mode(pkg, rec, "ctc_prefix_beam_search_times", BEAM),
+        **sized)
+    add("Transducer.ctc_context_prefix_beam_search",
+        lambda rec: _decode_mode(pkg, rec, "ctc_context_prefix_beam_search", BEAM, _graph(pkg, 0)), **sized)
+    for tdt in (False, True):
+        add(f"Transducer.beam_search_times tdt={int(bool(tdt))}",
+            lambda rec, t=tdt: _decode_mode(pkg, rec, "beam_search_times", BEAM, tdt=t, blank=1), **sized)
+        add(f"Transducer.beam_search_context tdt={int(bool(tdt))}",
+            lambda rec, t=tdt: _decode_mode(pkg, rec, "beam_search_context", BEAM, _graph(pkg), tdt=t, blank=1), **sized)
+    add("Transducer.beam_search_times weights", lambda rec: _decode_mode(
+        pkg, rec, "beam_search_times", BEAM, 0.5, 0.5, tdt=True, blank=1), **sized)
+    add("Transducer.beam_search_context weights", lambda rec: _decode_mode(
+        pkg, rec, "beam_search_context", BEAM, _graph(pkg), 0.5, 0.5, tdt=True, blank=1), **sized)
+    for what in ("ctc", "ctc context", "beam", "beam context"):
+        add(f"Transducer streaming {what}", lambda rec, w=what: _model_streams(pkg, rec, w), **sized)
+    add("Transducer streaming beam context tdt", lambda rec: _model_streams(pkg, rec, "beam context", tdt=True), **sized)
 
 
 def _refusals(pkg):
@@ -502,6 +800,7 @@ def _refusals(pkg):
     out["Transducer tdt forward_greedy_search"] = lambda rec: model(
         pkg, 26, tdt_durations=(0, 1, 2)).forward_greedy_search(*none)
     out["Transducer tdt greedy_search_batch"] = lambda rec: model(pkg, 26, tdt_durations=(0, 1, 2)).greedy_search_batch(*none)
+    _stream_refusals(pkg, out)
     return out
 
 
@@ -595,6 +894,7 @@ def cases(pkg):
         add(f"Transducer.compute_loss tdt={flag(tdt)} two ops", lambda rec, t=tdt: _loss_block(pkg, rec, t, None, fused=False))
         add(f"Transducer score tdt={flag(tdt)}", lambda rec, t=tdt: _score(pkg, rec, t))
     add("Transducer score tdt=0 two ops", lambda rec: _score(pkg, rec, False, fused=False))
+    _stream_cases(pkg, add)
     for name, fn in _refusals(pkg).items():
         add("refusal: " + name, fn, max_hyp=1, tmax=DT)
     return out

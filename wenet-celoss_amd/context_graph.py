@@ -103,3 +103,16 @@ class ContextGraph:
             self._device[device] = tuple(torch.from_numpy(pad(a).copy()).to(device) for a in (
                 self.arc_begin, self.arc_token, self.arc_next, self.arc_score, self.escape, self.final))
         return self._device[device]
+
+
+def mark_phrases(tokens, tags, start_tag_id: int, end_tag_id: int) -> list:
+    """UpdateOutputs (ctc_prefix_beam_search.cc:63-84) on one hypothesis: its tokens with `start_tag_id` in front of every
+    token whose tag has bit 0 (a phrase starts at it) and `end_tag_id` behind every token whose tag has bit 1 (one ends)."""
+    out = []
+    for tok, tag in zip(tokens, tags):
+        if tag & 1:
+            out.append(start_tag_id)
+        out.append(tok)
+        if tag & 2:
+            out.append(end_tag_id)
+    return out

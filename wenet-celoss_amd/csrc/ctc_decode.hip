@@ -360,35 +360,15 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_kernel(
 // log_add(pb, pnb) + bonus, step E looks it up again for the at most `beam` kept entries, and the tags are a fourth list
 // that travels with the tokens.  CTX = false compiles to the plain search: every added statement is under `if constexpr`.
 
-// next(state, token) of the context graph: runtime/core/decoder/context_graph.cc:86-108 on a table.  `state` is inside
-// [0, S); every CSR bound is clamped into [0, A] and every arc_next into [0, S) before it is used as an index.
-__device__ __forceinline__ void ctc_context_next(const CtcContextGraph &g, int state, int tok, int &st, float &sc, int &tag)
-{
-    int lo = g.arc_begin[state], end = g.arc_begin[state + 1];
-    lo = lo < 0 ? 0 : (lo > g.A ? g.A : lo);
-    end = end < lo ? lo : (end > g.A ? g.A : end);
-    int hi = end;
-    while (lo < hi) {                                                  // first arc whose token is >= tok
-        const int mid = (lo + hi) >> 1;
-        if (g.arc_token[mid] < tok) lo = mid + 1;
-        else hi = mid;
-    }
-    if (lo < end && g.arc_token[lo] == tok) {
-        int nx = g.arc_next[lo];
-        nx = nx < 0 ? 0 : (nx >= g.S ? g.S - 1 : nx);
-        st = nx; sc = g.arc_score[lo];
-        tag = (state == 0 ? 1 : 0) | (g.final_[nx] != 0 ? 2 : 0);
-    } else { st = 0; sc = g.escape[state]; tag = 0; }                 // the breaking token is not retried from the root
-}
-
 template <bool CTX>
 __global__ __launch_bounds__(256) void ctc_prefix_beam_chunk_kernel(
     const float *__restrict__ tkv, const int32_t *__restrict__ tki, const int32_t *__restrict__ lens, int T, int beam,
     int blank, int reset, int Lcap, char *__restrict__ state, CtcStreamState lay,
     int32_t *__restrict__ hyps /* [B][beam][Lcap] */, int32_t *__restrict__ hyp_lens, double *__restrict__ scores,
     double *__restrict__ viterbi, int32_t *__restrict__ times /* [B][beam][Lcap] */, int32_t *__restrict__ n_hyps,
-    int32_t *__restrict__ n_frames, CtcContextGraph cg, CtcContextOut cx)
+    int32_t *__restrict__ n_frames, CtcContextArgs cx)
 {
+    const ContextGraph &cg = cx.graph;                                 // CTX only
     constexpr int kLists = CTX ? kCtcContextLists : kCtcStreamLists;
     // the context of the current and the next beam, and the export order after finalisation (CTX only; 16 entries each)
     __shared__ int c_cst[CTX ? kMaxCtcBeam : 1], t_cst[CTX ? kMaxCtcBeam : 1], t_tag[CTX ? kMaxCtcBeam : 1],
@@ -551,12 +531,7 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_chunk_kernel(
             if constexpr (CTX) {                                       // total_score(): the prune ranks by score + bonus
                 const int e = s_base[i], tk = s_tok[i];
                 double bonus = c_csc[e];
-                if (tk >= 0) {
-                    int st_, tg_;
-                    float sc_;
-                    ctc_context_next(cg, c_cst[e], tk, st_, sc_, tg_);
-                    bonus += (double)sc_;
-                }
+                if (tk >= 0) bonus += (double)context_graph_next(cg, c_cst[e], tk).score;
                 r_score[i] = r_score[i] + bonus;
             }
             atomicAdd(&s_nrep, 1);
@@ -584,14 +559,13 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_chunk_kernel(
             const int f = order[tid];
             if constexpr (CTX) {                                       // the kept entries look their arc up again
                 const int e = s_base[f], tk = s_tok[f];
-                int st_ = c_cst[e], tg_ = 0;
+                ContextStep nx{c_cst[e], 0.f, 0};
                 double bonus = c_csc[e];
                 if (tk >= 0) {
-                    float sc_;
-                    ctc_context_next(cg, c_cst[e], tk, st_, sc_, tg_);
-                    bonus += (double)sc_;
+                    nx = context_graph_next(cg, c_cst[e], tk);
+                    bonus += (double)nx.score;
                 }
-                t_cst[tid] = st_; t_csc[tid] = bonus; t_tag[tid] = tg_;
+                t_cst[tid] = nx.state; t_csc[tid] = bonus; t_tag[tid] = nx.tag;
             }
             t_base[tid] = s_base[f]; t_tok[tid] = s_tok[f];
             t_len[tid] = s_len[f]; t_hash[tid] = s_hash[f]; t_pb[tid] = r_pb[f]; t_pnb[tid] = r_pnb[f];
@@ -655,7 +629,7 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_chunk_kernel(
         if constexpr (CTX) { g_cst[tid] = c_cst[tid]; g_csc[tid] = c_csc[tid]; }
     }
     if (tid == 0) { head[0] = marker; head[1] = a_next; head[2] = ncur; head[3] = sel; }
-    // ---- export ----
+    // ---- export: entry e goes to row(e) of the stream's outputs ----
     const int n = ncur;
     if constexpr (CTX) {
         // UpdateFinalContext in the export only: an entry inside a partial match gives the bonus of that match back, the
@@ -680,38 +654,15 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_chunk_kernel(
             x_pos[tid] = pos;
         }
         __syncthreads();
-        for (int i = tid; i < beam * Lcap; i += 256) {
-            const int e = i / Lcap, q = i - e * Lcap;
-            const bool in = e < n && q < c_len[e];
-            const size_t o = ((size_t)b * beam + (e < n ? x_pos[e] : e)) * Lcap + q;
-            int tok = -1, tm = -1, tg = -1;
-            if (in) {
-                const double vb = c_vb[e], vnb = c_vnb[e];
-                const int li = vb > vnb ? 0 : 1;
-                tok = sq[(size_t)sel * LB + (size_t)e * Lcap + q];
-                tg = tq[(size_t)sel * LB + (size_t)e * Lcap + q];
-                if ((vb > vnb ? vb : vnb) > NINF) tm = sq[(size_t)((1 + li) * 2 + sel) * LB + (size_t)e * Lcap + q];
-            }
-            hyps[o] = tok;
-            times[o] = tm;
-            cx.tags[o] = tg;
-        }
-        if (tid < beam) {
-            const size_t o = (size_t)b * beam + (tid < n ? x_pos[tid] : tid);
-            hyp_lens[o] = tid < n ? c_len[tid] : 0;
-            cx.ctc_scores[o] = tid < n ? x_ctc[tid] : NINF;
-            cx.context_scores[o] = tid < n ? x_ctx[tid] : 0.0;
-            scores[o] = tid < n ? x_ctc[tid] + x_ctx[tid] : NINF;
-            viterbi[o] = tid < n ? (c_vb[tid] > c_vnb[tid] ? c_vb[tid] : c_vnb[tid]) : NINF;
-            cx.context_states[o] = tid < n ? c_cst[tid] : 0;
-        }
-        if (tid == 0) { n_hyps[b] = n; n_frames[b] = a_next; }
-        return;
     }
+    auto row = [&](int e) -> size_t {
+        if constexpr (CTX) return (size_t)b * beam + (e < n ? x_pos[e] : e);
+        else return (size_t)b * beam + e;
+    };
     for (int i = tid; i < beam * Lcap; i += 256) {
         const int e = i / Lcap, q = i - e * Lcap;
         const bool in = e < n && q < c_len[e];
-        const size_t o = ((size_t)b * beam + e) * Lcap + q;
+        const size_t o = row(e) * Lcap + q;
         int tok = -1, tm = -1;
         if (in) {
             const double vb = c_vb[e], vnb = c_vnb[e];
@@ -721,11 +672,20 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_chunk_kernel(
         }
         hyps[o] = tok;
         times[o] = tm;
+        if constexpr (CTX) cx.tags[o] = in ? tq[(size_t)sel * LB + (size_t)e * Lcap + q] : -1;
     }
     if (tid < beam) {
-        hyp_lens[(size_t)b * beam + tid] = tid < n ? c_len[tid] : 0;
-        scores[(size_t)b * beam + tid] = tid < n ? py_log_add2(c_pb[tid], c_pnb[tid]) : NINF;
-        viterbi[(size_t)b * beam + tid] = tid < n ? (c_vb[tid] > c_vnb[tid] ? c_vb[tid] : c_vnb[tid]) : NINF;
+        const size_t o = row(tid);
+        hyp_lens[o] = tid < n ? c_len[tid] : 0;
+        viterbi[o] = tid < n ? (c_vb[tid] > c_vnb[tid] ? c_vb[tid] : c_vnb[tid]) : NINF;
+        if constexpr (CTX) {
+            cx.ctc_scores[o] = tid < n ? x_ctc[tid] : NINF;
+            cx.context_scores[o] = tid < n ? x_ctx[tid] : 0.0;
+            scores[o] = tid < n ? x_ctc[tid] + x_ctx[tid] : NINF;
+            cx.context_states[o] = tid < n ? c_cst[tid] : 0;
+        } else {
+            scores[o] = tid < n ? py_log_add2(c_pb[tid], c_pnb[tid]) : NINF;
+        }
     }
     if (tid == 0) { n_hyps[b] = n; n_frames[b] = a_next; }
 }
@@ -745,7 +705,7 @@ int ctc_decode_check_shape(int B, int T, int V, int blank) { return ctc_dec_chec
 int ctc_prefix_beam_chunk_launch(const float *logits_d, const int32_t *lens_d, int B, int T, int V, int beam, int blank,
                                  int reset, int Lcap, void *state_d, int32_t *hyps_d, int32_t *hyp_lens_d, double *scores_d,
                                  double *viterbi_d, int32_t *times_d, int32_t *n_hyps_d, int32_t *n_frames_d,
-                                 void *workspace_d, void *stream)
+                                 void *workspace_d, void *stream, const CtcContextArgs *cx)
 {
     const CtcStreamWs w = ctc_stream_ws_layout(B, T, beam);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -753,27 +713,11 @@ int ctc_prefix_beam_chunk_launch(const float *logits_d, const int32_t *lens_d, i
     // the frames' top-`beam` exactly as wr_ctc_prefix_beam_search finds them (dynamic LDS: one row of logits)
     WR_TRY(launch("ctc_frame_topk_kernel", ctc_frame_topk_kernel, dim3(B * T), dim3(256), (size_t)V * sizeof(float), st, logits_d, V,
                   beam, reinterpret_cast<float *>(ws + w.tkv_off), reinterpret_cast<int32_t *>(ws + w.tki_off)));
-    return launch("ctc_prefix_beam_chunk_kernel", ctc_prefix_beam_chunk_kernel<false>, dim3(B), dim3(256), 0, st,
+    return launch(cx ? "ctc_prefix_beam_chunk_kernel<context>" : "ctc_prefix_beam_chunk_kernel",
+                  cx ? ctc_prefix_beam_chunk_kernel<true> : ctc_prefix_beam_chunk_kernel<false>, dim3(B), dim3(256), 0, st,
                   reinterpret_cast<const float *>(ws + w.tkv_off), reinterpret_cast<const int32_t *>(ws + w.tki_off), lens_d, T, beam,
-                  blank, reset, Lcap, static_cast<char *>(state_d), ctc_stream_state_layout(beam, Lcap), hyps_d, hyp_lens_d,
-                  scores_d, viterbi_d, times_d, n_hyps_d, n_frames_d, CtcContextGraph{}, CtcContextOut{});
-}
-
-int ctc_prefix_beam_context_chunk_launch(const float *logits_d, const int32_t *lens_d, int B, int T, int V, int beam, int blank,
-                                         int reset, int Lcap, void *state_d, const CtcContextGraph &graph,
-                                         const CtcContextOut &ctx, int32_t *hyps_d, int32_t *hyp_lens_d, double *scores_d,
-                                         double *viterbi_d, int32_t *times_d, int32_t *n_hyps_d, int32_t *n_frames_d,
-                                         void *workspace_d, void *stream)
-{
-    const CtcStreamWs w = ctc_stream_ws_layout(B, T, beam);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char *ws = static_cast<char *>(workspace_d);
-    WR_TRY(launch("ctc_frame_topk_kernel", ctc_frame_topk_kernel, dim3(B * T), dim3(256), (size_t)V * sizeof(float), st, logits_d, V,
-                  beam, reinterpret_cast<float *>(ws + w.tkv_off), reinterpret_cast<int32_t *>(ws + w.tki_off)));
-    return launch("ctc_prefix_beam_chunk_kernel<context>", ctc_prefix_beam_chunk_kernel<true>, dim3(B), dim3(256), 0, st,
-                  reinterpret_cast<const float *>(ws + w.tkv_off), reinterpret_cast<const int32_t *>(ws + w.tki_off), lens_d, T, beam,
-                  blank, reset, Lcap, static_cast<char *>(state_d), ctc_context_state_layout(beam, Lcap), hyps_d, hyp_lens_d,
-                  scores_d, viterbi_d, times_d, n_hyps_d, n_frames_d, graph, ctx);
+                  blank, reset, Lcap, static_cast<char *>(state_d), ctc_stream_state_layout(beam, Lcap, cx != nullptr), hyps_d,
+                  hyp_lens_d, scores_d, viterbi_d, times_d, n_hyps_d, n_frames_d, cx ? *cx : CtcContextArgs{});
 }
 
 }  // namespace wr

@@ -2,7 +2,7 @@
 // (include/wr_api.h, "Streaming CTC prefix beam search").
 #pragma once
 
-#include "wr_common.hpp"
+#include "context_graph.hpp"
 
 namespace wr {
 
@@ -13,7 +13,7 @@ constexpr int kCtcStreamLists = 3;             // tokens, times_b, times_nb
 //   head    int32[4]: a marker made of (beam, Lcap), a_next, the number of entries, the sequence buffer in use
 //   pb, pnb, vb, vnb  double[beam];  hash  uint64[beam];  len, last  int32[beam]
 //   seq     int32[3][2][beam][Lcap]: tokens / times_b / times_nb, each double-buffered
-// The biased search's block (ctc_context_state_layout) has its own layout: the plain one, then, behind the plain stride,
+// The biased search's block (`ctx`) has its own layout: the plain one, then, behind the plain stride,
 //   csc     double[beam]: the entries' bonuses;  cst  int32[beam]: their context-graph states
 //   tag     int32[2][beam][Lcap]: a fourth list, the tags, double-buffered like the tokens it travels with
 // so it is larger than the plain block for every (beam, Lcap).  csc_off / cst_off / tag_off are 0 in the plain layout,
@@ -22,7 +22,9 @@ struct CtcStreamState {
     size_t pb_off, pnb_off, vb_off, vnb_off, hash_off, len_off, last_off, seq_off, stride, csc_off, cst_off, tag_off;
 };
 
-__host__ __device__ inline CtcStreamState ctc_stream_state_layout(int beam, int Lcap)
+constexpr int kCtcContextLists = 4;            // tokens, times_b, times_nb, tags
+
+__host__ __device__ inline CtcStreamState ctc_stream_state_layout(int beam, int Lcap, bool ctx)
 {
     CtcStreamState s;
     s.csc_off = 0; s.cst_off = 0; s.tag_off = 0;
@@ -36,37 +38,21 @@ __host__ __device__ inline CtcStreamState ctc_stream_state_layout(int beam, int 
     s.last_off = off; off += (size_t)beam * sizeof(int32_t);
     off = (off + 15) / 16 * 16;
     s.seq_off = off;  off += (size_t)kCtcStreamLists * 2 * beam * Lcap * sizeof(int32_t);
-    s.stride = (off + 255) / 256 * 256;
+    off = (off + 255) / 256 * 256;
+    if (ctx) {
+        s.csc_off = off;  off += (size_t)beam * sizeof(double);
+        s.cst_off = off;  off += (size_t)beam * sizeof(int32_t);
+        off = (off + 15) / 16 * 16;
+        s.tag_off = off;  off += (size_t)2 * beam * Lcap * sizeof(int32_t);
+        off = (off + 255) / 256 * 256;
+    }
+    s.stride = off;
     return s;
 }
 
-constexpr int kCtcContextLists = 4;            // tokens, times_b, times_nb, tags
-constexpr int kCtcContextMaxStates = 65536;
-constexpr int kCtcContextMaxArcs = 1048576;
-
-__host__ __device__ inline CtcStreamState ctc_context_state_layout(int beam, int Lcap)
-{
-    CtcStreamState s = ctc_stream_state_layout(beam, Lcap);
-    size_t off = s.stride;
-    s.csc_off = off;  off += (size_t)beam * sizeof(double);
-    s.cst_off = off;  off += (size_t)beam * sizeof(int32_t);
-    off = (off + 15) / 16 * 16;
-    s.tag_off = off;  off += (size_t)2 * beam * Lcap * sizeof(int32_t);
-    s.stride = (off + 255) / 256 * 256;
-    return s;
-}
-
-// The context graph as the kernel reads it (include/wr_api.h, "Context-graph biasing"): a deterministic table, state 0
-// the root.  The plain search passes an empty one.
-struct CtcContextGraph {
-    const int32_t *arc_begin, *arc_token, *arc_next;
-    const float *arc_score, *escape;
-    const int32_t *final_;
-    int S, A;
-};
-
-// What the biased call adds to the plain one's arguments: the flag and the four outputs.
-struct CtcContextOut {
+// What the biased call adds to the plain one's arguments: the table, the flag and the four outputs.
+struct CtcContextArgs {
+    ContextGraph graph;
     int finalize;
     double *ctc_scores, *context_scores;
     int32_t *tags, *context_states;
@@ -90,20 +76,13 @@ inline CtcStreamWs ctc_stream_ws_layout(int B, int T, int beam)
 // ctc_decode.hip: the shape checks every CTC decode entry point starts with (B, T positive, V > 1, blank inside V, V <= 16320)
 int ctc_decode_check_shape(int B, int T, int V, int blank);
 
-// ctc_decode.hip: the launches behind wr_ctc_prefix_beam_search_chunk, which has checked every argument: the fused
-// log-softmax + top-`beam` of the chunk's B * T frames, then one workgroup per stream that loads its beam from the state
-// block, consumes lens[b] frames, stores the beam back and exports.
+// ctc_decode.hip: the launches behind wr_ctc_prefix_beam_search_chunk and wr_ctc_prefix_beam_search_context_chunk (`cx`),
+// which have checked every argument: the fused log-softmax + top-`beam` of the chunk's B * T frames, then one workgroup per
+// stream that loads its beam from the state block, consumes lens[b] frames, stores the beam back and exports.  With `cx`
+// the kernel's biased instantiation runs, on the biased layout of the state block.
 int ctc_prefix_beam_chunk_launch(const float *logits_d, const int32_t *lens_d, int B, int T, int V, int beam, int blank,
                                  int reset, int Lcap, void *state_d, int32_t *hyps_d, int32_t *hyp_lens_d, double *scores_d,
                                  double *viterbi_d, int32_t *times_d, int32_t *n_hyps_d, int32_t *n_frames_d,
-                                 void *workspace_d, void *stream);
-
-// ctc_decode.hip: the same two launches behind wr_ctc_prefix_beam_search_context_chunk, with the kernel's biased
-// instantiation and the state layout of ctc_context_state_layout.
-int ctc_prefix_beam_context_chunk_launch(const float *logits_d, const int32_t *lens_d, int B, int T, int V, int beam, int blank,
-                                         int reset, int Lcap, void *state_d, const CtcContextGraph &graph,
-                                         const CtcContextOut &ctx, int32_t *hyps_d, int32_t *hyp_lens_d, double *scores_d,
-                                         double *viterbi_d, int32_t *times_d, int32_t *n_hyps_d, int32_t *n_frames_d,
-                                         void *workspace_d, void *stream);
+                                 void *workspace_d, void *stream, const CtcContextArgs *cx);
 
 }  // namespace wr

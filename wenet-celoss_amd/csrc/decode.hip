@@ -194,9 +194,7 @@ struct DevState {
     double *bctx_score;           // [n_utt, beam]           bonus of the entry
     int32_t *bctx_state;          // [n_utt, beam]           graph state of the entry
     int32_t *btags;               // [2, n_utt, beam, Lmax]  tag of each token of a hypothesis (slot 0, the seed: -1)
-    const int32_t *cg_begin, *cg_token, *cg_next, *cg_final;
-    const float *cg_score, *cg_escape;
-    int cg_S, cg_A;
+    ContextGraph cg;
 };
 
 struct GemmArgs {
@@ -1983,33 +1981,46 @@ struct BeamCtxLds : BeamUpdLds {
 template <bool CTX>
 using BeamLds = std::conditional_t<CTX, BeamCtxLds, BeamUpdLds>;
 
-// next(state, token) of the context graph for an entry at `state` with bonus `score` that appends `tok`: the arc is found by
-// one binary search over the state's arcs (strictly increasing tokens).  Every CSR bound is clamped into [0, A], every
-// arc_next and the incoming state into [0, S) before it is used as an index.
-__device__ __forceinline__ void ctx_graph_next(const DevState &S, int state, double score, int tok, int *st_out, double *sc_out,
-                                               int *tag_out)
+// The graph state, bonus and tag of candidate `c`, which extends entry `entry` of the beam by `tok` (context_graph.hpp); a
+// negative `tok` appends nothing and copies the entry's fields.
+//
+// The walk is context_graph_next of context_graph.hpp (same clamps, same search) with the float64 add done inside each
+// branch.  It stays a body of its own here: with the shared one the biased stream measured slower at equal registers,
+// LDS and occupancy (profiles/context_twins_ab.md, "Time against the parent").
+__device__ __forceinline__ void ctx_graph_next(const ContextGraph &g, int state, double score, int tok, int *st_out,
+                                               double *sc_out, int *tag_out)
 {
-    const int ns = S.cg_S, na = S.cg_A;
+    const int ns = g.S, na = g.A;
     state = state < 0 ? 0 : (state < ns ? state : ns - 1);
-    int lo = S.cg_begin[state], hi = S.cg_begin[state + 1];
+    int lo = g.arc_begin[state], hi = g.arc_begin[state + 1];
     lo = lo < 0 ? 0 : (lo < na ? lo : na);
     hi = hi < lo ? lo : (hi < na ? hi : na);
     const int end = hi;
     while (lo < hi) {
         const int mid = lo + ((hi - lo) >> 1);
-        if (S.cg_token[mid] < tok) lo = mid + 1; else hi = mid;
+        if (g.arc_token[mid] < tok) lo = mid + 1; else hi = mid;
     }
-    if (lo < end && S.cg_token[lo] == tok) {
-        int nx = S.cg_next[lo];
+    if (lo < end && g.arc_token[lo] == tok) {
+        int nx = g.arc_next[lo];
         nx = nx < 0 ? 0 : (nx < ns ? nx : ns - 1);
         *st_out = nx;
-        *sc_out = score + (double)S.cg_score[lo];
-        *tag_out = (state == 0 ? 1 : 0) | (S.cg_final[nx] != 0 ? 2 : 0);
+        *sc_out = score + (double)g.arc_score[lo];
+        *tag_out = (state == 0 ? 1 : 0) | (g.final_[nx] != 0 ? 2 : 0);
     } else {
         *st_out = 0;
-        *sc_out = score + (double)S.cg_escape[state];
+        *sc_out = score + (double)g.escape[state];
         *tag_out = 0;
     }
+}
+
+__device__ __forceinline__ void beam_ctx_candidate(const DevState &S, BeamCtxLds &L, int c, size_t entry, int tok)
+{
+    int cst = S.bctx_state[entry], ctag = 0;
+    double csc = S.bctx_score[entry];
+    if (tok >= 0) ctx_graph_next(S.cg, cst, csc, tok, &cst, &csc, &ctag);
+    L.c_cstate[c] = cst;
+    L.c_cscore[c] = csc;
+    L.c_ctag[c] = ctag;
 }
 
 // phase 2: class representative = the first candidate with the same token sequence (:130-142) -- and, WITH_FRAME, the same
@@ -2356,14 +2367,7 @@ __global__ __launch_bounds__(kBeamUpdThreads) void beam_update_kernel(DevState *
         L.c_hash[tid] = (tok != S.blank) ? hyp_hash_push(hh, tok) : hh;
         L.c_rep[tid] = tid;
         L.c_rank[tid] = 0;
-        if constexpr (CTX) {                       // a blank copies the entry's fields, a label takes next(state, token)
-            int cst = S.bctx_state[(size_t)b * beam + j], ctag = 0;
-            double csc = S.bctx_score[(size_t)b * beam + j];
-            if (tok != S.blank) ctx_graph_next(S, cst, csc, tok, &cst, &csc, &ctag);
-            L.c_cstate[tid] = cst;
-            L.c_cscore[tid] = csc;
-            L.c_ctag[tid] = ctag;
-        }
+        if constexpr (CTX) beam_ctx_candidate(S, L, tid, (size_t)b * beam + j, tok != S.blank ? tok : -1);   // a blank copies
     }
     __syncthreads();
     WR_STAMP(1);                                   // candidates built
@@ -2595,14 +2599,7 @@ __device__ __forceinline__ void tdt_beam_update(const DevState &S, BeamLds<CTX> 
         L.c_hash[tid] = tok >= 0 ? hyp_hash_push(hh, tok) : hh;
         L.c_rep[tid] = tid;
         L.c_rank[tid] = 0;
-        if constexpr (CTX) {                       // a waiting entry and a blank arc copy the entry's fields
-            int cst = S.bctx_state[(size_t)b * beam + e], ctag = 0;
-            double csc = S.bctx_score[(size_t)b * beam + e];
-            if (tok >= 0) ctx_graph_next(S, cst, csc, tok, &cst, &csc, &ctag);
-            L.c_cstate[tid] = cst;
-            L.c_cscore[tid] = csc;
-            L.c_ctag[tid] = ctag;
-        }
+        if constexpr (CTX) beam_ctx_candidate(S, L, tid, (size_t)b * beam + e, tok);   // a waiting entry, a blank arc: tok < 0
     }
     __syncthreads();
     beam_find_classes<true>(L, c_t, hy, S.Lmax, C, tid);
@@ -2775,9 +2772,9 @@ __global__ void beam_context_export_kernel(DevState *s, int32_t *hyps_out, int32
         double cx = 0.0, tot = -__builtin_huge_val();
         if (tid < N) {
             int st = s->bctx_state[(size_t)b * beam + tid];
-            st = st < 0 ? 0 : (st < s->cg_S ? st : s->cg_S - 1);
+            st = st < 0 ? 0 : (st < s->cg.S ? st : s->cg.S - 1);
             cx = s->bctx_score[(size_t)b * beam + tid];
-            if (fin && st != 0) cx += (double)s->cg_escape[st];
+            if (fin && st != 0) cx += (double)s->cg.escape[st];
             tot = s->bscores[(size_t)b * beam + tid] + cx;
         }
         s_ctx[tid] = cx;
@@ -3762,8 +3759,7 @@ struct BeamStreamState {
         s.bhyps = saved.bhyps; s.btimes = nullptr; s.bhyp_lens = saved.bhyp_lens; s.bscores = saved.bscores; s.bvscores = nullptr;
         s.bs_base = s.bs_F = s.bs_state = nullptr; s.bs_flags = nullptr;
         s.bctx_score = nullptr; s.bctx_state = nullptr; s.btags = nullptr;
-        s.cg_begin = s.cg_token = s.cg_next = s.cg_final = nullptr; s.cg_score = s.cg_escape = nullptr;
-        s.cg_S = s.cg_A = 0;
+        s.cg = ContextGraph{};
         s.Lmax = saved.Lmax;
     }
 };
@@ -3868,12 +3864,14 @@ int wr::beam_stream_chunk_body(wr_decoder *h, const float *enc_chunk_d, const in
                "%s: durations or blank changed in the middle of a stream (blank %d -> %d, D %d -> %d)", what, bs.blank, blank,
                bs.D, dur.D);
     if (cx) {
-        WR_REQUIRE(cx->S >= 1 && cx->A >= 0, WR_EINVAL, "%s: a context graph of S=%d states and A=%d arcs (S >= 1, A >= 0)", what,
-                   cx->S, cx->A);
-        WR_REQUIRE(cx->arc_begin && cx->arc_token && cx->arc_next && cx->arc_score && cx->escape && cx->final, WR_EINVAL,
+        const ContextGraph &g = cx->graph;
+        WR_REQUIRE(g.S >= 1 && g.A >= 0, WR_EINVAL, "%s: a context graph of S=%d states and A=%d arcs (S >= 1, A >= 0)", what, g.S,
+                   g.A);
+        WR_REQUIRE(g.arc_begin && g.arc_token && g.arc_next && g.arc_score && g.escape && g.final_, WR_EINVAL,
                    "%s: null context-graph table pointer", what);
-        WR_REQUIRE(cx->S <= 65536 && cx->A <= 1048576, WR_EUNSUPPORTED,
-                   "%s: a context graph of S=%d states and A=%d arcs exceeds 65536 states / 1048576 arcs", what, cx->S, cx->A);
+        WR_REQUIRE(g.S <= kContextMaxStates && g.A <= kContextMaxArcs, WR_EUNSUPPORTED,
+                   "%s: a context graph of S=%d states and A=%d arcs exceeds %d states / %d arcs", what, g.S, g.A,
+                   kContextMaxStates, kContextMaxArcs);
     }
     // ---- nothing is refused below this line; the host's record of the streams follows the call
     for (int b = 0; b < B; ++b) {
@@ -3892,10 +3890,7 @@ int wr::beam_stream_chunk_body(wr_decoder *h, const float *enc_chunk_d, const in
     s.n_utt = B; s.T = T; s.lanes_per_utt = beam; s.n_lanes = B * beam;
     s.beam = beam; s.ctc_weight = ctc_weight; s.tr_weight = transducer_weight; s.blank = blank;
     s.tdt_durs = durs; s.tdt_D = dur.D; s.hyp_frames = nullptr;
-    if (cx) {                                      // the table travels in the state block, never in a captured graph
-        s.cg_begin = cx->arc_begin; s.cg_token = cx->arc_token; s.cg_next = cx->arc_next; s.cg_score = cx->arc_score;
-        s.cg_escape = cx->escape; s.cg_final = cx->final; s.cg_S = cx->S; s.cg_A = cx->A;
-    }
+    if (cx) s.cg = cx->graph;                      // the table travels in the state block, never in a captured graph
     // the flags ride in the pinned slot of the state block's upload (upload_state waits for the slot's last copy, then
     // records the event behind both copies)
     const int slot = h->stage_next;

@@ -62,7 +62,7 @@ extern "C" int wr_prefix_beam_search_context_chunk(wr_decoder *h, const float *e
                    trans_scores_d && context_scores_d && tags_d && context_states_d,
                WR_EINVAL, "%s: null pointer argument", what);
     WR_REQUIRE(h != nullptr, WR_EINVAL, "%s: null handle", what);
-    const BeamCtxArgs cx{arc_begin_d, arc_token_d, arc_next_d, arc_score_d, escape_d, final_d, S, A,
+    const BeamCtxArgs cx{{arc_begin_d, arc_token_d, arc_next_d, arc_score_d, escape_d, final_d, S, A},
                          trans_scores_d, context_scores_d, tags_d, context_states_d};
     return beam_stream_chunk_body(h, enc_chunk_d, chunk_lens_d, ctc_logp_chunk_d, B, T, beam, ctc_weight, transducer_weight,
                                   blank, dur, flags, hyps_d, times_d, hyp_lens_d, scores_d, vscores_d, n_hyps_d, stream, &cx);

@@ -3,17 +3,15 @@
 // transducer prefix beam search").
 #pragma once
 
+#include "context_graph.hpp"
 #include "rnnt_tdt.hpp"
 
 namespace wr {
 
-// What wr_prefix_beam_search_context_chunk adds to the plain chunk call: the context graph's table (device pointers, S
-// states, A arcs) and the four further outputs.
+// What wr_prefix_beam_search_context_chunk adds to the plain chunk call: the context graph's table and the four further
+// outputs.
 struct BeamCtxArgs {
-    const int32_t *arc_begin, *arc_token, *arc_next;
-    const float *arc_score, *escape;
-    const int32_t *final;
-    int S, A;
+    ContextGraph graph;
     double *trans_scores, *context_scores;
     int32_t *tags, *context_states;
 };

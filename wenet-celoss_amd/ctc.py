@@ -144,14 +144,17 @@ class CtcPrefixBeamStream:
     state block (at least wr_ctc_stream_state_bytes(n_streams, beam_size, max_frames) bytes) instead of one allocated by
     the first search; whatever it holds, a new object or a reset() starts every stream fresh."""
 
+    # what the biased stream (CtcContextPrefixBeamStream) does differently: the size of its block and its entry point
+    _state_query, _entry = "wr_ctc_stream_state_bytes", "wr_ctc_prefix_beam_search_chunk"
+
     def __init__(self, n_streams: int, beam_size: int, max_frames: int, blank: int = 0, state: torch.Tensor = None):
         self.n_streams, self.beam_size, self.max_frames, self.blank = int(n_streams), int(beam_size), int(max_frames), int(blank)
+        self._name = type(self).__name__            # every message names the class that raised it
         if self.n_streams < 1 or self.max_frames < 1 or not 1 <= self.beam_size <= 16:
-            raise RuntimeError(f"CtcPrefixBeamStream: n_streams={n_streams}, beam_size={beam_size} (1..16), "
+            raise RuntimeError(f"{self._name}: n_streams={n_streams}, beam_size={beam_size} (1..16), "
                                f"max_frames={max_frames} must be positive")
         self._state = state             # allocated by the first search (on the chunk's device) unless the caller lends one
         self._vocab = None
-        self.frames = [0] * self.n_streams
         self.reset()
 
     def reset(self) -> None:
@@ -161,29 +164,49 @@ class CtcPrefixBeamStream:
         self.frames = [0] * self.n_streams
 
     def search(self, logits_chunk: torch.Tensor, lens: torch.Tensor):
+        return self._search(logits_chunk, lens)
+
+    # the two hooks of the biased stream
+    def _more(self, B, dev, finalize):
+        """(what the entry point takes between the state block and the outputs, the outputs it writes behind them)"""
+        return (), ()
+
+    def _result(self, rows):
+        """`rows`, the result of `_call`, completed from the further outputs"""
+        return rows
+
+    def _search(self, logits_chunk, lens, finalize=None):
+        name = self._name
         if logits_chunk.dim() != 3:
-            raise RuntimeError("CtcPrefixBeamStream: the chunk must be (n_streams, frames, vocab)")
+            raise RuntimeError(f"{name}: the chunk must be (n_streams, frames, vocab)")
         B, T, V = logits_chunk.shape
         if B != self.n_streams:
-            raise RuntimeError(f"CtcPrefixBeamStream: chunk has {B} streams, the stream set has {self.n_streams}")
+            raise RuntimeError(f"{name}: chunk has {B} streams, the stream set has {self.n_streams}")
         if self._vocab is not None and V != self._vocab:
-            raise RuntimeError(f"CtcPrefixBeamStream: vocabulary changed from {self._vocab} to {V}")
+            raise RuntimeError(f"{name}: vocabulary changed from {self._vocab} to {V}")
         if self._frames_done + T > self.max_frames:
-            raise RuntimeError(f"CtcPrefixBeamStream: {self._frames_done} frames done + a chunk of {T} exceeds "
-                               f"max_frames={self.max_frames}")
+            raise RuntimeError(f"{name}: {self._frames_done} frames done + a chunk of {T} exceeds max_frames={self.max_frames}")
         if not logits_chunk.is_cuda:
-            raise RuntimeError("wenet_celoss_amd.CtcPrefixBeamStream: logits must live on a HIP device (no CPU path)")
-        x = logits_chunk.detach().float().contiguous()
+            raise RuntimeError(f"wenet_celoss_amd.{name}: logits must live on a HIP device (no CPU path)")
+        out = self._call(logits_chunk.detach().float().contiguous(), lens, self._frames_done, finalize)
+        self._frames_done += T
+        self._vocab = V
+        return out
+
+    def _call(self, x, lens, frames_done, finalize):
+        """One call of the entry point on chunk `x` (`finalize` is the biased stream's, for `_more`) -> per stream
+        [(tokens, score, viterbi_score, times)], passed through `_result`."""
+        B, T, V = x.shape
         dev = x.device
         beam, cap = self.beam_size, self.max_frames
-        need = _lib.load().wr_ctc_stream_state_bytes(B, beam, cap)
+        need = getattr(_lib.load(), self._state_query)(B, beam, cap)
         if self._state is None:
             self._state = torch.empty(need, dtype=torch.uint8, device=dev)
         elif self._state.device != dev or self._state.numel() < need or self._state.dtype != torch.uint8:
-            raise RuntimeError(f"CtcPrefixBeamStream: the state tensor must be uint8 on {dev} with at least {need} bytes")
+            raise RuntimeError(f"{self._name}: the state tensor must be uint8 on {dev} with at least {need} bytes")
         ln = lens.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
         if ln.numel() != B:
-            raise RuntimeError(f"CtcPrefixBeamStream: lens has {ln.numel()} elements for {B} streams")
+            raise RuntimeError(f"{self._name}: lens has {ln.numel()} elements for {B} streams")
         ws = _lib.workspace("wr_ctc_stream_workspace_bytes", B, T, beam, device=dev)
         hyps = torch.empty(B, beam, cap, dtype=torch.int32, device=dev)
         tm = torch.empty(B, beam, cap, dtype=torch.int32, device=dev)
@@ -192,17 +215,16 @@ class CtcPrefixBeamStream:
         vt = torch.empty(B, beam, dtype=torch.float64, device=dev)
         nh = torch.empty(B, dtype=torch.int32, device=dev)
         nf = torch.empty(B, dtype=torch.int32, device=dev)
-        _lib.call("wr_ctc_prefix_beam_search_chunk", x, ln, B, T, V, beam, self.blank, int(self._fresh), self._frames_done,
-                  cap, self._state, self._state.numel(), hyps, hl, sc, vt, tm, nh, nf, ws, ws.numel(), device=dev)
+        graph_args, more_outputs = self._more(B, dev, finalize)
+        _lib.call(self._entry, x, ln, B, T, V, beam, self.blank, int(self._fresh), frames_done, cap, self._state,
+                  self._state.numel(), *graph_args, hyps, hl, sc, vt, tm, nh, nf, *more_outputs, ws, ws.numel(), device=dev)
         self._fresh = False
-        self._frames_done += T
-        self._vocab = V
         lc, scc, vtc, nc = hl.cpu().tolist(), sc.cpu().tolist(), vt.cpu().tolist(), nh.cpu().tolist()
         self.frames = nf.cpu().tolist()
         width = max(max(row) for row in lc)
         hc, tc = hyps[:, :, :width].cpu().tolist(), tm[:, :, :width].cpu().tolist()      # nested lists: one conversion each
-        return [[(tuple(hc[b][e][:lc[b][e]]), scc[b][e], vtc[b][e], tuple(tc[b][e][:lc[b][e]]))
-                 for e in range(nc[b])] for b in range(B)]
+        return self._result([[(tuple(hc[b][e][:lc[b][e]]), scc[b][e], vtc[b][e], tuple(tc[b][e][:lc[b][e]]))
+                              for e in range(nc[b])] for b in range(B)], *more_outputs)
 
 
 def ctc_prefix_beam_search_times(logits: torch.Tensor, lens: torch.Tensor, beam_size: int, blank: int = 0):
@@ -214,7 +236,7 @@ def ctc_prefix_beam_search_times(logits: torch.Tensor, lens: torch.Tensor, beam_
     return CtcPrefixBeamStream(logits.shape[0], beam_size, logits.shape[1], blank=blank).search(logits, lens)
 
 
-class CtcContextPrefixBeamStream:
+class CtcContextPrefixBeamStream(CtcPrefixBeamStream):
     """CtcPrefixBeamStream with the context-graph phrase biasing of the reference runtime (context_graph.cc,
     ctc_prefix_beam_search.cc:137-193, 213-234; the contract is in include/wr_api.h, "Context-graph biasing in the CTC
     prefix beam search"): every hypothesis walks `context_graph` (a ContextGraph) and the beam is pruned by score plus
@@ -226,49 +248,23 @@ class CtcContextPrefixBeamStream:
     match gives its bonus back and the list is sorted again; the stream itself is not changed, so it may go on.
     finalize() does that without new frames.  `context_states` holds, per stream, the graph states of the last result."""
 
+    _state_query, _entry = "wr_ctc_context_stream_state_bytes", "wr_ctc_prefix_beam_search_context_chunk"
+
     def __init__(self, n_streams: int, beam_size: int, max_frames: int, context_graph, blank: int = 0,
                  state: torch.Tensor = None):
         from .context_graph import ContextGraph
-        self.n_streams, self.beam_size, self.max_frames, self.blank = int(n_streams), int(beam_size), int(max_frames), int(blank)
-        if self.n_streams < 1 or self.max_frames < 1 or not 1 <= self.beam_size <= 16:
-            raise RuntimeError(f"CtcContextPrefixBeamStream: n_streams={n_streams}, beam_size={beam_size} (1..16), "
-                               f"max_frames={max_frames} must be positive")
+        super().__init__(n_streams, beam_size, max_frames, blank, state)
         if not isinstance(context_graph, ContextGraph):
             raise RuntimeError("CtcContextPrefixBeamStream: context_graph must be a ContextGraph")
         if context_graph.blank != self.blank:
             raise RuntimeError(f"CtcContextPrefixBeamStream: the graph was built for blank {context_graph.blank}, "
                                f"the search uses {self.blank}")
         self.context_graph = context_graph
-        self._state = state
-        self._vocab = None
         self._dev = None
-        self.frames = [0] * self.n_streams
         self.context_states = [[] for _ in range(self.n_streams)]
-        self.reset()
-
-    def reset(self) -> None:
-        """Every stream starts fresh with the next search."""
-        self._fresh = True
-        self._frames_done = 0
-        self.frames = [0] * self.n_streams
 
     def search(self, logits_chunk: torch.Tensor, lens: torch.Tensor, finalize: bool = False):
-        if logits_chunk.dim() != 3:
-            raise RuntimeError("CtcContextPrefixBeamStream: the chunk must be (n_streams, frames, vocab)")
-        B, T, V = logits_chunk.shape
-        if B != self.n_streams:
-            raise RuntimeError(f"CtcContextPrefixBeamStream: chunk has {B} streams, the stream set has {self.n_streams}")
-        if self._vocab is not None and V != self._vocab:
-            raise RuntimeError(f"CtcContextPrefixBeamStream: vocabulary changed from {self._vocab} to {V}")
-        if self._frames_done + T > self.max_frames:
-            raise RuntimeError(f"CtcContextPrefixBeamStream: {self._frames_done} frames done + a chunk of {T} exceeds "
-                               f"max_frames={self.max_frames}")
-        if not logits_chunk.is_cuda:
-            raise RuntimeError("wenet_celoss_amd.CtcContextPrefixBeamStream: logits must live on a HIP device (no CPU path)")
-        out = self._call(logits_chunk.detach().float().contiguous(), lens, self._frames_done, finalize)
-        self._frames_done += T
-        self._vocab = V
-        return out
+        return self._search(logits_chunk, lens, finalize)
 
     def finalize(self):
         """The finalised n-best of every stream without new frames: a chunk in which every stream has lens = 0."""
@@ -278,54 +274,27 @@ class CtcContextPrefixBeamStream:
         # the chunk is one frame wide and none of it is consumed: it counts against no capacity
         return self._call(x, torch.zeros(self.n_streams, dtype=torch.int32), min(self._frames_done, self.max_frames - 1), True)
 
-    def _call(self, x, lens, frames_done, finalize):
-        B, T, V = x.shape
-        dev = x.device
-        beam, cap, g = self.beam_size, self.max_frames, self.context_graph
-        need = _lib.load().wr_ctc_context_stream_state_bytes(B, beam, cap)
-        if self._state is None:
-            self._state = torch.empty(need, dtype=torch.uint8, device=dev)
-        elif self._state.device != dev or self._state.numel() < need or self._state.dtype != torch.uint8:
-            raise RuntimeError(f"CtcContextPrefixBeamStream: the state tensor must be uint8 on {dev} with at least {need} bytes")
-        ln = lens.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-        if ln.numel() != B:
-            raise RuntimeError(f"CtcContextPrefixBeamStream: lens has {ln.numel()} elements for {B} streams")
-        ws = _lib.workspace("wr_ctc_stream_workspace_bytes", B, T, beam, device=dev)
-        i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
-        hyps, tm, tg = torch.empty(B, beam, cap, **i32), torch.empty(B, beam, cap, **i32), torch.empty(B, beam, cap, **i32)
-        hl, cs, nh, nf = torch.empty(B, beam, **i32), torch.empty(B, beam, **i32), torch.empty(B, **i32), torch.empty(B, **i32)
-        sc, vt, cc, cx = (torch.empty(B, beam, **f64) for _ in range(4))
-        _lib.call("wr_ctc_prefix_beam_search_context_chunk", x, ln, B, T, V, beam, self.blank, int(self._fresh), frames_done,
-                  cap, self._state, self._state.numel(), *g.to(dev), g.n_states, g.n_arcs, int(bool(finalize)), hyps, hl, sc,
-                  vt, tm, nh, nf, cc, cx, tg, cs, ws, ws.numel(), device=dev)
-        self._fresh = False
+    def _more(self, B, dev, finalize):
+        beam, g = self.beam_size, self.context_graph
+        cc, cx = (torch.empty(B, beam, dtype=torch.float64, device=dev) for _ in range(2))
+        tg = torch.empty(B, beam, self.max_frames, dtype=torch.int32, device=dev)
+        cs = torch.empty(B, beam, dtype=torch.int32, device=dev)
         self._dev = dev
-        lc, nc = hl.cpu().tolist(), nh.cpu().tolist()
-        scc, vtc, ccc, cxc = sc.cpu().tolist(), vt.cpu().tolist(), cc.cpu().tolist(), cx.cpu().tolist()
-        self.frames = nf.cpu().tolist()
-        csc = cs.cpu().tolist()
-        self.context_states = [csc[b][:nc[b]] for b in range(B)]
-        width = max(max(row) for row in lc)
-        hc, tc, gc = (t[:, :, :width].cpu().tolist() for t in (hyps, tm, tg))
-        return [[(tuple(hc[b][e][:lc[b][e]]), scc[b][e], vtc[b][e], tuple(tc[b][e][:lc[b][e]]), ccc[b][e], cxc[b][e],
-                  tuple(gc[b][e][:lc[b][e]])) for e in range(nc[b])] for b in range(B)]
+        return (*g.to(dev), g.n_states, g.n_arcs, int(bool(finalize))), (cc, cx, tg, cs)
+
+    def _result(self, rows, cc, cx, tg, cs):
+        ccc, cxc, csc = cc.cpu().tolist(), cx.cpu().tolist(), cs.cpu().tolist()
+        self.context_states = [csc[b][:len(utt)] for b, utt in enumerate(rows)]
+        gc = tg[:, :, :max(len(h[0]) for utt in rows for h in utt)].cpu().tolist()
+        return [[h + (ccc[b][e], cxc[b][e], tuple(gc[b][e][:len(h[0])])) for e, h in enumerate(utt)]
+                for b, utt in enumerate(rows)]
 
     @staticmethod
     def outputs(result, start_tag_id: int, end_tag_id: int):
         """UpdateOutputs (ctc_prefix_beam_search.cc:63-84) on one stream's result: per hypothesis the tokens with
         `start_tag_id` in front of every token that starts a phrase and `end_tag_id` behind every token that ends one."""
-        outs = []
-        for hyp in result:
-            tokens, tags = hyp[0], hyp[6]
-            o = []
-            for tok, tag in zip(tokens, tags):
-                if tag & 1:
-                    o.append(start_tag_id)
-                o.append(tok)
-                if tag & 2:
-                    o.append(end_tag_id)
-            outs.append(o)
-        return outs
+        from .context_graph import mark_phrases
+        return [mark_phrases(hyp[0], hyp[6], start_tag_id, end_tag_id) for hyp in result]
 
 
 def ctc_context_prefix_beam_search(logits: torch.Tensor, lens: torch.Tensor, beam_size: int, context_graph, blank: int = 0):

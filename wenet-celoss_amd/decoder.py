@@ -254,21 +254,80 @@ class DeviceDecoder:
         return self._beam("wr_prefix_beam_search_tdt", encoder_out, encoder_out_lens, ctc_logp, beam_size, float(ctc_weight),
                           float(transducer_weight), int(blank), _durations_arg(durations), len(durations))
 
+    def _attach(self, size_query: str, attach: str, n_streams: int, beam: int, max_frames: int):
+        """The body of attach_beam_stream / attach_beam_context_stream: size the block with `size_query`, allocate it and
+        hand it to the handle with `attach` -> (n_streams, beam, max_frames), what the caller notes as attached."""
+        size = (int(n_streams), int(beam), int(max_frames))
+        nbytes = getattr(self._lib, size_query)(self._h, *size)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = getattr(self._lib, attach)(self._h, *size, _lib.ptr(ws), nbytes)
+        _lib.check(rc, attach)
+        self._beam_stream_ws = ws
+        return size
+
+    beam_stream = beam_context_stream = None       # the handle holds one form's block at a time
+
     def attach_beam_stream(self, n_streams: int, beam: int, max_frames: int) -> None:
         """Give the handle the state of `n_streams` streams of `prefix_beam_chunk` (`wr_decoder_attach_beam_stream`): beam
         `beam`, at most `max_frames` encoder frames (chunk widths summed) between two resets of a stream.  Attaching
         again replaces the state and ends every stream."""
-        n_streams, beam, max_frames = int(n_streams), int(beam), int(max_frames)
-        nbytes = self._lib.wr_decoder_beam_stream_workspace_bytes(self._h, n_streams, beam, max_frames)
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.wr_decoder_attach_beam_stream(self._h, n_streams, beam, max_frames, _lib.ptr(ws), nbytes)
-        _lib.check(rc, "wr_decoder_attach_beam_stream")
-        self._beam_stream_ws = ws
-        self.beam_stream = (n_streams, beam, max_frames)
-        self.beam_context_stream = None             # the handle holds one form's block at a time
+        self.beam_stream, self.beam_context_stream = self._attach(
+            "wr_decoder_beam_stream_workspace_bytes", "wr_decoder_attach_beam_stream", n_streams, beam, max_frames), None
 
-    beam_stream = None
+    def attach_beam_context_stream(self, n_streams: int, beam: int, max_frames: int) -> None:
+        """`attach_beam_stream` for the biased streams of `prefix_beam_context_chunk`
+        (`wr_decoder_attach_beam_context_stream`).  Attaching one form replaces the other and ends every stream."""
+        self.beam_context_stream, self.beam_stream = self._attach(
+            "wr_decoder_beam_context_stream_workspace_bytes", "wr_decoder_attach_beam_context_stream", n_streams, beam,
+            max_frames), None
+
+    def _beam_chunk(self, name: str, entry: str, attached, encoder_chunk, chunk_lens, beam_size, blank, ctc_logp, ctc_weight,
+                    transducer_weight, durations, reset, final, finalize=None, graph=None):
+        """The body of prefix_beam_chunk / prefix_beam_context_chunk (`graph` and `finalize` given: the biased one, `name` the
+        public method, `entry` its entry point, `attached` what its attach call noted): the masks become the flags, the
+        n-best buffers are allocated, the entry point runs and the lists are read back into tuples.  The biased call has a
+        third mask, a third list (the tags), two more scores and the graph states."""
+        enc = _f32(encoder_chunk)
+        ctc = None if ctc_logp is None else _f32(ctc_logp)
+        B, T, _ = enc.shape
+        biased = graph is not None
+
+        def mask(x):
+            return [bool(x)] * B if isinstance(x, (bool, int)) else [bool(v) for v in x]
+
+        rs, fin, fz = mask(reset), mask(final), mask(finalize) if biased else [False] * B
+        if len(rs) != B or len(fin) != B or len(fz) != B:
+            raise RuntimeError(f"DeviceDecoder.{name}: reset / final{' / finalize' if biased else ''} masks must have one "
+                               f"entry per stream ({B})")
+        flags = (ctypes.c_int32 * B)(*[int(r) | (int(f) << 1) | (int(z) << 2) for r, f, z in zip(rs, fin, fz)])
+        lens = chunk_lens.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+        if lens.numel() != B:
+            raise RuntimeError(f"DeviceDecoder.{name}: chunk_lens has {lens.numel()} elements for {B} streams")
+        cap = attached[2] + 1
+        beam_size = int(beam_size)
+        hyps = torch.empty(B, beam_size, cap, dtype=torch.int32, device=self.device)
+        tm = torch.empty(B, beam_size, cap, dtype=torch.int32, device=self.device)
+        hl = torch.empty(B, beam_size, dtype=torch.int32, device=self.device)
+        sc = torch.empty(B, beam_size, dtype=torch.float64, device=self.device)
+        vs = torch.empty(B, beam_size, dtype=torch.float64, device=self.device)
+        nh = torch.empty(B, dtype=torch.int32, device=self.device)
+        more = ()
+        if biased:
+            tg, cs = torch.empty_like(hyps), torch.empty_like(hl)
+            ts, cx = torch.empty_like(sc), torch.empty_like(sc)
+            more = (*graph.to(self.device), graph.n_states, graph.n_arcs, ts, cx, tg, cs)
+        dur = (None, 0) if durations is None else (_durations_arg(durations), len(durations))
+        self._call(entry, enc, lens, ctc, B, T, beam_size, float(ctc_weight), float(transducer_weight), int(blank), *dur,
+                   flags, hyps, tm, hl, sc, vs, nh, *more)
+        hl, sc, vs, nh = hl.cpu().tolist(), sc.cpu().tolist(), vs.cpu().tolist(), nh.cpu().tolist()
+        width = max(max(row) for row in hl)
+        hyps, tm = hyps[:, :, :width].cpu().tolist(), tm[:, :, :width].cpu().tolist()
+        if not biased:
+            return [[(hyps[b][e][:hl[b][e]], sc[b][e], vs[b][e], tm[b][e][1:hl[b][e]]) for e in range(nh[b])] for b in range(B)]
+        ts, cx, cs, tg = ts.cpu().tolist(), cx.cpu().tolist(), cs.cpu().tolist(), tg[:, :, :width].cpu().tolist()
+        return [[(hyps[b][e][:hl[b][e]], sc[b][e], vs[b][e], tm[b][e][1:hl[b][e]], ts[b][e], cx[b][e], tg[b][e][1:hl[b][e]],
+                  cs[b][e]) for e in range(nh[b])] for b in range(B)]
 
     def prefix_beam_chunk(self, encoder_chunk: torch.Tensor, chunk_lens: torch.Tensor, beam_size: int, blank: int = 0,
                           ctc_logp: torch.Tensor = None, ctc_weight: float = 0.0, transducer_weight: float = 1.0,
@@ -282,50 +341,8 @@ class DeviceDecoder:
         i + 1 was emitted.  `set_graph` applies; the result does not depend on it."""
         if self.beam_stream is None:
             raise RuntimeError("DeviceDecoder.prefix_beam_chunk: call attach_beam_stream(n_streams, beam, max_frames) first")
-        enc = _f32(encoder_chunk)
-        ctc = None if ctc_logp is None else _f32(ctc_logp)
-        B, T, _ = enc.shape
-
-        def mask(x):
-            return [bool(x)] * B if isinstance(x, (bool, int)) else [bool(v) for v in x]
-
-        rs, fin = mask(reset), mask(final)
-        if len(rs) != B or len(fin) != B:
-            raise RuntimeError(f"DeviceDecoder.prefix_beam_chunk: reset / final masks must have one entry per stream ({B})")
-        flags = (ctypes.c_int32 * B)(*[int(r) | (int(f) << 1) for r, f in zip(rs, fin)])
-        lens = chunk_lens.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
-        if lens.numel() != B:
-            raise RuntimeError(f"DeviceDecoder.prefix_beam_chunk: chunk_lens has {lens.numel()} elements for {B} streams")
-        cap = self.beam_stream[2] + 1
-        beam_size = int(beam_size)
-        hyps = torch.empty(B, beam_size, cap, dtype=torch.int32, device=self.device)
-        tm = torch.empty(B, beam_size, cap, dtype=torch.int32, device=self.device)
-        hl = torch.empty(B, beam_size, dtype=torch.int32, device=self.device)
-        sc = torch.empty(B, beam_size, dtype=torch.float64, device=self.device)
-        vs = torch.empty(B, beam_size, dtype=torch.float64, device=self.device)
-        nh = torch.empty(B, dtype=torch.int32, device=self.device)
-        dur = (None, 0) if durations is None else (_durations_arg(durations), len(durations))
-        self._call("wr_prefix_beam_search_chunk", enc, lens, ctc, B, T, beam_size, float(ctc_weight),
-                   float(transducer_weight), int(blank), *dur, flags, hyps, tm, hl, sc, vs, nh)
-        hl, sc, vs, nh = hl.cpu().tolist(), sc.cpu().tolist(), vs.cpu().tolist(), nh.cpu().tolist()
-        width = max(max(row) for row in hl)
-        hyps, tm = hyps[:, :, :width].cpu().tolist(), tm[:, :, :width].cpu().tolist()
-        return [[(hyps[b][e][:hl[b][e]], sc[b][e], vs[b][e], tm[b][e][1:hl[b][e]]) for e in range(nh[b])] for b in range(B)]
-
-    def attach_beam_context_stream(self, n_streams: int, beam: int, max_frames: int) -> None:
-        """`attach_beam_stream` for the biased streams of `prefix_beam_context_chunk`
-        (`wr_decoder_attach_beam_context_stream`).  Attaching one form replaces the other and ends every stream."""
-        n_streams, beam, max_frames = int(n_streams), int(beam), int(max_frames)
-        nbytes = self._lib.wr_decoder_beam_context_stream_workspace_bytes(self._h, n_streams, beam, max_frames)
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.wr_decoder_attach_beam_context_stream(self._h, n_streams, beam, max_frames, _lib.ptr(ws), nbytes)
-        _lib.check(rc, "wr_decoder_attach_beam_context_stream")
-        self._beam_stream_ws = ws
-        self.beam_stream = None
-        self.beam_context_stream = (n_streams, beam, max_frames)
-
-    beam_context_stream = None
+        return self._beam_chunk("prefix_beam_chunk", "wr_prefix_beam_search_chunk", self.beam_stream, encoder_chunk,
+                                chunk_lens, beam_size, blank, ctc_logp, ctc_weight, transducer_weight, durations, reset, final)
 
     def prefix_beam_context_chunk(self, encoder_chunk: torch.Tensor, chunk_lens: torch.Tensor, beam_size: int, blank: int,
                                   graph, ctc_logp: torch.Tensor = None, ctc_weight: float = 0.0,
@@ -340,37 +357,9 @@ class DeviceDecoder:
         if self.beam_context_stream is None:
             raise RuntimeError("DeviceDecoder.prefix_beam_context_chunk: call attach_beam_context_stream(n_streams, beam, "
                                "max_frames) first")
-        enc = _f32(encoder_chunk)
-        ctc = None if ctc_logp is None else _f32(ctc_logp)
-        B, T, _ = enc.shape
-
-        def mask(x):
-            return [bool(x)] * B if isinstance(x, (bool, int)) else [bool(v) for v in x]
-
-        rs, fin, fz = mask(reset), mask(final), mask(finalize)
-        if len(rs) != B or len(fin) != B or len(fz) != B:
-            raise RuntimeError("DeviceDecoder.prefix_beam_context_chunk: reset / final / finalize masks must have one entry "
-                               f"per stream ({B})")
-        flags = (ctypes.c_int32 * B)(*[int(r) | (int(f) << 1) | (int(z) << 2) for r, f, z in zip(rs, fin, fz)])
-        lens = chunk_lens.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
-        if lens.numel() != B:
-            raise RuntimeError(f"DeviceDecoder.prefix_beam_context_chunk: chunk_lens has {lens.numel()} elements for {B} streams")
-        cap = self.beam_context_stream[2] + 1
-        beam_size = int(beam_size)
-        i32, f64 = dict(dtype=torch.int32, device=self.device), dict(dtype=torch.float64, device=self.device)
-        hyps, tm, tg = (torch.empty(B, beam_size, cap, **i32) for _ in range(3))
-        hl, cs, nh = torch.empty(B, beam_size, **i32), torch.empty(B, beam_size, **i32), torch.empty(B, **i32)
-        sc, vs, ts, cx = (torch.empty(B, beam_size, **f64) for _ in range(4))
-        dur = (None, 0) if durations is None else (_durations_arg(durations), len(durations))
-        self._call("wr_prefix_beam_search_context_chunk", enc, lens, ctc, B, T, beam_size, float(ctc_weight),
-                   float(transducer_weight), int(blank), *dur, flags, hyps, tm, hl, sc, vs, nh, *graph.to(self.device),
-                   graph.n_states, graph.n_arcs, ts, cx, tg, cs)
-        hl, nh, cs = hl.cpu().tolist(), nh.cpu().tolist(), cs.cpu().tolist()
-        sc, vs, ts, cx = (t.cpu().tolist() for t in (sc, vs, ts, cx))
-        width = max(max(row) for row in hl)
-        hyps, tm, tg = (t[:, :, :width].cpu().tolist() for t in (hyps, tm, tg))
-        return [[(hyps[b][e][:hl[b][e]], sc[b][e], vs[b][e], tm[b][e][1:hl[b][e]], ts[b][e], cx[b][e], tg[b][e][1:hl[b][e]],
-                  cs[b][e]) for e in range(nh[b])] for b in range(B)]
+        return self._beam_chunk("prefix_beam_context_chunk", "wr_prefix_beam_search_context_chunk", self.beam_context_stream,
+                                encoder_chunk, chunk_lens, beam_size, blank, ctc_logp, ctc_weight, transducer_weight, durations,
+                                reset, final, finalize, graph)
 
     def predictor_step(self, tokens: torch.Tensor, cache_h: torch.Tensor, cache_c: torch.Tensor):
         """tokens (N,), cache (L, N, H) -> out (N, P), new_h, new_c (L, N, H)."""

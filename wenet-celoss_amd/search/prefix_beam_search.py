@@ -221,17 +221,8 @@ class TransducerContextPrefixBeamStream(TransducerPrefixBeamStream):
     def outputs(result, start_tag_id: int, end_tag_id: int):
         """UpdateOutputs on one stream's result: per hypothesis the tokens after the seed blank with `start_tag_id` in front
         of every token that starts a phrase and `end_tag_id` behind every token that ends one."""
-        outs = []
-        for hyp in result:
-            o = []
-            for tok, tag in zip(hyp[0][1:], hyp[6]):
-                if tag & 1:
-                    o.append(start_tag_id)
-                o.append(tok)
-                if tag & 2:
-                    o.append(end_tag_id)
-            outs.append(o)
-        return outs
+        from ..context_graph import mark_phrases
+        return [mark_phrases(hyp[0][1:], hyp[6], start_tag_id, end_tag_id) for hyp in result]
 
 
 class PrefixBeamSearch:

@@ -577,17 +577,25 @@ class Transducer(nn.Module):
                                                        num_decoding_left_chunks=num_decoding_left_chunks)
         return self.encoder(speech, speech_lengths, decoding_chunk_size, num_decoding_left_chunks)
 
+    def _encoded(self, speech, speech_lengths, *chunking):
+        """What every decode mode starts with: the shape asserts and the encoder -> (encoder_out, encoder_out_lens)."""
+        assert speech.shape[0] == speech_lengths.shape[0]
+        assert chunking[0] != 0                                           # decoding_chunk_size
+        encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, *chunking)
+        return encoder_out, encoder_mask.squeeze(1).sum(1)
+
+    def _ctc_logits(self, speech, speech_lengths, *chunking):
+        """`_encoded` and the CTC projection -> (ctc_lo output, encoder_out, encoder_out_lens)."""
+        encoder_out, encoder_out_lens = self._encoded(speech, speech_lengths, *chunking)
+        with torch.no_grad():
+            return self.ctc.ctc_lo(encoder_out), encoder_out, encoder_out_lens
+
     def ctc_greedy_search(self, speech: torch.Tensor, speech_lengths: torch.Tensor, decoding_chunk_size: int = -1,
                           num_decoding_left_chunks: int = -1, simulate_streaming: bool = False):
         """asr_model.py:281-324 -> (hyps, scores)."""
         from .ctc import ctc_greedy_search
-        assert speech.shape[0] == speech_lengths.shape[0]
-        assert decoding_chunk_size != 0
-        encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
-                                                          num_decoding_left_chunks, simulate_streaming)
-        encoder_out_lens = encoder_mask.squeeze(1).sum(1)
-        with torch.no_grad():
-            logits = self.ctc.ctc_lo(encoder_out)
+        logits, _, encoder_out_lens = self._ctc_logits(speech, speech_lengths, decoding_chunk_size,
+                                                       num_decoding_left_chunks, simulate_streaming)
         return ctc_greedy_search(logits, encoder_out_lens, blank=0, eos=self.eos)
 
     def _ctc_prefix_beam_search(self, speech: torch.Tensor, speech_lengths: torch.Tensor, beam_size: int,
@@ -595,13 +603,9 @@ class Transducer(nn.Module):
                                 simulate_streaming: bool = False):
         """asr_model.py:326-409 -> (hyps [(prefix, score)], encoder_out)."""
         from .ctc import ctc_prefix_beam_search
-        assert speech.shape[0] == speech_lengths.shape[0]
-        assert decoding_chunk_size != 0
         assert speech.shape[0] == 1
-        encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
-                                                          num_decoding_left_chunks, simulate_streaming)
-        with torch.no_grad():
-            logits = self.ctc.ctc_lo(encoder_out)
+        logits, encoder_out, _ = self._ctc_logits(speech, speech_lengths, decoding_chunk_size, num_decoding_left_chunks,
+                                                  simulate_streaming)
         lens = torch.tensor([encoder_out.size(1)], dtype=torch.int32)
         return ctc_prefix_beam_search(logits, lens, beam_size)[0], encoder_out
 
@@ -620,13 +624,8 @@ class Transducer(nn.Module):
         (the runtime's viterbi_likelihood() / Times(), ctc_prefix_beam_search.cc:107-211), for any batch size:
         per utterance [(prefix, score, viterbi_score, times)] best first."""
         from .ctc import ctc_prefix_beam_search_times
-        assert speech.shape[0] == speech_lengths.shape[0]
-        assert decoding_chunk_size != 0
-        encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
-                                                          num_decoding_left_chunks, simulate_streaming)
-        encoder_out_lens = encoder_mask.squeeze(1).sum(1)
-        with torch.no_grad():
-            logits = self.ctc.ctc_lo(encoder_out)
+        logits, _, encoder_out_lens = self._ctc_logits(speech, speech_lengths, decoding_chunk_size,
+                                                       num_decoding_left_chunks, simulate_streaming)
         return ctc_prefix_beam_search_times(logits, encoder_out_lens, beam_size)
 
     def ctc_context_prefix_beam_search(self, speech: torch.Tensor, speech_lengths: torch.Tensor, beam_size: int,
@@ -636,13 +635,8 @@ class Transducer(nn.Module):
         --context_score), finalised: per utterance [(prefix, score, viterbi_score, times, ctc_score, context_score,
         tags)] best first, score = ctc_score + context_score."""
         from .ctc import ctc_context_prefix_beam_search
-        assert speech.shape[0] == speech_lengths.shape[0]
-        assert decoding_chunk_size != 0
-        encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
-                                                          num_decoding_left_chunks, simulate_streaming)
-        encoder_out_lens = encoder_mask.squeeze(1).sum(1)
-        with torch.no_grad():
-            logits = self.ctc.ctc_lo(encoder_out)
+        logits, _, encoder_out_lens = self._ctc_logits(speech, speech_lengths, decoding_chunk_size,
+                                                       num_decoding_left_chunks, simulate_streaming)
         return ctc_context_prefix_beam_search(logits, encoder_out_lens, beam_size, context_graph)
 
     # ------------------------------------------- ASRModel surface the reference class inherits (asr_model.py) --
@@ -957,13 +951,11 @@ class Transducer(nn.Module):
         size, with the Viterbi score and the encoder frame of every token: per utterance [(tokens without the seed blank,
         score, viterbi_score, times)] best first.  One reset-and-final chunk of the streaming search."""
         from .search.prefix_beam_search import TransducerPrefixBeamStream
-        assert speech.shape[0] == speech_lengths.shape[0]
-        assert decoding_chunk_size != 0
-        encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
-                                                          num_decoding_left_chunks, simulate_streaming)
+        encoder_out, lens = self._encoded(speech, speech_lengths, decoding_chunk_size, num_decoding_left_chunks,
+                                          simulate_streaming)
         B, T, _ = encoder_out.shape
         stream = TransducerPrefixBeamStream(self, B, beam_size, T, T, ctc_weight, transducer_weight)
-        nbest = stream.search(encoder_out, encoder_mask.squeeze(1).sum(1), final=True)
+        nbest = stream.search(encoder_out, lens, final=True)
         return [[(h[1:], s, v, t) for h, s, v, t in utt] for utt in nbest]
 
     # ---- the same with context-graph phrase biasing (the context_graph_ member rnnt_prefix_beam_search.h drafts) --
@@ -993,13 +985,11 @@ class Transducer(nn.Module):
         [(tokens without the seed blank, score, viterbi_score, times, trans_score, context_score, tags, context_state)]
         best first.  One reset, final and finalised chunk of the biased streaming search."""
         from .search.prefix_beam_search import TransducerContextPrefixBeamStream
-        assert speech.shape[0] == speech_lengths.shape[0]
-        assert decoding_chunk_size != 0
-        encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
-                                                          num_decoding_left_chunks, simulate_streaming)
+        encoder_out, lens = self._encoded(speech, speech_lengths, decoding_chunk_size, num_decoding_left_chunks,
+                                          simulate_streaming)
         B, T, _ = encoder_out.shape
         stream = TransducerContextPrefixBeamStream(self, B, beam_size, T, T, context_graph, ctc_weight, transducer_weight)
-        nbest = stream.search(encoder_out, encoder_mask.squeeze(1).sum(1), final=True, finalize=True)
+        nbest = stream.search(encoder_out, lens, final=True, finalize=True)
         return [[(r[0][1:],) + tuple(r[1:]) for r in utt] for utt in nbest]
 
     # ------------------- streaming CTC prefix beam search (runtime/core/decoder/ctc_prefix_beam_search.cc:107-211) --
