@@ -59,7 +59,7 @@ const char *wr_last_error(void);
 
 /* Benchmarking hook: process-wide launch-shape knobs of the streaming kernels.  Results never depend
  * on them; the defaults are the measured best.  key 0: workgroups per CU of the RNN-T row-lse pass,
- * key 1: of the RNN-T gradient pass (0, the default: automatic -- one row per wave in the row-lse pass, about 68 KB of
+ * key 1: of the RNN-T gradient pass (0, the default: automatic -- one row per wave in the row-lse pass, about 104 KB of
  * logits per wave in the gradient pass; n > 0: a persistent grid of n workgroups per CU as in round 1), key 2: non-temporal bits (1: gradient-pass loads, 2: gradient-pass
  * stores, 4: row-lse loads; default 7), key 3 / key 4: 16-byte vectors in flight per lane in the gradient (4, 8 or 16;
  * default 16) / row-lse pass (4, 8 or 16; default 16),
@@ -77,7 +77,11 @@ const char *wr_last_error(void);
  * projection in the rounding of one composed weight matrix (formed in float64).  key 14: dead-cell skip of the RNN-T
  * gradient pass (1, the default: a cell whose every exponential is provably +0 -- its log-occupancy and the bounds of
  * its blank and label terms below -110 nats, a finite row log-sum-exp -- is written as grad_costs[b] * 0 without
- * reading its logits; 0: every valid cell reads its logits) -- bit-identical results either way. */
+ * reading its logits; 0: every valid cell reads its logits) -- bit-identical results either way.  key 15 / key 16: which
+ * rows a workgroup of the RNN-T row-lse / gradient pass visits (2, the default: XCD runs -- of every 8c consecutive
+ * 4-row blocks, the workgroups that land on XCD x take the c blocks from x*c on, so each XCD streams contiguous rows;
+ * 0 or any other value: block i is workgroup i, the order before), key 17: that c (0, the default: 8 * U1max) --
+ * bit-identical results either way; measurements in profiles/xcd_row_order.md. */
 int wr_tune_set(int key, int value);
 
 /* ------------------------------------------------------------------------

@@ -46,7 +46,8 @@ __global__ __launch_bounds__(256) void rnnt_lse_kernel(
     const T *__restrict__ logits, const int32_t *__restrict__ targets,
     const int32_t *__restrict__ llens, const int32_t *__restrict__ tlens,
     int B, int Tmax, int U1max, int V, int blank, int K, int S,
-    float2 *__restrict__ lp_skew, float *__restrict__ denom, const int32_t *__restrict__ run_if)
+    float2 *__restrict__ lp_skew, float *__restrict__ denom, const int32_t *__restrict__ run_if,
+    int order, int order_run /* logical_block's mode and c */)
 {
     if (run_if != nullptr && *run_if == 0) return;     // repair pass behind the joiner's fused epilogue: usually nothing to do
     const int lane = threadIdx.x & (kWave - 1);
@@ -55,7 +56,8 @@ __global__ __launch_bounds__(256) void rnnt_lse_kernel(
     const long nrows = (long)B * Tmax * U1max;
     const long stride = (long)gridDim.x * waves_per_block;
     const int cells = Tmax * U1max;
-    for (long r = (long)blockIdx.x * waves_per_block + wid; r < nrows; r += stride) {
+    const long first = (long)logical_block(blockIdx.x, gridDim.x, order, (unsigned)order_run);
+    for (long r = first * waves_per_block + wid; r < nrows; r += stride) {
         const int b = (int)(r / cells);
         const int c = (int)(r - (long)b * cells);
         const int t = c / U1max;
@@ -268,7 +270,8 @@ __global__ __launch_bounds__(256) void rnnt_grad_kernel(
     int B, int Tmax, int U1max, int V, int blank, float clamp, int K, int S,
     const double *__restrict__ alpha_skew, const double *__restrict__ beta_skew,
     const float *__restrict__ denom, const double *__restrict__ cost_ws,
-    const float *__restrict__ grad_costs, T *grads, int skip_dead, Reg... reg_args)
+    const float *__restrict__ grad_costs, T *grads, int skip_dead, int order, int order_run /* logical_block's mode and c */,
+    Reg... reg_args)
 {
     constexpr bool REG = sizeof...(Reg) != 0;
     typedef typename VecOf<T>::type vec_t;
@@ -279,7 +282,8 @@ __global__ __launch_bounds__(256) void rnnt_grad_kernel(
     const long nrows = (long)B * Tmax * U1max;
     const long stride = (long)gridDim.x * waves_per_block;
     const int cells = Tmax * U1max;
-    for (long r = (long)blockIdx.x * waves_per_block + wid; r < nrows; r += stride) {
+    const long first = (long)logical_block(blockIdx.x, gridDim.x, order, (unsigned)order_run);
+    for (long r = first * waves_per_block + wid; r < nrows; r += stride) {
         const int b = (int)(r / cells);
         const int c = (int)(r - (long)b * cells);
         const int t = c / U1max;
@@ -492,7 +496,7 @@ int check_shape(int B, int Tmax, int U1max, int V, int blank)
 }
 
 constexpr size_t kLseBytesPerWave = 16 * 1024;     // one row of 5 000 fp32 logits
-constexpr size_t kGradBytesPerWave = 68 * 1024;    // 3.4 such rows on average
+constexpr size_t kGradBytesPerWave = 104 * 1024;   // 5.2 such rows on average
 
 }  // namespace
 
@@ -505,6 +509,21 @@ constexpr size_t kGradBytesPerWave = 68 * 1024;    // 3.4 such rows on average
 //     read + write gradient pass: 34.49 ms at 16 per CU -> 33.65 (128) -> 33.35 (512) -> 33.18 (1 024) -> 32.96 ms at
 //                                 1 400 per CU (3.4 rows per wave); one or two rows per wave lose again (2 048 per CU =
 //                                 2.3 rows per wave: +2 %).
+// Workgroup order (logical_block, wr_common.hpp; profiles/xcd_row_order.md has every row of what was measured, B = 32 at
+// the BASELINE shape, sustained fwd + bwd, tools/tune_rnnt.py SWEEP=order / order2, two boxes, spread within a box
+// under 0.05 ms).  Consecutive workgroups run on consecutive XCDs; with XCD runs of c blocks (mode 2) the rows one XCD
+// streams are contiguous:
+//     read-only row pass:         identity 14.98 / 15.01 ms -> runs of c = 302: 13.86 / 13.84, 604: 13.79, 1 208 and
+//                                 longer: 13.76 ms; eight contiguous regions (the removed mode 1): 14.66 ms.
+//     read + write gradient pass: identity 25.24 / 25.66 ms at 1 355 per CU (68 KB per wave) -> runs: 25.30 on the second
+//                                 box; the run length (64 ... 1 208) moves it by less than the spread.  Runs gain
+//                                 0.35 - 0.41 ms at every grid measured (512 ... 1 355 per CU), and with them fewer
+//                                 rows in flight win: 24.78 (512) / 24.82 (768, 896) / 25.13 (1 024) / 25.39 ms (1 200)
+//                                 on one box, 24.64 (1 024) against 25.30 (1 355) on the other.  104 KB per wave is
+//                                 886 per CU.  Mode 1 reached 24.58 / 24.74 ms, but only with exactly one row per wave
+//                                 (27.8 ms at 2 048 per CU, 33.4 ms at 4 096) and is not kept.
+//     PMC bytes of the gradient pass: 60.86 GB read -> 60.11 (c = 302) / 60.04 (604); written 99.00 -> 99.04 GB.
+// Defaults: mode 2 for both passes (keys 15 and 16), c = 8 * U1max (order_run below).
 // `knob` > 0 forces that many workgroups per CU (the round-1 meaning of tuning keys 0 and 1); 0 = automatic: every wave
 // gets about `bytes_per_wave` of logits.
 int stream_grid(long nrows, int knob, size_t row_bytes, size_t bytes_per_wave)
@@ -522,6 +541,18 @@ int stream_grid(long nrows, int knob, size_t row_bytes, size_t bytes_per_wave)
     }
     if (blocks < 1) blocks = 1;
     return (int)blocks;
+}
+
+// logical_block's run length c for mode 2.  The 64-byte sector of alpha_skew / beta_skew that holds cell (t, u) also
+// holds (t-1, u+1) ... (t-7, u+7), rows U1max apart, so a run has to cover several frames of 4-row workgroups before
+// the gradient pass can share a sector inside one L2; that pass is flat from 2 to 8 frames' worth and the row pass
+// still gains up to c = 8 * U1max (1 208 at the BASELINE shape: 32 frames, 97 MB of logits per run).  Key 17 > 0
+// overrides it.
+static int order_run(int U1max)
+{
+    const int forced = tune_get(kTuneOrderRun);
+    const int c = forced > 0 ? forced : 8 * U1max;
+    return c < (1 << 24) ? c : (1 << 24);
 }
 
 int rnnt_launch_sweep(const RnntWs &w, char *ws, const int32_t *llens, const int32_t *tlens, int B, int Tmax,
@@ -550,7 +581,7 @@ int rnnt_launch_lse(const RnntWs &w, char *ws, const void *logits_d, int dtype, 
                               dim3(256), 0, st, static_cast<const T *>(logits_d), targets_d, logit_lengths_d,
                               target_lengths_d, B, Tmax, U1max, V, blank, w.K, w.S,
                               reinterpret_cast<float2 *>(ws + w.lp_off), reinterpret_cast<float *>(ws + w.denom_off),
-                              nullptr);
+                              nullptr, tune_get(kTuneLseOrder), order_run(U1max));
             });
         });
     });
@@ -610,7 +641,7 @@ int rnnt_loss_fwd_from_lse_body(const char *what, const float *logits_d, const i
                   dim3(stream_grid(nrows, tune_get(kTuneLseBlocksPerCu), (size_t)V * 4, kLseBytesPerWave)), dim3(256), 0, st,
                   logits_d, targets_d, logit_lengths_d, target_lengths_d, B, Tmax, U1max, V, blank, w.K, w.S,
                   reinterpret_cast<float2 *>(ws + w.lp_off), reinterpret_cast<float *>(ws + w.denom_off),
-                  reinterpret_cast<const int32_t *>(ws + w.flag_off)));
+                  reinterpret_cast<const int32_t *>(ws + w.flag_off), tune_get(kTuneLseOrder), order_run(U1max)));
     if (delay_penalty > 0.0)
         return wr_rnnt_lattice_sweeps(logit_lengths_d, target_lengths_d, B, Tmax, U1max, WR_LATTICE_REGULAR, delay_penalty,
                                       costs_d, workspace_d, workspace_bytes, stream);
@@ -693,7 +724,7 @@ int rnnt_loss_bwd_body(const char *what, const void *logits_d, int dtype, const 
                                   reinterpret_cast<const double *>(ws + w.beta_off),
                                   reinterpret_cast<const float *>(ws + w.denom_off),
                                   reinterpret_cast<const double *>(ws + w.cost_off), grad_costs_d,
-                                  static_cast<T *>(grads_d), skip);
+                                  static_cast<T *>(grads_d), skip, tune_get(kTuneGradOrder), order_run(U1max));
                 });
             });
         });
@@ -745,7 +776,7 @@ int wr::rnnt_launch_grad_reg(const RnntWs &w, const char *ws, const void *logits
                                   reinterpret_cast<const double *>(ws + w.beta_off),
                                   reinterpret_cast<const float *>(ws + w.denom_off),
                                   reinterpret_cast<const double *>(ws + w.cost_off), grad_costs_d, static_cast<T *>(grads_d),
-                                  skip, ra);
+                                  skip, tune_get(kTuneGradOrder), order_run(U1max), ra);
                 });
             });
         });

@@ -56,8 +56,26 @@ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 // ---- process-wide tuning knobs (wr_tune_set; defaults are the measured best) ----
-enum TuneKey { kTuneLseBlocksPerCu = 0, kTuneGradBlocksPerCu = 1, kTuneNonTemporal = 2, kTuneGradUnroll = 3, kTuneLseUnroll = 4, kTuneJointFwdVariant = 5, kTuneLaneGemmTile = 6, kTuneSplitParts = 7, kTuneDzTile = 8, kTuneDwExact = 9, kTuneDzExact = 10, kTuneFoldProj = 11, kTuneSplitFwdCells = 12, kTuneSplitFwdStore = 13, kTuneGradSkip = 14, kTuneCount = 15 };
+enum TuneKey { kTuneLseBlocksPerCu = 0, kTuneGradBlocksPerCu = 1, kTuneNonTemporal = 2, kTuneGradUnroll = 3, kTuneLseUnroll = 4, kTuneJointFwdVariant = 5, kTuneLaneGemmTile = 6, kTuneSplitParts = 7, kTuneDzTile = 8, kTuneDwExact = 9, kTuneDzExact = 10, kTuneFoldProj = 11, kTuneSplitFwdCells = 12, kTuneSplitFwdStore = 13, kTuneGradSkip = 14, kTuneLseOrder = 15, kTuneGradOrder = 16, kTuneOrderRun = 17, kTuneCount = 18 };
 int tune_get(int key);
+
+// ---- workgroup order of the RNN-T streaming passes (keys 15 - 17; measurements: profiles/xcd_row_order.md) ----
+// Workgroup i of a grid of G runs on XCD i & 7 (round-robin dispatch), each XCD with an L2 of its own; a streaming
+// kernel works on the rows of logical block logical_block(i, G, mode, c) instead of block i.  A bijection on [0, G)
+// for every G, mode and c:
+//   mode 2  XCD runs of c: inside every aligned group of 8c blocks XCD x takes the c consecutive blocks from x*c on,
+//           in order, so the grid still advances as one window of 8c blocks; the G % 8c blocks at the end keep the
+//           identity.
+//   any other mode (0: the order every pass had before): the identity, neighbouring blocks on neighbouring XCDs.
+// (Mode 1 was "XCD x takes one contiguous eighth of the grid": eight windows at a time; measured, not kept.)
+__host__ __device__ inline unsigned logical_block(unsigned i, unsigned G, int mode, unsigned c)
+{
+    if (mode == 2 && c > 0) {
+        const unsigned span = 8u * c;
+        if (i < G / span * span) return i / span * span + (i & 7u) * c + (i >> 3) % c;
+    }
+    return i;
+}
 
 // joint_split.hip: exact-fp32 activation gradient, 256 x 256 block tiling
 int joint_bwd_dz_block(const float *gout_d, const float *ep_d, const float *pp_d, const float *w_d, const int32_t *llens_d,
