@@ -80,6 +80,24 @@ def test_parity_ragged(B, T, U, V):
     check(*make_case(rng, B, T, U, V))
 
 
+def test_frameless_utterance_beside_live_ones_over_two_waves():
+    """T_b = 0 between two live utterances at U1 = 65: its two workgroups leave through the sweep's early exit while the
+    others run the two-wave barrier path.  The live ones against the float64 oracle (which has no T = 0 case of its own);
+    the frameless one costs 0 and has no gradient."""
+    rng = np.random.default_rng(65)
+    B, T, U, V = 3, 9, 64, 17
+    logits, targets, _, _ = make_case(rng, B, T, U, V)
+    llens, tlens = np.array([T, 0, 5], np.int32), np.array([U, 7, U], np.int32)
+    costs, grad = run_hip(logits, targets, llens, tlens)
+    live = [0, 2]
+    oc, og = oracle.rnnt_loss_f64(logits[live], targets[live], llens[live], tlens[live])
+    np.testing.assert_allclose(costs[live], oc, rtol=1e-5, atol=1e-5)
+    np.testing.assert_allclose(grad[live], og, rtol=1e-4, atol=1e-5)
+    assert costs[1] == 0 and not grad[1].any()
+    for b in live:                                        # padding is exactly zero
+        assert not grad[b, llens[b]:].any() and not grad[b, :, tlens[b] + 1:].any()
+
+
 def test_parity_full_lengths_and_blank_nonzero():
     rng = np.random.default_rng(5)
     logits, targets, llens, tlens = make_case(rng, 3, 25, 11, 48, full=True)

@@ -168,6 +168,18 @@ def test_modified_lattice_ragged_batch_over_several_waves():
     check_lattice(lm, am, symbols, t_lens, u_lens, 0.01)
 
 
+def test_modified_frameless_utterance_beside_live_ones_over_two_waves():
+    """T_b = 0 between two live utterances at U1 = 65: its two workgroups leave through the sweep's early exit while the
+    others run the two-wave barrier path.  Costs, gradients and occupancies against the float64 reference, which gives
+    the frameless utterance cost 0."""
+    rng = np.random.default_rng(65)
+    B, T, U, V = 3, 9, 64, 17
+    lm, am, symbols, _, _ = make_case(rng, B, T, U, V, "modified")
+    t_lens, u_lens = np.array([T, 0, 5]), np.array([T, 0, 3])
+    costs = check(lm, am, symbols, t_lens, u_lens, 0.0, 0.0, "modified", 0.0)
+    assert costs[1] == 0
+
+
 # -------------------------------------------------------------------------------- 2. simple and smoothed losses --
 @pytest.mark.parametrize("rnnt_type,dp", MODES)
 @pytest.mark.parametrize("ll,la", SCALES)

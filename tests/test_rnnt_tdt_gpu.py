@@ -176,6 +176,23 @@ def test_infeasible_utterance_and_unreachable_cells():
     assert torch.equal(c2, costs[:2]) and torch.equal(g2, grad[:2])
 
 
+def test_frameless_utterance_beside_live_ones_over_two_waves():
+    """T_b = 0 between two live utterances at U1 = 65: its two workgroups leave through the sweep's early exit while the
+    others run the two-wave barrier path.  The reference gives the frameless utterance cost 0 and no gradient."""
+    V, durs = 17, (0, 1, 2)
+    logits, targets = case(V, len(durs), shape=(3, 9, 64), seed=3)
+    llens, tlens = np.array([9, 0, 5], np.int32), np.array([64, 7, 64], np.int32)
+    oc, og, oa, ob = ref.tdt_ref(logits, targets, llens, tlens, durs, 0, 0.05)
+    assert np.isfinite(oc).all() and oc[1] == 0
+    costs, grad = run_hip(logits, targets, durs, llens, tlens, sigma=0.05)
+    compare(costs.numpy(), grad.numpy(), oc, og, 1e-5, 1e-5, 1e-4, 1e-5)
+    assert costs[1] == 0 and not grad[1].any()
+    assert_padding_zero(grad, llens, tlens)
+    _, alpha, beta = run_lattice(logits, targets, durs, llens, tlens, sigma=0.05)
+    np.testing.assert_allclose(alpha, oa, rtol=1e-5, atol=1e-5)
+    np.testing.assert_allclose(beta, ob, rtol=1e-5, atol=1e-5)
+
+
 @pytest.mark.parametrize("shape,durs", [((1, 3, 70), (0, 1, 2)), ((1, 40, 2), (0, 1, 3, 8))])
 def test_sweep_boundaries(shape, durs):
     """U + 1 = 71 columns: two waves in the sweep, so the LDS exchange across waves runs.  T = 40: longer than the prefetch

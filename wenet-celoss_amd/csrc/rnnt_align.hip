@@ -6,10 +6,9 @@
 // Two device passes:
 //   pass 1  rnnt_lse_kernel (rnnt_loss.hip, unchanged) -- or the joiner's statistics epilogue (wr_joint_rnnt_stats) --
 //           writes the {blank, emit} log-probs of every cell into the diagonal-skewed `lp_skew` of the RNN-T workspace.
-//   pass 2  rnnt_viterbi_kernel: the forward branch of rnnt_sweep_kernel with max in place of log-add-exp.  One
-//           workgroup per utterance, one lane per label column u, one step per anti-diagonal s = t + u: the lane's own
-//           previous value (blank predecessor) and its left neighbour's (emit predecessor) by a DPP rotate inside a wave,
-//           by a double-buffered LDS slot and one barrier across waves; PF rows of log-probs in flight; state in fp64.
+//   pass 2  rnnt_viterbi_kernel: the forward branch of rnnt_sweep_kernel with max in place of log-add-exp: the same
+//           rnnt_forward_step of lattice_wavefront.hpp (one workgroup per utterance, one lane per label column u, one
+//           step per anti-diagonal s = t + u; the scheme is described there) with another merge of the two candidates.
 //           Each step's decision bits ("the emit predecessor won") form one 64-bit ballot word per (diagonal, wave),
 //           stored by lane 0 of the wave into the workspace's beta region, which alignment never uses otherwise
 //           (B*S*ceil(U1/64) words against B*S*U1 doubles).  Then the same workgroup walks back from (T-1, U) to (0, 0),
@@ -19,7 +18,7 @@
 // Tie rule (shared with tests/rnnt_align_ref.py): the emit predecessor wins only if its candidate is strictly greater;
 // on equality or when a comparison involves a NaN the blank predecessor wins.  The value is NaN if either candidate is
 // NaN, so a NaN anywhere on the reachable lattice reaches the score, while the decisions still form a monotone path.
-#include "wr_common.hpp"
+#include "lattice_wavefront.hpp"
 #include "wr_launch.hpp"
 
 namespace wr {
@@ -34,16 +33,11 @@ __global__ __launch_bounds__(kRnntMaxCols) void rnnt_viterbi_kernel(
     double *__restrict__ scores)
 {
     constexpr double NEG = (double)kNegInf;
-    __shared__ double xch[2][kRnntMaxCols / kWave];
+    __shared__ SweepSlots<double> xch;
     __shared__ uint64_t stage[kAlignStageWords];
     __shared__ int frames[kRnntMaxCols];
-    const int b = blockIdx.x;
-    const int u = threadIdx.x;
-    const int lane = u & (kWave - 1), wave = u >> 6;
-    const int nw = blockDim.x >> 6;
-    int T = llens[b], U = tlens[b];
-    T = T < 0 ? 0 : (T > Tmax ? Tmax : T);
-    U = U < 0 ? 0 : (U > U1max - 1 ? U1max - 1 : U);
+    const SweepLane L = sweep_lane(llens, tlens, Tmax, U1max);
+    const int b = L.b, u = L.u, nw = L.nw, T = L.T, U = L.U;
     const int nsteps = (T > 0) ? T + U : 0;       // anti-diagonals that hold a valid cell
     int32_t *frames_out = label_frames + (size_t)b * (U1max - 1);
 
@@ -52,9 +46,7 @@ __global__ __launch_bounds__(kRnntMaxCols) void rnnt_viterbi_kernel(
         for (int i = u; i < U1max - 1; i += blockDim.x) frames_out[i] = -1;
         return;
     }
-    const bool in_row = u < U1max;
-    const int col = in_row ? u : U1max - 1;
-    const float2 *__restrict__ lp = lp_skew + (size_t)b * S * U1max + col;
+    const float2 *__restrict__ lp = lp_skew + (size_t)b * S * U1max + L.col;
     uint64_t *dec = decisions + (size_t)b * S * nw;
 
     auto load_row = [&](int s) -> float2 {
@@ -62,42 +54,19 @@ __global__ __launch_bounds__(kRnntMaxCols) void rnnt_viterbi_kernel(
         return lp[(size_t)sc * U1max];
     };
 
-    float2 ring[PF];
-    double st = NEG;      // A(t-1, u): this lane's value on the previous diagonal
-    float skp = 0.f;      // blank(t-1, u)
-    double send = NEG;    // A(t, u) + emit(t, u): what the lane to the right needs on the next diagonal
-    double result = 0.0;
-#pragma unroll
-    for (int i = 0; i < PF; ++i) ring[i] = load_row(i);
-    for (int base = 0; base < nsteps; base += PF) {
-#pragma unroll
-        for (int i = 0; i < PF; ++i) {
-            const int s = base + i;               // steps s >= nsteps have no active lane
-            const float2 cur = ring[i];
-            ring[i] = load_row(s + PF);
-            // A(t, u-1) + emit(t, u-1) from the lane to the left; the origin sees 0, column 0 sees -inf
-            double recv = lane_rotate_up_d(send);
-            if (lane == 0) recv = (wave == 0) ? ((s == 0) ? 0.0 : NEG) : xch[(s + 1) & 1][wave - 1];
-            const int t = s - u;
-            const bool active = (t >= 0) & (t < T) & (u <= U);
-            const float sk = active ? cur.x : 0.f;
-            const float em = active ? cur.y : 0.f;
-            const double top = (t >= 1) ? st + (double)skp : NEG;
+    RnntFwd f;
+    sweep_steps<PF, true>(0, nsteps, load_row, [&](int s, const float2 cur) {         // steps s >= nsteps have no active lane
+        rnnt_forward_step(L, xch, s, cur, f, [&](bool active, int t, double top, double recv) {
             const bool emit = (t == 0) | (recv > top);   // strict: ties and NaN comparisons go to the blank predecessor
             double v = emit ? recv : top;
             v = (recv != recv) ? recv : v;                // a NaN candidate makes the value NaN (top's NaN is kept above)
             v = active ? v : NEG;
             const uint64_t word = __ballot(active & emit);
-            if (lane == 0 && s < nsteps) dec[(size_t)s * nw + wave] = word;
-            result = (active && t == T - 1 && u == U) ? v + (double)sk : result;
-            send = v + (double)em;
-            if (lane == kWave - 1) xch[s & 1][wave] = send;
-            st = v;
-            skp = sk;
-            if (nw > 1) __syncthreads();
-        }
-    }
-    if (u == U) scores[b] = result;               // exactly one lane saw the terminal cell (T-1, U)
+            if (L.lane == 0 && s < nsteps) dec[(size_t)s * nw + L.wave] = word;
+            return v;
+        });
+    });
+    sweep_store_ll(L, scores, f.result);
 
     // The decision words were written by lane 0 of every wave: drain them and drop this CU's cached lines before the
     // workgroup reads them back.

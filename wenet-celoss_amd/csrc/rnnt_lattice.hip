@@ -9,14 +9,14 @@
 //                             [b][t][u] rows.  Regular lattice + penalty: in place, and rnnt_loss.hip's sweeps follow.
 //   lattice_mod_sweep_kernel  one workgroup per (utterance, direction), one lane per label column, T_b dependent steps
 //                             (+ 1 forward, for the terminal node).  Every lane is on the same frame, so a step reads and
-//                             writes one contiguous row.  The exchange is rnnt_sweep_kernel's: the lane's own previous
-//                             value and its neighbour's previous value (+ arc), by DPP rotate inside a wave and a
-//                             double-buffered LDS slot plus one barrier across waves.  fp64 state, PF rows in flight.
+//                             writes one contiguous row.  The exchange, the ring of PF rows in flight and the fp64 state
+//                             are lattice_wavefront.hpp's, as for rnnt_sweep_kernel.
 //   lattice_export_kernel     alpha / beta of either lattice as plain (B, T, U1) floats, for the tests.
 //
 // The token-and-duration transducer (TDT) loss and its forced alignment follow at the end of the file: a lattice of its
 // own, whose cells have 2 * D arcs that jump up to 8 frames (include/wr_api.h, "Token-and-duration transducer";
 // rnnt_tdt.hpp for the arrays).
+#include "lattice_wavefront.hpp"
 #include "rnnt_lattice.hpp"
 #include "rnnt_tdt.hpp"
 #include "row_stream.hpp"
@@ -24,17 +24,6 @@
 
 namespace wr {
 namespace {
-
-__device__ __forceinline__ int clampi(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
-// rnnt_loss.hip's log-add: fp64 state, the bounded log1p(exp(-|a-b|)) term in fp32; -inf safe
-__device__ __forceinline__ double log_add_exp_d(double a, double b)
-{
-    const double m = fmax(a, b);
-    const float d = (float)(-fabs(a - b));          // NaN when both are -inf
-    const float r = kLn2 * fast_log2(1.0f + fast_exp2(d * kLog2e));
-    return (m == (double)kNegInf) ? (double)kNegInf : m + (double)r;
-}
 
 // One thread per position (b, s = t + u, u) of the anti-diagonal array: whole lines of it are read.  MOD: the pair goes
 // to row t of the plain array `lp_plain` (another region of the workspace); otherwise the label term is rewritten in
@@ -69,99 +58,71 @@ __global__ __launch_bounds__(kRnntMaxCols) void lattice_mod_sweep_kernel(
     double *__restrict__ dump /* [2*B*kRnntMaxCols] scratch that absorbs the stores of idle lanes */)
 {
     constexpr double NEG = (double)kNegInf;
-    __shared__ double xch[2][kRnntMaxCols / kWave];
-    const int b = blockIdx.x;
+    __shared__ SweepSlots<double> xch;
+    const SweepLane L = sweep_lane(llens, tlens, Tmax, U1max);
     const bool backward = blockIdx.y != 0;
-    const int u = threadIdx.x;
-    const int lane = u & (kWave - 1), wave = u >> 6;
-    const int nw = blockDim.x >> 6;
-    const int T = clampi(llens[b], 0, Tmax), U = clampi(tlens[b], 0, U1max - 1);
+    const int u = L.u, T = L.T, U = L.U;
 
     if (T == 0) {
-        if (u == 0) {
-            if (backward) { cost_ws[b] = 0.0; costs_out[b] = 0.f; } else ll_out[b] = 0.0;
-        }
+        sweep_store_empty(L, backward, ll_out, cost_ws, costs_out);
         return;
     }
-    const bool in_row = u < U1max;
-    const int col = in_row ? u : U1max - 1;
-    const float2 *__restrict__ lp = lp_plain + (size_t)b * S * U1max + col;
-    double *__restrict__ out = (backward ? beta_plain : alpha_plain) + (size_t)b * S * U1max + col;
-    double *__restrict__ sink = dump + ((size_t)b * 2 + (backward ? 1 : 0)) * kRnntMaxCols + u;
-    const bool ucol = in_row && u <= U;
+    const float2 *__restrict__ lp = lp_plain + (size_t)L.b * S * U1max + L.col;
+    double *__restrict__ out = sweep_out(L, backward, alpha_plain, beta_plain, S, U1max);
+    double *__restrict__ sink = sweep_sink(L, backward, dump);
+    const bool ucol = L.ucol;
 
     auto load_row = [&](int t) -> float2 {
         const int tc = t < 0 ? 0 : (t >= T ? T - 1 : t);
         return lp[(size_t)tc * U1max];
     };
 
-    float2 ring[PF];
     double result = NEG;
 
     if (!backward) {
         double st = NEG;      // alpha(t-1, u)
         float skp = 0.f;      // blank(t-1, u)
         double send = NEG;    // alpha(t-1, u) + emit'(t-1, u): what lane u+1 needs
-#pragma unroll
-        for (int i = 0; i < PF; ++i) ring[i] = load_row(i);
-        for (int base = 0; base <= T; base += PF) {              // frames 0 .. T-1 and the terminal row T
-#pragma unroll
-            for (int i = 0; i < PF; ++i) {
-                const int t = base + i;                          // rows t > T have no active lane
-                const float2 cur = ring[i];
-                ring[i] = load_row(t + PF);
-                double recv = lane_rotate_up_d(send);
-                if (lane == 0)       // row 0 has no left neighbour yet (the LDS slots are still unwritten)
-                    recv = (t == 0) ? ((wave == 0) ? 0.0 : NEG) : ((wave == 0) ? NEG : xch[(t + 1) & 1][wave - 1]);
-                const bool active = (t < T) & ucol;
-                const float sk = active ? cur.x : 0.f;
-                const float em = active ? cur.y : 0.f;
-                const double top = (t >= 1) ? st + (double)skp : NEG;
-                double v = log_add_exp_d(top, recv);             // the origin sees recv = 0, top = -inf  ->  0
-                result = (t == T && u == U) ? v : result;        // the terminal node (T, U)
-                v = active ? v : NEG;
-                double *dst = active ? out + (size_t)t * U1max : sink;
-                *dst = v;
-                send = v + (double)em;
-                if (lane == kWave - 1) xch[t & 1][wave] = send;
-                st = v;
-                skp = sk;
-                if (nw > 1) __syncthreads();
-            }
-        }
-        if (u == U) ll_out[b] = result;
+        // frames 0 .. T-1 and the terminal row T; rows t > T have no active lane
+        sweep_steps<PF, true>(0, T + 1, load_row, [&](int t, const float2 cur) {
+            // every lane is live on row 0, before any slot is written
+            const double recv = sweep_recv<true>(L, xch, send, t, (t == 0) ? 0.0 : NEG, t == 0);
+            const bool active = (t < T) & ucol;
+            const float sk = active ? cur.x : 0.f;
+            const float em = active ? cur.y : 0.f;
+            const double top = (t >= 1) ? st + (double)skp : NEG;
+            double v = log_add_exp_d(top, recv);             // the origin sees recv = 0, top = -inf  ->  0
+            result = (t == T && u == U) ? v : result;        // the terminal node (T, U)
+            v = active ? v : NEG;
+            double *dst = active ? out + (size_t)t * U1max : sink;
+            *dst = v;
+            send = v + (double)em;
+            st = v;
+            skp = sk;
+            sweep_post<true>(L, xch, send, t);
+        });
+        sweep_store_ll(L, ll_out, result);
     } else {
         double st = (u == U) ? 0.0 : NEG;     // beta(t+1, u); row T is the terminal condition
         double send = st;                     // what lane u-1 needs
-        if (lane == 0) xch[T & 1][wave] = send;
-        if (nw > 1) __syncthreads();
-#pragma unroll
-        for (int i = 0; i < PF; ++i) ring[i] = load_row(T - 1 - i);
-        for (int base = 0; base < T; base += PF) {
-#pragma unroll
-            for (int i = 0; i < PF; ++i) {
-                const int t = T - 1 - (base + i);                // rows t < 0 have no active lane
-                const float2 cur = ring[i];
-                ring[i] = load_row(t - PF);
-                double recv = lane_rotate_down_d(send);
-                if (lane == kWave - 1) recv = (wave == nw - 1) ? NEG : xch[(t + 1) & 1][wave + 1];
-                const bool active = (t >= 0) & ucol;
-                const float sk = active ? cur.x : 0.f;
-                const float em = active ? cur.y : 0.f;
-                const double down = st + (double)sk;
-                const double diag = (u < U) ? recv + (double)em : NEG;
-                double v = log_add_exp_d(down, diag);
-                v = active ? v : NEG;
-                double *dst = active ? out + (size_t)t * U1max : sink;
-                *dst = v;
-                result = (t == 0 && u == 0) ? v : result;
-                send = v;
-                if (lane == 0) xch[t & 1][wave] = send;
-                st = v;
-                if (nw > 1) __syncthreads();
-            }
-        }
-        if (u == 0) { cost_ws[b] = -result; costs_out[b] = (float)(-result); }
+        sweep_post<false>(L, xch, send, T);
+        sweep_steps<PF, false>(T - 1, T, load_row, [&](int t, const float2 cur) {    // rows t < 0 have no active lane
+            const double recv = sweep_recv<false>(L, xch, send, t, NEG);     // never unwritten: row T was posted above
+            const bool active = (t >= 0) & ucol;
+            const float sk = active ? cur.x : 0.f;
+            const float em = active ? cur.y : 0.f;
+            const double down = st + (double)sk;
+            const double diag = (u < U) ? recv + (double)em : NEG;
+            double v = log_add_exp_d(down, diag);
+            v = active ? v : NEG;
+            double *dst = active ? out + (size_t)t * U1max : sink;
+            *dst = v;
+            result = (t == 0 && u == 0) ? v : result;
+            send = v;
+            st = v;
+            sweep_post<false>(L, xch, send, t);
+        });
+        sweep_store_cost(L, cost_ws, costs_out, result);
     }
 }
 
@@ -336,6 +297,23 @@ struct TdtArc {
     float w[kTdtMaxD];
 };
 
+// the arcs of column `col`'s cell on anti-diagonal s of utterance `ub`, its frame clamped into [0, T): always a position
+// of the arrays
+__device__ __forceinline__ TdtArc tdt_load_arc(const float2 *__restrict__ tok, const float *__restrict__ dur,
+                                               const TdtDur &dd, size_t ub, int col, int T, int U1max, int s)
+{
+    int t = s - col;
+    t = t < 0 ? 0 : (t >= T ? T - 1 : t);
+    const size_t k = ub + (size_t)(t + col) * U1max + col;
+    TdtArc a;
+    const float2 p = tok[k];
+    a.tb = p.x;
+    a.tl = p.y;
+#pragma unroll
+    for (int d = 0; d < kTdtMaxD; ++d) a.w[d] = dd.slot[d] >= 0 ? dur[k * dd.D + dd.slot[d]] : 0.f;
+    return a;
+}
+
 // Forward, lane u on anti-diagonal s at cell (t = s - u, u): own[j] / nbr[j] collect the mass that arcs of finished cells
 // of this column send into (t + j, u) / (t + j, u + 1).  alpha(t,u) = logadd(own[0], what lane u-1 sent a step ago); the
 // cell then pushes its 2 * D arcs into the rings, hands nbr[0] -- complete, every (t' <= t, u) is done -- to lane u + 1, and
@@ -351,131 +329,90 @@ __global__ __launch_bounds__(kRnntMaxCols) void tdt_sweep_kernel(
     float *__restrict__ costs_out, double *__restrict__ dump)
 {
     constexpr double NEG = (double)kNegInf;
-    __shared__ double xch[2][kRnntMaxCols / kWave];
-    const int b = blockIdx.x;
+    __shared__ SweepSlots<double> xch;
+    const SweepLane L = sweep_lane(llens, tlens, Tmax, U1max);
     const bool backward = blockIdx.y != 0;
-    const int u = threadIdx.x;
-    const int lane = u & (kWave - 1), wave = u >> 6;
-    const int nw = blockDim.x >> 6;
-    const int T = clampi(llens[b], 0, Tmax), U = clampi(tlens[b], 0, U1max - 1);
+    const int u = L.u, T = L.T, U = L.U;
 
     if (T == 0) {
-        if (u == 0) {
-            if (backward) { cost_ws[b] = 0.0; costs_out[b] = 0.f; } else ll_out[b] = 0.0;
-        }
+        sweep_store_empty(L, backward, ll_out, cost_ws, costs_out);
         return;
     }
-    const bool in_row = u < U1max;
-    const int col = in_row ? u : U1max - 1;
-    const bool ucol = in_row && u <= U;
-    const size_t ub = (size_t)b * S * U1max;
-    const int D = dd.D;
+    const bool ucol = L.ucol;
+    const size_t ub = (size_t)L.b * S * U1max;
     const int nsteps = T + U;                // anti-diagonals 0 .. T + U - 1 hold this utterance's cells
-    double *__restrict__ out = (backward ? beta_skew : alpha_skew) + ub + col;
-    double *__restrict__ sink = dump + ((size_t)b * 2 + (backward ? 1 : 0)) * kRnntMaxCols + u;
+    double *__restrict__ out = sweep_out(L, backward, alpha_skew, beta_skew, S, U1max);
+    double *__restrict__ sink = sweep_sink(L, backward, dump);
+    auto load_arc = [&](int s) -> TdtArc { return tdt_load_arc(tok, dur, dd, ub, L.col, T, U1max, s); };
 
-    // the arcs of this column's cell on anti-diagonal s, its frame clamped into [0, T): always a position of the arrays
-    auto load_arc = [&](int s) -> TdtArc {
-        int t = s - col;
-        t = t < 0 ? 0 : (t >= T ? T - 1 : t);
-        const size_t k = ub + (size_t)(t + col) * U1max + col;
-        TdtArc a;
-        const float2 p = tok[k];
-        a.tb = p.x;
-        a.tl = p.y;
-#pragma unroll
-        for (int d = 0; d < kTdtMaxD; ++d) a.w[d] = dd.slot[d] >= 0 ? dur[k * D + dd.slot[d]] : 0.f;
-        return a;
-    };
-
-    TdtArc ring[PF];
     double own[kTdtMaxD], nbr[kTdtMaxD];
 #pragma unroll
     for (int j = 0; j < kTdtMaxD; ++j) own[j] = nbr[j] = NEG;
     double send = NEG, result = NEG;
 
     if (!backward) {
+        // the cells' anti-diagonals and the terminal's; steps s > T + U have no active lane
+        sweep_steps<PF, true>(0, nsteps + 1, load_arc, [&](int s, const TdtArc &cur) {
+            const int t = s - u;
+            const double recv = sweep_recv<true>(L, xch, send, s, NEG, s == 0);    // step 0 has nothing to receive
+            const bool active = ucol & (t >= 0) & (t < T);
+            const double own0 = own[0];
+            double v = log_add_exp_d(own0, recv);
+            v = (s == 0 && u == 0) ? 0.0 : v;                 // the origin
+            result = (t == T && u == U) ? own0 : result;      // the terminal: blank arcs that end exactly at T
+            v = active ? v : NEG;
+            double *dst = active ? out + (size_t)s * U1max : sink;
+            *dst = v;
+            const double ab = v + (double)(active ? cur.tb : 0.f);
+            const double al = (u < U) ? v + (double)(active ? cur.tl : 0.f) : NEG;
 #pragma unroll
-        for (int i = 0; i < PF; ++i) ring[i] = load_arc(i);
-        for (int base = 0; base <= nsteps; base += PF) {          // the cells' anti-diagonals and the terminal's
-#pragma unroll
-            for (int i = 0; i < PF; ++i) {
-                const int s = base + i, t = s - u;                // steps s > T + U have no active lane
-                const TdtArc cur = ring[i];
-                ring[i] = load_arc(s + PF);
-                double recv = lane_rotate_up_d(send);
-                if (lane == 0)       // step 0 has nothing to receive (the LDS slots are still unwritten)
-                    recv = (s == 0 || wave == 0) ? NEG : xch[(s + 1) & 1][wave - 1];
-                const bool active = ucol & (t >= 0) & (t < T);
-                const double own0 = own[0];
-                double v = log_add_exp_d(own0, recv);
-                v = (s == 0 && u == 0) ? 0.0 : v;                 // the origin
-                result = (t == T && u == U) ? own0 : result;      // the terminal: blank arcs that end exactly at T
-                v = active ? v : NEG;
-                double *dst = active ? out + (size_t)s * U1max : sink;
-                *dst = v;
-                const double ab = v + (double)(active ? cur.tb : 0.f);
-                const double al = (u < U) ? v + (double)(active ? cur.tl : 0.f) : NEG;
-#pragma unroll
-                for (int d = 0; d < kTdtMaxD; ++d) {
-                    if (dd.slot[d] >= 0) {
-                        const double w = (double)(active ? cur.w[d] : 0.f);
-                        if (d >= 1) own[d] = log_add_exp_d(own[d], ab + w);
-                        nbr[d] = log_add_exp_d(nbr[d], al + w);
-                    }
+            for (int d = 0; d < kTdtMaxD; ++d) {
+                if (dd.slot[d] >= 0) {
+                    const double w = (double)(active ? cur.w[d] : 0.f);
+                    if (d >= 1) own[d] = log_add_exp_d(own[d], ab + w);
+                    nbr[d] = log_add_exp_d(nbr[d], al + w);
                 }
-                send = nbr[0];
-#pragma unroll
-                for (int j = 0; j + 1 < kTdtMaxD; ++j) { own[j] = own[j + 1]; nbr[j] = nbr[j + 1]; }
-                own[kTdtMaxD - 1] = nbr[kTdtMaxD - 1] = NEG;
-                if (lane == kWave - 1) xch[s & 1][wave] = send;
-                if (nw > 1) __syncthreads();
             }
-        }
-        if (u == U) ll_out[b] = result;
+            send = nbr[0];
+#pragma unroll
+            for (int j = 0; j + 1 < kTdtMaxD; ++j) { own[j] = own[j + 1]; nbr[j] = nbr[j + 1]; }
+            own[kTdtMaxD - 1] = nbr[kTdtMaxD - 1] = NEG;
+            sweep_post<true>(L, xch, send, s);
+        });
+        sweep_store_ll(L, ll_out, result);
     } else {
         const int s0 = nsteps - 1;                // lane U starts at (T - 1, U), below the terminal
         own[1] = (u == U) ? 0.0 : NEG;            // beta(T, U) = 0
-        if (lane == 0) xch[(s0 + 1) & 1][wave] = NEG;
-        if (nw > 1) __syncthreads();
+        sweep_post<false>(L, xch, NEG, s0 + 1);
+        sweep_steps<PF, false>(s0, nsteps, load_arc, [&](int s, const TdtArc &cur) {     // steps s < 0 have no active lane
+            const int t = s - u;
+            const double recv = sweep_recv<false>(L, xch, send, s, NEG);     // never unwritten: s0 + 1 was posted above
 #pragma unroll
-        for (int i = 0; i < PF; ++i) ring[i] = load_arc(s0 - i);
-        for (int base = 0; base < nsteps; base += PF) {
+            for (int j = kTdtMaxD - 1; j >= 1; --j) nbr[j] = nbr[j - 1];
+            nbr[0] = recv;                                    // beta(t, u + 1)
+            const bool active = ucol & (t >= 0) & (t < T);
+            const float tb = active ? cur.tb : 0.f;
+            const float tl = (active && u < U) ? cur.tl : kNegInf;
+            double acc = NEG;
 #pragma unroll
-            for (int i = 0; i < PF; ++i) {
-                const int s = s0 - (base + i), t = s - u;         // steps s < 0 have no active lane
-                const TdtArc cur = ring[i];
-                ring[i] = load_arc(s - PF);
-                double recv = lane_rotate_down_d(send);
-                if (lane == kWave - 1) recv = (wave == nw - 1) ? NEG : xch[(s + 1) & 1][wave + 1];
-#pragma unroll
-                for (int j = kTdtMaxD - 1; j >= 1; --j) nbr[j] = nbr[j - 1];
-                nbr[0] = recv;                                    // beta(t, u + 1)
-                const bool active = ucol & (t >= 0) & (t < T);
-                const float tb = active ? cur.tb : 0.f;
-                const float tl = (active && u < U) ? cur.tl : kNegInf;
-                double acc = NEG;
-#pragma unroll
-                for (int d = 0; d < kTdtMaxD; ++d) {
-                    if (dd.slot[d] >= 0) {
-                        const float w = active ? cur.w[d] : 0.f;
-                        if (d >= 1) acc = log_add_exp_d(acc, ((double)tb + (double)w) + own[d]);
-                        acc = log_add_exp_d(acc, ((double)tl + (double)w) + nbr[d]);
-                    }
+            for (int d = 0; d < kTdtMaxD; ++d) {
+                if (dd.slot[d] >= 0) {
+                    const float w = active ? cur.w[d] : 0.f;
+                    if (d >= 1) acc = log_add_exp_d(acc, ((double)tb + (double)w) + own[d]);
+                    acc = log_add_exp_d(acc, ((double)tl + (double)w) + nbr[d]);
                 }
-                const double v = active ? acc : NEG;
-                double *dst = active ? out + (size_t)s * U1max : sink;
-                *dst = v;
-                result = (s == 0 && u == 0) ? v : result;
-                send = v;
-#pragma unroll
-                for (int j = kTdtMaxD - 1; j >= 2; --j) own[j] = own[j - 1];
-                own[1] = v;
-                if (lane == 0) xch[s & 1][wave] = send;
-                if (nw > 1) __syncthreads();
             }
-        }
-        if (u == 0) { cost_ws[b] = -result; costs_out[b] = (float)(-result); }
+            const double v = active ? acc : NEG;
+            double *dst = active ? out + (size_t)s * U1max : sink;
+            *dst = v;
+            result = (s == 0 && u == 0) ? v : result;
+            send = v;
+#pragma unroll
+            for (int j = kTdtMaxD - 1; j >= 2; --j) own[j] = own[j - 1];
+            own[1] = v;
+            sweep_post<false>(L, xch, send, s);
+        });
+        sweep_store_cost(L, cost_ws, costs_out, result);
     }
 }
 
@@ -678,108 +615,81 @@ __global__ __launch_bounds__(kRnntMaxCols) void tdt_viterbi_kernel(
     double *__restrict__ scores)
 {
     constexpr double NEG = (double)kNegInf;
-    __shared__ double xch[2][kRnntMaxCols / kWave];
-    __shared__ int xtag[2][kRnntMaxCols / kWave];
+    __shared__ SweepSlots<double> xch;
+    __shared__ SweepSlots<int> xtag;
     __shared__ uint32_t stage[kTdtStageBytes / 4 + 1];
     __shared__ int lfr[kRnntMaxCols], ldu[kRnntMaxCols];
     __shared__ uint8_t jl[kTdtJumpWindow];
     __shared__ int cur[4];      // the backtrace cursor: t, u, state (0 walking, 1 at the origin, 2 no path), terminal's d
-    const int b = blockIdx.x;
-    const int u = threadIdx.x;
-    const int lane = u & (kWave - 1), wave = u >> 6;
-    const int nw = blockDim.x >> 6;
-    const int T = clampi(llens[b], 0, Tmax), U = clampi(tlens[b], 0, U1max - 1);
+    const SweepLane L = sweep_lane(llens, tlens, Tmax, U1max);
+    const int b = L.b, u = L.u, T = L.T, U = L.U;
     int32_t *frames_out = label_frames + (size_t)b * (U1max - 1);
     int32_t *durs_out = label_durations + (size_t)b * (U1max - 1);
     int32_t *jumps_out = blank_jumps ? blank_jumps + (size_t)b * Tmax : nullptr;
 
-    const bool in_row = u < U1max;
-    const int col = in_row ? u : U1max - 1;
-    const bool ucol = in_row && u <= U;
+    const bool ucol = L.ucol;
     const size_t ub = (size_t)b * S * U1max;
-    const int D = dd.D;
     const int nsteps = T + U;                // anti-diagonals 0 .. T + U - 1 hold this utterance's cells
     uint8_t *dec = decisions + ub;
 
-    auto load_arc = [&](int s) -> TdtArc {   // tdt_sweep_kernel's: always a position of the arrays
-        int t = s - col;
-        t = t < 0 ? 0 : (t >= T ? T - 1 : t);
-        const size_t k = ub + (size_t)(t + col) * U1max + col;
-        TdtArc a;
-        const float2 p = tok[k];
-        a.tb = p.x;
-        a.tl = p.y;
-#pragma unroll
-        for (int d = 0; d < kTdtMaxD; ++d) a.w[d] = dd.slot[d] >= 0 ? dur[k * D + dd.slot[d]] : 0.f;
-        return a;
-    };
+    auto load_arc = [&](int s) -> TdtArc { return tdt_load_arc(tok, dur, dd, ub, L.col, T, U1max, s); };
 
     double result = NEG;
     int rdec = 0;
     if (T > 0) {                             // T_b = 0 has no cell to read: no path (the Python layer refuses it)
-        TdtArc ring[PF];
         double own[kTdtMaxD], nbr[kTdtMaxD];
 #pragma unroll
         for (int j = 0; j < kTdtMaxD; ++j) own[j] = nbr[j] = NEG;
         uint64_t otags = 0, ntags = 0;
         double send = NEG;
         int stag = 0;
+        // the cells' anti-diagonals and the terminal's; steps s > T + U have no active lane
+        sweep_steps<PF, true>(0, nsteps + 1, load_arc, [&](int s, const TdtArc &cur_arc) {
+            const int t = s - u;
+            // step 0 has nothing to receive; the candidate's tag travels with it (the same wave rotate)
+            const double recv = sweep_recv<true>(L, xch, send, s, NEG, s == 0);
+            const int rtag = sweep_recv_slot<true, int>(L, xtag, __builtin_amdgcn_update_dpp(0, stag, 0x13C, 0xf, 0xf, false),
+                                                        s, 0, s == 0, 0);
+            const bool active = ucol & (t >= 0) & (t < T);
+            const double own0 = own[0];
+            const int otag0 = (int)(otags & 15);
+            const bool lab = recv > own0;                     // strict: a tie goes to the blank arc
+            double v = lab ? recv : own0;
+            unsigned by = lab ? (kTdtDecLabel | (unsigned)rtag) : (unsigned)otag0;
+            if (s == 0 && u == 0) { v = 0.0; by = 0; }        // the origin
+            if (t == T && u == U) { result = own0; rdec = otag0; }   // the terminal: blank arcs that end exactly at T
+            v = active ? v : NEG;
+            by = (v == NEG) ? kTdtDecNone : by;
+            if (active) dec[(size_t)s * U1max + u] = (uint8_t)by;
+            const double ab = v + (double)(active ? cur_arc.tb : 0.f);
+            const double al = (u < U) ? v + (double)(active ? cur_arc.tl : 0.f) : NEG;
 #pragma unroll
-        for (int i = 0; i < PF; ++i) ring[i] = load_arc(i);
-        for (int base = 0; base <= nsteps; base += PF) {          // the cells' anti-diagonals and the terminal's
-#pragma unroll
-            for (int i = 0; i < PF; ++i) {
-                const int s = base + i, t = s - u;                // steps s > T + U have no active lane
-                const TdtArc cur_arc = ring[i];
-                ring[i] = load_arc(s + PF);
-                double recv = lane_rotate_up_d(send);
-                int rtag = __builtin_amdgcn_update_dpp(0, stag, 0x13C, 0xf, 0xf, false);
-                if (lane == 0) {     // step 0 has nothing to receive (the LDS slots are still unwritten)
-                    const bool none = s == 0 || wave == 0;
-                    recv = none ? NEG : xch[(s + 1) & 1][wave - 1];
-                    rtag = none ? 0 : xtag[(s + 1) & 1][wave - 1];
-                }
-                const bool active = ucol & (t >= 0) & (t < T);
-                const double own0 = own[0];
-                const int otag0 = (int)(otags & 15);
-                const bool lab = recv > own0;                     // strict: a tie goes to the blank arc
-                double v = lab ? recv : own0;
-                unsigned by = lab ? (kTdtDecLabel | (unsigned)rtag) : (unsigned)otag0;
-                if (s == 0 && u == 0) { v = 0.0; by = 0; }        // the origin
-                if (t == T && u == U) { result = own0; rdec = otag0; }   // the terminal: blank arcs that end exactly at T
-                v = active ? v : NEG;
-                by = (v == NEG) ? kTdtDecNone : by;
-                if (active) dec[(size_t)s * U1max + u] = (uint8_t)by;
-                const double ab = v + (double)(active ? cur_arc.tb : 0.f);
-                const double al = (u < U) ? v + (double)(active ? cur_arc.tl : 0.f) : NEG;
-#pragma unroll
-                for (int d = 0; d < kTdtMaxD; ++d) {
-                    if (dd.slot[d] >= 0) {
-                        const double w = (double)(active ? cur_arc.w[d] : 0.f);
-                        const uint64_t clr = ~((uint64_t)15 << (4 * d)), tag = (uint64_t)d << (4 * d);
-                        if (d >= 1) {
-                            const double c = ab + w;
-                            const bool win = c >= own[d];
-                            own[d] = win ? c : own[d];
-                            otags = win ? ((otags & clr) | tag) : otags;
-                        }
-                        const double c = al + w;
-                        const bool win = c >= nbr[d];
-                        nbr[d] = win ? c : nbr[d];
-                        ntags = win ? ((ntags & clr) | tag) : ntags;
+            for (int d = 0; d < kTdtMaxD; ++d) {
+                if (dd.slot[d] >= 0) {
+                    const double w = (double)(active ? cur_arc.w[d] : 0.f);
+                    const uint64_t clr = ~((uint64_t)15 << (4 * d)), tag = (uint64_t)d << (4 * d);
+                    if (d >= 1) {
+                        const double c = ab + w;
+                        const bool win = c >= own[d];
+                        own[d] = win ? c : own[d];
+                        otags = win ? ((otags & clr) | tag) : otags;
                     }
+                    const double c = al + w;
+                    const bool win = c >= nbr[d];
+                    nbr[d] = win ? c : nbr[d];
+                    ntags = win ? ((ntags & clr) | tag) : ntags;
                 }
-                send = nbr[0];
-                stag = (int)(ntags & 15);
-#pragma unroll
-                for (int j = 0; j + 1 < kTdtMaxD; ++j) { own[j] = own[j + 1]; nbr[j] = nbr[j + 1]; }
-                own[kTdtMaxD - 1] = nbr[kTdtMaxD - 1] = NEG;
-                otags >>= 4;
-                ntags >>= 4;
-                if (lane == kWave - 1) { xch[s & 1][wave] = send; xtag[s & 1][wave] = stag; }
-                if (nw > 1) __syncthreads();
             }
-        }
+            send = nbr[0];
+            stag = (int)(ntags & 15);
+#pragma unroll
+            for (int j = 0; j + 1 < kTdtMaxD; ++j) { own[j] = own[j + 1]; nbr[j] = nbr[j + 1]; }
+            own[kTdtMaxD - 1] = nbr[kTdtMaxD - 1] = NEG;
+            otags >>= 4;
+            ntags >>= 4;
+            sweep_put<true>(L, xtag, stag, s);
+            sweep_post<true>(L, xch, send, s);
+        });
     }
     if (u == U) {
         scores[b] = result;

@@ -10,14 +10,8 @@
 //           denom(t,u) and the two log-probs the lattice needs
 //           (skip = blank, emit = label) into a *diagonal-skewed* array.
 //           HBM-bound: 4*V bytes read per cell.
-//   pass 2  rnnt_sweep_kernel  one workgroup per (utterance, direction), one lane per label column
-//           (64 * ceil(U1max/64) threads).  At step s every lane works on the cell (t = s - u, u) of
-//           anti-diagonal s; from diagonal s-1 it needs its own previous value and its neighbour
-//           lane's: inside a wave one DPP wave shift, across a wave boundary an 8-byte LDS slot
-//           (double buffered) and one s_barrier per step.  Because pass 1 stored the log-probs skewed
-//           by the same rule, step s reads one contiguous row; PF rows are kept in flight under counted
-//           waits.  State in fp64, the bounded log1p(exp(-|a-b|)) term in fp32.  Latency-bound
-//           (T + U dependent steps, ~0.26 us each: 0.30 ms at the BASELINE shape).
+//   pass 2  rnnt_sweep_kernel  one workgroup per (utterance, direction), one lane per label column, one anti-diagonal
+//           per dependent step (the wavefront scheme: lattice_wavefront.hpp).  Latency-bound.
 //   pass 3  rnnt_grad_kernel   one wave per cell again: re-reads the V logits,
 //           writes grad = g_b * (exp(logit + alpha + beta + cost - denom) with
 //           the blank / label corrections), zero in the padded region.  A dead
@@ -31,6 +25,7 @@
 // cell, 2 * 4 * V + two sectors read per faint cell (+ 4*V per padded cell).
 // Dead and faint cells are about 38 % of the BASELINE batch (iid N(0,1)
 // logits; 2 % faint); the share depends on the data.
+#include "lattice_wavefront.hpp"
 #include "rnnt_latency.hpp"
 #include "row_stream.hpp"
 #include "wr_common.hpp"
@@ -81,27 +76,8 @@ __global__ __launch_bounds__(256) void rnnt_lse_kernel(
 }
 
 // ------------------------------------------------------------------ pass 2 --
-// One wave per (utterance, direction).  K label columns per lane.
-//
-// Precision: alpha/beta reach magnitudes ~ (T+U)*log(V) (1e4 at the BASELINE
-// shape), where an fp32 ulp is 1e-3.  The lattice state is therefore carried in
-// fp64 (adds, max) while the transcendental part log1p(exp(-|a-b|)) in [0, ln 2]
-// is evaluated in fp32: absolute error ~1e-7 per step instead of ~5e-4.
-__device__ __forceinline__ double log_add_exp_d(double a, double b)
-{
-    const double m = fmax(a, b);
-    const float d = (float)(-fabs(a - b));          // NaN when both are -inf
-    const float r = kLn2 * fast_log2(1.0f + fast_exp2(d * kLog2e));
-    return (m == (double)kNegInf) ? (double)kNegInf : m + (double)r;
-}
-
-// One workgroup per (utterance, direction), one lane per label column u (NW = ceil(U1max/64) waves).
-// At step s every lane works on the cell (t = s - u, u) of anti-diagonal s.  What a cell needs from
-// diagonal s -/+ 1 is the lane's own previous value and its neighbouring lane's previous value: inside a
-// wave that is one DPP wave rotate; across the wave boundary (lane 63 -> lane 0 of the next wave) it goes
-// through an 8-byte LDS slot, double buffered, with one s_barrier per step.  The loop body is
-// straight-line: loads are unconditional (clamped rows, values masked afterwards) and idle lanes store
-// to a sink, so PF rows of log-probs stay in flight under counted s_waitcnt.
+// The wavefront scheme (lanes, neighbour exchange, PF-deep ring, fp64 state and why) is lattice_wavefront.hpp's; the
+// forward step is its rnnt_forward_step, shared with rnnt_viterbi_kernel.  Step s: cell (t = s - u, u) of anti-diagonal s.
 template <int PF>
 __global__ __launch_bounds__(kRnntMaxCols) void rnnt_sweep_kernel(
     const float2 *__restrict__ lp_skew, const int32_t *__restrict__ llens,
@@ -111,71 +87,44 @@ __global__ __launch_bounds__(kRnntMaxCols) void rnnt_sweep_kernel(
     double *__restrict__ dump /* [2*B*kRnntMaxCols] scratch that absorbs the stores of idle lanes */)
 {
     constexpr double NEG = (double)kNegInf;
-    __shared__ double xch[2][kRnntMaxCols / kWave];
-    const int b = blockIdx.x;
+    __shared__ SweepSlots<double> xch;
+    const SweepLane L = sweep_lane(llens, tlens, Tmax, U1max);
     const bool backward = blockIdx.y != 0;
-    const int u = threadIdx.x;
-    const int lane = u & (kWave - 1), wave = u >> 6;
-    const int nw = blockDim.x >> 6;
-    int T = llens[b], U = tlens[b];
-    T = T < 0 ? 0 : (T > Tmax ? Tmax : T);
-    U = U < 0 ? 0 : (U > U1max - 1 ? U1max - 1 : U);
+    const int u = L.u, T = L.T, U = L.U;
     const int nsteps = (T > 0) ? T + U : 0;       // anti-diagonals that hold a valid cell
 
     if (nsteps == 0) {
-        if (u == 0) {
-            if (backward) { cost_ws[b] = 0.0; costs_out[b] = 0.f; } else ll_out[b] = 0.0;
-        }
+        sweep_store_empty(L, backward, ll_out, cost_ws, costs_out);
         return;
     }
-    const bool in_row = u < U1max;
-    const int col = in_row ? u : U1max - 1;
-    const float2 *__restrict__ lp = lp_skew + (size_t)b * S * U1max + col;
-    double *__restrict__ out = (backward ? beta_skew : alpha_skew) + (size_t)b * S * U1max + col;
-    double *__restrict__ sink = dump + ((size_t)b * 2 + (backward ? 1 : 0)) * kRnntMaxCols + u;
+    const float2 *__restrict__ lp = lp_skew + (size_t)L.b * S * U1max + L.col;
+    double *__restrict__ out = sweep_out(L, backward, alpha_skew, beta_skew, S, U1max);
+    double *__restrict__ sink = sweep_sink(L, backward, dump);
 
     auto load_row = [&](int s) -> float2 {
         const int sc = s < 0 ? 0 : (s >= nsteps ? nsteps - 1 : s);
         return lp[(size_t)sc * U1max];
     };
 
-    float2 ring[PF];
-    double st = NEG;      // alpha(t-1, u) / beta(t+1, u): this lane's value on the previous diagonal
-    float skp = 0.f;      // forward only: skip(t-1, u)
-    double send = NEG;    // what the neighbouring lane needs from this lane's previous diagonal
-    double result = 0.0;
-
     if (!backward) {
-#pragma unroll
-        for (int i = 0; i < PF; ++i) ring[i] = load_row(i);
-        for (int base = 0; base < nsteps; base += PF) {
-#pragma unroll
-            for (int i = 0; i < PF; ++i) {
-                const int s = base + i;           // steps s >= nsteps have no active lane
-                const float2 cur = ring[i];
-                ring[i] = load_row(s + PF);
-                // alpha(t, u-1) + emit(t, u-1) from the lane to the left
-                double recv = lane_rotate_up_d(send);
-                if (lane == 0) recv = (wave == 0) ? ((s == 0) ? 0.0 : NEG) : xch[(s + 1) & 1][wave - 1];
-                const int t = s - u;
-                const bool active = (t >= 0) & (t < T) & (u <= U);
-                const float sk = active ? cur.x : 0.f;
-                const float em = active ? cur.y : 0.f;
-                const double top = (t >= 1) ? st + (double)skp : NEG;
+        RnntFwd f;
+        sweep_steps<PF, true>(0, nsteps, load_row, [&](int s, const float2 cur) {     // steps s >= nsteps have no active lane
+            rnnt_forward_step(L, xch, s, cur, f, [&](bool active, int, double top, double recv) {
                 double v = log_add_exp_d(top, recv);     // the origin sees recv = 0, top = -inf  ->  0
                 v = active ? v : NEG;
                 double *dst = active ? out + (size_t)s * U1max : sink;
                 *dst = v;
-                result = (active && t == T - 1 && u == U) ? v + (double)sk : result;
-                send = v + (double)em;
-                if (lane == kWave - 1) xch[s & 1][wave] = send;
-                st = v;
-                skp = sk;
-                if (nw > 1) __syncthreads();
-            }
-        }
-        if (u == U) ll_out[b] = result;          // exactly one lane saw the terminal cell (T-1, U)
+                return v;
+            });
+        });
+        sweep_store_ll(L, ll_out, f.result);
     } else {
+        double st = NEG;      // beta(t+1, u): this lane's value on the previous diagonal
+        double send = NEG;    // beta(t, u): what the lane to the left needs on the next step
+        double result = 0.0;
+        // This branch keeps its own ring loop and its own receive: with sweep_steps or sweep_recv the kernel compiles to
+        // 66 VGPRs (7 waves per SIMD) against 62 (8) as written here (profiles/lattice_wavefront.md).
+        float2 ring[PF];
 #pragma unroll
         for (int i = 0; i < PF; ++i) ring[i] = load_row(nsteps - 1 - i);
         for (int base = 0; base < nsteps; base += PF) {
@@ -184,9 +133,9 @@ __global__ __launch_bounds__(kRnntMaxCols) void rnnt_sweep_kernel(
                 const int s = nsteps - 1 - (base + i);   // steps s < 0 have no active lane
                 const float2 cur = ring[i];
                 ring[i] = load_row(s - PF);
-                // beta(t, u+1) from the lane to the right
+                // beta(t, u+1) from the lane to the right (on the first step the lanes at a wave boundary are idle)
                 double recv = lane_rotate_down_d(send);
-                if (lane == kWave - 1) recv = (wave == nw - 1) ? NEG : xch[(s + 1) & 1][wave + 1];
+                if (L.lane == kWave - 1) recv = (L.wave == L.nw - 1) ? NEG : xch[(s + 1) & 1][L.wave + 1];
                 const int t = s - u;
                 const bool active = (t >= 0) & (t < T) & (u <= U);
                 const float sk = active ? cur.x : 0.f;
@@ -200,12 +149,11 @@ __global__ __launch_bounds__(kRnntMaxCols) void rnnt_sweep_kernel(
                 *dst = v;
                 result = (active && t == 0 && u == 0) ? v : result;
                 send = v;
-                if (lane == 0) xch[s & 1][wave] = send;
                 st = v;
-                if (nw > 1) __syncthreads();
+                sweep_post<false>(L, xch, send, s);
             }
         }
-        if (u == 0) { cost_ws[b] = -result; costs_out[b] = (float)(-result); }
+        sweep_store_cost(L, cost_ws, costs_out, result);
     }
 }
 

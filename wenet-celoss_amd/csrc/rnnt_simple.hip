@@ -70,8 +70,6 @@ inline SimpleWs simple_ws_layout(int B, int T, int U1)
     return w;
 }
 
-__device__ __forceinline__ int clampi(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
 // ------------------------------------------------------------------------------------------------ row maxima --
 // rows [0, B*T) are am's, rows [B*T, B*T + B*U1) are lm's
 __global__ __launch_bounds__(256) void simple_rowmax_kernel(const float *__restrict__ am, const float *__restrict__ lm,

@@ -130,6 +130,7 @@ int stream_grid(long nrows, int knob, size_t row_bytes, size_t bytes_per_wave);
 // ---- device helpers ---------------------------------------------------------
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ float fast_log2(float x) { return __builtin_amdgcn_logf(x); }
+__device__ __forceinline__ int clampi(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 // Rotate a double by one lane: lane l receives lane l-1 (lane 0 receives lane 63).  gfx9 DPP wave_ror:1.
 __device__ __forceinline__ double lane_rotate_up_d(double v)
